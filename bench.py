@@ -27,6 +27,13 @@ Workloads
 processes (python -m torch.distributed.run ... bench.py ...), before anything in this process has imported
 torch or touched a GPU, and relays rank 0's JSON line; under an external torchrun (RANK set) it is a rank.
 It exits non-zero whenever the world size differs from --gpus.
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, ms_per_step, ...); its
+timed loop is the one --full times.  --full adds everything else the line can carry, each at its own cost: the CPU
+baseline, the roofline block, the host-inclusive and package-API rates, the nadir_1e5 side measurement
+(--no-cpu-baseline, --no-host-inclusive, --no-package-api, --no-extra leave single ones out), the re-run determinism
+check and, N > 1, the sampled gather check.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import hashlib
@@ -84,10 +91,18 @@ def parse_args(argv):
     ap.add_argument("--no-host-inclusive", action="store_true")
     ap.add_argument("--no-package-api", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the configs[1] side measurement of the N = 1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well (CPU baseline, roofline, host-inclusive "
+                         "and package-API rates, nadir_1e5 side measurement, re-run determinism, N > 1 gather check)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / sharding / gather rehearsal on the CPU (gloo): no library, no GPU, the forward "
                          "model replaced by a checksum of each ray's geometry; the line says dry_run")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -487,11 +502,16 @@ def main(argv):
             raise SystemExit("a ray overflowed NLOS")
         if not bool(torch.isfinite(d_rad).all()):
             raise SystemExit("non-finite radiance in the benchmark output")
+    if args.dump_outputs and rank == 0:
+        outputs = {"rad": gathered if use_dist else d_rad}
+        if model and not use_dist:      # the rest of what jur_formod_device hands its caller, rays as rows
+            outputs.update(tau=d_tau, tp=d_tp.T, np=d_np)
+        dump_outputs(args.dump_outputs, outputs)
 
     # run-to-run determinism, as the reference's own benchmark harness checks it (formod.c:107-157): run again,
     # count every element that differs from the previous result
     mismatches = 0
-    if model:
+    if model and args.full:
         first_rad, first_tau = d_rad.clone(), d_tau.clone()
         for _ in range(2):
             step()
@@ -517,7 +537,7 @@ def main(argv):
 
     # rank 0: the gathered rows must be what ONE process computes for those global ray indices
     verified = None
-    if rank == 0 and use_dist:
+    if rank == 0 and use_dist and args.full:
         rng = np.random.default_rng(5)
         idx = np.unique(np.concatenate([rng.integers(0, total, 4096), [0, total - 1],
                                         np.cumsum(counts)[:-1], np.cumsum(counts)[:-1] - 1]))
@@ -565,19 +585,21 @@ def main(argv):
                                    "builds its own rows only",
                        "sharding": "one global seeded ray set, contiguous range per rank (shard.ray_range), "
                                    "obs.rad gathered to rank 0 peer-to-root (shard.gather_rows)"},
-            "rerun_mismatches": mismatches,
+            "full": args.full,
             "launcher": {"children": peers},
             "note": "radiance parity is against oracle/ (a CPU restatement of the reference: the reference's own "
                     "emissivity tables and GSL are missing blobs, so only its ray-tracing columns are pinned to "
                     "reference-produced data)",
         }
+        if args.full:
+            out["rerun_mismatches"] = mismatches
         if verified:
             out["gather_check"] = verified
         if os.environ.get("JUR_BENCH_REHEARSAL") == "1" and not dry:
             out["rehearsal"] = "ranks share GPUs, gloo instead of RCCL: exercises the N-rank code path, measures nothing"
         if dry:
             out["dry_run"] = True
-        else:
+        elif args.full:
             sum_np = float(d_np.sum(dtype=torch.int64).item())
             pairs = [(g, d) for (g, d) in case.rows]
             shape = (case.ctl.ng, nd, max(case.ctl.nw, 1), len(pairs), len({g for g, _ in pairs}))
@@ -626,6 +648,26 @@ def plan_memory(lib, model, device, nrays, nd, gathered_rows):
     return dict(pci_bus_id=info["pci_bus_id"], device_total_bytes=info["total"], free_bytes_after_tables=info["free"],
                 table_bytes=model.table_bytes(), own_arrays_bytes=own, workspace_budget_bytes=budget,
                 workspace_budget_lowered=budget < default)
+
+
+DUMP_BYTES = 60_000_000        # --dump-outputs: array data in all, below 64 MB with the .npy headers
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: tensors whose rows are rays -> dirname/<name>.npy, float64.  Where all rows would take more than
+    DUMP_BYTES, every array gets the same sample of rows: sorted, drawn by numpy.random.default_rng(0) from the number
+    of rows alone, so equal arguments give equal files from run to run and from build to build."""
+    import numpy as np
+    import torch
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(8 * (a.numel() // max(n, 1)) for a in arrays.values())
+    k = min(n, DUMP_BYTES // max(row_bytes, 1))
+    idx = None if k == n else torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, k, replace=False)))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if idx is not None:
+            a = a[idx.to(a.device)]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a.to("cpu", torch.float64).numpy()))
 
 
 def side_workload(workload, dev, steps, warmup):

@@ -75,7 +75,7 @@ def _bench(*argv, env=None):
 
 def test_bench_starts_its_own_ranks():
     """What the round-1 bench could not do: `bench.py --gpus 2` without torchrun."""
-    out = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--rays", "2001", "--dry-run")
+    out = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--rays", "2001", "--dry-run", "--full")
     assert out.returncode == 0, out.stdout + out.stderr
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout                               # exactly one JSON line on stdout
@@ -117,7 +117,8 @@ def test_bench_airs_workload_starts_the_wide_build_and_shards_by_index():
     with the ND = 2378 dimensions exported (the ranks import 2378-channel structs), every rank builds only its own rows
     of the index-addressable observation set, rank 0 re-builds the sampled rows from their indices and finds them
     equal to what was gathered."""
-    out = _bench("--gpus", "2", "--workload", "airs_2378_sharded", "--steps", "1", "--warmup", "0", "--rays", "301", "--dry-run")
+    out = _bench("--gpus", "2", "--workload", "airs_2378_sharded", "--steps", "1", "--warmup", "0", "--rays", "301", "--dry-run",
+                 "--full")
     assert out.returncode == 0, out.stdout + out.stderr
     doc = json.loads(out.stdout.strip())
     assert doc["n_gpus"] == 2 and doc["dry_run"] is True and doc["scaling"] == "weak"
@@ -137,7 +138,7 @@ def test_bench_eight_ranks_ragged_dry_run():
     tile the set, the gather verified on sampled rows (shard boundaries included), the backend recorded per rank."""
     for workload, rays, nd in (("limb_1e7_sharded", 100_003, 4), ("airs_2378_sharded", 1_003, 2378)):
         out = _bench("--gpus", "8", "--workload", workload, "--steps", "1", "--warmup", "1", "--rays", str(rays), "--dry-run",
-                     env=dict(OMP_NUM_THREADS="1"))
+                     "--full", env=dict(OMP_NUM_THREADS="1"))
         assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
         doc = json.loads(out.stdout.strip())
         assert doc["n_gpus"] == 8 and doc["dry_run"] is True and doc["config"]["channels"] == nd

@@ -28,6 +28,7 @@ on) share that arithmetic and are held to each other BIT FOR BIT in tests/test_p
 chunking / permutation invariance tests here.
 """
 import ctypes as C
+import json
 import os
 import subprocess
 import sys
@@ -879,6 +880,28 @@ def test_large_batch_properties(hip, oracle):
     assert worst < RTOL
     assert np.all(np.abs(a["tau"][idx] - ref["tau"]) <= RTOL * np.abs(ref["tau"]) + common.tau_atol(ref["tau"]))
     model.close()
+
+
+def test_bench_dump_outputs_are_the_timed_path_results(hip, oracle, tmp_path):
+    """A plain `bench.py --dump-outputs DIR` run: what its last timed step computed -- the batched kernels on the headline
+    workload's rays, tables and profiles at 20 000 rays -- as the caller receives it, sampled against the oracle."""
+    import bench
+    nr = 20_000
+    out = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--rays", str(nr), "--steps", "2",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    doc = json.loads(out.stdout)
+    assert doc["steps"] == 2 and doc["full"] is False and doc["config"]["rays_total"] == nr and doc["ms_per_step"] > 0
+    a = {k: np.load(tmp_path / (k + ".npy")) for k in ("rad", "tau", "tp", "np")}
+    assert [a[k].shape for k in ("rad", "tau", "tp", "np")] == [(nr, 4), (nr, 4), (nr, 3), (nr,)]
+    assert all(v.dtype == np.float64 for v in a.values())
+    idx = np.sort(np.random.default_rng(3).choice(nr, 400, replace=False))
+    case = bench.build_case("limb_1e6", bench.workload_rays("limb_1e6", idx))
+    ref = oracle.formod_rays(case.ctl, case.atm, case.oracle_tables(oracle), case.geom)
+    assert np.array_equal(a["np"][idx], ref["np"])
+    assert common.rel_err(a["rad"][idx], ref["rad"]).max() < RTOL
+    assert np.all(np.abs(a["tau"][idx] - ref["tau"]) <= RTOL * np.abs(ref["tau"]) + common.tau_atol(ref["tau"]))
+    assert np.abs(a["tp"][idx] - ref["tp"]).max() < 1e-9
 
 
 def test_nadir_1e5_properties(hip, oracle):

@@ -14,13 +14,14 @@
 
 (2) jurassic-gpu_amd/data/ctm.bin (continuum coefficients, reference src/ctm*.tbl, read at jr_common.h:317,
     335, 366, 380) and clim.bin (src/climatology.tbl) are numeric data packed once by tools/extract_*.py: their
-    sha256 is pinned here, and where the reference tree is present (the build container) they are re-derived
-    from it and compared byte for byte.
+    sha256 is pinned here, and they are re-derived from the numbers of those files (tests/golden/reference_data)
+    and compared byte for byte.
 """
 import ctypes as C
 import hashlib
 import os
 import shutil
+import struct
 import subprocess
 import sys
 import numpy as np
@@ -151,18 +152,36 @@ def test_packed_data_blobs_are_the_pinned_ones():
     assert os.path.getsize(os.path.join(data, "clim.bin")) == 30 * (8 + 8 * 121)
 
 
-def test_packed_data_blobs_rederive_from_the_reference_tree(tmp_path):
-    """Where the reference tree is at hand, pack its ctm*.tbl / climatology.tbl again and compare byte for byte."""
-    ref_src = "/root/reference/src"
-    if not os.path.exists(os.path.join(ref_src, "ctmco2.tbl")):
-        pytest.skip("the reference tree is not on this machine (it never travels to the GPU box); the sha256 pins hold")
+def _reference_arrays(stem):
+    """{name: values} of tests/golden/reference_data/<stem>.txt: the numbers of the reference's src/<stem>.tbl as
+    written there, each array as a line `[name] count` and then its values."""
+    arrays, counts = {}, {}
+    for line in open(os.path.join(common.GOLD, "reference_data", stem + ".txt")):
+        if line.startswith("#"):
+            continue
+        if line.startswith("["):
+            name, n = line[1:].split("]")
+            arrays[name], counts[name] = [], int(n)
+        else:
+            arrays[name] += [float(v) for v in line.split()]
+    assert {k: len(v) for k, v in arrays.items()} == counts, stem
+    return arrays
+
+
+def test_packed_data_blobs_rederive_from_the_reference_tree():
+    """Pack the numbers of the reference's ctm*.tbl / climatology.tbl (tests/golden/reference_data) again, in the
+    order tools/extract_ctm.py and tools/extract_clim.py write them, and compare with the blobs byte for byte."""
     data = os.path.join(common.ROOT, "jurassic-gpu_amd", "data")
-    for tool, blob in (("extract_ctm.py", "ctm.bin"), ("extract_clim.py", "clim.bin")):
-        out = tmp_path / blob
-        subprocess.run([sys.executable, os.path.join(common.ROOT, "tools", tool), ref_src, str(out)], check=True,
-                       capture_output=True)
-        assert open(out, "rb").read() == open(os.path.join(data, blob), "rb").read(), blob
+    co2, h2o, n2, o2 = (_reference_arrays(f) for f in ("ctmco2", "ctmh2o", "ctmn2", "ctmo2"))
+    seq = [co2["co2296"], co2["co2260"], co2["co2230"], h2o["h2o296"], h2o["h2o260"], h2o["h2ofrn"],
+           n2["ba"], n2["betaa"], o2["ba"], o2["betaa"]]
+    assert [len(v) for v in seq] == [2001] * 6 + [98, 98, 90, 90]
+    ctm_blob = b"".join(struct.pack("<%dd" % len(v), *v) for v in seq)
+    assert ctm_blob == open(os.path.join(data, "ctm.bin"), "rb").read(), "ctm.bin"
+    clim = _reference_arrays("climatology")
+    assert list(clim)[:3] == ["z", "pre", "tem"] and all(len(v) == 121 for v in clim.values())
+    clim_blob = b"".join(k.lower().encode().ljust(8, b"\0") + struct.pack("<121d", *v) for k, v in clim.items())
+    assert clim_blob == open(os.path.join(data, "clim.bin"), "rb").read(), "clim.bin"
     # spot values against the text of the reference's initialisers (first CO2 296 K coefficient, last O2 beta)
     ctm = np.fromfile(os.path.join(data, "ctm.bin"), dtype="<f8")
-    first = float(open(os.path.join(ref_src, "ctmco2.tbl")).read().split("{", 1)[1].split(",", 1)[0])
-    assert ctm[0] == first
+    assert ctm[0] == 9.3388e-5 and ctm[-1] == 504.0

@@ -20,9 +20,9 @@ step() { # name, seconds, command...
 for w in $WHAT; do
   case $w in
     tests) step gpu_tests 1100 python3 -m pytest tests -q -m gpu -p no:cacheprovider ;;
-    bench) TAIL=1 step bench 600 python3 bench.py --steps 5 ;;
-    airs) TAIL=1 step bench_airs 900 python3 bench.py --workload airs_2378_sharded --steps 3 --warmup 1 --no-cpu-baseline --no-host-inclusive --no-package-api ;;
-    nadir) TAIL=1 step bench_nadir 300 python3 bench.py --workload nadir_1e5 --steps 20 --no-cpu-baseline ;;
+    bench) TAIL=1 step bench 600 python3 bench.py --full --steps 5 ;;
+    airs) TAIL=1 step bench_airs 900 python3 bench.py --full --workload airs_2378_sharded --steps 3 --warmup 1 --no-cpu-baseline --no-host-inclusive --no-package-api ;;
+    nadir) TAIL=1 step bench_nadir 300 python3 bench.py --full --workload nadir_1e5 --steps 20 --no-cpu-baseline ;;
     small) TAIL=1 step small 300 python3 tools/bench_small.py ;;
     lanes) TAIL=5 step lanes 300 bash tools/run_lanes_bench.sh ;;
     micro) step microbench_build 120 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -Wno-unused-result -o /tmp/microbench_valu tools/microbench_valu.hip
@@ -36,7 +36,7 @@ for w in $WHAT; do
     lanesmode) for md in "JUR_NO_ZERO_COPY=1" "GPU_MAX_HW_QUEUES=8" "JUR_PENCIL_RAYS=0"; do
              TAIL=6 EXTRA_ENV="env $md" CALLS=16 step lanesmode_${md%%=*} 300 bash tools/run_lanes_bench.sh
            done ;;
-    torchrun1) TAIL=1 step bench_torchrun1 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 3 --no-cpu-baseline --no-host-inclusive --no-package-api ;;
+    torchrun1) TAIL=1 step bench_torchrun1 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 3 --no-cpu-baseline --no-host-inclusive --no-package-api ;;
     wide) TAIL=1 JUR_ND=2378 JUR_NG=3 JUR_SUFFIX=_nd2378 step wide 900 python3 tools/bench_wide.py 4096 ;;
     widestats) cd /tmp; export TMPDIR=/tmp
            JUR_ND=2378 JUR_NG=3 JUR_SUFFIX=_nd2378 step wide_stats 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUTDIR/${TAG}_wide_stats -- python3 $GRAFT_REPO_ROOT/tools/bench_wide.py 4096
@@ -55,7 +55,7 @@ for w in $WHAT; do
     kat) step kat 600 python3 -m pytest tests/test_kat_gpu.py -q -p no:cacheprovider ;;
     ab) TAIL=20 step ab 900 bash tools/ab_env.sh $AB ;;
     fuzz) TAIL=3 step fuzz 1100 python3 tools/fuzz_parity.py ${FUZZ:-3000 400} ;;
-    rehearse2) TAIL=1 JUR_BENCH_REHEARSAL=1 step rehearse2 900 python3 bench.py --gpus 2 --rays 600000 --steps 2 --warmup 1 ;;
+    rehearse2) TAIL=1 JUR_BENCH_REHEARSAL=1 step rehearse2 900 python3 bench.py --full --gpus 2 --rays 600000 --steps 2 --warmup 1 ;;
     abso) TAIL=20 step abso 900 bash tools/ab_env.sh "JURASSIC_HIP_SO=$GRAFT_REPO_ROOT/jurassic-gpu_amd/libjurassic_hip.so" "JURASSIC_HIP_SO=$GRAFT_REPO_ROOT/jurassic-gpu_amd/libjurassic_hip$ABSUF.so"
           TAIL=2 step abso_cmp 600 python3 tools/compare_builds.py jurassic-gpu_amd/libjurassic_hip.so jurassic-gpu_amd/libjurassic_hip$ABSUF.so 300000 ;;
     abv) TAIL=30 step abv 1100 bash tools/ab_so.sh $ABV ;;
