@@ -29,6 +29,10 @@ extern "C" {
 void formod(ctl_t const *ctl, atm_t *atm, obs_t *obs);
 void formod_GPU(ctl_t const *ctl, atm_t *atm, obs_t *obs);
 void formod_pencil(ctl_t const *ctl, atm_t *atm, obs_t *obs, int const ir);
+/* formod() plus the contribution of every emitter (the reference's `formod ... TASK contrib`) in one call: obs as
+ * formod() leaves it; contrib[0 .. ng] (caller's array of ng + 1 obs_t) receive obs's geometry and tangent points and
+ * the spectra of jur_formod_contrib_host's variants (contrib[g]: emitter g alone, contrib[ng]: the extinction alone) */
+void formod_contrib(ctl_t const *ctl, atm_t *atm, obs_t *obs, obs_t *contrib);
 /* field-of-view convolution of the radiances / transmittances in obs (jurassic.h:521, jurassic.c:214-258);
  * no-op when ctl->fov is "-"; host code */
 void formod_fov(ctl_t const *ctl, obs_t *obs);
@@ -138,6 +142,20 @@ void  jur_host_free(void *p);
 int  jur_formod_device(jur_model_t *m, long nr, double const *d_geom,
                        double *d_rad, double *d_tau, double *d_tp, int *d_np,
                        int *d_status, void *stream);
+
+/* Contributions of the emitters: the call of jur_formod_host / jur_formod_device (rad, tau, tp, np the same doubles)
+ * and, from its one ray trace and one table look-up, ng + 1 further spectra rad_c / tau_c [ng + 1][nr][nd] in the
+ * caller's ray order:
+ *   variant g < ng  the forward model on the atmosphere with q of every other gas and k of every window set to 0;
+ *   variant ng      ... with every q set to 0 (the extinction alone).
+ * The control block applies as it is (continua, write_bbt, hydz, refraction); every variant carries the NaN mask of
+ * the input rad.  With ctl->hydz >= 0 and H2O the hydrostatic step's emitter (CTM_H2O on), zeroing q_H2O changes the
+ * pressure profile: the variants other than H2O's are then traced on their own edited atmospheres (stacked as profile
+ * slices, one further batched call) and the device entry waits for its stream before it returns. */
+int  jur_formod_contrib_host(jur_model_t *m, long nr, double const *const geom[7], double *rad, double *tau,
+                             double *const tp[3], int *np_out, double *rad_c, double *tau_c);
+int  jur_formod_contrib_device(jur_model_t *m, long nr, double const *d_geom, double *d_rad, double *d_tau,
+                               double *d_tp, int *d_np, int *d_status, double *d_rad_c, double *d_tau_c, void *stream);
 
 /* ---- several GPUs in one process ------------------------------------------------------------------------------
  * The reference's device loop lives inside formod_GPU (GPUdrivers.cu:344-358: one OpenMP thread per device, every
@@ -291,6 +309,8 @@ int  jur_model_enable_timing(jur_model_t *m, int on);
 int  jur_model_last_kernel_ms(jur_model_t *m, double out_ms[3], long out_launches[3]);
 /* ... and of the fused kernel (call jur_model_last_kernel_ms first) */
 int  jur_model_last_pencil_ms(jur_model_t *m, double *out_ms, long *out_launches);
+/* ... and of the contribution kernel (jur_contrib_kernel; call jur_model_last_kernel_ms first) */
+int  jur_model_last_contrib_ms(jur_model_t *m, double *out_ms, long *out_launches);
 
 /* ---- known-answer hooks (for tests; not on the product path) -------------------------------------------
  * The device functions of the path evaluated on host arrays of n inputs, one element per lane, so that each can be

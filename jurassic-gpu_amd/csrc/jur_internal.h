@@ -126,6 +126,9 @@ int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream);   /* 
 int jurk_launch_trace(jur_view_t const *v, jur_chunk_t const *c, void *stream);
 int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, void *stream);
 int jurk_launch_combine(jur_view_t const *v, jur_chunk_t const *c, void *stream);
+/* contributions of the emitters from the transmittance plane of the chunk (after jurk_launch_ega, before the plane is
+ * reused; reads c->rad as the NaN mask, so before jurk_launch_combine): rad_c / tau_c [ng + 1][nr][nd] by ray id */
+int jurk_launch_contrib(jur_view_t const *v, jur_chunk_t const *c, long nr, double *rad_c, double *tau_c, void *stream);
 int jurk_tile_max(int n, int const *d_np, int *d_tile_np, void *stream);
 /* dense difference quotients kq[nq][n] from rad[(n + 1) * nq] (nq = rays x channels of the unperturbed block) and steps h[n] */
 int jurk_launch_kquot(long nq, long n, double const *d_rad, double const *d_h, double *d_kq, void *stream);   /* longest path per tile of 64 slots */

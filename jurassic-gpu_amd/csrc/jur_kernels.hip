@@ -1863,6 +1863,75 @@ __global__ __launch_bounds__(512, JUR_COMBINE_WAVES) void jur_combine_group_kern
   c.tau[oidx] = tau;
 }
 
+// jur_contrib_kernel: the contribution of every emitter (formod TASK contrib) from the transmittance plane the look-up
+// kernel has just written -- one lane per (ray, channel, variant), the lane program of jur_combine_kernel with:
+//   variant g < ng   only gas g's path transmittance, no extinction, the CO2 / H2O continuum only if g is that emitter,
+//                    N2 / O2 as switched: the forward model on the atmosphere with every other q and every k set to 0;
+//   variant ng       no gas (tau_gas = 1), the extinction and the N2 / O2 continua: every q set to 0.
+// A gas's path transmittance depends on its own column only (ega_eps, jr_common.h:237-268) and the line of sight on p and
+// T only, so one trace and one look-up serve all ng + 2 spectra.  Outputs rad_c / tau_c [ng + 1][nr][nd] by ray id.
+// Grid: xcd_block_item over (ray block) x (channel, variant), the ng + 1 variants of a channel adjacent: they share the
+// source-function table and read the ray block's LOS rows from one L2; each plane entry is read once, non-temporally.
+// (8 waves per SIMD: within 64 VGPRs, no scratch -- tests/test_contrib_cpu.py)
+__global__ __launch_bounds__(256, 8) void jur_contrib_kernel(jur_view_t v, jur_chunk_t c, int nrb, long nr, double *__restrict__ rad_c,
+                                                             double *__restrict__ tau_c) {
+  int const nd = v.nd, ng = v.ng, nvar = ng + 1;
+  BlockItem const bi = xcd_block_item((int)blockIdx.x, nrb, nd * nvar);
+  int const rb = bi.rb;
+  if (rb < 0) return;
+  int const d = bi.item / nvar, g = bi.item - d * nvar;          // channel, variant (g == ng: extinction): uniform
+  int const r = rb * blockDim.x + threadIdx.x;
+  double *const sr = reinterpret_cast<double *>(jur_lds);
+  Exp2Lds const e2t{sr + TBLNS};
+  {
+    double const *const gsr = v.sr + (size_t)d * TBLNS;
+    for (int i = threadIdx.x; i < TBLNS; i += blockDim.x) sr[i] = gsr[i];
+    if (threadIdx.x < 64) sr[TBLNS + threadIdx.x] = JUR_EXP2_64[threadIdx.x];
+    __syncthreads();
+  }
+  if (r >= c.n) return;
+  long const ray = c.order ? (long)c.order[r] : c.first + r;
+  int const nfield = JUR_F_K + v.nw + ng;
+  int const tile = __builtin_amdgcn_readfirstlane(r >> 6);
+  unsigned const lane = (unsigned)(r & 63);
+  size_t const R = (size_t)nfield * 64, Re = (size_t)nd * ng * 64;
+  double const *const los = c.los + (size_t)tile * los_tile_doubles(nfield);
+  jur_chan_t const ch = v.chan[d];
+  bool const ext = g == ng;
+  bool const has = !ext && v.pair[g * nd + d].a >= 2;           // the plane holds this gas's transmittance (else it is 1)
+  double const *const epsb = c.eps + eps_tile_point0(c, tile) * Re + ((size_t)d * ng + (ext ? 0 : g)) * 64;
+  int const f_k = JUR_F_K + ch.window, f_g = JUR_F_K + v.nw + (ext ? 0 : g);
+  bool const do_co2 = !ext && g == v.ig_co2 && (v.fourbit & 8) && ch.co2_on,
+             do_h2o = !ext && g == v.ig_h2o && (v.fourbit & 4) && ch.h2o_on,
+             do_n2 = (v.fourbit & 2) && ch.n2_on, do_o2 = (v.fourbit & 1) && ch.o2_on;
+  bool const masked = !isfinite(c.rad[(size_t)ray * nd + d]);   // the input radiances: combine has not run yet
+  double rad = 0.0, tau = 1.0, pprev = 1.0;
+  int const np = c.np[r];
+  for (int ip = 0; ip < np; ++ip) {
+    double const *const row = los + (size_t)ip * R;
+    double const p = ldg<double>(row + JUR_F_P * 64, lane), t = ldg<double>(row + JUR_F_T * 64, lane),
+                 ds = ldg<double>(row + JUR_F_DS * 64, lane);
+    double const k = ext ? ldg<double>(row + (size_t)f_k * 64, lane) : 0.;
+    double const ug = (do_co2 || do_h2o) ? ldg<double>(row + (size_t)f_g * 64, lane) : 0.;
+    double const qh = do_h2o ? ldg<double>(row + JUR_F_QH2O * 64, lane) : 0.;
+    double const pcur = has ? ld_stream(epsb + (size_t)ip * Re, lane) : 1.0;
+    double beta_ds = k * ds;                                     // (0 for a gas: the extinction is set to 0 there)
+    if (do_co2) beta_ds += ctm_co2(ch, p, t, ug);
+    double const rt = rcp_t(t);
+    if (do_h2o) beta_ds += ctm_h2o(e2t, ch, p, t, rt, qh, ug);
+    if (do_n2) beta_ds += ctm_n2(e2t, ch, p, t, rt) * ds;
+    if (do_o2) beta_ds += ctm_o2(e2t, ch, p, t, rt) * ds;
+    double const tau_gas = ext ? 1.0 : segment_tau_gas(pcur, pprev);
+    pprev = pcur;
+    new_obs_step(e2t, tau_gas, beta_ds, planck_src(sr, t), rad, tau);
+  }
+  ray_epilogue(sr, ch.nu, c.tsurf[r], v.write_bbt, rad, tau);
+  if (masked) rad = __builtin_nan("");
+  size_t const o = ((size_t)g * (size_t)nr + (size_t)ray) * nd + d;
+  rad_c[o] = rad;
+  tau_c[o] = tau;
+}
+
 // ---------------------------------------------------------------------------------------
 // jur_pencil_kernel: the whole path of a ray pencil inside ONE workgroup -- for calls of the size the
 // reference's callers make (packages of <= NR = 1088 rays, formod.c:100, kernel() jurassic.c:844), which cannot
@@ -2628,6 +2697,18 @@ extern "C" int jurk_launch_combine(jur_view_t const *v, jur_chunk_t const *c, vo
   }
   hipLaunchKernelGGL(jur_combine_kernel, dim3(grid), dim3(block), sizeof(double) * (JUR_TBLNS + 64), (hipStream_t)stream, *v, *c,
                      nrb);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_launch_contrib(jur_view_t const *v, jur_chunk_t const *c, long nr, double *rad_c, double *tau_c, void *stream) {
+  if (c->n <= 0) return 0;
+  int const block = 256;
+  int const nrb = (c->n + block - 1) / block;
+  long const nitem = (long)v->nd * (v->ng + 1);
+  if (((long)(nrb >> 3) + 1) * 8 * nitem * block >= (1L << 32)) return (int)hipErrorInvalidValue;   // (xcd_grid <= that)
+  unsigned const grid = xcd_grid(nrb, (int)nitem);
+  hipLaunchKernelGGL(jur_contrib_kernel, dim3(grid), dim3(block), sizeof(double) * (JUR_TBLNS + 64), (hipStream_t)stream, *v, *c,
+                     nrb, nr, rad_c, tau_c);
   return (int)hipGetLastError();
 }
 

@@ -96,10 +96,14 @@ struct jur_model {
   /* timing */
   int timing;
   hipEvent_t *evpool;           /* 2 events per timed launch                     */
-  unsigned char *evkind;        /* 0 trace, 1 ega, 2 combine, 3 fused (pencil)   */
+  unsigned char *evkind;        /* 0 trace, 1 ega, 2 combine, 3 fused (pencil), 4 contributions */
   int ntimed;
   double pencil_ms;
   long pencil_launches;
+  double contrib_ms;            /* jur_contrib_kernel's share (kind 4), collected with the others */
+  long contrib_launches;
+  double *d_ctb;                /* jur_formod_contrib_host: grow-only device scratch rad_c | tau_c */
+  long ctb_cap;
 };
 
 #define JUR_MAX_TIMED 4096
@@ -351,7 +355,7 @@ void jur_model_destroy(jur_model_t *m) {
   (void)hipSetDevice(m->device);
   if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_sl = m->d_items = m->d_rec = NULL;
   void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_sl, m->d_items, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp,
-                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_kq};
+                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_kq, m->d_ctb};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
   if (m->h_io) (void)hipHostFree(m->h_io);
@@ -687,7 +691,8 @@ int jur_model_last_kernel_ms(jur_model_t *m, double out_ms[3], long out_launches
     HIPCHK(hipEventSynchronize(m->evpool[2 * i + 1]));
     HIPCHK(hipEventElapsedTime(&ms, m->evpool[2 * i], m->evpool[2 * i + 1]));
     if (m->evkind[i] < 3) { out_ms[m->evkind[i]] += ms; out_launches[m->evkind[i]]++; }
-    else { m->pencil_ms += ms; m->pencil_launches++; }
+    else if (m->evkind[i] == 3) { m->pencil_ms += ms; m->pencil_launches++; }
+    else { m->contrib_ms += ms; m->contrib_launches++; }
   }
   m->ntimed = 0;
   return JUR_OK;
@@ -700,6 +705,15 @@ int jur_model_last_pencil_ms(jur_model_t *m, double *out_ms, long *out_launches)
   *out_launches = m->pencil_launches;
   m->pencil_ms = 0;
   m->pencil_launches = 0;
+  return JUR_OK;
+}
+
+/* ... and of the contribution kernel (same protocol) */
+int jur_model_last_contrib_ms(jur_model_t *m, double *out_ms, long *out_launches) {
+  *out_ms = m->contrib_ms;
+  *out_launches = m->contrib_launches;
+  m->contrib_ms = 0;
+  m->contrib_launches = 0;
   return JUR_OK;
 }
 
@@ -768,15 +782,28 @@ int jur_formod_device(jur_model_t *m, long nr, double const *d_geom, double *d_r
   return jur_formod_device_ld(m, nr, d_geom, nr, d_rad, d_tau, d_tp, nr, d_np, d_status, stream);
 }
 
+/* where the contribution kernel writes (jur_formod_contrib_device): [ng + 1][nr][nd] each */
+typedef struct { double *rad, *tau; } contrib_out_t;
+static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, long ldg, double *d_rad, double *d_tau, double *d_tp,
+                              long ldtp, int *d_np, int *d_status, void *stream, contrib_out_t const *co);
+
 int jur_formod_device_ld(jur_model_t *m, long nr, double const *d_geom, long ldg, double *d_rad, double *d_tau, double *d_tp,
                          long ldtp, int *d_np, int *d_status, void *stream) {
+  return formod_device_body(m, nr, d_geom, ldg, d_rad, d_tau, d_tp, ldtp, d_np, d_status, stream, NULL);
+}
+
+/* The batched path; with `co` the contribution kernel runs after every look-up launch, on the plane it has just
+ * written and before the radiance update overwrites the input radiances (the NaN mask).  Contributions never take the
+ * fused kernel: it keeps no plane. */
+static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, long ldg, double *d_rad, double *d_tau, double *d_tp,
+                              long ldtp, int *d_np, int *d_status, void *stream, contrib_out_t const *co) {
   if (!m || nr < 0) { jur_set_error("formod_device: bad arguments"); return JUR_EINVAL; }
   if (nr == 0) return JUR_OK;
   if (nr > 0x7fffffffL) { jur_set_error("formod_device: at most 2^31-1 rays per call"); return JUR_EINVAL; }
   if (m->view.atm_np < 2) { jur_set_error("formod_device: no atmosphere set"); return JUR_EINVAL; }
   HIPCHK(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
-  int const rb = pencil_rays_per_group(m, nr);
+  int const rb = co ? 0 : pencil_rays_per_group(m, nr);
   if (rb > 0) {
     /* a package-sized call: the whole path in one launch, a workgroup per rb rays, LOS state in LDS */
     jur_chunk_t c;
@@ -894,6 +921,7 @@ int jur_formod_device_ld(jur_model_t *m, long nr, double const *d_geom, long ldg
         c.los = m->d_los + (size_t)s0 * JUR_NLOS * m->nfield;
         c.eps_off = m->d_eps_off + t0c;
         TIMED(1, jurk_launch_ega(&m->view, &c, s), "ega");
+        if (co) TIMED(4, jurk_launch_contrib(&m->view, &c, nr, co->rad, co->tau, s), "contribution");
         TIMED(2, jurk_launch_combine(&m->view, &c, s), "combine");
         m->n_launch_ega++;
         t0c = t1c;
@@ -909,6 +937,7 @@ int jur_formod_device_ld(jur_model_t *m, long nr, double const *d_geom, long ldg
       c.tsurf = m->d_tsurf + s0;
       c.los = m->d_los + (size_t)s0 * JUR_NLOS * m->nfield;   /* tiles of 64 slots, [tile][point][field][64]: s0 is a multiple of 64 */
       TIMED(1, jurk_launch_ega(&m->view, &c, s), "ega");
+      if (co) TIMED(4, jurk_launch_contrib(&m->view, &c, nr, co->rad, co->tau, s), "contribution");
       TIMED(2, jurk_launch_combine(&m->view, &c, s), "combine");
       m->n_launch_ega++;
     }
@@ -1098,6 +1127,160 @@ int jur_formod_host(jur_model_t *m, long nr, double const *const geom[7], double
     if (!pin_tau) par_memcpy(tau, h_tau, sizeof(double) * nrd);
   }
   if (status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); return JUR_ENLOS; }
+  return JUR_OK;
+}
+
+/* ---- contributions of the emitters (formod TASK contrib) ------------------------------ */
+/* Variant v of the atmosphere last set (the rows of m->h_atm, before the hydrostatic step) at `at` of rows `stride`
+ * long: v < ng keeps q[v] and no other gas and no extinction, v == ng keeps the extinction and no gas; then the
+ * hydrostatic step, as jur_model_set_atm would take it. */
+static void pack_variant_rows(jur_model_t const *m, double *h, size_t stride, size_t at, int v) {
+  int const n = (int)m->h_atm_n, ng = m->view.ng;
+  size_t const nrow = 6 + (size_t)ng + m->view.nw;
+  for (size_t row = 0; row < nrow; row++) {
+    int const g = (int)row - 6, w = g - ng;
+    double *const dst = h + row * stride + at;
+    if ((g >= 0 && g < ng && g != v) || (w >= 0 && v < ng)) memset(dst, 0, sizeof(double) * n);
+    else memcpy(dst, m->h_atm + row * (size_t)n, sizeof(double) * n);
+  }
+  hydrostatic_rows(m, h, stride, at, n);
+}
+
+/* With ctl->hydz >= 0 and H2O the emitter the hydrostatic step reads, zeroing q_H2O moves the pressure profile -- and
+ * with it the line of sight -- of every variant but H2O's own.  Those naff variants are computed by their definition, as
+ * kernel_ld does the Jacobian: the edited atmospheres stacked as profile slices (time stamps shifted by j * span), every
+ * ray once per slice, one ordinary batched call; then the caller's atmosphere goes back on the device.  fb: device
+ * scratch geom[7][N] | rad[N][nd] | tau[N][nd] | tp[3][N] (N = naff * nr) whose rad already holds the input radiances
+ * once per slice (the NaN mask).  Waits for the stream. */
+static int contrib_hydrostatic(jur_model_t *m, long nr, int naff, double const *d_geom, double *fb, int *d_status,
+                               double *d_rad_c, double *d_tau_c, hipStream_t s) {
+  int const ng = m->view.ng, nd = m->view.nd, n0 = (int)m->h_atm_n;
+  size_t const nrow = 6 + (size_t)ng + m->view.nw, N = (size_t)naff * nr, NT = (size_t)naff * n0, nrd = (size_t)nr * nd;
+  double *const fb_geom = fb, *const fb_rad = fb + 7 * N, *const fb_tau = fb_rad + N * nd, *const fb_tp = fb_tau + N * nd;
+  double *const hg = (double *)malloc(sizeof(double) * 7 * ((size_t)nr + N));
+  double *const h = (double *)malloc(sizeof(double) * nrow * NT);
+  int rc = JUR_OK, moved = 0;
+  hipError_t e = hipSuccess;
+  if (!hg || !h) { rc = JUR_ENOMEM; goto done; }
+  e = hipMemcpyAsync(hg, d_geom, sizeof(double) * 7 * (size_t)nr, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) goto done;
+  {
+    double *const g2 = hg + 7 * (size_t)nr;
+    double tmin = m->h_atm[0], tmax = m->h_atm[0];
+    for (int i = 0; i < n0; i++) { tmin = fmin(tmin, m->h_atm[i]); tmax = fmax(tmax, m->h_atm[i]); }
+    for (long i = 0; i < nr; i++) { tmin = fmin(tmin, hg[i]); tmax = fmax(tmax, hg[i]); }
+    double const span = (tmax - tmin) + 1.0;
+    for (int v = 0, j = 0; v <= ng; v++) {
+      if (v == m->view.ig_h2o) continue;          /* H2O's own variant came from the shared plane */
+      pack_variant_rows(m, h, NT, (size_t)j * n0, v);
+      for (int i = 0; i < n0; i++) h[(size_t)j * n0 + i] += (double)j * span;
+      for (int k = 0; k < 7; k++)
+        for (long i = 0; i < nr; i++) g2[k * N + (size_t)j * nr + i] = hg[k * (size_t)nr + i] + (k == 0 ? (double)j * span : 0.);
+      j++;
+    }
+    e = hipMemcpyAsync(fb_geom, g2, sizeof(double) * 7 * N, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) goto done;
+    m->h_atm_n = 0;                               /* the device no longer holds the caller's atmosphere */
+    moved = 1;
+    if ((rc = upload_atm_rows(m, h, (long)NT))) goto done;
+    if ((rc = jur_formod_device(m, (long)N, fb_geom, fb_rad, fb_tau, fb_tp, NULL, d_status ? d_status : m->d_status, s))) goto done;
+    for (int v = 0, j = 0; v <= ng && e == hipSuccess; v++) {
+      if (v == m->view.ig_h2o) continue;
+      e = hipMemcpyAsync(d_rad_c + (size_t)v * nrd, fb_rad + (size_t)j * nrd, sizeof(double) * nrd, hipMemcpyDeviceToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_tau_c + (size_t)v * nrd, fb_tau + (size_t)j * nrd, sizeof(double) * nrd, hipMemcpyDeviceToDevice, s);
+      j++;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  }
+done:
+  if (e != hipSuccess && !rc) { jur_set_error("formod_contrib: %s", hipGetErrorString(e)); rc = JUR_EHIP; }
+  if (moved && h) {                               /* the caller's atmosphere back, hydrostatic step and all */
+    memcpy(h, m->h_atm, sizeof(double) * nrow * n0);
+    hydrostatic_rows(m, h, (size_t)n0, 0, n0);
+    int const r2 = upload_atm_rows(m, h, n0);
+    if (!r2) m->h_atm_n = n0;
+    if (!rc) rc = r2;
+  }
+  free(hg);
+  free(h);
+  return rc;
+}
+
+int jur_formod_contrib_device(jur_model_t *m, long nr, double const *d_geom, double *d_rad, double *d_tau, double *d_tp, int *d_np,
+                              int *d_status, double *d_rad_c, double *d_tau_c, void *stream) {
+  if (!m || nr < 0 || (nr > 0 && (!d_geom || !d_rad || !d_tau || !d_tp || !d_rad_c || !d_tau_c))) {
+    jur_set_error("formod_contrib_device: bad arguments");
+    return JUR_EINVAL;
+  }
+  if (nr == 0) return JUR_OK;
+  if (m->view.atm_np < 2) { jur_set_error("formod_contrib_device: no atmosphere set"); return JUR_EINVAL; }
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t const s = (hipStream_t)stream;
+  int const nd = m->view.nd;
+  /* the variants whose line of sight is not the call's: all but H2O's when the hydrostatic step reads q_H2O */
+  int const naff = (m->ctl->hydz >= 0 && m->view.ig_h2o >= 0) ? m->view.ng : 0;
+  size_t const nrd = (size_t)nr * nd, N = (size_t)naff * nr;
+  double *fb = NULL;
+  if (naff) {
+    if (!m->h_atm || m->h_atm_n != m->view.atm_np) {
+      jur_set_error("formod_contrib_device: with HYDZ >= 0 the atmosphere must have been set by jur_model_set_atm");
+      return JUR_EINVAL;
+    }
+    HIPCHK(hipMalloc((void **)&fb, sizeof(double) * N * (10 + 2 * (size_t)nd)));
+    hipError_t e = hipSuccess;
+    for (int j = 0; j < naff && e == hipSuccess; j++)    /* the NaN mask, before the radiance update overwrites it */
+      e = hipMemcpyAsync(fb + 7 * N + (size_t)j * nrd, d_rad, sizeof(double) * nrd, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) { (void)hipFree(fb); jur_set_error("formod_contrib_device: %s", hipGetErrorString(e)); return JUR_EHIP; }
+  }
+  contrib_out_t const co = {d_rad_c, d_tau_c};
+  int rc = formod_device_body(m, nr, d_geom, nr, d_rad, d_tau, d_tp, nr, d_np, d_status, stream, &co);
+  if (!rc && naff) rc = contrib_hydrostatic(m, nr, naff, d_geom, fb, d_status, d_rad_c, d_tau_c, s);
+  if (fb) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(fb);
+  }
+  return rc;
+}
+
+int jur_formod_contrib_host(jur_model_t *m, long nr, double const *const geom[7], double *rad, double *tau, double *const tp[3],
+                            int *np_out, double *rad_c, double *tau_c) {
+  if (!m || nr < 0 || !rad_c || !tau_c) { jur_set_error("formod_contrib_host: bad arguments"); return JUR_EINVAL; }
+  if (nr == 0) return JUR_OK;
+  HIPCHK(hipSetDevice(m->device));
+  int const nd = m->view.nd;
+  size_t const N = (size_t)nr, nrd = N * nd, nc = (size_t)(m->view.ng + 1) * nrd;
+  hipStream_t const s = m->stream;
+  int rc = ensure_io(m, nr, 1);
+  if (rc) return rc;
+  if ((long)(2 * nc) > m->ctb_cap) {
+    if (m->d_ctb) (void)hipFree(m->d_ctb);
+    m->d_ctb = NULL; m->ctb_cap = 0;
+    HIPCHK(hipMalloc((void **)&m->d_ctb, sizeof(double) * 2 * nc));
+    m->ctb_cap = (long)(2 * nc);
+  }
+  /* the staging of jur_formod_host's packages: the model's pinned image, one transfer in, one out */
+  double *const d_geom = m->d_io, *const d_rad = d_geom + 7 * N, *const d_tau = d_rad + nrd, *const d_tp = d_tau + nrd;
+  double *const h_geom = m->h_io, *const h_rad = h_geom + 7 * N, *const h_tau = h_rad + nrd, *const h_tp = h_tau + nrd;
+  int *const h_np = (int *)(h_tp + 3 * N);
+  for (int k = 0; k < 7; k++) par_memcpy(h_geom + k * N, geom[k], sizeof(double) * N);
+  par_memcpy(h_rad, rad, sizeof(double) * nrd);
+  HIPCHK(hipMemcpyAsync(d_geom, h_geom, sizeof(double) * (7 * N + nrd), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(m->d_status, 0, sizeof(int), s));
+  if ((rc = jur_formod_contrib_device(m, nr, d_geom, d_rad, d_tau, d_tp, m->d_io_np, m->d_status, m->d_ctb, m->d_ctb + nc, s)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(h_rad, d_rad, sizeof(double) * (2 * nrd + 3 * N), hipMemcpyDeviceToHost, s));
+  if (np_out) HIPCHK(hipMemcpyAsync(h_np, m->d_io_np, sizeof(int) * N, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(rad_c, m->d_ctb, sizeof(double) * nc, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(tau_c, m->d_ctb + nc, sizeof(double) * nc, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); return JUR_ENLOS; }
+  par_memcpy(rad, h_rad, sizeof(double) * nrd);
+  par_memcpy(tau, h_tau, sizeof(double) * nrd);
+  for (int k = 0; k < 3; k++) memcpy(tp[k], h_tp + k * N, sizeof(double) * N);
+  if (np_out) memcpy(np_out, h_np, sizeof(int) * N);
   return JUR_OK;
 }
 
@@ -1457,6 +1640,7 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
   c->h_io = NULL; c->h_io_cap = 0; c->h_pkg = NULL; c->h_atm = NULL; c->h_atm_n = 0; c->h_atm_cap = 0; c->h_status = NULL;
   c->stream = NULL; c->stream2 = NULL; c->ev_mask = NULL; c->ev_trace = NULL;
   c->host_call = 0; c->have_done = 0; c->ev_done = NULL; c->d_fov = NULL; c->fov_cap = 0; c->d_kq = NULL; c->h_kq = NULL; c->kq_cap = 0;
+  c->d_ctb = NULL; c->ctb_cap = 0;
   c->timing = 0; c->evpool = NULL; c->evkind = NULL; c->ntimed = 0;
   if (hipSetDevice(c->device) != hipSuccess || create_streams(c) != JUR_OK ||
       hipMalloc((void **)&c->d_status, sizeof(int)) != hipSuccess || hipMemset(c->d_status, 0, sizeof(int)) != hipSuccess) {
@@ -1591,6 +1775,57 @@ void formod(ctl_t const *ctl, atm_t *atm, obs_t *obs) {
 }
 
 void formod_pencil(ctl_t const *ctl, atm_t *atm, obs_t *obs, int const ir) { formod_range(ctl, atm, obs, ir, 1); }
+
+/* formod() and the contribution of every emitter in one call (formod TASK contrib): obs as formod() leaves it,
+ * contrib[g] (g < ng) the spectrum of emitter g alone, contrib[ng] that of the extinction alone; each gets obs's
+ * geometry and tangent points (jur_formod_contrib_host). */
+void formod_contrib(ctl_t const *ctl, atm_t *atm, obs_t *obs, obs_t *contrib) {
+  if (ctl->checkmode) { printf("# %s: no operation in checkmode\n", __func__); return; }
+  if (!obs || !atm || !contrib) DIE("null argument");
+  int const nr = obs->nr, nd = ctl->nd, nv = ctl->ng + 1;
+  if (nr < 0 || nr > JUR_NR) DIE("ray count outside the package (max %d rays)", JUR_NR);
+  for (int v = 0; v < nv; v++) contrib[v].nr = nr;
+  if (nr == 0) return;
+  int const lane = acquire_lane(ctl);
+  jur_model_t *m = g_lane[lane];
+  if (jur_model_set_atm(m, atm) != JUR_OK) DIE("%s", jur_last_error());
+  size_t const nrd = (size_t)nr * nd;
+  double *const buf = (double *)malloc(sizeof(double) * (2 + 2 * (size_t)nv) * nrd);
+  if (!buf) DIE("Out of memory!");
+  double *const rad = buf, *const tau = rad + nrd, *const rad_c = tau + nrd, *const tau_c = rad_c + nv * nrd;
+  for (int i = 0; i < nr; i++)
+    for (int id = 0; id < nd; id++) rad[(size_t)i * nd + id] = obs->rad[i][id];
+  double const *geom[7] = {obs->time, obs->obsz, obs->obslon, obs->obslat, obs->vpz, obs->vplon, obs->vplat};
+  double *tp[3] = {obs->tpz, obs->tplon, obs->tplat};
+  int const rc = jur_formod_contrib_host(m, nr, geom, rad, tau, tp, NULL, rad_c, tau_c);
+  if (rc == JUR_ENLOS) DIE("Too many LOS points!");
+  if (rc != JUR_OK) DIE("%s", jur_last_error());
+  for (int v = -1; v < nv; v++) {                 /* v = -1: obs itself */
+    obs_t *const o = (v < 0) ? obs : &contrib[v];
+    double const *const r = (v < 0) ? rad : rad_c + (size_t)v * nrd, *const t = (v < 0) ? tau : tau_c + (size_t)v * nrd;
+    if (v >= 0) {
+      memcpy(o->time, obs->time, sizeof(double) * nr);
+      memcpy(o->obsz, obs->obsz, sizeof(double) * nr);
+      memcpy(o->obslon, obs->obslon, sizeof(double) * nr);
+      memcpy(o->obslat, obs->obslat, sizeof(double) * nr);
+      memcpy(o->vpz, obs->vpz, sizeof(double) * nr);
+      memcpy(o->vplon, obs->vplon, sizeof(double) * nr);
+      memcpy(o->vplat, obs->vplat, sizeof(double) * nr);
+      memcpy(o->tpz, obs->tpz, sizeof(double) * nr);
+      memcpy(o->tplon, obs->tplon, sizeof(double) * nr);
+      memcpy(o->tplat, obs->tplat, sizeof(double) * nr);
+    }
+    for (int i = 0; i < nr; i++) {
+      for (int id = 0; id < nd; id++) {
+        o->rad[i][id] = r[(size_t)i * nd + id];
+        o->tau[i][id] = t[(size_t)i * nd + id];
+      }
+      for (int id = nd; id < JUR_ND; id++) { o->rad[i][id] = 0.0; o->tau[i][id] = 1.0; }
+    }
+  }
+  free(buf);
+  release_lane(lane);
+}
 
 /* kernel() under its own name (jurassic.h:664, jurassic.c:812-857): the Jacobian into a gsl_matrix of
  * (finite measurements) x (state elements).  GSL is not a dependency of this library: jur_gsl_matrix_t restates the

@@ -59,6 +59,10 @@ def lib():
         L.jur_host_alloc.argtypes = [C.c_size_t]
         L.jur_host_free.argtypes = [C.c_void_p]
         L.jur_formod_device.argtypes = [C.c_void_p, C.c_long] + [C.c_void_p] * 7
+        L.jur_formod_contrib_host.argtypes = [C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), C.POINTER(C.c_int), dp, dp]
+        L.jur_formod_contrib_device.argtypes = [C.c_void_p, C.c_long] + [C.c_void_p] * 9
+        L.formod_contrib.argtypes = [C.c_void_p] * 4
+        L.formod_contrib.restype = None
         L.jur_model_reserve.argtypes = [C.c_void_p, C.c_long]
         L.jur_model_workspace_bytes.restype = C.c_long
         L.jur_model_workspace_bytes.argtypes = [C.c_void_p]
@@ -76,6 +80,7 @@ def lib():
         L.jur_model_enable_timing.argtypes = [C.c_void_p, C.c_int]
         L.jur_model_last_kernel_ms.argtypes = [C.c_void_p, dp, C.POINTER(C.c_long)]
         L.jur_model_last_pencil_ms.argtypes = [C.c_void_p, dp, C.POINTER(C.c_long)]
+        L.jur_model_last_contrib_ms.argtypes = [C.c_void_p, dp, C.POINTER(C.c_long)]
         L.jur_model_set_pencil.argtypes = [C.c_void_p, C.c_long, C.c_int]
         L.jur_model_set_arithmetic.argtypes = [C.c_void_p, C.c_int]
         L.jur_model_arithmetic.argtypes = [C.c_void_p]
@@ -281,6 +286,23 @@ class Model:
         _chk(lib().jur_formod_host(self.h, nr, garr, _p(rad), _p(tau), tarr, npts.ctypes.data_as(C.POINTER(C.c_int))))
         return dict(rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts)
 
+    def formod_contrib_host(self, geom, rad_in=None):
+        """formod_host plus the contribution of every emitter (jur_formod_contrib_host): the formod_host dict with
+        rad_c, tau_c of shape (ng + 1, nr, nd) -- [g] emitter g alone, [ng] the extinction alone."""
+        g = np.ascontiguousarray(np.asarray(geom, dtype=np.float64).T)
+        nr, nd = g.shape[1], self.nd
+        rad = np.zeros((nr, nd)) if rad_in is None else np.ascontiguousarray(rad_in, dtype=np.float64).copy()
+        tau = np.zeros((nr, nd))
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        rad_c = np.zeros((self.ng + 1, nr, nd))
+        tau_c = np.zeros((self.ng + 1, nr, nd))
+        garr = (dp * 7)(*[_p(g[k]) for k in range(7)])
+        tarr = (dp * 3)(*[_p(tp[k]) for k in range(3)])
+        _chk(lib().jur_formod_contrib_host(self.h, nr, garr, _p(rad), _p(tau), tarr, npts.ctypes.data_as(C.POINTER(C.c_int)),
+                                           _p(rad_c), _p(tau_c)))
+        return dict(rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, rad_c=rad_c, tau_c=tau_c)
+
     def host_buffers(self, nr, pinned=True):
         return HostBuffers(nr, self.nd, pinned)
 
@@ -310,6 +332,11 @@ class Model:
     def formod_device(self, nr, d_geom, d_rad, d_tau, d_tp, d_np=0, d_status=0, stream=0):
         """All arguments are raw device addresses (ints), e.g. torch_tensor.data_ptr()."""
         _chk(lib().jur_formod_device(self.h, nr, d_geom, d_rad, d_tau, d_tp, d_np, d_status, stream))
+
+    def formod_contrib_device(self, nr, d_geom, d_rad, d_tau, d_tp, d_rad_c, d_tau_c, d_np=0, d_status=0, stream=0):
+        """jur_formod_contrib_device: raw device addresses as for formod_device; d_rad_c / d_tau_c hold
+        (ng + 1) x nr x nd doubles."""
+        _chk(lib().jur_formod_contrib_device(self.h, nr, d_geom, d_rad, d_tau, d_tp, d_np, d_status, d_rad_c, d_tau_c, stream))
 
     def fov_apply_device(self, nr, d_time, d_vpz, d_rad, d_tau, dz, w, stream=0):
         """Field-of-view convolution of device arrays in place (raw device addresses as for formod_device)."""
@@ -357,6 +384,12 @@ class Model:
         _chk(lib().jur_model_last_pencil_ms(self.h, C.byref(pm), C.byref(pn)))
         return dict(trace_ms=ms[0], ega_ms=ms[1], combine_ms=ms[2], trace_launches=n[0], ega_launches=n[1],
                     combine_launches=n[2], pencil_ms=pm.value, pencil_launches=pn.value)
+
+    def contrib_ms(self):
+        """The contribution kernel's share of the launches timed since the last call (call kernel_ms first)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        _chk(lib().jur_model_last_contrib_ms(self.h, C.byref(ms), C.byref(n)))
+        return dict(contrib_ms=ms.value, contrib_launches=n.value)
 
     def workspace_bytes(self):
         return lib().jur_model_workspace_bytes(self.h)
@@ -462,6 +495,13 @@ def formod_device_multi(models, nr, d_geom, d_rad, d_tau, d_tp, d_np=0, d_status
 def formod(ctl, atm, obs):
     """Drop-in entry (reference CPUdrivers.c:179): tables from ctl.tblbase files."""
     lib().formod(C.byref(ctl), C.byref(atm), C.byref(obs))
+
+
+def formod_contrib(ctl, atm, obs):
+    """Drop-in formod_contrib(): obs as formod() leaves it; -> list of ng + 1 obs_t (emitters, then EXTINCT)."""
+    out = (abi.obs_t * (ctl.ng + 1))()
+    lib().formod_contrib(C.byref(ctl), C.byref(atm), C.byref(obs), out)
+    return list(out)
 
 
 def dropin_finalize():
