@@ -369,7 +369,8 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, double con
     }
   }
 
-  bool const outside = (obsz < zmin) || (vpz > zmax - 0.001);
+  // (zmin == zmax: a slice without vertical extent is not entered -- DESIGN.md section 2)
+  bool const outside = (obsz < zmin) || (vpz > zmax - 0.001) || (zmin == zmax);
   // (fused kernel: which lanes' rays never enter the atmosphere is said by ONE lane, in its own program order
   // before it starts stepping -- a branch of the lanes concerned could be scheduled behind the others' loop)
   L.never_enter(__ballot(outside));
@@ -2101,17 +2102,18 @@ __global__ __launch_bounds__(1024) void jur_pencil_kernel(jur_view_t v, jur_chun
     __syncthreads();
     int const a0 = sl_lo;
     if (a0 == sl_hi) {
-      // its extent: the points that share the first one's time stamp (time stamps are sorted when atm_sorted;
-      // otherwise no copy is made)
+      // its extent as locate_atm forms it (its second search, jr_common.h:141-152; time stamps are sorted when
+      // atm_sorted, otherwise no copy is made): the points that share the first one's time stamp -- and the last
+      // point of the atmosphere too when that one alone follows them
       int n = 0;
       if (v.atm_sorted) {
         double const t0 = v.atm_time[a0];
-        int lo = a0, hi = v.atm_np;              // first index in (a0, atm_np] whose time differs
+        int lo = a0, hi = v.atm_np - 1;
         while (hi > lo + 1) {
           int const i = (lo + hi) / 2;
-          if (v.atm_time[i] == t0) lo = i; else hi = i;
+          if (v.atm_time[i] > t0) hi = i; else lo = i;
         }
-        n = hi - a0;
+        n = ((hi == v.atm_np - 1) ? v.atm_np : hi) - a0;
       }
       if (n >= 2 && n <= atm_cap) {
         int const nrow = 7 + ng + v.nw;

@@ -435,6 +435,48 @@ static void hydrostatic_rows(jur_model_t const *m, double *h, size_t stride, siz
               ig >= 0 ? h + (6 + (size_t)ig) * stride + at : NULL, h + 4 * stride + at);
 }
 
+/* locate_atm (jr_common.h:127-154): the slice [*first, *first + return) of the n points with time stamps `time` that
+ * a ray with time stamp t is traced through */
+static int atm_slice(double const *time, long n, double t, long *first) {
+  long lo = 0, hi = n - 1;
+  while (hi > lo + 1) {
+    long const i = (lo + hi) / 2;
+    if (time[i] < t) lo = i; else hi = i;
+  }
+  long const lower = (0 == lo) ? lo : hi;
+  lo = lower;
+  hi = n - 1;
+  while (hi > lo + 1) {
+    long const i = (lo + hi) / 2;
+    if (time[i] > t) hi = i; else lo = i;
+  }
+  *first = lower;
+  return (int)(((hi == n - 1) ? n : hi) - lower);
+}
+
+/* Time stamps of an atmosphere of n points stacked behind others (kernel_ld, contrib_hydrostatic), shifted by `shift`.
+ * Stacked, its end points are no longer the ends of the array, where locate_atm lets one point alone join the slice
+ * next to it (jr_common.h:127-154): such a point takes that slice's time stamp, and the two points of a two-point
+ * atmosphere (every ray's slice alone) one time stamp.  Then every slice of two or more points that a ray meets in
+ * the atmosphere alone is a run of equal time stamps of the block (time stamps sorted; unsorted ones make locate_atm's
+ * bisection depend on the array's length, and no stacking reproduces it).  In place is allowed. */
+static void stack_times(double *dst, double const *src, int n, double shift) {
+  double const first = (n >= 2 && src[0] != src[1]) ? src[1] : src[0];
+  double const last = (n >= 3 && src[n - 1] != src[n - 2]) ? src[n - 2] : (n == 2 ? first : src[n - 1]);
+  for (int i = 1; i < n - 1; i++) dst[i] = src[i] + shift;
+  dst[0] = first + shift;
+  dst[n - 1] = last + shift;
+}
+
+/* Time stamp of a ray of a stacked block: the stacked time stamp (block_time, from stack_times) of the first point of
+ * the slice the ray has in the atmosphere alone (time, n points), so that it finds the same points there -- also where
+ * its own time stamp matches no profile but locate_atm still hands it two points or more.  A ray whose slice alone is
+ * one point (not entered) gets `above`, a time stamp above all, and with it the last point alone. */
+static double stacked_ray_time(double const *time, int n, double t, double const *block_time, double above) {
+  long first;
+  return atm_slice(time, n, t, &first) >= 2 ? block_time[first] : above;
+}
+
 /* upload packed rows [6+ng+nw][n] and derive what the kernels want to know about them */
 static int upload_atm_rows(jur_model_t *m, double const *h, long n) {
   HIPCHK(hipSetDevice(m->device));
@@ -463,18 +505,22 @@ static int upload_atm_rows(jur_model_t *m, double const *h, long n) {
   for (long i = 1; i < n; i++) { if (z[i] < m->atm_zmin) m->atm_zmin = z[i]; if (z[i] > m->atm_zmax) m->atm_zmax = z[i]; }
   v->atm_sorted = 1;
   v->atm_maxslice = 1;
-  for (long i = 1, dir = 0, run = 1; i < n; i++) {
-    run = (time[i] != time[i - 1]) ? 1 : run + 1;
-    if (run > v->atm_maxslice) v->atm_maxslice = (int)run;
-    if (time[i] != time[i - 1]) {
-      m->atm_slices++;
-      if (time[i] < time[i - 1]) v->atm_sorted = 0;
-      dir = 0;
-      continue;
-    }
-    long const d = (z[i] > z[i - 1]) - (z[i] < z[i - 1]);
-    if (d == 0 || (dir != 0 && d != dir)) v->atm_sorted = 0;
-    dir = d;
+  for (long i = 1; i < n; i++) {
+    if (time[i] != time[i - 1]) m->atm_slices++;
+    if (time[i] < time[i - 1]) v->atm_sorted = 0;
+  }
+  /* The slices are those locate_atm hands the rays whose time stamps match a profile -- not always the runs of equal
+   * time stamps: one point alone at either end of the atmosphere joins the slice next to it (jr_common.h:127-154).
+   * Ray time stamps that match no profile get one point, or the last two, which never needs a sorted axis. */
+  for (long a = 0; a < n;) {
+    long lo, b = a + 1;
+    while (b < n && time[b] == time[a]) b++;
+    int const len = atm_slice(time, n, time[a], &lo);
+    if (len > v->atm_maxslice) v->atm_maxslice = len;
+    for (long i = lo + 2; i < lo + len; i++)            /* z strictly monotone inside the slice */
+      if ((z[i] > z[i - 1]) != (z[lo + 1] > z[lo]) || z[i] == z[i - 1]) v->atm_sorted = 0;
+    if (len >= 2 && z[lo + 1] == z[lo]) v->atm_sorted = 0;
+    a = b;
   }
   double const *d = (double const *)m->d_atm;
   v->atm_np = (int)n;
@@ -1174,9 +1220,11 @@ static int contrib_hydrostatic(jur_model_t *m, long nr, int naff, double const *
     for (int v = 0, j = 0; v <= ng; v++) {
       if (v == m->view.ig_h2o) continue;          /* H2O's own variant came from the shared plane */
       pack_variant_rows(m, h, NT, (size_t)j * n0, v);
-      for (int i = 0; i < n0; i++) h[(size_t)j * n0 + i] += (double)j * span;
-      for (int k = 0; k < 7; k++)
-        for (long i = 0; i < nr; i++) g2[k * N + (size_t)j * nr + i] = hg[k * (size_t)nr + i] + (k == 0 ? (double)j * span : 0.);
+      stack_times(h + (size_t)j * n0, h + (size_t)j * n0, n0, (double)j * span);
+      for (long i = 0; i < nr; i++)
+        g2[(size_t)j * nr + i] = stacked_ray_time(m->h_atm, n0, hg[i], h + (size_t)j * n0, tmax + (naff + 1.0) * span);
+      for (int k = 1; k < 7; k++)
+        for (long i = 0; i < nr; i++) g2[k * N + (size_t)j * nr + i] = hg[k * (size_t)nr + i];
       j++;
     }
     e = hipMemcpyAsync(fb_geom, g2, sizeof(double) * 7 * N, hipMemcpyHostToDevice, s);
@@ -1531,7 +1579,7 @@ static int kernel_ld(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, si
         h[row * NT + at + ipa[e]] = x0[e] + hh;
       }
       hydrostatic_rows(m, h, NT, at, np0);
-      for (int i = 0; i < np0; i++) h[at + i] = atm->time[i] + (double)j * span;
+      stack_times(h + at, atm->time, np0, (double)j * span);
     }
     m->h_atm_n = 0;                            /* the device no longer holds the caller's atmosphere */
     rc = upload_atm_rows(m, h, (long)NT);
@@ -1545,7 +1593,7 @@ static int kernel_ld(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, si
     for (size_t j = 0; j < ncopy; j++)
       for (int i = 0; i < nr; i++) {
         size_t const r = j * (size_t)nr + i;
-        geom[0][r] = src[0][i] + (double)j * span;
+        geom[0][r] = stacked_ray_time(atm->time, np0, src[0][i], h + j * (size_t)np0, tmax + (ncopy + 1.0) * span);
         for (int q = 1; q < 7; q++) geom[q][r] = src[q][i];
         for (int id = 0; id < nd; id++) rad[r * nd + id] = obs->rad[i][id];   /* carries the NaN mask */
       }

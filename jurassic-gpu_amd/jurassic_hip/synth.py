@@ -174,3 +174,201 @@ def stack_profiles(atm, ctl, nprofiles, seed=0, dp=0.05, dt=30.0):
         np.ctypeslib.as_array(out.q)[:, s] = q
         np.ctypeslib.as_array(out.k)[:, s] = k
     return out
+
+
+# ---- ragged multi-profile scenes across the globe ----------------------------------------------------------------
+# The atmospheres above are copies of one profile on one z grid at one place.  These put profiles of their own length,
+# vertical range, order and location side by side, and rays at every profile in any azimuth, so that the slice a ray
+# is traced through (locate_atm / altitude_range_nn, jr_common.h:127-154, 411-420) is a different one per ray.
+
+def _cart(alt, lon, lat):
+    r, lo, la = RE + np.asarray(alt, dtype=np.float64), np.radians(lon), np.radians(lat)
+    return np.stack([r * np.cos(la) * np.cos(lo), r * np.cos(la) * np.sin(lo), r * np.sin(la)], axis=-1)
+
+
+def _geo(x):
+    """(alt, lon, lat) of Cartesian points, as cart2geo forms them."""
+    x = np.asarray(x, dtype=np.float64)
+    r = np.sqrt((x * x).sum(axis=-1))
+    return r - RE, np.degrees(np.arctan2(x[..., 1], x[..., 0])), np.degrees(np.arcsin(x[..., 2] / r))
+
+
+def ragged_atmosphere(ctl, spec, seed=0, base=None, order=None):
+    """atm_t holding one profile per entry of `spec`, each regridded from the first profile of `base` (an atm_t) and
+    perturbed (p * (1 + U(-5 %, 5 %)), T + U(-10, 10) K per profile, then 1 % / 1 K per level).  An entry is a dict:
+
+      time        time stamp (any double)                lon, lat   location [deg]
+      n           number of levels (1 ... )              z0, z1     bottom and top altitude [km]
+      descending  written top-down (default False)       p0_top     pressure 0 at the top level
+      q_nonpos    list of (emitter, level, value): q <= 0 there, as retrieval iterates carry them
+      move_at     level from which on the location is lon + 0.5, lat - 0.25 (altitude_range_nn stops there)
+
+    order: permutation of the profiles in the array (default: as given)."""
+    assert base is not None, "ragged_atmosphere needs a base profile"
+    rng = np.random.default_rng(seed)
+    nb = base.np
+    bz = np.ctypeslib.as_array(base.z)[:nb]
+    srt = np.argsort(bz)
+    bz = bz[srt]
+    blnp = np.log(np.ctypeslib.as_array(base.p)[:nb][srt])
+    bt = np.ctypeslib.as_array(base.t)[:nb][srt]
+    bq = np.ctypeslib.as_array(base.q)[:, :nb][:, srt]
+    bk = np.ctypeslib.as_array(base.k)[:, :nb][:, srt]
+    blocks = []
+    for s in spec:
+        n = int(s["n"])
+        z = np.linspace(s["z0"], s["z1"], n) if n > 1 else np.array([float(s["z0"])])
+        fp, ft = 1.0 + rng.uniform(-0.05, 0.05), rng.uniform(-10.0, 10.0)
+        p = np.exp(np.interp(z, bz, blnp)) * fp * (1.0 + rng.uniform(-0.01, 0.01, n))
+        t = np.interp(z, bz, bt) + ft + rng.uniform(-1.0, 1.0, n)
+        q = np.array([np.interp(z, bz, bq[g]) for g in range(ctl.ng)]).reshape(ctl.ng, n)
+        q *= 1.0 + rng.uniform(-0.05, 0.05, (ctl.ng, 1))
+        k = np.array([np.interp(z, bz, bk[w]) for w in range(ctl.nw)]).reshape(ctl.nw, n)
+        if s.get("p0_top"):
+            p[np.argmax(z)] = 0.0
+        for g, lev, val in s.get("q_nonpos", ()):
+            q[g, lev] = val
+        lon = np.full(n, float(s["lon"]))
+        lat = np.full(n, float(s["lat"]))
+        if s.get("descending"):
+            z, p, t, q, k = z[::-1], p[::-1], t[::-1], q[:, ::-1], k[:, ::-1]
+        if s.get("move_at") is not None:
+            lon[s["move_at"]:] += 0.5
+            lat[s["move_at"]:] -= 0.25
+        blocks.append((np.full(n, float(s["time"])), z, lon, lat, p, t, q, k))
+    order = range(len(spec)) if order is None else order
+    cols = [np.concatenate([blocks[i][f] for i in order], axis=-1) for f in range(8)]
+    n = cols[0].shape[-1]
+    assert 2 <= n <= abi.NP
+    out = abi.atm_t()
+    out.np = n
+    for f, name in enumerate(("time", "z", "lon", "lat", "p", "t")):
+        np.ctypeslib.as_array(getattr(out, name))[:n] = cols[f]
+    np.ctypeslib.as_array(out.q)[:ctl.ng, :n] = cols[6]
+    np.ctypeslib.as_array(out.k)[:ctl.nw, :n] = cols[7]
+    return out
+
+
+def global_geometry(profiles, n, seed=0, obsz=750.0):
+    """(n, 7) rays, ray i at profile i mod len(profiles) (its location and time stamp), kind i // len(profiles) mod 6:
+
+      0, 1  limb in a random azimuth, tangent point within 2 deg of the profile, tangent height U(z0 - 5, z1 + 5) km
+            (below ground to above the top); the view point is the tangent point
+      2     nadir: view point straight below the observer, on the ground
+      3     off-nadir: view point on the ground 1 - 15 deg away in a random azimuth
+      4, 5  observer inside the profile's range looking up (4) or down (5) at 20 - 80 deg elevation
+
+    Profiles at a pole or at lon +-180 put rays over the pole and across the dateline."""
+    rng = np.random.default_rng(seed)
+    g = np.zeros((n, 7))
+    npro = len(profiles)
+    for i in range(n):
+        s = profiles[i % npro]
+        kind = (i // npro) % 6
+        zlo, zhi = min(s["z0"], s["z1"]), max(s["z0"], s["z1"])
+        up = _cart(0.0, s["lon"], s["lat"])
+        up /= np.linalg.norm(up)
+        # a horizontal unit vector in a random azimuth (well defined at the poles too)
+        a = rng.normal(size=3)
+        a -= up * (a @ up)
+        h = a / np.linalg.norm(a)
+        if kind in (0, 1):
+            off = rng.uniform(0.0, 2.0)
+            b = rng.normal(size=3)
+            b -= up * (b @ up)
+            b /= np.linalg.norm(b)
+            ut = np.cos(np.radians(off)) * up + np.sin(np.radians(off)) * b
+            ht = h - ut * (h @ ut)
+            ht /= np.linalg.norm(ht)
+            zt = rng.uniform(zlo - 5.0, zhi + 5.0)
+            xt = (RE + zt) * ut
+            xo = xt - np.sqrt((RE + obsz) ** 2 - (RE + zt) ** 2) * ht
+            obs, vp = _geo(xo), _geo(xt)
+        elif kind == 2:
+            obs, vp = (obsz, s["lon"], s["lat"]), (0.0, s["lon"], s["lat"])
+        elif kind == 3:
+            ang = np.radians(rng.uniform(1.0, 15.0))
+            xv = RE * (np.cos(ang) * up + np.sin(ang) * h)
+            obs, vp = (obsz, s["lon"], s["lat"]), _geo(xv)
+        else:
+            zo = rng.uniform(zlo + 0.2 * (zhi - zlo), zhi - 0.2 * (zhi - zlo))
+            el = np.radians(rng.uniform(20.0, 80.0))
+            xo = (RE + zo) * up
+            d = np.cos(el) * h + np.sin(el) * (up if kind == 4 else -up)
+            # view point half way to the top (bottom) along the ray: inside the atmosphere, below its top
+            obs, vp = (zo, s["lon"], s["lat"]), _geo(xo + 0.5 * ((zhi - zo) if kind == 4 else (zo - zlo)) / np.sin(el) * d)
+        g[i] = (s["time"],) + tuple(float(x) for x in obs) + tuple(float(x) for x in vp)
+    return g
+
+
+def _spec(time, lon, lat, n, z0, z1, **kw):
+    return dict(time=time, lon=lon, lat=lat, n=n, z0=z0, z1=z1, **kw)
+
+
+# Named scenes: name -> (profile specs in array order, extra ray time stamps that match no profile, order).
+#   ragged    five profiles of 2 ... 150 levels, own ranges and places (a pole, lon -180, the dateline's other side),
+#             ascending and descending, non-integer sorted time stamps
+#   unsorted  the same kind of profiles stored out of time order (atm_sorted = 0), with p = 0 at a top level, q <= 0
+#             at some levels and a location change part-way through a profile
+#   lone_ends a first and a last profile of one point: locate_atm gives the slice after the first one point and the
+#             slice before the last one point the foreign point too (jr_common.h:127-154); the last one lies above the
+#             descending profile before it, at the same place, so that it widens that slice's altitude range
+#   lone_up   the same two one-point profiles where the slices they join stay monotone: the first one 1 km below the
+#             ascending profile after it, the last one 15 km above the ASCENDING profile before it, each at that
+#             profile's place -- atm_sorted holds, so the fused kernel copies the joined slice (foreign point
+#             included) to LDS and the tracer resumes its altitude brackets on it
+#   short_last a last profile of two levels: a ray time stamp between the profiles before it and it is traced through
+#             it (locate_atm's second search), though it matches no profile
+#   at_cap    a slice of 315 levels: 13 rows (5 emitters, 1 window) of 315 doubles fill 32 KB of LDS as far as they
+#             can (jur_pencil_kernel's profile copy is made)
+#   over_cap  a slice of 316 levels: one more than fits (no copy)
+SCENES = {
+    "ragged": ([_spec(0.5, 10.0, 45.0, 60, 0.0, 80.0),
+                _spec(1.25, -180.0, -30.0, 150, 2.0, 95.0, descending=True),
+                _spec(2.0, 179.9, 0.0, 2, 0.0, 70.0),
+                _spec(2.75, 45.0, 89.99, 33, 0.0, 60.0, descending=True),
+                _spec(4.0, -75.0, -90.0, 41, 5.0, 85.0)],
+               [0.0, 1.5, 3.5, 9.0], None),
+    "unsorted": ([_spec(3.0, 120.0, 60.0, 45, 0.0, 90.0, p0_top=True, q_nonpos=[(1, 10, 0.0), (2, 20, -1e-9)]),
+                  _spec(-1.5, -10.0, -89.99, 80, 0.0, 75.0, descending=True, p0_top=True),
+                  _spec(7.0, 180.0, 10.0, 30, 3.0, 65.0, move_at=20),
+                  _spec(0.0, 0.0, 90.0, 25, 0.0, 100.0, q_nonpos=[(0, 3, -1e-7), (1, 0, 0.0)])],
+                 [2.0, 10.0], [2, 0, 3, 1]),
+    "lone_ends": ([_spec(0.0, 30.0, 20.0, 1, 5.0, 5.0),
+                   _spec(1.0, 30.0, 20.0, 50, 0.0, 70.0),
+                   _spec(2.5, -120.0, -45.0, 40, 0.0, 80.0),
+                   _spec(4.0, 60.0, 70.0, 45, 0.0, 60.0, descending=True),
+                   _spec(5.0, 60.0, 70.0, 1, 75.0, 75.0)],
+                  [-2.0, 0.0, 0.5, 3.0, 4.5, 5.0, 9.0], None),
+    "lone_up": ([_spec(0.0, 30.0, 20.0, 1, -1.0, -1.0),
+                 _spec(1.0, 30.0, 20.0, 50, 0.0, 70.0),
+                 _spec(2.5, -120.0, -45.0, 40, 0.0, 80.0, descending=True),
+                 _spec(4.0, 60.0, 70.0, 45, 0.0, 60.0),
+                 _spec(5.0, 60.0, 70.0, 1, 75.0, 75.0)],
+                [-2.0, 0.0, 0.5, 3.0, 4.5, 5.0, 9.0], None),
+    "short_last": ([_spec(0.0, -60.0, 35.0, 40, 0.0, 70.0),
+                    _spec(1.0, 100.0, -20.0, 30, 0.0, 85.0, descending=True),
+                    _spec(2.0, 170.0, 5.0, 2, 0.0, 80.0)],
+                   [0.5, 1.5, 3.0], None),
+    "at_cap": ([_spec(0.0, 20.0, -10.0, 315, 0.0, 90.0),
+                _spec(1.0, -150.0, 50.0, 120, 0.0, 80.0, descending=True)],
+               [], None),
+    "over_cap": ([_spec(0.0, 20.0, -10.0, 316, 0.0, 90.0, descending=True),
+                  _spec(1.0, -150.0, 50.0, 120, 0.0, 80.0)],
+                 [], None),
+}
+
+
+def scene(name, ctl, base, nrays=180, seed=0):
+    """-> (atm_t, geom (nrays + extra, 7), profile specs) of a named scene.  The rays carry their profile's time stamp;
+    after them come six limb rays per extra time stamp (one that matches no profile, or lies below the first or
+    above the last), looking at the first profile's place."""
+    spec, extra, order = SCENES[name]
+    atm = ragged_atmosphere(ctl, spec, seed=seed, base=base, order=order)
+    live = [s for s in spec if s["n"] > 1]
+    geom = global_geometry(live, nrays, seed=seed + 1)
+    if extra:
+        g2 = global_geometry(live[:1], 6 * len(extra), seed=seed + 2)
+        g2[:, 0] = np.repeat(extra, 6)
+        geom = np.vstack([geom, g2])
+    return atm, geom, spec

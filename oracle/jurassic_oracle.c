@@ -576,6 +576,9 @@ static int traceray(ctl_t const *ctl, atm_t const *atm, double const geom[7], po
   altitude_range_nn(atm, atmIdx, atmNp, &zmin, &zmax);
   if (obsz < zmin) return 0;
   if (vpz > zmax - 0.001) return 0;
+  /* A slice without vertical extent (one point, or a first column of one level) is not entered: the reference would
+   * step out of it at its first point and read los[-1] below */
+  if (zmin == zmax) return 0;
   geo2cart(obsz, obslon, obslat, xobs);
   geo2cart(vpz, vplon, vplat, xvp);
   for (int i = 0; i < 3; i++) ex0[i] = xvp[i] - xobs[i];
@@ -607,14 +610,16 @@ static int traceray(ctl_t const *ctl, atm_t const *atm, double const geom[7], po
     }
     cart2geo(x, &z, &lon, &lat);
     if ((z < zmin) || (z > zmax)) {                     /* LOS escaped :637-648 */
-      double xh[3];
       stop = (z < zmin) ? 2 : 1;
-      geo2cart(los[np - 1].z, los[np - 1].lon, los[np - 1].lat, xh);
-      double const zfrac = (z < zmin) ? zmin : zmax;
-      double const frac = (zfrac - los[np - 1].z) / (z - los[np - 1].z);
-      for (int i = 0; i < 3; i++) x[i] = xh[i] + frac * (x[i] - xh[i]);
-      cart2geo(x, &z, &lon, &lat);
-      los[np - 1].ds = ds * frac;
+      if (np > 0) {      /* at the first point there is no segment to cut: that point alone, ds = 0 */
+        double xh[3];
+        geo2cart(los[np - 1].z, los[np - 1].lon, los[np - 1].lat, xh);
+        double const zfrac = (z < zmin) ? zmin : zmax;
+        double const frac = (zfrac - los[np - 1].z) / (z - los[np - 1].z);
+        for (int i = 0; i < 3; i++) x[i] = xh[i] + frac * (x[i] - xh[i]);
+        cart2geo(x, &z, &lon, &lat);
+        los[np - 1].ds = ds * frac;
+      }
       ds = 0.;
     }
     intpol_pt(atm, (int)atmIdx, atmNp, z, &p, &t);
