@@ -289,13 +289,6 @@ enum { JUR_ARITH_FAST = 0, JUR_ARITH_EXACT = 1 };
 int  jur_model_set_arithmetic(jur_model_t *m, int mode);
 int  jur_model_arithmetic(jur_model_t const *m);
 
-/* Look-up kernel arrangement (experiment of round 4): nch in 2 .. 4 lets one lane walk up to nch
- * channels of a gas whose tables stand on the same (p, T) grid (brackets and LOS row once per segment and group);
- * nch < 2 (the default) keeps one (channel, gas) pair per workgroup, which is faster on every shape measured.
- * Strictly increasing tables only; bit-identical results. */
-int  jur_model_set_ega_group(jur_model_t *m, int nch);
-int  jur_model_ega_group(jur_model_t const *m);   /* channels per lane of the next call (0: one pair per workgroup) */
-
 /* Frees the process-global state behind formod() / formod_GPU() / formod_pencil(): the lanes (streams, atmosphere,
  * workspaces, pinned images) and the emissivity tables loaded by the first call.  Upstream keeps its counterparts for
  * the life of the process (GPUdrivers.cu:263-273, 309; jr_common.h:60-78).  Waits for calls in flight; returns the

@@ -12,10 +12,9 @@ extern "C" {
 
 typedef struct { int a, b; } jur_int2;
 typedef struct { float u, eps; } jur_ue_t;
-/* slopes of the bracket [entry i, entry i+1] of a curve, formed on the device once per model from the fp32 entries
- * (strictly increasing tables only): what get_u and get_eps multiply with instead of dividing by the bracket width */
-typedef struct { double du_de, de_du; } __attribute__((aligned(16))) jur_sl_t;
-/* bracket [entry i, entry i+1] of a curve in one record: the two entries as stored and both slopes (strict tables) */
+/* bracket [entry i, entry i+1] of a curve in one record: the two entries as stored and both slopes, formed on the
+ * device once per model from the fp32 entries (strictly increasing tables only): what get_u and get_eps multiply with
+ * instead of dividing by the bracket width */
 typedef struct { float u0, e0, u1, e1; double du_de, de_du; } __attribute__((aligned(32))) jur_rec_t;
 /* 16-byte descriptors: one load brings the axis value together with the extent
  * and the offset of the next level of the hierarchy. */
@@ -23,20 +22,6 @@ typedef struct { double p; int nt; int c0; } jur_lvl_t;   /* pressure level: nt 
 typedef struct { double t; int nu; int e0; } jur_crv_t;   /* curve: nu (u,eps) entries from entry e0 OF ITS PAIR
                                                              (pair_e0[pair] + e0 in the ue array): 32 bits hold any
                                                              pair (<= 40 x 30 x 304 entries), the set may hold > 2^31 */
-
-/* Work item of jur_ega_group_kernel: up to JUR_EGA_NCH channels of ONE gas whose tables stand on the same (p, T)
- * grid (same levels, same temperatures per level) -- what tables produced on one grid do.  A lane then owns a ray and
- * the gas and walks the item's channels inside the segment loop: the LOS row, the p bracket, both T brackets are
- * found once per segment and item instead of once per (channel, gas) pair (jr_common.h:241-246: the brackets do not
- * depend on the curve). */
-#define JUR_EGA_NCH 4
-typedef struct {
-  int g, nch;
-  int flags;                    /* bit 0: every curve of the item's tables has >= 2 entries */
-  int pad;
-  int d[JUR_EGA_NCH];
-  long long e0[JUR_EGA_NCH];    /* first entry of pair (g, d[k]) in ue */
-} jur_item_t;
 
 /* Everything about the continua that depends on the channel only, reduced on
  * the host once per model with the reference's own expression order
@@ -73,7 +58,6 @@ typedef struct {
   jur_lvl_t const *lvl;
   jur_crv_t const *crv;
   jur_ue_t const *ue;
-  jur_sl_t const *sl;           /* [entries] bracket slopes, indexed like ue; NULL unless strict_tables            */
   jur_rec_t const *rec;         /* [entries] bracket records (entries i, i+1 and the slopes of [i, i+1]), or NULL      */
   long long const *pair_e0;     /* [ng*nd] first entry of every pair in ue (64 bits: a full-extent many-channel set --
                                    2378 channels x 3 gases x 40 x 30 x 304 = 2.6e9 entries -- is addressed as
@@ -86,9 +70,6 @@ typedef struct {
                                    no bracket of the look-up has zero width                                     */
   int fast_arith;               /* the look-up runs the strict-table arithmetic (JUR_ARITH_FAST on strict tables whose
                                    descriptors fit the LDS staging); 0: the reference's divisions operand for operand */
-  jur_item_t const *ega_items;  /* [ega_nitems] channel groups on a shared (p, T) grid, or NULL: one pair per workgroup */
-  int ega_nitems;
-  int ega_nch;                  /* channels of the largest item (1: nothing is shared)                           */
   /* atmosphere, compact SoA of atm_np points */
   int atm_np;
   int atm_sorted;               /* time stamps non-decreasing and z strictly monotone inside every slice */
@@ -136,9 +117,8 @@ void jurk_tune_combine(int group, int sync, long min_lanes);
 void jurk_tune_trace(int lanes);
 /* Curtis-Godson columns of the traced chunk: outputs [ray][gas][JUR_NLOS], indexed by ray id */
 int jurk_launch_cg(jur_view_t const *v, jur_chunk_t const *c, double *cgp, double *cgt, double *cgu, void *stream);
-/* bracket slopes of all n table entries (the last entry of a curve gets a value nobody reads) */
-int jurk_fill_slopes(jur_ue_t const *ue, jur_sl_t *sl, long long n, void *stream);
-int jurk_fill_records(jur_ue_t const *ue, jur_sl_t const *sl, jur_rec_t *rec, long long n, void *stream);   /* ue, sl: n + 1 entries */
+/* bracket records of all n table entries (the last entry of a curve gets slopes nobody reads) */
+int jurk_fill_records(jur_ue_t const *ue, jur_rec_t *rec, long long n, void *stream);   /* ue: n + 1 entries */
 /* order rays by their geometric tangent altitude: fills order[nr]; `tmp` is a
  * device scratch of jurk_sort_tmp_bytes(nr) bytes */
 long jurk_sort_tmp_bytes(long nr);
@@ -219,11 +199,6 @@ typedef struct {
   jur_ue_t *ue;
 } jur_flat_t;
 int  jur_tables_flatten(jur_tables_t const *tb, jur_flat_t *out);
-/* channel groups on a shared (p, T) grid: the class of every pair, then items of at most nch channels (malloc'ed;
- * pairs without a table are in no item) */
-int  jur_flat_grid_classes(jur_flat_t const *f, int ng, int nd, int *cls, unsigned char *all_curves);
-int  jur_group_items(int ng, int nd, int nch, int const *cls, unsigned char const *all_curves, long long const *pair_e0,
-                     jur_item_t **items, int *nitems, int *max_nch);
 void jur_flat_free(jur_flat_t *f);
 
 void jur_tables_cache_filename(char *out, size_t len, ctl_t const *ctl);

@@ -101,8 +101,8 @@ __device__ __forceinline__ double lip_finite(double x0, double y0, double x1, do
 // divisions is not needed to stay 1e3 .. 1e6 times inside that, and it is what 40 % of the look-up's fp64 work went
 // into.  On tables whose axes and curves are strictly increasing (no zero-width bracket) the look-up uses:
 //   lip_slope  the eight curve interpolations as y0 + (x - x0) s, one fused multiply-add, with the bracket's slope s
-//              read from jur_sl_t (jur_slopes_kernel: the correctly rounded quotient of the bracket's fp64 differences,
-//              formed once per model) where rounds 1 - 2 divided (8 instructions) and the first round-3 version
+//              read from the bracket's record (jur_records_kernel: the correctly rounded quotient of the bracket's fp64
+//              differences, formed once per model) where rounds 1 - 2 divided (8 instructions) and the first round-3 version
 //              multiplied with a Newton-refined v_rcp_f64 (4, and the difference y1 - y0): good to an ulp or two of
 //              the interpolated value;
 //   lip_mulr   the p and T blends as y0 + ((x - x0) (y1 - y0)) r with r = RN(1 / (x1 - x0)): two roundings instead
@@ -708,19 +708,12 @@ __device__ __forceinline__ void ld_pair(void const *__restrict__ ue, unsigned id
   a = ab.a; b = ab.b;
 }
 
-// slope of the bracket [idx, idx+1]: WHICH = 0 du/deps (get_u), 1 deps/du (get_eps)
-template <int WHICH>
-__device__ __forceinline__ double ld_slope(void const *__restrict__ sl, unsigned idx) {
-  return *reinterpret_cast<double const *>(static_cast<char const *>(sl) + (size_t)(idx * 16u + WHICH * 8u));
-}
-
-// The same loads where the lanes of a wavefront may all want the same element -- rays sorted by tangent altitude walk
-// through the same brackets of the same curves nearly in step.  Then the element is fetched ONCE through the scalar
-// data cache (s_load into SGPRs) instead of 64 times through the vector L1, whose address pipeline -- 16 accesses per
-// gather -- is what the kernel runs out of next to its vector ALUs (profiles/pmc_current.json: TCP stalled or busy
-// > 90 % of the time).  Any lane that differs sends the wavefront through the gather; the values are the same.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// Table loads where the lanes of a wavefront may all want the same element (ld_rec_u, ld_rec2 below) -- rays sorted by
+// tangent altitude walk through the same brackets of the same curves nearly in step.  Then the element is fetched ONCE
+// through the scalar data cache (s_load into SGPRs) instead of 64 times through the vector L1, whose address pipeline --
+// 16 accesses per gather -- is what the kernel runs out of next to its vector ALUs (profiles/pmc_current.json: TCP
+// stalled or busy > 90 % of the time).  Any lane that differs sends the wavefront through the gather; the values are
+// the same.
 template <class T>
 __device__ __forceinline__ T ld_scalar(void const *__restrict__ base, unsigned byte0) {   // byte0: wave-uniform offset
   typedef T const __attribute__((address_space(4))) *cptr;
@@ -732,36 +725,7 @@ __device__ __forceinline__ bool all_lanes_at(unsigned idx, unsigned &idx0) {
 }
 // (Serving the lanes that disagree in rounds of scalar loads -- a "waterfall", one round per distinct element -- was
 // measured too: 59.6 ms with two rounds, 47.8 with one round and the gather for the rest, against 40.0 for the plain
-// all-or-nothing test below; each round waits for its own scalar load inside divergent control flow.)
-__device__ __forceinline__ Ue ld_ue_u(void const *__restrict__ ue, unsigned idx) {
-  unsigned i0;
-  if (all_lanes_at(idx, i0)) { f32x2 const v = ld_scalar<f32x2>(ue, i0 * 8u); return Ue{v.x, v.y}; }
-  return ld_ue(ue, idx);
-}
-// the brackets of the two curves of a pressure level, requested together
-__device__ __forceinline__ void ld_pair2(void const *__restrict__ ue, unsigned ia, unsigned ib, Ue &a0, Ue &b0, Ue &a1, Ue &b1) {
-  unsigned fa, fb;
-  bool const ua = all_lanes_at(ia, fa), ub = all_lanes_at(ib, fb);
-  if (ua & ub) {
-    f32x4 const x = ld_scalar<f32x4>(ue, fa * 8u), y = ld_scalar<f32x4>(ue, fb * 8u);
-    a0 = Ue{x.x, x.y}; b0 = Ue{x.z, x.w}; a1 = Ue{y.x, y.y}; b1 = Ue{y.z, y.w};
-    return;
-  }
-  ld_pair(ue, ia, a0, b0);
-  ld_pair(ue, ib, a1, b1);
-}
-template <int WHICH>
-__device__ __forceinline__ void ld_slope2(void const *__restrict__ sl, unsigned ia, unsigned ib, double &s0, double &s1) {
-  unsigned fa, fb;
-  bool const ua = all_lanes_at(ia, fa), ub = all_lanes_at(ib, fb);
-  if (ua & ub) {
-    s0 = ld_scalar<double>(sl, fa * 16u + WHICH * 8u);
-    s1 = ld_scalar<double>(sl, fb * 16u + WHICH * 8u);
-    return;
-  }
-  s0 = ld_slope<WHICH>(sl, ia);
-  s1 = ld_slope<WHICH>(sl, ib);
-}
+// all-or-nothing test; each round waits for its own scalar load inside divergent control flow.)
 
 template <bool ON_EPS>
 __device__ __forceinline__ double ukey(Ue const &e) { return ON_EPS ? (double)e.eps : (double)e.u; }
@@ -833,62 +797,6 @@ __device__ __forceinline__ double cvt_keep(float f) {
   asm volatile("v_cvt_f64_f32 %0, %1" : "=v"(d) : "v"(f));
   return d;
 }
-template <bool ON_EPS>
-__device__ __forceinline__ double kkey(Ue const &e) { return cvt_keep(ON_EPS ? e.eps : e.u); }
-
-// seek_curve that works on, and hands back, the keys of its bracket as doubles: ka = key(e[i]), kb = key(e[i+1]) --
-// formed here unless the caller HAS them already (get_eps's search starts on the bracket whose column keys get_u's
-// interpolation has just converted).  Same probes, same bracket as seek_curve.  (The two far-move branches each end in
-// their own reload: with a shared tail the register allocator needs 91 VGPRs for jur_ega_kernel instead of 71 --
-// tests/test_abi_cpu.py watches that number.)
-template <bool ON_EPS, bool HAVE>
-__device__ __forceinline__ void seek_curve_keys(void const *__restrict__ ue, unsigned e0, int n, double x, int &i, Ue &a, Ue &b,
-                                                double &ka, double &kb) {
-  if (!HAVE) { ka = kkey<ON_EPS>(a); kb = kkey<ON_EPS>(b); }
-  bool const up = x >= kb, down = x < ka;
-  if (!(up | down)) return;
-  if (up) {
-    if (i >= n - 2) return;
-    Ue const c = ld_ue_u(ue, e0 + i + 2);
-    double const kc = kkey<ON_EPS>(c);
-    if (i + 2 >= n - 1 || kc > x) { ++i; a = b; b = c; ka = kb; kb = kc; return; }
-    int lo = i + 2, hi, step = 2;
-    for (;;) {
-      hi = lo + step;
-      if (hi >= n - 1) { hi = n - 1; break; }
-      if (ukey<ON_EPS>(ld_ue(ue, e0 + hi)) > x) break;
-      lo = hi;
-      step <<= 1;
-    }
-    while (hi > lo + 1) {
-      int const mid = (lo + hi) >> 1;
-      if (ukey<ON_EPS>(ld_ue(ue, e0 + mid)) > x) hi = mid; else lo = mid;
-    }
-    i = lo;
-    ld_pair(ue, e0 + i, a, b);
-    ka = kkey<ON_EPS>(a); kb = kkey<ON_EPS>(b);
-  } else {
-    if (i <= 0) return;
-    Ue const c = ld_ue_u(ue, e0 + i - 1);
-    double const kc = kkey<ON_EPS>(c);
-    if (i - 1 <= 0 || kc <= x) { --i; b = a; a = c; kb = ka; ka = kc; return; }
-    int hi = i - 1, lo, step = 2;
-    for (;;) {
-      lo = hi - step;
-      if (lo <= 0) { lo = 0; break; }
-      if (ukey<ON_EPS>(ld_ue(ue, e0 + lo)) <= x) break;
-      hi = lo;
-      step <<= 1;
-    }
-    while (hi > lo + 1) {
-      int const mid = (lo + hi) >> 1;
-      if (ukey<ON_EPS>(ld_ue(ue, e0 + mid)) > x) hi = mid; else lo = mid;
-    }
-    i = lo;
-    ld_pair(ue, e0 + i, a, b);
-    ka = kkey<ON_EPS>(a); kb = kkey<ON_EPS>(b);
-  }
-}
 
 // ---- bracket records (round 4) ---------------------------------------------------------------------------------
 // Everything the strict-table look-up needs of bracket [i, i+1] of a curve in ONE 32-byte record, indexed like the
@@ -931,8 +839,11 @@ template <bool ON_EPS>
 __device__ __forceinline__ double rec_key(void const *__restrict__ rec, unsigned idx) {
   return (double)*reinterpret_cast<float const *>(static_cast<char const *>(rec) + (size_t)(idx * 32u + (ON_EPS ? 4u : 0u)));
 }
-// seek_curve_keys on records: bracket i of curve [e0, e0 + n) with its record r and its keys ka, kb as doubles (formed
-// here unless the caller HAS them).  Same probes, same bracket.
+// seek_curve on records: bracket i of curve [e0, e0 + n) with its record r and its keys ka, kb as doubles -- formed
+// here unless the caller HAS them already (get_eps's search starts on the bracket whose column keys get_u's
+// interpolation has just converted).  Same probes, same bracket as seek_curve.  (The two far-move branches each end in
+// their own reload: with a shared tail the register allocator needs 90 VGPRs for jur_ega_kernel instead of 61 --
+// tests/test_abi_cpu.py watches that number.)
 template <bool ON_EPS, bool HAVE, bool SCALAR = true>      // SCALAR: try the scalar cache for the neighbouring record (lanes = neighbouring rays)
 __device__ __forceinline__ void seek_rec(void const *__restrict__ rec, unsigned e0, int n, double x, int &i, Rec &r, double &ka, double &kb) {
   if (!HAVE) { ka = cvt_keep(ON_EPS ? r.e0 : r.u0); kb = cvt_keep(ON_EPS ? r.e1 : r.u1); }
@@ -991,7 +902,6 @@ template <bool LDS>
 struct PairDesc {
   void const *lvb, *cvb;       // global arrays
   void const *ueb;             // first (u, eps) entry of the pair
-  void const *slb;             // ... and its bracket slopes (strict tables)
   unsigned l0;                 // first level of the pair
   unsigned kbase;              // first curve of the pair (LDS copy starts there)
   __device__ __forceinline__ Lvl lvl(int i) const {
@@ -1081,11 +991,10 @@ __device__ __forceinline__ double ega_eps_exact(jur_view_t const &v, jur_int2 co
 // RCPB is the strict-table arithmetic described at lip_slope; with PATH the function returns the NEW path
 // transmittance (1 - eps_t, or tau where the reference's look-up answers 1) instead of the segment's
 // transmittance (1 - eps_t) / tau -- what the kernels carry and write; the known-answer hook asks for the quotient.
-template <bool LDS, bool RCPB, bool PATH = false, bool REC = false>
+template <bool LDS, bool RCPB, bool PATH = false>
 __device__ __forceinline__ double ega_eps_warm(jur_view_t const &v, jur_int2 const pr, PairDesc<LDS> const &D, double tau, double t,
                                                double u, double p, unsigned &br, unsigned &ia, unsigned &ib) {
   static_assert(RCPB || !PATH, "only the strict-table arithmetic carries the path transmittance itself");
-  static_assert(RCPB || !REC, "bracket records hold the slopes of the strict-table arithmetic");
   double const one = PATH ? tau : 1.;          // the look-up's "no change" answer
   if (tau < 1e-9) return 0.;
   if (pr.a < 2) return one;
@@ -1126,11 +1035,13 @@ __device__ __forceinline__ double ega_eps_warm(jur_view_t const &v, jur_int2 con
     unsigned const e0[2] = {(unsigned)ca.e0, (unsigned)cb.e0};
     int const n[2] = {ca.nu, cb.nu};
     int i[2] = {(int)(packed & 0xffffu), (int)(packed >> 16)};
-    Ue a[2], b[2];
 #pragma unroll
     for (int k = 0; k < 2; k++) i[k] = min(i[k], n[k] - 2);
     double x[2], ec[2];
-    if constexpr (REC) {   // one record per bracket: keys and both slopes in one fetch
+    // get_u (jr_common.h:179-185): u at which the curve reaches eps; get_eps (:156-177): the curve's
+    // emissivity at that u plus the segment's column -- the column only grows, so the second search
+    // starts where the first ended
+    if constexpr (RCPB) {   // one record per bracket: keys and both slopes in one fetch
       Rec r[2];
       ld_rec2(D.recb, e0[0] + i[0], e0[1] + i[1], r[0], r[1]);      // both fetches in flight, then one curve after the other
       // (carrying the four table values of a record as doubles, converted where the record is fetched, costs four more
@@ -1146,34 +1057,10 @@ __device__ __forceinline__ double ega_eps_warm(jur_view_t const &v, jur_int2 con
         seek_rec<false, true>(D.recb, e0[k], n[k], x[k], i[k], r[k], ka, kb);
         ec[k] = c01_num(lip_slope(ka, (double)r[k].e0, r[k].de_du, x[k]));
       }
-    } else
-    if constexpr (RCPB) ld_pair2(ueb, e0[0] + i[0], e0[1] + i[1], a[0], b[0], a[1], b[1]);
-    else {
+    } else {
+      Ue a[2], b[2];
 #pragma unroll
       for (int k = 0; k < 2; k++) ld_pair(ueb, e0[k] + i[k], a[k], b[k]);
-    }
-    // get_u (jr_common.h:179-185): u at which the curve reaches eps; get_eps (:156-177): the curve's
-    // emissivity at that u plus the segment's column -- the column only grows, so the second search
-    // starts where the first ended
-    if constexpr (REC) {
-    } else if constexpr (RCPB) {  // the keys of each bracket as doubles from the search that tests them to the interpolation
-      double ka[2], kb[2];
-#pragma unroll
-      for (int k = 0; k < 2; k++) seek_curve_keys<true, false>(ueb, e0[k], n[k], eps, i[k], a[k], b[k], ka[k], kb[k]);
-      double s[2];
-      ld_slope2<0>(D.slb, e0[0] + i[0], e0[1] + i[1], s[0], s[1]);
-#pragma unroll
-      for (int k = 0; k < 2; k++) {
-        double const ya = kkey<false>(a[k]), yb = kkey<false>(b[k]);    // ... which serve get_eps's search as its keys
-        x[k] = lip_slope(ka[k], ya, s[k], eps) + u;
-        ka[k] = ya; kb[k] = yb;
-      }
-#pragma unroll
-      for (int k = 0; k < 2; k++) seek_curve_keys<false, true>(ueb, e0[k], n[k], x[k], i[k], a[k], b[k], ka[k], kb[k]);
-      ld_slope2<1>(D.slb, e0[0] + i[0], e0[1] + i[1], s[0], s[1]);
-#pragma unroll
-      for (int k = 0; k < 2; k++) ec[k] = c01_num(lip_slope(ka[k], (double)a[k].eps, s[k], x[k]));
-    } else {
 #pragma unroll
       for (int k = 0; k < 2; k++) seek_curve<true>(ueb, e0[k], n[k], eps, i[k], a[k], b[k]);
 #pragma unroll
@@ -1242,31 +1129,17 @@ __device__ __forceinline__ double ega_eps_warm_quad(jur_view_t const &v, jur_int
   unsigned const e0 = (unsigned)mine.e0;
   int const n = mine.nu;
   int i = min((int)ix, n - 2);
-  Ue a, b;
-  if (!(FAST && D.recb)) ld_pair(ueb, e0 + i, a, b);
   double const eps = 1 - tau;
-  if constexpr (FAST) {
+  if constexpr (FAST) {   // bracket records (round 4): one fetch for the curve's keys and both slopes -- the same doubles
     bool const nan_in = (tau != tau || t != t || u != u || p != p);   // as ega_eps_warm: min/max clamps below
-    if (D.recb) {   // bracket records (round 4): one fetch for the curve's keys and both slopes -- the same doubles
-      Rec r = ld_rec(D.recb, e0 + i);
-      double ka, kb;
-      seek_rec<true, false, false>(D.recb, e0, n, eps, i, r, ka, kb);
-      double const ya = (double)r.u0;
-      double const x = lip_slope(ka, ya, r.du_de, eps) + u;
-      ka = ya; kb = (double)r.u1;
-      seek_rec<false, true, false>(D.recb, e0, n, x, i, r, ka, kb);
-      double const ec = c01_num(lip_slope(ka, (double)r.e0, r.de_du, x));
-      ix = (unsigned)i;
-      double const ec0 = quad_bcast<0>(ec), ec1 = quad_bcast<1>(ec), ec2 = quad_bcast<2>(ec), ec3 = quad_bcast<3>(ec);
-      double const eps_p0 = c01_num(lip_mulr(c00.t, ec0, ec1, t, 1. / (c01_.t - c00.t)));
-      double const eps_p1 = c01_num(lip_mulr(c10.t, ec2, ec3, t, 1. / (c11.t - c10.t)));
-      double const tau_new = 1. - c01_num(lip_mulr(l0.p, eps_p0, eps_p1, p, 1. / (l1.p - l0.p)));
-      return nan_in ? __builtin_nan("") : tau_new;
-    }
-    seek_curve<true>(ueb, e0, n, eps, i, a, b);
-    double const x = lip_slope((double)a.eps, (double)a.u, ld_slope<0>(D.slb, e0 + i), eps) + u;
-    seek_curve<false>(ueb, e0, n, x, i, a, b);
-    double const ec = c01_num(lip_slope((double)a.u, (double)a.eps, ld_slope<1>(D.slb, e0 + i), x));
+    Rec r = ld_rec(D.recb, e0 + i);
+    double ka, kb;
+    seek_rec<true, false, false>(D.recb, e0, n, eps, i, r, ka, kb);
+    double const ya = (double)r.u0;
+    double const x = lip_slope(ka, ya, r.du_de, eps) + u;
+    ka = ya; kb = (double)r.u1;
+    seek_rec<false, true, false>(D.recb, e0, n, x, i, r, ka, kb);
+    double const ec = c01_num(lip_slope(ka, (double)r.e0, r.de_du, x));
     ix = (unsigned)i;
     double const ec0 = quad_bcast<0>(ec), ec1 = quad_bcast<1>(ec), ec2 = quad_bcast<2>(ec), ec3 = quad_bcast<3>(ec);
     double const eps_p0 = c01_num(lip_mulr(c00.t, ec0, ec1, t, 1. / (c01_.t - c00.t)));
@@ -1274,6 +1147,8 @@ __device__ __forceinline__ double ega_eps_warm_quad(jur_view_t const &v, jur_int
     double const tau_new = 1. - c01_num(lip_mulr(l0.p, eps_p0, eps_p1, p, 1. / (l1.p - l0.p)));
     return nan_in ? __builtin_nan("") : tau_new;
   } else {
+    Ue a, b;
+    ld_pair(ueb, e0 + i, a, b);
     seek_curve<true>(ueb, e0, n, eps, i, a, b);
     double const x = lip((double)a.eps, (double)a.u, (double)b.eps, (double)b.u, eps) + u;
     seek_curve<false>(ueb, e0, n, x, i, a, b);
@@ -1470,8 +1345,8 @@ __device__ __forceinline__ void stage_pair(jur_view_t const &v, jur_int2 const p
 #ifndef JUR_REC_WAVES
 #define JUR_REC_WAVES 7
 #endif
-template <bool WARM, bool LDS, bool RCPB, bool REC = false>
-__global__ __launch_bounds__(256, REC ? JUR_REC_WAVES : 5) void jur_ega_kernel(jur_view_t v, jur_chunk_t c, int nrb) {
+template <bool WARM, bool LDS, bool RCPB>
+__global__ __launch_bounds__(256, RCPB ? JUR_REC_WAVES : 5) void jur_ega_kernel(jur_view_t v, jur_chunk_t c, int nrb) {
   static_assert(WARM || !RCPB, "reciprocal widths need strictly increasing axes");
   int const npair = v.nd * v.ng;
   BlockItem const bi = xcd_block_item((int)blockIdx.x, nrb, npair);
@@ -1482,8 +1357,8 @@ __global__ __launch_bounds__(256, REC ? JUR_REC_WAVES : 5) void jur_ega_kernel(j
   int const pair_idx = g * v.nd + d;
   jur_int2 const pd = v.pair[pair_idx];
   if (pd.a < 2) return;                          // no table: transmittance 1, the combine kernel knows
-  PairDesc<LDS> D{v.lvl, v.crv, v.ue + v.pair_e0[pair_idx], v.sl + v.pair_e0[pair_idx], (unsigned)pd.b, 0u, 0u, 0u};
-  if constexpr (REC) D.recb = v.rec + v.pair_e0[pair_idx];
+  PairDesc<LDS> D{v.lvl, v.crv, v.ue + v.pair_e0[pair_idx], (unsigned)pd.b, 0u, 0u, 0u};
+  if constexpr (RCPB) D.recb = v.rec + v.pair_e0[pair_idx];
   stage_pair<LDS, RCPB>(v, pd, D);
   if (r >= c.n) return;
   // the workspaces are addressed as (wave-uniform pointer into this wavefront's tile) + lane offset
@@ -1516,181 +1391,10 @@ __global__ __launch_bounds__(256, REC ? JUR_REC_WAVES : 5) void jur_ega_kernel(j
     } else { p = ldg<double>(los_p + o, lane); t = ldg<double>(los_t + o, lane); }
     double const u = ldg<double>(los_u + o, lane);
     // what is carried and written is the gas's transmittance of the path up to and including this segment
-    if constexpr (RCPB) tau_path = ega_eps_warm<LDS, true, true, REC>(v, pd, D, tau_path, t, u, p, br, ia, ib);
+    if constexpr (RCPB) tau_path = ega_eps_warm<LDS, true, true>(v, pd, D, tau_path, t, u, p, br, ia, ib);
     else if constexpr (WARM) tau_path *= ega_eps_warm<LDS, false>(v, pd, D, tau_path, t, u, p, br, ia, ib);
     else tau_path *= ega_eps_exact<LDS>(v, pd, D, tau_path, t, u, p);
     st_stream(out + (size_t)ip * Re, lane, tau_path);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// jur_ega_group_kernel (round 4): one lane per (ray, gas), walking the channels of an ITEM -- up to JUR_EGA_NCH
-// channels whose tables of this gas stand on the same (p, T) grid (jur_flat_group_items) -- inside the segment loop.
-// What depends on the ray, the gas and the grid only is done once per segment and item instead of once per
-// (channel, gas) pair: the three LOS loads (p, T, u[g]), the pressure bracket, the two temperature brackets
-// (jr_common.h:241-246 -- the brackets do not depend on the curve), the NaN test of the inputs, the differences
-// p - p0, T - T0 of the three blends.  Per channel there remain the four curve walks with their blends: the same
-// operations on the same operands in the same order as ega_eps_warm<.., true, true>, hence the same doubles (the
-// test suite compares the two kernels bit for bit).
-// LDS per workgroup: the grid (levels {p, nt, first curve RELATIVE to the pair}, curve temperatures, reciprocal
-// bracket widths), per channel the curves' {nu, first entry}, and the chain state {path transmittance, curve
-// positions} of every (lane, channel): the channel loop is rolled, its state cannot live in registers.
-// Strict tables only (the arithmetic of lip_slope / lip_mulr); everything else keeps jur_ega_kernel.
-// ---------------------------------------------------------------------------------------
-
-// LDS of a workgroup of `block` lanes: grid {levels, curve temperatures, reciprocal T widths, reciprocal p widths},
-// first entries of the curves per channel (4 B each: a curve's length is the distance to the next one's start),
-// chain state [channel][lane] as two 8-byte arrays
-__host__ __device__ inline size_t ega_group_lds_bytes(int max_pair_curves, int nch, int block) {
-  size_t const capC = (size_t)max_pair_curves + 4;
-  return 16 * (size_t)JUR_TBLNP + 8 * capC * 2 + 8 * (size_t)JUR_TBLNP + ((4 * capC * nch + 15) & ~(size_t)15) + 16 * (size_t)block * nch;
-}
-
-template <int WAVES>
-__global__ __launch_bounds__(1024, WAVES) void jur_ega_group_kernel(jur_view_t v, jur_chunk_t c, int nrb) {
-  int const nitems = v.ega_nitems;
-  int const BLOCK = (int)blockDim.x;
-  BlockItem const bi = xcd_block_item((int)blockIdx.x, nrb, nitems);
-  int const rb = bi.rb, it = bi.item;                                       // ray block, item: uniform
-  if (rb < 0) return;
-  jur_item_t const *const item = v.ega_items + it;
-  int const g = item->g, nch = item->nch;
-  bool const all_curves = item->flags & 1;         // every curve of the item's tables has >= 2 entries (uniform)
-  int const capC = v.max_pair_curves + 4;
-  Lvl *const sL = reinterpret_cast<Lvl *>(jur_lds);
-  double *const sT = reinterpret_cast<double *>(jur_lds + 16 * JUR_TBLNP), *const sRT = sT + capC, *const sRP = sRT + capC;
-  int *const sE0 = reinterpret_cast<int *>(sRP + JUR_TBLNP);
-  // chain state, [channel][lane] with 8-byte elements: conflict-free 64-bit LDS accesses
-  double *const sTau = reinterpret_cast<double *>(jur_lds + 16 * JUR_TBLNP + 16 * (size_t)capC + 8 * JUR_TBLNP +
-                                                  ((4 * (size_t)capC * v.ega_nch + 15) & ~(size_t)15));
-  unsigned *const sPos = reinterpret_cast<unsigned *>(sTau + (size_t)v.ega_nch * BLOCK);   // [level 0 / 1][channel][lane]
-  jur_int2 const pd0 = v.pair[g * v.nd + item->d[0]];
-  int const npl = pd0.a;                           // >= 2: pairs without a table are in no item
-  {
-    Lvl const *const gl = reinterpret_cast<Lvl const *>(v.lvl) + pd0.b;
-    int const kb0 = gl[0].c0;
-    Lvl const last = gl[npl - 1];
-    int const ncrv = last.c0 + last.nt - kb0;
-    Crv const *const gc = reinterpret_cast<Crv const *>(v.crv) + kb0;
-    for (int i = threadIdx.x; i < npl; i += BLOCK) { Lvl l = gl[i]; l.c0 -= kb0; sL[i] = l; }
-    for (int i = threadIdx.x; i < ncrv + 2; i += BLOCK) sT[i] = i < ncrv ? gc[i].t : 0.;
-    // reciprocal widths exactly as stage_pair forms them (entries that straddle two axes are never used)
-    for (int i = threadIdx.x; i + 1 < npl; i += BLOCK) sRP[i] = 1. / (gl[i + 1].p - gl[i].p);
-    for (int i = threadIdx.x; i + 1 < ncrv; i += BLOCK) sRT[i] = 1. / (gc[i + 1].t - gc[i].t);
-    for (int k = 0; k < nch; k++) {
-      jur_int2 const pdk = v.pair[g * v.nd + item->d[k]];
-      Crv const *const gck = reinterpret_cast<Crv const *>(v.crv) + reinterpret_cast<Lvl const *>(v.lvl)[pdk.b].c0;
-      int const end = gck[ncrv - 1].e0 + gck[ncrv - 1].nu;            // the curves of a pair follow each other in ue
-      for (int i = threadIdx.x; i < ncrv + 4; i += BLOCK) sE0[(size_t)k * capC + i] = i < ncrv ? gck[i].e0 : end;
-    }
-    __syncthreads();
-  }
-  int const r = rb * BLOCK + threadIdx.x;
-  if (r >= c.n) return;
-  int const nfield = JUR_F_K + v.nw + v.ng;
-  int const tile = __builtin_amdgcn_readfirstlane(r >> 6);
-  unsigned const lane = (unsigned)(r & 63);
-  size_t const R = (size_t)nfield * 64;
-  double const *const los_tile = c.los + (size_t)tile * los_tile_doubles(nfield);
-  double const *const los_p = los_tile + JUR_F_P * 64, *const los_t = los_tile + JUR_F_T * 64,
-               *const los_u = los_tile + (size_t)(JUR_F_K + v.nw + g) * 64;
-  size_t const Re = (size_t)v.nd * v.ng * 64;
-  double *const out_tile = c.eps + eps_tile_point0(c, tile) * Re;
-  int const np = c.np[r];
-  double *const mytau = sTau + threadIdx.x;
-  unsigned *const mypos = sPos + threadIdx.x;
-  int const HS = v.ega_nch * BLOCK;                 // from a chain's positions on level l0 to those on l1
-  for (int k = 0; k < nch; k++) { mytau[k * BLOCK] = 1.0; mypos[k * BLOCK] = 0u; mypos[HS + k * BLOCK] = 0u; }
-  // the item's fields inside the segment loop come through the scalar cache (constant address space: a plain load
-  // behind the loop's stores is a vector load of a uniform value)
-  unsigned const item_byte = (unsigned)it * (unsigned)sizeof(jur_item_t);
-  unsigned br = 0;
-
-  for (int ip = 0; ip < np; ++ip) {
-    size_t const o = (size_t)ip * R;
-    // (no request one segment ahead as in jur_ega_kernel: the row's latency is spread over the item's channels)
-    double const p = ldg<double>(los_p + o, lane), t = ldg<double>(los_t + o, lane), u = ldg<double>(los_u + o, lane);
-    // ---- once per segment: the brackets of the shared grid
-    int ipr = min((int)(br & 0xffu), npl - 2);
-    Lvl l0 = sL[ipr], l1 = sL[ipr + 1];
-    if ((p < l0.p) | (p >= l1.p)) {
-      while (p < l0.p && ipr > 0) { --ipr; l1 = l0; l0 = sL[ipr]; }
-      while (p >= l1.p && ipr < npl - 2) { ++ipr; l0 = l1; l1 = sL[ipr + 1]; }
-    }
-    bool const valid = (l0.nt >= 2) & (l1.nt >= 2);                 // else the look-up answers "no change"
-    int it0 = max(min((int)((br >> 8) & 0xffu), l0.nt - 2), 0), it1 = max(min((int)((br >> 16) & 0xffu), l1.nt - 2), 0);
-    double T00 = sT[l0.c0 + it0], T01 = sT[l0.c0 + it0 + 1], T10 = sT[l1.c0 + it1], T11 = sT[l1.c0 + it1 + 1];
-    if (valid && ((t < T00) | (t >= T01) | (t < T10) | (t >= T11))) {
-      while (t < T00 && it0 > 0) { --it0; T01 = T00; T00 = sT[l0.c0 + it0]; }
-      while (t >= T01 && it0 < l0.nt - 2) { ++it0; T00 = T01; T01 = sT[l0.c0 + it0 + 1]; }
-      while (t < T10 && it1 > 0) { --it1; T11 = T10; T10 = sT[l1.c0 + it1]; }
-      while (t >= T11 && it1 < l1.nt - 2) { ++it1; T10 = T11; T11 = sT[l1.c0 + it1 + 1]; }
-    }
-    br = (unsigned)ipr | ((unsigned)it0 << 8) | ((unsigned)it1 << 16);
-    int const kc0 = l0.c0 + it0, kc1 = l1.c0 + it1;
-    double const dp = p - l0.p, dt0 = t - T00, dt1 = t - T10;      // (x - x0) of the three blends
-    bool const nan_in = (t != t) | (u != u) | (p != p);
-    // ---- per channel: the four curve walks and the blends
-#pragma unroll 1
-    for (int k = 0; k < nch; k++) {
-      double const tau = mytau[k * BLOCK];
-      unsigned *const pos = mypos + k * BLOCK;       // [0]: the chain's positions in level l0's curve pair, [HS]: l1's
-      unsigned const ku = (unsigned)__builtin_amdgcn_readfirstlane(k);
-      double tau_new = tau;
-      if (tau < 1e-9) tau_new = 0.;
-      else if (valid) {
-        int const *const ne = sE0 + (size_t)k * capC;
-        bool curves_ok = true;
-        if (!all_curves) {
-          int const a0 = ne[kc0], a1 = ne[kc0 + 1], a2 = ne[kc0 + 2], b0 = ne[kc1], b1 = ne[kc1 + 1], b2 = ne[kc1 + 2];
-          curves_ok = (a1 - a0 >= 2) & (a2 - a1 >= 2) & (b1 - b0 >= 2) & (b2 - b1 >= 2);
-        }
-        if (curves_ok) {
-          if (nan_in || tau != tau) tau_new = __builtin_nan("");
-          else {
-            long long const pe0 = ld_scalar<long long>(v.ega_items, item_byte + (unsigned)offsetof(jur_item_t, e0) + ku * 8u);
-            void const *const recb = v.rec + pe0;
-            double const eps = 1 - tau;
-            double eps_p0 = 0, eps_p1 = 0;
-#pragma unroll 1
-            for (int h = 0; h < 2; h++) {
-              int const kc = h ? kc1 : kc0;
-              int const ea = ne[kc], eb = ne[kc + 1], ec_ = ne[kc + 2];
-              unsigned const packed = pos[h ? HS : 0];
-              unsigned const e0[2] = {(unsigned)ea, (unsigned)eb};
-              int const n[2] = {eb - ea, ec_ - eb};
-              int i[2] = {(int)(packed & 0xffffu), (int)(packed >> 16)};
-#pragma unroll
-              for (int q = 0; q < 2; q++) i[q] = min(i[q], n[q] - 2);
-              double x[2], ec[2];
-              {   // bracket records (one fetch per curve), as jur_ega_kernel
-                Rec r[2];
-                ld_rec2(recb, e0[0] + i[0], e0[1] + i[1], r[0], r[1]);
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                  double ka, kb;
-                  seek_rec<true, false>(recb, e0[q], n[q], eps, i[q], r[q], ka, kb);
-                  double const ya = cvt_keep(r[q].u0);
-                  x[q] = lip_slope(ka, ya, r[q].du_de, eps) + u;
-                  ka = ya; kb = cvt_keep(r[q].u1);
-                  seek_rec<false, true>(recb, e0[q], n[q], x[q], i[q], r[q], ka, kb);
-                  ec[q] = c01_num(lip_slope(ka, (double)r[q].e0, r[q].de_du, x[q]));
-                }
-              }
-              pos[h ? HS : 0] = (unsigned)i[0] | ((unsigned)i[1] << 16);
-              // lip_mulr(T0, ec0, ec1, t, rt) with its (t - T0) formed above
-              double const e = c01_num(ec[0] + ((h ? dt1 : dt0) * (ec[1] - ec[0])) * sRT[kc]);
-              if (h) eps_p1 = e; else eps_p0 = e;
-            }
-            tau_new = 1. - c01_num(eps_p0 + (dp * (eps_p1 - eps_p0)) * sRP[br & 0xffu]);
-          }
-        }
-      }
-      mytau[k * BLOCK] = tau_new;
-      int const dk = ld_scalar<int>(v.ega_items, item_byte + (unsigned)offsetof(jur_item_t, d) + ku * 4u);
-      double *const out = out_tile + (size_t)(dk * v.ng + g) * 64;
-      st_stream(out + (size_t)ip * Re, lane, tau_new);
-    }
   }
 }
 
@@ -2165,7 +1869,7 @@ __global__ __launch_bounds__(1024) void jur_pencil_kernel(jur_view_t v, jur_chun
     // chain, one corner curve each ----
     constexpr int CS = (QUAD && WARM) ? 2 : 0;                  // lanes per chain = 1 << CS
     int const w = wave - 1, nl = (NE * 64) >> CS, me = (w * 64 + lane) >> CS;
-    PairDesc<false> D{v.lvl, v.crv, nullptr, nullptr, 0u, 0u, 0u, 0u};
+    PairDesc<false> D{v.lvl, v.crv, nullptr, 0u, 0u, 0u, 0u};
     for (int ip = 0;; ++ip) {
       int const cnt = wait_point(&ctl, ip);
       if (cnt <= ip) break;
@@ -2181,8 +1885,7 @@ __global__ __launch_bounds__(1024) void jur_pencil_kernel(jur_view_t v, jur_chun
         if (pd.a < 2) continue;                                    // no table: the combine role knows
         D.l0 = (unsigned)pd.b;
         D.ueb = v.ue + v.pair_e0[g * nd + d];
-        D.slb = v.sl + v.pair_e0[g * nd + d];      // only read by the strict-table arithmetic, where v.sl is set
-        D.recb = (v.fast_arith && v.rec) ? static_cast<void const *>(v.rec + v.pair_e0[g * nd + d]) : nullptr;
+        D.recb = v.fast_arith ? static_cast<void const *>(v.rec + v.pair_e0[g * nd + d]) : nullptr;
         double const p = slot[JUR_F_P * RB + r], t = slot[JUR_F_T * RB + r], u = slot[(JUR_F_K + v.nw + g) * RB + r];
         double const tau_path = st_tau[e];
         double tau_new;                                            // the gas's path transmittance after this segment
@@ -2193,8 +1896,7 @@ __global__ __launch_bounds__(1024) void jur_pencil_kernel(jur_view_t v, jur_chun
           st_br[e] = br; st_ix[4 * e + (lane & 3)] = ix;
         } else if constexpr (WARM) {
           unsigned br = st_br[e], ia = st_ix[4 * e], ib = st_ix[4 * e + 1];
-          if (v.fast_arith && v.rec) tau_new = ega_eps_warm<false, true, true, true>(v, pd, D, tau_path, t, u, p, br, ia, ib);
-          else if (v.fast_arith) tau_new = ega_eps_warm<false, true, true>(v, pd, D, tau_path, t, u, p, br, ia, ib);
+          if (v.fast_arith) tau_new = ega_eps_warm<false, true, true>(v, pd, D, tau_path, t, u, p, br, ia, ib);
           else tau_new = tau_path * ega_eps_warm<false, false>(v, pd, D, tau_path, t, u, p, br, ia, ib);
           st_br[e] = br; st_ix[4 * e] = ia; st_ix[4 * e + 1] = ib;
         } else tau_new = tau_path * ega_eps_exact<false>(v, pd, D, tau_path, t, u, p);
@@ -2309,21 +2011,14 @@ __global__ __launch_bounds__(256) void jur_cg_kernel(jur_view_t v, jur_chunk_t c
 // optionally grouped by the atmosphere slice the ray uses (neighbouring lanes then walk through
 // the same profile, i.e. the same table brackets)
 // ---------------------------------------------------------------------------------------
-// Bracket slopes of the emissivity curves, once per model: entry j gets the slopes of [entry j, entry j+1] in both
-// directions, formed from the fp32 entries with fp64 differences and IEEE divisions.  The last entry of a curve pairs
-// with the first of the next one; the look-up never reads that slot (its bracket index ends at nu - 2).
-// bracket records from the entries and their slopes (entry i and i + 1, slopes of bracket [i, i+1]); once per model
-__global__ __launch_bounds__(256) void jur_records_kernel(long long n, jur_ue_t const *__restrict__ ue, jur_sl_t const *__restrict__ sl,
-                                                          jur_rec_t *__restrict__ rec) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    rec[i] = jur_rec_t{ue[i].u, ue[i].eps, ue[i + 1].u, ue[i + 1].eps, sl[i].du_de, sl[i].de_du};
-}
-
-__global__ __launch_bounds__(256) void jur_slopes_kernel(long long n, jur_ue_t const *__restrict__ ue, jur_sl_t *__restrict__ sl) {
-  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j + 1 < n; j += (long long)gridDim.x * blockDim.x) {
-    double const du = (double)ue[j + 1].u - (double)ue[j].u, de = (double)ue[j + 1].eps - (double)ue[j].eps;
-    sl[j].du_de = du / de;
-    sl[j].de_du = de / du;
+// Bracket records of the emissivity curves, once per model: record i holds entries i and i + 1 and the slopes of
+// [entry i, entry i+1] in both directions, formed from the fp32 entries with fp64 differences and IEEE divisions.  The
+// last entry of a curve pairs with the first of the next one; the look-up never reads that record (its bracket index
+// ends at nu - 2).
+__global__ __launch_bounds__(256) void jur_records_kernel(long long n, jur_ue_t const *__restrict__ ue, jur_rec_t *__restrict__ rec) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    double const du = (double)ue[i + 1].u - (double)ue[i].u, de = (double)ue[i + 1].eps - (double)ue[i].eps;
+    rec[i] = jur_rec_t{ue[i].u, ue[i].eps, ue[i + 1].u, ue[i + 1].eps, du / de, de / du};
   }
 }
 
@@ -2505,17 +2200,17 @@ __global__ __launch_bounds__(128) void jur_intpol_kernel(IntpolArgs a) {
 // chain != 0: ONE lane walks the n inputs in order and carries the warm-start state (br, ia, ib) from element
 // to element as jur_ega_kernel carries it from segment to segment -- the result of a look-up must not depend on
 // where the previous one left the brackets.
-template <bool WARM, bool LDS, bool RCPB, bool REC = false>
+template <bool WARM, bool LDS, bool RCPB>
 __global__ __launch_bounds__(256) void jur_kat_ega_kernel(jur_view_t v, int g, int d, long n, double const *__restrict__ tau,
                                                           double const *__restrict__ t, double const *__restrict__ u,
                                                           double const *__restrict__ p, int chain, double *__restrict__ out) {
   jur_int2 const pd = v.pair[g * v.nd + d];
-  PairDesc<LDS> D{v.lvl, v.crv, v.ue + v.pair_e0[g * v.nd + d], v.sl + v.pair_e0[g * v.nd + d], (unsigned)pd.b, 0u, 0u, 0u};
-  if constexpr (REC) D.recb = v.rec + v.pair_e0[g * v.nd + d];
+  PairDesc<LDS> D{v.lvl, v.crv, v.ue + v.pair_e0[g * v.nd + d], (unsigned)pd.b, 0u, 0u, 0u};
+  if constexpr (RCPB) D.recb = v.rec + v.pair_e0[g * v.nd + d];
   if (pd.a >= 2) stage_pair<LDS, RCPB>(v, pd, D);       // uniform branch; stage_pair ends in a barrier
   unsigned br = 0, ia = 0, ib = 0;
   auto one = [&](long i) {
-    if constexpr (WARM) out[i] = ega_eps_warm<LDS, RCPB, false, REC>(v, pd, D, tau[i], t[i], u[i], p[i], br, ia, ib);
+    if constexpr (WARM) out[i] = ega_eps_warm<LDS, RCPB>(v, pd, D, tau[i], t[i], u[i], p[i], br, ia, ib);
     else out[i] = ega_eps_exact<LDS>(v, pd, D, tau[i], t[i], u[i], p[i]);
   };
   if (chain) {
@@ -2600,38 +2295,8 @@ static int raise_lds_limit(std::mutex &mu, unsigned long long &raised, void cons
   return 0;
 }
 
-// Channel groups on a shared (p, T) grid (jur_ega_group_kernel) when the model has any and its tables are strictly
-// increasing; workgroup size from the LDS the chain states need (JUR_EGA_BLOCK overrides; JUR_EGA_GROUP=0 switches the
-// kernel off).  Returns -1 when the call is not for it.
-static int launch_ega_group(jur_view_t const *v, jur_chunk_t const *c, hipStream_t s) {
-  static int const env_group = getenv("JUR_EGA_GROUP") ? atoi(getenv("JUR_EGA_GROUP")) : -1;      // A/B switches, read once
-  static int const env_block = getenv("JUR_EGA_BLOCK") ? atoi(getenv("JUR_EGA_BLOCK")) : 0;
-  static int const env_waves = getenv("JUR_EGA_WAVES") ? atoi(getenv("JUR_EGA_WAVES")) : 0;
-  if (!v->ega_items || v->ega_nitems <= 0 || v->ega_nch < 2 || !v->fast_arith || !v->rec || env_group == 0 || getenv("JUR_EGA_NO_LDS")) return -1;
-  int const block = (env_block >= 64 && env_block <= 1024 && env_block % 64 == 0) ? env_block : 256;
-  int const waves = env_waves >= 6 && env_waves <= 8 ? env_waves : 7;
-  size_t const lds = ega_group_lds_bytes(v->max_pair_curves, v->ega_nch, block);
-  if (lds > 128 * 1024) return -1;
-  static std::mutex mu;
-  static unsigned long long raised = 0;
-  void const *const funcs[] = {reinterpret_cast<void const *>(&jur_ega_group_kernel<6>), reinterpret_cast<void const *>(&jur_ega_group_kernel<7>),
-                               reinterpret_cast<void const *>(&jur_ega_group_kernel<8>)};
-  int const e = raise_lds_limit(mu, raised, funcs, 3, lds > 64 * 1024);
-  if (e) return e;
-  int const nrb = (c->n + block - 1) / block;
-  unsigned const grid = xcd_grid(nrb, v->ega_nitems);
-  if (waves == 6) hipLaunchKernelGGL((jur_ega_group_kernel<6>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
-  else if (waves == 7) hipLaunchKernelGGL((jur_ega_group_kernel<7>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
-  else hipLaunchKernelGGL((jur_ega_group_kernel<8>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
-  return (int)hipGetLastError();
-}
-
 extern "C" int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, void *stream) {
   if (c->n <= 0 || v->ng <= 0) return 0;
-  {
-    int const e = launch_ega_group(v, c, (hipStream_t)stream);
-    if (e >= 0) return e;
-  }
   int const block = 256;   // (128 rays per workgroup: 34.6 against 33.7 ms; 64: the staged descriptors limit the occupancy, 45 ms)
   int const nrb = (c->n + block - 1) / block, npair = v->nd * v->ng;
   unsigned const grid = xcd_grid(nrb, npair);
@@ -2639,11 +2304,10 @@ extern "C" int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, void *
   // LDS copy of one pair's descriptors per workgroup: 16 B x (levels + curves of the largest pair)
   // (+ 8 B x the same counts for the reciprocal bracket widths of strictly increasing tables)
   size_t const lds = (sizeof(jur_lvl_t) + 8) * JUR_TBLNP + (sizeof(jur_crv_t) + 8) * (size_t)v->max_pair_curves;
-  bool const use_lds = v->max_pair_curves > 0 && lds <= 48 * 1024 && !getenv("JUR_EGA_NO_LDS");
+  bool const use_lds = v->max_pair_curves > 0 && lds <= 48 * 1024;
   bool const rcpb = use_lds && v->fast_arith;
   if (v->sorted_tables) {
-    if (rcpb && v->rec) hipLaunchKernelGGL((jur_ega_kernel<true, true, true, true>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
-    else if (rcpb) hipLaunchKernelGGL((jur_ega_kernel<true, true, true>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
+    if (rcpb) hipLaunchKernelGGL((jur_ega_kernel<true, true, true>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
     else if (use_lds) hipLaunchKernelGGL((jur_ega_kernel<true, true, false>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
     else hipLaunchKernelGGL((jur_ega_kernel<true, false, false>), dim3(grid), dim3(block), 0, s, *v, *c, nrb);
   } else {
@@ -2783,8 +2447,7 @@ extern "C" int jurk_kat_ega(jur_view_t const *v, int g, int d, long n, double co
     else hipLaunchKernelGGL((jur_kat_ega_kernel<false, false, false>), grid, block, 0, s, *v, g, d, n, tau, t, u, p, chain, out);
   } else if (mode == 1) hipLaunchKernelGGL((jur_kat_ega_kernel<true, false, false>), grid, block, 0, s, *v, g, d, n, tau, t, u, p, chain, out);
   else if (mode == 2) hipLaunchKernelGGL((jur_kat_ega_kernel<true, true, false>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);
-  else if (v->rec) hipLaunchKernelGGL((jur_kat_ega_kernel<true, true, true, true>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);   // what the batched kernel runs
-  else hipLaunchKernelGGL((jur_kat_ega_kernel<true, true, true>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);
+  else hipLaunchKernelGGL((jur_kat_ega_kernel<true, true, true>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);   // what the batched kernel runs
   return (int)hipGetLastError();
 }
 
@@ -2853,15 +2516,9 @@ extern "C" int jurk_launch_pencil(jur_view_t const *v, jur_chunk_t const *c, int
   return (int)hipGetLastError();
 }
 
-extern "C" int jurk_fill_records(jur_ue_t const *ue, jur_sl_t const *sl, jur_rec_t *rec, long long n, void *stream) {
+extern "C" int jurk_fill_records(jur_ue_t const *ue, jur_rec_t *rec, long long n, void *stream) {
   long long const nb = (n + 255) / 256;
-  hipLaunchKernelGGL(jur_records_kernel, dim3((unsigned)(nb < 65536 ? (nb > 0 ? nb : 1) : 65536)), dim3(256), 0, (hipStream_t)stream, n, ue, sl, rec);
-  return (int)hipGetLastError();
-}
-
-extern "C" int jurk_fill_slopes(jur_ue_t const *ue, jur_sl_t *sl, long long n, void *stream) {
-  long long const nb = (n + 255) / 256;
-  hipLaunchKernelGGL(jur_slopes_kernel, dim3((unsigned)(nb < 65536 ? (nb > 0 ? nb : 1) : 65536)), dim3(256), 0, (hipStream_t)stream, n, ue, sl);
+  hipLaunchKernelGGL(jur_records_kernel, dim3((unsigned)(nb < 65536 ? (nb > 0 ? nb : 1) : 65536)), dim3(256), 0, (hipStream_t)stream, n, ue, rec);
   return (int)hipGetLastError();
 }
 

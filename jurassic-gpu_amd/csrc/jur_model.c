@@ -32,11 +32,8 @@ struct jur_model {
   jur_view_t view;              /* device pointers                               */
   long table_bytes;
   /* device allocations owned by the model */
-  void *d_chan, *d_sr, *d_pair, *d_pair_e0, *d_lvl, *d_crv, *d_ue, *d_sl, *d_items, *d_rec;
+  void *d_chan, *d_sr, *d_pair, *d_pair_e0, *d_lvl, *d_crv, *d_ue, *d_rec;
   int arith;                    /* JUR_ARITH_*                                   */
-  int *grid_cls;                /* [ng*nd] grid class of every pair (strict tables), see jur_model_set_ega_group */
-  unsigned char *grid_all;
-  long long *h_pair_e0;
   void *d_atm;                  /* one slab for the compact atmosphere           */
   int atm_cap;
   int atm_slices;               /* distinct time stamps in the atmosphere        */
@@ -205,41 +202,19 @@ int jur_model_create(jur_model_t **out, ctl_t const *ctl, jur_tables_t const *tb
   if (!rc) rc = upload(&m->d_lvl, fl.lvl, sizeof(jur_lvl_t) * (fl.nlevel + 2));
   if (!rc) rc = upload(&m->d_crv, fl.crv, sizeof(jur_crv_t) * (fl.ncurve + 2));
   if (!rc) rc = upload(&m->d_ue, fl.ue, sizeof(jur_ue_t) * (fl.nentry + 2));
-  if (!rc && fl.strict) {       /* bracket slopes for the strict-table look-up: 16 B per entry next to the 8 B of the entry */
-    rc = upload(&m->d_sl, NULL, sizeof(jur_sl_t) * (fl.nentry + 2));
-    if (!rc && (jurk_fill_slopes((jur_ue_t const *)m->d_ue, (jur_sl_t *)m->d_sl, fl.nentry + 2, NULL) || hipStreamSynchronize(NULL) != hipSuccess)) {
-      jur_set_error("cannot form the bracket slopes of the tables");
-      rc = JUR_EHIP;
-    }
-  }
-  if (!rc && fl.strict && !getenv("JUR_EGA_NO_REC")) {   /* bracket records: entries i, i+1 and both slopes in 32 bytes (what the
-                                                            batched look-up kernel reads; JUR_EGA_NO_REC: the two arrays, A/B) */
+  if (!rc && fl.strict) {       /* bracket records for the strict-table look-up: entries i, i+1 and both slopes in 32 bytes */
     rc = upload(&m->d_rec, NULL, sizeof(jur_rec_t) * (fl.nentry + 2));
-    if (!rc && (jurk_fill_records((jur_ue_t const *)m->d_ue, (jur_sl_t const *)m->d_sl, (jur_rec_t *)m->d_rec, fl.nentry + 1, NULL) ||
+    if (!rc && (jurk_fill_records((jur_ue_t const *)m->d_ue, (jur_rec_t *)m->d_rec, fl.nentry + 1, NULL) ||
                 hipStreamSynchronize(NULL) != hipSuccess)) {
       jur_set_error("cannot form the bracket records of the tables");
       rc = JUR_EHIP;
     }
     v->rec = (jur_rec_t const *)m->d_rec;
-    if (!rc) {   /* every kernel of the strict-table arithmetic reads the records; the slope array was their source only */
-      (void)hipFree(m->d_sl);
-      m->d_sl = NULL;
-    }
-  }
-  if (!rc && fl.strict && npair > 0) {   /* which channels of a gas stand on one (p, T) grid: jur_model_set_ega_group */
-    m->grid_cls = (int *)malloc(sizeof(int) * npair);
-    m->grid_all = (unsigned char *)malloc(npair);
-    m->h_pair_e0 = (long long *)malloc(sizeof(long long) * npair);
-    if (!m->grid_cls || !m->grid_all || !m->h_pair_e0) rc = JUR_ENOMEM;
-    else {
-      memcpy(m->h_pair_e0, fl.pair_e0, sizeof(long long) * npair);
-      rc = jur_flat_grid_classes(&fl, ctl->ng, ctl->nd, m->grid_cls, m->grid_all);
-    }
   }
   v->sorted_tables = fl.sorted;
   v->strict_tables = fl.strict;
   v->max_pair_curves = fl.max_pair_curves;
-  m->table_bytes = (long)((sizeof(jur_ue_t) + (m->d_sl ? sizeof(jur_sl_t) : 0) + (m->d_rec ? sizeof(jur_rec_t) : 0)) * fl.nentry + 16 * fl.ncurve + 16 * fl.nlevel + 8 * npair);
+  m->table_bytes = (long)((sizeof(jur_ue_t) + (m->d_rec ? sizeof(jur_rec_t) : 0)) * fl.nentry + 16 * fl.ncurve + 16 * fl.nlevel + 8 * npair);
   jur_flat_free(&fl);
   if (rc) { jur_model_destroy(m); return rc; }
   v->chan = (jur_chan_t const *)m->d_chan;
@@ -249,13 +224,7 @@ int jur_model_create(jur_model_t **out, ctl_t const *ctl, jur_tables_t const *tb
   v->lvl = (jur_lvl_t const *)m->d_lvl;
   v->crv = (jur_crv_t const *)m->d_crv;
   v->ue = (jur_ue_t const *)m->d_ue;
-  v->sl = (jur_sl_t const *)m->d_sl;
   if ((rc = jur_model_set_arithmetic(m, getenv("JUR_EGA_NO_RCP") ? JUR_ARITH_EXACT : JUR_ARITH_FAST))) { jur_model_destroy(m); return rc; }
-  /* measured slower than one pair per workgroup: only on request */
-  if (getenv("JUR_EGA_GROUP") && atoi(getenv("JUR_EGA_GROUP")) >= 2 && (rc = jur_model_set_ega_group(m, atoi(getenv("JUR_EGA_GROUP"))))) {
-    jur_model_destroy(m);
-    return rc;
-  }
 
   m->nfield = JUR_F_K + v->nw + v->ng;
   m->chunk_rays = 1 << 21;      /* upper bound; the workspace budget sets the real size (1.4 M rays for 96 KB per ray).
@@ -279,45 +248,21 @@ int jur_model_create(jur_model_t **out, ctl_t const *ctl, jur_tables_t const *tb
   return JUR_OK;
 }
 
-/* JUR_ARITH_FAST (default): on strictly increasing tables whose descriptors fit the LDS staging the look-up uses bracket
- * slopes, reciprocal bracket widths and carries the path transmittance as 1 - eps (~1e-13 from the reference's
- * divisions); JUR_ARITH_EXACT: the reference's divisions operand for operand (what every other table gets anyway).
- * Takes effect with the next call; calls in flight are the caller's to wait for. */
+/* JUR_ARITH_FAST (default): on strictly increasing tables whose descriptors fit the LDS staging the look-up uses the
+ * bracket records (both entries and both slopes of a bracket), reciprocal bracket widths and carries the path
+ * transmittance as 1 - eps (~1e-13 from the reference's divisions); JUR_ARITH_EXACT: the reference's divisions operand
+ * for operand (what every other table gets anyway).  Takes effect with the next call; calls in flight are the caller's
+ * to wait for. */
 int jur_model_set_arithmetic(jur_model_t *m, int mode) {
   if (mode != JUR_ARITH_FAST && mode != JUR_ARITH_EXACT) { jur_set_error("set_arithmetic: JUR_ARITH_FAST or JUR_ARITH_EXACT"); return JUR_EINVAL; }
   jur_view_t *v = &m->view;
   /* (the staging size of jurk_launch_ega: 24 B per level and curve of the largest pair, at most 48 KB) */
-  int const lds_ok = v->max_pair_curves > 0 && 24L * JUR_TBLNP + 24L * v->max_pair_curves <= 48 * 1024 && !getenv("JUR_EGA_NO_LDS");
+  int const lds_ok = v->max_pair_curves > 0 && 24L * JUR_TBLNP + 24L * v->max_pair_curves <= 48 * 1024;
   m->arith = mode;
-  v->fast_arith = (mode == JUR_ARITH_FAST) && v->strict_tables && (v->sl || v->rec) && lds_ok;
+  v->fast_arith = (mode == JUR_ARITH_FAST) && v->strict_tables && v->rec && lds_ok;
   return JUR_OK;
 }
 int jur_model_arithmetic(jur_model_t const *m) { return m->arith; }
-
-/* Channels of a gas whose tables stand on one (p, T) grid walked together by one lane (jur_ega_group_kernel), at most
- * nch (2 .. JUR_EGA_NCH) per lane; nch < 2: one (channel, gas) pair per workgroup (jur_ega_kernel, the default).
- * Strict tables only; results are the same doubles either way. */
-int jur_model_set_ega_group(jur_model_t *m, int nch) {
-  if (m->shared_tables) { jur_set_error("set_ega_group: a lane shares its tables with another model"); return JUR_EINVAL; }
-  HIPCHK(hipSetDevice(m->device));
-  jur_view_t *v = &m->view;
-  if (m->have_done) HIPCHK(hipEventSynchronize(m->ev_done));      /* launches in flight still read the old items */
-  if (m->d_items) { (void)hipFree(m->d_items); m->d_items = NULL; }
-  v->ega_items = NULL; v->ega_nitems = 0; v->ega_nch = 0;
-  if (nch < 2 || !v->strict_tables || !m->grid_cls) return JUR_OK;      /* (runs only while fast_arith is on) */
-  jur_item_t *items = NULL;
-  int nitems = 0, max_nch = 0;
-  int rc = jur_group_items(v->ng, v->nd, nch, m->grid_cls, m->grid_all, m->h_pair_e0, &items, &nitems, &max_nch);
-  if (!rc && max_nch >= 2) {
-    rc = upload(&m->d_items, items, sizeof(jur_item_t) * nitems);
-    if (!rc) { v->ega_items = (jur_item_t const *)m->d_items; v->ega_nitems = nitems; v->ega_nch = max_nch; }
-  }
-  free(items);
-  return rc;
-}
-
-/* channels per lane the next call's look-up kernel walks (0: one pair per workgroup) */
-int jur_model_ega_group(jur_model_t const *m) { return (m->view.ega_items && m->view.fast_arith && m->view.rec) ? m->view.ega_nch : 0; }
 
 int jur_model_create_from_files(jur_model_t **out, ctl_t const *ctl, int device) {
   *out = NULL;
@@ -353,8 +298,8 @@ int jur_model_create_from_files(jur_model_t **out, ctl_t const *ctl, int device)
 void jur_model_destroy(jur_model_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
-  if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_sl = m->d_items = m->d_rec = NULL;
-  void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_sl, m->d_items, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp,
+  if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_rec = NULL;
+  void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp,
                   m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_kq, m->d_ctb};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
@@ -363,7 +308,6 @@ void jur_model_destroy(jur_model_t *m) {
   if (m->h_kq) (void)hipHostFree(m->h_kq);
   if (m->h_status) (void)hipHostFree(m->h_status);
   free(m->h_atm);
-  if (!m->shared_tables) { free(m->grid_cls); free(m->grid_all); free(m->h_pair_e0); }
   if (m->stream) (void)hipStreamDestroy(m->stream);
   if (m->stream2) (void)hipStreamDestroy(m->stream2);
   if (m->ev_mask) (void)hipEventDestroy(m->ev_mask);

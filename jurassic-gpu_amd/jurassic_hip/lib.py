@@ -84,8 +84,6 @@ def lib():
         L.jur_model_set_pencil.argtypes = [C.c_void_p, C.c_long, C.c_int]
         L.jur_model_set_arithmetic.argtypes = [C.c_void_p, C.c_int]
         L.jur_model_arithmetic.argtypes = [C.c_void_p]
-        L.jur_model_set_ega_group.argtypes = [C.c_void_p, C.c_int]
-        L.jur_model_ega_group.argtypes = [C.c_void_p]
         L.jur_multi_balance.argtypes = [C.c_void_p, C.c_long, C.POINTER(dp), C.c_int, C.POINTER(C.c_long)]
         L.jur_estimate_los_points.argtypes = [C.c_double] * 4 + [C.c_long, C.POINTER(dp), dp]
         L.jur_balance_rays.argtypes = [C.c_double] * 4 + [C.c_long, C.POINTER(dp), C.c_int, C.POINTER(C.c_long)]
@@ -261,11 +259,6 @@ class Model:
     def set_arithmetic(self, mode):
         """ARITH_FAST (default) or ARITH_EXACT: the look-up's arithmetic on strictly increasing tables."""
         _chk(lib().jur_model_set_arithmetic(self.h, int(mode)))
-
-    def set_ega_group(self, nch):
-        """nch in 2..4: the channel-group look-up kernel (round-4 experiment); < 2: one pair per workgroup (default)."""
-        _chk(lib().jur_model_set_ega_group(self.h, int(nch)))
-        return lib().jur_model_ega_group(self.h)       # channels per lane the next call will walk (0: default kernel)
 
     def set_trace_multiple(self, mult):
         _chk(lib().jur_model_set_trace_multiple(self.h, mult))

@@ -303,13 +303,14 @@ def test_product_never_imports_the_oracle():
                 assert "oracle" not in txt.lower(), f"{f} mentions the oracle"
 
 
-def test_kernel_register_budgets(tmp_path):
+def test_kernel_register_budgets_and_cache_policy(tmp_path):
     """The batched kernels' occupancy is part of their measured speed and hangs on a few registers (DESIGN 4.3, 8 vii):
     jur_ega_kernel (strict tables; with the shorter fetch chain of the bracket records the eighth wavefront is worth 4 %)
     must stay within 64 VGPRs (8 wavefronts per SIMD), the radiance-update kernels within 64 (8: a
     workgroup of the grouped one is 8 wavefronts, so a 65th register costs a whole workgroup per CU), the tracer within
     128 (4); jur_ega_kernel and the radiance update use no scratch memory at all, the tracer no more than the few
-    doubles it keeps there today (outside its inner loop)."""
+    doubles it keeps there today (outside its inner loop).  The streams written once and read once bypass the L2, and
+    neither the channel-group look-up nor a kernel for a separate slope array is built."""
     import subprocess
     csrc = os.path.join(common.ROOT, "jurassic-gpu_amd", "csrc")
     asm = tmp_path / "k.s"
@@ -324,8 +325,7 @@ def test_kernel_register_budgets(tmp_path):
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
         seen[name] = (int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1)),
                       int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)))
-    budget = {"jur_ega_kernelILb1ELb1ELb1ELb1E": (64, 0),      # the look-up on bracket records: what strict tables run
-              "jur_ega_kernelILb1ELb1ELb1ELb0E": (64, 0),      # ... on the two arrays (JUR_EGA_NO_REC)
+    budget = {"jur_ega_kernelILb1ELb1ELb1EE": (64, 0),         # the look-up on bracket records: what strict tables run
               "jur_combine_kernel": (64, 0), "jur_combine_group_kernel": (64, 0),
               "jur_trace_kernel": (128, 32), "jur_trace_lanes_kernel": (128, 32)}
     for key, (limit, scratch_limit) in budget.items():
@@ -333,6 +333,8 @@ def test_kernel_register_budgets(tmp_path):
         assert len(hits) == 1, (key, list(seen))
         (vgprs, scratch), = hits.values()
         assert vgprs <= limit and scratch <= scratch_limit, (key, vgprs, scratch)
+    # the channel-group look-up and the separate slope array are gone (the records carry the slopes)
+    assert not [n for n in seen if "jur_ega_group_kernel" in n or "jur_slopes_kernel" in n], list(seen)
 
     # the cache policy of the three streams that are written once and read once (profiles/
     # r04_cache_policy_experiment.json): non-temporal stores of the path transmittances and of the tracer's LOS rows,
@@ -342,7 +344,7 @@ def test_kernel_register_budgets(tmp_path):
         start = text.index("\n" + name + ":")
         return text[start:text.index("s_endpgm", start)]
     nt = lambda code, op: len(re.findall(r"^\s*%s\S*\s.*\bnt\b" % op, code, re.M))
-    ega = body("jur_ega_kernelILb1ELb1ELb1ELb1E")
+    ega = body("jur_ega_kernelILb1ELb1ELb1EE")
     assert nt(ega, "global_store") >= 1 and nt(ega, "global_load") == 0, (nt(ega, "global_store"), nt(ega, "global_load"))
     assert nt(body("jur_trace_kernel"), "global_store") >= 5      # (the emitter and window loops are rolled in this build)
     assert nt(body("jur_combine_group_kernel"), "global_load") >= 1 and nt(body("jur_combine_kernel"), "global_load") >= 1

@@ -72,8 +72,8 @@ def test_formod_task_contrib_names_its_outputs_in_checkmode(tmp_path):
 
 
 def test_contrib_kernel_register_budget(tmp_path):
-    """jur_contrib_kernel, compiled as test_abi_cpu.test_kernel_register_budgets compiles the kernels: within 64 VGPRs
-    (8 wavefronts per SIMD) and no scratch, like the other radiance-update kernels; the transmittance plane is read with
+    """jur_contrib_kernel, compiled as test_abi_cpu.test_kernel_register_budgets_and_cache_policy compiles the kernels:
+    within 64 VGPRs (8 wavefronts per SIMD) and no scratch, like the other radiance-update kernels; the transmittance plane is read with
     non-temporal loads."""
     csrc = os.path.join(ROOT, "jurassic-gpu_amd", "csrc")
     asm = tmp_path / "k.s"

@@ -1,6 +1,6 @@
 """GPU tests of the round-4 entry points: several models in one process (jur_formod_host_multi,
 jur_formod_device_multi -- on a one-GPU box the same device is listed 1, 2 and 3 times, as the lanes of the drop-in
-entry rehearse concurrency on one device), the per-model arithmetic switch, and the channel-group look-up kernel.
+entry rehearse concurrency on one device) and the per-model arithmetic switch.
 
 Everything here is an ARRANGEMENT of the same arithmetic: the assertions are bit for bit against the single-model,
 one-pair-per-workgroup results, which tests/test_parity_gpu.py holds against the oracle."""
@@ -164,40 +164,13 @@ def test_arithmetic_is_a_per_model_choice(hip):
     m.close()
 
 
-@pytest.mark.parametrize("nch", [2, 3, 4])
-def test_channel_group_lookup_kernel_equals_one_pair_per_workgroup(hip, nch):
-    """jur_ega_group_kernel (one lane per (ray, gas) walking up to nch channels that share a (p, T) grid; round-4
-    experiment, off by default) against jur_ega_kernel: the same operations on the same operands, so BIT FOR BIT -- full
-    and ragged groups (5 channels in groups of 2, 3, 4), a gas without a table for one channel, a channel whose table
-    stands on ANOTHER grid (it gets an item of its own), rays that miss the atmosphere, several launches per call."""
-    nu = list(np.round(np.linspace(700.0, 2400.0, 5), 4))
-    def shapes(g, d):
-        return dict(nlev=21, ntemp=6) if (g, d) == (1, 3) else {}      # one pair on a coarser grid
-    g = synth.limb_geometry(3000, seed=nch, nprofiles=3)
-    extra = np.array([[0, 780.0, 0, 0, 95.0, 0, 20.0], [1, 30.0, 0, 0, 5.0, 0, 3.0]])
-    geom = np.vstack([g[:1700], extra, g[1700:], synth.nadir_geometry(90, seed=2, nprofiles=3)])
-    case = common.Case(["CO2", "H2O", "O3"], nu, os.path.join(common.GOLD, "limb", "atm.tab"), geom, nprofiles=3,
-                       table_kw=shapes, missing={(2, 1)})
-    m = hip.Model(case.ctl, case.lib_tables())
-    m.set_atm(case.atm)
-    m.set_pencil(0)
-    ref = m.formod_host(case.geom)
-    assert m.set_ega_group(nch) == nch               # the group kernel is what the next call runs
-    out = m.formod_host(case.geom)
-    m.set_chunk_rays(448)
-    chunked = m.formod_host(case.geom)
-    assert m.set_ega_group(0) == 0
-    back = m.formod_host(case.geom)
-    for k in ("rad", "tau", "tp", "np"):
-        assert same_bits(out[k], ref[k]) and same_bits(chunked[k], ref[k]) and same_bits(back[k], ref[k]), (k, nch)
-    m.close()
-
-
 def test_workspace_laid_out_by_path_lengths(hip):
     """Calls that need several integration launches pack the transmittance tiles by the longest path of each tile
     instead of JUR_NLOS = 400 points per ray: nadir rays (182 points) then take less than half the launches, a limb scan
     (122 .. 393) fewer -- and every output equals the one-launch result and the JUR_NLOS-strided chunking bit for bit,
-    for sorted and unsorted rays, a mix with rays that never enter the atmosphere, and a budget-driven layout."""
+    for sorted and unsorted rays, a mix with rays that never enter the atmosphere, and a budget-driven layout; and, in
+    launches of 448 rays, for three gases with one pair on a coarser (p, T) grid and one gas without a table for one
+    channel."""
     g = synth.limb_geometry(6000, seed=3, nprofiles=2)
     geom = np.vstack([g[:2500], np.array([[0, 780.0, 0, 0, 95.0, 0, 20.0]] * 70), g[2500:], synth.nadir_geometry(3000, seed=2, nprofiles=2)])
     case = common.limb_case(geom=geom, nu=common.CTM4_NU, nprofiles=2)
@@ -225,6 +198,26 @@ def test_workspace_laid_out_by_path_lengths(hip):
     m.set_sort_rays(1)
     m.set_chunk_rays(1 << 21)
     m.set_workspace_budget(200 << 20)
+    out = m.formod_host(case.geom)
+    assert m.last_launches() > 1
+    for k in ("rad", "tau", "tp", "np"):
+        assert same_bits(out[k], ref[k]), k
+    m.close()
+
+    nu = list(np.round(np.linspace(700.0, 2400.0, 5), 4))
+    def shapes(g, d):
+        return dict(nlev=21, ntemp=6) if (g, d) == (1, 3) else {}      # one pair on a coarser grid
+    g = synth.limb_geometry(3000, seed=2, nprofiles=3)
+    extra = np.array([[0, 780.0, 0, 0, 95.0, 0, 20.0], [1, 30.0, 0, 0, 5.0, 0, 3.0]])
+    geom = np.vstack([g[:1700], extra, g[1700:], synth.nadir_geometry(90, seed=2, nprofiles=3)])
+    case = common.Case(["CO2", "H2O", "O3"], nu, os.path.join(common.GOLD, "limb", "atm.tab"), geom, nprofiles=3,
+                       table_kw=shapes, missing={(2, 1)})
+    m = hip.Model(case.ctl, case.lib_tables())
+    m.set_atm(case.atm)
+    m.set_pencil(0)
+    ref = m.formod_host(case.geom)
+    assert m.last_launches() == 1
+    m.set_chunk_rays(448)
     out = m.formod_host(case.geom)
     assert m.last_launches() > 1
     for k in ("rad", "tau", "tp", "np"):

@@ -23,8 +23,7 @@ increasing only:
     strictly increasing keep the reference's divisions operand for operand;
   * radiance update: shared 1/T, exp through a 64-entry table, tanh through exp: ~1e-15 relative per segment.
 
-The arrangements below (fused / batched / batched_grouped, and the channel-group look-up kernel where it is switched
-on) share that arithmetic and are held to each other BIT FOR BIT in tests/test_pencil_gpu.py and in the
+The arrangements below (fused / batched / batched_grouped) share that arithmetic and are held to each other BIT FOR BIT in tests/test_pencil_gpu.py and in the
 chunking / permutation invariance tests here.
 """
 import ctypes as C
