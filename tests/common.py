@@ -108,3 +108,60 @@ def oracle_goldens():
         arr["np"] = np.array(g["np"], dtype=np.int32)
         out[name] = (cases[name], arr)
     return out
+
+
+def random_case(seed):
+    """Random small configuration: emitters, channels, table shapes (levels, temperatures, grid ratio,
+    curve end), missing tables, perturbed atmosphere, mixed geometries, control switches."""
+    rng = np.random.default_rng(seed)
+    ng = int(rng.integers(1, 6))
+    nd = int(rng.integers(1, 7))
+    emitters = list(rng.permutation(LIMB_EMITTERS)[:ng])
+    nu = sorted(float(x) for x in np.round(rng.uniform(650.0, 2600.0, nd), 4))
+    missing = {(g, d) for g in range(ng) for d in range(nd) if rng.random() < 0.15}
+    kw = dict(nlev=int(rng.integers(2, 9)), ntemp=int(rng.integers(2, 7)), ratio=float(rng.uniform(1.06, 2.2)),
+              umax_eps=float(rng.choice([0.5, 0.9, 0.999, 0.99999])))
+    nlimb, nnadir, nin = int(rng.integers(20, 120)), int(rng.integers(0, 60)), int(rng.integers(0, 20))
+    geom = [synth.limb_geometry(nlimb, seed=seed, zmin=float(rng.uniform(-10, 10)), zmax=float(rng.uniform(20, 80)))]
+    if nnadir:
+        geom.append(synth.nadir_geometry(nnadir, seed=seed + 1, lat0=-40.0, lat1=40.0))
+    for _ in range(nin):                               # observer inside the atmosphere, arbitrary view point
+        geom.append(np.array([[0, rng.uniform(1, 80), rng.uniform(-5, 5), rng.uniform(-5, 5),
+                               rng.uniform(0, 85), rng.uniform(-5, 5), rng.uniform(-5, 5)]]))
+    switches = dict(refrac=int(rng.integers(0, 2)), write_bbt=int(rng.integers(0, 2)),
+                    rayds=float(rng.choice([10.0, 20.0])), raydz=float(rng.choice([0.5, 1.0])),
+                    ctm_co2=int(rng.integers(0, 2)), ctm_h2o=int(rng.integers(0, 2)), ctm_auto=1)
+    if rng.random() < 0.3:
+        switches["hydz"] = float(rng.uniform(5, 30))
+    case = Case(emitters, nu, os.path.join(GOLD, "limb", "atm.tab"), np.vstack(geom),
+                       nprofiles=int(rng.integers(1, 5)), table_kw=kw, missing=missing, **switches)
+    n = case.atm.np                                    # reshuffle the gas columns of the shipped profile
+    q = np.ctypeslib.as_array(case.atm.q)
+    base = q[:5, :n].copy()
+    for g, em in enumerate(emitters):
+        q[g, :n] = base[LIMB_EMITTERS.index(em)] * rng.uniform(0.5, 2.0)
+    np.ctypeslib.as_array(case.atm.k)[0, :n] = rng.uniform(0, 1e-4)
+    case.geom[:, 0] = rng.integers(0, max(1, case.atm.np // 91), len(case.geom))   # random profile per ray
+    return case
+
+
+def obs_from_geom(geom, nd):
+    obs = abi.obs_t()
+    obs.nr = len(geom)
+    for k, name in enumerate(("time", "obsz", "obslon", "obslat", "vpz", "vplon", "vplat")):
+        np.ctypeslib.as_array(getattr(obs, name))[:len(geom)] = geom[:, k]
+    np.ctypeslib.as_array(obs.rad)[:] = 7.0      # stale content the call must overwrite
+    np.ctypeslib.as_array(obs.tau)[:] = 7.0
+    return obs
+
+
+def retrieval_case(**kw):
+    case = limb_case(**kw)
+    c = case.ctl
+    c.retp_zmin, c.retp_zmax = 20.0, 25.0
+    c.rett_zmin, c.rett_zmax = 10.0, 40.0
+    for g in range(c.ng):
+        c.retq_zmin[g], c.retq_zmax[g] = -999.0, -999.0
+    c.retq_zmin[2], c.retq_zmax[2] = 15.0, 35.0          # O3
+    c.retk_zmin[0], c.retk_zmax[0] = 10.0, 20.0
+    return case

@@ -2,7 +2,8 @@
 
 (1) example/{limb,nadir}/rad.org columns 11+ (radiance, transmittance) were produced by the reference with
     emissivity tables that are NOT in the reference tree (.MISSING_LARGE_BLOBS lines 1-11), so no radiance of
-    this repository is pinned to reference-produced data yet.  Point JUR_REF_TABLES at a directory that holds
+    this repository is pinned to THOSE numbers yet (tests/test_reference_cpu.py and test_reference_gpu.py pin oracle
+    and HIP path to the reference's own CPU program on synthetic tables).  Point JUR_REF_TABLES at a directory that holds
 
         boxcar_792.0000_{CO2,H2O,O3,CCl4}.tab  boxcar_832.0000_{CO2,H2O,O3,F11}.tab     (limb)
         airs_{667.7820,668.5410,669.8110}_CO2.tab                                       (nadir)
@@ -45,7 +46,8 @@ def _need_tables(example):
     if not REF_TABLES:
         pytest.skip("JUR_REF_TABLES is not set: the emissivity tables behind example/%s/rad.org columns 11+ are missing "
                     "blobs of the reference tree (.MISSING_LARGE_BLOBS), so there is no reference-produced radiance to "
-                    "compare with -- radiance parity stays pinned to the oracle restatement only" % example)
+                    "compare with -- radiances stay pinned to the reference's CPU program on synthetic tables only "
+                    "(tests/test_reference_cpu.py)" % example)
     missing = [f for f in EXAMPLES[example]["need"] if not os.path.exists(os.path.join(REF_TABLES, f))]
     if missing:
         pytest.skip("JUR_REF_TABLES=%s lacks %s" % (REF_TABLES, ", ".join(missing)))
