@@ -116,9 +116,9 @@ void jur_model_destroy(jur_model_t *m);
  * Ordering: the upload waits for the model's last jur_formod_device call
  * (whose kernels may still read the old atmosphere) through an event of the
  * model's own that the call left on the caller's stream -- no handle of the
- * caller's is kept, the stream may have been destroyed since.  Calls enqueued
- * on OTHER streams before that one, and launches of a captured graph, are the
- * caller's to synchronise. */
+ * caller's is kept, the stream may have been destroyed since.  Device-entry
+ * calls on other streams are chained to that one (see jur_formod_device);
+ * launches of a captured graph are the caller's to synchronise. */
 int  jur_model_set_atm(jur_model_t *m, atm_t const *atm);
 
 /* Forward model for nr rays, host arrays.  geom[7] = {time, obsz, obslon,
@@ -138,7 +138,13 @@ void  jur_host_free(void *p);
 /* Same, all pointers in device memory of the model's GPU; work is enqueued on
  * `stream` (a hipStream_t, may be NULL) and the call returns without waiting.
  * d_geom is [7][nr], d_tp is [3][nr], d_np (optional) [nr].
- * d_status (optional, int[1]) is set non-zero on device if a ray overflowed NLOS. */
+ * d_status (optional, int[1]) is set non-zero on device if a ray overflowed NLOS.
+ * Ordering between calls of ONE model: they share its workspace, so every call first lets its stream wait for an
+ * event that the model's last device-entry call left behind its work, whichever stream that was on -- this entry on
+ * `stream`; jur_formod_host, jur_formod_contrib_host, jur_kernel and jur_curtis_godson_host on the model's own stream.
+ * Calls on different streams thus run in call order, one after the other (one model per stream overlaps).  While
+ * `stream` is being captured into a graph the call neither waits nor leaves the event: launches of the graph are the
+ * caller's to order against every other call of the model.  One host thread at a time per model. */
 int  jur_formod_device(jur_model_t *m, long nr, double const *d_geom,
                        double *d_rad, double *d_tau, double *d_tp, int *d_np,
                        int *d_status, void *stream);
@@ -194,7 +200,9 @@ int  jur_formod_device_multi(jur_model_t *const models[], int nmodel, long nr, l
  * call (n+1 stacked atmospheres) whose difference quotients are formed on the device.  k is row-major
  * [jur_measurement_size][jur_state_size];
  * obs returns the unperturbed result.  The reference's signature takes a gsl_matrix;
- * bind with k = matrix->data when matrix->tda == matrix->size2. */
+ * bind with k = matrix->data when matrix->tda == matrix->size2.
+ * The model holds `atm` afterwards (as after jur_model_set_atm) -- after an error return (JUR_ENLOS, ...) too; if
+ * that upload fails, it holds no atmosphere and refuses the next call. */
 size_t jur_state_size(jur_model_t const *m, atm_t const *atm);
 size_t jur_measurement_size(jur_model_t const *m, obs_t const *obs);
 int    jur_kernel(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, size_t mrows, size_t ncols);

@@ -427,6 +427,7 @@ static int upload_atm_rows(jur_model_t *m, double const *h, long n) {
   jur_view_t *v = &m->view;
   int const ng = v->ng, nw = v->nw;
   size_t const nrow = 6 + (size_t)ng + nw;
+  v->atm_np = 0;                /* until the rows are up: a failure below leaves the model without atmosphere */
   if (n > m->atm_cap) {
     if (m->d_atm) (void)hipFree(m->d_atm);
     m->d_atm = NULL;
@@ -467,13 +468,13 @@ static int upload_atm_rows(jur_model_t *m, double const *h, long n) {
     a = b;
   }
   double const *d = (double const *)m->d_atm;
-  v->atm_np = (int)n;
+  v->atm_np = (int)n;           /* (jurk_prepare_atm reads it) */
   v->atm_time = d; v->atm_z = d + (size_t)n; v->atm_lon = d + 2 * (size_t)n; v->atm_lat = d + 3 * (size_t)n;
   v->atm_p = d + 4 * (size_t)n; v->atm_t = d + 5 * (size_t)n;
   v->atm_q = d + 6 * (size_t)n; v->atm_k = d + (6 + (size_t)ng) * n;
   v->atm_pslope = d + nrow * (size_t)n;
   int const ek = jurk_prepare_atm(v, (double *)m->d_atm + nrow * (size_t)n, m->stream);
-  if (ek || hipStreamSynchronize(m->stream) != hipSuccess) { jur_set_error("atm preparation kernel failed"); return JUR_EHIP; }
+  if (ek || hipStreamSynchronize(m->stream) != hipSuccess) { v->atm_np = 0; jur_set_error("atm preparation kernel failed"); return JUR_EHIP; }
   return JUR_OK;
 }
 
@@ -767,6 +768,20 @@ static int record_done(jur_model_t *m, hipStream_t s) {
   return JUR_OK;
 }
 
+/* Every forward-model call of a model shares its workspace (LOS rows, transmittances, ray order, status word), and the
+ * host entries, jur_kernel and jur_curtis_godson_host its I/O image too: before a call enqueues anything, its stream
+ * waits for the event the last jur_formod_device call left behind, whichever stream that was on.  The event is then
+ * recorded again behind this call, so the chain holds across any number of streams.  Not while the stream is being
+ * captured: a graph cannot wait for work outside it; its launches are the caller's to order against other calls. */
+static int wait_done(jur_model_t *m, hipStream_t s) {
+  if (!m->have_done) return JUR_OK;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); st = hipStreamCaptureStatusNone; }
+  if (st != hipStreamCaptureStatusNone) return JUR_OK;
+  HIPCHK(hipStreamWaitEvent(s, m->ev_done, 0));
+  return JUR_OK;
+}
+
 int jur_formod_device(jur_model_t *m, long nr, double const *d_geom, double *d_rad, double *d_tau, double *d_tp,
                       int *d_np, int *d_status, void *stream) {
   return jur_formod_device_ld(m, nr, d_geom, nr, d_rad, d_tau, d_tp, nr, d_np, d_status, stream);
@@ -793,6 +808,8 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
   if (m->view.atm_np < 2) { jur_set_error("formod_device: no atmosphere set"); return JUR_EINVAL; }
   HIPCHK(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
+  int rc = wait_done(m, s);
+  if (rc) return rc;
   int const rb = co ? 0 : pencil_rays_per_group(m, nr);
   if (rb > 0) {
     /* a package-sized call: the whole path in one launch, a workgroup per rb rays, LOS state in LDS */
@@ -814,7 +831,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
     if (m->host_call) HIPCHK(hipEventRecord(m->ev_trace, s));
     return record_done(m, s);
   }
-  int rc = ensure_workspace(m, nr);
+  rc = ensure_workspace(m, nr);
   if (rc) return rc;
   long const R = m->use_rays;
   int const *order = NULL;
@@ -1029,6 +1046,7 @@ int jur_formod_host(jur_model_t *m, long nr, double const *const geom[7], double
   size_t const N = (size_t)nr, nrd = N * nd;
   hipStream_t const s = m->stream, s2 = m->stream2;
   int status = 0, rc;
+  if ((rc = wait_done(m, s))) return rc;         /* a device-entry call on a stream of the caller's may still be running */
 
   if (nr <= JUR_SMALL_CALL) {
     /* a package: everything through the pinned image, one transfer in, one out */
@@ -1193,6 +1211,7 @@ done:
     hydrostatic_rows(m, h, (size_t)n0, 0, n0);
     int const r2 = upload_atm_rows(m, h, n0);
     if (!r2) m->h_atm_n = n0;
+    else m->view.atm_np = 0;                      /* never the stacked one: the next call is refused ("no atmosphere set") */
     if (!rc) rc = r2;
   }
   free(hg);
@@ -1244,7 +1263,8 @@ int jur_formod_contrib_host(jur_model_t *m, long nr, double const *const geom[7]
   int const nd = m->view.nd;
   size_t const N = (size_t)nr, nrd = N * nd, nc = (size_t)(m->view.ng + 1) * nrd;
   hipStream_t const s = m->stream;
-  int rc = ensure_io(m, nr, 1);
+  int rc = wait_done(m, s);
+  if (!rc) rc = ensure_io(m, nr, 1);
   if (rc) return rc;
   if ((long)(2 * nc) > m->ctb_cap) {
     if (m->d_ctb) (void)hipFree(m->d_ctb);
@@ -1290,6 +1310,7 @@ int jur_curtis_godson_host(jur_model_t *m, long nr, double const *const geom[7],
   if (rc) return rc;
   long const Rt = m->use_trace_rays;
   hipStream_t s = m->stream;
+  if ((rc = wait_done(m, s))) return rc;
   size_t const per_ray = (size_t)(ng > 0 ? ng : 1) * JUR_NLOS;
   double *d_geom = NULL, *d_out = NULL, *d_tp = NULL;
   int *d_np = NULL;
@@ -1497,7 +1518,7 @@ static int kernel_ld(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, si
   size_t const NT = ncopy * (size_t)np0, NRT = ncopy * (size_t)nr;
   double *h = (double *)malloc(sizeof(double) * nrow * NT);
   double *g = NULL;                                /* the model's pinned image of the call's arrays (ensure_io) */
-  int rc = JUR_OK;
+  int rc = JUR_OK, stacked = 0;
   if (!x0 || !hstep || !iqa || !ipa || !h) { rc = JUR_ENOMEM; goto done; }
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("jur_kernel: cannot select the device"); rc = JUR_EHIP; goto done; }
   if ((rc = ensure_io(m, (long)NRT, 1))) goto done;
@@ -1526,6 +1547,7 @@ static int kernel_ld(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, si
       stack_times(h + at, atm->time, np0, (double)j * span);
     }
     m->h_atm_n = 0;                            /* the device no longer holds the caller's atmosphere */
+    stacked = 1;
     rc = upload_atm_rows(m, h, (long)NT);
     if (rc) goto done;
     double *geom[7], *tp[3], *rad, *tau;
@@ -1589,7 +1611,15 @@ static int kernel_ld(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, si
   }
 done:
   free(x0); free(hstep); free(iqa); free(ipa); free(h);
-  if (rc == JUR_OK) rc = jur_model_set_atm(m, atm);   /* leave the model with the caller's atmosphere */
+  /* leave the model with the caller's atmosphere -- after an error too (JUR_ENLOS, a failed launch): never with the
+   * stacked one, which later calls would accept; if it cannot go back, with none ("no atmosphere set") */
+  if (rc == JUR_OK) rc = jur_model_set_atm(m, atm);
+  else if (stacked) {
+    char msg[512];
+    snprintf(msg, sizeof msg, "%s", jur_last_error());
+    if (jur_model_set_atm(m, atm) != JUR_OK) { m->view.atm_np = 0; m->h_atm_n = 0; }
+    jur_set_error("%s", msg);
+  }
   return rc;
 }
 
