@@ -323,13 +323,23 @@ int  jur_model_last_contrib_ms(jur_model_t *m, double *out_ms, long *out_launche
  * jur_kat_continua: out[4][n] = continua_ctmco2/h2o/n2/o2 (jr_common.h:315-390) of channel id (0 outside a window).
  * jur_kat_update: what 0: src[i] = src_planck_core(a[i]); (rad, tau)[i] updated by new_obs_core with
  *   tau_gas = b[i], beta_ds = c[i] (jr_common.h:220-224, 293-300); what 1: add_surface_core with surface
- *   temperature a[i] and, if b[i] != 0, brightness_core (jr_common.h:187-190, 227-234). */
+ *   temperature a[i] and, if b[i] != 0, brightness_core (jr_common.h:187-190, 227-234).
+ * jur_kat_traceray: the LOS records the batched ray tracer writes for nr rays (traceray, jr_common.h:585-711), through
+ *   the launches jur_formod_host makes (rays per launch as jur_model_set_chunk_rays leaves them, lanes per ray as
+ *   jur_tune_trace says).  geom, tp (optional), np_out (optional) as in jur_formod_host.  los is a host array
+ *   [nr][nfield][JUR_NLOS], nfield = 4 + nw + ng, rows p, T, ds (trapezoid weight), q_H2O, k[nw], u[ng] (column
+ *   densities); entries from np[ray] on are 0, and so is the q_H2O row when the model has no H2O continuum emitter
+ *   (the tracer never writes it then).  tsurf [nr]: the surface temperature of a ray that hits the ground, else -999.
+ *   JUR_ENLOS, with the records clamped to JUR_NLOS - 1 points, when a ray overflows.  The fused kernel hands its
+ *   records on through LDS and cannot be read this way. */
 int jur_kat_ega_eps(jur_model_t *m, int ig, int id, long n, double const *tau, double const *t, double const *u,
                     double const *p, int mode, int chain, double *out);
 int jur_kat_continua(jur_model_t *m, int id, long n, double const *p, double const *t, double const *q,
                      double const *u_co2, double const *u_h2o, double *out);
 int jur_kat_update(jur_model_t *m, int id, long n, int what, double const *a, double const *b, double const *c,
                    double *rad, double *tau, double *src);
+int jur_kat_traceray(jur_model_t *m, long nr, double const *const geom[7], double *los, double *tsurf, double *const tp[3],
+                     int *np_out);
 
 #ifdef __cplusplus
 }

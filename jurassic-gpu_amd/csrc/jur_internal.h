@@ -144,6 +144,8 @@ int jurk_kat_continua(jur_view_t const *v, int d, long n, double const *p, doubl
                       double const *u_h2o, double *out, void *stream);
 int jurk_kat_update(jur_view_t const *v, int d, long n, int what, double const *a, double const *b, double const *c, double *rad,
                     double *tau, double *src, void *stream);
+/* LOS records of the traced chunk (after jurk_launch_trace): los[ray][nfield][JUR_NLOS], tsurf[ray], indexed by ray id */
+int jurk_kat_los(jur_view_t const *v, jur_chunk_t const *c, double *los, double *tsurf, void *stream);
 
 /* internals of a model that jur_multi.c needs (jur_model.c) */
 /* jur_formod_device on rays that are part of larger arrays: geometry field k at d_geom + k * ldg, tangent-point field k

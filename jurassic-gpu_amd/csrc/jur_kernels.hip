@@ -2255,6 +2255,26 @@ __global__ __launch_bounds__(256) void jur_kat_update_kernel(jur_view_t v, int d
   tau[i] = tt;
 }
 
+// The LOS records of a traced chunk as the tracer left them in the workspace, [tile][point][field][64], gathered to
+// los[ray][field][NLOS] and tsurf[ray] by ray id: one lane per (slot, point), plain loads and stores.  Points from
+// np[slot] on read nothing and come back 0; so does the q_H2O row when the tracer never writes it (v.ig_h2o < 0).
+__global__ __launch_bounds__(256) void jur_kat_los_kernel(jur_view_t v, jur_chunk_t c, double *__restrict__ los,
+                                                          double *__restrict__ tsurf) {
+  long const i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)c.n * NLOS) return;
+  int const r = (int)(i / NLOS), ip = (int)(i - (long)r * NLOS);
+  long const ray = c.order ? (long)c.order[r] : c.first + r;
+  int const nfield = JUR_F_K + v.nw + v.ng;
+  int const np = c.np[r] < NLOS ? c.np[r] : NLOS;
+  double const *const src = c.los + (size_t)(r >> 6) * los_tile_doubles(nfield) + (size_t)ip * nfield * 64 + (r & 63);
+  double *const dst = los + (size_t)ray * nfield * NLOS + ip;
+  for (int f = 0; f < nfield; f++) {
+    bool const written = ip < np && !(f == JUR_F_QH2O && v.ig_h2o < 0);
+    dst[(size_t)f * NLOS] = written ? src[(size_t)f * 64] : 0.;
+  }
+  if (ip == 0) tsurf[ray] = c.tsurf[r];
+}
+
 }  // namespace
 
 extern "C" int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream) {
@@ -2464,6 +2484,13 @@ extern "C" int jurk_kat_update(jur_view_t const *v, int d, long n, int what, dou
   if (n <= 0) return 0;
   hipLaunchKernelGGL(jur_kat_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *v, d, n, what,
                      a, b, c, rad, tau, src);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_kat_los(jur_view_t const *v, jur_chunk_t const *c, double *los, double *tsurf, void *stream) {
+  if (c->n <= 0) return 0;
+  long const n = (long)c->n * NLOS;
+  hipLaunchKernelGGL(jur_kat_los_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *v, *c, los, tsurf);
   return (int)hipGetLastError();
 }
 

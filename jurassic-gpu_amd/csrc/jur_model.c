@@ -1460,6 +1460,72 @@ int jur_kat_update(jur_model_t *m, int id, long n, int what, double const *a, do
   return kat_finish(m, ek, n, 3, 3, io, d);
 }
 
+/* The ray tracer's LOS records point by point: the chunk loop of jur_curtis_godson_host (the same launches of
+ * jurk_launch_trace, so jur_tune_trace selects the kernel as in production), each chunk gathered from the workspace
+ * before the next one overwrites it.  An overflowing ray comes back clamped, with JUR_ENLOS. */
+int jur_kat_traceray(jur_model_t *m, long nr, double const *const geom[7], double *los, double *tsurf, double *const tp[3],
+                     int *np_out) {
+  if (!m || nr < 1 || !geom || !los || !tsurf) { jur_set_error("kat_traceray: bad arguments"); return JUR_EINVAL; }
+  if (m->view.atm_np < 2) { jur_set_error("kat_traceray: no atmosphere set"); return JUR_EINVAL; }
+  HIPCHK(hipSetDevice(m->device));
+  int rc = ensure_workspace(m, nr);
+  if (rc) return rc;
+  long const Rt = m->use_trace_rays;
+  hipStream_t s = m->stream;
+  if ((rc = wait_done(m, s))) return rc;
+  size_t const per_ray = (size_t)m->nfield * JUR_NLOS;
+  double *d_geom = NULL, *d_los = NULL, *d_tsurf = NULL, *d_tp = NULL;
+  int *d_np = NULL;
+  hipError_t e = hipMalloc((void **)&d_geom, sizeof(double) * 7 * (size_t)nr);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_tp, sizeof(double) * 3 * (size_t)nr);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_np, sizeof(int) * (size_t)nr);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_tsurf, sizeof(double) * (size_t)nr);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_los, sizeof(double) * per_ray * (size_t)nr);
+  if (e != hipSuccess) { rc = JUR_EHIP; jur_set_error("kat_traceray: hipMalloc failed"); goto done; }
+  for (int k = 0; k < 7; k++)
+    if (hipMemcpyAsync(d_geom + (size_t)k * nr, geom[k], sizeof(double) * nr, hipMemcpyHostToDevice, s) != hipSuccess) { rc = JUR_EHIP; goto done; }
+  if (hipMemsetAsync(m->d_status, 0, sizeof(int), s) != hipSuccess) { rc = JUR_EHIP; goto done; }
+  {
+    for (long t0 = 0; t0 < nr; t0 += Rt) {
+      jur_chunk_t c;
+      memset(&c, 0, sizeof c);
+      c.n = (int)((nr - t0 < Rt) ? nr - t0 : Rt);
+      c.stride = (int)Rt;
+      c.stride_eps = (int)m->use_rays;
+      c.first = t0;
+      c.order = NULL;
+      for (int k = 0; k < 7; k++) c.geom[k] = d_geom + (size_t)k * nr;
+      for (int k = 0; k < 3; k++) c.tp[k] = d_tp + (size_t)k * nr;
+      c.np_out = d_np;
+      c.np = m->d_np;
+      c.tsurf = m->d_tsurf;
+      c.los = m->d_los;
+      c.eps = m->d_eps;
+      c.status = m->d_status;
+      int ek = jurk_launch_trace(&m->view, &c, s);
+      if (!ek) ek = jurk_kat_los(&m->view, &c, d_los, d_tsurf, s);
+      if (ek) { jur_set_error("kat_traceray: kernel launch failed: %s", hipGetErrorString((hipError_t)ek)); rc = JUR_EHIP; goto done; }
+    }
+    int status = 0;
+    hipError_t ec = hipMemcpyAsync(los, d_los, sizeof(double) * per_ray * (size_t)nr, hipMemcpyDeviceToHost, s);
+    if (ec == hipSuccess) ec = hipMemcpyAsync(tsurf, d_tsurf, sizeof(double) * nr, hipMemcpyDeviceToHost, s);
+    for (int k = 0; k < 3 && tp && ec == hipSuccess; k++)
+      ec = hipMemcpyAsync(tp[k], d_tp + (size_t)k * nr, sizeof(double) * nr, hipMemcpyDeviceToHost, s);
+    if (np_out && ec == hipSuccess) ec = hipMemcpyAsync(np_out, d_np, sizeof(int) * nr, hipMemcpyDeviceToHost, s);
+    if (ec == hipSuccess) ec = hipMemcpyAsync(&status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (ec == hipSuccess) ec = hipStreamSynchronize(s);
+    if (ec != hipSuccess) { jur_set_error("kat_traceray: copy back failed: %s", hipGetErrorString(ec)); rc = JUR_EHIP; goto done; }
+    if (status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
+  }
+done:
+  if (d_geom) (void)hipFree(d_geom);
+  if (d_tp) (void)hipFree(d_tp);
+  if (d_np) (void)hipFree(d_np);
+  if (d_tsurf) (void)hipFree(d_tsurf);
+  if (d_los) (void)hipFree(d_los);
+  return rc;
+}
+
 /* ---- retrieval Jacobian -------------------------------------------------------- */
 /* State vector of the atmosphere inside the retrieval windows (atm2x, jurassic.c:1491-1513):
  * quantity index iqa (0 p, 1 T, 2+g q, 2+ng+w k) and atmosphere point ipa per element. */

@@ -103,6 +103,7 @@ def lib():
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
         L.jur_kat_update.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int] + [dp] * 6
+        L.jur_kat_traceray.argtypes = [C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), C.POINTER(C.c_int)]
         for name in ("formod", "formod_GPU"):
             getattr(L, name).argtypes = [C.c_void_p] * 3
             getattr(L, name).restype = None
@@ -229,6 +230,7 @@ class Model:
         self.h = h
         self.nd = ctl.nd
         self.ng = ctl.ng
+        self.nw = ctl.nw
 
     def close(self):
         if getattr(self, "h", None):
@@ -366,6 +368,27 @@ class Model:
         _chk(lib().jur_kat_update(self.h, id_, len(a), what, _p(a), _p(b), _p(c), _p(rad), _p(tau), _p(src)))
         return rad, tau, src
 
+    def kat_traceray(self, geom, overflow_ok=False):
+        """The batched ray tracer's LOS records (jur_kat_traceray).  geom: (nr, 7) -> dict(p, t, ds, qh2o (nr, NLOS),
+        k (nw, nr, NLOS), u (ng, nr, NLOS), np, tsurf (nr,), tp (nr, 3), status); entries from np[ray] on are 0.
+        overflow_ok: a ray that needs NLOS points comes back clamped with status == ENLOS instead of raising."""
+        g = np.ascontiguousarray(np.asarray(geom, dtype=np.float64).T)
+        nr = g.shape[1]
+        nw = self.nw
+        los = np.zeros((nr, 4 + nw + self.ng, abi.NLOS))
+        tsurf = np.zeros(nr)
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        garr = (dp * 7)(*[_p(g[k]) for k in range(7)])
+        tarr = (dp * 3)(*[_p(tp[k]) for k in range(3)])
+        rc = lib().jur_kat_traceray(self.h, nr, garr, _p(los), _p(tsurf), tarr, npts.ctypes.data_as(C.POINTER(C.c_int)))
+        if not (overflow_ok and rc == ENLOS):
+            _chk(rc)
+        return dict(p=los[:, 0], t=los[:, 1], ds=los[:, 2], qh2o=los[:, 3],
+                    k=np.ascontiguousarray(los[:, 4:4 + nw].transpose(1, 0, 2)),
+                    u=np.ascontiguousarray(los[:, 4 + nw:].transpose(1, 0, 2)),
+                    np=npts, tsurf=tsurf, tp=np.ascontiguousarray(tp.T), status=rc)
+
     def enable_timing(self, on=True):
         _chk(lib().jur_model_enable_timing(self.h, int(on)))
 
@@ -399,6 +422,7 @@ class Model:
 
 
 ARITH_FAST, ARITH_EXACT = 0, 1
+ENLOS = -5                             # JUR_ENLOS
 
 
 class GslMatrix(C.Structure):

@@ -145,6 +145,18 @@ def random_case(seed):
     return case
 
 
+def extinction_profile(atm, k0=3e-4, h=6.0):
+    """Writes an aerosol extinction that varies with altitude into window 0 of atm (in place; -> atm):
+    k(z) = k0 exp(-z / h) (1 + 0.3 sin z) km^-1, z in km.  The shipped profiles carry k = 0 and every other builder a
+    constant, which lip() returns from ANY bracket: only a profile like this one shows a wrong bracket, a wrong hint or
+    a slip in the k row of the ray tracer.  For the scenes apply it to the base profile before synth.scene, which
+    regrids k from the base."""
+    n = atm.np
+    z = np.ctypeslib.as_array(atm.z)[:n]
+    np.ctypeslib.as_array(atm.k)[0, :n] = k0 * np.exp(-z / h) * (1.0 + 0.3 * np.sin(z))
+    return atm
+
+
 def obs_from_geom(geom, nd):
     obs = abi.obs_t()
     obs.nr = len(geom)

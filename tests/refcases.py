@@ -37,10 +37,25 @@ TABLE_SHAPES = {"descending": dict(table_kw=dict(descending=True)),
                 "missing": dict(missing={(0, 1), (2, 0), (3, 0), (3, 1)})}
 
 
-def scene_case(name):
+def scene_case(name, extinction=False):
     case = common.limb_case()
+    if extinction:                                      # on the base profile: synth.scene regrids k from it
+        common.extinction_profile(case.atm)
     case.atm, case.geom, _ = synth.scene(name, case.ctl, case.atm)
     return case
+
+
+def _with_extinction(case):
+    """The shipped profiles carry k = 0 and the random cases a constant: these carry common.extinction_profile."""
+    common.extinction_profile(case.atm)
+    return case
+
+
+def _extinction_only():
+    """No emitter, no continuum: the extinction alone, on the limb example's rays and 13 nadir rays."""
+    geom = np.vstack([common.golden_geometry("limb"), synth.nadir_geometry(13, seed=4)])
+    return _with_extinction(common.Case([], [792.0, 832.0], os.path.join(common.GOLD, "limb", "atm.tab"), geom,
+                                        ctm_co2=0, ctm_h2o=0, ctm_n2=0, ctm_o2=0, ctm_auto=1))
 
 
 def _nan_mask():
@@ -65,17 +80,26 @@ def _builders():
     b["nan_mask"] = _nan_mask
     for name in sorted(synth.SCENES):
         b["scene_" + name] = lambda name=name: (scene_case(name), None)
+    b["extinction_limb"] = lambda: (_with_extinction(common.limb_case()), None)
+    b["extinction_nadir"] = lambda: (_with_extinction(common.nadir_case()), None)
+    b["extinction_only"] = lambda: (_extinction_only(), None)
+    b["scene_ragged_extinction"] = lambda: (scene_case("ragged", extinction=True), None)
     return b
 
 
 FORMOD = _builders()
 SCENE_CASES = [n for n in FORMOD if n.startswith("scene_")]
-JACOBIANS = {"jacobian": dict(), "jacobian_hydz10": dict(hydz=10.0)}
+# (extinction: the retk columns, 10 .. 20 km, perturb the non-zero values of common.extinction_profile)
+JACOBIANS = {"jacobian": dict(), "jacobian_hydz10": dict(hydz=10.0), "jacobian_extinction": dict(extinction=True)}
 
 
 def jacobian_case(name):
     """-> (case, obs with one measurement masked) as test_jacobian_matches_reference_kernel."""
-    case = common.retrieval_case(**JACOBIANS[name])
+    kw = dict(JACOBIANS[name])
+    extinction = kw.pop("extinction", False)
+    case = common.retrieval_case(**kw)
+    if extinction:
+        common.extinction_profile(case.atm)
     obs = common.obs_from_geom(case.geom, case.ctl.nd)
     obs.rad[5][1] = float("nan")
     return case, obs

@@ -85,18 +85,29 @@ def assert_total_is_formod(m, case, out, rad_in=None):
         assert np.array_equal(out[key], ref[key], equal_nan=key == "rad"), key
 
 
-@pytest.mark.parametrize("name", ["limb", "limb_ctm4", "nadir_bbt"])
+@pytest.mark.parametrize("name", ["limb", "limb_ctm4", "nadir_bbt", "limb_ext"])
 def test_every_variant_against_the_oracle(hip, oracle, name):
     if name == "nadir_bbt":
         case = common.nadir_case()                   # WRITE_BBT, rays that end on the surface
     else:
         case = common.limb_case(nu=common.CTM4_NU) if name == "limb_ctm4" else common.limb_case()
+    if name == "limb_ext":                           # an extinction that varies with altitude (the shipped profile has k = 0)
+        common.extinction_profile(case.atm)
     m = model_for(hip, case)
     out = m.formod_contrib_host(case.geom)
     assert out["rad_c"].shape == (case.ctl.ng + 1, len(case.geom), case.ctl.nd)
     check_oracle(oracle, case, out)
     assert_total_is_formod(m, case, out)
     m.close()
+    if name == "limb_ext":
+        ng = case.ctl.ng
+        assert out["tau_c"][ng].min() < 0.9          # the EXTINCT variant is not empty here ...
+        tb = case.oracle_tables(oracle)
+        for v in range(ng):                          # ... and a gas variant that kept k would show: gas v alone WITH k
+            a = edited_atm(case, v)
+            np.ctypeslib.as_array(a.k)[:] = np.ctypeslib.as_array(case.atm.k)
+            with_k = oracle.formod_rays(case.ctl, a, tb, case.geom)
+            assert np.abs(out["tau_c"][v] - with_k["tau"]).max() > 1e-3, v
 
 
 @pytest.mark.parametrize("seed", [100, 103, 107, 111])

@@ -9,6 +9,10 @@ end-to-end parity tests only reach by chance:
   src_planck_core    jr_common.h:220-224  T = 100 K, 399.99 K, grid points
   new_obs_core       jr_common.h:293-300  tau_gas around the 1e-50 gate
   add_surface_core / brightness_core      jr_common.h:187-190, 227-234
+  traceray           jr_common.h:585-711  the LOS record of every point (p, T, ds, q_H2O, k, u) and tsurf, on limb scans,
+                                          nadir and edge rays, paths of one to three points, ragged / unsorted scenes
+                                          and every control switch of the tracer, always with an extinction that varies
+                                          with altitude (tests/losrecords.py)
 
 The look-up is plain IEEE arithmetic in the reference's operand order, so ega_eps must come back BIT-IDENTICAL in
 modes 0 .. 2 (the reference's bisections; warm-started searches, descriptors from global memory / from LDS): these
@@ -21,6 +25,7 @@ import os
 import numpy as np
 import pytest
 import common
+import losrecords as L
 from jurassic_hip import abi, synth
 
 pytestmark = pytest.mark.gpu
@@ -230,3 +235,120 @@ def test_source_function_update_gate_surface_and_brightness(hip, oracle):
         assert same_doubles(rad_e[plain], ref_e[plain])                              # surface term: same doubles
         assert np.abs(rad_e[~plain] / ref_e[~plain] - 1).max() < 1e-14               # log1p of the device library
     m.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the ray tracer's LOS records, point by point
+
+def _bit_equal_records(a, b, what):
+    for key in ("p", "t", "ds", "qh2o", "k", "u", "tsurf", "tp"):
+        assert same_doubles(a[key], b[key]), (what, key)
+    assert np.array_equal(a["np"], b["np"]), what
+
+
+@pytest.mark.parametrize("name", list(L.CONFIGS))
+def test_los_records_against_the_oracle(hip, oracle, tmp_path, name):
+    """What jur_trace_kernel / jur_trace_lanes_kernel write for every LOS point -- p, T, ds, q_H2O, k, u[ng] -- and
+    tsurf per ray, read back through jur_kat_traceray and held to oracle.traceray, on the configurations of
+    tests/losrecords.py (every one with an extinction that varies with altitude).
+
+    Exactly: the point counts and the rays that hit the ground are the oracle's; tsurf of such a ray is the hook's own
+    T of its last point, bit for bit; everything from np[ray] on is 0, and so is the q_H2O row of a model whose
+    tracer never writes it; one lane per ray, a quad of lanes per ray and launches of 64 rays (two or more trace
+    launches per call, the workspace slots reused) give the same doubles in every field of every point.
+    Within the oracle's own conditioning (losrecords.yardstick, FACTOR, CAP): every field of every point of the rays
+    whose point count a one-ulp nudge of the geometry does not change.  Y_f and the device's worst scaled deviation are
+    printed per field; DESIGN.md section 2 records them.
+
+    The fused kernel hands its LOS through LDS and cannot be read this way: it stays covered by the bit equality of its
+    results with the batched kernels' (tests/test_pencil_gpu.py)."""
+    case = L.CONFIGS[name](str(tmp_path))
+    base, use, Y = L.yardstick(oracle, case)
+    assert (~use).sum() <= 0.02 * len(use), ("rays whose point count a one-ulp nudge changes", np.nonzero(~use)[0])
+    m = hip.Model(case.ctl, case.lib_tables())
+    m.set_atm(case.atm)
+    try:
+        hip.tune_trace(1)
+        one = m.kat_traceray(case.geom)
+        hip.tune_trace(4)
+        quad = m.kat_traceray(case.geom)
+        # 64 rays per launch, and JUR_NLOS points set aside per ray (the compact layout would trace all rays in one launch)
+        m.set_chunk_rays(64)
+        m.set_compact_workspace(False)
+        chunk4 = m.kat_traceray(case.geom)
+        hip.tune_trace(1)
+        chunk1 = m.kat_traceray(case.geom)
+    finally:
+        hip.tune_trace(0)
+        m.close()
+    _bit_equal_records(quad, one, "four lanes per ray == one lane per ray")
+    _bit_equal_records(chunk4, one, "launches of 64 rays, four lanes == one launch")
+    _bit_equal_records(chunk1, one, "launches of 64 rays, one lane == one launch")
+
+    ctl, nr = case.ctl, len(case.geom)
+    ref_np = np.array([tr["np"] for tr in base], dtype=np.int32)
+    ref_tsurf = np.array([tr["tsurf"] for tr in base])
+    assert one["status"] == 0 and np.array_equal(one["np"], ref_np), np.nonzero(one["np"] != ref_np)[0]
+    assert np.array_equal(one["tsurf"] == -999, ref_tsurf == -999)
+    assert (ref_tsurf != -999).any() and (ref_tsurf == -999).any()              # ground hits are among the rays
+    worst = {f: (0.0, -1) for f in L.FIELDS}
+    for i in range(nr):
+        n = int(ref_np[i])
+        for key in ("p", "t", "ds", "qh2o"):
+            assert np.all(bits(one[key][i, n:]) == 0), (i, key, "beyond np")
+        assert np.all(bits(one["k"][:, i, n:]) == 0) and np.all(bits(one["u"][:, i, n:]) == 0), (i, "beyond np")
+        if L.h2o_index(ctl) < 0:
+            assert np.all(bits(one["qh2o"][i]) == 0), (i, "q_H2O row of a tracer that never writes it")
+        if ref_tsurf[i] != -999:
+            assert bits(one["tsurf"][i:i + 1])[0] == bits(one["t"][i, n - 1:n])[0], (i, "tsurf is T of the last point")
+        if n == 0:
+            continue
+        rows, ref_rows = L.hook_rows(ctl, one, i, n), L.rows_of(ctl, base[i])
+        if not np.any(base[i]["ds"]):
+            assert not np.any(rows["ds"]), (i, "a path without length")
+        if use[i]:
+            for f, v in L.scaled_deviation(ref_rows, rows).items():
+                if v > worst[f][0]:
+                    worst[f] = (v, i)
+    print("LOS %s: %d rays (%d traced, %d left out), fields %s" % (name, nr, (ref_np > 0).sum(), (~use).sum(), " ".join(L.FIELDS)))
+    print("LOS %s: Y_f      %s" % (name, " ".join("%.2e" % Y[f] for f in L.FIELDS)))
+    print("LOS %s: device   %s" % (name, " ".join("%.2e" % worst[f][0] for f in L.FIELDS)))
+    print("LOS %s: bound    %s" % (name, " ".join("%.2e" % L.bound(Y[f]) for f in L.FIELDS)))
+    for f in L.FIELDS:
+        v, i = worst[f]
+        if v > L.bound(Y[f]):                                                  # a finding: say where
+            a, b = L.rows_of(ctl, base[i])[f], L.hook_rows(ctl, one, i, int(ref_np[i]))[f]
+            row, point = np.unravel_index(np.argmax(np.abs(b - a)), a.shape)
+            raise AssertionError("field %s: scaled deviation %.3e above %.3e (Y = %.3e) at ray %d %s, row %d, point %d of %d: "
+                                 "device %r, oracle %r" % (f, v, L.bound(Y[f]), Y[f], i, case.geom[i], row, point, ref_np[i],
+                                                           b[row, point], a[row, point]))
+    # the tangent point comes from the same bookkeeping: the suite's bounds (tests/test_parity_gpu.py)
+    ref_tp = np.array([tr["tp"] for tr in base])
+    assert np.abs(one["tp"] - ref_tp).max() < 1e-9
+
+
+def test_los_records_of_a_ray_that_needs_nlos_points(hip):
+    """The reported status the suite already exercises (test_nlos_overflow_is_reported, tests/sequences.py "overflow" on
+    "tall"), through the hook only: the oracle ends the process on such a ray.  JUR_ENLOS, np clamped to NLOS - 1, the
+    records the same doubles with one lane and with four lanes per ray."""
+    case = common.limb_case(geom=synth.limb_geometry(1, scan=True, zmin=1.9, zmax=1.9))
+    np.ctypeslib.as_array(case.atm.z)[:case.atm.np] *= 1.08                     # sequences.atmosphere(..., "tall")
+    common.extinction_profile(case.atm)
+    m = hip.Model(case.ctl, case.lib_tables())
+    m.set_atm(case.atm)
+    try:
+        with pytest.raises(hip.JurassicError, match="Too many LOS points"):
+            m.kat_traceray(case.geom)
+        hip.tune_trace(1)
+        one = m.kat_traceray(case.geom, overflow_ok=True)
+        hip.tune_trace(4)
+        quad = m.kat_traceray(case.geom, overflow_ok=True)
+    finally:
+        hip.tune_trace(0)
+        m.close()
+    assert one["status"] == quad["status"] == hip.ENLOS
+    assert list(one["np"]) == [abi.NLOS - 1]
+    _bit_equal_records(quad, one, "overflow: four lanes per ray == one lane per ray")
+    n = abi.NLOS - 1
+    assert np.all(one["p"][0, :n] > 0) and np.all(one["ds"][0, :n] > 0) and np.all(one["k"][0, 0, :n] > 0)
+    assert np.all(bits(one["p"][0, n:]) == 0) and np.all(bits(one["u"][:, 0, n:]) == 0)

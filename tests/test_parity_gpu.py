@@ -96,7 +96,7 @@ def run_both(hip, oracle, case, rad_in=None):
     return out, ref
 
 
-def assert_parity(out, ref, rtol=RTOL):
+def assert_parity(out, ref, rtol=RTOL, cartesian_tp=False):
     assert np.array_equal(out["np"], ref["np"])
     fin = np.isfinite(ref["rad"])
     assert np.array_equal(fin, np.isfinite(out["rad"]))
@@ -110,6 +110,9 @@ def assert_parity(out, ref, rtol=RTOL):
     k = np.unravel_index(np.argmax(terr - allow), terr.shape)
     assert np.all(terr <= allow), (k, out["tau"][k], ref["tau"][k])
     assert np.abs(out["tp"][:, 0] - ref["tp"][:, 0]).max() < 1e-9      # km
+    if cartesian_tp:       # rays over a pole or across the dateline (tests/test_scenes_gpu.py): positions 0.1 mm apart
+        assert np.linalg.norm(synth._cart(*out["tp"].T) - synth._cart(*ref["tp"].T), axis=1).max() < 1e-7
+        return
     # tangent-point longitude / latitude [deg]: 1e-9 (0.1 mm on the ground).  Rays that graze the surface put the parabola
     # through the three lowest points close to degenerate: seed 61660 of tools/fuzz_parity.py (tangent altitude -5.6 m)
     # reaches 2.4e-10 with every arrangement of the kernels; the ray tracer has been the same code since round 1
@@ -249,6 +252,48 @@ def test_degenerate_sizes(hip, oracle):
     assert out["np"].max() == 0 and out["rad"].max() == 0.0 and out["tau"].min() == 1.0
     out, ref = run_both(hip, oracle, common.limb_case(geom=synth.limb_geometry(257, seed=7), nu=common.CTM4_NU))
     assert_parity(out, ref)
+
+
+def test_extinction_that_varies_with_altitude(hip, oracle):
+    """The shipped profiles carry k = 0 and every other case a constant, which the interpolation returns from any
+    bracket; common.extinction_profile varies by a factor 1e6 over the profile.  The limb example's rays and nadir rays
+    with all four continua on; the "ragged" scene (descending slices, a 2-level profile; synth.scene regrids k from the
+    base); and extinction alone -- no emitter, no continuum -- where the transmittance of a ray is
+    exp(-sum k_i ds_i) over its LOS record (jur_kat_traceray: k and the trapezoid weights ds as the tracer wrote them).
+    The oracle meets that identity to 2.0e-15 on these rays (smallest tau 0.87); 1e-13 relative is 50 x that, for a device
+    exp good to about one ulp per segment, and equals common.tau_atol at tau ~ 1."""
+    import math
+    limb_nadir = np.vstack([common.golden_geometry("limb"), synth.nadir_geometry(13, seed=4)])
+    case = common.limb_case(geom=limb_nadir, nu=common.CTM4_NU)
+    common.extinction_profile(case.atm)
+    out, ref = run_both(hip, oracle, case)
+    assert_parity(out, ref)
+    assert ref["tau"].min() < 0.5 < ref["tau"].max()
+
+    case = common.limb_case()
+    common.extinction_profile(case.atm)
+    case.atm, case.geom, _ = synth.scene("ragged", case.ctl, case.atm)
+    out, ref = run_both(hip, oracle, case)
+    assert_parity(out, ref, cartesian_tp=True)
+    assert (ref["np"] > 1).sum() >= 150
+
+    case = common.Case([], [792.0, 832.0], os.path.join(common.GOLD, "limb", "atm.tab"), limb_nadir,
+                       ctm_co2=0, ctm_h2o=0, ctm_n2=0, ctm_o2=0, ctm_auto=1)
+    common.extinction_profile(case.atm)
+    out, ref = run_both(hip, oracle, case)
+    assert_parity(out, ref)
+    assert out["tau"].min() < 0.9                              # the identity below is not a trivial one
+    model = hip.Model(case.ctl, case.lib_tables())
+    model.set_atm(case.atm)
+    los = model.kat_traceray(case.geom)
+    model.close()
+    assert np.array_equal(los["np"], out["np"])
+    worst = 0.0
+    for i, n in enumerate(los["np"]):
+        want = math.exp(-math.fsum(los["k"][0, i, :n] * los["ds"][i, :n]))
+        worst = max(worst, float(np.abs(out["tau"][i] / want - 1).max()))
+    print("extinction only: largest |tau / exp(-sum k ds) - 1| = %.2e, smallest tau %.4f" % (worst, out["tau"].min()))
+    assert worst <= 1e-13
 
 
 def test_against_committed_example_results(hip):
@@ -665,13 +710,17 @@ _retrieval_case = common.retrieval_case
 
 
 @pytest.mark.parametrize("arith", ["fast", "exact"])
-@pytest.mark.parametrize("kw", [dict(), dict(hydz=10.0)])
+@pytest.mark.parametrize("kw", [dict(), dict(hydz=10.0), dict(extinction=True)])
 def test_jacobian_matches_reference_kernel(hip, oracle, kw, arith):
     """jur_kernel (one batched call over n+1 stacked atmospheres) against the restated
     kernel() loop of n+1 formod calls (jurassic.c:812-857), under both arithmetics of the look-up
     (jur_model_set_arithmetic).  Columns are difference quotients (y1-y0)/h: compared relative to the largest entry of
     each column."""
+    kw = dict(kw)
+    extinction = kw.pop("extinction", False)
     case = _retrieval_case(**kw)
+    if extinction:                                        # the retk columns (10 .. 20 km) perturb non-zero values
+        common.extinction_profile(case.atm)
     obs_ref = _obs_from_geom(case.geom, 2)
     obs = _obs_from_geom(case.geom, 2)
     for o in (obs_ref, obs):
@@ -686,6 +735,8 @@ def test_jacobian_matches_reference_kernel(hip, oracle, kw, arith):
     live = scale > 0          # with HYDZ >= 0 the pressure columns away from the reference level vanish
     assert live.sum() >= 31 + 21 + 11 and np.all(k[:, ~live] == 0)
     assert np.max(np.abs(k[:, live] - k_ref[:, live]) / scale[live]) < 1e-6
+    if extinction:
+        assert np.all(live[-11:]) and np.all(np.abs(k[:, -11:]).max(axis=0) > 0)      # the extinction columns are live
     n = obs.nr
     a, b = np.ctypeslib.as_array(obs.rad)[:n, :2], np.ctypeslib.as_array(obs_ref.rad)[:n, :2]
     fin = np.isfinite(b)

@@ -13,6 +13,7 @@ import math
 import numpy as np
 import pytest
 import common
+import losrecords as L
 from jurassic_hip import abi, synth
 
 
@@ -163,3 +164,36 @@ def test_leaving_the_slice_at_the_first_point(oracle):
     a = oracle.formod_rays(case.ctl, atm, case.oracle_tables(oracle), geom)
     b = oracle.formod_rays(case.ctl, atm, case.oracle_tables(oracle), geom)
     assert np.array_equal(a["rad"], b["rad"]) and np.all(a["np"] == 1) and np.all(np.isfinite(a["rad"]))
+
+
+@pytest.mark.parametrize("name", list(L.CONFIGS))
+def test_los_record_yardstick_and_short_paths(oracle, tmp_path, name):
+    """CPU twin of tests/test_kat_gpu.py::test_los_records_against_the_oracle: the configurations and the yardstick the
+    device's LOS records are held to (tests/losrecords.py), proven without a GPU.  No ray needs NLOS points (the oracle
+    would end the process); at most 2 % of the rays change their point count under a one-ulp nudge of the geometry; every
+    Y_f is a few 1e-11 at most (FACTOR * Y_f is then below the 1e-9 cap for p, T, k, q and reaches it for ds and u of
+    the longest limb paths); the extinction the tracer interpolates varies along the paths; and the short paths have the point counts they are
+    there for."""
+    case = L.CONFIGS[name](str(tmp_path))
+    base, use, Y = L.yardstick(oracle, case)
+    nps = np.array([tr["np"] for tr in base])
+    tsurf = np.array([tr["tsurf"] for tr in base])
+    print("LOS %s: %d rays, %d traced, %d left out, np <= %d, Y_f %s"
+          % (name, len(nps), (nps > 0).sum(), (~use).sum(), nps.max(), " ".join("%s %.2e" % (f, Y[f]) for f in L.FIELDS)))
+    assert 100 <= len(nps) <= 230 and (nps > 0).sum() >= 25 and nps.max() < abi.NLOS - 1
+    assert (~use).sum() <= 0.02 * len(use)
+    assert (tsurf != -999).any() and (tsurf == -999).any()
+    for f in L.FIELDS:
+        present = f not in ("q", "u") or (case.ctl.ng > 0 and (f == "u" or L.h2o_index(case.ctl) >= 0))
+        assert (0 < Y[f] < 1e-10) if present else Y[f] == 0.0, (f, Y[f])
+        assert 64 * 2.0 ** -52 <= L.bound(Y[f]) <= L.CAP
+    long_ray = base[int(np.argmax(nps))]
+    assert long_ray["k"].min() > 0 and long_ray["k"].max() > 20 * long_ray["k"].min()      # the profile of common.extinction_profile
+    if name == "thin_slice":
+        assert list(nps[:2]) == [1, 1] and all(tr["ds"][0] == 0.0 for tr in base[:2])
+    elif name not in ("ragged", "unsorted", "lone_up"):
+        short = base[-len(L.SHORT_PATHS):]
+        want = [2, 2, 2, 2] if name == "coarse_steps" else L.SHORT_NP                       # (one step of 1 km leaves the top)
+        assert [tr["np"] for tr in short] == want
+        assert short[2]["tsurf"] != -999 and short[3]["tsurf"] != -999 and not np.any(short[3]["ds"])
+        assert short[0]["tsurf"] == -999 and short[1]["tsurf"] == -999

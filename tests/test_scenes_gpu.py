@@ -30,6 +30,9 @@ def hip():
 
 def scene_case(name, sort_by_time=False, **ctl_kw):
     case = common.limb_case(**ctl_kw)
+    if name.endswith("_ext"):         # the scene with an extinction that varies with altitude (regridded from the base)
+        common.extinction_profile(case.atm)
+        name = name[:-len("_ext")]
     atm, geom, _ = synth.scene(name, case.ctl, case.atm)
     if sort_by_time:                  # whole workgroups of the fused kernel share one slice: its LDS copy is made
         geom = geom[np.argsort(geom[:, 0], kind="stable")]
@@ -165,7 +168,7 @@ def edited_atm(case, v):
 
 @pytest.mark.parametrize("hydz", [-999.0, 10.0])
 @pytest.mark.parametrize("arrangement", ["fused", "batched"])
-@pytest.mark.parametrize("name", ["ragged", "lone_ends", "lone_up", "short_last"])
+@pytest.mark.parametrize("name", ["ragged", "lone_ends", "lone_up", "short_last", "ragged_ext"])
 def test_contributions(hip, oracle, name, arrangement, hydz):
     """formod_contrib_host: every variant against the oracle on the edited atmosphere.  With HYDZ >= 0 and H2O among
     the emitters the variants other than H2O's are one stacked call (time stamps shifted per copy), where every ray
@@ -191,6 +194,8 @@ def test_contributions(hip, oracle, name, arrangement, hydz):
         assert np.all((err <= RTOL * np.abs(r["rad"])) | (err <= 1e-14 * np.abs(ref["rad"]))), v
         terr = np.abs(out["tau_c"][v] - r["tau"])
         assert np.all(terr[fin] <= (RTOL * np.abs(r["tau"]) + common.tau_atol(r["tau"]))[fin]), v
+    if name.endswith("_ext"):
+        assert out["tau_c"][case.ctl.ng].min() < 0.9          # the extinction alone is not empty
 
 
 def _obs(geom, nd):
