@@ -207,6 +207,39 @@ size_t jur_state_size(jur_model_t const *m, atm_t const *atm);
 size_t jur_measurement_size(jur_model_t const *m, obs_t const *obs);
 int    jur_kernel(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, size_t mrows, size_t ncols);
 
+/* The Jacobian of a whole scene as per-ray blocks, for any number of rays.  A ray is traced through the slice
+ * [first, first + len) of the atmosphere that locate_atm hands it (jr_common.h:127-154) and through nothing else, so
+ * its rows of jur_kernel's matrix are exactly 0 outside the state elements of that slice: only those are computed.
+ *
+ * jur_scene_layout (host arithmetic, no GPU): slice of every ray with time stamp time[r], and where its block starts:
+ *   width[r] = number of state elements (atm2x order, ctl->ret*_zmin/zmax) whose point lies in the slice, 0 for a slice
+ *   of fewer than 2 points; rowptr[0] = 0, rowptr[r + 1] = rowptr[r] + width[r]; rowptr is [nr + 1].
+ * jur_scene_columns: the global state indices (columns of jur_kernel's matrix) of the slice, ascending; returns their
+ *   number (cols may be NULL to count) or JUR_EINVAL.  Slices are pairs (first, len), not profiles: a lone end point
+ *   joins its neighbour's slice, and a ray time stamp may match no profile.
+ * jur_kernel_scene_host: geom, rad (read first for the NaN mask), tau, tp, np_out as jur_formod_host; they return the
+ *   unperturbed forward model, the doubles of jur_formod_host on `atm`.  k holds rowptr[nr] * nd doubles: the block of
+ *   ray r starts at k + rowptr[r] * nd, is laid out [nd][width[r]] with the columns of jur_scene_columns, and entry
+ *   (id, e) is (y1 - y0) / h with the reference's step h (jurassic.c:833-836) -- the doubles of jur_kernel's entry.
+ *   A channel masked on input gives a row of NaN; rows are never compacted.  rowptr must be jur_scene_layout's
+ *   (JUR_EINVAL otherwise).  The perturbed slices, the replicated rays and the quotients are made on the device; rays
+ *   are taken in contiguous passes whose replicated count (width + 1 per ray) stays within max_rays_per_pass (0: a
+ *   sixteenth of what the stacked slices leave of the model's workspace budget, 4096 at least; a ray beyond it alone
+ *   goes alone); the blocks of a pass are copied straight into k
+ *   (pinned memory from jur_host_alloc travels fastest).
+ *   JUR_EINVAL, with a message: ctl->hydz >= 0 (the hydrostatic adjustment treats all points as one profile, so every
+ *   p, T or H2O element moves every pressure and there are no blocks: use jur_kernel); time stamps of atm not
+ *   ascending; atm->np outside 2..JUR_NP.  JUR_ENOMEM when the stacked slices exceed half the workspace budget (call
+ *   with the rays of fewer slices).  nr == 0 is JUR_OK; a state of zero elements gives the forward model alone.
+ *   The model holds `atm` afterwards, after a refusal or an error too (as jur_kernel).
+ * jur_model_last_scene_ms: the share of the stacking, replication and quotient kernels in the launches timed since
+ *   the last call (after jur_model_last_kernel_ms, which collects the events). */
+int  jur_scene_layout(ctl_t const *ctl, atm_t const *atm, long nr, double const *time, int *first, int *len, long *rowptr);
+long jur_scene_columns(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols);
+int  jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                           double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass);
+int  jur_model_last_scene_ms(jur_model_t *m, double *out_ms, long *out_launches);
+
 /* Curtis-Godson means along each line of sight (reference curtis_godson(), jr_common.h:455-473, which
  * upstream compiles only with -DCURTIS_GODSON for FORMOD=1): per ray, emitter and LOS point the
  * column-weighted pressure cgp, temperature cgt and the cumulative column cgu.  Host arrays

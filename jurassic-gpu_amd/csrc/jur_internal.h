@@ -147,6 +147,59 @@ int jurk_kat_update(jur_view_t const *v, int d, long n, int what, double const *
 /* LOS records of the traced chunk (after jurk_launch_trace): los[ray][nfield][JUR_NLOS], tsurf[ray], indexed by ray id */
 int jurk_kat_los(jur_view_t const *v, jur_chunk_t const *c, double *los, double *tsurf, void *stream);
 
+/* Block Jacobian of a scene (jur_kernel_scene_host).  The stacked atmosphere is a list of copies: copy 0 is the base
+ * atmosphere, copy j >= 1 the points of one slice with one state element raised.  All arrays are device memory. */
+typedef struct {
+  int ncopy;                    /* copies, the base included                                              */
+  int np0;                      /* points of the base atmosphere (row length of `base`)                   */
+  int nrow;                     /* rows of an atmosphere: 6 + ng + nw                                      */
+  int ng;
+  long nt;                      /* points of the stacked atmosphere (row length of `rows`)                */
+  long const *off;              /* [ncopy + 1] first stacked point of every copy; off[ncopy] = nt         */
+  int const *first;             /* [ncopy] first base point of the copy                                    */
+  int const *prow;              /* [ncopy] row of the raised value (-1: the base)                          */
+  int const *pip;               /* [ncopy] base point of the raised value                                  */
+  double const *base;           /* [nrow][np0] base rows (time stamps as stack_times leaves them)          */
+  double *rows;                 /* [nrow][nt] stacked rows, written                                        */
+  double *h;                    /* [ncopy] step of every copy, written (h[0] is not)                       */
+  double tmax, span;            /* copy j >= 1 carries the time stamp tmax + j * span                      */
+} jur_scene_stack_t;
+
+/* one pass: the rays [r0, r1) of the call, ray r replicated width[r] + 1 times from slot off(r) =
+ * (rowptr[r] - rowptr[r0]) + (r - r0) of the pass on */
+typedef struct {
+  long nr;                      /* rays of the call (row length of in_geom, out_tp)                        */
+  long r0, r1;
+  int nd;
+  long const *rowptr;           /* [nr + 1]                                                                */
+  int const *first, *len;       /* [nr] slice of every ray in the base atmosphere                          */
+  int const *copy0;             /* [nr] copy that raises the first state element of the ray's slice        */
+  long const *off;              /* [ncopy + 1] as jur_scene_stack_t                                        */
+  double const *atm_time;       /* [nt] time stamps of the stacked atmosphere                              */
+  double above;                 /* a time stamp above all of them                                          */
+  double const *in_geom;        /* [7][nr] the caller's geometry                                           */
+  double const *in_rad;         /* [nr][nd] the caller's radiances (NaN mask)                              */
+  long n;                       /* slots of the pass                                                       */
+  double *geom;                 /* [7][n] replicated geometry, written                                     */
+  double *rad, *tau, *tp;       /* [n][nd], [n][nd], [3][n] of the pass: rad written (mask), then the forward model's */
+  int *np;                      /* [n]                                                                     */
+  double const *h;              /* [ncopy]                                                                 */
+  double *k;                    /* [(rowptr[r1] - rowptr[r0]) * nd] blocks of the pass, written            */
+  double *out_rad, *out_tau;    /* [nr][nd] unperturbed results by ray, written                            */
+  double *out_tp;               /* [3][nr]                                                                 */
+  int *out_np;                  /* [nr]                                                                    */
+} jur_scene_pass_t;
+
+int jurk_scene_stack(jur_scene_stack_t const *a, void *stream);
+int jurk_scene_rays(jur_scene_pass_t const *a, void *stream);      /* geometry and mask of the pass */
+int jurk_scene_quot(jur_scene_pass_t const *a, long nk, void *stream);   /* the nk block elements and the unperturbed results of the pass */
+
+/* host arithmetic shared by jur_model.c and jur_scene.c (not exported) */
+#define JUR_HIDDEN __attribute__((visibility("hidden")))
+JUR_HIDDEN int jur_atm_slice(double const *time, long n, double t, long *first);
+JUR_HIDDEN size_t jur_state_vector(ctl_t const *ctl, atm_t const *atm, double *x, int *iqa, int *ipa);
+JUR_HIDDEN long jur_scene_slice_elements(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols, int *iqa, int *ipa);
+
 /* internals of a model that jur_multi.c needs (jur_model.c) */
 /* jur_formod_device on rays that are part of larger arrays: geometry field k at d_geom + k * ldg, tangent-point field k
  * at d_tp + k * ldtp (jur_formod_device: ldg = ldtp = nr) */

@@ -2275,12 +2275,128 @@ __global__ __launch_bounds__(256) void jur_kat_los_kernel(jur_view_t v, jur_chun
   if (ip == 0) tsurf[ray] = c.tsurf[r];
 }
 
+// ---- block Jacobian of a scene (jur_kernel_scene_host): streaming copies and one division per element ----------------
+// largest i in [lo, hi) with a[i] + bias(i) <= x, for a non-decreasing a[] with a[lo] + bias(lo) <= x
+template <bool PlusIndex>
+__device__ inline long scene_find(long const *__restrict__ a, long lo, long hi, long x) {
+  while (hi - lo > 1) {
+    long const mid = lo + ((hi - lo) >> 1);
+    if (a[mid] + (PlusIndex ? mid : 0) <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// The stacked atmosphere, one lane per (copy, point): copy 0 is the base atmosphere as it stands, copy j >= 1 the points
+// [first, first + len) of one slice under ONE time stamp tmax + j * span, with the value of row prow at base point pip
+// raised by the reference's step (jurassic.c:831-837), formed here from the base value with the host's operations
+// (kernel_ld in jur_model.c) and kept in h[j].  Lanes of a wavefront read and write consecutive points of every row.
+__global__ __launch_bounds__(256) void jur_scene_stack_kernel(jur_scene_stack_t a) {
+  long const t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.nt) return;
+  long const j = scene_find<false>(a.off, 0, a.ncopy, t);
+  long const src = a.first[j] + (t - a.off[j]);
+  int const prow = a.prow[j];
+  bool const raised = prow >= 0 && src == a.pip[j];
+  for (int row = 0; row < a.nrow; row++) {
+    double x = a.base[(long)row * a.np0 + src];
+    if (row == 0 && j > 0) x = a.tmax + (double)j * a.span;
+    if (raised && row == prow) {
+      double hh;
+      if (row == 4) hh = fmax(fabs(0.01 * x), 1e-7);
+      else if (row == 5) hh = 1;
+      else if (row < 6 + a.ng) hh = fmax(fabs(0.01 * x), 1e-15);
+      else hh = 1e-4;
+      a.h[j] = hh;
+      x = x + hh;
+    }
+    a.rows[(long)row * a.nt + t] = x;
+  }
+}
+
+// slot of ray r in the pass that starts at ray r0
+__device__ inline long scene_slot(jur_scene_pass_t const &a, long r) { return (a.rowptr[r] - a.rowptr[a.r0]) + (r - a.r0); }
+
+// Replicated geometry of a pass, one lane per slot: copy 0 of a ray carries the time stamp of its slice's first point in
+// the stacked base block (`above`, and with it one point alone, where its slice is a single point), copy e + 1 the time
+// stamp of the stacked copy that raises element e of its slice.
+__global__ __launch_bounds__(256) void jur_scene_rays_kernel(jur_scene_pass_t a) {
+  long const s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= a.n) return;
+  long const r = scene_find<true>(a.rowptr, a.r0, a.r1, s + a.rowptr[a.r0] + a.r0);
+  long const e = s - scene_slot(a, r);
+  double time;
+  if (e == 0) time = a.len[r] >= 2 ? a.atm_time[a.first[r]] : a.above;
+  else time = a.atm_time[a.off[a.copy0[r] + e - 1]];
+  a.geom[s] = time;
+  for (int q = 1; q < 7; q++) a.geom[q * a.n + s] = a.in_geom[q * a.nr + r];
+}
+
+// ... and its input radiances (the NaN mask), one lane per (slot, channel)
+__global__ __launch_bounds__(256) void jur_scene_mask_kernel(jur_scene_pass_t a) {
+  long const t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.n * a.nd) return;
+  long const s = t / a.nd, id = t - s * a.nd;
+  long const r = scene_find<true>(a.rowptr, a.r0, a.r1, s + a.rowptr[a.r0] + a.r0);
+  a.rad[t] = a.in_rad[r * a.nd + id];
+}
+
+// Difference quotients of a pass straight into the block layout, one lane per element: block of ray r at
+// (rowptr[r] - rowptr[r0]) * nd, [nd][width], entry (id, e) = (rad[copy e + 1][id] - rad[copy 0][id]) / h.
+__global__ __launch_bounds__(256) void jur_scene_quot_kernel(jur_scene_pass_t a) {
+  long const t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long const base = a.rowptr[a.r0];
+  if (t >= (a.rowptr[a.r1] - base) * a.nd) return;
+  long const r = scene_find<false>(a.rowptr, a.r0, a.r1, base + t / a.nd);   // the last ray that starts there: the one with columns
+  long const w = a.rowptr[r + 1] - a.rowptr[r];
+  long const local = t - (a.rowptr[r] - base) * a.nd;
+  long const id = local / w, e = local - id * w;
+  long const s0 = scene_slot(a, r);
+  a.k[t] = (a.rad[(s0 + e + 1) * a.nd + id] - a.rad[s0 * a.nd + id]) / a.h[a.copy0[r] + e];
+}
+
+// copy 0 of every ray of a pass into the caller's order, one lane per (ray, channel)
+__global__ __launch_bounds__(256) void jur_scene_gather_kernel(jur_scene_pass_t a) {
+  long const t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (a.r1 - a.r0) * a.nd) return;
+  long const r = a.r0 + t / a.nd, id = t - (r - a.r0) * a.nd;
+  long const s0 = scene_slot(a, r);
+  a.out_rad[r * a.nd + id] = a.rad[s0 * a.nd + id];
+  a.out_tau[r * a.nd + id] = a.tau[s0 * a.nd + id];
+  if (id == 0) {
+    for (int q = 0; q < 3; q++) a.out_tp[q * a.nr + r] = a.tp[q * a.n + s0];
+    a.out_np[r] = a.np[s0];
+  }
+}
+
 }  // namespace
 
 extern "C" int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream) {
   int const block = 256;
   hipLaunchKernelGGL(jur_pslope_kernel, dim3((v->atm_np + block - 1) / block), dim3(block), 0, (hipStream_t)stream,
                      v->atm_np, v->atm_z, v->atm_p, d_pslope);
+  return (int)hipGetLastError();
+}
+
+static unsigned scene_grid(long lanes) { return (unsigned)((lanes + 255) / 256); }
+
+extern "C" int jurk_scene_stack(jur_scene_stack_t const *a, void *stream) {
+  if (a->nt <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_stack_kernel, dim3(scene_grid(a->nt)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_rays(jur_scene_pass_t const *a, void *stream) {
+  if (a->n <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_rays_kernel, dim3(scene_grid(a->n)), dim3(256), 0, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(jur_scene_mask_kernel, dim3(scene_grid(a->n * a->nd)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+// (rowptr is device memory: the host passes the number of block elements of the pass)
+extern "C" int jurk_scene_quot(jur_scene_pass_t const *a, long nk, void *stream) {
+  if (nk > 0) hipLaunchKernelGGL(jur_scene_quot_kernel, dim3(scene_grid(nk)), dim3(256), 0, (hipStream_t)stream, *a);
+  if (a->r1 > a->r0)
+    hipLaunchKernelGGL(jur_scene_gather_kernel, dim3(scene_grid((a->r1 - a->r0) * a->nd)), dim3(256), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

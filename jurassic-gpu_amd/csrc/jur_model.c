@@ -93,7 +93,7 @@ struct jur_model {
   /* timing */
   int timing;
   hipEvent_t *evpool;           /* 2 events per timed launch                     */
-  unsigned char *evkind;        /* 0 trace, 1 ega, 2 combine, 3 fused (pencil), 4 contributions */
+  unsigned char *evkind;        /* 0 trace, 1 ega, 2 combine, 3 fused (pencil), 4 contributions, 5 scene Jacobian */
   int ntimed;
   double pencil_ms;
   long pencil_launches;
@@ -101,6 +101,10 @@ struct jur_model {
   long contrib_launches;
   double *d_ctb;                /* jur_formod_contrib_host: grow-only device scratch rad_c | tau_c */
   long ctb_cap;
+  void *d_scene;                /* jur_kernel_scene_host: grow-only device slab (base rows, descriptors, per-ray arrays, blocks of a pass) */
+  size_t scene_bytes;
+  double scene_ms;              /* its kernels' share (kind 5), collected with the others */
+  long scene_launches;
 };
 
 #define JUR_MAX_TIMED 4096
@@ -300,7 +304,7 @@ void jur_model_destroy(jur_model_t *m) {
   (void)hipSetDevice(m->device);
   if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_rec = NULL;
   void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp,
-                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_kq, m->d_ctb};
+                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_kq, m->d_ctb, m->d_scene};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
   if (m->h_io) (void)hipHostFree(m->h_io);
@@ -379,25 +383,6 @@ static void hydrostatic_rows(jur_model_t const *m, double *h, size_t stride, siz
               ig >= 0 ? h + (6 + (size_t)ig) * stride + at : NULL, h + 4 * stride + at);
 }
 
-/* locate_atm (jr_common.h:127-154): the slice [*first, *first + return) of the n points with time stamps `time` that
- * a ray with time stamp t is traced through */
-static int atm_slice(double const *time, long n, double t, long *first) {
-  long lo = 0, hi = n - 1;
-  while (hi > lo + 1) {
-    long const i = (lo + hi) / 2;
-    if (time[i] < t) lo = i; else hi = i;
-  }
-  long const lower = (0 == lo) ? lo : hi;
-  lo = lower;
-  hi = n - 1;
-  while (hi > lo + 1) {
-    long const i = (lo + hi) / 2;
-    if (time[i] > t) hi = i; else lo = i;
-  }
-  *first = lower;
-  return (int)(((hi == n - 1) ? n : hi) - lower);
-}
-
 /* Time stamps of an atmosphere of n points stacked behind others (kernel_ld, contrib_hydrostatic), shifted by `shift`.
  * Stacked, its end points are no longer the ends of the array, where locate_atm lets one point alone join the slice
  * next to it (jr_common.h:127-154): such a point takes that slice's time stamp, and the two points of a two-point
@@ -418,7 +403,34 @@ static void stack_times(double *dst, double const *src, int n, double shift) {
  * one point (not entered) gets `above`, a time stamp above all, and with it the last point alone. */
 static double stacked_ray_time(double const *time, int n, double t, double const *block_time, double above) {
   long first;
-  return atm_slice(time, n, t, &first) >= 2 ? block_time[first] : above;
+  return jur_atm_slice(time, n, t, &first) >= 2 ? block_time[first] : above;
+}
+
+/* what the kernels want to know about the n points with time stamps `time` and altitudes `z` */
+static void derive_atm_facts(jur_model_t *m, double const *time, double const *z, long n) {
+  jur_view_t *v = &m->view;
+  m->atm_slices = 1;
+  m->atm_zmin = m->atm_zmax = z[0];
+  for (long i = 1; i < n; i++) { if (z[i] < m->atm_zmin) m->atm_zmin = z[i]; if (z[i] > m->atm_zmax) m->atm_zmax = z[i]; }
+  v->atm_sorted = 1;
+  v->atm_maxslice = 1;
+  for (long i = 1; i < n; i++) {
+    if (time[i] != time[i - 1]) m->atm_slices++;
+    if (time[i] < time[i - 1]) v->atm_sorted = 0;
+  }
+  /* The slices are those locate_atm hands the rays whose time stamps match a profile -- not always the runs of equal
+   * time stamps: one point alone at either end of the atmosphere joins the slice next to it (jr_common.h:127-154).
+   * Ray time stamps that match no profile get one point, or the last two, which never needs a sorted axis. */
+  for (long a = 0; a < n;) {
+    long lo, b = a + 1;
+    while (b < n && time[b] == time[a]) b++;
+    int const len = jur_atm_slice(time, n, time[a], &lo);
+    if (len > v->atm_maxslice) v->atm_maxslice = len;
+    for (long i = lo + 2; i < lo + len; i++)            /* z strictly monotone inside the slice */
+      if ((z[i] > z[i - 1]) != (z[lo + 1] > z[lo]) || z[i] == z[i - 1]) v->atm_sorted = 0;
+    if (len >= 2 && z[lo + 1] == z[lo]) v->atm_sorted = 0;
+    a = b;
+  }
 }
 
 /* upload packed rows [6+ng+nw][n] and derive what the kernels want to know about them */
@@ -444,29 +456,7 @@ static int upload_atm_rows(jur_model_t *m, double const *h, long n) {
   }
   HIPCHK(hipMemcpyAsync(m->d_atm, h, sizeof(double) * nrow * (size_t)n, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
-  double const *time = h, *z = h + (size_t)n;
-  m->atm_slices = 1;
-  m->atm_zmin = m->atm_zmax = z[0];
-  for (long i = 1; i < n; i++) { if (z[i] < m->atm_zmin) m->atm_zmin = z[i]; if (z[i] > m->atm_zmax) m->atm_zmax = z[i]; }
-  v->atm_sorted = 1;
-  v->atm_maxslice = 1;
-  for (long i = 1; i < n; i++) {
-    if (time[i] != time[i - 1]) m->atm_slices++;
-    if (time[i] < time[i - 1]) v->atm_sorted = 0;
-  }
-  /* The slices are those locate_atm hands the rays whose time stamps match a profile -- not always the runs of equal
-   * time stamps: one point alone at either end of the atmosphere joins the slice next to it (jr_common.h:127-154).
-   * Ray time stamps that match no profile get one point, or the last two, which never needs a sorted axis. */
-  for (long a = 0; a < n;) {
-    long lo, b = a + 1;
-    while (b < n && time[b] == time[a]) b++;
-    int const len = atm_slice(time, n, time[a], &lo);
-    if (len > v->atm_maxslice) v->atm_maxslice = len;
-    for (long i = lo + 2; i < lo + len; i++)            /* z strictly monotone inside the slice */
-      if ((z[i] > z[i - 1]) != (z[lo + 1] > z[lo]) || z[i] == z[i - 1]) v->atm_sorted = 0;
-    if (len >= 2 && z[lo + 1] == z[lo]) v->atm_sorted = 0;
-    a = b;
-  }
+  derive_atm_facts(m, h, h + (size_t)n, n);
   double const *d = (double const *)m->d_atm;
   v->atm_np = (int)n;           /* (jurk_prepare_atm reads it) */
   v->atm_time = d; v->atm_z = d + (size_t)n; v->atm_lon = d + 2 * (size_t)n; v->atm_lat = d + 3 * (size_t)n;
@@ -683,7 +673,8 @@ int jur_model_last_kernel_ms(jur_model_t *m, double out_ms[3], long out_launches
     HIPCHK(hipEventElapsedTime(&ms, m->evpool[2 * i], m->evpool[2 * i + 1]));
     if (m->evkind[i] < 3) { out_ms[m->evkind[i]] += ms; out_launches[m->evkind[i]]++; }
     else if (m->evkind[i] == 3) { m->pencil_ms += ms; m->pencil_launches++; }
-    else { m->contrib_ms += ms; m->contrib_launches++; }
+    else if (m->evkind[i] == 4) { m->contrib_ms += ms; m->contrib_launches++; }
+    else { m->scene_ms += ms; m->scene_launches++; }
   }
   m->ntimed = 0;
   return JUR_OK;
@@ -705,6 +696,15 @@ int jur_model_last_contrib_ms(jur_model_t *m, double *out_ms, long *out_launches
   *out_launches = m->contrib_launches;
   m->contrib_ms = 0;
   m->contrib_launches = 0;
+  return JUR_OK;
+}
+
+/* ... and of the stacking, replication and quotient kernels of jur_kernel_scene_host (same protocol) */
+int jur_model_last_scene_ms(jur_model_t *m, double *out_ms, long *out_launches) {
+  *out_ms = m->scene_ms;
+  *out_launches = m->scene_launches;
+  m->scene_ms = 0;
+  m->scene_launches = 0;
   return JUR_OK;
 }
 
@@ -1527,30 +1527,7 @@ done:
 }
 
 /* ---- retrieval Jacobian -------------------------------------------------------- */
-/* State vector of the atmosphere inside the retrieval windows (atm2x, jurassic.c:1491-1513):
- * quantity index iqa (0 p, 1 T, 2+g q, 2+ng+w k) and atmosphere point ipa per element. */
-static size_t state_vector(ctl_t const *ctl, atm_t const *atm, double *x, int *iqa, int *ipa) {
-  size_t n = 0;
-  int const nquant = 2 + ctl->ng + ctl->nw;
-  for (int iq = 0; iq < nquant; iq++) {
-    double zmin, zmax;
-    double const *value;
-    if (iq == 0) { zmin = ctl->retp_zmin; zmax = ctl->retp_zmax; value = atm->p; }
-    else if (iq == 1) { zmin = ctl->rett_zmin; zmax = ctl->rett_zmax; value = atm->t; }
-    else if (iq < 2 + ctl->ng) { zmin = ctl->retq_zmin[iq - 2]; zmax = ctl->retq_zmax[iq - 2]; value = atm->q[iq - 2]; }
-    else { int const w = iq - 2 - ctl->ng; zmin = ctl->retk_zmin[w]; zmax = ctl->retk_zmax[w]; value = atm->k[w]; }
-    for (int ip = 0; ip < atm->np; ip++)
-      if (atm->z[ip] >= zmin && atm->z[ip] <= zmax) {
-        if (x) x[n] = value[ip];
-        if (iqa) iqa[n] = iq;
-        if (ipa) ipa[n] = ip;
-        n++;
-      }
-  }
-  return n;
-}
-
-size_t jur_state_size(jur_model_t const *m, atm_t const *atm) { return state_vector(m->ctl, atm, NULL, NULL, NULL); }
+size_t jur_state_size(jur_model_t const *m, atm_t const *atm) { return jur_state_vector(m->ctl, atm, NULL, NULL, NULL); }
 
 size_t jur_measurement_size(jur_model_t const *m, obs_t const *obs) {
   size_t n = 0;
@@ -1573,12 +1550,12 @@ static int kernel_ld(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, si
   ctl_t const *ctl = m->ctl;
   int const np0 = atm->np, nr = obs->nr, nd = ctl->nd, ng = m->view.ng, nw = m->view.nw;
   if (np0 < 2 || np0 > JUR_NP || nr < 1 || nr > JUR_NR) { jur_set_error("jur_kernel: bad atm->np / obs->nr"); return JUR_EINVAL; }
-  size_t const n = state_vector(ctl, atm, NULL, NULL, NULL);
+  size_t const n = jur_state_vector(ctl, atm, NULL, NULL, NULL);
   if (n != ncols) { jur_set_error("jur_kernel: state vector has %zu elements, matrix has %zu columns", n, ncols); return JUR_EINVAL; }
   if (jur_measurement_size(m, obs) != mrows) { jur_set_error("jur_kernel: measurement vector size does not match the matrix rows"); return JUR_EINVAL; }
   double *x0 = (double *)malloc(sizeof(double) * (n + 1)), *hstep = (double *)malloc(sizeof(double) * (n + 1));
   int *iqa = (int *)malloc(sizeof(int) * (n + 1)), *ipa = (int *)malloc(sizeof(int) * (n + 1));
-  state_vector(ctl, atm, x0, iqa, ipa);
+  jur_state_vector(ctl, atm, x0, iqa, ipa);
 
   size_t const ncopy = n + 1, nrow = 6 + (size_t)ng + nw;
   size_t const NT = ncopy * (size_t)np0, NRT = ncopy * (size_t)nr;
@@ -1686,6 +1663,294 @@ done:
     if (jur_model_set_atm(m, atm) != JUR_OK) { m->view.atm_np = 0; m->h_atm_n = 0; }
     jur_set_error("%s", msg);
   }
+  return rc;
+}
+
+/* ---- block Jacobian of a scene -------------------------------------------------- */
+/* Events around the kernels of jur_kernel_scene_host while timing is on (kind 5) */
+static int scene_timed_begin(jur_model_t *m, hipStream_t s) {
+  int const ti = (m->timing && m->ntimed < JUR_MAX_TIMED) ? m->ntimed++ : -1;
+  if (ti >= 0) { m->evkind[ti] = 5; if (hipEventRecord(m->evpool[2 * ti], s) != hipSuccess) (void)hipGetLastError(); }
+  return ti;
+}
+static void scene_timed_end(jur_model_t *m, int ti, hipStream_t s) {
+  if (ti >= 0 && hipEventRecord(m->evpool[2 * ti + 1], s) != hipSuccess) (void)hipGetLastError();
+}
+
+/* Sibling of upload_atm_rows for rows that a kernel is about to write on the device: makes room for nt points in the
+ * model's slab, waits for readers of the old rows and points the view at the new ones.  No host image of these rows
+ * exists, so the facts come from the base atmosphere they are stacked from: atm_sorted, atm_maxslice and the altitude
+ * range are the base's (every copy is a slice of it under one time stamp of its own), the slices the base's plus one
+ * per copy.  The caller fills the rows on the model's stream and then runs jurk_prepare_atm on them. */
+static int install_stacked_rows(jur_model_t *m, atm_t const *base, long nt, long ncopies) {
+  HIPCHK(hipSetDevice(m->device));
+  jur_view_t *v = &m->view;
+  size_t const ng = (size_t)v->ng, nrow = 6 + ng + (size_t)v->nw, n = (size_t)nt;
+  v->atm_np = 0;
+  if (nt > m->atm_cap) {
+    if (m->d_atm) (void)hipFree(m->d_atm);
+    m->d_atm = NULL;
+    m->atm_cap = 0;
+    HIPCHK(hipMalloc(&m->d_atm, sizeof(double) * (nrow + 1) * n));
+    m->atm_cap = (int)nt;
+  }
+  if (m->have_done) {
+    HIPCHK(hipEventSynchronize(m->ev_done));
+    m->have_done = 0;
+  }
+  derive_atm_facts(m, base->time, base->z, base->np);
+  m->atm_slices += (int)ncopies;
+  double const *d = (double const *)m->d_atm;
+  v->atm_np = (int)nt;
+  v->atm_time = d; v->atm_z = d + n; v->atm_lon = d + 2 * n; v->atm_lat = d + 3 * n;
+  v->atm_p = d + 4 * n; v->atm_t = d + 5 * n;
+  v->atm_q = d + 6 * n; v->atm_k = d + (6 + ng) * n;
+  v->atm_pslope = d + nrow * n;
+  return JUR_OK;
+}
+
+/* a distinct slice of the scene: points [first, first + len), its state elements raised by copies copy0 ... */
+typedef struct { int first, len, next; long copy0, nel; } scene_slice_t;
+
+static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                             double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
+  if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("jur_kernel_scene_host: bad arguments"); return JUR_EINVAL; }
+  ctl_t const *ctl = m->ctl;
+  if (ctl->hydz >= 0) {
+    jur_set_error("jur_kernel_scene_host: hydz = %g >= 0 adjusts all points as one profile, so every p, T or H2O element moves "
+                  "every pressure and the Jacobian has no blocks: use jur_kernel", ctl->hydz);
+    return JUR_EINVAL;
+  }
+  int const np0 = atm->np, nd = ctl->nd, ng = m->view.ng, nw = m->view.nw;
+  if (np0 < 2 || np0 > JUR_NP) { jur_set_error("jur_kernel_scene_host: need 2..%d atmospheric points", JUR_NP); return JUR_EINVAL; }
+  for (int i = 1; i < np0; i++)
+    if (!(atm->time[i] >= atm->time[i - 1])) {
+      jur_set_error("jur_kernel_scene_host: the time stamps of the atmosphere are not ascending (point %d): the slices of a "
+                    "stacked atmosphere cannot reproduce locate_atm there", i);
+      return JUR_EINVAL;
+    }
+  if (nr == 0) return JUR_OK;
+  if (nr > 0x7fffffffL) { jur_set_error("jur_kernel_scene_host: at most 2^31-1 rays per call"); return JUR_EINVAL; }
+  if (!geom || !rad || !tau || !tp || !rowptr) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
+
+  size_t const NR = (size_t)nr, nrow = 6 + (size_t)ng + nw;
+  int rc = JUR_OK, enqueued = 0;
+  int *first = (int *)malloc(sizeof(int) * 3 * NR), *len = first ? first + NR : NULL, *copy0 = first ? len + NR : NULL;
+  long *rp = (long *)malloc(sizeof(long) * (NR + 1));
+  int *head = (int *)malloc(sizeof(int) * (size_t)np0);
+  scene_slice_t *sl = NULL;
+  long *off = NULL, *pass = NULL;
+  int *cdesc = NULL, *iqa = NULL, *ipa = NULL;
+  double *hbase = NULL;
+  if (!first || !rp || !head) { rc = JUR_ENOMEM; goto done; }
+  if ((rc = jur_scene_layout(ctl, atm, nr, geom[0], first, len, rp))) goto done;
+  if (memcmp(rp, rowptr, sizeof(long) * (NR + 1))) {
+    jur_set_error("jur_kernel_scene_host: rowptr is not jur_scene_layout's for these rays, this atmosphere and these windows");
+    rc = JUR_EINVAL;
+    goto done;
+  }
+  if (rp[nr] > 0 && !k) { jur_set_error("jur_kernel_scene_host: null argument"); rc = JUR_EINVAL; goto done; }
+
+  /* the distinct slices that have state elements, in the order the rays meet them, and their copies */
+  long nslice = 0, ncopies = 0, nt = np0;
+  {
+    long cap = 0;
+    for (int i = 0; i < np0; i++) head[i] = -1;
+    for (long r = 0; r < nr; r++) {
+      copy0[r] = 0;
+      if (rp[r + 1] == rp[r]) continue;
+      int q = head[first[r]];
+      while (q >= 0 && sl[q].len != len[r]) q = sl[q].next;
+      if (q < 0) {
+        if (nslice == cap) {
+          cap = cap ? 2 * cap : 64;
+          scene_slice_t *grown = (scene_slice_t *)realloc(sl, sizeof *sl * (size_t)cap);
+          if (!grown) { rc = JUR_ENOMEM; goto done; }
+          sl = grown;
+        }
+        q = (int)nslice++;
+        sl[q].first = first[r]; sl[q].len = len[r]; sl[q].next = head[first[r]];
+        sl[q].copy0 = 1 + ncopies; sl[q].nel = rp[r + 1] - rp[r];
+        head[first[r]] = q;
+        ncopies += sl[q].nel;
+        nt += sl[q].nel * sl[q].len;
+      }
+      if (sl[q].copy0 > 0x7fffffffL) break;           /* (refused below) */
+      copy0[r] = (int)sl[q].copy0;
+    }
+  }
+  long const ncopy = ncopies + 1;
+  size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)nt;
+  if (nt > 0x7fffffffL || (long)atm_bytes > m->ws_budget / 2) {
+    jur_set_error("jur_kernel_scene_host: the stacked atmosphere (%ld points, %zu bytes) exceeds the workspace budget: "
+                  "call with the rays of fewer slices at a time", nt, atm_bytes);
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+
+  /* passes: contiguous ranges of rays whose slots (width + 1 each) stay within the cap; one ray beyond it goes alone */
+  size_t const slot_bytes = sizeof(double) * (10 + 3 * (size_t)nd) + sizeof(int);
+  long cap = max_rays_per_pass;
+  if (cap == 0) {
+    /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
+     * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
+     * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
+    long const avail = (m->ws_budget - (long)atm_bytes) / 16;
+    cap = avail / (long)slot_bytes;
+    if (cap < 4096) cap = 4096;
+  }
+  if (cap > 0x7fffffffL) cap = 0x7fffffffL;
+  long npass = 0, nmax = 0, kmax = 0;
+  pass = (long *)malloc(sizeof(long) * (NR + 1));
+  if (!pass) { rc = JUR_ENOMEM; goto done; }
+  for (long r0 = 0; r0 < nr;) {
+    long r1 = r0 + 1;
+    while (r1 < nr && (rp[r1 + 1] - rp[r0]) + (r1 + 1 - r0) <= cap) r1++;
+    long const n = (rp[r1] - rp[r0]) + (r1 - r0);
+    if (n > 0x7fffffffL) { jur_set_error("jur_kernel_scene_host: a ray with 2^31 state elements"); rc = JUR_EINVAL; goto done; }
+    if (n > nmax) nmax = n;
+    if (rp[r1] - rp[r0] > kmax) kmax = rp[r1] - rp[r0];
+    pass[npass++] = r0;
+    r0 = r1;
+  }
+  pass[npass] = nr;
+  kmax *= nd;
+
+  /* descriptors of the copies (copy 0: the base) and the base rows */
+  off = (long *)malloc(sizeof(long) * ((size_t)ncopy + 1));
+  cdesc = (int *)malloc(sizeof(int) * 3 * (size_t)ncopy);
+  iqa = (int *)malloc(sizeof(int) * 2 * (size_t)np0 * (2 + (size_t)ng + nw));
+  hbase = (double *)malloc(sizeof(double) * nrow * (size_t)np0);
+  if (!off || !cdesc || !iqa || !hbase) { rc = JUR_ENOMEM; goto done; }
+  ipa = iqa + (size_t)np0 * (2 + (size_t)ng + nw);
+  int *const cfirst = cdesc, *const prow = cdesc + ncopy, *const pip = cdesc + 2 * ncopy;
+  off[0] = 0; cfirst[0] = 0; prow[0] = -1; pip[0] = 0;
+  off[1] = np0;
+  for (long q = 0; q < nslice; q++) {
+    long const n = jur_scene_slice_elements(ctl, atm, sl[q].first, sl[q].len, NULL, iqa, ipa);
+    if (n != sl[q].nel) { jur_set_error("jur_kernel_scene_host: layout out of step"); rc = JUR_EINVAL; goto done; }
+    for (long e = 0; e < n; e++) {
+      long const j = sl[q].copy0 + e;
+      cfirst[j] = sl[q].first;
+      prow[j] = (iqa[e] == 0) ? 4 : (iqa[e] == 1) ? 5 : 4 + iqa[e];   /* q rows start at 6, k rows follow */
+      pip[j] = ipa[e];
+      off[j + 1] = off[j] + sl[q].len;
+    }
+  }
+  pack_atm_rows(m, atm, hbase, (size_t)np0, 0);
+  stack_times(hbase, atm->time, np0, 0.0);
+  double tmin = atm->time[0], tmax = atm->time[0];
+  for (int i = 0; i < np0; i++) { tmin = fmin(tmin, atm->time[i]); tmax = fmax(tmax, atm->time[i]); }
+  for (long i = 0; i < nr; i++) { tmin = fmin(tmin, geom[0][i]); tmax = fmax(tmax, geom[0][i]); }
+  double const span = (tmax - tmin) + 1.0;
+
+  /* the device slab: doubles, then 64-bit integers, then 32-bit ones */
+  size_t const nrd = NR * (size_t)nd;
+  size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_rad = o_inrad + nrd,
+               o_tau = o_rad + nrd, o_tp = o_tau + nrd, o_h = o_tp + 3 * NR, o_k = o_h + (size_t)ncopy,
+               o_rowptr = o_k + (size_t)kmax, o_off = o_rowptr + NR + 1, o_int = o_off + (size_t)ncopy + 1;
+  size_t const nint = 4 * NR + 3 * (size_t)ncopy, bytes = sizeof(double) * o_int + sizeof(int) * nint;
+  if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("jur_kernel_scene_host: cannot select the device"); rc = JUR_EHIP; goto done; }
+  hipStream_t const s = m->stream;
+  if ((rc = wait_done(m, s))) goto done;
+  if (bytes > m->scene_bytes) {
+    if (m->d_scene) (void)hipFree(m->d_scene);
+    m->d_scene = NULL; m->scene_bytes = 0;
+    if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
+      (void)hipGetLastError(); jur_set_error("jur_kernel_scene_host: no device memory for %zu bytes", bytes); rc = JUR_ENOMEM; goto done;
+    }
+    m->scene_bytes = bytes;
+  }
+  if ((rc = ensure_io(m, nmax, 0))) goto done;
+  {
+    double *const D = (double *)m->d_scene;
+    long *const L = (long *)m->d_scene;
+    int *const I = (int *)(D + o_int);
+    int *const d_first = I, *const d_len = I + NR, *const d_copy0 = I + 2 * NR, *const d_np = I + 3 * NR, *const d_cdesc = I + 4 * NR;
+    enqueued = 1;
+    hipError_t e = hipMemcpyAsync(D + o_base, hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
+    for (int q = 0; q < 7 && e == hipSuccess; q++) e = hipMemcpyAsync(D + o_geom + (size_t)q * NR, geom[q], sizeof(double) * NR, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D + o_inrad, rad, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(L + o_rowptr, rp, sizeof(long) * (NR + 1), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(L + o_off, off, sizeof(long) * ((size_t)ncopy + 1), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_first, first, sizeof(int) * 3 * NR, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cdesc, cdesc, sizeof(int) * 3 * (size_t)ncopy, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
+    if (e != hipSuccess) { jur_set_error("jur_kernel_scene_host: %s", hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+
+    m->h_atm_n = 0;                              /* the device no longer holds the caller's atmosphere */
+    if ((rc = install_stacked_rows(m, atm, nt, ncopies))) goto done;
+    jur_scene_stack_t st;
+    memset(&st, 0, sizeof st);
+    st.ncopy = (int)ncopy; st.np0 = np0; st.nrow = (int)nrow; st.ng = ng; st.nt = nt;
+    st.off = L + o_off; st.first = d_cdesc; st.prow = d_cdesc + ncopy; st.pip = d_cdesc + 2 * ncopy;
+    st.base = D + o_base; st.rows = (double *)m->d_atm; st.h = D + o_h;
+    st.tmax = tmax; st.span = span;
+    int ti = scene_timed_begin(m, s);
+    int ek = jurk_scene_stack(&st, s);
+    scene_timed_end(m, ti, s);
+    if (!ek) ek = jurk_prepare_atm(&m->view, (double *)m->d_atm + nrow * (size_t)nt, s);
+    /* the one wait before the passes: the uploads have left the host arrays, the stacked rows stand */
+    if (ek || hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipGetLastError(); m->view.atm_np = 0; jur_set_error("jur_kernel_scene_host: stacking the atmosphere failed"); rc = JUR_EHIP; goto done;
+    }
+    if ((rc = jur_model_reserve(m, nmax))) goto done;   /* the forward model's workspace for the largest pass, before the first */
+
+    jur_scene_pass_t a;
+    memset(&a, 0, sizeof a);
+    a.nr = nr; a.nd = nd;
+    a.rowptr = L + o_rowptr; a.first = d_first; a.len = d_len; a.copy0 = d_copy0; a.off = L + o_off;
+    a.atm_time = m->view.atm_time;
+    a.above = tmax + ((double)ncopy + 1.0) * span;
+    a.in_geom = D + o_geom; a.in_rad = D + o_inrad;
+    a.h = D + o_h; a.k = D + o_k;
+    a.out_rad = D + o_rad; a.out_tau = D + o_tau; a.out_tp = D + o_tp; a.out_np = d_np;
+    for (long p = 0; p < npass; p++) {
+      long const r0 = pass[p], r1 = pass[p + 1], n = (rp[r1] - rp[r0]) + (r1 - r0), nk = (rp[r1] - rp[r0]) * nd;
+      size_t const N = (size_t)n;
+      a.r0 = r0; a.r1 = r1; a.n = n;
+      a.geom = m->d_io; a.rad = a.geom + 7 * N; a.tau = a.rad + N * nd; a.tp = a.tau + N * nd; a.np = m->d_io_np;
+      ti = scene_timed_begin(m, s);
+      ek = jurk_scene_rays(&a, s);
+      scene_timed_end(m, ti, s);
+      if (ek) { jur_set_error("jur_kernel_scene_host: replication kernel launch failed"); rc = JUR_EHIP; goto done; }
+      if ((rc = jur_formod_device(m, n, a.geom, a.rad, a.tau, a.tp, a.np, m->d_status, s))) goto done;
+      ti = scene_timed_begin(m, s);
+      ek = jurk_scene_quot(&a, nk, s);
+      scene_timed_end(m, ti, s);
+      if (ek) { jur_set_error("jur_kernel_scene_host: quotient kernel launch failed"); rc = JUR_EHIP; goto done; }
+      /* the blocks of the pass go home; the one wait of the pass */
+      e = nk > 0 ? hipMemcpyAsync(k + (size_t)rp[r0] * nd, a.k, sizeof(double) * (size_t)nk, hipMemcpyDeviceToHost, s) : hipSuccess;
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      if (e != hipSuccess) { jur_set_error("jur_kernel_scene_host: %s", hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    }
+    e = hipMemcpyAsync(rad, a.out_rad, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(tau, a.out_tau, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
+    for (int q = 0; q < 3 && e == hipSuccess; q++) e = hipMemcpyAsync(tp[q], a.out_tp + (size_t)q * NR, sizeof(double) * NR, hipMemcpyDeviceToHost, s);
+    if (np_out && e == hipSuccess) e = hipMemcpyAsync(np_out, a.out_np, sizeof(int) * NR, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("jur_kernel_scene_host: %s", hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
+  }
+done:
+  if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
+  free(first); free(rp); free(head); free(sl); free(off); free(pass); free(cdesc); free(iqa); free(hbase);
+  return rc;
+}
+
+int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                          double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
+  if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
+  int rc = kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass);
+  /* leave the model with the caller's atmosphere -- after a refusal or an error too: never with the stacked one, which
+   * later calls would accept; if it cannot go back, with none ("no atmosphere set") */
+  if (atm->np < 2 || atm->np > JUR_NP) return rc;
+  if (rc == JUR_OK) return jur_model_set_atm(m, atm);
+  char msg[512];
+  snprintf(msg, sizeof msg, "%s", jur_last_error());
+  if (jur_model_set_atm(m, atm) != JUR_OK) { m->view.atm_np = 0; m->h_atm_n = 0; }
+  jur_set_error("%s", msg);
   return rc;
 }
 

@@ -1,0 +1,109 @@
+/* jur_scene.c -- layout of the block Jacobian of a scene (jur_kernel_scene_host): which slice of the atmosphere every
+ * ray is traced through and which state elements lie in it.  Host arithmetic only: no GPU, no model. */
+#include <stdlib.h>
+#include "jur_internal.h"
+
+/* locate_atm (jr_common.h:127-154): the slice [*first, *first + return) of the n points with time stamps `time` that
+ * a ray with time stamp t is traced through */
+int jur_atm_slice(double const *time, long n, double t, long *first) {
+  long lo = 0, hi = n - 1;
+  while (hi > lo + 1) {
+    long const i = (lo + hi) / 2;
+    if (time[i] < t) lo = i; else hi = i;
+  }
+  long const lower = (0 == lo) ? lo : hi;
+  lo = lower;
+  hi = n - 1;
+  while (hi > lo + 1) {
+    long const i = (lo + hi) / 2;
+    if (time[i] > t) hi = i; else lo = i;
+  }
+  *first = lower;
+  return (int)(((hi == n - 1) ? n : hi) - lower);
+}
+
+/* retrieval window and values of quantity iq (0 p, 1 T, 2+g q, 2+ng+w k) */
+static double const *quantity(ctl_t const *ctl, atm_t const *atm, int iq, double *zmin, double *zmax) {
+  if (iq == 0) { *zmin = ctl->retp_zmin; *zmax = ctl->retp_zmax; return atm->p; }
+  if (iq == 1) { *zmin = ctl->rett_zmin; *zmax = ctl->rett_zmax; return atm->t; }
+  if (iq < 2 + ctl->ng) { *zmin = ctl->retq_zmin[iq - 2]; *zmax = ctl->retq_zmax[iq - 2]; return atm->q[iq - 2]; }
+  int const w = iq - 2 - ctl->ng;
+  *zmin = ctl->retk_zmin[w]; *zmax = ctl->retk_zmax[w];
+  return atm->k[w];
+}
+
+/* State vector of the atmosphere inside the retrieval windows (atm2x, jurassic.c:1491-1513):
+ * quantity index iqa (0 p, 1 T, 2+g q, 2+ng+w k) and atmosphere point ipa per element. */
+size_t jur_state_vector(ctl_t const *ctl, atm_t const *atm, double *x, int *iqa, int *ipa) {
+  size_t n = 0;
+  int const nquant = 2 + ctl->ng + ctl->nw;
+  for (int iq = 0; iq < nquant; iq++) {
+    double zmin, zmax;
+    double const *value = quantity(ctl, atm, iq, &zmin, &zmax);
+    for (int ip = 0; ip < atm->np; ip++)
+      if (atm->z[ip] >= zmin && atm->z[ip] <= zmax) {
+        if (x) x[n] = value[ip];
+        if (iqa) iqa[n] = iq;
+        if (ipa) ipa[n] = ip;
+        n++;
+      }
+  }
+  return n;
+}
+
+/* The state elements of the points [first, first + len), in the state vector's order (quantity-major, point index
+ * inside): global index, quantity and point of each; any output may be NULL.  Returns their number. */
+long jur_scene_slice_elements(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols, int *iqa, int *ipa) {
+  long n = 0, base = 0;
+  int const nquant = 2 + ctl->ng + ctl->nw;
+  for (int iq = 0; iq < nquant; iq++) {
+    double zmin, zmax;
+    (void)quantity(ctl, atm, iq, &zmin, &zmax);
+    for (int ip = 0; ip < atm->np; ip++) {
+      if (!(atm->z[ip] >= zmin && atm->z[ip] <= zmax)) continue;
+      if (ip >= first && ip < first + len) {
+        if (cols) cols[n] = base;
+        if (iqa) iqa[n] = iq;
+        if (ipa) ipa[n] = ip;
+        n++;
+      }
+      base++;
+    }
+  }
+  return n;
+}
+
+long jur_scene_columns(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols) {
+  if (!ctl || !atm || first < 0 || len < 0 || (long)first + len > atm->np) {
+    jur_set_error("scene_columns: slice [%d, %d + %d) outside the atmosphere", first, first, len);
+    return JUR_EINVAL;
+  }
+  return jur_scene_slice_elements(ctl, atm, first, len, cols, NULL, NULL);
+}
+
+int jur_scene_layout(ctl_t const *ctl, atm_t const *atm, long nr, double const *time, int *first, int *len, long *rowptr) {
+  if (!ctl || !atm || nr < 0 || !rowptr || (nr > 0 && (!time || !first || !len))) { jur_set_error("scene_layout: bad arguments"); return JUR_EINVAL; }
+  int const np = atm->np;
+  if (np < 2 || np > JUR_NP) { jur_set_error("scene_layout: need 2..%d atmospheric points", JUR_NP); return JUR_EINVAL; }
+  /* elements of the state at or before every point, over all quantities: the width of a slice is a difference of two */
+  long *upto = (long *)calloc((size_t)np + 1, sizeof(long));
+  if (!upto) return JUR_ENOMEM;
+  int const nquant = 2 + ctl->ng + ctl->nw;
+  for (int iq = 0; iq < nquant; iq++) {
+    double zmin, zmax;
+    (void)quantity(ctl, atm, iq, &zmin, &zmax);
+    for (int ip = 0; ip < np; ip++)
+      if (atm->z[ip] >= zmin && atm->z[ip] <= zmax) upto[ip + 1]++;
+  }
+  for (int ip = 0; ip < np; ip++) upto[ip + 1] += upto[ip];
+  rowptr[0] = 0;
+  for (long r = 0; r < nr; r++) {
+    long lo;
+    int const n = jur_atm_slice(atm->time, np, time[r], &lo);
+    first[r] = (int)lo;
+    len[r] = n;
+    rowptr[r + 1] = rowptr[r] + (n >= 2 ? upto[lo + n] - upto[lo] : 0);
+  }
+  free(upto);
+  return JUR_OK;
+}

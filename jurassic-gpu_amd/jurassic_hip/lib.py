@@ -99,6 +99,13 @@ def lib():
         L.jur_measurement_size.restype = C.c_size_t
         L.jur_measurement_size.argtypes = [C.c_void_p, C.c_void_p]
         L.jur_kernel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, dp, C.c_size_t, C.c_size_t]
+        ip_, lp_ = C.POINTER(C.c_int), C.POINTER(C.c_long)
+        L.jur_scene_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_long, dp, ip_, ip_, lp_]
+        L.jur_scene_columns.restype = C.c_long
+        L.jur_scene_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, lp_]
+        L.jur_kernel_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_, dp,
+                                            C.c_long]
+        L.jur_model_last_scene_ms.argtypes = [C.c_void_p, dp, lp_]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -231,6 +238,7 @@ class Model:
         self.nd = ctl.nd
         self.ng = ctl.ng
         self.nw = ctl.nw
+        self.ctl = ctl                 # (the model holds a private copy; kernel_scene lays its blocks out with this one)
 
     def close(self):
         if getattr(self, "h", None):
@@ -346,6 +354,38 @@ class Model:
         _chk(lib().jur_kernel(self.h, C.byref(atm), C.byref(obs), _p(k), m, n))
         return k
 
+    def kernel_scene(self, atm, geom, rad_in=None, max_rays_per_pass=0, rowptr=None):
+        """Block Jacobian of a scene (jur_kernel_scene_host).  geom: (nr, 7) -> the formod_host dict plus first, len
+        (nr,), rowptr (nr + 1,) of scene_layout and the flat k: the block of ray r is
+        k[rowptr[r] * nd : rowptr[r + 1] * nd].reshape(nd, width[r]), its columns those of scene_columns(first[r],
+        len[r]).  rowptr: pass one to have it checked instead of the layout's own.
+        The layout is made with the ctl_t the Model was created with, of which the model keeps a copy of its own: change
+        that ctl_t afterwards (retrieval windows, say) and the call is refused with EINVAL (rowptr) -- make a new Model."""
+        g = np.ascontiguousarray(np.asarray(geom, dtype=np.float64).T)
+        nr, nd = g.shape[1], self.nd
+        lay = _scene_layout(self.ctl, atm, g[0] if nr else np.zeros(0))
+        rp = lay["rowptr"] if rowptr is None else np.ascontiguousarray(rowptr, dtype=np.int64)
+        if rp.shape != lay["rowptr"].shape:
+            raise ValueError("rowptr holds %d entries, the call has %d rays" % (len(rp), nr))
+        rad = np.zeros((nr, nd)) if rad_in is None else np.ascontiguousarray(rad_in, dtype=np.float64).copy()
+        tau = np.zeros((nr, nd))
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        k = np.zeros(int(lay["rowptr"][-1]) * nd)
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
+        _chk(lib().jur_kernel_scene_host(self.h, C.byref(atm), nr, garr, _p(rad), _p(tau), tarr,
+                                         npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(C.POINTER(C.c_long)),
+                                         _p(k), max_rays_per_pass))
+        return dict(rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, first=lay["first"], len=lay["len"],
+                    rowptr=lay["rowptr"], k=k)
+
+    def scene_ms(self):
+        """The share of kernel_scene's own kernels in the launches timed since the last call (call kernel_ms first)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        _chk(lib().jur_model_last_scene_ms(self.h, C.byref(ms), C.byref(n)))
+        return dict(scene_ms=ms.value, scene_launches=n.value)
+
     # known-answer hooks: device functions on arrays (include/jurassic_hip.h)
     def kat_ega_eps(self, ig, id_, tau, t, u, p, mode=3, chain=False):
         a = [np.ascontiguousarray(x, dtype=np.float64) for x in (tau, t, u, p)]
@@ -422,6 +462,7 @@ class Model:
 
 
 ARITH_FAST, ARITH_EXACT = 0, 1
+EINVAL = -1                            # JUR_EINVAL
 ENLOS = -5                             # JUR_ENLOS
 
 
@@ -440,6 +481,51 @@ def kernel(ctl, atm, obs, m, n, tda=None):
     lib().kernel(C.byref(ctl), C.byref(atm), C.byref(obs), C.byref(mat))
     assert np.all(store[:, n:] == -7.0)               # nothing written beyond the matrix's width
     return store[:, :n].copy()
+
+
+def _scene_layout(ctl, atm, time):
+    t = np.ascontiguousarray(time, dtype=np.float64)
+    nr = len(t)
+    first, length = np.zeros(nr, dtype=np.int32), np.zeros(nr, dtype=np.int32)
+    rowptr = np.zeros(nr + 1, dtype=np.int64)
+    ip_ = C.POINTER(C.c_int)
+    _chk(lib().jur_scene_layout(C.byref(ctl), C.byref(atm), nr, _p(t), first.ctypes.data_as(ip_), length.ctypes.data_as(ip_),
+                                rowptr.ctypes.data_as(C.POINTER(C.c_long))))
+    return dict(first=first, len=length, rowptr=rowptr)
+
+
+def scene_layout(ctl, atm, time):
+    """jur_scene_layout (host arithmetic, no GPU): the slice [first, first + len) of the atmosphere that every ray time
+    stamp is traced through and the running sum rowptr (nr + 1,) of the block widths -> dict(first, len, rowptr)."""
+    return _scene_layout(ctl, atm, time)
+
+
+def scene_columns(ctl, atm, first, length):
+    """jur_scene_columns: the global state indices (columns of Model.kernel's matrix) of the slice, ascending."""
+    n = _chk(lib().jur_scene_columns(C.byref(ctl), C.byref(atm), int(first), int(length), None))
+    cols = np.zeros(n, dtype=np.int64)
+    _chk(lib().jur_scene_columns(C.byref(ctl), C.byref(atm), int(first), int(length), cols.ctypes.data_as(C.POINTER(C.c_long))))
+    return cols
+
+
+def scene_blocks_to_dense(ctl, atm, out, n=None):
+    """Scatters the blocks of Model.kernel_scene's result into the dense (nr * nd, n) matrix (row ray * nd + channel,
+    the state's n columns; zero outside the blocks): for tests and small cases."""
+    nr = len(out["first"])
+    nd = out["rad"].shape[1]
+    if n is None:
+        n = len(scene_columns(ctl, atm, 0, atm.np))
+    dense = np.zeros((nr * nd, n))
+    rp, cache = out["rowptr"], {}
+    for r in range(nr):
+        w = int(rp[r + 1] - rp[r])
+        if w == 0:
+            continue
+        key = (int(out["first"][r]), int(out["len"][r]))
+        if key not in cache:
+            cache[key] = scene_columns(ctl, atm, *key)
+        dense[r * nd:(r + 1) * nd, cache[key]] = out["k"][rp[r] * nd:rp[r + 1] * nd].reshape(nd, w)
+    return dense
 
 
 def device_info(device):
