@@ -60,8 +60,28 @@ namespace {
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ double c01(double x) { return (x > 1.) ? 1. : ((x < 0.) ? 0. : x); }
 // the same clamp for an x that is known not to be NaN (v_min_f64 / v_max_f64 return the other operand for a
-// NaN, the comparisons above return the NaN): 2 instructions instead of 6
+// NaN, the comparisons above return the NaN): 2 instructions instead of 6.  No caller is left since fma_c01 / add_c01
+// below; it stays as the definition of what those two compute.
 __device__ __forceinline__ double c01_num(double x) { return __builtin_fmax(__builtin_fmin(x, 1.), 0.); }
+// c01_num folded into the instruction that produces x: the VOP3 `clamp` output modifier clamps the rounded fp64 result
+// to [0, 1], for every non-NaN x the very double min(max(x, 0), 1) -- and no instruction of its own, where c01_num is two
+// at the fp64 rate.  (The compiler does not form the modifier here: without fast-math the fold needs a no-NaN
+// guarantee.)  What the modifier makes of a NaN depends on the kernel's DX10-clamp mode (0 with it, the NaN without);
+// that does not matter where these are used: the strict-table look-up answers NaN inputs before it reaches a clamp, and
+// the tables hold none.  The one value the two forms could give differently is a zero's sign (x = -0).  No table rule is
+// needed against that: a clamp's result is only ever added to, subtracted from or multiplied, a zero of either sign gives
+// the same non-zero results there and at most another zero of either sign, and what the look-up hands on is
+// 1 - eps_t = 1 for both -- the sign of a zero never reaches an output.
+__device__ __forceinline__ double fma_c01(double a, double b, double c) {      // c01_num(fma(a, b, c))
+  double d;
+  asm volatile("v_fma_f64 %0, %1, %2, %3 clamp" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+__device__ __forceinline__ double add_c01(double a, double b) {                // c01_num(a + b)
+  double d;
+  asm volatile("v_add_f64 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
 
 __device__ __forceinline__ double lip(double x0, double y0, double x1, double y1, double x) {
   return y0 + (x - x0) * (y1 - y0) / (x1 - x0);
@@ -116,6 +136,11 @@ __device__ __forceinline__ double lip_finite(double x0, double y0, double x1, do
 __device__ __forceinline__ double lip_slope(double x0, double y0, double s, double x) { return __builtin_fma(x - x0, s, y0); }
 __device__ __forceinline__ double lip_mulr(double x0, double y0, double y1, double x, double r) {
   return y0 + ((x - x0) * (y1 - y0)) * r;
+}
+// c01_num of the two, clamped by their last instruction (fma_c01 / add_c01): the same doubles
+__device__ __forceinline__ double lip_slope_c01(double x0, double y0, double s, double x) { return fma_c01(x - x0, s, y0); }
+__device__ __forceinline__ double lip_mulr_c01(double x0, double y0, double y1, double x, double r) {
+  return add_c01(y0, ((x - x0) * (y1 - y0)) * r);
 }
 
 // exp(x) of the radiance update and the continua (round 3).  The device library's exp is a degree-11 polynomial whose
@@ -1020,8 +1045,8 @@ __device__ __forceinline__ double ega_eps_warm(jur_view_t const &v, jur_int2 con
     br = (unsigned)ipr | ((unsigned)it0 << 8) | ((unsigned)it1 << 16);
     if (c00.nu < 2 || c01_.nu < 2 || c10.nu < 2 || c11.nu < 2) return one;
   }
-  // RCPB clamps with min/max, which would turn a NaN into 0: a NaN among the inputs (the tables hold none) is
-  // answered here with what the comparisons of c01 would have handed through
+  // RCPB clamps with the clamp modifier (fma_c01 / add_c01), which would turn a NaN into 0: a NaN among the inputs (the
+  // tables hold none) is answered here with what the comparisons of c01 would have handed through
   if (RCPB && (tau != tau || t != t || u != u || p != p)) return __builtin_nan("");
   double const eps = 1 - tau;
   double eps_p0 = 0, eps_p1 = 0;
@@ -1055,7 +1080,7 @@ __device__ __forceinline__ double ega_eps_warm(jur_view_t const &v, jur_int2 con
         x[k] = lip_slope(ka, ya, r[k].du_de, eps) + u;
         ka = ya; kb = cvt_keep(r[k].u1);
         seek_rec<false, true>(D.recb, e0[k], n[k], x[k], i[k], r[k], ka, kb);
-        ec[k] = c01_num(lip_slope(ka, (double)r[k].e0, r[k].de_du, x[k]));
+        ec[k] = lip_slope_c01(ka, (double)r[k].e0, r[k].de_du, x[k]);
       }
     } else {
       Ue a[2], b[2];
@@ -1073,7 +1098,7 @@ __device__ __forceinline__ double ega_eps_warm(jur_view_t const &v, jur_int2 con
     unsigned const last = (unsigned)i[0] | ((unsigned)i[1] << 16);
     if (h) ib = last; else ia = last;
     double e;
-    if constexpr (RCPB) e = c01_num(lip_mulr(ca.t, ec[0], ec[1], t, D.rt(kc)));
+    if constexpr (RCPB) e = lip_mulr_c01(ca.t, ec[0], ec[1], t, D.rt(kc));
     else e = c01(lip(ca.t, ec[0], cb.t, ec[1], t));
     if (h) eps_p1 = e; else eps_p0 = e;
   }
@@ -1082,7 +1107,7 @@ __device__ __forceinline__ double ega_eps_warm(jur_view_t const &v, jur_int2 con
     // kept the kernel at 7 waves per SIMD with the keys held as doubles (round 2; 8 waves at 62 VGPRs since the slopes)
     int q = ipr;
     asm volatile("" : "+v"(q));
-    double const tau_new = 1. - c01_num(lip_mulr(D.lvl(q).p, eps_p0, eps_p1, p, D.rp(q)));
+    double const tau_new = 1. - lip_mulr_c01(D.lvl(q).p, eps_p0, eps_p1, p, D.rp(q));
     if constexpr (PATH) return tau_new;
     else return div_finite(tau_new, tau);
   }
@@ -1131,7 +1156,7 @@ __device__ __forceinline__ double ega_eps_warm_quad(jur_view_t const &v, jur_int
   int i = min((int)ix, n - 2);
   double const eps = 1 - tau;
   if constexpr (FAST) {   // bracket records (round 4): one fetch for the curve's keys and both slopes -- the same doubles
-    bool const nan_in = (tau != tau || t != t || u != u || p != p);   // as ega_eps_warm: min/max clamps below
+    bool const nan_in = (tau != tau || t != t || u != u || p != p);   // as ega_eps_warm: clamp modifiers below
     Rec r = ld_rec(D.recb, e0 + i);
     double ka, kb;
     seek_rec<true, false, false>(D.recb, e0, n, eps, i, r, ka, kb);
@@ -1139,12 +1164,12 @@ __device__ __forceinline__ double ega_eps_warm_quad(jur_view_t const &v, jur_int
     double const x = lip_slope(ka, ya, r.du_de, eps) + u;
     ka = ya; kb = (double)r.u1;
     seek_rec<false, true, false>(D.recb, e0, n, x, i, r, ka, kb);
-    double const ec = c01_num(lip_slope(ka, (double)r.e0, r.de_du, x));
+    double const ec = lip_slope_c01(ka, (double)r.e0, r.de_du, x);
     ix = (unsigned)i;
     double const ec0 = quad_bcast<0>(ec), ec1 = quad_bcast<1>(ec), ec2 = quad_bcast<2>(ec), ec3 = quad_bcast<3>(ec);
-    double const eps_p0 = c01_num(lip_mulr(c00.t, ec0, ec1, t, 1. / (c01_.t - c00.t)));
-    double const eps_p1 = c01_num(lip_mulr(c10.t, ec2, ec3, t, 1. / (c11.t - c10.t)));
-    double const tau_new = 1. - c01_num(lip_mulr(l0.p, eps_p0, eps_p1, p, 1. / (l1.p - l0.p)));
+    double const eps_p0 = lip_mulr_c01(c00.t, ec0, ec1, t, 1. / (c01_.t - c00.t));
+    double const eps_p1 = lip_mulr_c01(c10.t, ec2, ec3, t, 1. / (c11.t - c10.t));
+    double const tau_new = 1. - lip_mulr_c01(l0.p, eps_p0, eps_p1, p, 1. / (l1.p - l0.p));
     return nan_in ? __builtin_nan("") : tau_new;
   } else {
     Ue a, b;
