@@ -240,6 +240,39 @@ int  jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double con
                            double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass);
 int  jur_model_last_scene_ms(jur_model_t *m, double *out_ms, long *out_launches);
 
+/* The Gauss-Newton normal equations of a scene per slice, accumulated on the device from the blocks of
+ * jur_kernel_scene_host while they lie there: for every distinct slice s of the scene, over its live measurements
+ * (r, id), with F the unperturbed radiance the call returns in rad and K_r the block of ray r,
+ *   A_s[i][j] = sum weight * K_r[id][i] * K_r[id][j],  b_s[i] = sum weight * K_r[id][i] * (y - F),
+ *   cost[s] = sum weight * (y - F)^2,  nlive[s] = number of terms.
+ *
+ * jur_scene_slices (host arithmetic, no GPU): the distinct slices (first, len) of width > 0 among the rays with time
+ *   stamps time[r], in the order the rays first meet them; rays with different time stamps can share one.  sid[r] is the
+ *   slice of ray r, -1 for a ray of width 0; wptr and aptr [nslice + 1] are the running sums of the widths w_s and of
+ *   w_s^2.  Any output may be NULL: a first call counts.  Returns nslice, or what jur_scene_layout refuses, as there.
+ * jur_scene_elements: jur_scene_columns plus the quantity iq (0 p, 1 T, 2 + g q, 2 + ng + w k) and the atmosphere point
+ *   ip of every element (any output may be NULL): what writes a solved step back into an atm_t.
+ * jur_normal_scene_host: geom, rad (read first for the NaN mask), tau, tp, np_out, rowptr and max_rays_per_pass as
+ *   jur_kernel_scene_host, with the same doubles out and the same refusals.  y and weight are [nr][nd]: the
+ *   measurements and the diagonal of the inverse of their covariance, 1 / sigma^2.  A weight that is negative or not
+ *   finite gives JUR_EINVAL.  A measurement is live when its channel is not masked on input (any non-finite rad masks), y is finite, its weight
+ *   is > 0 and its ray has a slice; one that is not contributes nothing (no 0 * NaN is formed).
+ *   A holds aptr[nslice] doubles, A_s at A + aptr[s] laid out [w_s][w_s], full, its two triangles bit-identical;
+ *   b holds wptr[nslice] doubles, b_s at b + wptr[s]; cost and nlive hold nslice entries, all laid out by
+ *   jur_scene_slices of the same rays.  Every sum runs in ascending ray order and within a ray in ascending channel
+ *   order, without atomics, in accumulators that stay on the device across the passes: the results depend neither on
+ *   max_rays_per_pass nor on k nor on where the rays of a slice sit in the call.
+ *   k may be NULL: no block leaves the device then.  Otherwise it receives the blocks of jur_kernel_scene_host.
+ *   nr == 0 and a state of zero elements are JUR_OK with nslice == 0: nothing is written to A, b, cost, nlive.
+ *   JUR_ENOMEM when the normal matrices do not fit beside the stacked slices in half the workspace budget.
+ *   The kernel's time counts into jur_model_last_scene_ms.  The model holds `atm` afterwards, after an error too. */
+long jur_scene_slices(ctl_t const *ctl, atm_t const *atm, long nr, double const *time, int *sid, int *sfirst, int *slen,
+                      long *wptr, long *aptr);
+long jur_scene_elements(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols, int *iq, int *ip);
+int  jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                           double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                           double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass);
+
 /* Curtis-Godson means along each line of sight (reference curtis_godson(), jr_common.h:455-473, which
  * upstream compiles only with -DCURTIS_GODSON for FORMOD=1): per ray, emitter and LOS point the
  * column-weighted pressure cgp, temperature cgt and the cumulative column cgu.  Host arrays

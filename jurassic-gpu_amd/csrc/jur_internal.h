@@ -194,11 +194,30 @@ int jurk_scene_stack(jur_scene_stack_t const *a, void *stream);
 int jurk_scene_rays(jur_scene_pass_t const *a, void *stream);      /* geometry and mask of the pass */
 int jurk_scene_quot(jur_scene_pass_t const *a, long nk, void *stream);   /* the nk block elements and the unperturbed results of the pass */
 
+/* Normal equations of a scene (jur_normal_scene_host): per distinct slice s of width w_s the sums over its live
+ * measurements, kept in device memory across the passes.  One workgroup per 16 x 16 tile of the lower triangle of A_s. */
+typedef struct {
+  long nslice;
+  long const *tptr;             /* [nslice + 1] running sum of the tiles T (T + 1) / 2, T = ceil(w_s / 16)  */
+  long const *sptr;             /* [nslice + 1] rays of every slice in srays                                */
+  int const *srays;             /* the rays of every slice, ascending                                       */
+  long const *wptr, *aptr;      /* [nslice + 1] running sums of w_s and of w_s^2                             */
+  double const *y, *weight;     /* [nr][nd] measurements and the diagonal of their inverse covariance       */
+  double *A, *b, *cost;         /* [aptr[nslice]], [wptr[nslice]], [nslice] accumulators, read and written   */
+  long *nlive;                  /* [nslice]                                                                 */
+} jur_scene_normal_t;
+/* the terms of the rays [a->r0, a->r1) from the blocks a->k and the results a->out_rad of the pass (after jurk_scene_quot) */
+int jurk_scene_normal(jur_scene_pass_t const *a, jur_scene_normal_t const *n, long ntiles, void *stream);
+
 /* host arithmetic shared by jur_model.c and jur_scene.c (not exported) */
 #define JUR_HIDDEN __attribute__((visibility("hidden")))
 JUR_HIDDEN int jur_atm_slice(double const *time, long n, double t, long *first);
 JUR_HIDDEN size_t jur_state_vector(ctl_t const *ctl, atm_t const *atm, double *x, int *iqa, int *ipa);
 JUR_HIDDEN long jur_scene_slice_elements(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols, int *iqa, int *ipa);
+/* a distinct slice of a scene: points [first, first + len) with nel state elements; next: chain of the slices that
+ * share the first point */
+typedef struct { int first, len, next; long nel; } jur_scene_slice_t;
+JUR_HIDDEN long jur_scene_distinct(int np, long nr, int const *first, int const *len, long const *rp, int *sid, jur_scene_slice_t **out);
 
 /* internals of a model that jur_multi.c needs (jur_model.c) */
 /* jur_formod_device on rays that are part of larger arrays: geometry field k at d_geom + k * ldg, tangent-point field k

@@ -2393,6 +2393,87 @@ __global__ __launch_bounds__(256) void jur_scene_gather_kernel(jur_scene_pass_t 
   }
 }
 
+// ---- normal equations of a scene (jur_normal_scene_host) -------------------------------------------------------------
+// first i in [lo, hi) with a[i] >= x (hi if none), for an ascending a[]
+__device__ inline long scene_lower(int const *__restrict__ a, long lo, long hi, long x) {
+  while (lo < hi) {
+    long const mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// One workgroup per 16 x 16 tile (ti, tj), tj <= ti, of one slice's A; lane (ty, tx) owns A[16 ti + ty][16 tj + tx] and
+// carries its chain of terms weight * K[id][i] * K[id][j] over the slice's rays of the pass, ascending, and their
+// channels, ascending: the chain starts from the value the earlier passes left and goes back there, so where a pass
+// ends changes no bit.  The measurements (ray, channel) of the sub-range are taken eight at a time: the 32 entries of
+// each block row that the tile needs (columns of ti, then of tj) are staged in LDS, one per lane, in one of two buffers
+// (one barrier per group: a lane can be no further than one group ahead of the slowest), with the weight (0: not live,
+// the term is skipped, so that the NaN row of a masked channel is never multiplied) and y - F.  K_i * K_j is rounded
+// first and is the same for (i, j) and (j, i), so the mirror image written for tj < ti equals what a tile (tj, ti) would
+// have made, and the two halves of a diagonal tile agree bit for bit.  The tiles of the first tile column (tj == 0) carry
+// b of their rows in the lanes tx == 0, tile (0, 0) cost and nlive in lane 0.
+__global__ __launch_bounds__(256) void jur_scene_normal_kernel(jur_scene_pass_t a, jur_scene_normal_t n) {
+  __shared__ double rows[2][8][32];
+  __shared__ double wl[2][8], dl[2][8];
+  long const s = scene_find<false>(n.tptr, 0, n.nslice, (long)blockIdx.x);
+  long const q0 = scene_lower(n.srays, n.sptr[s], n.sptr[s + 1], a.r0), q1 = scene_lower(n.srays, q0, n.sptr[s + 1], a.r1);
+  if (q1 == q0) return;                                   // (uniform: before any barrier)
+  long const t = (long)blockIdx.x - n.tptr[s];
+  int ti = 0;
+  while ((long)(ti + 1) * (ti + 2) / 2 <= t) ti++;
+  int const tj = (int)(t - (long)ti * (ti + 1) / 2);
+  int const w = (int)(n.wptr[s + 1] - n.wptr[s]), nd = a.nd;
+  int const ty = threadIdx.x >> 4, tx = threadIdx.x & 15, i = ti * 16 + ty, j = tj * 16 + tx;
+  bool const inside = i < w && j < w, with_b = tj == 0 && tx == 0 && i < w, with_cost = ti == 0 && threadIdx.x == 0;
+  double *const As = n.A + n.aptr[s];
+  double acc = inside ? As[(long)i * w + j] : 0.;
+  double acc_b = with_b ? n.b[n.wptr[s] + i] : 0.;
+  double acc_c = with_cost ? n.cost[s] : 0.;
+  long count = with_cost ? n.nlive[s] : 0;
+  int const lc = threadIdx.x >> 5, lcol = threadIdx.x & 31;
+  int const col = lcol < 16 ? ti * 16 + lcol : tj * 16 + lcol - 16;
+  long const M = (q1 - q0) * nd, kbase = a.rowptr[a.r0];
+  for (long m0 = 0; m0 < M; m0 += 8) {
+    int const buf = (int)(m0 >> 3) & 1;
+    long const mm = m0 + lc;
+    double v = 0., ww = 0., d = 0.;
+    if (mm < M) {
+      long const q = mm / nd;
+      int const id = (int)(mm - q * nd);
+      long const r = n.srays[q0 + q], at = r * nd + id;
+      double const yy = n.y[at], wt = n.weight[at];
+      double const f = a.out_rad[at];
+      // (masked as the forward model masks: any non-finite input; F of a channel that is not masked is finite)
+      if (isfinite(a.in_rad[at]) && isfinite(f) && isfinite(yy) && wt > 0) {
+        ww = wt;
+        d = yy - f;
+        if (col < w) v = a.k[(a.rowptr[r] - kbase) * nd + (long)id * w + col];
+      }
+    }
+    rows[buf][lc][lcol] = v;
+    if (lcol == 0) { wl[buf][lc] = ww; dl[buf][lc] = d; }
+    __syncthreads();
+    for (int c = 0; c < 8; c++) {
+      double const wc = wl[buf][c];
+      if (!(wc > 0)) continue;                            // (uniform)
+      double const ki = rows[buf][c][ty], kj = rows[buf][c][16 + tx];
+      acc = fma(ki * kj, wc, acc);
+      if (with_b || with_cost) {
+        double const dc = dl[buf][c], wd = wc * dc;
+        if (with_b) acc_b = fma(ki, wd, acc_b);
+        if (with_cost) { acc_c = fma(wd, dc, acc_c); count++; }
+      }
+    }
+  }
+  if (inside) {
+    As[(long)i * w + j] = acc;
+    if (tj < ti) As[(long)j * w + i] = acc;
+  }
+  if (with_b) n.b[n.wptr[s] + i] = acc_b;
+  if (with_cost) { n.cost[s] = acc_c; n.nlive[s] = count; }
+}
+
 }  // namespace
 
 extern "C" int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream) {
@@ -2422,6 +2503,13 @@ extern "C" int jurk_scene_quot(jur_scene_pass_t const *a, long nk, void *stream)
   if (nk > 0) hipLaunchKernelGGL(jur_scene_quot_kernel, dim3(scene_grid(nk)), dim3(256), 0, (hipStream_t)stream, *a);
   if (a->r1 > a->r0)
     hipLaunchKernelGGL(jur_scene_gather_kernel, dim3(scene_grid((a->r1 - a->r0) * a->nd)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+// (the tile counts are the host's: ntiles = tptr[nslice])
+extern "C" int jurk_scene_normal(jur_scene_pass_t const *a, jur_scene_normal_t const *n, long ntiles, void *stream) {
+  if (ntiles <= 0 || a->r1 <= a->r0) return 0;
+  hipLaunchKernelGGL(jur_scene_normal_kernel, dim3((unsigned)ntiles), dim3(256), 0, (hipStream_t)stream, *a, *n);
   return (int)hipGetLastError();
 }
 

@@ -1709,81 +1709,120 @@ static int install_stacked_rows(jur_model_t *m, atm_t const *base, long nt, long
   return JUR_OK;
 }
 
-/* a distinct slice of the scene: points [first, first + len), its state elements raised by copies copy0 ... */
-typedef struct { int first, len, next; long copy0, nel; } scene_slice_t;
+/* what jur_normal_scene_host adds to a call: measurements and weights in, the sums per slice out */
+typedef struct {
+  double const *y, *weight;
+  double *A, *b, *cost;
+  long *nlive;
+} scene_normal_t;
 
+/* nm == NULL: jur_kernel_scene_host.  Otherwise the normal equations of the slices are accumulated on the device after
+ * the quotients of every pass, and the blocks go home only where k is given. */
 static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
-                             double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
-  if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("jur_kernel_scene_host: bad arguments"); return JUR_EINVAL; }
+                             double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
+                             scene_normal_t const *nm) {
+  char const *const who = nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+  if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   ctl_t const *ctl = m->ctl;
   if (ctl->hydz >= 0) {
-    jur_set_error("jur_kernel_scene_host: hydz = %g >= 0 adjusts all points as one profile, so every p, T or H2O element moves "
-                  "every pressure and the Jacobian has no blocks: use jur_kernel", ctl->hydz);
+    jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so every p, T or H2O element moves "
+                  "every pressure and the Jacobian has no blocks: use jur_kernel", who, ctl->hydz);
     return JUR_EINVAL;
   }
   int const np0 = atm->np, nd = ctl->nd, ng = m->view.ng, nw = m->view.nw;
-  if (np0 < 2 || np0 > JUR_NP) { jur_set_error("jur_kernel_scene_host: need 2..%d atmospheric points", JUR_NP); return JUR_EINVAL; }
+  if (np0 < 2 || np0 > JUR_NP) { jur_set_error("%s: need 2..%d atmospheric points", who, JUR_NP); return JUR_EINVAL; }
   for (int i = 1; i < np0; i++)
     if (!(atm->time[i] >= atm->time[i - 1])) {
-      jur_set_error("jur_kernel_scene_host: the time stamps of the atmosphere are not ascending (point %d): the slices of a "
-                    "stacked atmosphere cannot reproduce locate_atm there", i);
+      jur_set_error("%s: the time stamps of the atmosphere are not ascending (point %d): the slices of a "
+                    "stacked atmosphere cannot reproduce locate_atm there", who, i);
       return JUR_EINVAL;
     }
   if (nr == 0) return JUR_OK;
-  if (nr > 0x7fffffffL) { jur_set_error("jur_kernel_scene_host: at most 2^31-1 rays per call"); return JUR_EINVAL; }
-  if (!geom || !rad || !tau || !tp || !rowptr) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
+  if (nr > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 rays per call", who); return JUR_EINVAL; }
+  if (!geom || !rad || !tau || !tp || !rowptr) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
 
   size_t const NR = (size_t)nr, nrow = 6 + (size_t)ng + nw;
   int rc = JUR_OK, enqueued = 0;
   int *first = (int *)malloc(sizeof(int) * 3 * NR), *len = first ? first + NR : NULL, *copy0 = first ? len + NR : NULL;
   long *rp = (long *)malloc(sizeof(long) * (NR + 1));
-  int *head = (int *)malloc(sizeof(int) * (size_t)np0);
-  scene_slice_t *sl = NULL;
-  long *off = NULL, *pass = NULL;
+  int *sid = (int *)malloc(sizeof(int) * NR), *srays = NULL;
+  jur_scene_slice_t *sl = NULL;
+  long *off = NULL, *pass = NULL, *scopy = NULL, *nptr = NULL;
   int *cdesc = NULL, *iqa = NULL, *ipa = NULL;
   double *hbase = NULL;
-  if (!first || !rp || !head) { rc = JUR_ENOMEM; goto done; }
+  if (!first || !rp || !sid) { rc = JUR_ENOMEM; goto done; }
   if ((rc = jur_scene_layout(ctl, atm, nr, geom[0], first, len, rp))) goto done;
   if (memcmp(rp, rowptr, sizeof(long) * (NR + 1))) {
-    jur_set_error("jur_kernel_scene_host: rowptr is not jur_scene_layout's for these rays, this atmosphere and these windows");
+    jur_set_error("%s: rowptr is not jur_scene_layout's for these rays, this atmosphere and these windows", who);
     rc = JUR_EINVAL;
     goto done;
   }
-  if (rp[nr] > 0 && !k) { jur_set_error("jur_kernel_scene_host: null argument"); rc = JUR_EINVAL; goto done; }
-
-  /* the distinct slices that have state elements, in the order the rays meet them, and their copies */
-  long nslice = 0, ncopies = 0, nt = np0;
-  {
-    long cap = 0;
-    for (int i = 0; i < np0; i++) head[i] = -1;
-    for (long r = 0; r < nr; r++) {
-      copy0[r] = 0;
-      if (rp[r + 1] == rp[r]) continue;
-      int q = head[first[r]];
-      while (q >= 0 && sl[q].len != len[r]) q = sl[q].next;
-      if (q < 0) {
-        if (nslice == cap) {
-          cap = cap ? 2 * cap : 64;
-          scene_slice_t *grown = (scene_slice_t *)realloc(sl, sizeof *sl * (size_t)cap);
-          if (!grown) { rc = JUR_ENOMEM; goto done; }
-          sl = grown;
+  if (rp[nr] > 0 && !k && !nm) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
+  if (nm) {
+    if (!nm->y || !nm->weight) { jur_set_error("jur_normal_scene_host: null argument"); rc = JUR_EINVAL; goto done; }
+    for (long r = 0; r < nr; r++)
+      for (int id = 0; id < nd; id++) {
+        double const w = nm->weight[(size_t)r * nd + id];
+        if (!(w >= 0) || isinf(w)) {
+          jur_set_error("jur_normal_scene_host: the weight of ray %ld, channel %d is %g: negative or not finite", r, id, w);
+          rc = JUR_EINVAL;
+          goto done;
         }
-        q = (int)nslice++;
-        sl[q].first = first[r]; sl[q].len = len[r]; sl[q].next = head[first[r]];
-        sl[q].copy0 = 1 + ncopies; sl[q].nel = rp[r + 1] - rp[r];
-        head[first[r]] = q;
-        ncopies += sl[q].nel;
-        nt += sl[q].nel * sl[q].len;
       }
-      if (sl[q].copy0 > 0x7fffffffL) break;           /* (refused below) */
-      copy0[r] = (int)sl[q].copy0;
-    }
   }
+
+  /* the distinct slices that have state elements, in the order the rays meet them, and their copies: slice q is
+   * raised element by element by the copies scopy[q] ... */
+  long const nslice = jur_scene_distinct(np0, nr, first, len, rp, sid, &sl);
+  long ncopies = 0, nt = np0;
+  if (nslice < 0) { rc = JUR_ENOMEM; goto done; }
+  scopy = (long *)malloc(sizeof(long) * ((size_t)nslice + 1));
+  if (!scopy) { rc = JUR_ENOMEM; goto done; }
+  for (long q = 0; q < nslice; q++) {
+    scopy[q] = 1 + ncopies;
+    ncopies += sl[q].nel;
+    nt += sl[q].nel * sl[q].len;
+  }
+  for (long r = 0; r < nr; r++)                       /* (a copy beyond 2^31 is refused below with nt) */
+    copy0[r] = (sid[r] >= 0 && scopy[sid[r]] <= 0x7fffffffL) ? (int)scopy[sid[r]] : 0;
+
+  /* normal equations: where the sums of every slice lie, its rays as one CSR over the call, its tiles */
+  long nlist = 0, ntiles = 0, na = 0, nb = 0;
+  long *sptr = NULL, *tptr = NULL, *wptr = NULL, *aptr = NULL;
+  if (nm && nslice > 0) {
+    if (!nm->A || !nm->b || !nm->cost || !nm->nlive) { jur_set_error("jur_normal_scene_host: null argument"); rc = JUR_EINVAL; goto done; }
+    nptr = (long *)calloc(4 * ((size_t)nslice + 1), sizeof(long));
+    srays = (int *)malloc(sizeof(int) * NR);
+    if (!nptr || !srays) { rc = JUR_ENOMEM; goto done; }
+    sptr = nptr; tptr = sptr + nslice + 1; wptr = tptr + nslice + 1; aptr = wptr + nslice + 1;
+    for (long r = 0; r < nr; r++) if (sid[r] >= 0) sptr[sid[r] + 1]++;
+    for (long q = 0; q < nslice; q++) {
+      long const w = sl[q].nel, T = (w + 15) / 16;
+      sptr[q + 1] += sptr[q];
+      tptr[q + 1] = tptr[q] + T * (T + 1) / 2;
+      wptr[q + 1] = wptr[q] + w;
+      aptr[q + 1] = aptr[q] + w * w;
+    }
+    for (long r = 0; r < nr; r++) if (sid[r] >= 0) srays[sptr[sid[r]]++] = (int)r;   /* (sptr[q] now ends slice q ...) */
+    for (long q = nslice; q > 0; q--) sptr[q] = sptr[q - 1];                          /* ... and starts it again      */
+    sptr[0] = 0;
+    nlist = sptr[nslice]; ntiles = tptr[nslice]; na = aptr[nslice]; nb = wptr[nslice];
+    if (ntiles > 0x7fffffffL) { jur_set_error("jur_normal_scene_host: 2^31 tiles: call with the rays of fewer slices at a time"); rc = JUR_EINVAL; goto done; }
+  }
+  /* what the sums add to the slab: the accumulators A | b | cost | nlive, y and weight, the four running sums, the ray lists */
+  size_t const nacc = (size_t)na + (size_t)nb + 2 * (size_t)(ntiles ? nslice : 0);
+  size_t const acc_bytes = ntiles ? sizeof(double) * (nacc + 2 * NR * (size_t)nd + 4 * ((size_t)nslice + 1)) + sizeof(int) * (size_t)nlist : 0;
   long const ncopy = ncopies + 1;
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)nt;
   if (nt > 0x7fffffffL || (long)atm_bytes > m->ws_budget / 2) {
-    jur_set_error("jur_kernel_scene_host: the stacked atmosphere (%ld points, %zu bytes) exceeds the workspace budget: "
-                  "call with the rays of fewer slices at a time", nt, atm_bytes);
+    jur_set_error("%s: the stacked atmosphere (%ld points, %zu bytes) exceeds the workspace budget: "
+                  "call with the rays of fewer slices at a time", who, nt, atm_bytes);
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+  if (acc_bytes > 0 && (double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("jur_normal_scene_host: the normal matrices (%ld doubles) do not fit beside the stacked atmosphere (%zu bytes) "
+                  "in the workspace budget: call with the rays of fewer slices at a time", na, atm_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
@@ -1795,7 +1834,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
      * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
      * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
-    long const avail = (m->ws_budget - (long)atm_bytes) / 16;
+    long const avail = (m->ws_budget - (long)atm_bytes - (long)acc_bytes) / 16;
     cap = avail / (long)slot_bytes;
     if (cap < 4096) cap = 4096;
   }
@@ -1807,7 +1846,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     long r1 = r0 + 1;
     while (r1 < nr && (rp[r1 + 1] - rp[r0]) + (r1 + 1 - r0) <= cap) r1++;
     long const n = (rp[r1] - rp[r0]) + (r1 - r0);
-    if (n > 0x7fffffffL) { jur_set_error("jur_kernel_scene_host: a ray with 2^31 state elements"); rc = JUR_EINVAL; goto done; }
+    if (n > 0x7fffffffL) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
     if (n > nmax) nmax = n;
     if (rp[r1] - rp[r0] > kmax) kmax = rp[r1] - rp[r0];
     pass[npass++] = r0;
@@ -1828,9 +1867,9 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   off[1] = np0;
   for (long q = 0; q < nslice; q++) {
     long const n = jur_scene_slice_elements(ctl, atm, sl[q].first, sl[q].len, NULL, iqa, ipa);
-    if (n != sl[q].nel) { jur_set_error("jur_kernel_scene_host: layout out of step"); rc = JUR_EINVAL; goto done; }
+    if (n != sl[q].nel) { jur_set_error("%s: layout out of step", who); rc = JUR_EINVAL; goto done; }
     for (long e = 0; e < n; e++) {
-      long const j = sl[q].copy0 + e;
+      long const j = scopy[q] + e;
       cfirst[j] = sl[q].first;
       prow[j] = (iqa[e] == 0) ? 4 : (iqa[e] == 1) ? 5 : 4 + iqa[e];   /* q rows start at 6, k rows follow */
       pip[j] = ipa[e];
@@ -1848,16 +1887,20 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const nrd = NR * (size_t)nd;
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_rad = o_inrad + nrd,
                o_tau = o_rad + nrd, o_tp = o_tau + nrd, o_h = o_tp + 3 * NR, o_k = o_h + (size_t)ncopy,
-               o_rowptr = o_k + (size_t)kmax, o_off = o_rowptr + NR + 1, o_int = o_off + (size_t)ncopy + 1;
-  size_t const nint = 4 * NR + 3 * (size_t)ncopy, bytes = sizeof(double) * o_int + sizeof(int) * nint;
-  if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("jur_kernel_scene_host: cannot select the device"); rc = JUR_EHIP; goto done; }
+               o_rowptr = o_k + (size_t)kmax, o_off = o_rowptr + NR + 1, o_y = o_off + (size_t)ncopy + 1;
+  /* (the normal equations' part, empty without them: y, weight, the accumulators A | b | cost | nlive in one piece,
+   * then sptr | tptr | wptr | aptr) */
+  size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
+               o_int = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0);
+  size_t const nint = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, bytes = sizeof(double) * o_int + sizeof(int) * nint;
+  if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
   hipStream_t const s = m->stream;
   if ((rc = wait_done(m, s))) goto done;
   if (bytes > m->scene_bytes) {
     if (m->d_scene) (void)hipFree(m->d_scene);
     m->d_scene = NULL; m->scene_bytes = 0;
     if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
-      (void)hipGetLastError(); jur_set_error("jur_kernel_scene_host: no device memory for %zu bytes", bytes); rc = JUR_ENOMEM; goto done;
+      (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
     }
     m->scene_bytes = bytes;
   }
@@ -1876,7 +1919,14 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (e == hipSuccess) e = hipMemcpyAsync(d_first, first, sizeof(int) * 3 * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_cdesc, cdesc, sizeof(int) * 3 * (size_t)ncopy, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
-    if (e != hipSuccess) { jur_set_error("jur_kernel_scene_host: %s", hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if (ntiles) {                                 /* the accumulators are zeroed here, once */
+      if (e == hipSuccess) e = hipMemcpyAsync(D + o_y, nm->y, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(D + o_w, nm->weight, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(L + o_nptr, nptr, sizeof(long) * 4 * ((size_t)nslice + 1), hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_cdesc + 3 * ncopy, srays, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
+    }
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
 
     m->h_atm_n = 0;                              /* the device no longer holds the caller's atmosphere */
     if ((rc = install_stacked_rows(m, atm, nt, ncopies))) goto done;
@@ -1892,7 +1942,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (!ek) ek = jurk_prepare_atm(&m->view, (double *)m->d_atm + nrow * (size_t)nt, s);
     /* the one wait before the passes: the uploads have left the host arrays, the stacked rows stand */
     if (ek || hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipGetLastError(); m->view.atm_np = 0; jur_set_error("jur_kernel_scene_host: stacking the atmosphere failed"); rc = JUR_EHIP; goto done;
+      (void)hipGetLastError(); m->view.atm_np = 0; jur_set_error("%s: stacking the atmosphere failed", who); rc = JUR_EHIP; goto done;
     }
     if ((rc = jur_model_reserve(m, nmax))) goto done;   /* the forward model's workspace for the largest pass, before the first */
 
@@ -1905,6 +1955,15 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     a.in_geom = D + o_geom; a.in_rad = D + o_inrad;
     a.h = D + o_h; a.k = D + o_k;
     a.out_rad = D + o_rad; a.out_tau = D + o_tau; a.out_tp = D + o_tp; a.out_np = d_np;
+    jur_scene_normal_t nq;
+    memset(&nq, 0, sizeof nq);
+    if (ntiles) {
+      nq.nslice = nslice;
+      nq.sptr = L + o_nptr; nq.tptr = nq.sptr + nslice + 1; nq.wptr = nq.tptr + nslice + 1; nq.aptr = nq.wptr + nslice + 1;
+      nq.srays = d_cdesc + 3 * ncopy;
+      nq.y = D + o_y; nq.weight = D + o_w;
+      nq.A = D + o_acc; nq.b = nq.A + na; nq.cost = nq.b + nb; nq.nlive = (long *)(nq.cost + nslice);
+    }
     for (long p = 0; p < npass; p++) {
       long const r0 = pass[p], r1 = pass[p + 1], n = (rp[r1] - rp[r0]) + (r1 - r0), nk = (rp[r1] - rp[r0]) * nd;
       size_t const N = (size_t)n;
@@ -1913,38 +1972,48 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       ti = scene_timed_begin(m, s);
       ek = jurk_scene_rays(&a, s);
       scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("jur_kernel_scene_host: replication kernel launch failed"); rc = JUR_EHIP; goto done; }
+      if (ek) { jur_set_error("%s: replication kernel launch failed", who); rc = JUR_EHIP; goto done; }
       if ((rc = jur_formod_device(m, n, a.geom, a.rad, a.tau, a.tp, a.np, m->d_status, s))) goto done;
       ti = scene_timed_begin(m, s);
       ek = jurk_scene_quot(&a, nk, s);
       scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("jur_kernel_scene_host: quotient kernel launch failed"); rc = JUR_EHIP; goto done; }
-      /* the blocks of the pass go home; the one wait of the pass */
-      e = nk > 0 ? hipMemcpyAsync(k + (size_t)rp[r0] * nd, a.k, sizeof(double) * (size_t)nk, hipMemcpyDeviceToHost, s) : hipSuccess;
+      if (ek) { jur_set_error("%s: quotient kernel launch failed", who); rc = JUR_EHIP; goto done; }
+      if (ntiles) {
+        ti = scene_timed_begin(m, s);
+        ek = jurk_scene_normal(&a, &nq, ntiles, s);
+        scene_timed_end(m, ti, s);
+        if (ek) { jur_set_error("jur_normal_scene_host: normal-equation kernel launch failed"); rc = JUR_EHIP; goto done; }
+      }
+      /* the blocks of the pass go home (where asked for); the one wait of the pass */
+      e = (nk > 0 && k) ? hipMemcpyAsync(k + (size_t)rp[r0] * nd, a.k, sizeof(double) * (size_t)nk, hipMemcpyDeviceToHost, s) : hipSuccess;
       if (e == hipSuccess) e = hipStreamSynchronize(s);
-      if (e != hipSuccess) { jur_set_error("jur_kernel_scene_host: %s", hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     }
     e = hipMemcpyAsync(rad, a.out_rad, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(tau, a.out_tau, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
     for (int q = 0; q < 3 && e == hipSuccess; q++) e = hipMemcpyAsync(tp[q], a.out_tp + (size_t)q * NR, sizeof(double) * NR, hipMemcpyDeviceToHost, s);
     if (np_out && e == hipSuccess) e = hipMemcpyAsync(np_out, a.out_np, sizeof(int) * NR, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (ntiles) {                                 /* the sums go home here, once */
+      if (e == hipSuccess) e = hipMemcpyAsync(nm->A, nq.A, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(nm->b, nq.b, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(nm->cost, nq.cost, sizeof(double) * (size_t)nslice, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(nm->nlive, nq.nlive, sizeof(long) * (size_t)nslice, hipMemcpyDeviceToHost, s);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { jur_set_error("jur_kernel_scene_host: %s", hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
-  free(first); free(rp); free(head); free(sl); free(off); free(pass); free(cdesc); free(iqa); free(hbase);
+  free(first); free(rp); free(sid); free(srays); free(sl); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa);
+  free(hbase);
   return rc;
 }
 
-int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
-                          double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
-  if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
-  int rc = kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass);
-  /* leave the model with the caller's atmosphere -- after a refusal or an error too: never with the stacked one, which
-   * later calls would accept; if it cannot go back, with none ("no atmosphere set") */
+/* leave the model with the caller's atmosphere -- after a refusal or an error too: never with the stacked one, which
+ * later calls would accept; if it cannot go back, with none ("no atmosphere set") */
+static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
   if (atm->np < 2 || atm->np > JUR_NP) return rc;
   if (rc == JUR_OK) return jur_model_set_atm(m, atm);
   char msg[512];
@@ -1952,6 +2021,20 @@ int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double cons
   if (jur_model_set_atm(m, atm) != JUR_OK) { m->view.atm_np = 0; m->h_atm_n = 0; }
   jur_set_error("%s", msg);
   return rc;
+}
+
+int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                          double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
+  if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL));
+}
+
+int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                          double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                          double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
+  if (!m || !atm) { jur_set_error("jur_normal_scene_host: null argument"); return JUR_EINVAL; }
+  scene_normal_t const nm = {y, weight, A, b, cost, nlive};
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm));
 }
 
 /* ---- drop-in entry points ------------------------------------------------------ */

@@ -1,5 +1,6 @@
-/* jur_scene.c -- layout of the block Jacobian of a scene (jur_kernel_scene_host): which slice of the atmosphere every
- * ray is traced through and which state elements lie in it.  Host arithmetic only: no GPU, no model. */
+/* jur_scene.c -- layout of the block Jacobian of a scene (jur_kernel_scene_host) and of its normal equations
+ * (jur_normal_scene_host): which slice of the atmosphere every ray is traced through, which state elements lie in it
+ * and which distinct slices a scene has.  Host arithmetic only: no GPU, no model. */
 #include <stdlib.h>
 #include "jur_internal.h"
 
@@ -106,4 +107,71 @@ int jur_scene_layout(ctl_t const *ctl, atm_t const *atm, long nr, double const *
   }
   free(upto);
   return JUR_OK;
+}
+
+long jur_scene_elements(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols, int *iq, int *ip) {
+  if (!ctl || !atm || first < 0 || len < 0 || (long)first + len > atm->np) {
+    jur_set_error("scene_elements: slice [%d, %d + %d) outside the atmosphere", first, first, len);
+    return JUR_EINVAL;
+  }
+  return jur_scene_slice_elements(ctl, atm, first, len, cols, iq, ip);
+}
+
+/* The distinct slices (first, len) among the rays that have state elements (rp[r + 1] > rp[r]), in the order the rays
+ * first meet them: sid[r] is the slice of ray r, -1 for a ray without elements.  Slices with the same first point are
+ * chained through `next` from head[first].  *out is malloc'ed (NULL for no slices); returns their number or JUR_ENOMEM. */
+long jur_scene_distinct(int np, long nr, int const *first, int const *len, long const *rp, int *sid, jur_scene_slice_t **out) {
+  jur_scene_slice_t *sl = NULL;
+  long nslice = 0, cap = 0;
+  int *head = (int *)malloc(sizeof(int) * (size_t)(np > 0 ? np : 1));
+  *out = NULL;
+  if (!head) return JUR_ENOMEM;
+  for (int i = 0; i < np; i++) head[i] = -1;
+  for (long r = 0; r < nr; r++) {
+    sid[r] = -1;
+    if (rp[r + 1] == rp[r]) continue;
+    int q = head[first[r]];
+    while (q >= 0 && sl[q].len != len[r]) q = sl[q].next;
+    if (q < 0) {
+      if (nslice == cap) {
+        cap = cap ? 2 * cap : 64;
+        jur_scene_slice_t *grown = (jur_scene_slice_t *)realloc(sl, sizeof *sl * (size_t)cap);
+        if (!grown) { free(sl); free(head); return JUR_ENOMEM; }
+        sl = grown;
+      }
+      q = (int)nslice++;
+      sl[q].first = first[r]; sl[q].len = len[r]; sl[q].next = head[first[r]];
+      sl[q].nel = rp[r + 1] - rp[r];
+      head[first[r]] = q;
+    }
+    sid[r] = q;
+  }
+  free(head);
+  *out = sl;
+  return nslice;
+}
+
+long jur_scene_slices(ctl_t const *ctl, atm_t const *atm, long nr, double const *time, int *sid, int *sfirst, int *slen,
+                      long *wptr, long *aptr) {
+  if (!ctl || !atm || nr < 0 || (nr > 0 && !time)) { jur_set_error("scene_slices: bad arguments"); return JUR_EINVAL; }
+  size_t const NR = (size_t)nr;
+  int *first = (int *)malloc(sizeof(int) * (3 * NR + 1)), *len = first ? first + NR : NULL, *own = first ? len + NR : NULL;
+  long *rp = (long *)malloc(sizeof(long) * (NR + 1));
+  jur_scene_slice_t *sl = NULL;
+  long n = JUR_ENOMEM;
+  if (!first || !rp) { jur_set_error("scene_slices: out of memory"); goto done; }
+  if ((n = jur_scene_layout(ctl, atm, nr, time, first, len, rp))) goto done;
+  n = jur_scene_distinct(atm->np, nr, first, len, rp, sid ? sid : own, &sl);
+  if (n < 0) { jur_set_error("scene_slices: out of memory"); goto done; }
+  if (wptr) wptr[0] = 0;
+  if (aptr) aptr[0] = 0;
+  for (long q = 0; q < n; q++) {
+    if (sfirst) sfirst[q] = sl[q].first;
+    if (slen) slen[q] = sl[q].len;
+    if (wptr) wptr[q + 1] = wptr[q] + sl[q].nel;
+    if (aptr) aptr[q + 1] = aptr[q] + sl[q].nel * sl[q].nel;
+  }
+done:
+  free(first); free(rp); free(sl);
+  return n;
 }

@@ -106,6 +106,12 @@ def lib():
         L.jur_kernel_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_, dp,
                                             C.c_long]
         L.jur_model_last_scene_ms.argtypes = [C.c_void_p, dp, lp_]
+        L.jur_scene_slices.restype = C.c_long
+        L.jur_scene_slices.argtypes = [C.c_void_p, C.c_void_p, C.c_long, dp, ip_, ip_, ip_, lp_, lp_]
+        L.jur_scene_elements.restype = C.c_long
+        L.jur_scene_elements.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, lp_, ip_, ip_]
+        L.jur_normal_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
+                                            dp, dp, dp, dp, dp, lp_, dp, C.c_long]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -380,6 +386,43 @@ class Model:
         return dict(rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, first=lay["first"], len=lay["len"],
                     rowptr=lay["rowptr"], k=k)
 
+    def normal_scene(self, atm, geom, y, weight, rad_in=None, max_rays_per_pass=0, want_k=False, rowptr=None):
+        """Normal equations of a scene per slice (jur_normal_scene_host).  geom: (nr, 7); y, weight: (nr, nd) -> the
+        formod_host dict plus the layout (first, len, rowptr of scene_layout; sid, sfirst, slen, wptr, aptr of
+        scene_slices) and the flat A, b, cost, nlive: A[aptr[s]:aptr[s + 1]].reshape(w, w), b[wptr[s]:wptr[s + 1]].
+        want_k: also the blocks k as kernel_scene returns them; without it no block leaves the device.
+        rowptr and the ctl_t: as kernel_scene."""
+        g = np.ascontiguousarray(np.asarray(geom, dtype=np.float64).T)
+        nr, nd = g.shape[1], self.nd
+        time = g[0] if nr else np.zeros(0)
+        lay = _scene_layout(self.ctl, atm, time)
+        lay.update(scene_slices(self.ctl, atm, time))
+        rp = lay["rowptr"] if rowptr is None else np.ascontiguousarray(rowptr, dtype=np.int64)
+        if rp.shape != lay["rowptr"].shape:
+            raise ValueError("rowptr holds %d entries, the call has %d rays" % (len(rp), nr))
+        yy, ww = (np.ascontiguousarray(x, dtype=np.float64) for x in (y, weight))
+        if yy.shape != (nr, nd) or ww.shape != (nr, nd):
+            raise ValueError("y and weight must be (%d, %d)" % (nr, nd))
+        rad = np.zeros((nr, nd)) if rad_in is None else np.ascontiguousarray(rad_in, dtype=np.float64).copy()
+        tau = np.zeros((nr, nd))
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        ns = len(lay["sfirst"])
+        A, b = np.zeros(int(lay["aptr"][-1])), np.zeros(int(lay["wptr"][-1]))
+        cost, nlive = np.zeros(ns), np.zeros(ns, dtype=np.int64)
+        k = np.zeros(int(lay["rowptr"][-1]) * nd) if want_k else None
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
+        lp_ = C.POINTER(C.c_long)
+        _chk(lib().jur_normal_scene_host(self.h, C.byref(atm), nr, garr, _p(rad), _p(tau), tarr,
+                                         npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(lp_), _p(yy), _p(ww),
+                                         _p(A), _p(b), _p(cost), nlive.ctypes.data_as(lp_), _p(k) if want_k else None,
+                                         max_rays_per_pass))
+        out = dict(lay, rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, A=A, b=b, cost=cost, nlive=nlive)
+        if want_k:
+            out["k"] = k
+        return out
+
     def scene_ms(self):
         """The share of kernel_scene's own kernels in the launches timed since the last call (call kernel_ms first)."""
         ms, n = C.c_double(0), C.c_long(0)
@@ -506,6 +549,33 @@ def scene_columns(ctl, atm, first, length):
     cols = np.zeros(n, dtype=np.int64)
     _chk(lib().jur_scene_columns(C.byref(ctl), C.byref(atm), int(first), int(length), cols.ctypes.data_as(C.POINTER(C.c_long))))
     return cols
+
+
+def scene_slices(ctl, atm, time):
+    """jur_scene_slices (host arithmetic, no GPU): the distinct slices of width > 0 among the rays with these time
+    stamps, in the order the rays first meet them -> dict(sid (nr,; -1: width 0), sfirst, slen (nslice,), wptr, aptr
+    (nslice + 1,): running sums of the widths and of their squares)."""
+    t = np.ascontiguousarray(time, dtype=np.float64)
+    nr = len(t)
+    ip_, lp_ = C.POINTER(C.c_int), C.POINTER(C.c_long)
+    ns = _chk(lib().jur_scene_slices(C.byref(ctl), C.byref(atm), nr, _p(t), None, None, None, None, None))
+    sid = np.zeros(nr, dtype=np.int32)
+    sfirst, slen = np.zeros(ns, dtype=np.int32), np.zeros(ns, dtype=np.int32)
+    wptr, aptr = np.zeros(ns + 1, dtype=np.int64), np.zeros(ns + 1, dtype=np.int64)
+    _chk(lib().jur_scene_slices(C.byref(ctl), C.byref(atm), nr, _p(t), sid.ctypes.data_as(ip_), sfirst.ctypes.data_as(ip_),
+                                slen.ctypes.data_as(ip_), wptr.ctypes.data_as(lp_), aptr.ctypes.data_as(lp_)))
+    return dict(sid=sid, sfirst=sfirst, slen=slen, wptr=wptr, aptr=aptr)
+
+
+def scene_elements(ctl, atm, first, length):
+    """jur_scene_elements: scene_columns plus the quantity (0 p, 1 T, 2 + g q, 2 + ng + w k) and the atmosphere point
+    of every state element of the slice -> dict(cols, iq, ip)."""
+    n = _chk(lib().jur_scene_elements(C.byref(ctl), C.byref(atm), int(first), int(length), None, None, None))
+    cols, iq, ip = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    ip_ = C.POINTER(C.c_int)
+    _chk(lib().jur_scene_elements(C.byref(ctl), C.byref(atm), int(first), int(length), cols.ctypes.data_as(C.POINTER(C.c_long)),
+                                  iq.ctypes.data_as(ip_), ip.ctypes.data_as(ip_)))
+    return dict(cols=cols, iq=iq, ip=ip)
 
 
 def scene_blocks_to_dense(ctl, atm, out, n=None):
