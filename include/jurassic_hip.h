@@ -273,6 +273,60 @@ int  jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double con
                            double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
                            double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass);
 
+/* The Levenberg-Marquardt step of every slice: a batched, ragged Cholesky solve on the device of the damped, optionally
+ * regularised normal equations, for nlam dampings in one call.  One system (slice s, width w, damping lam), with
+ * r = prior_ivar (inverse a-priori variances) and d = prior_dx (a-priori minus current state), both 0 without a prior:
+ *   D_i = A_ii + r_i;  element i is live when D_i > 0 (anything else, NaN included, is dead)
+ *   s_i = D_i (JUR_DAMP_MARQUARDT) or r_i (JUR_DAMP_PRIOR, the damping (1 + lam) Sa^-1)
+ *   M_ii = fma(lam, s_i, D_i),  M_ij = A_ij (i > j, both live),  g_i = fma(r_i, d_i, b_i)
+ *   M = L L^T on the live elements, L z = g, L^T dx = z;  pred = sum dx_i * (g_i + lam s_i dx_i),
+ * pred being the decrease of the cost sum weight (y - F)^2 + sum r (x - xa)^2 that the linearised model predicts for the
+ * step.  Only the diagonal and the lower triangle of A_s are read.  A dead element's row and column are ignored, its dx
+ * is +0.0 and in L its diagonal is 1 and the rest of its row and column 0 (in the A_s of jur_normal_scene_host a zero
+ * diagonal means a zero row, so nothing is lost).  A pivot that is not > 0 just before its square root (NaN included)
+ * breaks the system down: status = 1 + the index in the slice of that column, dx_s all +0.0, pred 0, L_s all zeros; no
+ * other system is affected.  Otherwise status = 0.
+ *
+ * jur_solve_in_t: lam is [nlam][nslice], each >= 0 and finite; prior_ivar (each >= 0 and finite) and prior_dx (finite)
+ *   hold wptr[nslice] doubles each and are given both or neither; JUR_DAMP_PRIOR needs them.
+ * jur_solve_out_t: dx [nlam][wptr[nslice]], pred and status [nlam][nslice]; L is optional, [nlam][aptr[nslice]], L_s laid
+ *   out as A_s with exact zeros above the diagonal.  The caller owns all of them.
+ * Every double of a system depends on its own inputs and on w alone: not on the number or the order of the systems of
+ *   the call, not on nlam, not on max_rays_per_pass, not on which of the two entries was called.  No atomics; every sum
+ *   runs in an order fixed by w.
+ * jur_solve_slices_host: systems the caller holds (the re-solve after a rejected step): A_s at A + aptr[s], [w_s][w_s],
+ *   aptr the running sum of w_s^2 with w_s = wptr[s + 1] - wptr[s]; b_s at b + wptr[s].  The model supplies the device
+ *   and the stream and the call is ordered against the model's other calls; the model's atmosphere and workspace are
+ *   not touched.  nslice == 0 is JUR_OK and writes nothing.
+ * jur_step_scene_host: jur_normal_scene_host followed by the solve on accumulators that stay on the device: every
+ *   argument of that entry as there, with the same doubles out and the same refusals; A, b and k may be NULL and then
+ *   never leave the device.  The layout of dx, pred, status, L is that of jur_scene_slices of the same rays.
+ * JUR_EINVAL, with a message that names the slice and the damping or the element: nlam < 1; an unknown mode; a lam that
+ *   is negative or not finite; a prior_ivar that is negative or not finite; a prior_dx that is not finite; one of the
+ *   prior pair without the other; JUR_DAMP_PRIOR without a prior; NULL among lam, dx, pred, status; wptr not ascending.
+ * JUR_ENOMEM (jur_step_scene_host, before anything is launched) when the accumulators and the solver scratch -- one
+ *   more copy of the matrices, the vectors of one damping and the outputs of all -- do not fit beside the stacked
+ *   slices in half the workspace budget.  JUR_EHIP when a launch fails.
+ * The kernel's time counts into jur_model_last_scene_ms. */
+enum { JUR_DAMP_MARQUARDT = 0, JUR_DAMP_PRIOR = 1 };
+typedef struct {
+  int nlam, mode;
+  double const *lam;                      /* [nlam][nslice] */
+  double const *prior_ivar, *prior_dx;    /* [wptr[nslice]] each; both or neither */
+} jur_solve_in_t;
+typedef struct {
+  double *dx;                             /* [nlam][wptr[nslice]] */
+  double *pred;                           /* [nlam][nslice] */
+  int *status;                            /* [nlam][nslice] */
+  double *L;                              /* optional, [nlam][aptr[nslice]], rows as A_s, strict upper 0 */
+} jur_solve_out_t;
+int  jur_solve_slices_host(jur_model_t *m, long nslice, long const *wptr, double const *A, double const *b,
+                           jur_solve_in_t const *in, jur_solve_out_t const *out);
+int  jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                         double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                         jur_solve_in_t const *in, jur_solve_out_t const *out,
+                         double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass);
+
 /* Curtis-Godson means along each line of sight (reference curtis_godson(), jr_common.h:455-473, which
  * upstream compiles only with -DCURTIS_GODSON for FORMOD=1): per ray, emitter and LOS point the
  * column-weighted pressure cgp, temperature cgt and the cumulative column cgu.  Host arrays

@@ -209,6 +209,23 @@ typedef struct {
 /* the terms of the rays [a->r0, a->r1) from the blocks a->k and the results a->out_rad of the pass (after jurk_scene_quot) */
 int jurk_scene_normal(jur_scene_pass_t const *a, jur_scene_normal_t const *n, long ntiles, void *stream);
 
+/* Levenberg-Marquardt step of a scene (jur_solve_slices_host, jur_step_scene_host): the damped, optionally regularised
+ * system of every slice under one damping each, one workgroup per system.  All arrays are device memory. */
+typedef struct {
+  long nslice;
+  long const *wptr, *aptr;      /* [nslice + 1] running sums of w_s and of w_s^2                             */
+  double const *A, *b;          /* [aptr[nslice]], [wptr[nslice]] read only: diagonal and lower triangle of A_s */
+  double const *lam;            /* [nslice] the damping of every system                                     */
+  double const *prior_ivar, *prior_dx;   /* [wptr[nslice]] each, or both NULL                                */
+  int mode;                     /* JUR_DAMP_MARQUARDT or JUR_DAMP_PRIOR                                      */
+  double *M;                    /* [aptr[nslice]] scratch: M_s, factored in place; L_s afterwards             */
+  double *live;                 /* [wptr[nslice]] scratch: D_i of a live element, 0 of a dead one             */
+  double *dx;                   /* [wptr[nslice]] g, then z, then the step, written                           */
+  double *pred;                 /* [nslice] written                                                         */
+  int *status;                  /* [nslice] written: 0, or 1 + the column whose pivot was not > 0            */
+} jur_scene_solve_t;
+int jurk_scene_solve(jur_scene_solve_t const *a, void *stream);
+
 /* host arithmetic shared by jur_model.c and jur_scene.c (not exported) */
 #define JUR_HIDDEN __attribute__((visibility("hidden")))
 JUR_HIDDEN int jur_atm_slice(double const *time, long n, double t, long *first);

@@ -2474,6 +2474,192 @@ __global__ __launch_bounds__(256) void jur_scene_normal_kernel(jur_scene_pass_t 
   if (with_cost) { n.cost[s] = acc_c; n.nlive[s] = count; }
 }
 
+// ---- Levenberg-Marquardt step of a scene (jur_solve_slices_host, jur_step_scene_host) -------------------------------
+// One workgroup per system: M = L L^T in place in the system's part of the scratch a.M (global memory, L2-resident),
+// L z = g and L^T dx = z in a.dx, pred.  Nothing waits on another workgroup, no atomics; every chain of operations is
+// fixed by w alone.  A dead element (D_i = A_ii + r_i not > 0) is an identity row and column with g_i = 0: its L_ii is 1,
+// it adds exact zeros to the chains of the live elements, and its dx is set to +0.0 at the end.
+//
+// Right-looking, 16 columns a step: the 16 x 16 diagonal block is factored in LDS (T; a pivot that is not > 0 just before
+// its square root ends the system: status 1 + column, L, dx and pred zeroed) and the forward substitution of its 16
+// elements of z is done with it; the rows below take one lane each (their 16 entries of the panel in registers, one true
+// division per entry, then their z); the trailing update takes the panel from LDS in chunks of 64 rows (PI, PJ: what
+// is staged does not grow with w), a 4 x 4 micro-tile of a 64 x 64 piece of the lower triangle per lane.  The back
+// substitution walks the blocks upwards, lane i taking column i of the block's rows.  LDS: 21 KB.
+#define SOLVE_NB 16
+#define SOLVE_CH 64
+__global__ __launch_bounds__(256) void jur_scene_solve_kernel(jur_scene_solve_t a) {
+  __shared__ double T[SOLVE_NB][SOLVE_NB + 1], zb[SOLVE_NB], dg[SOLVE_NB];
+  __shared__ double PI[SOLVE_NB][SOLVE_CH + 1], PJ[SOLVE_NB][SOLVE_CH + 1];
+  __shared__ double red[256];
+  long const s = blockIdx.x;
+  int const tid = threadIdx.x, w = (int)(a.wptr[s + 1] - a.wptr[s]);
+  if (w <= 0) {                                             // (uniform)
+    if (tid == 0) { a.pred[s] = 0.; a.status[s] = 0; }
+    return;
+  }
+  double const *const A = a.A + a.aptr[s], *const b = a.b + a.wptr[s];
+  double const *const pr = a.prior_ivar ? a.prior_ivar + a.wptr[s] : nullptr;
+  double const *const pd = a.prior_ivar ? a.prior_dx + a.wptr[s] : nullptr;
+  double *const M = a.M + a.aptr[s], *const lv = a.live + a.wptr[s], *const z = a.dx + a.wptr[s];
+  double const lam = a.lam[s];
+  bool const by_prior = a.mode == JUR_DAMP_PRIOR;
+
+  // D, liveness, M_ii and g
+  for (int i = tid; i < w; i += 256) {
+    double const ri = pr ? pr[i] : 0., di = pr ? pd[i] : 0., D = A[(long)i * w + i] + ri;
+    bool const live = D > 0;
+    lv[i] = live ? D : 0.;
+    M[(long)i * w + i] = live ? fma(lam, by_prior ? ri : D, D) : 1.;
+    z[i] = live ? fma(ri, di, b[i]) : 0.;
+  }
+  __syncthreads();
+  // the lower triangle between live elements; zeros elsewhere
+  for (int i = tid >> 6; i < w; i += 4) {
+    bool const li = lv[i] > 0;
+    for (int j = tid & 63; j < w; j += 64)
+      if (j != i) M[(long)i * w + j] = (j < i && li && lv[j] > 0) ? A[(long)i * w + j] : 0.;
+  }
+  __syncthreads();
+
+  int const tr = tid >> 4, tc = tid & 15;
+  int bad = 0;                                              // 1 + the column of the pivot that is not > 0 (uniform)
+  for (int k0 = 0; k0 < w && !bad; k0 += SOLVE_NB) {
+    int const nb = min(SOLVE_NB, w - k0);
+    if (tr < nb && tc <= tr) T[tr][tc] = M[(long)(k0 + tr) * w + k0 + tc];
+    if (tid < nb) zb[tid] = z[k0 + tid];
+    __syncthreads();
+    for (int k = 0; k < nb; k++) {
+      double const piv = T[k][k];                           // (stays as it is: the root goes to dg)
+      if (!(piv > 0)) { bad = 1 + k0 + k; break; }          // (every lane reads the same value)
+      double const l = sqrt(piv);
+      if (tc == k && tr > k && tr < nb) T[tr][k] = T[tr][k] / l;
+      if (tid == 0) dg[k] = l;
+      __syncthreads();
+      if (tr < nb && tc > k && tc <= tr) T[tr][tc] = fma(-T[tr][k], T[tc][k], T[tr][tc]);
+      __syncthreads();
+    }
+    if (bad) break;
+    if (tid < nb) T[tid][tid] = dg[tid];
+    __syncthreads();
+    if (tid == 0)
+      for (int c = 0; c < nb; c++) {
+        double acc = zb[c];
+        for (int k = 0; k < c; k++) acc = fma(-T[c][k], zb[k], acc);
+        zb[c] = acc / T[c][c];
+      }
+    if (tr < nb && tc <= tr) M[(long)(k0 + tr) * w + k0 + tc] = T[tr][tc];
+    __syncthreads();
+    if (tid < nb) z[k0 + tid] = zb[tid];
+    if (k0 + SOLVE_NB >= w) break;                          // (no rows below: nb == SOLVE_NB from here on)
+    // the panel: row i of L's 16 columns, then z_i
+    for (int i = k0 + SOLVE_NB + tid; i < w; i += 256) {
+      double *const row = M + (long)i * w + k0;
+      double x[SOLVE_NB];
+#pragma unroll
+      for (int c = 0; c < SOLVE_NB; c++) x[c] = row[c];
+      double zi = z[i];
+#pragma unroll
+      for (int c = 0; c < SOLVE_NB; c++) {
+        double acc = x[c];
+#pragma unroll
+        for (int k = 0; k < c; k++) acc = fma(-x[k], T[c][k], acc);
+        x[c] = acc / T[c][c];
+        row[c] = x[c];
+        zi = fma(-x[c], zb[c], zi);
+      }
+      z[i] = zi;
+    }
+    __syncthreads();
+    // the trailing update M_ij -= sum_k L_ik L_jk, k ascending, for k0 + 16 <= j <= i
+    for (int I0 = k0 + SOLVE_NB; I0 < w; I0 += SOLVE_CH) {
+      for (int e = tid; e < SOLVE_NB * SOLVE_CH; e += 256) {
+        int const rr = e >> 4, kk = e & 15, i = I0 + rr;
+        PI[kk][rr] = i < w ? M[(long)i * w + k0 + kk] : 0.;
+      }
+      for (int J0 = k0 + SOLVE_NB; J0 <= I0; J0 += SOLVE_CH) {
+        for (int e = tid; e < SOLVE_NB * SOLVE_CH; e += 256) {
+          int const rr = e >> 4, kk = e & 15, j = J0 + rr;
+          PJ[kk][rr] = j < w ? M[(long)j * w + k0 + kk] : 0.;
+        }
+        __syncthreads();
+        double acc[4][4];
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            int const i = I0 + tr + 16 * p, j = J0 + tc + 16 * q;
+            acc[p][q] = (i < w && j <= i) ? M[(long)i * w + j] : 0.;
+          }
+#pragma unroll
+        for (int k = 0; k < SOLVE_NB; k++) {
+          double pi[4], pj[4];
+#pragma unroll
+          for (int p = 0; p < 4; p++) { pi[p] = PI[k][tr + 16 * p]; pj[p] = PJ[k][tc + 16 * p]; }
+#pragma unroll
+          for (int p = 0; p < 4; p++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) acc[p][q] = fma(-pi[p], pj[q], acc[p][q]);
+        }
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            int const i = I0 + tr + 16 * p, j = J0 + tc + 16 * q;
+            if (i < w && j <= i) M[(long)i * w + j] = acc[p][q];
+          }
+        __syncthreads();
+      }
+    }
+  }
+  if (bad) {
+    for (long e = tid; e < (long)w * w; e += 256) M[e] = 0.;
+    for (int i = tid; i < w; i += 256) z[i] = 0.;
+    if (tid == 0) { a.pred[s] = 0.; a.status[s] = bad; }
+    return;
+  }
+  __syncthreads();
+
+  // L^T dx = z, from the last block upwards
+  for (int k0 = ((w - 1) / SOLVE_NB) * SOLVE_NB; k0 >= 0; k0 -= SOLVE_NB) {
+    int const nb = min(SOLVE_NB, w - k0);
+    if (tr < nb && tc <= tr) T[tr][tc] = M[(long)(k0 + tr) * w + k0 + tc];
+    if (tid < nb) zb[tid] = z[k0 + tid];
+    __syncthreads();
+    if (tid == 0)
+      for (int c = nb - 1; c >= 0; c--) {
+        double acc = zb[c];
+        for (int k = c + 1; k < nb; k++) acc = fma(-T[k][c], zb[k], acc);
+        zb[c] = acc / T[c][c];
+      }
+    __syncthreads();
+    if (tid < nb) z[k0 + tid] = zb[tid];
+    for (int i = tid; i < k0; i += 256) {
+      double zi = z[i];
+      for (int k = 0; k < nb; k++) zi = fma(-M[(long)(k0 + k) * w + i], zb[k], zi);
+      z[i] = zi;
+    }
+    __syncthreads();
+  }
+
+  // dx of the dead elements, pred: every lane its elements ascending, then a fixed tree over the lanes
+  double sum = 0.;
+  for (int i = tid; i < w; i += 256) {
+    double const D = lv[i];
+    if (D > 0) {
+      double const ri = pr ? pr[i] : 0., di = pr ? pd[i] : 0., dx = z[i];
+      sum += dx * fma(lam * (by_prior ? ri : D), dx, fma(ri, di, b[i]));
+    } else z[i] = 0.;
+  }
+  red[tid] = sum;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) { a.pred[s] = red[0]; a.status[s] = 0; }
+}
+
 }  // namespace
 
 extern "C" int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream) {
@@ -2510,6 +2696,13 @@ extern "C" int jurk_scene_quot(jur_scene_pass_t const *a, long nk, void *stream)
 extern "C" int jurk_scene_normal(jur_scene_pass_t const *a, jur_scene_normal_t const *n, long ntiles, void *stream) {
   if (ntiles <= 0 || a->r1 <= a->r0) return 0;
   hipLaunchKernelGGL(jur_scene_normal_kernel, dim3((unsigned)ntiles), dim3(256), 0, (hipStream_t)stream, *a, *n);
+  return (int)hipGetLastError();
+}
+
+// (one damping per launch: a->lam, a->dx, a->pred, a->status are that damping's)
+extern "C" int jurk_scene_solve(jur_scene_solve_t const *a, void *stream) {
+  if (a->nslice <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_solve_kernel, dim3((unsigned)a->nslice), dim3(256), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

@@ -1716,13 +1716,103 @@ typedef struct {
   long *nlive;
 } scene_normal_t;
 
+/* ---- Levenberg-Marquardt step of the slices (jur_solve_slices_host, jur_step_scene_host) ------------------------- */
+/* what jur_step_scene_host adds to jur_normal_scene_host */
+typedef struct { jur_solve_in_t const *in; jur_solve_out_t const *out; } scene_solve_t;
+
+/* the refusals that need no sizes */
+static int solve_check_args(char const *who, jur_solve_in_t const *in, jur_solve_out_t const *out) {
+  if (!in || !out) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if (in->nlam < 1) { jur_set_error("%s: nlam = %d: at least one damping is needed", who, in->nlam); return JUR_EINVAL; }
+  if (in->mode != JUR_DAMP_MARQUARDT && in->mode != JUR_DAMP_PRIOR) { jur_set_error("%s: unknown mode %d", who, in->mode); return JUR_EINVAL; }
+  if (!in->prior_ivar != !in->prior_dx) {
+    jur_set_error("%s: %s without %s: the prior is given as a pair", who, in->prior_ivar ? "prior_ivar" : "prior_dx",
+                  in->prior_ivar ? "prior_dx" : "prior_ivar");
+    return JUR_EINVAL;
+  }
+  if (in->mode == JUR_DAMP_PRIOR && !in->prior_ivar) { jur_set_error("%s: JUR_DAMP_PRIOR without a prior", who); return JUR_EINVAL; }
+  if (!in->lam || !out->dx || !out->pred || !out->status) {
+    jur_set_error("%s: null argument (%s)", who, !in->lam ? "lam" : !out->dx ? "dx" : !out->pred ? "pred" : "status");
+    return JUR_EINVAL;
+  }
+  return JUR_OK;
+}
+
+/* the dampings and the prior of nslice systems laid out by wptr */
+static int solve_check_values(char const *who, long nslice, long const *wptr, jur_solve_in_t const *in) {
+  for (int l = 0; l < in->nlam; l++)
+    for (long q = 0; q < nslice; q++) {
+      double const v = in->lam[(size_t)l * (size_t)nslice + (size_t)q];
+      if (!(v >= 0) || isinf(v)) {
+        jur_set_error("%s: lam of slice %ld, damping %d is %g: negative or not finite", who, q, l, v);
+        return JUR_EINVAL;
+      }
+    }
+  if (in->prior_ivar)
+    for (long q = 0; q < nslice; q++)
+      for (long e = wptr[q]; e < wptr[q + 1]; e++) {
+        double const r = in->prior_ivar[e], d = in->prior_dx[e];
+        if (!(r >= 0) || isinf(r)) {
+          jur_set_error("%s: prior_ivar of slice %ld, element %ld is %g: negative or not finite", who, q, e - wptr[q], r);
+          return JUR_EINVAL;
+        }
+        if (!isfinite(d)) {
+          jur_set_error("%s: prior_dx of slice %ld, element %ld is %g: not finite", who, q, e - wptr[q], d);
+          return JUR_EINVAL;
+        }
+      }
+  return JUR_OK;
+}
+
+/* doubles of device memory the solve needs beside A and b: the scratch copy of the matrices, the liveness of one
+ * damping, then for all dampings dx | pred | lam, the prior pair, status (ints, rounded up) */
+static size_t solve_doubles(size_t na, size_t nb, size_t ns, size_t nlam, int prior) {
+  return na + nb + nlam * nb + 2 * nlam * ns + (prior ? 2 * nb : 0) + (nlam * ns + 1) / 2;
+}
+
+/* Enqueues on s: the uploads of the dampings and the prior, one launch per damping over the one scratch (stream order
+ * protects the copy-out of L), the copies home.  The caller waits for the stream before the host arrays go. */
+static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nslice, long na, long nb, long const *d_wptr,
+                         long const *d_aptr, double const *d_A, double const *d_b, double *W, jur_solve_in_t const *in,
+                         jur_solve_out_t const *out) {
+  size_t const NA = (size_t)na, NB = (size_t)nb, NS = (size_t)nslice, NL = (size_t)in->nlam, npr = in->prior_ivar ? NB : 0;
+  double *const dM = W, *const dlive = dM + NA, *const ddx = dlive + NB, *const dpred = ddx + NL * NB, *const dlam = dpred + NL * NS,
+         *const dr = dlam + NL * NS, *const dd = dr + npr;
+  int *const dstat = (int *)(dd + npr);
+  hipError_t e = hipMemcpyAsync(dlam, in->lam, sizeof(double) * NL * NS, hipMemcpyHostToDevice, s);
+  if (npr && e == hipSuccess) e = hipMemcpyAsync(dr, in->prior_ivar, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+  if (npr && e == hipSuccess) e = hipMemcpyAsync(dd, in->prior_dx, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
+  jur_scene_solve_t q;
+  memset(&q, 0, sizeof q);
+  q.nslice = nslice; q.wptr = d_wptr; q.aptr = d_aptr; q.A = d_A; q.b = d_b;
+  q.prior_ivar = npr ? dr : NULL; q.prior_dx = npr ? dd : NULL; q.mode = in->mode;
+  q.M = dM; q.live = dlive;
+  for (size_t l = 0; l < NL; l++) {
+    q.lam = dlam + l * NS; q.dx = ddx + l * NB; q.pred = dpred + l * NS; q.status = dstat + l * NS;
+    int const ti = scene_timed_begin(m, s);
+    int const ek = jurk_scene_solve(&q, s);
+    scene_timed_end(m, ti, s);
+    if (ek) { jur_set_error("%s: solve kernel launch failed", who); return JUR_EHIP; }
+    if (out->L && NA) e = hipMemcpyAsync(out->L + l * NA, dM, sizeof(double) * NA, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
+  }
+  if (NB) e = hipMemcpyAsync(out->dx, ddx, sizeof(double) * NL * NB, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(out->pred, dpred, sizeof(double) * NL * NS, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(out->status, dstat, sizeof(int) * NL * NS, hipMemcpyDeviceToHost, s);
+  if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
+  return JUR_OK;
+}
+
 /* nm == NULL: jur_kernel_scene_host.  Otherwise the normal equations of the slices are accumulated on the device after
- * the quotients of every pass, and the blocks go home only where k is given. */
+ * the quotients of every pass, and the blocks go home only where k is given.  With sv (jur_step_scene_host; nm is given
+ * then) the systems are solved where they lie after the last pass, and A and b go home only where they are given. */
 static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                              double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
-                             scene_normal_t const *nm) {
-  char const *const who = nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+                             scene_normal_t const *nm, scene_solve_t const *sv) {
+  char const *const who = sv ? "jur_step_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
   ctl_t const *ctl = m->ctl;
   if (ctl->hydz >= 0) {
     jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so every p, T or H2O element moves "
@@ -1759,12 +1849,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   }
   if (rp[nr] > 0 && !k && !nm) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
   if (nm) {
-    if (!nm->y || !nm->weight) { jur_set_error("jur_normal_scene_host: null argument"); rc = JUR_EINVAL; goto done; }
+    if (!nm->y || !nm->weight) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
     for (long r = 0; r < nr; r++)
       for (int id = 0; id < nd; id++) {
         double const w = nm->weight[(size_t)r * nd + id];
         if (!(w >= 0) || isinf(w)) {
-          jur_set_error("jur_normal_scene_host: the weight of ray %ld, channel %d is %g: negative or not finite", r, id, w);
+          jur_set_error("%s: the weight of ray %ld, channel %d is %g: negative or not finite", who, r, id, w);
           rc = JUR_EINVAL;
           goto done;
         }
@@ -1790,7 +1880,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   long nlist = 0, ntiles = 0, na = 0, nb = 0;
   long *sptr = NULL, *tptr = NULL, *wptr = NULL, *aptr = NULL;
   if (nm && nslice > 0) {
-    if (!nm->A || !nm->b || !nm->cost || !nm->nlive) { jur_set_error("jur_normal_scene_host: null argument"); rc = JUR_EINVAL; goto done; }
+    if ((!sv && (!nm->A || !nm->b)) || !nm->cost || !nm->nlive) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
     nptr = (long *)calloc(4 * ((size_t)nslice + 1), sizeof(long));
     srays = (int *)malloc(sizeof(int) * NR);
     if (!nptr || !srays) { rc = JUR_ENOMEM; goto done; }
@@ -1807,11 +1897,15 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     for (long q = nslice; q > 0; q--) sptr[q] = sptr[q - 1];                          /* ... and starts it again      */
     sptr[0] = 0;
     nlist = sptr[nslice]; ntiles = tptr[nslice]; na = aptr[nslice]; nb = wptr[nslice];
-    if (ntiles > 0x7fffffffL) { jur_set_error("jur_normal_scene_host: 2^31 tiles: call with the rays of fewer slices at a time"); rc = JUR_EINVAL; goto done; }
+    if (ntiles > 0x7fffffffL) { jur_set_error("%s: 2^31 tiles: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
+    if (sv && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
   }
   /* what the sums add to the slab: the accumulators A | b | cost | nlive, y and weight, the four running sums, the ray lists */
   size_t const nacc = (size_t)na + (size_t)nb + 2 * (size_t)(ntiles ? nslice : 0);
   size_t const acc_bytes = ntiles ? sizeof(double) * (nacc + 2 * NR * (size_t)nd + 4 * ((size_t)nslice + 1)) + sizeof(int) * (size_t)nlist : 0;
+  /* ... and the solve: one more copy of the matrices, the vectors of one damping, the outputs of all */
+  size_t const nsv = (sv && ntiles) ? solve_doubles((size_t)na, (size_t)nb, (size_t)nslice, (size_t)sv->in->nlam, sv->in->prior_ivar != NULL) : 0;
+  size_t const sv_bytes = sizeof(double) * nsv;
   long const ncopy = ncopies + 1;
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)nt;
   if (nt > 0x7fffffffL || (long)atm_bytes > m->ws_budget / 2) {
@@ -1821,8 +1915,14 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     goto done;
   }
   if (acc_bytes > 0 && (double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
-    jur_set_error("jur_normal_scene_host: the normal matrices (%ld doubles) do not fit beside the stacked atmosphere (%zu bytes) "
-                  "in the workspace budget: call with the rays of fewer slices at a time", na, atm_bytes);
+    jur_set_error("%s: the normal matrices (%ld doubles) do not fit beside the stacked atmosphere (%zu bytes) "
+                  "in the workspace budget: call with the rays of fewer slices at a time", who, na, atm_bytes);
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+  if (sv_bytes > 0 && (double)atm_bytes + (double)acc_bytes + (double)sv_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("%s: the solver scratch (%zu bytes) does not fit beside the normal matrices (%ld doubles) and the stacked "
+                  "atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, sv_bytes, na, atm_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
@@ -1834,7 +1934,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
      * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
      * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
-    long const avail = (m->ws_budget - (long)atm_bytes - (long)acc_bytes) / 16;
+    long const avail = (m->ws_budget - (long)atm_bytes - (long)acc_bytes - (long)sv_bytes) / 16;
     cap = avail / (long)slot_bytes;
     if (cap < 4096) cap = 4096;
   }
@@ -1889,9 +1989,9 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
                o_tau = o_rad + nrd, o_tp = o_tau + nrd, o_h = o_tp + 3 * NR, o_k = o_h + (size_t)ncopy,
                o_rowptr = o_k + (size_t)kmax, o_off = o_rowptr + NR + 1, o_y = o_off + (size_t)ncopy + 1;
   /* (the normal equations' part, empty without them: y, weight, the accumulators A | b | cost | nlive in one piece,
-   * then sptr | tptr | wptr | aptr) */
+   * then sptr | tptr | wptr | aptr, then what the solve needs) */
   size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
-               o_int = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0);
+               o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_int = o_sv + nsv;
   size_t const nint = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, bytes = sizeof(double) * o_int + sizeof(int) * nint;
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
   hipStream_t const s = m->stream;
@@ -1982,21 +2082,22 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         ti = scene_timed_begin(m, s);
         ek = jurk_scene_normal(&a, &nq, ntiles, s);
         scene_timed_end(m, ti, s);
-        if (ek) { jur_set_error("jur_normal_scene_host: normal-equation kernel launch failed"); rc = JUR_EHIP; goto done; }
+        if (ek) { jur_set_error("%s: normal-equation kernel launch failed", who); rc = JUR_EHIP; goto done; }
       }
       /* the blocks of the pass go home (where asked for); the one wait of the pass */
       e = (nk > 0 && k) ? hipMemcpyAsync(k + (size_t)rp[r0] * nd, a.k, sizeof(double) * (size_t)nk, hipMemcpyDeviceToHost, s) : hipSuccess;
       if (e == hipSuccess) e = hipStreamSynchronize(s);
       if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     }
+    if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out))) goto done;
     e = hipMemcpyAsync(rad, a.out_rad, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(tau, a.out_tau, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
     for (int q = 0; q < 3 && e == hipSuccess; q++) e = hipMemcpyAsync(tp[q], a.out_tp + (size_t)q * NR, sizeof(double) * NR, hipMemcpyDeviceToHost, s);
     if (np_out && e == hipSuccess) e = hipMemcpyAsync(np_out, a.out_np, sizeof(int) * NR, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
     if (ntiles) {                                 /* the sums go home here, once */
-      if (e == hipSuccess) e = hipMemcpyAsync(nm->A, nq.A, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(nm->b, nq.b, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
+      if (nm->A && e == hipSuccess) e = hipMemcpyAsync(nm->A, nq.A, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, s);
+      if (nm->b && e == hipSuccess) e = hipMemcpyAsync(nm->b, nq.b, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
       if (e == hipSuccess) e = hipMemcpyAsync(nm->cost, nq.cost, sizeof(double) * (size_t)nslice, hipMemcpyDeviceToHost, s);
       if (e == hipSuccess) e = hipMemcpyAsync(nm->nlive, nq.nlive, sizeof(long) * (size_t)nslice, hipMemcpyDeviceToHost, s);
     }
@@ -2026,7 +2127,7 @@ static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
 int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                           double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL));
 }
 
 int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -2034,7 +2135,76 @@ int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double cons
                           double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_normal_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL));
+}
+
+int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                        double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                        jur_solve_in_t const *in, jur_solve_out_t const *out,
+                        double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
+  if (!m || !atm) { jur_set_error("jur_step_scene_host: null argument"); return JUR_EINVAL; }
+  scene_normal_t const nm = {y, weight, A, b, cost, nlive};
+  scene_solve_t const sv = {in, out};
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv));
+}
+
+/* Systems the caller holds.  The device slab of the scene entries serves (it holds nothing between calls): wptr | aptr,
+ * A, b, then the solver's part.  Neither the atmosphere nor the forward model's workspace is touched. */
+int jur_solve_slices_host(jur_model_t *m, long nslice, long const *wptr, double const *A, double const *b,
+                          jur_solve_in_t const *in, jur_solve_out_t const *out) {
+  char const *const who = "jur_solve_slices_host";
+  if (!m || nslice < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  int rc = solve_check_args(who, in, out);
+  if (rc) return rc;
+  if (nslice == 0) return JUR_OK;
+  if (nslice > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 systems per call", who); return JUR_EINVAL; }
+  if (!wptr || !A || !b) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  size_t const NS = (size_t)nslice;
+  long *ptr = (long *)malloc(sizeof(long) * 2 * (NS + 1)), *aptr = ptr ? ptr + NS + 1 : NULL;
+  if (!ptr) return JUR_ENOMEM;
+  int enqueued = 0;
+  aptr[0] = 0;
+  for (long q = 0; q < nslice; q++) {
+    long const w = wptr[q + 1] - wptr[q];
+    if (wptr[0] != 0 || w < 0 || w > 0x7fffffffL) {
+      jur_set_error("%s: wptr is not an ascending running sum of widths from 0 (slice %ld)", who, q);
+      rc = JUR_EINVAL;
+      goto done;
+    }
+    aptr[q + 1] = aptr[q] + w * w;
+  }
+  memcpy(ptr, wptr, sizeof(long) * (NS + 1));
+  if ((rc = solve_check_values(who, nslice, wptr, in))) goto done;
+  {
+    long const na = aptr[nslice], nb = wptr[nslice];
+    size_t const o_A = 2 * (NS + 1), o_b = o_A + (size_t)na, o_sv = o_b + (size_t)nb;
+    size_t const bytes = sizeof(double) * (o_sv + solve_doubles((size_t)na, (size_t)nb, NS, (size_t)in->nlam, in->prior_ivar != NULL));
+    if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
+    hipStream_t const s = m->stream;
+    if ((rc = wait_done(m, s))) goto done;
+    if (bytes > m->scene_bytes) {
+      if (m->d_scene) (void)hipFree(m->d_scene);
+      m->d_scene = NULL; m->scene_bytes = 0;
+      if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
+        (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
+      }
+      m->scene_bytes = bytes;
+    }
+    double *const D = (double *)m->d_scene;
+    long *const L = (long *)m->d_scene;
+    enqueued = 1;
+    hipError_t e = hipMemcpyAsync(L, ptr, sizeof(long) * 2 * (NS + 1), hipMemcpyHostToDevice, s);
+    if (na && e == hipSuccess) e = hipMemcpyAsync(D + o_A, A, sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s);
+    if (nb && e == hipSuccess) e = hipMemcpyAsync(D + o_b, b, sizeof(double) * (size_t)nb, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if ((rc = solve_enqueue(m, s, who, nslice, na, nb, L, L + NS + 1, D + o_A, D + o_b, D + o_sv, in, out))) goto done;
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
+  }
+done:
+  if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
+  free(ptr);
+  return rc;
 }
 
 /* ---- drop-in entry points ------------------------------------------------------ */

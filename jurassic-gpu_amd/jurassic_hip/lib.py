@@ -112,6 +112,9 @@ def lib():
         L.jur_scene_elements.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, lp_, ip_, ip_]
         L.jur_normal_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
                                             dp, dp, dp, dp, dp, lp_, dp, C.c_long]
+        L.jur_solve_slices_host.argtypes = [C.c_void_p, C.c_long, lp_, dp, dp, C.c_void_p, C.c_void_p]
+        L.jur_step_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
+                                          dp, dp, C.c_void_p, C.c_void_p, dp, dp, dp, lp_, dp, C.c_long]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -423,6 +426,65 @@ class Model:
             out["k"] = k
         return out
 
+    def step_scene(self, atm, geom, y, weight, lam, mode=0, prior_ivar=None, prior_dx=None, want_normal=False, want_k=False,
+                   want_factor=False, rad_in=None, max_rays_per_pass=0, rowptr=None):
+        """Levenberg-Marquardt step of every slice of a scene (jur_step_scene_host): normal_scene followed by the solve
+        on the device.  lam, mode, prior_ivar, prior_dx, want_factor: as solve_slices, laid out by scene_slices of these
+        rays -> normal_scene's dict without A and b, plus dx (nlam, n), pred and status (nlam, nslice) and, with
+        want_factor, L (nlam, aptr[-1]).  want_normal: also A and b; want_k: also the blocks.  What is not wanted never
+        leaves the device."""
+        g = np.ascontiguousarray(np.asarray(geom, dtype=np.float64).T)
+        nr, nd = g.shape[1], self.nd
+        time = g[0] if nr else np.zeros(0)
+        lay = _scene_layout(self.ctl, atm, time)
+        lay.update(scene_slices(self.ctl, atm, time))
+        rp = lay["rowptr"] if rowptr is None else np.ascontiguousarray(rowptr, dtype=np.int64)
+        if rp.shape != lay["rowptr"].shape:
+            raise ValueError("rowptr holds %d entries, the call has %d rays" % (len(rp), nr))
+        yy, ww = (np.ascontiguousarray(x, dtype=np.float64) for x in (y, weight))
+        if yy.shape != (nr, nd) or ww.shape != (nr, nd):
+            raise ValueError("y and weight must be (%d, %d)" % (nr, nd))
+        rad = np.zeros((nr, nd)) if rad_in is None else np.ascontiguousarray(rad_in, dtype=np.float64).copy()
+        tau = np.zeros((nr, nd))
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        ns, n, na = len(lay["sfirst"]), int(lay["wptr"][-1]), int(lay["aptr"][-1])
+        cost, nlive = np.zeros(ns), np.zeros(ns, dtype=np.int64)
+        A, b = (np.zeros(na), np.zeros(n)) if want_normal else (None, None)
+        k = np.zeros(int(lay["rowptr"][-1]) * nd) if want_k else None
+        sin, sout, res, keep = _solve_structs(ns, n, na, lam, mode, prior_ivar, prior_dx, want_factor)
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
+        lp_ = C.POINTER(C.c_long)
+        _chk(lib().jur_step_scene_host(self.h, C.byref(atm), nr, garr, _p(rad), _p(tau), tarr,
+                                       npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(lp_), _p(yy), _p(ww),
+                                       C.byref(sin), C.byref(sout), _p(A) if want_normal else None,
+                                       _p(b) if want_normal else None, _p(cost), nlive.ctypes.data_as(lp_),
+                                       _p(k) if want_k else None, max_rays_per_pass))
+        out = dict(lay, rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, cost=cost, nlive=nlive, **res)
+        if want_normal:
+            out.update(A=A, b=b)
+        if want_k:
+            out["k"] = k
+        return out
+
+    def solve_slices(self, wptr, A, b, lam, mode=0, prior_ivar=None, prior_dx=None, want_factor=False):
+        """Batched Cholesky solve of damped, optionally regularised systems the caller holds (jur_solve_slices_host): the
+        re-solve of a Levenberg-Marquardt iteration.  wptr (nslice + 1,): running sum of the widths; A flat, A_s at the
+        running sum of the squared widths, [w][w] (diagonal and lower triangle are read); b (n,).  lam: a scalar, (nlam,)
+        or (nlam, nslice).  mode: DAMP_MARQUARDT or DAMP_PRIOR; prior_ivar, prior_dx (n,): both or neither.
+        -> dict(dx (nlam, n), pred (nlam, nslice), status (nlam, nslice)) and, with want_factor, L (nlam, A.size)."""
+        wp = np.ascontiguousarray(wptr, dtype=np.int64)
+        ns = len(wp) - 1
+        n, na = int(wp[-1]), int((np.diff(wp) ** 2).sum())
+        AA, bb = (np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (A, b))
+        if AA.size != na or bb.size != n:
+            raise ValueError("A must hold %d doubles and b %d" % (na, n))
+        sin, sout, res, keep = _solve_structs(ns, n, na, lam, mode, prior_ivar, prior_dx, want_factor)
+        _chk(lib().jur_solve_slices_host(self.h, ns, wp.ctypes.data_as(C.POINTER(C.c_long)), _p(AA), _p(bb), C.byref(sin),
+                                         C.byref(sout)))
+        return res
+
     def scene_ms(self):
         """The share of kernel_scene's own kernels in the launches timed since the last call (call kernel_ms first)."""
         ms, n = C.c_double(0), C.c_long(0)
@@ -505,8 +567,48 @@ class Model:
 
 
 ARITH_FAST, ARITH_EXACT = 0, 1
+DAMP_MARQUARDT, DAMP_PRIOR = 0, 1      # JUR_DAMP_MARQUARDT, JUR_DAMP_PRIOR
 EINVAL = -1                            # JUR_EINVAL
 ENLOS = -5                             # JUR_ENLOS
+
+
+class SolveIn(C.Structure):
+    """jur_solve_in_t"""
+    _fields_ = [("nlam", C.c_int), ("mode", C.c_int), ("lam", dp), ("prior_ivar", dp), ("prior_dx", dp)]
+
+
+class SolveOut(C.Structure):
+    """jur_solve_out_t"""
+    _fields_ = [("dx", dp), ("pred", dp), ("status", C.POINTER(C.c_int)), ("L", dp)]
+
+
+def _solve_structs(ns, n, na, lam, mode, prior_ivar, prior_dx, want_factor):
+    """(jur_solve_in_t, jur_solve_out_t, the result dict, the input arrays to keep alive) of ns systems with n elements
+    and na matrix entries in all.  Nothing is refused here that the library refuses."""
+    lm = np.asarray(lam, dtype=np.float64)
+    if lm.ndim == 0:
+        lm = lm.reshape(1, 1)
+    elif lm.ndim == 1:
+        lm = lm.reshape(-1, 1)
+    if lm.ndim != 2 or lm.shape[1] not in (1, ns):
+        raise ValueError("lam must be a scalar, (nlam,) or (nlam, %d)" % ns)
+    nlam = lm.shape[0]
+    lm = np.ascontiguousarray(np.broadcast_to(lm, (nlam, ns)))
+    pri = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (prior_ivar, prior_dx)]
+    if any(x is not None and x.size != n for x in pri):
+        raise ValueError("prior_ivar and prior_dx must hold %d doubles" % n)
+    res = dict(dx=np.zeros((nlam, n)), pred=np.zeros((nlam, ns)), status=np.zeros((nlam, ns), dtype=np.int32))
+    if want_factor:
+        res["L"] = np.zeros((nlam, na))
+    sin = SolveIn(nlam, int(mode), _p(lm), None if pri[0] is None else _p(pri[0]), None if pri[1] is None else _p(pri[1]))
+    sout = SolveOut(_p(res["dx"]), _p(res["pred"]), res["status"].ctypes.data_as(C.POINTER(C.c_int)),
+                    _p(res["L"]) if want_factor else None)
+    return sin, sout, res, (lm, pri)
+
+
+def solve_slices(model, wptr, A, b, lam, **kw):
+    """Model.solve_slices as a function"""
+    return model.solve_slices(wptr, A, b, lam, **kw)
 
 
 class GslMatrix(C.Structure):
