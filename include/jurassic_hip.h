@@ -395,6 +395,12 @@ int  jur_model_set_pencil(jur_model_t *m, long max_rays, int rays_per_group);
  * probes of a step (jr_common.h:665-681) and the emitters' columns are taken side by side; same results bit for bit
  * (tests/test_multi_gpu.py). */
 void jur_tune_trace(int lanes_per_ray);
+/* Process-wide: whether one-lane-per-ray launches of the batched ray tracer keep the profile slice of a workgroup's
+ * rays in LDS (workgroups of 256 rays; rows z, p, T, ln-p slope, q[ng], k[nw], at most 1280 doubles for the longest
+ * slice).  0 = chosen per launch (slice-sorted launches of at least 262 144 rays whose longest slice fits), 1 = never,
+ * 2 = wherever the longest slice fits.  A workgroup whose rays use two slices reads the model's arrays.  Same results
+ * bit for bit (tests/test_trace_lds_gpu.py). */
+void jur_tune_trace_slice(int mode);
 /* Process-wide tuning of the radiance-update kernel of the batched path: up to `channels_per_group` (0 .. 6, default
  * 4; 0 = one channel per workgroup always) channels of a ray block share a workgroup, with a barrier every
  * `sync_segments` segments (default 8; <= 0 none), for launches of at least `min_lanes` rays x channels (default

@@ -100,6 +100,8 @@ typedef struct {
   int const *eps_off;           /* [tiles of the chunk] first point slot of every tile in eps when the tiles are laid out
                                    by their longest path instead of JUR_NLOS points each; NULL: tile * JUR_NLOS       */
   int *status;                  /* device flag: bit0 = NLOS overflow            */
+  int slice_sorted;             /* neighbouring slots use the same atmosphere slice (one slice, or `order` groups the
+                                   rays by slice): the ray tracer may keep a workgroup's slice in LDS            */
 } jur_chunk_t;
 
 /* kernel launchers (jur_kernels.hip); return hipError_t as int */
@@ -115,6 +117,7 @@ int jurk_tile_max(int n, int const *d_np, int *d_tile_np, void *stream);
 int jurk_launch_kquot(long nq, long n, double const *d_rad, double const *d_h, double *d_kq, void *stream);   /* longest path per tile of 64 slots */
 void jurk_tune_combine(int group, int sync, long min_lanes);
 void jurk_tune_trace(int lanes);
+void jurk_tune_trace_slice(int mode);
 /* Curtis-Godson columns of the traced chunk: outputs [ray][gas][JUR_NLOS], indexed by ray id */
 int jurk_launch_cg(jur_view_t const *v, jur_chunk_t const *c, double *cgp, double *cgt, double *cgu, void *stream);
 /* bracket records of all n table entries (the last entry of a curve gets slopes nobody reads) */

@@ -187,8 +187,10 @@ __device__ __forceinline__ double exp_tab(Tab const &tab, double x) {
 struct Exp2Global { __device__ __forceinline__ double operator[](int j) const { return JUR_EXP2_64[j]; } };
 struct Exp2Lds { double const *t; __device__ __forceinline__ double operator[](int j) const { return t[j]; } };
 
-// bracket search on an ascending or descending axis (jr_common.h:87-104)
-__device__ __forceinline__ int locate_axis(double const *__restrict__ xx, int n, double x) {
+// bracket search on an ascending or descending axis (jr_common.h:87-104); P: a pointer to doubles in global memory
+// or (lds_cptr, the tracer's staged profile slice) in LDS
+template <class P>
+__device__ __forceinline__ int locate_axis(P xx, int n, double x) {
   int ilo = 0, ihi = n - 1, i = (n - 1) >> 1;
   if (xx[i] < xx[i + 1]) {
     while (ihi > ilo + 1) {
@@ -231,7 +233,8 @@ __device__ __forceinline__ double refractivity(double p, double t) { return 7.75
 
 // Same bracket as locate_axis for a sorted axis, found by walking from a guess (the previous
 // point's bracket: altitude changes by <= RAYDZ per step).  dir > 0 ascending, < 0 descending.
-__device__ __forceinline__ int locate_axis_from(double const *__restrict__ xx, int n, double x, int dir, int g) {
+template <class P>
+__device__ __forceinline__ int locate_axis_from(P xx, int n, double x, int dir, int g) {
   int i = min(max(g, 0), n - 2);
   if (dir > 0) {
     while (i > 0 && xx[i] > x) --i;
@@ -248,24 +251,56 @@ __device__ __forceinline__ int locate_axis_from(double const *__restrict__ xx, i
 // WANT_R: the caller interpolates more quantities on the same bracket; for a sorted axis (dir != 0: z strictly
 // monotone, bracket width non-zero) it gets rdz = RN(1 / (zb - za)) and every such interpolation, the
 // temperature's included, divides through it (lip_rcp: the same doubles, 3 instructions per quotient).
-template <bool WANT_R = false>
-__device__ __forceinline__ int intpol_pt(jur_view_t const &v, int i0, int n, double z0, double &p, double &t, int dir,
+//
+// Where the tracer reads the profile rows from.  AtmGlobal: the model's arrays, indexed by atmosphere point.  AtmLds:
+// the rows z, p, T, pslope, q[ng], k[nw] of ONE slice, n levels each, staged in LDS by the workgroup and indexed from
+// the slice's first level -- pointers typed as LDS, so that every read is a ds_read (counted on lgkmcnt alone: a
+// read through a generic pointer to the same bytes is a flat_load, which also waits in vmcnt behind the LOS stores).
+// origin(atm0): index of the slice's first level in the rows.
+typedef __attribute__((address_space(3))) double const *lds_cptr;
+struct AtmGlobal {
+  typedef double const *ptr;
+  jur_view_t const &v;
+  __device__ __forceinline__ ptr z() const { return v.atm_z; }
+  __device__ __forceinline__ ptr p() const { return v.atm_p; }
+  __device__ __forceinline__ ptr t() const { return v.atm_t; }
+  __device__ __forceinline__ ptr pslope() const { return v.atm_pslope; }
+  __device__ __forceinline__ ptr q(int ig) const { return v.atm_q + (size_t)ig * v.atm_np; }
+  __device__ __forceinline__ ptr k(int iw) const { return v.atm_k + (size_t)iw * v.atm_np; }
+  __device__ __forceinline__ int origin(int atm0) const { return atm0; }
+};
+struct AtmLds {
+  typedef lds_cptr ptr;
+  lds_cptr rows;
+  int n, ng;
+  __device__ __forceinline__ ptr z() const { return rows; }
+  __device__ __forceinline__ ptr p() const { return rows + n; }
+  __device__ __forceinline__ ptr t() const { return rows + 2 * n; }
+  __device__ __forceinline__ ptr pslope() const { return rows + 3 * n; }
+  __device__ __forceinline__ ptr q(int ig) const { return rows + (4 + ig) * n; }
+  __device__ __forceinline__ ptr k(int iw) const { return rows + (4 + ng + iw) * n; }
+  __device__ __forceinline__ int origin(int) const { return 0; }
+};
+
+template <bool WANT_R = false, class Atm>
+__device__ __forceinline__ int intpol_pt(Atm const &A, int i0, int n, double z0, double &p, double &t, int dir,
                                          int &hint, double *rdz = nullptr) {
-  int const loc = dir ? locate_axis_from(v.atm_z + i0, n, z0, dir, hint) : locate_axis(v.atm_z + i0, n, z0);
+  typename Atm::ptr const az = A.z(), ap = A.p(), at = A.t();
+  int const loc = dir ? locate_axis_from(az + i0, n, z0, dir, hint) : locate_axis(az + i0, n, z0);
   hint = loc;
   int const ip = i0 + loc;
-  double const za = v.atm_z[ip], zb = v.atm_z[ip + 1];
+  double const za = az[ip], zb = az[ip + 1];
   // eip (jr_common.h:53-57) with log(p1/p0)/(z1-z0) taken from the per-level array that
   // jur_pslope_kernel filled with exactly that expression; NaN marks a non-positive pressure
-  double const sl = v.atm_pslope[ip];
+  double const sl = A.pslope()[ip];
   if (WANT_R && dir) {
     double const r = 1. / (zb - za);
     *rdz = r;
-    p = (sl == sl) ? v.atm_p[ip] * exp(sl * (z0 - za)) : lip_rcp(za, v.atm_p[ip], zb, v.atm_p[ip + 1], z0, r);
-    t = lip_rcp(za, v.atm_t[ip], zb, v.atm_t[ip + 1], z0, r);
+    p = (sl == sl) ? ap[ip] * exp(sl * (z0 - za)) : lip_rcp(za, ap[ip], zb, ap[ip + 1], z0, r);
+    t = lip_rcp(za, at[ip], zb, at[ip + 1], z0, r);
   } else {
-    p = (sl == sl) ? v.atm_p[ip] * exp(sl * (z0 - za)) : lip(za, v.atm_p[ip], zb, v.atm_p[ip + 1], z0);
-    t = lip(za, v.atm_t[ip], zb, v.atm_t[ip + 1], z0);
+    p = (sl == sl) ? ap[ip] * exp(sl * (z0 - za)) : lip(za, ap[ip], zb, ap[ip + 1], z0);
+    t = lip(za, at[ip], zb, at[ip + 1], z0);
   }
   return ip;
 }
@@ -315,15 +350,15 @@ __device__ __attribute__((noinline)) ClipOut clip_exit(double px0, double px1, d
   return {xh[0] + frac * (x0 - xh[0]), xh[1] + frac * (x1 - xh[1]), xh[2] + frac * (x2 - xh[2]), frac};
 }
 
-#define TR_PZ tr_sh[0][threadIdx.x]
-#define TR_PX(i) tr_sh[1 + (i)][threadIdx.x]
-#define TR_LZ0 tr_sh[4][threadIdx.x]
-#define TR_LX0(i) tr_sh[5 + (i)][threadIdx.x]
-#define TR_LZ1 tr_sh[8][threadIdx.x]
-#define TR_LDS1 tr_sh[9][threadIdx.x]
-#define TR_LZ2 tr_sh[10][threadIdx.x]
-#define TR_LX2(i) tr_sh[11 + (i)][threadIdx.x]
-#define TR_LDS2 tr_sh[14][threadIdx.x]
+#define TR_PZ tr_sh[0][threadIdx.x & 63]
+#define TR_PX(i) tr_sh[1 + (i)][threadIdx.x & 63]
+#define TR_LZ0 tr_sh[4][threadIdx.x & 63]
+#define TR_LX0(i) tr_sh[5 + (i)][threadIdx.x & 63]
+#define TR_LZ1 tr_sh[8][threadIdx.x & 63]
+#define TR_LDS1 tr_sh[9][threadIdx.x & 63]
+#define TR_LZ2 tr_sh[10][threadIdx.x & 63]
+#define TR_LX2(i) tr_sh[11 + (i)][threadIdx.x & 63]
+#define TR_LDS2 tr_sh[14][threadIdx.x & 63]
 // value of lane K of the caller's quad (lanes 4q .. 4q+3), for all four lanes: two DPP moves
 template <int K>
 __device__ __forceinline__ double quad_bcast(double x) {
@@ -344,7 +379,9 @@ __device__ __forceinline__ double quad_bcast(double x) {
 //   L.never_enter(mask)     called once by all lanes together: the lanes whose rays never enter the atmosphere
 //   L.ray_final(n, tsurf)   called when the ray has left the atmosphere with n points, all final (not for a ray
 //                           that runs into the NLOS limit: see the returned np)
-// tr_sh: the per-lane tangent-point bookkeeping in LDS, column threadIdx.x.
+// tr_sh: the per-lane tangent-point bookkeeping of the caller's wavefront in LDS, column threadIdx.x & 63.
+// A: where the profile rows are read from in the stepping loop (AtmGlobal / AtmLds).  What a ray reads once -- the
+// slice search, the altitude range, redo_columns -- goes to the model's arrays in either case.
 // QUAD: the ray is traced by the four lanes of a quad together (fused kernel, where the tracer wavefront has lanes
 // to spare and the call's latency is the tracer's dependent instruction chain).  All four run the step
 // redundantly -- same inputs, same doubles -- except for the refractivity gradient (jr_common.h:665-681), 58 % of
@@ -356,10 +393,30 @@ struct TraceResult { int np; double tsurf, tpz, tplon, tplat; };
 // LANES = 4 is the QUAD described above, 1 a lane per ray.  (A pair of lanes per ray -- two probes each -- was built and
 // measured in round 4: bit-identical and no faster than one lane at the launch sizes it was meant for, 100 000 rays:
 // profiles/r04_size_sweep.json.)
-template <class Los, int LANES = 1>
-__device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, double const time, double const obsz, double const obslon,
-                                                 double const obslat, double const vpz, double const vplon, double const vplat,
-                                                 Los &L, double (&tr_sh)[15][64], int *status) {
+// profile slice [atm0, atm0 + atmn) that carries a ray's time stamp (jr_common.h:127-154)
+__device__ __forceinline__ void find_slice(jur_view_t const &v, double const time, int &atm0, int &atmn) {
+  int lo = 0, hi = v.atm_np - 1;
+  while (hi > lo + 1) {
+    int const i = (lo + hi) / 2;
+    if (v.atm_time[i] < time) lo = i; else hi = i;
+  }
+  int const lower = (0 == lo) ? lo : hi;
+  lo = lower;
+  hi = v.atm_np - 1;
+  while (hi > lo + 1) {
+    int const i = (lo + hi) / 2;
+    if (v.atm_time[i] > time) hi = i; else lo = i;
+  }
+  int const upper = (hi == v.atm_np - 1) ? v.atm_np : hi;
+  atm0 = lower;
+  atmn = upper - lower;
+}
+
+template <class Los, int LANES = 1, class Atm>
+__device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const &A, double const time, double const obsz,
+                                                 double const obslon, double const obslat, double const vpz,
+                                                 double const vplon, double const vplat, Los &L, double (&tr_sh)[15][64],
+                                                 int *status) {
   int const f_k = JUR_F_K, f_u = JUR_F_K + v.nw;
   double tsurf = -999;
   double tpz = vpz, tplon = vplon, tplat = vplat;
@@ -367,23 +424,8 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, double con
 
   // profile slice that carries this ray's time stamp (jr_common.h:127-154)
   int atm0, atmn;
-  {
-    int lo = 0, hi = v.atm_np - 1;
-    while (hi > lo + 1) {
-      int const i = (lo + hi) / 2;
-      if (v.atm_time[i] < time) lo = i; else hi = i;
-    }
-    int const lower = (0 == lo) ? lo : hi;
-    lo = lower;
-    hi = v.atm_np - 1;
-    while (hi > lo + 1) {
-      int const i = (lo + hi) / 2;
-      if (v.atm_time[i] > time) hi = i; else lo = i;
-    }
-    int const upper = (hi == v.atm_np - 1) ? v.atm_np : hi;
-    atm0 = lower;
-    atmn = upper - lower;
-  }
+  find_slice(v, time, atm0, atmn);
+  int const ab = A.origin(atm0);       // the slice's first level in A's rows
   // altitude range of the first column of that slice (jr_common.h:411-420)
   double zmin = v.atm_z[atm0], zmax = zmin;
   {
@@ -477,22 +519,22 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, double con
       }
 
       double p, t, rdz = 0;
-      int const ia = intpol_pt<true>(v, atm0, atmn, z, p, t, zdir, zhint, &rdz);
+      int const ia = intpol_pt<true>(A, ab, atmn, z, p, t, zdir, zhint, &rdz);
       double const dsn = (np >= 1) ? 0.5 * (ds_p + ds) : ds * 0.5;   // redone for the point before the exit
       L.put(JUR_F_DS, np, dsn);
       {  // remaining quantities on the same bracket (jr_common.h:557-567)
-        double const za = v.atm_z[ia], zb = v.atm_z[ia + 1];
+        double const za = A.z()[ia], zb = A.z()[ia + 1];
         double const kt = JUR_BOLTZMANN * t, rkt = 1. / kt;   // one division for all emitters' columns (div_rcp)
         // (LANES > 1: the lanes of the ray share the emitters' columns between them; nobody in the tracer reads them back)
         for (int ig = LANES > 1 ? (int)(threadIdx.x & (LANES - 1)) : 0; ig < v.ng; ig += LANES) {
-          double const *q = v.atm_q + (size_t)ig * v.atm_np;
+          auto const q = A.q(ig);
           double qv;
           if (zdir) qv = lip_rcp(za, q[ia], zb, q[ia + 1], z, rdz); else qv = lip(za, q[ia], zb, q[ia + 1], z);
           L.put(f_u + ig, np, div_rcp(10. * qv * p, kt, rkt) * dsn);
           if (ig == v.ig_h2o) L.put(JUR_F_QH2O, np, qv);
         }
         for (int iw = 0; iw < v.nw; iw++) {
-          double const *k = v.atm_k + (size_t)iw * v.atm_np;
+          auto const k = A.k(iw);
           if (zdir) L.put(f_k + iw, np, lip_rcp(za, k[ia], zb, k[ia + 1], z, rdz));
           else L.put(f_k + iw, np, lip(za, k[ia], zb, k[ia + 1], z));
         }
@@ -534,7 +576,7 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, double con
                                 (j == 3) ? xh[2] + h : xh[2]};
           cart2geo(xq, zz, llon, llat);
           double rdzb = 0;
-          intpol_pt<true>(v, atm0, atmn, zz, pp, tt, zdir, rhint, &rdzb);   // (lip_rcp == lip: same doubles as the plain search)
+          intpol_pt<true>(A, ab, atmn, zz, pp, tt, zdir, rhint, &rdzb);   // (lip_rcp == lip: same doubles as the plain search)
           double const nj = refractivity(pp, tt), n2 = quad_bcast<0>(nj);
           ngr[0] = div_rcp(quad_bcast<1>(nj) - n2, h, 1. / h);
           ngr[1] = div_rcp(quad_bcast<2>(nj) - n2, h, 1. / h);
@@ -542,13 +584,13 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, double con
         } else {
         cart2geo(xh, zz, llon, llat);
         double rdzb = 0;
-        int const ib = intpol_pt<true>(v, atm0, atmn, zz, pp, tt, zdir, rhint, &rdzb);
+        int const ib = intpol_pt<true>(A, ab, atmn, zz, pp, tt, zdir, rhint, &rdzb);
         double const n2 = refractivity(pp, tt);
         // the three displaced probes lie 0.02 km away: almost always in the bracket just found, whose six
         // values are then reused instead of being looked up and loaded again
-        double const za = v.atm_z[ib], zb = v.atm_z[ib + 1], pa = v.atm_p[ib], pb = v.atm_p[ib + 1],
-                     ta = v.atm_t[ib], tb = v.atm_t[ib + 1], sl = v.atm_pslope[ib];
-        bool const first = (ib == atm0), lastb = (ib == atm0 + atmn - 2);
+        double const za = A.z()[ib], zb = A.z()[ib + 1], pa = A.p()[ib], pb = A.p()[ib + 1],
+                     ta = A.t()[ib], tb = A.t()[ib + 1], sl = A.pslope()[ib];
+        bool const first = (ib == ab), lastb = (ib == ab + atmn - 2);
         for (int i = 0; i < 3; i++) {
           double const h = 0.02;
           xh[i] += h;
@@ -559,7 +601,7 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, double con
             pp = (sl == sl) ? pa * exp(sl * (zz - za)) : lip_rcp(za, pa, zb, pb, zz, rdzb);   // inside => sorted axis
             tt = lip_rcp(za, ta, zb, tb, zz, rdzb);
           } else {
-            intpol_pt(v, atm0, atmn, zz, pp, tt, zdir, rhint);
+            intpol_pt(A, ab, atmn, zz, pp, tt, zdir, rhint);
           }
           ngr[i] = div_rcp(refractivity(pp, tt) - n2, h, 1. / h);
           xh[i] -= h;
@@ -652,8 +694,8 @@ __global__ __launch_bounds__(64, 4) void jur_trace_kernel(jur_view_t v, jur_chun
   if (r >= c.n) return;
   long const ray = c.order ? (long)c.order[r] : c.first + r;
   LosWorkspace L{c.los + (size_t)(r >> 6) * los_tile_doubles(JUR_F_K + v.nw + v.ng) + (r & 63), JUR_F_K + v.nw + v.ng};
-  TraceResult const t = trace_ray(v, c.geom[0][ray], c.geom[1][ray], c.geom[2][ray], c.geom[3][ray], c.geom[4][ray],
-                                  c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
+  TraceResult const t = trace_ray(v, AtmGlobal{v}, c.geom[0][ray], c.geom[1][ray], c.geom[2][ray], c.geom[3][ray],
+                                  c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
   c.np[r] = t.np;
   c.tsurf[r] = t.tsurf;
   if (c.np_out) c.np_out[ray] = t.np;
@@ -676,7 +718,7 @@ __global__ __launch_bounds__(64, 4) void jur_trace_lanes_kernel(jur_view_t v, ju
   if (r >= c.n) return;
   long const ray = c.order ? (long)c.order[r] : c.first + r;
   LosWorkspace L{c.los + (size_t)(r >> 6) * los_tile_doubles(JUR_F_K + v.nw + v.ng) + (r & 63), JUR_F_K + v.nw + v.ng};
-  TraceResult const t = trace_ray<LosWorkspace, LANES>(v, c.geom[0][ray], c.geom[1][ray], c.geom[2][ray], c.geom[3][ray],
+  TraceResult const t = trace_ray<LosWorkspace, LANES>(v, AtmGlobal{v}, c.geom[0][ray], c.geom[1][ray], c.geom[2][ray], c.geom[3][ray],
                                                        c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
   if (threadIdx.x & (LANES - 1)) return;
   c.np[r] = t.np;
@@ -685,6 +727,74 @@ __global__ __launch_bounds__(64, 4) void jur_trace_lanes_kernel(jur_view_t v, ju
   c.tp[0][ray] = t.tpz;
   c.tp[1][ray] = t.tplon;
   c.tp[2][ray] = t.tplat;
+}
+
+// One lane per ray in workgroups of four LOS tiles, for launches that are sorted by profile slice: when all rays of
+// the workgroup use ONE slice [a0, a0 + n) and its rows fit the slab the launch has sized, the rows z, p, T, pslope,
+// q[ng], k[nw] are copied to LDS once and the stepping loop reads them there through LDS-typed pointers (AtmLds).
+// The loop's dependent gathers -- bracket walk, bracket values, the displaced probes, the emitters' columns -- then
+// neither take the trip to the L2 nor wait in vmcnt behind the point's LOS stores.  A workgroup whose rays straddle
+// two slices, or whose slice does not fit, runs the loop on the model's arrays as jur_trace_kernel does.  Same
+// values from another place, same operations: same doubles.
+// Dynamic LDS: tr_sh of the four wavefronts, then slab_doubles doubles of slab (>= 2: its head holds the four words
+// of the agreement before the rows are copied over them).
+#ifndef JUR_TRACE_SLICE_WAVES          // (other values: experiment builds, make EXTRA=-DJUR_TRACE_SLICE_WAVES=...)
+#define JUR_TRACE_SLICE_WAVES 4
+#endif
+extern __shared__ double jur_trace_lds[];
+__global__ __launch_bounds__(64 * JUR_TRACE_SLICE_WAVES, 4) void jur_trace_slice_kernel(jur_view_t v, jur_chunk_t c,
+                                                                                        int slab_doubles) {
+  double (&tr_sh)[15][64] = reinterpret_cast<double (*)[15][64]>(jur_trace_lds)[threadIdx.x >> 6];
+  double *const slab = jur_trace_lds + JUR_TRACE_SLICE_WAVES * 15 * 64;
+  int *const agree = reinterpret_cast<int *>(slab);      // min a0, max a0, min n, max n over the workgroup's rays
+  int const r = blockIdx.x * blockDim.x + threadIdx.x;   // slot in the chunk
+  bool const live = r < c.n;
+  if (threadIdx.x == 0) { agree[0] = 0x7fffffff; agree[1] = -1; agree[2] = 0x7fffffff; agree[3] = -1; }
+  __syncthreads();
+  if (live) {
+    int a, m;
+    find_slice(v, c.geom[0][c.order ? (long)c.order[r] : c.first + r], a, m);   // what trace_ray finds for this ray
+    atomicMin(&agree[0], a); atomicMax(&agree[1], a);
+    atomicMin(&agree[2], m); atomicMax(&agree[3], m);
+  }
+  __syncthreads();
+  int const a0 = __builtin_amdgcn_readfirstlane(agree[0]), n = __builtin_amdgcn_readfirstlane(agree[2]);
+  int const nrow = 4 + v.ng + v.nw;
+  bool const staged = __builtin_amdgcn_readfirstlane((a0 == agree[1]) && (n == agree[3]) && (n >= 2) &&
+                                                     ((long)n * nrow <= (long)slab_doubles));
+  __syncthreads();                        // the agreement has been read: the slab may be written
+  if (staged) {
+    for (int i = threadIdx.x; i < nrow * n; i += blockDim.x) {   // (a0 + k < a0 + n <= atm_np; i < slab_doubles)
+      int const row = i / n, k = i - row * n;
+      double const *const src = (row == 0) ? v.atm_z : (row == 1) ? v.atm_p : (row == 2) ? v.atm_t
+                              : (row == 3) ? v.atm_pslope
+                              : (row < 4 + v.ng) ? v.atm_q + (size_t)(row - 4) * v.atm_np
+                                                 : v.atm_k + (size_t)(row - 4 - v.ng) * v.atm_np;
+      slab[i] = src[a0 + k];
+    }
+    __syncthreads();                      // (uniform branch: every thread of the workgroup is here)
+  }
+  if (!live) return;
+  long const ray = c.order ? (long)c.order[r] : c.first + r;
+  LosWorkspace L{c.los + (size_t)(r >> 6) * los_tile_doubles(JUR_F_K + v.nw + v.ng) + (r & 63), JUR_F_K + v.nw + v.ng};
+  TraceResult t;
+  if (staged)
+    t = trace_ray(v, AtmLds{(lds_cptr)slab, n, v.ng}, c.geom[0][ray], c.geom[1][ray], c.geom[2][ray], c.geom[3][ray],
+                  c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
+  else
+    t = trace_ray(v, AtmGlobal{v}, c.geom[0][ray], c.geom[1][ray], c.geom[2][ray], c.geom[3][ray], c.geom[4][ray],
+                  c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
+  // (slot and ray id are formed again from the slot's 32 bits: the compiler otherwise keeps their 64-bit forms and the
+  // scaled ray id in scratch while the ray is traced, beyond the tracer's budget of 32 B)
+  int ro = r;
+  asm volatile("" : "+v"(ro));
+  c.np[ro] = t.np;
+  c.tsurf[ro] = t.tsurf;
+  long const ray_out = c.order ? (long)c.order[ro] : c.first + ro;
+  if (c.np_out) c.np_out[ray_out] = t.np;
+  c.tp[0][ray_out] = t.tpz;
+  c.tp[1][ray_out] = t.tplon;
+  c.tp[2][ray_out] = t.tplat;
 }
 
 #undef TR_PZ
@@ -1872,8 +1982,9 @@ __global__ __launch_bounds__(1024) void jur_pencil_kernel(jur_view_t v, jur_chun
     if (slot < nray) {
       long const ray = c.first + ray0 + slot;
       LosRing L{ring, &ctl, npr, tsurf, nfield, RB, slot, NC, SH, 0ull};
-      TraceResult const t = trace_ray<LosRing, QUAD ? 4 : 1>(vt, c.geom[0][ray], c.geom[1][ray], c.geom[2][ray], c.geom[3][ray],
-                                                     c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
+      TraceResult const t = trace_ray<LosRing, QUAD ? 4 : 1>(vt, AtmGlobal{vt}, c.geom[0][ray], c.geom[1][ray], c.geom[2][ray],
+                                                     c.geom[3][ray], c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh,
+                                                     c.status);
       if ((lane & ((1 << SH) - 1)) == 0) {
         if (c.np_out) c.np_out[ray] = t.np;
         c.tp[0][ray] = t.tpz;
@@ -2708,6 +2819,13 @@ extern "C" int jurk_scene_solve(jur_scene_solve_t const *a, void *stream) {
 
 static int g_trace_lanes = 0;          // 0: by launch size
 extern "C" void jurk_tune_trace(int lanes) { g_trace_lanes = (lanes == 1 || lanes == 4) ? lanes : 0; }
+static int g_trace_slice = 0;          // 0: by launch (see jurk_launch_trace), 1: never, 2: wherever the slice fits
+extern "C" void jurk_tune_trace_slice(int mode) { g_trace_slice = (mode == 1 || mode == 2) ? mode : 0; }
+// room for the slice's rows beside the four wavefronts' tangent-point columns: 4 x 7680 B + 10 240 B = 40 KiB, a
+// quarter of the CU's LDS
+#ifndef JUR_TRACE_SLAB_DOUBLES
+#define JUR_TRACE_SLAB_DOUBLES 1280
+#endif
 
 extern "C" int jurk_launch_trace(jur_view_t const *v, jur_chunk_t const *c, void *stream) {
   if (c->n <= 0) return 0;
@@ -2717,6 +2835,20 @@ extern "C" int jurk_launch_trace(jur_view_t const *v, jur_chunk_t const *c, void
   static int const env_lanes = getenv("JUR_TRACE_LANES") ? atoi(getenv("JUR_TRACE_LANES")) : 0;     // A/B switch, read once
   int const forced = g_trace_lanes ? g_trace_lanes : env_lanes;
   int const lanes = forced == 1 || forced == 4 ? forced : ((c->n <= 65536 && v->ng >= 3) ? 4 : 1);
+  // The profile slice in LDS (jur_trace_slice_kernel) where a lane traces a ray and the longest slice fits the slab: four
+  // workgroups of 4 x 7680 B of tangent-point columns + slab share the CU's 160 KiB, as the sixteen wavefronts of
+  // jur_trace_kernel do.  By itself only for launches that are sorted by slice (else most workgroups straddle two) and
+  // fill the chip's 4096 tracer wavefront slots: below that a workgroup of four tiles spreads the rays over fewer CUs.
+  static int const env_slice = getenv("JUR_TRACE_SLICE") ? atoi(getenv("JUR_TRACE_SLICE")) : 0;     // A/B switch, read once
+  int const mode = g_trace_slice ? g_trace_slice : (env_slice == 1 || env_slice == 2) ? env_slice : 0;
+  long const slab = (long)(4 + v->ng + v->nw) * v->atm_maxslice;
+  bool const fits = v->atm_maxslice >= 2 && slab <= JUR_TRACE_SLAB_DOUBLES;
+  if (lanes == 1 && fits && mode != 1 && (mode == 2 || (c->slice_sorted && c->n >= 4096 * 64))) {
+    int const wg = 64 * JUR_TRACE_SLICE_WAVES;
+    size_t const lds = 8 * (size_t)(JUR_TRACE_SLICE_WAVES * 15 * 64 + slab);
+    hipLaunchKernelGGL(jur_trace_slice_kernel, dim3((c->n + wg - 1) / wg), dim3(wg), lds, (hipStream_t)stream, *v, *c, (int)slab);
+    return (int)hipGetLastError();
+  }
   int const grid = (int)(((long)c->n * lanes + block - 1) / block);
   if (lanes == 4) hipLaunchKernelGGL(jur_trace_lanes_kernel<4>, dim3(grid), dim3(block), 0, (hipStream_t)stream, *v, *c);
   else hipLaunchKernelGGL(jur_trace_kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, *v, *c);

@@ -642,6 +642,7 @@ int jur_model_set_pencil(jur_model_t *m, long max_rays, int rays_per_group) {
 }
 
 void jur_tune_trace(int lanes_per_ray) { jurk_tune_trace(lanes_per_ray); }
+void jur_tune_trace_slice(int mode) { jurk_tune_trace_slice(mode); }
 
 void jur_tune_combine(int channels_per_group, int sync_segments, long min_lanes) {
   jurk_tune_combine(channels_per_group, sync_segments, min_lanes);
@@ -835,6 +836,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
   if (rc) return rc;
   long const R = m->use_rays;
   int const *order = NULL;
+  int slice_sorted = m->atm_slices == 1;
   if (m->sort_rays && nr > 64) {
     /* similar rays side by side: equal trip counts inside a wavefront and neighbouring
      * table/profile addresses across its lanes */
@@ -845,6 +847,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
     int const e = jurk_sort_rays(&m->view, by_profile, nr, d_geom, ldg, m->d_order, m->d_sort_tmp, m->sort_tmp_bytes, s);
     if (e) { jur_set_error("ray sort failed: %s", hipGetErrorString((hipError_t)e)); return JUR_EHIP; }
     order = m->d_order;
+    slice_sorted |= by_profile;
   }
   long const Rt = m->use_trace_rays;
   m->n_launch_ega = 0;
@@ -868,6 +871,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
     c.np_out = d_np;
     c.eps = m->d_eps;
     c.status = d_status ? d_status : m->d_status;
+    c.slice_sorted = slice_sorted;
     /* trace the whole super-chunk */
     c.n = (int)nt;
     c.first = t0;

@@ -94,6 +94,9 @@ def lib():
         L.jur_tune_combine.restype = None
         L.jur_tune_trace.argtypes = [C.c_int]
         L.jur_tune_trace.restype = None
+        if hasattr(L, "jur_tune_trace_slice"):       # (an older build selected with JURASSIC_HIP_SO for an A/B run has none)
+            L.jur_tune_trace_slice.argtypes = [C.c_int]
+            L.jur_tune_trace_slice.restype = None
         L.jur_state_size.restype = C.c_size_t
         L.jur_state_size.argtypes = [C.c_void_p, C.c_void_p]
         L.jur_measurement_size.restype = C.c_size_t
@@ -816,6 +819,11 @@ def formod_pencil(ctl, atm, obs, ir):
 def tune_trace(lanes_per_ray=0):
     """Process-wide: lanes per ray of the batched ray tracer (0: chosen per launch)."""
     lib().jur_tune_trace(lanes_per_ray)
+
+
+def tune_trace_slice(mode=0):
+    """Process-wide: profile slice of the batched ray tracer in LDS (0: chosen per launch, 1: never, 2: wherever it fits)."""
+    lib().jur_tune_trace_slice(mode)
 
 
 def tune_combine(channels_per_group=4, sync_segments=8, min_lanes=1_000_000):

@@ -25,7 +25,7 @@ agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(os.path.join(root, "*", "**", "*counter_collection.csv"), recursive=True):
     for row in csv.DictReader(open(f)):
         k = row["Kernel_Name"]
-        short = ("trace" if "jur_trace_kernel" in k else "ega" if "jur_ega_kernel" in k else
+        short = ("trace" if "jur_trace_" in k else "ega" if "jur_ega_kernel" in k else
                  "combine" if "jur_combine" in k else "pencil" if "jur_pencil_kernel" in k else None)
         if short is None:
             continue
