@@ -327,6 +327,72 @@ int  jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const
                          jur_solve_in_t const *in, jur_solve_out_t const *out,
                          double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass);
 
+/* Retrieval of a scene: iterated Levenberg-Marquardt with trial steps, slice by slice, on the device.
+ * All arrays follow the layout of jur_scene_slices of the call's rays; the entries refuse what jur_step_scene_host refuses
+ * (hydz >= 0, time stamps that are not ascending, np outside 2..JUR_NP, a rowptr that is not jur_scene_layout's).
+ *
+ * jur_trial_scene_host: the cost of every slice under ntrial candidate steps, forward only.  For trial t and slice s the
+ *   atmosphere is atm with every element e of s set to x_e + dx[t][e] (one IEEE addition), formed on the device in a copy
+ *   of the slice's points under a time stamp of its own; the rays of s are traced through it, ntrial rays per ray, and
+ *   cost[t][s] is the chain of jur_normal_scene_host's cost (acc = fma(weight * d, d, acc), d = y - F, ascending rays, then
+ *   ascending channels) over the live measurements (rad_in's NaN mask, y finite, weight > 0, a ray with a slice): bit for
+ *   bit what jur_normal_scene_host returns on the atmosphere with the step written back.  A trial radiance that is not
+ *   finite makes that one cost NaN.  prior[t][s] = sum_e r_e (xa_e - (x_e + dx[t][e]))^2 as separately rounded operations
+ *   (difference, r * d, * d, sum; ascending e), +0.0 without a prior.  No atomics: every double depends on its slice's
+ *   inputs alone, not on the other slices, ntrial or the passes (max_rays_per_pass caps the replicated rays, ntrial per
+ *   ray).  JUR_EINVAL: ntrial outside 1..64, a dx that is not finite, half a prior.  JUR_ENOMEM, before anything is
+ *   launched, when the trial copies and accumulators do not fit into half the workspace budget.  The model holds atm
+ *   afterwards.
+ * jur_retrieve_decide: the accept/reject policy of one iteration, host arithmetic, no GPU.  Per slice with
+ *   state == JUR_RET_ACTIVE: the candidates are the l with status[l][s] == 0 and a Jt[l][s] that is not NaN; best is the
+ *   one with the smallest Jt (ties: the smallest l), -1 without candidates; accept = best >= 0 && Jt[best] < J (strict).
+ *   Accepted: lam = lamt[best], and state = JUR_RET_CONVERGED if J - Jt[best] <= tol * J.  Rejected: state =
+ *   JUR_RET_STALLED if lam == lam_max on entry, otherwise lam = min(lam * fac_max, lam_max).  Other slices are left
+ *   alone, with best = accept = -1.
+ * jur_retrieve_scene_host: the loop.  Per iteration, for the slices still active: the body of jur_step_scene_host on the
+ *   current state with the dampings lamt[l][s] = min(max(lam_s * fac[l], lam_min), lam_max) and prior_dx = xa - x formed
+ *   on the device; J = cost + prior; the trial pass on the nlam steps where they lie; jur_retrieve_decide on the scalars
+ *   brought home; x += dx[best] for the accepted slices in the base rows on the device.  A slice that is no longer active
+ *   has its rays in no later pass; what is still active after max_iter becomes JUR_RET_MAXITER.  Geometry, mask, y,
+ *   weight, prior and first guess go up once; per iteration the scalars per slice and damping come home and the dampings
+ *   and choices go up (and, when slices have ended, the list of the remaining rays); x and the forward results come home
+ *   once.  atm_ret is a copy of atm0 with the retrieved elements replaced (it may be atm0 itself; written only on
+ *   success); rad, tau, tp, np_out are the doubles of jur_formod_host on atm_ret (rad in: the NaN mask), and the model
+ *   holds atm_ret.  On any error (JUR_ENLOS from a trial ray included) the model holds atm0 and atm_ret is untouched.
+ *   The slices of a scene must be disjoint in atmosphere points (JUR_EINVAL names the two that are not).
+ * The kernels' time counts into jur_model_last_scene_ms. */
+int  jur_trial_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double const *rad_in,
+                          long const *rowptr, double const *y, double const *weight,
+                          int ntrial, double const *dx,          /* [ntrial][wptr[nslice]] */
+                          double const *prior_ivar, double const *prior_xa,   /* [wptr[nslice]] each; both or neither */
+                          double *cost, double *prior,           /* [ntrial][nslice] each */
+                          long max_rays_per_pass);
+enum { JUR_RET_ACTIVE = 0, JUR_RET_CONVERGED = 1, JUR_RET_STALLED = 2, JUR_RET_MAXITER = 3 };
+int  jur_retrieve_decide(int nlam, long nslice, double tol, double lam_max, double fac_max,
+                         double const *J, double const *Jt, double const *lamt, int const *status, /* [nslice]; [nlam][nslice] x 3 */
+                         double *lam, int *state,               /* [nslice] in/out */
+                         int *best, int *accept);               /* [nslice] out; -1 for a slice that is not ACTIVE */
+typedef struct {
+  int max_iter, nlam, mode;            /* >= 1; 1..8; JUR_DAMP_* */
+  double const *fac;                   /* [nlam] each > 0 and finite, at least one > 1 */
+  double lam0, lam_min, lam_max, tol;  /* 0 < lam_min <= lam0 <= lam_max, all finite; tol >= 0 finite */
+  double const *prior_ivar, *prior_xa; /* [wptr[nslice]]; both or neither; JUR_DAMP_PRIOR needs them */
+} jur_retrieve_in_t;
+typedef struct {
+  double *x, *lam, *cost, *prior;      /* final: [wptr[nslice]], [nslice] x 3 (cost, prior: of the state x) */
+  long *nlive; int *state, *iters;     /* [nslice] */
+  /* optional history, all or none: */
+  double *h_cost, *h_prior;            /* [max_iter][nslice] at the iteration's start (a slice that has ended: its last) */
+  double *h_lam, *h_tcost, *h_tprior;  /* [max_iter][nlam][nslice]; NaN where the slice took no part */
+  int *h_status;                       /* [max_iter][nlam][nslice]; -1 where the slice took no part */
+  int *h_best, *h_accept;              /* [max_iter][nslice]; -1 where the slice took no part */
+  long *h_work;                        /* [max_iter][2] replicated rays of the Jacobian passes, of the trial passes */
+} jur_retrieve_out_t;
+int  jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, long nr, double const *const geom[7],
+                             double *rad, double *tau, double *const tp[3], int *np_out, long const *rowptr,
+                             double const *y, double const *weight, jur_retrieve_in_t const *in,
+                             jur_retrieve_out_t const *out, long max_rays_per_pass);
+
 /* Curtis-Godson means along each line of sight (reference curtis_godson(), jr_common.h:455-473, which
  * upstream compiles only with -DCURTIS_GODSON for FORMOD=1): per ray, emitter and LOS point the
  * column-weighted pressure cgp, temperature cgt and the cumulative column cgu.  Host arrays

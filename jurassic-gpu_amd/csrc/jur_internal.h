@@ -226,8 +226,73 @@ typedef struct {
   double *dx;                   /* [wptr[nslice]] g, then z, then the step, written                           */
   double *pred;                 /* [nslice] written                                                         */
   int *status;                  /* [nslice] written: 0, or 1 + the column whose pivot was not > 0            */
+  int const *state;             /* [nslice] or NULL: a system whose state is not 0 is left alone (jur_retrieve_scene_host) */
 } jur_scene_solve_t;
 int jurk_scene_solve(jur_scene_solve_t const *a, void *stream);
+
+/* Trial states of a scene (jur_trial_scene_host, jur_retrieve_scene_host): the state elements of the slices where they
+ * lie in the base rows, and ntrial candidate steps of each.  The trial atmosphere is stacked like the Jacobian's: copy 0
+ * the base, copy 1 + s * ntrial + t the points of slice s with all its elements moved by dx[t].  All arrays are device
+ * memory. */
+typedef struct {
+  long nslice;
+  int ntrial, np0;
+  long nt;                      /* points of the stacked trial atmosphere (row length of `rows`)            */
+  long const *wptr;             /* [nslice + 1] running sum of the widths                                   */
+  long const *off;              /* [1 + nslice * ntrial + 1] first stacked point of every copy              */
+  int const *sfirst;            /* [nslice] first base point of every slice                                 */
+  int const *erow, *eip;        /* [wptr[nslice]] row and base point of every state element                 */
+  int const *state;             /* [nslice] or NULL: slices whose state is not 0 take no part               */
+  int const *choice;            /* [nslice] JUR_ELEM_ACCEPT: the accepted trial, -1 for none                */
+  double *base;                 /* [nrow][np0] base rows; written by JUR_ELEM_ACCEPT only                   */
+  double const *dx;             /* [ntrial][wptr[nslice]]                                                   */
+  double *rows;                 /* [nrow][nt] stacked rows (after jurk_scene_stack); the moved values are written */
+  double const *ivar, *xa;      /* [wptr[nslice]] diagonal prior (jurk_scene_prior, JUR_ELEM_PRIOR_DX)      */
+  double *prior;                /* [ntrial][nslice] written by jurk_scene_prior ([nslice] with dx == NULL)  */
+  double *out;                  /* [wptr[nslice]] written by JUR_ELEM_PRIOR_DX (xa - x) and JUR_ELEM_STATE (x) */
+} jur_scene_trial_t;
+enum { JUR_ELEM_APPLY = 0, JUR_ELEM_PRIOR_DX = 1, JUR_ELEM_ACCEPT = 2, JUR_ELEM_STATE = 3 };
+/* one lane per state element (JUR_ELEM_APPLY: per trial and element) of the nb = wptr[nslice]: what `op` says */
+int jurk_scene_elements(jur_scene_trial_t const *a, int op, long nb, void *stream);
+/* prior[t][s] = sum_i r_i (xa_i - (x_i + dx[t][i]))^2 as a chain of separately rounded operations, ascending i; with
+ * dx == NULL the one row of the state as it stands */
+int jurk_scene_prior(jur_scene_trial_t const *a, void *stream);
+
+/* one pass of trial rays: the rays [r0, r1) of the call, each replicated ntrial times, slot (r - r0) * ntrial + t */
+typedef struct {
+  long nr, r0, r1;
+  int nd, ntrial;
+  int const *first, *len;       /* [nr] slice of every ray in the base atmosphere                          */
+  int const *tcopy0;            /* [nr] trial copy 0 of the ray's slice, 0 for a ray without state elements */
+  long const *off;              /* as jur_scene_trial_t                                                    */
+  double const *atm_time;       /* [nt] time stamps of the stacked trial atmosphere                        */
+  double above;
+  double const *in_geom;        /* [7][nr]                                                                 */
+  double const *in_rad;         /* [nr][nd] NaN mask                                                       */
+  long n;                       /* slots of the pass                                                       */
+  double *geom, *rad;           /* [7][n], [n][nd] of the pass: written, rad then by the forward model     */
+  long nslice;
+  long const *sptr;             /* [nslice + 1] as jur_scene_normal_t                                      */
+  int const *srays;
+  int const *state;             /* [nslice] or NULL                                                        */
+  double const *y, *weight;     /* [nr][nd]                                                                */
+  double *cost;                 /* [ntrial][nslice] accumulators, read and written                         */
+} jur_scene_trial_pass_t;
+int jurk_scene_trial_rays(jur_scene_trial_pass_t const *a, void *stream);   /* geometry and mask of the pass */
+int jurk_scene_trial_cost(jur_scene_trial_pass_t const *a, void *stream);   /* after the forward model on the pass */
+
+/* the rays act[0 .. n) of a call gathered into arrays of their own (jur_retrieve_scene_host: the rays of the slices
+ * that are still active) */
+typedef struct {
+  long nr, n;                   /* rays of the call, rays gathered                                          */
+  int nd;
+  int const *act;               /* [n] ascending                                                            */
+  double const *geom, *rad, *y, *weight;   /* [7][nr], [nr][nd] x 3                                          */
+  int const *first, *len, *copy0, *tcopy0; /* [nr]                                                          */
+  double *geom_c, *rad_c, *y_c, *weight_c; /* [7][n], [n][nd] x 3                                            */
+  int *first_c, *len_c, *copy0_c, *tcopy0_c;   /* [n]                                                        */
+} jur_scene_compact_t;
+int jurk_scene_compact(jur_scene_compact_t const *a, void *stream);
 
 /* host arithmetic shared by jur_model.c and jur_scene.c (not exported) */
 #define JUR_HIDDEN __attribute__((visibility("hidden")))

@@ -2609,6 +2609,7 @@ __global__ __launch_bounds__(256) void jur_scene_solve_kernel(jur_scene_solve_t 
     if (tid == 0) { a.pred[s] = 0.; a.status[s] = 0; }
     return;
   }
+  if (a.state && a.state[s] != 0) return;                   // (uniform) a slice whose retrieval has ended
   double const *const A = a.A + a.aptr[s], *const b = a.b + a.wptr[s];
   double const *const pr = a.prior_ivar ? a.prior_ivar + a.wptr[s] : nullptr;
   double const *const pd = a.prior_ivar ? a.prior_dx + a.wptr[s] : nullptr;
@@ -2771,6 +2772,123 @@ __global__ __launch_bounds__(256) void jur_scene_solve_kernel(jur_scene_solve_t 
   if (tid == 0) { a.pred[s] = red[0]; a.status[s] = 0; }
 }
 
+// ---- trial states of a scene (jur_trial_scene_host, jur_retrieve_scene_host) -----------------------------------------
+// One lane per state element e of slice s (JUR_ELEM_APPLY: per trial t and element).  The value of element e is
+// base[erow[e]][eip[e]]; its place in trial copy 1 + s * ntrial + t is the same row at off[copy] + (eip[e] - sfirst[s]).
+//   JUR_ELEM_APPLY     rows[copy of (s, t)] = x_e + dx[t][e], one IEEE addition (after jur_scene_stack_kernel has copied
+//                      the slices as they stand: stream order, no lane writes what another reads)
+//   JUR_ELEM_PRIOR_DX  out[e] = xa[e] - x_e
+//   JUR_ELEM_ACCEPT    x_e += dx[choice[s]][e] in the base rows where choice[s] >= 0
+//   JUR_ELEM_STATE     out[e] = x_e
+__global__ __launch_bounds__(256) void jur_scene_elements_kernel(jur_scene_trial_t a, int op) {
+  long const g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long const nb = a.wptr[a.nslice];
+  if (g >= (op == JUR_ELEM_APPLY ? nb * a.ntrial : nb)) return;
+  long const t = g / nb, e = g - t * nb;
+  long const s = scene_find<false>(a.wptr, 0, a.nslice, e);
+  if (a.state && a.state[s] != 0 && op != JUR_ELEM_STATE) return;
+  long const at = (long)a.erow[e] * a.np0 + a.eip[e];
+  double const x = a.base[at];
+  if (op == JUR_ELEM_APPLY) {
+    long const copy = 1 + s * a.ntrial + t;
+    a.rows[(long)a.erow[e] * a.nt + a.off[copy] + (a.eip[e] - a.sfirst[s])] = x + a.dx[g];
+  } else if (op == JUR_ELEM_PRIOR_DX) a.out[e] = a.xa[e] - x;
+  else if (op == JUR_ELEM_ACCEPT) {
+    int const c = a.choice[s];
+    if (c >= 0) a.base[at] = x + a.dx[(long)c * nb + e];
+  } else a.out[e] = x;
+}
+
+// One lane per (trial, slice): the prior term as the fixed chain d = xa - (x + dx); t = r * d; t = t * d; acc = acc + t
+// over the slice's elements ascending (this file is compiled without contraction: four roundings per element).
+__global__ __launch_bounds__(64) void jur_scene_prior_kernel(jur_scene_trial_t a) {
+  long const g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  int const nrow = a.dx ? a.ntrial : 1;
+  if (g >= a.nslice * nrow) return;
+  long const t = g / a.nslice, s = g - t * a.nslice;
+  if (a.state && a.state[s] != 0) return;
+  long const nb = a.wptr[a.nslice];
+  double acc = 0.;
+  for (long e = a.wptr[s]; e < a.wptr[s + 1]; e++) {
+    double x = a.base[(long)a.erow[e] * a.np0 + a.eip[e]];
+    if (a.dx) x = x + a.dx[t * nb + e];
+    double const d = a.xa[e] - x;
+    double term = a.ivar[e] * d;
+    term = term * d;
+    acc = acc + term;
+  }
+  a.prior[g] = acc;
+}
+
+// Replicated geometry and mask of a pass of trial rays, one lane per slot: trial t of ray r carries the time stamp of
+// copy tcopy0[r] + t; a ray without state elements is traced through the base block as jur_scene_rays_kernel's copy 0.
+__global__ __launch_bounds__(256) void jur_scene_trial_rays_kernel(jur_scene_trial_pass_t a) {
+  long const s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= a.n) return;
+  long const r = a.r0 + s / a.ntrial, t = s - (r - a.r0) * a.ntrial;
+  double time;
+  if (a.tcopy0[r] > 0) time = a.atm_time[a.off[a.tcopy0[r] + t]];
+  else time = a.len[r] >= 2 ? a.atm_time[a.first[r]] : a.above;
+  a.geom[s] = time;
+  for (int q = 1; q < 7; q++) a.geom[q * a.n + s] = a.in_geom[q * a.nr + r];
+  for (int id = 0; id < a.nd; id++) a.rad[s * a.nd + id] = a.in_rad[r * a.nd + id];
+}
+
+// One wavefront per (slice, trial): cost[t][s] continues jur_scene_normal_kernel's chain acc = fma(weight * d, d, acc),
+// d = y - F, over the slice's rays of the pass, ascending, and their channels, ascending, from the value the earlier
+// passes left.  64 measurements at a time are fetched by the lanes and chained by lane 0.  Live: the rule of
+// jur_scene_normal_kernel on the inputs; a trial radiance that is not finite makes d, and with it this cost, NaN.
+__global__ __launch_bounds__(64) void jur_scene_trial_cost_kernel(jur_scene_trial_pass_t a) {
+  __shared__ double wl[64], dl[64];
+  long const s = (long)blockIdx.x / a.ntrial, t = (long)blockIdx.x - s * a.ntrial;
+  if (a.state && a.state[s] != 0) return;                  // (uniform)
+  long const q0 = scene_lower(a.srays, a.sptr[s], a.sptr[s + 1], a.r0), q1 = scene_lower(a.srays, q0, a.sptr[s + 1], a.r1);
+  if (q1 == q0) return;                                     // (uniform: before any barrier)
+  int const lane = threadIdx.x, nd = a.nd;
+  double acc = a.cost[t * a.nslice + s];
+  long const M = (q1 - q0) * nd;
+  for (long m0 = 0; m0 < M; m0 += 64) {
+    long const mm = m0 + lane;
+    double ww = 0., d = 0.;
+    if (mm < M) {
+      long const q = mm / nd;
+      int const id = (int)(mm - q * nd);
+      long const r = a.srays[q0 + q], at = r * nd + id;
+      double const yy = a.y[at], wt = a.weight[at];
+      if (isfinite(a.in_rad[at]) && isfinite(yy) && wt > 0) {
+        double const f = a.rad[((r - a.r0) * a.ntrial + t) * nd + id];
+        ww = wt;
+        d = isfinite(f) ? yy - f : __builtin_nan("");
+      }
+    }
+    wl[lane] = ww; dl[lane] = d;
+    __syncthreads();
+    if (lane == 0)
+      for (int c = 0; c < 64; c++) {
+        double const wc = wl[c];
+        if (!(wc > 0)) continue;
+        double const dc = dl[c], wd = wc * dc;
+        acc = fma(wd, dc, acc);
+      }
+    __syncthreads();
+  }
+  if (lane == 0) a.cost[t * a.nslice + s] = acc;
+}
+
+// the rays act[i] of a call in arrays of their own, one lane per gathered ray
+__global__ __launch_bounds__(256) void jur_scene_compact_kernel(jur_scene_compact_t a) {
+  long const i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  long const r = a.act[i];
+  for (int q = 0; q < 7; q++) a.geom_c[q * a.n + i] = a.geom[q * a.nr + r];
+  for (int id = 0; id < a.nd; id++) {
+    a.rad_c[i * a.nd + id] = a.rad[r * a.nd + id];
+    a.y_c[i * a.nd + id] = a.y[r * a.nd + id];
+    a.weight_c[i * a.nd + id] = a.weight[r * a.nd + id];
+  }
+  a.first_c[i] = a.first[r]; a.len_c[i] = a.len[r]; a.copy0_c[i] = a.copy0[r]; a.tcopy0_c[i] = a.tcopy0[r];
+}
+
 }  // namespace
 
 extern "C" int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream) {
@@ -2814,6 +2932,39 @@ extern "C" int jurk_scene_normal(jur_scene_pass_t const *a, jur_scene_normal_t c
 extern "C" int jurk_scene_solve(jur_scene_solve_t const *a, void *stream) {
   if (a->nslice <= 0) return 0;
   hipLaunchKernelGGL(jur_scene_solve_kernel, dim3((unsigned)a->nslice), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+// (wptr is device memory: the host passes the number of state elements nb = wptr[nslice])
+extern "C" int jurk_scene_elements(jur_scene_trial_t const *a, int op, long nb, void *stream) {
+  long const lanes = op == JUR_ELEM_APPLY ? nb * a->ntrial : nb;
+  if (lanes <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_elements_kernel, dim3(scene_grid(lanes)), dim3(256), 0, (hipStream_t)stream, *a, op);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_prior(jur_scene_trial_t const *a, void *stream) {
+  long const lanes = a->nslice * (a->dx ? a->ntrial : 1);
+  if (lanes <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_prior_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_trial_rays(jur_scene_trial_pass_t const *a, void *stream) {
+  if (a->n <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_trial_rays_kernel, dim3(scene_grid(a->n)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_trial_cost(jur_scene_trial_pass_t const *a, void *stream) {
+  if (a->nslice <= 0 || a->r1 <= a->r0) return 0;
+  hipLaunchKernelGGL(jur_scene_trial_cost_kernel, dim3((unsigned)(a->nslice * a->ntrial)), dim3(64), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_compact(jur_scene_compact_t const *a, void *stream) {
+  if (a->n <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_compact_kernel, dim3(scene_grid(a->n)), dim3(256), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

@@ -1778,20 +1778,23 @@ static size_t solve_doubles(size_t na, size_t nb, size_t ns, size_t nlam, int pr
  * protects the copy-out of L), the copies home.  The caller waits for the stream before the host arrays go. */
 static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nslice, long na, long nb, long const *d_wptr,
                          long const *d_aptr, double const *d_A, double const *d_b, double *W, jur_solve_in_t const *in,
-                         jur_solve_out_t const *out) {
+                         jur_solve_out_t const *out, int const *d_state) {
+  /* d_state (jur_retrieve_scene_host): the prior pair is on the device already, the steps stay there, and a system
+   * whose state is not 0 is left alone */
+  int const resident = d_state != NULL;
   size_t const NA = (size_t)na, NB = (size_t)nb, NS = (size_t)nslice, NL = (size_t)in->nlam, npr = in->prior_ivar ? NB : 0;
   double *const dM = W, *const dlive = dM + NA, *const ddx = dlive + NB, *const dpred = ddx + NL * NB, *const dlam = dpred + NL * NS,
          *const dr = dlam + NL * NS, *const dd = dr + npr;
   int *const dstat = (int *)(dd + npr);
   hipError_t e = hipMemcpyAsync(dlam, in->lam, sizeof(double) * NL * NS, hipMemcpyHostToDevice, s);
-  if (npr && e == hipSuccess) e = hipMemcpyAsync(dr, in->prior_ivar, sizeof(double) * NB, hipMemcpyHostToDevice, s);
-  if (npr && e == hipSuccess) e = hipMemcpyAsync(dd, in->prior_dx, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+  if (npr && !resident && e == hipSuccess) e = hipMemcpyAsync(dr, in->prior_ivar, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+  if (npr && !resident && e == hipSuccess) e = hipMemcpyAsync(dd, in->prior_dx, sizeof(double) * NB, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
   jur_scene_solve_t q;
   memset(&q, 0, sizeof q);
   q.nslice = nslice; q.wptr = d_wptr; q.aptr = d_aptr; q.A = d_A; q.b = d_b;
   q.prior_ivar = npr ? dr : NULL; q.prior_dx = npr ? dd : NULL; q.mode = in->mode;
-  q.M = dM; q.live = dlive;
+  q.M = dM; q.live = dlive; q.state = d_state;
   for (size_t l = 0; l < NL; l++) {
     q.lam = dlam + l * NS; q.dx = ddx + l * NB; q.pred = dpred + l * NS; q.status = dstat + l * NS;
     int const ti = scene_timed_begin(m, s);
@@ -1801,22 +1804,224 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
     if (out->L && NA) e = hipMemcpyAsync(out->L + l * NA, dM, sizeof(double) * NA, hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
   }
-  if (NB) e = hipMemcpyAsync(out->dx, ddx, sizeof(double) * NL * NB, hipMemcpyDeviceToHost, s);
+  if (NB && !resident) e = hipMemcpyAsync(out->dx, ddx, sizeof(double) * NL * NB, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(out->pred, dpred, sizeof(double) * NL * NS, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(out->status, dstat, sizeof(int) * NL * NS, hipMemcpyDeviceToHost, s);
   if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
   return JUR_OK;
 }
 
+/* ---- trial states and the retrieval loop (jur_trial_scene_host, jur_retrieve_scene_host) ----------------------------- */
+/* Host image of what the trial kernels index by: two blocks, each uploaded with one copy.
+ * longs: wptr[ns + 1] | off[ncopy + 1] | sptr[ns + 1];  ints: cdesc[3 ncopy] (first | prow = -1 | pip = 0 of every copy,
+ * for jur_scene_stack_kernel) | sfirst[ns] | erow[nb] | eip[nb] | tcopy0[nr] | srays[nlist] */
+typedef struct {
+  int ntrial;
+  long nslice, nb, ncopy, nt, nr, nlist;
+  long *longs, *wptr, *off, *sptr;
+  int *ints, *cdesc, *sfirst, *erow, *eip, *tcopy0, *srays;
+  size_t nlong, nint;
+} trial_plan_t;
+
+static void trial_plan_free(trial_plan_t *p) { free(p->longs); free(p->ints); memset(p, 0, sizeof *p); }
+
+static int trial_plan_make(trial_plan_t *p, char const *who, ctl_t const *ctl, atm_t const *atm, int ntrial, long nr, long nslice,
+                           jur_scene_slice_t const *sl, int const *sid) {
+  memset(p, 0, sizeof *p);
+  size_t const NS = (size_t)nslice, NR = (size_t)nr;
+  long nb = 0, nt = atm->np;
+  for (long q = 0; q < nslice; q++) { nb += sl[q].nel; nt += (long)ntrial * sl[q].len; }
+  long const ncopy = 1 + nslice * ntrial;
+  p->ntrial = ntrial; p->nslice = nslice; p->nb = nb; p->ncopy = ncopy; p->nt = nt; p->nr = nr;
+  p->nlong = 2 * (NS + 1) + (size_t)ncopy + 1;
+  p->nint = 3 * (size_t)ncopy + NS + 2 * (size_t)nb + 2 * NR;
+  p->longs = (long *)calloc(p->nlong, sizeof(long));
+  p->ints = (int *)calloc(p->nint ? p->nint : 1, sizeof(int));
+  int *scratch = (int *)malloc(sizeof(int) * 2 * (size_t)(nb ? nb : 1));
+  if (!p->longs || !p->ints || !scratch) { free(scratch); trial_plan_free(p); return JUR_ENOMEM; }
+  p->wptr = p->longs; p->off = p->wptr + NS + 1; p->sptr = p->off + ncopy + 1;
+  p->cdesc = p->ints; p->sfirst = p->cdesc + 3 * ncopy; p->erow = p->sfirst + NS; p->eip = p->erow + nb;
+  p->tcopy0 = p->eip + nb; p->srays = p->tcopy0 + NR;
+  int *const cfirst = p->cdesc, *const prow = p->cdesc + ncopy;
+  cfirst[0] = 0; prow[0] = -1;
+  p->off[0] = 0; p->off[1] = atm->np;
+  int rc = JUR_OK;
+  for (long q = 0; q < nslice && !rc; q++) {
+    p->wptr[q + 1] = p->wptr[q] + sl[q].nel;
+    p->sfirst[q] = sl[q].first;
+    long const n = jur_scene_slice_elements(ctl, atm, sl[q].first, sl[q].len, NULL, scratch, scratch + nb);
+    if (n != sl[q].nel) { jur_set_error("%s: layout out of step", who); rc = JUR_EINVAL; break; }
+    for (long e = 0; e < n; e++) {
+      int const iq = scratch[e];
+      p->erow[p->wptr[q] + e] = (iq == 0) ? 4 : (iq == 1) ? 5 : 4 + iq;   /* q rows start at 6, k rows follow */
+      p->eip[p->wptr[q] + e] = scratch[nb + e];
+    }
+    for (int t = 0; t < ntrial; t++) {
+      long const j = 1 + q * ntrial + t;
+      cfirst[j] = sl[q].first; prow[j] = -1;
+      p->off[j + 1] = p->off[j] + sl[q].len;
+    }
+  }
+  free(scratch);
+  if (rc) { trial_plan_free(p); return rc; }
+  for (long r = 0; r < nr; r++) {
+    p->tcopy0[r] = sid[r] >= 0 ? (int)(1 + (long)sid[r] * ntrial) : 0;
+    if (sid[r] >= 0) p->sptr[sid[r] + 1]++;
+  }
+  for (long q = 0; q < nslice; q++) p->sptr[q + 1] += p->sptr[q];
+  for (long r = 0; r < nr; r++) if (sid[r] >= 0) p->srays[p->sptr[sid[r]]++] = (int)r;
+  for (long q = nslice; q > 0; q--) p->sptr[q] = p->sptr[q - 1];
+  p->sptr[0] = 0;
+  p->nlist = p->sptr[nslice];
+  return JUR_OK;
+}
+
+/* contiguous ranges of rays whose ntrial slots each stay within cap; one ray beyond it goes alone.  Returns the number
+ * of passes, *nmax the slots of the largest; pass has room for nr + 1 entries. */
+static long trial_passes(long nr, int ntrial, long cap, long *pass, long *nmax) {
+  long per = cap / ntrial, npass = 0;
+  if (per < 1) per = 1;
+  if (per > 0x7fffffffL / ntrial) per = 0x7fffffffL / ntrial;
+  for (long r0 = 0; r0 < nr; r0 += per) {
+    long const r1 = r0 + per < nr ? r0 + per : nr;
+    if ((r1 - r0) * ntrial > *nmax) *nmax = (r1 - r0) * ntrial;
+    pass[npass++] = r0;
+  }
+  pass[npass] = nr;
+  return npass;
+}
+
+/* One trial pass over the device: stacks the trial copies from the base rows (st->base), moves the elements by st->dx,
+ * forms the prior terms (or zeroes them), traces the rays of every pass and continues the cost chains.  ps carries the
+ * ray arrays of the call (or of its gathered rays); its r0, r1, n, geom, rad, atm_time and `above` are set here.  The
+ * model's view is left on the trial atmosphere.  Nothing is waited for after the stacking. */
+static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, jur_scene_stack_t *sk, jur_scene_trial_t *st,
+                     jur_scene_trial_pass_t *ps, long nb, long npass, long const *pass, long nmax) {
+  size_t const nrow = (size_t)sk->nrow;
+  int const nd = ps->nd;
+  int rc;
+  m->h_atm_n = 0;
+  if ((rc = install_stacked_rows(m, atm, sk->nt, sk->ncopy - 1))) return rc;
+  sk->rows = (double *)m->d_atm; st->rows = (double *)m->d_atm;
+  int ti = scene_timed_begin(m, s);
+  int ek = jurk_scene_stack(sk, s);
+  if (!ek) ek = jurk_scene_elements(st, JUR_ELEM_APPLY, nb, s);
+  hipError_t e = hipMemsetAsync(ps->cost, 0, sizeof(double) * (size_t)ps->nslice * (size_t)ps->ntrial, s);
+  if (!ek && e == hipSuccess) {
+    if (st->ivar) ek = jurk_scene_prior(st, s);
+    else e = hipMemsetAsync(st->prior, 0, sizeof(double) * (size_t)ps->nslice * (size_t)ps->ntrial, s);
+  }
+  scene_timed_end(m, ti, s);
+  if (!ek) ek = jurk_prepare_atm(&m->view, (double *)m->d_atm + nrow * (size_t)sk->nt, s);
+  if (ek || e != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    (void)hipGetLastError(); m->view.atm_np = 0; jur_set_error("%s: stacking the trial atmosphere failed", who); return JUR_EHIP;
+  }
+  if ((rc = jur_model_reserve(m, nmax))) return rc;
+  ps->atm_time = m->view.atm_time;
+  ps->above = sk->tmax + ((double)sk->ncopy + 1.0) * sk->span;
+  for (long p = 0; p < npass; p++) {
+    long const n = (pass[p + 1] - pass[p]) * ps->ntrial;
+    size_t const N = (size_t)n;
+    ps->r0 = pass[p]; ps->r1 = pass[p + 1]; ps->n = n;
+    ps->geom = m->d_io; ps->rad = ps->geom + 7 * N;
+    double *const tau = ps->rad + N * nd, *const tp = tau + N * nd;
+    ti = scene_timed_begin(m, s);
+    ek = jurk_scene_trial_rays(ps, s);
+    scene_timed_end(m, ti, s);
+    if (ek) { jur_set_error("%s: trial replication kernel launch failed", who); return JUR_EHIP; }
+    if ((rc = jur_formod_device(m, n, ps->geom, ps->rad, tau, tp, m->d_io_np, m->d_status, s))) return rc;
+    ti = scene_timed_begin(m, s);
+    ek = jurk_scene_trial_cost(ps, s);
+    scene_timed_end(m, ti, s);
+    if (ek) { jur_set_error("%s: trial cost kernel launch failed", who); return JUR_EHIP; }
+  }
+  return JUR_OK;
+}
+
+/* the refusals of jur_retrieve_scene_host that need no sizes */
+static int retrieve_check_args(char const *who, jur_retrieve_in_t const *in, jur_retrieve_out_t const *out) {
+  if (!in || !out) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if (in->max_iter < 1) { jur_set_error("%s: max_iter = %d: at least one iteration is needed", who, in->max_iter); return JUR_EINVAL; }
+  if (in->nlam < 1 || in->nlam > 8) { jur_set_error("%s: nlam = %d: 1 to 8 dampings per iteration", who, in->nlam); return JUR_EINVAL; }
+  if (in->mode != JUR_DAMP_MARQUARDT && in->mode != JUR_DAMP_PRIOR) { jur_set_error("%s: unknown mode %d", who, in->mode); return JUR_EINVAL; }
+  if (!in->fac) { jur_set_error("%s: null argument (fac)", who); return JUR_EINVAL; }
+  int above_one = 0;
+  for (int l = 0; l < in->nlam; l++) {
+    if (!(in->fac[l] > 0) || isinf(in->fac[l])) { jur_set_error("%s: fac[%d] is %g: not positive or not finite", who, l, in->fac[l]); return JUR_EINVAL; }
+    if (in->fac[l] > 1) above_one = 1;
+  }
+  if (!above_one) { jur_set_error("%s: no fac above 1: a rejected damping could never grow", who); return JUR_EINVAL; }
+  if (!(in->lam_min > 0) || !(in->lam_min <= in->lam0) || !(in->lam0 <= in->lam_max) || isinf(in->lam_max)) {
+    jur_set_error("%s: lam_min = %g, lam0 = %g, lam_max = %g: need 0 < lam_min <= lam0 <= lam_max, all finite", who, in->lam_min,
+                  in->lam0, in->lam_max);
+    return JUR_EINVAL;
+  }
+  if (!(in->tol >= 0) || isinf(in->tol)) { jur_set_error("%s: tol is %g: negative or not finite", who, in->tol); return JUR_EINVAL; }
+  if (!in->prior_ivar != !in->prior_xa) {
+    jur_set_error("%s: %s without %s: the prior is given as a pair", who, in->prior_ivar ? "prior_ivar" : "prior_xa",
+                  in->prior_ivar ? "prior_xa" : "prior_ivar");
+    return JUR_EINVAL;
+  }
+  if (in->mode == JUR_DAMP_PRIOR && !in->prior_ivar) { jur_set_error("%s: JUR_DAMP_PRIOR without a prior", who); return JUR_EINVAL; }
+  if (!out->x || !out->lam || !out->cost || !out->prior || !out->nlive || !out->state || !out->iters) {
+    jur_set_error("%s: null argument (%s)", who, !out->x ? "x" : !out->lam ? "lam" : !out->cost ? "cost" : !out->prior ? "prior" :
+                  !out->nlive ? "nlive" : !out->state ? "state" : "iters");
+    return JUR_EINVAL;
+  }
+  int const nh = !!out->h_cost + !!out->h_prior + !!out->h_lam + !!out->h_tcost + !!out->h_tprior + !!out->h_status + !!out->h_best +
+                 !!out->h_accept + !!out->h_work;
+  if (nh != 0 && nh != 9) { jur_set_error("%s: %d of the 9 history arrays are given: all or none", who, nh); return JUR_EINVAL; }
+  return JUR_OK;
+}
+
+/* a diagonal prior laid out by wptr: r >= 0 and finite, xa finite */
+static int prior_check_values(char const *who, long nslice, long const *wptr, double const *ivar, double const *xa) {
+  for (long q = 0; q < nslice; q++)
+    for (long e = wptr[q]; e < wptr[q + 1]; e++) {
+      if (!(ivar[e] >= 0) || isinf(ivar[e])) {
+        jur_set_error("%s: prior_ivar of slice %ld, element %ld is %g: negative or not finite", who, q, e - wptr[q], ivar[e]);
+        return JUR_EINVAL;
+      }
+      if (!isfinite(xa[e])) {
+        jur_set_error("%s: prior_xa of slice %ld, element %ld is %g: not finite", who, q, e - wptr[q], xa[e]);
+        return JUR_EINVAL;
+      }
+    }
+  return JUR_OK;
+}
+
+/* Passes of the Jacobian entries: contiguous ranges of the nr rays with row pointer rp whose slots (width + 1 each) stay
+ * within cap; one ray beyond it goes alone.  pass has room for nr + 1 entries; *nmax and *kmax grow to the slots and the
+ * block columns of the largest pass.  Returns the number of passes, -1 for a pass of 2^31 slots. */
+static long scene_passes(long nr, long const *rp, long cap, long *pass, long *nmax, long *kmax) {
+  long npass = 0;
+  for (long r0 = 0; r0 < nr;) {
+    long r1 = r0 + 1;
+    while (r1 < nr && (rp[r1 + 1] - rp[r0]) + (r1 + 1 - r0) <= cap) r1++;
+    long const n = (rp[r1] - rp[r0]) + (r1 - r0);
+    if (n > 0x7fffffffL) return -1;
+    if (n > *nmax) *nmax = n;
+    if (rp[r1] - rp[r0] > *kmax) *kmax = rp[r1] - rp[r0];
+    pass[npass++] = r0;
+    r0 = r1;
+  }
+  pass[npass] = nr;
+  return npass;
+}
+
+/* what jur_retrieve_scene_host adds to jur_step_scene_host */
+typedef struct { jur_retrieve_in_t const *in; jur_retrieve_out_t const *out; atm_t *atm_ret; } scene_retrieve_t;
+
 /* nm == NULL: jur_kernel_scene_host.  Otherwise the normal equations of the slices are accumulated on the device after
  * the quotients of every pass, and the blocks go home only where k is given.  With sv (jur_step_scene_host; nm is given
  * then) the systems are solved where they lie after the last pass, and A and b go home only where they are given. */
 static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                              double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
-                             scene_normal_t const *nm, scene_solve_t const *sv) {
-  char const *const who = sv ? "jur_step_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+                             scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt) {
+  char const *const who = rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
+  if (rt) { int const rs = retrieve_check_args(who, rt->in, rt->out); if (rs) return rs; }
   ctl_t const *ctl = m->ctl;
   if (ctl->hydz >= 0) {
     jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so every p, T or H2O element moves "
@@ -1843,7 +2048,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   jur_scene_slice_t *sl = NULL;
   long *off = NULL, *pass = NULL, *scopy = NULL, *nptr = NULL;
   int *cdesc = NULL, *iqa = NULL, *ipa = NULL;
-  double *hbase = NULL;
+  double *hbase = NULL, *rd = NULL;
+  int *ri = NULL, *hact = NULL;
+  long *hcomp = NULL;
+  atm_t *ret_atm = NULL;
+  trial_plan_t pl;
+  memset(&pl, 0, sizeof pl);
   if (!first || !rp || !sid) { rc = JUR_ENOMEM; goto done; }
   if ((rc = jur_scene_layout(ctl, atm, nr, geom[0], first, len, rp))) goto done;
   if (memcmp(rp, rowptr, sizeof(long) * (NR + 1))) {
@@ -1870,6 +2080,27 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   long const nslice = jur_scene_distinct(np0, nr, first, len, rp, sid, &sl);
   long ncopies = 0, nt = np0;
   if (nslice < 0) { rc = JUR_ENOMEM; goto done; }
+  /* the retrieval loop is the step entry driven from here: its dampings, costs, predictions and statuses are host
+   * arrays of this call (rd: lamt | pred | tcost | tprior | Jt [nlam][ns] each, cost | prior | J [ns] each; ri: status
+   * [nlam][ns], best | accept | choice | active-before [ns] each) */
+  scene_normal_t nm_rt;
+  scene_solve_t sv_rt;
+  jur_solve_in_t sin_rt;
+  jur_solve_out_t sout_rt;
+  size_t const RL = rt ? (size_t)rt->in->nlam : 0, RS = (size_t)nslice;
+  if (rt) {
+    rd = (double *)calloc(5 * RL * RS + 3 * RS + 1, sizeof(double));
+    ri = (int *)calloc(RL * RS + 4 * RS + 1, sizeof(int));
+    if (!rd || !ri) { rc = JUR_ENOMEM; goto done; }
+    memset(&sin_rt, 0, sizeof sin_rt); memset(&sout_rt, 0, sizeof sout_rt);
+    sin_rt.nlam = rt->in->nlam; sin_rt.mode = rt->in->mode; sin_rt.lam = rd;
+    sin_rt.prior_ivar = rt->in->prior_ivar; sin_rt.prior_dx = rt->in->prior_xa;   /* (prior_dx is formed on the device) */
+    sout_rt.pred = rd + RL * RS; sout_rt.status = ri;
+    nm_rt = *nm;                                    /* (y and weight: the entry passes them this way) */
+    nm_rt.cost = rd + 5 * RL * RS; nm_rt.nlive = rt->out->nlive;
+    sv_rt.in = &sin_rt; sv_rt.out = &sout_rt;
+    nm = &nm_rt; sv = &sv_rt;
+  }
   scopy = (long *)malloc(sizeof(long) * ((size_t)nslice + 1));
   if (!scopy) { rc = JUR_ENOMEM; goto done; }
   for (long q = 0; q < nslice; q++) {
@@ -1902,7 +2133,27 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     sptr[0] = 0;
     nlist = sptr[nslice]; ntiles = tptr[nslice]; na = aptr[nslice]; nb = wptr[nslice];
     if (ntiles > 0x7fffffffL) { jur_set_error("%s: 2^31 tiles: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
-    if (sv && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
+    if (sv && !rt && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
+    if (rt) {
+      if (rt->in->prior_ivar && (rc = prior_check_values(who, nslice, wptr, rt->in->prior_ivar, rt->in->prior_xa))) goto done;
+      /* one atmosphere is the state of all slices only where no point lies in two of them */
+      int *owner = (int *)malloc(sizeof(int) * (size_t)np0);
+      if (!owner) { rc = JUR_ENOMEM; goto done; }
+      for (int i = 0; i < np0; i++) owner[i] = -1;
+      for (long q = 0; q < nslice && !rc; q++)
+        for (int i = sl[q].first; i < sl[q].first + sl[q].len; i++) {
+          if (owner[i] >= 0) {
+            jur_set_error("%s: point %d of the atmosphere lies in the slices %d and %ld: their retrievals are not independent", who,
+                          i, owner[i], q);
+            rc = JUR_EINVAL;
+            break;
+          }
+          owner[i] = (int)q;
+        }
+      free(owner);
+      if (rc) goto done;
+      if ((rc = trial_plan_make(&pl, who, ctl, atm, rt->in->nlam, nr, nslice, sl, sid))) goto done;
+    }
   }
   /* what the sums add to the slab: the accumulators A | b | cost | nlive, y and weight, the four running sums, the ray lists */
   size_t const nacc = (size_t)na + (size_t)nb + 2 * (size_t)(ntiles ? nslice : 0);
@@ -1931,6 +2182,24 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     goto done;
   }
 
+  /* ... and the retrieval loop: the trial copies (counted beside the stacked rows, whose memory they share in turn), the
+   * trial costs and priors, the prior term and the state, the arrays of the rays that remain once slices have ended
+   * (geometry, mask, y, weight; rowptr and sptr of their own), the plan's index arrays */
+  int const looping = rt && ntiles;
+  size_t const NRD = NR * (size_t)nd;
+  size_t const rt_dbl = looping ? 2 * RL * RS + RS + 2 * (size_t)nb + 7 * NR + 3 * NRD : 0;
+  size_t const rt_lng = looping ? pl.nlong + (NR + 1) + (RS + 1) : 0;
+  size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist : 0;
+  size_t const rt_atm_bytes = looping ? sizeof(double) * (nrow + 1) * (size_t)pl.nt : 0;
+  size_t const rt_bytes = sizeof(double) * (rt_dbl + rt_lng) + sizeof(int) * rt_int;
+  if (looping && (double)atm_bytes + (double)acc_bytes + (double)sv_bytes + (double)rt_atm_bytes + (double)rt_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("%s: the trial copies (%ld points, %zu bytes) and the loop's arrays (%zu bytes) do not fit beside the solver "
+                  "scratch, the normal matrices and the stacked atmosphere (%zu bytes) in the workspace budget: call with the rays "
+                  "of fewer slices at a time", who, pl.nt, rt_atm_bytes, rt_bytes, atm_bytes + acc_bytes + sv_bytes);
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+
   /* passes: contiguous ranges of rays whose slots (width + 1 each) stay within the cap; one ray beyond it goes alone */
   size_t const slot_bytes = sizeof(double) * (10 + 3 * (size_t)nd) + sizeof(int);
   long cap = max_rays_per_pass;
@@ -1944,20 +2213,16 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   }
   if (cap > 0x7fffffffL) cap = 0x7fffffffL;
   long npass = 0, nmax = 0, kmax = 0;
-  pass = (long *)malloc(sizeof(long) * (NR + 1));
+  pass = (long *)malloc(sizeof(long) * 2 * (NR + 1));       /* (second half: the trial passes of the retrieval loop) */
   if (!pass) { rc = JUR_ENOMEM; goto done; }
-  for (long r0 = 0; r0 < nr;) {
-    long r1 = r0 + 1;
-    while (r1 < nr && (rp[r1 + 1] - rp[r0]) + (r1 + 1 - r0) <= cap) r1++;
-    long const n = (rp[r1] - rp[r0]) + (r1 - r0);
-    if (n > 0x7fffffffL) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
-    if (n > nmax) nmax = n;
-    if (rp[r1] - rp[r0] > kmax) kmax = rp[r1] - rp[r0];
-    pass[npass++] = r0;
-    r0 = r1;
-  }
-  pass[npass] = nr;
+  if ((npass = scene_passes(nr, rp, cap, pass, &nmax, &kmax)) < 0) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
   kmax *= nd;
+  long *const tpass = pass + NR + 1;
+  long ntpass = 0, ntmax = 0;
+  if (looping) {
+    ntpass = trial_passes(nr, rt->in->nlam, cap, tpass, &ntmax);
+    if (ntmax > nmax) nmax = ntmax;                  /* (the arrays of a pass serve both kinds) */
+  }
 
   /* descriptors of the copies (copy 0: the base) and the base rows */
   off = (long *)malloc(sizeof(long) * ((size_t)ncopy + 1));
@@ -1995,8 +2260,9 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   /* (the normal equations' part, empty without them: y, weight, the accumulators A | b | cost | nlive in one piece,
    * then sptr | tptr | wptr | aptr, then what the solve needs) */
   size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
-               o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_int = o_sv + nsv;
-  size_t const nint = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, bytes = sizeof(double) * o_int + sizeof(int) * nint;
+               o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_rt = o_sv + nsv, o_int = o_rt + rt_dbl + rt_lng;
+  size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int;   /* (the loop's ints follow the others) */
+  size_t const bytes = sizeof(double) * o_int + sizeof(int) * nint;
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
   hipStream_t const s = m->stream;
   if ((rc = wait_done(m, s))) goto done;
@@ -2032,29 +2298,16 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     }
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
 
-    m->h_atm_n = 0;                              /* the device no longer holds the caller's atmosphere */
-    if ((rc = install_stacked_rows(m, atm, nt, ncopies))) goto done;
     jur_scene_stack_t st;
     memset(&st, 0, sizeof st);
     st.ncopy = (int)ncopy; st.np0 = np0; st.nrow = (int)nrow; st.ng = ng; st.nt = nt;
     st.off = L + o_off; st.first = d_cdesc; st.prow = d_cdesc + ncopy; st.pip = d_cdesc + 2 * ncopy;
-    st.base = D + o_base; st.rows = (double *)m->d_atm; st.h = D + o_h;
+    st.base = D + o_base; st.h = D + o_h;
     st.tmax = tmax; st.span = span;
-    int ti = scene_timed_begin(m, s);
-    int ek = jurk_scene_stack(&st, s);
-    scene_timed_end(m, ti, s);
-    if (!ek) ek = jurk_prepare_atm(&m->view, (double *)m->d_atm + nrow * (size_t)nt, s);
-    /* the one wait before the passes: the uploads have left the host arrays, the stacked rows stand */
-    if (ek || hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipGetLastError(); m->view.atm_np = 0; jur_set_error("%s: stacking the atmosphere failed", who); rc = JUR_EHIP; goto done;
-    }
-    if ((rc = jur_model_reserve(m, nmax))) goto done;   /* the forward model's workspace for the largest pass, before the first */
-
     jur_scene_pass_t a;
     memset(&a, 0, sizeof a);
     a.nr = nr; a.nd = nd;
     a.rowptr = L + o_rowptr; a.first = d_first; a.len = d_len; a.copy0 = d_copy0; a.off = L + o_off;
-    a.atm_time = m->view.atm_time;
     a.above = tmax + ((double)ncopy + 1.0) * span;
     a.in_geom = D + o_geom; a.in_rad = D + o_inrad;
     a.h = D + o_h; a.k = D + o_k;
@@ -2068,6 +2321,151 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       nq.y = D + o_y; nq.weight = D + o_w;
       nq.A = D + o_acc; nq.b = nq.A + na; nq.cost = nq.b + nb; nq.nlive = (long *)(nq.cost + nslice);
     }
+
+    /* the retrieval loop: what it adds on the device (uploaded once) and on the host */
+    jur_retrieve_in_t const *const rin = rt ? rt->in : NULL;
+    jur_retrieve_out_t const *const ro = rt ? rt->out : NULL;
+    double *const d_tcost = D + o_rt, *const d_tprior = d_tcost + RL * RS, *const d_prior0 = d_tprior + RL * RS, *const d_xout = d_prior0 + RS,
+           *const d_xa = d_xout + nb, *const d_geomc = d_xa + nb, *const d_radc = d_geomc + 7 * NR, *const d_yc = d_radc + NRD,
+           *const d_wc = d_yc + NRD;
+    long *const Lr = (long *)(D + o_rt + rt_dbl), *const d_rpc = Lr + pl.nlong, *const d_sptrc = d_rpc + NR + 1;
+    int *const Ir = I + nint0, *const d_state = Ir + pl.nint, *const d_choice = d_state + RS, *const d_act = d_choice + RS,
+        *const d_firstc = d_act + NR, *const d_lenc = d_firstc + NR, *const d_copy0c = d_lenc + NR, *const d_tcopy0c = d_copy0c + NR,
+        *const d_sraysc = d_tcopy0c + NR;
+    size_t const npr = (looping && rin->prior_ivar) ? (size_t)nb : 0;
+    /* (the solver's part of the slab, as solve_enqueue lays it out) */
+    double *const sv_dx = D + o_sv + (size_t)na + (size_t)nb, *const sv_r = sv_dx + RL * (size_t)nb + 2 * RL * RS, *const sv_d = sv_r + npr;
+    double *const lamt = rd, *const htcost = rd ? rd + 2 * RL * RS : NULL, *const htprior = rd ? rd + 3 * RL * RS : NULL,
+           *const Jt = rd ? rd + 4 * RL * RS : NULL, *const hcost = rd ? rd + 5 * RL * RS : NULL, *const hprior0 = hcost ? hcost + RS : NULL,
+           *const J = hprior0 ? hprior0 + RS : NULL;
+    int *const hstatus = ri, *const best = ri ? ri + RL * RS : NULL, *const accept = best ? best + RS : NULL, *const choice = accept ? accept + RS : NULL;
+    jur_scene_stack_t tsk;
+    jur_scene_trial_t tst;
+    jur_scene_trial_pass_t tps;
+    memset(&tsk, 0, sizeof tsk); memset(&tst, 0, sizeof tst); memset(&tps, 0, sizeof tps);
+    long *hrpc = NULL, *hsptrc = NULL, *hnlive = NULL;
+    long const *rp_cur = rp;
+    long nr_cur = nr, nactive_built = (nlist == nr) ? nslice : -1;   /* (rays without state elements are in no pass of the loop) */
+    double fac_max = 0;
+    if (rt && !looping) {                         /* no state elements: nothing to retrieve */
+      for (int it = 0; ro->h_work && it < rin->max_iter; it++) ro->h_work[2 * it] = ro->h_work[2 * it + 1] = 0;
+    }
+    if (looping) {
+      hcomp = (long *)malloc(sizeof(long) * ((NR + 1) + (RS + 1) + RS));
+      hact = (int *)malloc(sizeof(int) * (2 * NR + (size_t)nlist + 1));
+      if (!hcomp || !hact) { rc = JUR_ENOMEM; goto done; }
+      hrpc = hcomp; hsptrc = hrpc + NR + 1; hnlive = hsptrc + RS + 1;
+      e = hipMemcpyAsync(Lr, pl.longs, sizeof(long) * pl.nlong, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(Ir, pl.ints, sizeof(int) * pl.nint, hipMemcpyHostToDevice, s);
+      if (npr && e == hipSuccess) e = hipMemcpyAsync(sv_r, rin->prior_ivar, sizeof(double) * npr, hipMemcpyHostToDevice, s);
+      if (npr && e == hipSuccess) e = hipMemcpyAsync(d_xa, rin->prior_xa, sizeof(double) * npr, hipMemcpyHostToDevice, s);
+      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+      long const *const t_off = Lr + (pl.off - pl.longs);
+      tsk.ncopy = (int)pl.ncopy; tsk.np0 = np0; tsk.nrow = (int)nrow; tsk.ng = ng; tsk.nt = pl.nt;
+      tsk.off = t_off; tsk.first = Ir; tsk.prow = Ir + pl.ncopy; tsk.pip = Ir + 2 * pl.ncopy;
+      tsk.base = D + o_base; tsk.tmax = tmax; tsk.span = span;
+      tst.nslice = nslice; tst.ntrial = rin->nlam; tst.np0 = np0; tst.nt = pl.nt;
+      tst.wptr = Lr; tst.off = t_off; tst.sfirst = Ir + (pl.sfirst - pl.ints); tst.erow = Ir + (pl.erow - pl.ints);
+      tst.eip = Ir + (pl.eip - pl.ints); tst.state = d_state; tst.choice = d_choice;
+      tst.base = D + o_base; tst.dx = sv_dx; tst.ivar = npr ? sv_r : NULL; tst.xa = npr ? d_xa : NULL; tst.prior = d_tprior;
+      tps.nr = nr; tps.nd = nd; tps.ntrial = rin->nlam; tps.first = d_first; tps.len = d_len; tps.tcopy0 = Ir + (pl.tcopy0 - pl.ints);
+      tps.off = t_off; tps.in_geom = D + o_geom; tps.in_rad = D + o_inrad; tps.nslice = nslice; tps.sptr = Lr + (pl.sptr - pl.longs);
+      tps.srays = Ir + (pl.srays - pl.ints); tps.state = d_state; tps.y = D + o_y; tps.weight = D + o_w; tps.cost = d_tcost;
+      for (int l = 0; l < rin->nlam; l++) fac_max = fmax(fac_max, rin->fac[l]);
+      for (long q = 0; q < nslice; q++) { ro->lam[q] = rin->lam0; ro->state[q] = JUR_RET_ACTIVE; ro->iters[q] = 0; ro->cost[q] = ro->prior[q] = 0; ro->nlive[q] = 0; }
+      if (ro->h_cost) {
+        size_t const MI = (size_t)rin->max_iter;
+        for (size_t i = 0; i < MI * RL * RS; i++) { ro->h_lam[i] = ro->h_tcost[i] = ro->h_tprior[i] = NAN; ro->h_status[i] = -1; }
+        for (size_t i = 0; i < MI * RS; i++) ro->h_best[i] = ro->h_accept[i] = -1;
+        for (size_t i = 0; i < 2 * MI; i++) ro->h_work[i] = 0;
+      }
+    }
+    int ti, ek;
+    int const niter = rt ? (looping ? rin->max_iter : 0) : 1;
+    for (int it = 0; it < niter; it++) {
+    if (looping) {
+      /* the rays of the slices that are still active, in arrays of their own once a slice has ended */
+      long nactive = 0;
+      for (long q = 0; q < nslice; q++) nactive += ro->state[q] == JUR_RET_ACTIVE;
+      if (nactive == 0) break;
+      if (nactive != nactive_built) {
+        int *const act = hact, *const pos = hact + NR, *const sraysc = pos + NR;
+        long n = 0;
+        hrpc[0] = 0;
+        for (long r = 0; r < nr; r++) {
+          pos[r] = -1;
+          if (sid[r] < 0 || ro->state[sid[r]] != JUR_RET_ACTIVE) continue;
+          act[n] = (int)r; pos[r] = (int)n;
+          hrpc[n + 1] = hrpc[n] + (rp[r + 1] - rp[r]);
+          n++;
+        }
+        long nl = 0;
+        for (long q = 0; q < nslice; q++) {
+          hsptrc[q] = nl;
+          if (ro->state[q] == JUR_RET_ACTIVE)
+            for (long i = sptr[q]; i < sptr[q + 1]; i++) sraysc[nl++] = pos[srays[i]];
+        }
+        hsptrc[nslice] = nl;
+        nr_cur = n; rp_cur = hrpc; nactive_built = nactive;
+        long dummy_n = 0, dummy_k = 0;
+        npass = scene_passes(nr_cur, rp_cur, cap, pass, &dummy_n, &dummy_k);
+        ntpass = trial_passes(nr_cur, rin->nlam, cap, tpass, &dummy_n);
+        e = hipMemcpyAsync(d_act, act, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_sraysc, sraysc, sizeof(int) * (size_t)(nl ? nl : 1), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rpc, hrpc, sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_sptrc, hsptrc, sizeof(long) * (RS + 1), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+        jur_scene_compact_t cq;
+        memset(&cq, 0, sizeof cq);
+        cq.nr = nr; cq.n = n; cq.nd = nd; cq.act = d_act;
+        cq.geom = D + o_geom; cq.rad = D + o_inrad; cq.y = D + o_y; cq.weight = D + o_w;
+        cq.first = d_first; cq.len = d_len; cq.copy0 = d_copy0; cq.tcopy0 = Ir + (pl.tcopy0 - pl.ints);
+        cq.geom_c = d_geomc; cq.rad_c = d_radc; cq.y_c = d_yc; cq.weight_c = d_wc;
+        cq.first_c = d_firstc; cq.len_c = d_lenc; cq.copy0_c = d_copy0c; cq.tcopy0_c = d_tcopy0c;
+        ti = scene_timed_begin(m, s);
+        ek = jurk_scene_compact(&cq, s);
+        scene_timed_end(m, ti, s);
+        if (ek) { jur_set_error("%s: gathering kernel launch failed", who); rc = JUR_EHIP; goto done; }
+        a.nr = n; a.rowptr = d_rpc; a.first = d_firstc; a.len = d_lenc; a.copy0 = d_copy0c; a.in_geom = d_geomc; a.in_rad = d_radc;
+        nq.sptr = d_sptrc; nq.srays = d_sraysc; nq.y = d_yc; nq.weight = d_wc;
+        tps.nr = n; tps.first = d_firstc; tps.len = d_lenc; tps.tcopy0 = d_tcopy0c; tps.in_geom = d_geomc; tps.in_rad = d_radc;
+        tps.sptr = d_sptrc; tps.srays = d_sraysc; tps.y = d_yc; tps.weight = d_wc;
+      }
+      /* the dampings of this iteration (the product is rounded first), the states, fresh accumulators, the prior */
+      for (int l = 0; l < rin->nlam; l++)
+        for (long q = 0; q < nslice; q++) {
+          double const v = ro->lam[q] * rin->fac[l];
+          lamt[(size_t)l * RS + (size_t)q] = fmin(fmax(v, rin->lam_min), rin->lam_max);
+        }
+      e = hipMemcpyAsync(d_state, ro->state, sizeof(int) * RS, hipMemcpyHostToDevice, s);
+      if (it > 0 && e == hipSuccess) e = hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
+      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+      ek = 0;
+      if (npr) {
+        jur_scene_trial_t pq = tst;
+        pq.out = sv_d; pq.dx = NULL; pq.prior = d_prior0;
+        ti = scene_timed_begin(m, s);
+        ek = jurk_scene_elements(&pq, JUR_ELEM_PRIOR_DX, nb, s);
+        if (!ek) ek = jurk_scene_prior(&pq, s);
+        scene_timed_end(m, ti, s);
+      } else if (hipMemsetAsync(d_prior0, 0, sizeof(double) * RS, s) != hipSuccess) ek = 1;
+      if (ek) { (void)hipGetLastError(); jur_set_error("%s: prior kernel launch failed", who); rc = JUR_EHIP; goto done; }
+    }
+    m->h_atm_n = 0;                              /* the device no longer holds the caller's atmosphere */
+    if ((rc = install_stacked_rows(m, atm, nt, ncopies))) goto done;
+    st.rows = (double *)m->d_atm;
+    a.atm_time = m->view.atm_time;
+    ti = scene_timed_begin(m, s);
+    ek = jurk_scene_stack(&st, s);
+    scene_timed_end(m, ti, s);
+    if (!ek) ek = jurk_prepare_atm(&m->view, (double *)m->d_atm + nrow * (size_t)nt, s);
+    /* the one wait before the passes: the uploads have left the host arrays, the stacked rows stand */
+    if (ek || hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipGetLastError(); m->view.atm_np = 0; jur_set_error("%s: stacking the atmosphere failed", who); rc = JUR_EHIP; goto done;
+    }
+    if ((rc = jur_model_reserve(m, nmax))) goto done;   /* the forward model's workspace for the largest pass, before the first */
+
+    long const *const rp = rp_cur;               /* (the passes below: of all rays, or of those that remain) */
     for (long p = 0; p < npass; p++) {
       long const r0 = pass[p], r1 = pass[p + 1], n = (rp[r1] - rp[r0]) + (r1 - r0), nk = (rp[r1] - rp[r0]) * nd;
       size_t const N = (size_t)n;
@@ -2093,13 +2491,102 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (e == hipSuccess) e = hipStreamSynchronize(s);
       if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     }
-    if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out))) goto done;
+    if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out,
+                                   looping ? d_state : NULL))) goto done;
+    if (!looping) break;
+
+    /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
+    if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax))) goto done;
+    e = hipMemcpyAsync(hcost, nq.cost, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hnlive, nq.nlive, sizeof(long) * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hprior0, d_prior0, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(htcost, d_tcost, sizeof(double) * RL * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(htprior, d_tprior, sizeof(double) * RL * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; goto done; }
+    {
+      long work = 0;
+      for (long r = 0; r < nr_cur; r++) work += rp_cur[r + 1] - rp_cur[r] + 1;
+      for (long q = 0; q < nslice; q++) {
+        if (ro->state[q] != JUR_RET_ACTIVE) continue;
+        ro->cost[q] = hcost[q]; ro->prior[q] = hprior0[q]; ro->nlive[q] = hnlive[q]; ro->iters[q]++;
+        J[q] = hcost[q] + hprior0[q];
+        for (size_t l = 0; l < RL; l++) Jt[l * RS + (size_t)q] = htcost[l * RS + (size_t)q] + htprior[l * RS + (size_t)q];
+      }
+      if (ro->h_cost) {
+        size_t const at1 = (size_t)it * RS, at2 = (size_t)it * RL * RS;
+        for (long q = 0; q < nslice; q++) {
+          ro->h_cost[at1 + (size_t)q] = ro->cost[q]; ro->h_prior[at1 + (size_t)q] = ro->prior[q];
+          if (ro->state[q] != JUR_RET_ACTIVE) continue;
+          for (size_t l = 0; l < RL; l++) {
+            size_t const i = l * RS + (size_t)q;
+            ro->h_lam[at2 + i] = lamt[i]; ro->h_tcost[at2 + i] = htcost[i]; ro->h_tprior[at2 + i] = htprior[i]; ro->h_status[at2 + i] = hstatus[i];
+          }
+        }
+        ro->h_work[2 * it] = work; ro->h_work[2 * it + 1] = nr_cur * rin->nlam;
+      }
+      if ((rc = jur_retrieve_decide(rin->nlam, nslice, rin->tol, rin->lam_max, fac_max, J, Jt, lamt, hstatus, ro->lam, ro->state, best, accept))) goto done;
+      for (long q = 0; q < nslice; q++) {
+        choice[q] = accept[q] == 1 ? best[q] : -1;
+        if (accept[q] == 1) { ro->cost[q] = htcost[(size_t)best[q] * RS + (size_t)q]; ro->prior[q] = htprior[(size_t)best[q] * RS + (size_t)q]; }
+        if (ro->h_best) { ro->h_best[(size_t)it * RS + (size_t)q] = best[q]; ro->h_accept[(size_t)it * RS + (size_t)q] = accept[q]; }
+      }
+      e = hipMemcpyAsync(d_choice, choice, sizeof(int) * RS, hipMemcpyHostToDevice, s);
+      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+      jur_scene_trial_t aq = tst;
+      aq.state = NULL;                              /* (the choice alone says who moves: a slice may just have converged) */
+      ti = scene_timed_begin(m, s);
+      ek = jurk_scene_elements(&aq, JUR_ELEM_ACCEPT, nb, s);
+      scene_timed_end(m, ti, s);
+      if (ek || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); jur_set_error("%s: accepting the steps failed", who); rc = JUR_EHIP; goto done; }
+    }
+    }                                             /* (iterations) */
+
+    if (rt) {
+      /* what is still active has run out of iterations; the state comes home; the forward model on the retrieved
+       * atmosphere, for all rays, from the geometry and the mask that went up at the start */
+      atm_t *ret = (atm_t *)malloc(sizeof(atm_t));
+      if (!ret) { rc = JUR_ENOMEM; goto done; }
+      memcpy(ret, atm, sizeof(atm_t));
+      if (looping) {
+        for (long q = 0; q < nslice; q++) if (ro->state[q] == JUR_RET_ACTIVE) ro->state[q] = JUR_RET_MAXITER;
+        if (ro->h_cost)
+          for (int it = 0; it < rin->max_iter; it++)
+            if (ro->h_work[2 * it] == 0)                /* (an iteration that no slice reached) */
+              for (long q = 0; q < nslice; q++) { ro->h_cost[(size_t)it * RS + (size_t)q] = ro->cost[q]; ro->h_prior[(size_t)it * RS + (size_t)q] = ro->prior[q]; }
+        jur_scene_trial_t xq = tst;
+        xq.out = d_xout;
+        ti = scene_timed_begin(m, s);
+        ek = jurk_scene_elements(&xq, JUR_ELEM_STATE, nb, s);
+        scene_timed_end(m, ti, s);
+        e = ek ? hipErrorUnknown : hipMemcpyAsync(ro->x, d_xout, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipGetLastError(); free(ret); jur_set_error("%s: bringing the state home failed", who); rc = JUR_EHIP; goto done; }
+        for (long i = 0; i < nb; i++) {
+          int const row = pl.erow[i], ip = pl.eip[i];
+          double *const dst = row == 4 ? ret->p : row == 5 ? ret->t : row < 6 + ng ? ret->q[row - 6] : ret->k[row - 6 - ng];
+          dst[ip] = ro->x[i];
+        }
+      }
+      rc = jur_model_set_atm(m, ret);
+      if (!rc) {
+        e = hipMemcpyAsync(D + o_rad, D + o_inrad, sizeof(double) * nrd, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
+        if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
+      }
+      if (!rc) rc = jur_formod_device(m, nr, D + o_geom, D + o_rad, D + o_tau, D + o_tp, d_np, m->d_status, s);
+      if (rc) { free(ret); goto done; }
+      a.out_rad = D + o_rad; a.out_tau = D + o_tau; a.out_tp = D + o_tp; a.out_np = d_np;
+      ret_atm = ret;
+    }
     e = hipMemcpyAsync(rad, a.out_rad, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(tau, a.out_tau, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
     for (int q = 0; q < 3 && e == hipSuccess; q++) e = hipMemcpyAsync(tp[q], a.out_tp + (size_t)q * NR, sizeof(double) * NR, hipMemcpyDeviceToHost, s);
     if (np_out && e == hipSuccess) e = hipMemcpyAsync(np_out, a.out_np, sizeof(int) * NR, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (ntiles) {                                 /* the sums go home here, once */
+    if (ntiles && !rt) {                          /* the sums go home here, once */
       if (nm->A && e == hipSuccess) e = hipMemcpyAsync(nm->A, nq.A, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, s);
       if (nm->b && e == hipSuccess) e = hipMemcpyAsync(nm->b, nq.b, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
       if (e == hipSuccess) e = hipMemcpyAsync(nm->cost, nq.cost, sizeof(double) * (size_t)nslice, hipMemcpyDeviceToHost, s);
@@ -2108,11 +2595,13 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
+    if (rt && !rc) memcpy(rt->atm_ret, ret_atm, sizeof(atm_t));
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
   free(first); free(rp); free(sid); free(srays); free(sl); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa);
-  free(hbase);
+  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm);
+  trial_plan_free(&pl);
   return rc;
 }
 
@@ -2131,7 +2620,7 @@ static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
 int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                           double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL));
 }
 
 int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -2139,7 +2628,7 @@ int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double cons
                           double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_normal_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL));
 }
 
 int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -2149,7 +2638,191 @@ int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const 
   if (!m || !atm) { jur_set_error("jur_step_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_solve_t const sv = {in, out};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL));
+}
+
+int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, long nr, double const *const geom[7],
+                            double *rad, double *tau, double *const tp[3], int *np_out, long const *rowptr,
+                            double const *y, double const *weight, jur_retrieve_in_t const *in,
+                            jur_retrieve_out_t const *out, long max_rays_per_pass) {
+  if (!m || !atm0 || !atm_ret) { jur_set_error("jur_retrieve_scene_host: null argument"); return JUR_EINVAL; }
+  scene_normal_t const nm = {y, weight, NULL, NULL, NULL, NULL};
+  scene_retrieve_t const rt = {in, out, atm_ret};
+  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt);
+  if (rc) return scene_restore_atm(m, atm0, rc);    /* (on success the model holds atm_ret) */
+  if (nr != 0) return JUR_OK;
+  if (atm_ret != atm0) memcpy(atm_ret, atm0, sizeof(atm_t));   /* no rays: nothing was retrieved */
+  return scene_restore_atm(m, atm0, JUR_OK);
+}
+
+/* The device slab of the scene entries serves: doubles (base rows, geometry, mask, y, weight, dx, the prior pair, cost,
+ * prior), then the plan's longs, then its ints. */
+static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double const *rad_in,
+                            long const *rowptr, double const *y, double const *weight, int ntrial, double const *dx,
+                            double const *prior_ivar, double const *prior_xa, double *cost, double *prior, long max_rays_per_pass) {
+  char const *const who = "jur_trial_scene_host";
+  if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  if (ntrial < 1 || ntrial > 64) { jur_set_error("%s: ntrial = %d: 1 to 64 trials per call", who, ntrial); return JUR_EINVAL; }
+  if (!prior_ivar != !prior_xa) {
+    jur_set_error("%s: %s without %s: the prior is given as a pair", who, prior_ivar ? "prior_ivar" : "prior_xa",
+                  prior_ivar ? "prior_xa" : "prior_ivar");
+    return JUR_EINVAL;
+  }
+  ctl_t const *ctl = m->ctl;
+  if (ctl->hydz >= 0) {
+    jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so a step of one slice moves every pressure: "
+                  "the slices are no independent problems", who, ctl->hydz);
+    return JUR_EINVAL;
+  }
+  int const np0 = atm->np, nd = ctl->nd, ng = m->view.ng, nw = m->view.nw;
+  if (np0 < 2 || np0 > JUR_NP) { jur_set_error("%s: need 2..%d atmospheric points", who, JUR_NP); return JUR_EINVAL; }
+  for (int i = 1; i < np0; i++)
+    if (!(atm->time[i] >= atm->time[i - 1])) {
+      jur_set_error("%s: the time stamps of the atmosphere are not ascending (point %d): the slices of a "
+                    "stacked atmosphere cannot reproduce locate_atm there", who, i);
+      return JUR_EINVAL;
+    }
+  if (nr == 0) return JUR_OK;
+  if (nr > 0x7fffffffL / ntrial) { jur_set_error("%s: at most 2^31-1 trial rays per call", who); return JUR_EINVAL; }
+  if (!geom || !rad_in || !rowptr || !y || !weight) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+
+  size_t const NR = (size_t)nr, nrow = 6 + (size_t)ng + nw, nrd = NR * (size_t)nd;
+  int rc = JUR_OK, enqueued = 0;
+  int *first = (int *)malloc(sizeof(int) * 3 * NR), *len = first ? first + NR : NULL, *sid = first ? len + NR : NULL;
+  long *rp = (long *)malloc(sizeof(long) * 2 * (NR + 1)), *pass = rp ? rp + NR + 1 : NULL;
+  jur_scene_slice_t *sl = NULL;
+  double *hbase = NULL;
+  trial_plan_t pl;
+  memset(&pl, 0, sizeof pl);
+  if (!first || !rp) { rc = JUR_ENOMEM; goto done; }
+  if ((rc = jur_scene_layout(ctl, atm, nr, geom[0], first, len, rp))) goto done;
+  if (memcmp(rp, rowptr, sizeof(long) * (NR + 1))) {
+    jur_set_error("%s: rowptr is not jur_scene_layout's for these rays, this atmosphere and these windows", who);
+    rc = JUR_EINVAL;
+    goto done;
+  }
+  for (long r = 0; r < nr; r++)
+    for (int id = 0; id < nd; id++) {
+      double const w = weight[(size_t)r * nd + id];
+      if (!(w >= 0) || isinf(w)) {
+        jur_set_error("%s: the weight of ray %ld, channel %d is %g: negative or not finite", who, r, id, w);
+        rc = JUR_EINVAL;
+        goto done;
+      }
+    }
+  long const nslice = jur_scene_distinct(np0, nr, first, len, rp, sid, &sl);
+  if (nslice < 0) { rc = JUR_ENOMEM; goto done; }
+  if (nslice == 0) goto done;                         /* no state elements: nothing to write */
+  if (!dx || !cost || !prior) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
+  if ((rc = trial_plan_make(&pl, who, ctl, atm, ntrial, nr, nslice, sl, sid))) goto done;
+  long const nb = pl.nb;
+  for (int t = 0; t < ntrial; t++)
+    for (long q = 0; q < nslice; q++)
+      for (long e = pl.wptr[q]; e < pl.wptr[q + 1]; e++)
+        if (!isfinite(dx[(size_t)t * (size_t)nb + (size_t)e])) {
+          jur_set_error("%s: dx of trial %d, slice %ld, element %ld is %g: not finite", who, t, q, e - pl.wptr[q],
+                        dx[(size_t)t * (size_t)nb + (size_t)e]);
+          rc = JUR_EINVAL;
+          goto done;
+        }
+  if (prior_ivar && (rc = prior_check_values(who, nslice, pl.wptr, prior_ivar, prior_xa))) goto done;
+
+  size_t const NB = (size_t)nb, NS = (size_t)nslice, NT = (size_t)ntrial, npr = prior_ivar ? NB : 0;
+  size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)pl.nt;
+  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS);
+  if ((double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("%s: the trial copies (%ld points, %zu bytes) and accumulators (%zu bytes) exceed the workspace budget: "
+                  "call with fewer trials or the rays of fewer slices at a time", who, pl.nt, atm_bytes, acc_bytes);
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+  size_t const slot_bytes = sizeof(double) * (10 + 3 * (size_t)nd) + sizeof(int);
+  long cap = max_rays_per_pass;
+  if (cap == 0) {                                     /* as the Jacobian entries size their passes */
+    cap = (m->ws_budget - (long)atm_bytes - (long)acc_bytes) / 16 / (long)slot_bytes;
+    if (cap < 4096) cap = 4096;
+  }
+  long nmax = 0;
+  long const npass = trial_passes(nr, ntrial, cap, pass, &nmax);
+
+  hbase = (double *)malloc(sizeof(double) * nrow * (size_t)np0);
+  if (!hbase) { rc = JUR_ENOMEM; goto done; }
+  pack_atm_rows(m, atm, hbase, (size_t)np0, 0);
+  stack_times(hbase, atm->time, np0, 0.0);
+  double tmin = atm->time[0], tmax = atm->time[0];
+  for (int i = 0; i < np0; i++) { tmin = fmin(tmin, atm->time[i]); tmax = fmax(tmax, atm->time[i]); }
+  for (long i = 0; i < nr; i++) { tmin = fmin(tmin, geom[0][i]); tmax = fmax(tmax, geom[0][i]); }
+
+  size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_y = o_inrad + nrd, o_w = o_y + nrd,
+               o_dx = o_w + nrd, o_r = o_dx + NT * NB, o_xa = o_r + npr, o_cost = o_xa + npr, o_prior = o_cost + NT * NS,
+               o_long = o_prior + NT * NS, o_int = o_long + pl.nlong;
+  size_t const bytes = sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR);
+  if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
+  hipStream_t const s = m->stream;
+  if ((rc = wait_done(m, s))) goto done;
+  if (bytes > m->scene_bytes) {
+    if (m->d_scene) (void)hipFree(m->d_scene);
+    m->d_scene = NULL; m->scene_bytes = 0;
+    if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
+      (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
+    }
+    m->scene_bytes = bytes;
+  }
+  if ((rc = ensure_io(m, nmax, 0))) goto done;
+  {
+    double *const D = (double *)m->d_scene;
+    long *const L = (long *)(D + o_long);
+    int *const I = (int *)(D + o_int), *const d_first = I + pl.nint, *const d_len = d_first + NR;
+    enqueued = 1;
+    hipError_t e = hipMemcpyAsync(D + o_base, hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
+    for (int q = 0; q < 7 && e == hipSuccess; q++) e = hipMemcpyAsync(D + o_geom + (size_t)q * NR, geom[q], sizeof(double) * NR, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D + o_inrad, rad_in, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D + o_y, y, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D + o_w, weight, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && NB) e = hipMemcpyAsync(D + o_dx, dx, sizeof(double) * NT * NB, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && npr) e = hipMemcpyAsync(D + o_r, prior_ivar, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && npr) e = hipMemcpyAsync(D + o_xa, prior_xa, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(L, pl.longs, sizeof(long) * pl.nlong, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(I, pl.ints, sizeof(int) * pl.nint, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_first, first, sizeof(int) * 2 * NR, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+
+    jur_scene_stack_t sk;
+    jur_scene_trial_t st;
+    jur_scene_trial_pass_t ps;
+    memset(&sk, 0, sizeof sk); memset(&st, 0, sizeof st); memset(&ps, 0, sizeof ps);
+    long const *const d_wptr = L, *const d_off = L + (pl.off - pl.longs), *const d_sptr = L + (pl.sptr - pl.longs);
+    sk.ncopy = (int)pl.ncopy; sk.np0 = np0; sk.nrow = (int)nrow; sk.ng = ng; sk.nt = pl.nt;
+    sk.off = d_off; sk.first = I; sk.prow = I + pl.ncopy; sk.pip = I + 2 * pl.ncopy;
+    sk.base = D + o_base; sk.h = NULL; sk.tmax = tmax; sk.span = (tmax - tmin) + 1.0;
+    st.nslice = nslice; st.ntrial = ntrial; st.np0 = np0; st.nt = pl.nt;
+    st.wptr = d_wptr; st.off = d_off; st.sfirst = I + (pl.sfirst - pl.ints); st.erow = I + (pl.erow - pl.ints); st.eip = I + (pl.eip - pl.ints);
+    st.base = D + o_base; st.dx = D + o_dx; st.ivar = npr ? D + o_r : NULL; st.xa = npr ? D + o_xa : NULL; st.prior = D + o_prior;
+    ps.nr = nr; ps.nd = nd; ps.ntrial = ntrial; ps.first = d_first; ps.len = d_len; ps.tcopy0 = I + (pl.tcopy0 - pl.ints); ps.off = d_off;
+    ps.in_geom = D + o_geom; ps.in_rad = D + o_inrad; ps.nslice = nslice; ps.sptr = d_sptr; ps.srays = I + (pl.srays - pl.ints);
+    ps.y = D + o_y; ps.weight = D + o_w; ps.cost = D + o_cost;
+    if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax))) goto done;
+    e = hipMemcpyAsync(cost, D + o_cost, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(prior, D + o_prior, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
+  }
+done:
+  if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
+  free(first); free(rp); free(sl); free(hbase);
+  trial_plan_free(&pl);
+  return rc;
+}
+
+int jur_trial_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double const *rad_in,
+                         long const *rowptr, double const *y, double const *weight, int ntrial, double const *dx,
+                         double const *prior_ivar, double const *prior_xa, double *cost, double *prior, long max_rays_per_pass) {
+  if (!m || !atm) { jur_set_error("jur_trial_scene_host: null argument"); return JUR_EINVAL; }
+  return scene_restore_atm(m, atm, trial_scene_body(m, atm, nr, geom, rad_in, rowptr, y, weight, ntrial, dx, prior_ivar, prior_xa,
+                                                    cost, prior, max_rays_per_pass));
 }
 
 /* Systems the caller holds.  The device slab of the scene entries serves (it holds nothing between calls): wptr | aptr,
@@ -2201,7 +2874,7 @@ int jur_solve_slices_host(jur_model_t *m, long nslice, long const *wptr, double 
     if (na && e == hipSuccess) e = hipMemcpyAsync(D + o_A, A, sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s);
     if (nb && e == hipSuccess) e = hipMemcpyAsync(D + o_b, b, sizeof(double) * (size_t)nb, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if ((rc = solve_enqueue(m, s, who, nslice, na, nb, L, L + NS + 1, D + o_A, D + o_b, D + o_sv, in, out))) goto done;
+    if ((rc = solve_enqueue(m, s, who, nslice, na, nb, L, L + NS + 1, D + o_A, D + o_b, D + o_sv, in, out, NULL))) goto done;
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
   }

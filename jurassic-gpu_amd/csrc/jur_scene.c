@@ -151,6 +151,38 @@ long jur_scene_distinct(int np, long nr, int const *first, int const *len, long 
   return nslice;
 }
 
+/* The policy of one iteration of jur_retrieve_scene_host (include/jurassic_hip.h).  `x != x` is the NaN test: +inf is a
+ * candidate like any other, and never accepted against a finite J by the strict comparison. */
+int jur_retrieve_decide(int nlam, long nslice, double tol, double lam_max, double fac_max, double const *J, double const *Jt,
+                        double const *lamt, int const *status, double *lam, int *state, int *best, int *accept) {
+  if (nlam < 1 || nslice < 0 || (nslice > 0 && (!J || !Jt || !lamt || !status || !lam || !state || !best || !accept))) {
+    jur_set_error("jur_retrieve_decide: bad arguments");
+    return JUR_EINVAL;
+  }
+  for (long s = 0; s < nslice; s++) {
+    best[s] = accept[s] = -1;
+    if (state[s] != JUR_RET_ACTIVE) continue;
+    int b = -1;
+    for (int l = 0; l < nlam; l++) {
+      size_t const at = (size_t)l * (size_t)nslice + (size_t)s;
+      if (status[at] != 0 || Jt[at] != Jt[at]) continue;
+      if (b < 0 || Jt[at] < Jt[(size_t)b * (size_t)nslice + (size_t)s]) b = l;
+    }
+    best[s] = b;
+    double const jb = b >= 0 ? Jt[(size_t)b * (size_t)nslice + (size_t)s] : 0.;
+    accept[s] = (b >= 0 && jb < J[s]) ? 1 : 0;
+    if (accept[s]) {
+      lam[s] = lamt[(size_t)b * (size_t)nslice + (size_t)s];
+      if (J[s] - jb <= tol * J[s]) state[s] = JUR_RET_CONVERGED;
+    } else if (lam[s] == lam_max) state[s] = JUR_RET_STALLED;
+    else {
+      double const grown = lam[s] * fac_max;
+      lam[s] = grown < lam_max ? grown : lam_max;
+    }
+  }
+  return JUR_OK;
+}
+
 long jur_scene_slices(ctl_t const *ctl, atm_t const *atm, long nr, double const *time, int *sid, int *sfirst, int *slen,
                       long *wptr, long *aptr) {
   if (!ctl || !atm || nr < 0 || (nr > 0 && !time)) { jur_set_error("scene_slices: bad arguments"); return JUR_EINVAL; }

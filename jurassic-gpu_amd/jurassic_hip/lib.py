@@ -118,6 +118,11 @@ def lib():
         L.jur_solve_slices_host.argtypes = [C.c_void_p, C.c_long, lp_, dp, dp, C.c_void_p, C.c_void_p]
         L.jur_step_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
                                           dp, dp, C.c_void_p, C.c_void_p, dp, dp, dp, lp_, dp, C.c_long]
+        L.jur_trial_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, lp_, dp, dp, C.c_int, dp, dp, dp,
+                                           dp, dp, C.c_long]
+        L.jur_retrieve_decide.argtypes = [C.c_int, C.c_long, C.c_double, C.c_double, C.c_double, dp, dp, dp, ip_, dp, ip_, ip_, ip_]
+        L.jur_retrieve_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp),
+                                              ip_, lp_, dp, dp, C.c_void_p, C.c_void_p, C.c_long]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -471,6 +476,99 @@ class Model:
             out["k"] = k
         return out
 
+    def _scene_inputs(self, atm, geom, y, weight, rad_in, rowptr):
+        """what the retrieval methods share with normal_scene: (g, layout, rowptr, y, weight, rad)"""
+        g = np.ascontiguousarray(np.asarray(geom, dtype=np.float64).T)
+        nr, nd = g.shape[1], self.nd
+        time = g[0] if nr else np.zeros(0)
+        lay = _scene_layout(self.ctl, atm, time)
+        lay.update(scene_slices(self.ctl, atm, time))
+        rp = lay["rowptr"] if rowptr is None else np.ascontiguousarray(rowptr, dtype=np.int64)
+        if rp.shape != lay["rowptr"].shape:
+            raise ValueError("rowptr holds %d entries, the call has %d rays" % (len(rp), nr))
+        yy, ww = (np.ascontiguousarray(x, dtype=np.float64) for x in (y, weight))
+        if yy.shape != (nr, nd) or ww.shape != (nr, nd):
+            raise ValueError("y and weight must be (%d, %d)" % (nr, nd))
+        rad = np.zeros((nr, nd)) if rad_in is None else np.ascontiguousarray(rad_in, dtype=np.float64).copy()
+        return g, lay, rp, yy, ww, rad
+
+    def trial_scene(self, atm, geom, y, weight, dx, prior_ivar=None, prior_xa=None, rad_in=None, max_rays_per_pass=0, rowptr=None):
+        """Costs of candidate steps, forward only (jur_trial_scene_host).  dx: (ntrial, n) or (n,), laid out by
+        scene_slices of these rays; prior_ivar, prior_xa (n,): both or neither -> the layout plus cost and prior
+        (ntrial, nslice): cost[t, s] is normal_scene's cost of slice s on the atmosphere with dx[t] written back, bit for
+        bit; prior[t, s] the prior term of that state (+0.0 without a prior)."""
+        g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, rowptr)
+        nr = g.shape[1]
+        ns, n = len(lay["sfirst"]), int(lay["wptr"][-1])
+        d = np.ascontiguousarray(dx, dtype=np.float64)
+        if d.ndim == 1:
+            d = d.reshape(1, -1)
+        if d.ndim != 2 or d.shape[1] != n:
+            raise ValueError("dx must be (ntrial, %d)" % n)
+        nt = d.shape[0]
+        pri = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (prior_ivar, prior_xa)]
+        if any(x is not None and x.size != n for x in pri):
+            raise ValueError("prior_ivar and prior_xa must hold %d doubles" % n)
+        cost, prior = np.zeros((nt, ns)), np.zeros((nt, ns))
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        _chk(lib().jur_trial_scene_host(self.h, C.byref(atm), nr, garr, _p(rad), rp.ctypes.data_as(C.POINTER(C.c_long)), _p(yy),
+                                        _p(ww), nt, _p(d), None if pri[0] is None else _p(pri[0]),
+                                        None if pri[1] is None else _p(pri[1]), _p(cost), _p(prior), max_rays_per_pass))
+        return dict(lay, cost=cost, prior=prior)
+
+    def retrieve_scene(self, atm, geom, y, weight, max_iter, fac, lam0=1.0, lam_min=1e-6, lam_max=1e6, tol=0.0, mode=0,
+                       prior_ivar=None, prior_xa=None, history=False, rad_in=None, max_rays_per_pass=0, rowptr=None,
+                       atm_ret=None):
+        """Retrieval of a scene on the device (jur_retrieve_scene_host): iterated Levenberg-Marquardt with trial steps,
+        every slice a problem of its own.  atm_ret: an atm_t to receive the result (written only on success; it may be
+        atm itself) instead of a new one.  fac (nlam,): the dampings tried per iteration are lam * fac, clamped to
+        [lam_min, lam_max]; tol: a slice has converged when an accepted step lowers J = cost + prior by no more than
+        tol * J; prior_ivar, prior_xa (n,): both or neither, laid out by scene_slices.
+        -> the layout, "atm" (a new atm_t: atm with the retrieved elements replaced), the formod_host dict on it, x (n,),
+        lam, cost, prior, nlive, state (RET_*), iters (nslice,) and, with history, h_cost, h_prior (max_iter, nslice),
+        h_lam, h_tcost, h_tprior, h_status (max_iter, nlam, nslice), h_best, h_accept (max_iter, nslice) and h_work
+        (max_iter, 2): the replicated rays of the Jacobian and of the trial passes.  Where a slice took no part in an
+        iteration its h_lam, h_tcost, h_tprior are NaN and its h_status, h_best, h_accept -1."""
+        g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, rowptr)
+        nr, nd = g.shape[1], self.nd
+        ns, n = len(lay["sfirst"]), int(lay["wptr"][-1])
+        ff = np.ascontiguousarray(fac, dtype=np.float64).ravel()
+        nlam, mi = len(ff), max(int(max_iter), 0)
+        pri = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (prior_ivar, prior_xa)]
+        if any(x is not None and x.size != n for x in pri):
+            raise ValueError("prior_ivar and prior_xa must hold %d doubles" % n)
+        tau, tp, npts = np.zeros((nr, nd)), np.zeros((3, nr)), np.zeros(nr, dtype=np.int32)
+        res = dict(x=np.zeros(n), lam=np.zeros(ns), cost=np.zeros(ns), prior=np.zeros(ns), nlive=np.zeros(ns, dtype=np.int64),
+                   state=np.zeros(ns, dtype=np.int32), iters=np.zeros(ns, dtype=np.int32))
+        hist = {}
+        if history is True:
+            hist = dict(h_cost=np.zeros((mi, ns)), h_prior=np.zeros((mi, ns)), h_lam=np.zeros((mi, nlam, ns)),
+                        h_tcost=np.zeros((mi, nlam, ns)), h_tprior=np.zeros((mi, nlam, ns)),
+                        h_status=np.zeros((mi, nlam, ns), dtype=np.int32), h_best=np.zeros((mi, ns), dtype=np.int32),
+                        h_accept=np.zeros((mi, ns), dtype=np.int32), h_work=np.zeros((mi, 2), dtype=np.int64))
+        elif history:                                   # (a subset of the names: only the library can refuse it)
+            hist = {name: np.zeros(1) for name in history}
+        rin = RetrieveIn(int(max_iter), nlam, int(mode), _p(ff), lam0, lam_min, lam_max, tol,
+                         None if pri[0] is None else _p(pri[0]), None if pri[1] is None else _p(pri[1]))
+        rout = RetrieveOut()
+        for name, ctype in RetrieveOut._fields_:
+            arr = res.get(name, hist.get(name))
+            if arr is not None:
+                setattr(rout, name, arr.ctypes.data_as(ctype))
+        ret = atm_ret
+        if ret is None:
+            ret = abi.atm_t()
+            C.memmove(C.byref(ret), C.byref(atm), C.sizeof(abi.atm_t))
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
+        _chk(lib().jur_retrieve_scene_host(self.h, C.byref(atm), C.byref(ret), nr, garr, _p(rad), _p(tau), tarr,
+                                           npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(C.POINTER(C.c_long)),
+                                           _p(yy), _p(ww), C.byref(rin), C.byref(rout), max_rays_per_pass))
+        out = dict(lay, atm=ret, rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, **res)
+        if history is True:
+            out.update(hist)
+        return out
+
     def solve_slices(self, wptr, A, b, lam, mode=0, prior_ivar=None, prior_dx=None, want_factor=False):
         """Batched Cholesky solve of damped, optionally regularised systems the caller holds (jur_solve_slices_host): the
         re-solve of a Levenberg-Marquardt iteration.  wptr (nslice + 1,): running sum of the widths; A flat, A_s at the
@@ -583,6 +681,47 @@ class SolveIn(C.Structure):
 class SolveOut(C.Structure):
     """jur_solve_out_t"""
     _fields_ = [("dx", dp), ("pred", dp), ("status", C.POINTER(C.c_int)), ("L", dp)]
+
+
+RET_ACTIVE, RET_CONVERGED, RET_STALLED, RET_MAXITER = 0, 1, 2, 3      # JUR_RET_*
+
+
+class RetrieveIn(C.Structure):
+    """jur_retrieve_in_t"""
+    _fields_ = [("max_iter", C.c_int), ("nlam", C.c_int), ("mode", C.c_int), ("fac", dp), ("lam0", C.c_double),
+                ("lam_min", C.c_double), ("lam_max", C.c_double), ("tol", C.c_double), ("prior_ivar", dp), ("prior_xa", dp)]
+
+
+_ip, _lp = C.POINTER(C.c_int), C.POINTER(C.c_long)
+
+
+class RetrieveOut(C.Structure):
+    """jur_retrieve_out_t"""
+    _fields_ = [("x", dp), ("lam", dp), ("cost", dp), ("prior", dp), ("nlive", _lp), ("state", _ip), ("iters", _ip),
+                ("h_cost", dp), ("h_prior", dp), ("h_lam", dp), ("h_tcost", dp), ("h_tprior", dp), ("h_status", _ip),
+                ("h_best", _ip), ("h_accept", _ip), ("h_work", _lp)]
+
+
+def retrieve_decide(J, Jt, lamt, status, lam, state, tol, lam_max, fac_max):
+    """jur_retrieve_decide (host arithmetic, no GPU): the accept/reject policy of one iteration of Model.retrieve_scene.
+    J (nslice,); Jt, lamt, status (nlam, nslice); lam, state (nslice,) -> dict(lam, state: the updated copies; best,
+    accept: -1 for a slice that is not RET_ACTIVE)."""
+    JJ = np.ascontiguousarray(J, dtype=np.float64)
+    ns = len(JJ)
+    T, LT = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1, ns) for x in (Jt, lamt))
+    S = np.ascontiguousarray(status, dtype=np.int32).reshape(-1, ns)
+    nlam = T.shape[0]
+    if LT.shape != T.shape or S.shape != T.shape:
+        raise ValueError("Jt, lamt and status must be (nlam, %d)" % ns)
+    lm = np.array(lam, dtype=np.float64)
+    st = np.array(state, dtype=np.int32)
+    if lm.shape != (ns,) or st.shape != (ns,):
+        raise ValueError("lam and state must be (%d,)" % ns)
+    best, accept = np.zeros(ns, dtype=np.int32), np.zeros(ns, dtype=np.int32)
+    ip_ = C.POINTER(C.c_int)
+    _chk(lib().jur_retrieve_decide(nlam, ns, tol, lam_max, fac_max, _p(JJ), _p(T), _p(LT), S.ctypes.data_as(ip_), _p(lm),
+                                   st.ctypes.data_as(ip_), best.ctypes.data_as(ip_), accept.ctypes.data_as(ip_)))
+    return dict(lam=lm, state=st, best=best, accept=accept)
 
 
 def _solve_structs(ns, n, na, lam, mode, prior_ivar, prior_dx, want_factor):
