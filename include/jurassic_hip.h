@@ -467,6 +467,16 @@ void jur_tune_trace(int lanes_per_ray);
  * 2 = wherever the longest slice fits.  A workgroup whose rays use two slices reads the model's arrays.  Same results
  * bit for bit (tests/test_trace_lds_gpu.py). */
 void jur_tune_trace_slice(int mode);
+/* Process-wide: whether a batched call whose rays were sorted and fit ONE ray-tracing launch starts that launch's blocks
+ * of 256 sorted slots in ascending order of the tangent altitude of their lowest ray, i.e. longest paths first, in the
+ * one-lane-per-ray tracers and, where one integration launch covers the same slots, in the radiance update (instead of
+ * in slot order, which ends every launch on the long blocks of the last profiles).  0 = chosen per call (at least
+ * 262 144 rays), 1 = never, 2 = whenever the rays were sorted and the call is one trace launch.  Placement only: same
+ * results bit for bit (tests/test_block_order_gpu.py). */
+void jur_tune_block_order(int mode);
+/* The block order of the model's last batched call, for tests and tools: copies up to `cap` entries to `out` (a
+ * permutation of 0 .. n - 1) and returns n = (rays + 255) / 256, 0 if the call built none, JUR_EHIP on failure. */
+long jur_model_block_order(jur_model_t *m, int *out, long cap);
 /* Process-wide tuning of the radiance-update kernel of the batched path: up to `channels_per_group` (0 .. 6, default
  * 4; 0 = one channel per workgroup always) channels of a ray block share a workgroup, with a barrier every
  * `sync_segments` segments (default 8; <= 0 none), for launches of at least `min_lanes` rays x channels (default

@@ -102,6 +102,8 @@ typedef struct {
   int *status;                  /* device flag: bit0 = NLOS overflow            */
   int slice_sorted;             /* neighbouring slots use the same atmosphere slice (one slice, or `order` groups the
                                    rays by slice): the ray tracer may keep a workgroup's slice in LDS            */
+  int const *blk_order;         /* [(n + 255) / 256] blocks of 256 slots in the order the launch starts them, longest
+                                   paths first (jurk_block_order), or NULL: in order.  Placement only              */
 } jur_chunk_t;
 
 /* kernel launchers (jur_kernels.hip); return hipError_t as int */
@@ -127,6 +129,9 @@ int jurk_fill_records(jur_ue_t const *ue, jur_rec_t *rec, long long n, void *str
 long jurk_sort_tmp_bytes(long nr);
 int jurk_sort_rays(jur_view_t const *v, int by_profile, long nr, double const *d_geom, long ld, int *d_order, void *tmp,
                    long tmp_bytes, void *stream);   /* field k of ray r at d_geom[k * ld + r] */
+/* after jurk_sort_rays on the same `tmp`: fills blk_order[(nr + 255) / 256] with the blocks of 256 consecutive slots
+ * in ascending order of their lowest ray's tangent altitude (a permutation, whatever the keys) */
+int jurk_block_order(long nr, int *d_blk_order, void *tmp, long tmp_bytes, void *stream);
 
 /* the whole path of small calls in one kernel, RB rays per workgroup (c->order is ignored: nothing is sorted) */
 long jurk_pencil_lds_bytes(jur_view_t const *v, int RB);

@@ -688,9 +688,18 @@ struct LosWorkspace {
 
 // 4 waves per SIMD (128 VGPRs, some scratch): measured 20 % faster than 2 waves without spills once a
 // launch carries enough rays (>= 4 x 131072) to fill them
+// Where a launch has a block order (jur_chunk_t::blk_order), its workgroups take the blocks of 256 slots in that order
+// instead of blockIdx order: workgroup b of a kernel with M workgroups to the block works on part b % M of block
+// blk_order[b / M].  The hardware hands workgroups out in blockIdx order, so the blocks with the longest paths start
+// first and the launch ends on short ones.  Wave-uniform (a scalar register); the grid covers whole blocks then.
+template <int M>
+__device__ __forceinline__ int ordered_block(int const *__restrict__ blk_order, int b) {
+  return blk_order ? __builtin_amdgcn_readfirstlane(blk_order[b / M]) * M + b % M : b;
+}
+
 __global__ __launch_bounds__(64, 4) void jur_trace_kernel(jur_view_t v, jur_chunk_t c) {
   __shared__ double tr_sh[15][64];
-  int const r = blockIdx.x * blockDim.x + threadIdx.x;   // slot in the chunk
+  int const r = ordered_block<4>(c.blk_order, (int)blockIdx.x) * blockDim.x + threadIdx.x;   // slot in the chunk
   if (r >= c.n) return;
   long const ray = c.order ? (long)c.order[r] : c.first + r;
   LosWorkspace L{c.los + (size_t)(r >> 6) * los_tile_doubles(JUR_F_K + v.nw + v.ng) + (r & 63), JUR_F_K + v.nw + v.ng};
@@ -747,7 +756,8 @@ __global__ __launch_bounds__(64 * JUR_TRACE_SLICE_WAVES, 4) void jur_trace_slice
   double (&tr_sh)[15][64] = reinterpret_cast<double (*)[15][64]>(jur_trace_lds)[threadIdx.x >> 6];
   double *const slab = jur_trace_lds + JUR_TRACE_SLICE_WAVES * 15 * 64;
   int *const agree = reinterpret_cast<int *>(slab);      // min a0, max a0, min n, max n over the workgroup's rays
-  int const r = blockIdx.x * blockDim.x + threadIdx.x;   // slot in the chunk
+  // (workgroups wider than a block of 256 slots get no block order: jurk_launch_trace)
+  int const r = ordered_block<(JUR_TRACE_SLICE_WAVES < 4 ? 4 / JUR_TRACE_SLICE_WAVES : 1)>(c.blk_order, (int)blockIdx.x) * blockDim.x + threadIdx.x;   // slot in the chunk
   bool const live = r < c.n;
   if (threadIdx.x == 0) { agree[0] = 0x7fffffff; agree[1] = -1; agree[2] = 0x7fffffff; agree[3] = -1; }
   __syncthreads();
@@ -1574,8 +1584,8 @@ __global__ __launch_bounds__(256, 6) void jur_combine_kernel(jur_view_t v, jur_c
   // same XCD-aware order as jur_ega_kernel: the nd workgroups of one ray block follow each other
   // on one XCD and share the block's LOS rows in that L2
   BlockItem const bi = xcd_block_item((int)blockIdx.x, nrb, nd);
-  int const rb = bi.rb, d = bi.item;                             // ray block, channel: uniform
-  if (rb < 0) return;
+  if (bi.rb < 0) return;
+  int const rb = ordered_block<1>(c.blk_order, bi.rb), d = bi.item;   // ray block, channel: uniform
   int const r = rb * blockDim.x + threadIdx.x;
   // the channel's source-function table (1201 doubles) is staged in LDS: its two reads per segment are
   // gathers by temperature, everything else this kernel loads is a coalesced stream
@@ -1640,8 +1650,11 @@ __global__ __launch_bounds__(512, JUR_COMBINE_WAVES) void jur_combine_group_kern
   int const nd = v.nd, ng = v.ng;
   int const ncg = (nd + CG - 1) / CG, SUB = (int)(blockDim.x >> 6) / CG;
   BlockItem const bi = xcd_block_item((int)blockIdx.x, nsb, ncg);
-  int const sb = bi.rb, cg = bi.item;                                // ray super-block, channel group: uniform
-  if (sb < 0) return;
+  if (bi.rb < 0) return;
+  // ray super-block, channel group: uniform.  4 / SUB super-blocks of SUB x 64 slots to the block of the launch's block
+  // order (jurk_launch_combine passes one only where SUB is 1, 2 or 4)
+  int const msb = 4 / SUB, cg = bi.item;
+  int const sb = c.blk_order ? __builtin_amdgcn_readfirstlane(c.blk_order[bi.rb / msb]) * msb + bi.rb % msb : bi.rb;
   int const w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);   // uniform: channel constants stay in SGPRs
   int const cw = w % CG, sub = w / CG;
   int const d = cg * CG + cw;
@@ -2207,6 +2220,24 @@ __global__ __launch_bounds__(256) void jur_raykey_kernel(long nr, long ld, doubl
   }
   key[r] = (slice << 32) | ord;
   id[r] = (int)r;
+}
+
+// One key per block of 256 consecutive slots of the sorted launch, a wavefront per block: the tangent-altitude bits (the
+// low word of the sorted key) of the block's LOWEST ray, the one with the longest path.  Within a profile the slots
+// ascend in tangent altitude and that is the block's first slot; a block that straddles two profiles begins with the
+// highest rays of one and holds the lowest of the next, which cost the most (keyed by its first slot it would start
+// last and be the launch's tail: tools/dispatch_order_model.py).
+__global__ __launch_bounds__(256) void jur_blockkey_kernel(long nr, int nblk, unsigned long long const *__restrict__ sorted_key,
+                                                           unsigned *__restrict__ key, int *__restrict__ id) {
+  int const b = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = (int)(threadIdx.x & 63);
+  if (b >= nblk) return;                               // (whole wavefronts: b is uniform)
+  unsigned m = 0xffffffffu;
+  for (int k = 0; k < 4; k++) {
+    long const r = (long)b * 256 + k * 64 + lane;
+    if (r < nr) m = min(m, (unsigned)sorted_key[r]);
+  }
+  for (int o = 32; o > 0; o >>= 1) m = min(m, (unsigned)__shfl_xor((int)m, o));
+  if (lane == 0) { key[b] = m; id[b] = b; }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2997,10 +3028,14 @@ extern "C" int jurk_launch_trace(jur_view_t const *v, jur_chunk_t const *c, void
   if (lanes == 1 && fits && mode != 1 && (mode == 2 || (c->slice_sorted && c->n >= 4096 * 64))) {
     int const wg = 64 * JUR_TRACE_SLICE_WAVES;
     size_t const lds = 8 * (size_t)(JUR_TRACE_SLICE_WAVES * 15 * 64 + slab);
-    hipLaunchKernelGGL(jur_trace_slice_kernel, dim3((c->n + wg - 1) / wg), dim3(wg), lds, (hipStream_t)stream, *v, *c, (int)slab);
+    jur_chunk_t cs = *c;
+    if (wg > 256) cs.blk_order = NULL;
+    // with a block order the grid covers whole blocks of 256 slots: any block may come last
+    unsigned const grid = cs.blk_order ? (unsigned)((c->n + 255) / 256) * (256 / wg) : (unsigned)((c->n + wg - 1) / wg);
+    hipLaunchKernelGGL(jur_trace_slice_kernel, dim3(grid), dim3(wg), lds, (hipStream_t)stream, *v, cs, (int)slab);
     return (int)hipGetLastError();
   }
-  int const grid = (int)(((long)c->n * lanes + block - 1) / block);
+  int const grid = (lanes == 1 && c->blk_order) ? (c->n + 255) / 256 * 4 : (int)(((long)c->n * lanes + block - 1) / block);
   if (lanes == 4) hipLaunchKernelGGL(jur_trace_lanes_kernel<4>, dim3(grid), dim3(block), 0, (hipStream_t)stream, *v, *c);
   else hipLaunchKernelGGL(jur_trace_kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, *v, *c);
   return (int)hipGetLastError();
@@ -3078,12 +3113,15 @@ extern "C" int jurk_launch_combine(jur_view_t const *v, jur_chunk_t const *c, vo
   bool const fits = g_combine_forced || (group == 4 && (v->nd % 4 == 0 || v->nd >= 64));
   if (group > 0 && v->nd > 1 && fits && (long)c->n * v->nd >= g_combine_min_lanes) {
     int const CG = v->nd < group ? v->nd : group, SUB = 8 / CG, W = CG * SUB;
-    int const nsb = (c->n + SUB * 64 - 1) / (SUB * 64), ncg = (v->nd + CG - 1) / CG;
+    jur_chunk_t cs = *c;
+    if (SUB > 4) cs.blk_order = NULL;              // super-blocks of 512 slots: wider than the blocks of the order
+    // (with a block order the grid covers whole blocks of 256 slots: any block may come last)
+    int const nsb = cs.blk_order ? (c->n + 255) / 256 * (4 / SUB) : (c->n + SUB * 64 - 1) / (SUB * 64), ncg = (v->nd + CG - 1) / CG;
     unsigned const g2 = xcd_grid(nsb, ncg);
     int mask = -1;                                 // barrier every 2^k segments, k from JUR_COMBINE_SYNC (<= 0: none)
     if (sync > 0) { mask = 1; while (mask * 2 <= sync) mask *= 2; mask -= 1; }
     hipLaunchKernelGGL(jur_combine_group_kernel, dim3(g2), dim3(64 * W), sizeof(double) * (JUR_TBLNS * CG + 2 + 64), (hipStream_t)stream,
-                       *v, *c, nsb, CG, mask);
+                       *v, cs, nsb, CG, mask);
     return (int)hipGetLastError();
   }
   hipLaunchKernelGGL(jur_combine_kernel, dim3(grid), dim3(block), sizeof(double) * (JUR_TBLNS + 64), (hipStream_t)stream, *v, *c,
@@ -3132,6 +3170,12 @@ extern "C" long jurk_sort_tmp_bytes(long nr) {
   if (hipcub::DeviceRadixSort::SortPairs(nullptr, cub, (unsigned long long const *)nullptr, (unsigned long long *)nullptr,
                                          (int const *)nullptr, (int *)nullptr, (int)nr) != hipSuccess)
     cub = 64 * (size_t)nr + (1 << 20);
+  // ... and of the sort of the launch's blocks (jurk_block_order), which runs after it in the same scratch
+  size_t cub_blk = 0;
+  if (hipcub::DeviceRadixSort::SortPairs(nullptr, cub_blk, (unsigned const *)nullptr, (unsigned *)nullptr, (int const *)nullptr,
+                                         (int *)nullptr, (int)((nr + 255) / 256)) != hipSuccess)
+    cub_blk = cub;
+  if (cub_blk > cub) cub = cub_blk;
   return (long)(2 * align_up(8 * (size_t)nr) + align_up(4 * (size_t)nr) + align_up(cub) + 256);
 }
 
@@ -3151,6 +3195,29 @@ extern "C" int jurk_sort_rays(jur_view_t const *v, int by_profile, long nr, doub
   if (e != hipSuccess) return (int)e;
   e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, key_in, key_out, id_in, d_order, (int)nr, 0,
                                          by_profile ? 64 : 32, s);
+  return (int)e;
+}
+
+// The order in which a launch over the sorted slots starts its blocks of 256: ascending tangent altitude of the block's
+// lowest ray, so the longest paths first (see jur_chunk_t::blk_order).  Reads the sorted keys jurk_sort_rays has left in
+// `tmp`; its own keys and ids lie where the ray sort's unsorted keys were.  The radix sort is stable: equal keys keep
+// their blocks in ascending order, a permutation in any case.
+extern "C" int jurk_block_order(long nr, int *d_blk_order, void *tmp, long tmp_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  size_t const seg8 = align_up(8 * (size_t)nr), seg4 = align_up(4 * (size_t)nr);
+  int const nblk = (int)((nr + 255) / 256);
+  size_t const seg = (4 * (size_t)nblk + 15) & ~(size_t)15;
+  if (nr < 1 || 3 * seg > seg8) return (int)hipErrorInvalidValue;
+  char *base = (char *)tmp;
+  unsigned long long const *sorted_key = (unsigned long long const *)(base + seg8);
+  unsigned *key_in = (unsigned *)base, *key_out = (unsigned *)(base + seg);
+  int *id_in = (int *)(base + 2 * seg);
+  void *cub_tmp = base + 2 * seg8 + seg4;
+  size_t cub_bytes = (size_t)tmp_bytes - 2 * seg8 - seg4;
+  hipLaunchKernelGGL(jur_blockkey_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, nr, nblk, sorted_key, key_in, id_in);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, key_in, key_out, id_in, d_blk_order, nblk, 0, 32, s);
   return (int)e;
 }
 

@@ -63,6 +63,9 @@ struct jur_model {
   int *d_order;
   void *d_sort_tmp;
   long order_cap, sort_tmp_bytes;
+  int *d_blk_order;             /* [(order_cap + 255) / 256] blocks of 256 sorted slots, longest paths first (see
+                                   formod_device_body)                                                       */
+  long n_blk_order;             /* blocks of the last batched call's order, 0: it built none                  */
   /* staging for the host entry */
   double *d_io;                 /* geom[7][cap] tp[3][cap] rad/tau[cap][nd]      */
   int *d_io_np;
@@ -303,7 +306,7 @@ void jur_model_destroy(jur_model_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_rec = NULL;
-  void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp,
+  void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp, m->d_blk_order,
                   m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_kq, m->d_ctb, m->d_scene};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
@@ -612,6 +615,18 @@ void jur_model_cost_params(jur_model_t const *m, double *rayds, double *raydz, d
 }
 int jur_model_chunk_rays(jur_model_t const *m) { return m->chunk_rays; }
 long jur_model_last_launches(jur_model_t const *m) { return m->n_launch_ega; }
+/* the block order of the last batched call (see formod_device_body), for tests and tools: waits for that call */
+long jur_model_block_order(jur_model_t *m, int *out, long cap) {
+  if (!m || m->n_blk_order <= 0) return 0;
+  long const n = m->n_blk_order < cap ? m->n_blk_order : cap;
+  if (hipSetDevice(m->device) != hipSuccess || (m->have_done && hipEventSynchronize(m->ev_done) != hipSuccess) ||
+      (out && n > 0 && hipMemcpy(out, m->d_blk_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)) {
+    (void)hipGetLastError();
+    jur_set_error("block order: read-back failed");
+    return JUR_EHIP;
+  }
+  return m->n_blk_order;
+}
 int jur_model_set_compact_workspace(jur_model_t *m, int on) { m->compact_ws = on ? 1 : 0; return JUR_OK; }
 
 int jur_model_set_sort_rays(jur_model_t *m, int on) { m->sort_rays = on ? 1 : 0; return JUR_OK; }
@@ -643,6 +658,19 @@ int jur_model_set_pencil(jur_model_t *m, long max_rays, int rays_per_group) {
 
 void jur_tune_trace(int lanes_per_ray) { jurk_tune_trace(lanes_per_ray); }
 void jur_tune_trace_slice(int mode) { jurk_tune_trace_slice(mode); }
+static int g_block_order = 0;          /* 0: by launch (see formod_device_body), 1: never, 2: whenever the rays were sorted */
+void jur_tune_block_order(int mode) { g_block_order = (mode == 1 || mode == 2) ? mode : 0; }
+/* ... or, where nothing has been set, JUR_BLOCK_ORDER (A/B switch, read once); JUR_BLOCK_ORDER_COMBINE=0 keeps the
+ * radiance update in order (the ray tracer's share on its own) */
+static int g_block_order_env = -1, g_block_order_combine = 1;
+static int block_order_mode(void) {
+  if (g_block_order_env < 0) {
+    g_block_order_combine = getenv("JUR_BLOCK_ORDER_COMBINE") ? atoi(getenv("JUR_BLOCK_ORDER_COMBINE")) != 0 : 1;
+    int const e = getenv("JUR_BLOCK_ORDER") ? atoi(getenv("JUR_BLOCK_ORDER")) : 0;
+    g_block_order_env = (e == 1 || e == 2) ? e : 0;
+  }
+  return g_block_order ? g_block_order : g_block_order_env;
+}
 
 void jur_tune_combine(int channels_per_group, int sync_segments, long min_lanes) {
   jurk_tune_combine(channels_per_group, sync_segments, min_lanes);
@@ -714,8 +742,10 @@ static int ensure_sort_buffers(jur_model_t *m, long nr) {
   if (nr > m->order_cap || need > m->sort_tmp_bytes) {
     if (m->d_order) (void)hipFree(m->d_order);
     if (m->d_sort_tmp) (void)hipFree(m->d_sort_tmp);
-    m->d_order = NULL; m->d_sort_tmp = NULL; m->order_cap = 0; m->sort_tmp_bytes = 0;
+    if (m->d_blk_order) (void)hipFree(m->d_blk_order);
+    m->d_order = NULL; m->d_sort_tmp = NULL; m->d_blk_order = NULL; m->order_cap = 0; m->sort_tmp_bytes = 0;
     HIPCHK(hipMalloc((void **)&m->d_order, sizeof(int) * (size_t)nr));
+    HIPCHK(hipMalloc((void **)&m->d_blk_order, sizeof(int) * (size_t)((nr + 255) / 256)));
     HIPCHK(hipMalloc(&m->d_sort_tmp, (size_t)need));
     m->order_cap = nr; m->sort_tmp_bytes = need;
   }
@@ -850,6 +880,21 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
     slice_sorted |= by_profile;
   }
   long const Rt = m->use_trace_rays;
+  /* Sorted slots ascend in tangent altitude within each profile, so a launch over them is a sawtooth of workgroup costs
+   * (a limb ray at 3 km has four times the points of one at 68 km), handed out in blockIdx order: it ends with the long
+   * workgroups of the last profiles on a mostly empty chip.  When the call is ONE trace launch, its blocks of 256 slots
+   * are ordered by the tangent altitude of their lowest ray and the ray tracer and the radiance update start them in
+   * that order, longest first.  By default for launches the size of the slice tracer's (262 144 rays): below that the
+   * chip is not filled several times over and the second sort is not paid for. */
+  int const *blk_order = NULL;
+  m->n_blk_order = 0;
+  int const bo_mode = block_order_mode();
+  if (order && nr <= Rt && bo_mode != 1 && (bo_mode == 2 || nr >= 4096L * 64)) {
+    int const e = jurk_block_order(nr, m->d_blk_order, m->d_sort_tmp, m->sort_tmp_bytes, s);
+    if (e) { jur_set_error("block order failed: %s", hipGetErrorString((hipError_t)e)); return JUR_EHIP; }
+    blk_order = m->d_blk_order;
+    m->n_blk_order = (nr + 255) / 256;
+  }
   m->n_launch_ega = 0;
 #define TIMED(kind, launch, what)                                                              \
   do {                                                                                         \
@@ -879,7 +924,9 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
     c.np = m->d_np;
     c.tsurf = m->d_tsurf;
     c.los = m->d_los;
+    c.blk_order = blk_order;                          /* (set only where the call is this one launch) */
     TIMED(0, jurk_launch_trace(&m->view, &c, s), "trace");
+    c.blk_order = NULL;
     if (m->host_call) {
       /* host entry: the input radiances, which only the epilogue reads (NaN mask), are uploaded beside the first
        * ray-tracing launch; tangent points and point counts are final after the last one and are copied out
@@ -949,7 +996,10 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
       c.los = m->d_los + (size_t)s0 * JUR_NLOS * m->nfield;   /* tiles of 64 slots, [tile][point][field][64]: s0 is a multiple of 64 */
       TIMED(1, jurk_launch_ega(&m->view, &c, s), "ega");
       if (co) TIMED(4, jurk_launch_contrib(&m->view, &c, nr, co->rad, co->tau, s), "contribution");
+      /* the radiance update takes the trace launch's block order where it covers the same slots */
+      if (blk_order && g_block_order_combine && s0 == 0 && c.n == nt) c.blk_order = blk_order;
       TIMED(2, jurk_launch_combine(&m->view, &c, s), "combine");
+      c.blk_order = NULL;
       m->n_launch_ega++;
     }
   }
@@ -2918,7 +2968,7 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
   c->view.atm_np = 0;
   c->d_los = NULL; c->d_eps = NULL; c->d_np = NULL; c->d_tsurf = NULL; c->d_status = NULL;
   c->los_bytes = 0; c->ws_rays = 0; c->ws_trace_rays = 0;
-  c->d_order = NULL; c->d_sort_tmp = NULL; c->order_cap = 0; c->sort_tmp_bytes = 0;
+  c->d_order = NULL; c->d_sort_tmp = NULL; c->d_blk_order = NULL; c->order_cap = 0; c->sort_tmp_bytes = 0; c->n_blk_order = 0;
   c->d_io = NULL; c->d_io_np = NULL; c->io_cap = 0;
   c->h_io = NULL; c->h_io_cap = 0; c->h_pkg = NULL; c->h_atm = NULL; c->h_atm_n = 0; c->h_atm_cap = 0; c->h_status = NULL;
   c->stream = NULL; c->stream2 = NULL; c->ev_mask = NULL; c->ev_trace = NULL;

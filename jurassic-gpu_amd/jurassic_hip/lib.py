@@ -97,6 +97,11 @@ def lib():
         if hasattr(L, "jur_tune_trace_slice"):       # (an older build selected with JURASSIC_HIP_SO for an A/B run has none)
             L.jur_tune_trace_slice.argtypes = [C.c_int]
             L.jur_tune_trace_slice.restype = None
+        if hasattr(L, "jur_tune_block_order"):       # (likewise)
+            L.jur_tune_block_order.argtypes = [C.c_int]
+            L.jur_tune_block_order.restype = None
+            L.jur_model_block_order.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_long]
+            L.jur_model_block_order.restype = C.c_long
         L.jur_state_size.restype = C.c_size_t
         L.jur_state_size.argtypes = [C.c_void_p, C.c_void_p]
         L.jur_measurement_size.restype = C.c_size_t
@@ -289,6 +294,16 @@ class Model:
 
     def set_trace_multiple(self, mult):
         _chk(lib().jur_model_set_trace_multiple(self.h, mult))
+
+    def block_order(self):
+        """The block order of the last batched call (jur_model_block_order): an int32 array, empty if it built none."""
+        n = lib().jur_model_block_order(self.h, None, 0)
+        if n < 0:
+            _chk(int(n))
+        out = np.zeros(max(n, 0), dtype=np.int32)
+        if n > 0 and lib().jur_model_block_order(self.h, out.ctypes.data_as(C.POINTER(C.c_int)), n) != n:
+            raise RuntimeError("jur_model_block_order: the order changed between two reads")
+        return out
 
     def set_workspace_budget(self, nbytes):
         _chk(lib().jur_model_set_workspace_budget(self.h, nbytes))
@@ -963,6 +978,12 @@ def tune_trace(lanes_per_ray=0):
 def tune_trace_slice(mode=0):
     """Process-wide: profile slice of the batched ray tracer in LDS (0: chosen per launch, 1: never, 2: wherever it fits)."""
     lib().jur_tune_trace_slice(mode)
+
+
+def tune_block_order(mode=0):
+    """Process-wide: longest blocks of a sorted launch first (0: chosen per call, 1: never, 2: whenever the rays were sorted
+    and the call is one trace launch)."""
+    lib().jur_tune_block_order(mode)
 
 
 def tune_combine(channels_per_group=4, sync_segments=8, min_lanes=1_000_000):
