@@ -393,6 +393,56 @@ int  jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, 
                              double const *y, double const *weight, jur_retrieve_in_t const *in,
                              jur_retrieve_out_t const *out, long max_rays_per_pass);
 
+/* Posterior diagnostics of the slices: covariance, averaging kernel, degrees of freedom, errors, on the device.
+ * One system (slice s, width w), with r = prior_ivar (all 0 without a prior): D_i = A_ii + r_i, element i live when
+ * D_i > 0 (anything else, NaN included, is dead) -- the solve's rule; on the live elements M = A + diag(r) = L L^T, the
+ * solve's M at lam = 0 (no damping).  Only the diagonal and the lower triangle of A_s are read.
+ *   S = M^-1              posterior covariance, [w][w], full, its two triangles bit-identical
+ *   AVK = S A             averaging kernel, [w][w], row i the response of retrieved element i (a product, not
+ *                         I - S diag(r))
+ *   avk_diag_i = AVK_ii;  dofs[s] = sum_i AVK_ii
+ *   sigma_i = sqrt(S_ii);  sigma_noise_i = sqrt(max(sum_j AVK_ij S_ji, 0)), the diagonal of S A S;
+ *   sigma_smooth_i = sqrt(sum_j S_ij^2 r_j), the diagonal of S diag(r) S
+ * A dead element has its row and column of S and AVK +0.0, its sigmas and avk_diag +0.0, and adds nothing to dofs.  A
+ * pivot that is not > 0 gives status[s] = 1 + its column as in the solve; every output of that system is +0.0 then and
+ * no other system is affected.  Otherwise status[s] = 0.  A system of width 0 writes dofs = 0, status = 0.
+ * Every double of a system depends on its own inputs and on w alone: not on the number or the order of the systems of
+ *   the call, not on which of the two entries was called, not on max_rays_per_pass, not on whether S or avk were asked
+ *   for.  No atomics; every sum runs in an order fixed by w.
+ * jur_diag_out_t: sigma, sigma_noise, sigma_smooth, avk_diag [wptr[nslice]] and dofs, status [nslice] are required; S
+ *   and avk are optional, [aptr[nslice]] each, laid out as A_s.  The caller owns all of them.
+ * jur_diagnose_slices_host: systems the caller holds, laid out as for jur_solve_slices_host and under its contract (the
+ *   model supplies device and stream; its atmosphere and workspace are not touched; nslice == 0 is JUR_OK and writes
+ *   nothing).
+ * jur_diagnose_scene_host: jur_normal_scene_host on `atm` -- the same doubles out, the same refusals; A, b, cost, nlive
+ *   and k may each be NULL and then never leave the device -- followed by the diagnostics on the accumulators where they
+ *   lie.  The layout is that of jur_scene_slices of the same rays.  Meant to be called once on the atm_ret of
+ *   jur_retrieve_scene_host, with that call's prior_ivar.  The model holds `atm` afterwards.
+ * JUR_EINVAL with a message naming the slice or the element: a required output that is NULL; wptr that does not ascend;
+ *   a prior_ivar that is negative or not finite.  JUR_ENOMEM (jur_diagnose_scene_host, before anything is launched) when
+ *   the factor, S, AVK and the vectors do not fit beside the normal matrices and the stacked slices in half the
+ *   workspace budget.  JUR_EHIP when a launch fails.  The kernels' time counts into jur_model_last_scene_ms.
+ * jur_avk_summary (host arithmetic, no GPU): what is read off one slice's averaging kernel avk [w][w], with the elements
+ *   of jur_scene_elements(ctl, atm, first, len, ...), quantity iq and point ip each:
+ *   dofs_q[q] = sum of AVK_ii over the elements of quantity q (2 + ng + nw entries);
+ *   area_i = sum_j AVK_ij over the j of i's quantity, ascending (near 1: the measurement drives the element);
+ *   resolution_i = dz_i / AVK_ii, dz_i half the altitude distance between the neighbouring retrieved points of i's
+ *   quantity in the slice, the full distance to the one neighbour at either end, 0 for a lone element; +inf where AVK_ii
+ *   is not > 0.  JUR_EINVAL for a slice outside the atmosphere or a NULL argument. */
+typedef struct {
+  double *sigma, *sigma_noise, *sigma_smooth, *avk_diag;  /* [wptr[nslice]] each, required */
+  double *dofs; int *status;                              /* [nslice], required */
+  double *S, *avk;                                        /* optional, [aptr[nslice]] each, laid out as A_s */
+} jur_diag_out_t;
+int  jur_diagnose_slices_host(jur_model_t *m, long nslice, long const *wptr, double const *A,
+                              double const *prior_ivar /* or NULL */, jur_diag_out_t const *out);
+int  jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                             double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                             double const *prior_ivar, jur_diag_out_t const *out,
+                             double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass);
+int  jur_avk_summary(ctl_t const *ctl, atm_t const *atm, int first, int len, double const *avk /* [w][w] */,
+                     double *dofs_q /* [2 + ng + nw] */, double *area /* [w] */, double *resolution /* [w] */);
+
 /* Curtis-Godson means along each line of sight (reference curtis_godson(), jr_common.h:455-473, which
  * upstream compiles only with -DCURTIS_GODSON for FORMOD=1): per ray, emitter and LOS point the
  * column-weighted pressure cgp, temperature cgt and the cumulative column cgu.  Host arrays

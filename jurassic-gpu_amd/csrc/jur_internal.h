@@ -235,6 +235,33 @@ typedef struct {
 } jur_scene_solve_t;
 int jurk_scene_solve(jur_scene_solve_t const *a, void *stream);
 
+/* Posterior diagnostics of a scene (jur_diagnose_slices_host, jur_diagnose_scene_host), after jurk_scene_solve with
+ * lam = 0 and a zero right-hand side has left L_s in `L`, D_i in `live` and the breakdowns in `status`.  All arrays are
+ * device memory.  S and avk are always formed: what the caller did not ask for stays on the device. */
+typedef struct {
+  long nslice;
+  long const *wptr, *aptr;      /* [nslice + 1] running sums of w_s and of w_s^2                             */
+  double const *A;              /* [aptr[nslice]] read only: diagonal and lower triangle of A_s              */
+  double const *prior_ivar;     /* [wptr[nslice]] or NULL                                                   */
+  double const *L;              /* [aptr[nslice]] the factors                                               */
+  double const *live;           /* [wptr[nslice]] D_i of a live element, 0 of a dead one                     */
+  int const *status;            /* [nslice] 0, or 1 + the column of the breakdown                            */
+  int const *imap;              /* [ninv][2] column block -> (system, first column), 16 columns a block       */
+  int const *tmap;              /* [ntile][3] output tile -> (system, first row, first column), 64 x 64       */
+  double *S, *avk;              /* [aptr[nslice]] each, written                                             */
+  double *sigma, *sigma_noise, *sigma_smooth, *avk_diag;   /* [wptr[nslice]] each, written                   */
+  double *dofs;                 /* [nslice] written                                                         */
+} jur_scene_diag_t;
+/* S, then AVK, then the vectors: four launches in stream order (nb = wptr[nslice]; the block counts are the host's) */
+int jurk_scene_diag(jur_scene_diag_t const *a, long ninv, long ntile, long nb, void *stream);
+enum { JUR_DIAG_NB = 16, JUR_DIAG_TILE = 64 };
+/* host arithmetic of the diagnostics (jur_scene.c; no GPU): the refusals, and the two block maps of jur_scene_diag_t
+ * (either may be NULL: a first call counts).  jur_diag_maps returns the number of column blocks and sets *ntile. */
+int jur_diag_check_out(char const *who, jur_diag_out_t const *out);
+int jur_diag_check_wptr(char const *who, long nslice, long const *wptr);
+int jur_diag_check_prior(char const *who, long nslice, long const *wptr, double const *prior_ivar);
+long jur_diag_maps(long nslice, long const *wptr, int *imap, int *tmap, long *ntile);
+
 /* Trial states of a scene (jur_trial_scene_host, jur_retrieve_scene_host): the state elements of the slices where they
  * lie in the base rows, and ntrial candidate steps of each.  The trial atmosphere is stacked like the Jacobian's: copy 0
  * the base, copy 1 + s * ntrial + t the points of slice s with all its elements moved by dx[t].  All arrays are device

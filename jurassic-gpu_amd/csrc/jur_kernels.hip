@@ -2803,6 +2803,209 @@ __global__ __launch_bounds__(256) void jur_scene_solve_kernel(jur_scene_solve_t 
   if (tid == 0) { a.pred[s] = red[0]; a.status[s] = 0; }
 }
 
+// ---- posterior diagnostics of a scene (jur_diagnose_slices_host, jur_diagnose_scene_host) ---------------------------
+// S = M^-1 from the factor jur_scene_solve_kernel left (lam = 0): L Y = I, then L^T S = Y.  One workgroup per block of 16
+// columns (c0 ...) of one system, so a wide system spreads over w / 16 workgroups that share nothing.  Column j of Y is
+// zero above row j and rows i >= j of column j of S need only the rows below them, so the workgroup works on the rows
+// >= c0 alone, in place in its 16 columns of S: the lower triangle is what is computed, and it is mirrored at the end
+// (the rows above c0 of these columns receive the mirror images of the workgroups to the left and are never read here).
+// Both substitutions go by blocks of 16 rows: lane (tr, tc) carries element (k0 + tr, c0 + tc) of the block's right-hand
+// side as a chain of fused multiply-adds over the rows already solved, ascending, staged through LDS 64 at a time (LT: L,
+// YT: the solved rows), then the 16 x 16 diagonal block of L is taken to LDS (T) and lane c < 16 substitutes column c
+// of the block (true divisions).  Every chain is fixed by w and the column alone.  A dead element is an identity row and
+// column of L; its row and column of S, the diagonal included, are set to +0.0 at the end.  A system that broke down
+// (status != 0, L all zeros) gets +0.0 throughout.  LDS: 21 KB.
+#define DIAG_NB 16
+#define DIAG_KC 64
+__global__ __launch_bounds__(256) void jur_scene_inverse_kernel(jur_scene_diag_t a) {
+  __shared__ double T[DIAG_NB][DIAG_NB + 1], X[DIAG_NB][DIAG_NB + 1];
+  __shared__ double LT[DIAG_KC][DIAG_NB + 1], YT[DIAG_KC][DIAG_NB + 1];
+  long const s = a.imap[2 * (long)blockIdx.x];
+  int const c0 = a.imap[2 * (long)blockIdx.x + 1];
+  int const tid = threadIdx.x, tr = tid >> 4, tc = tid & 15, w = (int)(a.wptr[s + 1] - a.wptr[s]);
+  int const nc = min(DIAG_NB, w - c0);
+  double const *const L = a.L + a.aptr[s], *const lv = a.live + a.wptr[s];
+  double *const S = a.S + a.aptr[s];
+  if (a.status[s] != 0) {                                   // (uniform)
+    for (long e = tid; e < (long)w * DIAG_NB; e += 256) {
+      int const i = (int)(e >> 4), c = (int)(e & 15);
+      if (c < nc) S[(long)i * w + c0 + c] = 0.;
+    }
+    return;
+  }
+
+  // L Y = I, from the block of the diagonal downwards
+  for (int k0 = c0; k0 < w; k0 += DIAG_NB) {
+    int const nb = min(DIAG_NB, w - k0);
+    double acc = (k0 == c0 && tr == tc) ? 1. : 0.;
+    for (int kk = c0; kk < k0; kk += DIAG_KC) {
+      int const kn = min(DIAG_KC, k0 - kk);                 // (a multiple of 16)
+      for (int e = tid; e < DIAG_NB * DIAG_KC; e += 256) {
+        int const r = e >> 6, k = e & 63;
+        LT[k][r] = (r < nb && k < kn) ? L[(long)(k0 + r) * w + kk + k] : 0.;
+      }
+      for (int e = tid; e < DIAG_NB * DIAG_KC; e += 256) {
+        int const k = e >> 4, c = e & 15;
+        YT[k][c] = (k < kn && c < nc) ? S[(long)(kk + k) * w + c0 + c] : 0.;
+      }
+      __syncthreads();
+#pragma unroll 16
+      for (int k = 0; k < kn; k++) acc = fma(-LT[k][tr], YT[k][tc], acc);
+      __syncthreads();
+    }
+    if (tr < nb && tc <= tr) T[tr][tc] = L[(long)(k0 + tr) * w + k0 + tc];
+    X[tr][tc] = acc;
+    __syncthreads();
+    if (tid < nc)
+      for (int r = 0; r < nb; r++) {
+        double v = X[r][tid];
+        for (int k = 0; k < r; k++) v = fma(-T[r][k], X[k][tid], v);
+        X[r][tid] = v / T[r][r];
+      }
+    __syncthreads();
+    if (tr < nb && tc < nc) S[(long)(k0 + tr) * w + c0 + tc] = X[tr][tc];
+    __syncthreads();
+  }
+
+  // L^T S = Y, from the last block upwards to the block of the diagonal
+  for (int k0 = ((w - 1) / DIAG_NB) * DIAG_NB; k0 >= c0; k0 -= DIAG_NB) {
+    int const nb = min(DIAG_NB, w - k0);
+    double acc = (tr < nb && tc < nc) ? S[(long)(k0 + tr) * w + c0 + tc] : 0.;
+    for (int kk = k0 + DIAG_NB; kk < w; kk += DIAG_KC) {
+      int const kn = min(DIAG_KC, w - kk);
+      for (int e = tid; e < DIAG_NB * DIAG_KC; e += 256) {
+        int const k = e >> 4, c = e & 15;
+        bool const in = k < kn;
+        LT[k][c] = in ? L[(long)(kk + k) * w + k0 + c] : 0.;   // (rows below exist: the block k0 is a full one)
+        YT[k][c] = (in && c < nc) ? S[(long)(kk + k) * w + c0 + c] : 0.;
+      }
+      __syncthreads();
+      for (int k = 0; k < kn; k++) acc = fma(-LT[k][tr], YT[k][tc], acc);
+      __syncthreads();
+    }
+    if (tr < nb && tc <= tr) T[tr][tc] = L[(long)(k0 + tr) * w + k0 + tc];
+    X[tr][tc] = acc;
+    __syncthreads();
+    if (tid < nc)
+      for (int r = nb - 1; r >= 0; r--) {
+        double v = X[r][tid];
+        for (int k = r + 1; k < nb; k++) v = fma(-T[k][r], X[k][tid], v);
+        X[r][tid] = v / T[r][r];
+      }
+    __syncthreads();
+    if (tr < nb && tc < nc) S[(long)(k0 + tr) * w + c0 + tc] = X[tr][tc];
+    __syncthreads();
+  }
+
+  // the dead elements, and the mirror image of what lies below the diagonal
+  for (long e = tid; e < (long)(w - c0) * DIAG_NB; e += 256) {
+    int const i = c0 + (int)(e >> 4), j = c0 + (int)(e & 15);
+    if (j >= w || i < j) continue;
+    double v = S[(long)i * w + j];
+    if (!(lv[i] > 0) || !(lv[j] > 0)) { v = 0.; S[(long)i * w + j] = v; }
+    if (i > j) S[(long)j * w + i] = v;
+  }
+}
+
+// AVK = S A.  One workgroup per 64 x 64 tile of one system's AVK; lane (tr, tc) holds the 4 x 4 micro-tile of the
+// elements (i0 + tr + 16 p, j0 + tc + 16 q) and carries each as one chain of fused multiply-adds over k = 0 .. w - 1,
+// ascending (padded with exact zeros to a multiple of 16), the operands staged through LDS 16 values of k at a time: SI
+// the tile's rows of S, AJ its columns of A.  Of A only the diagonal and the lower triangle are read (A_kj from
+// A[max][min]), and an entry in the row or column of a dead element counts as 0, whatever the caller left there.  The
+// rows and columns of dead elements, and a system that broke down, are written as +0.0.  LDS: 17 KB.
+#define DIAG_TILE 64
+__global__ __launch_bounds__(256) void jur_scene_avk_kernel(jur_scene_diag_t a) {
+  __shared__ double SI[DIAG_NB][DIAG_TILE + 1], AJ[DIAG_NB][DIAG_TILE + 1];
+  long const s = a.tmap[3 * (long)blockIdx.x];
+  int const i0 = a.tmap[3 * (long)blockIdx.x + 1], j0 = a.tmap[3 * (long)blockIdx.x + 2];
+  int const tid = threadIdx.x, tr = tid >> 4, tc = tid & 15, w = (int)(a.wptr[s + 1] - a.wptr[s]);
+  double const *const A = a.A + a.aptr[s], *const S = a.S + a.aptr[s], *const lv = a.live + a.wptr[s];
+  double *const K = a.avk + a.aptr[s];
+  bool const bad = a.status[s] != 0;                        // (uniform)
+  double acc[4][4];
+#pragma unroll
+  for (int p = 0; p < 4; p++)
+#pragma unroll
+    for (int q = 0; q < 4; q++) acc[p][q] = 0.;
+  for (int k0 = 0; k0 < w && !bad; k0 += DIAG_NB) {
+    for (int e = tid; e < DIAG_NB * DIAG_TILE; e += 256) {
+      int const rr = e >> 4, kk = e & 15, i = i0 + rr, k = k0 + kk;
+      SI[kk][rr] = (i < w && k < w) ? S[(long)i * w + k] : 0.;
+    }
+    for (int e = tid; e < DIAG_NB * DIAG_TILE; e += 256) {
+      int const kk = e >> 6, cc = e & 63, k = k0 + kk, j = j0 + cc;
+      double v = 0.;
+      if (k < w && j < w && lv[k] > 0 && lv[j] > 0) v = k >= j ? A[(long)k * w + j] : A[(long)j * w + k];
+      AJ[kk][cc] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < DIAG_NB; k++) {
+      double si[4], aj[4];
+#pragma unroll
+      for (int p = 0; p < 4; p++) { si[p] = SI[k][tr + 16 * p]; aj[p] = AJ[k][tc + 16 * p]; }
+#pragma unroll
+      for (int p = 0; p < 4; p++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[p][q] = fma(si[p], aj[q], acc[p][q]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int p = 0; p < 4; p++)
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      int const i = i0 + tr + 16 * p, j = j0 + tc + 16 * q;
+      if (i < w && j < w) K[(long)i * w + j] = (bad || !(lv[i] > 0) || !(lv[j] > 0)) ? 0. : acc[p][q];
+    }
+}
+
+// The vectors, one wavefront per element e = (system s, row i): avk_diag = AVK_ii, sigma = sqrt(S_ii), and the two sums
+// over the row, sum_j AVK_ij S_ij (S_ji has the same bits) and sum_j S_ij^2 r_j: lane l takes j = l, l + 64, ... ascending
+// as a chain of fused multiply-adds, then a fixed tree runs over the 64 lanes.  No LDS, no barrier.
+__global__ __launch_bounds__(256) void jur_scene_diag_rows_kernel(jur_scene_diag_t a) {
+  long const nb = a.wptr[a.nslice], e = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= nb) return;                                      // (uniform in the wavefront)
+  int const lane = threadIdx.x & 63;
+  long const s = scene_find<false>(a.wptr, 0, a.nslice, e);
+  int const w = (int)(a.wptr[s + 1] - a.wptr[s]), i = (int)(e - a.wptr[s]);
+  double const *const Si = a.S + a.aptr[s] + (long)i * w, *const Ki = a.avk + a.aptr[s] + (long)i * w;
+  double const *const r = a.prior_ivar ? a.prior_ivar + a.wptr[s] : nullptr;
+  double noise = 0., smooth = 0.;
+  for (int j = lane; j < w; j += 64) {
+    double const sij = Si[j];
+    noise = fma(Ki[j], sij, noise);
+    if (r) smooth = fma(sij * sij, r[j], smooth);
+  }
+  for (int h = 32; h > 0; h >>= 1) {
+    noise += __shfl_down(noise, h, 64);
+    smooth += __shfl_down(smooth, h, 64);
+  }
+  if (lane == 0) {
+    a.avk_diag[e] = Ki[i];
+    a.sigma[e] = sqrt(Si[i]);
+    a.sigma_noise[e] = sqrt(noise > 0 ? noise : 0.);
+    a.sigma_smooth[e] = sqrt(smooth);
+  }
+}
+
+// dofs[s] = sum_i AVK_ii, one workgroup per system: every lane its elements ascending, then a fixed tree over the lanes
+__global__ __launch_bounds__(256) void jur_scene_dofs_kernel(jur_scene_diag_t a) {
+  __shared__ double red[256];
+  long const s = blockIdx.x;
+  int const tid = threadIdx.x, w = (int)(a.wptr[s + 1] - a.wptr[s]);
+  double const *const d = a.avk_diag + a.wptr[s];
+  double sum = 0.;
+  for (int i = tid; i < w; i += 256) sum += d[i];
+  red[tid] = sum;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) a.dofs[s] = red[0];
+}
+
 // ---- trial states of a scene (jur_trial_scene_host, jur_retrieve_scene_host) -----------------------------------------
 // One lane per state element e of slice s (JUR_ELEM_APPLY: per trial t and element).  The value of element e is
 // base[erow[e]][eip[e]]; its place in trial copy 1 + s * ntrial + t is the same row at off[copy] + (eip[e] - sfirst[s]).
@@ -2963,6 +3166,17 @@ extern "C" int jurk_scene_normal(jur_scene_pass_t const *a, jur_scene_normal_t c
 extern "C" int jurk_scene_solve(jur_scene_solve_t const *a, void *stream) {
   if (a->nslice <= 0) return 0;
   hipLaunchKernelGGL(jur_scene_solve_kernel, dim3((unsigned)a->nslice), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+// (the maps and wptr are device memory: the host passes the block counts and nb = wptr[nslice])
+extern "C" int jurk_scene_diag(jur_scene_diag_t const *a, long ninv, long ntile, long nb, void *stream) {
+  if (a->nslice <= 0) return 0;
+  hipStream_t const s = (hipStream_t)stream;
+  if (ninv > 0) hipLaunchKernelGGL(jur_scene_inverse_kernel, dim3((unsigned)ninv), dim3(256), 0, s, *a);
+  if (ntile > 0) hipLaunchKernelGGL(jur_scene_avk_kernel, dim3((unsigned)ntile), dim3(256), 0, s, *a);
+  if (nb > 0) hipLaunchKernelGGL(jur_scene_diag_rows_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, *a);
+  hipLaunchKernelGGL(jur_scene_dofs_kernel, dim3((unsigned)a->nslice), dim3(256), 0, s, *a);
   return (int)hipGetLastError();
 }
 

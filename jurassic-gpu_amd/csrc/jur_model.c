@@ -1861,6 +1861,76 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
   return JUR_OK;
 }
 
+/* ---- posterior diagnostics of the slices (jur_diagnose_slices_host, jur_diagnose_scene_host) ------------------------ */
+/* what jur_diagnose_scene_host adds to jur_normal_scene_host */
+typedef struct { double const *prior_ivar; jur_diag_out_t const *out; } scene_diag_t;
+
+/* doubles of device memory the diagnostics need beside A: L | S | AVK, then live | z | zeros (the solve's b and
+ * prior_dx) | prior_ivar, the four vectors, lam (zeros) | pred | dofs, and the ints status | imap | tmap (rounded up) */
+static size_t diag_doubles(size_t na, size_t nb, size_t ns, int prior, size_t ninv, size_t ntile) {
+  return 3 * na + 3 * nb + (prior ? nb : 0) + 4 * nb + 3 * ns + (ns + 2 * ninv + 3 * ntile + 1) / 2;
+}
+
+/* Enqueues on s: the uploads of the prior and the block maps (hmap: imap | tmap), the factorisation by the solve kernel
+ * (lam = 0, zero right-hand side, zero prior_dx), the inverse, the product and the vectors, the copies home.  The caller
+ * waits for the stream before the host arrays go. */
+static int diag_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nslice, long na, long nb, long const *d_wptr,
+                        long const *d_aptr, double const *d_A, double *W, double const *prior_ivar, jur_diag_out_t const *out,
+                        long ninv, long ntile, int const *hmap) {
+  size_t const NA = (size_t)na, NB = (size_t)nb, NS = (size_t)nslice, npr = prior_ivar ? NB : 0;
+  double *const dL = W, *const dS = dL + NA, *const dK = dS + NA, *const dlive = dK + NA, *const dz = dlive + NB, *const dzero = dz + NB,
+         *const dr = dzero + NB, *const dvec = dr + npr, *const dlam = dvec + 4 * NB, *const dpred = dlam + NS, *const ddofs = dpred + NS;
+  int *const dstat = (int *)(ddofs + NS), *const dimap = dstat + NS, *const dtmap = dimap + 2 * (size_t)ninv;
+  hipError_t e = hipMemsetAsync(dlam, 0, sizeof(double) * NS, s);
+  if (NB && e == hipSuccess) e = hipMemsetAsync(dzero, 0, sizeof(double) * NB, s);
+  if (npr && e == hipSuccess) e = hipMemcpyAsync(dr, prior_ivar, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+  if (ninv + ntile > 0 && e == hipSuccess)
+    e = hipMemcpyAsync(dimap, hmap, sizeof(int) * (2 * (size_t)ninv + 3 * (size_t)ntile), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
+  jur_scene_solve_t q;
+  memset(&q, 0, sizeof q);
+  q.nslice = nslice; q.wptr = d_wptr; q.aptr = d_aptr; q.A = d_A; q.b = dzero;
+  q.prior_ivar = npr ? dr : NULL; q.prior_dx = npr ? dzero : NULL; q.mode = JUR_DAMP_MARQUARDT;
+  q.M = dL; q.live = dlive; q.lam = dlam; q.dx = dz; q.pred = dpred; q.status = dstat;
+  jur_scene_diag_t d;
+  memset(&d, 0, sizeof d);
+  d.nslice = nslice; d.wptr = d_wptr; d.aptr = d_aptr; d.A = d_A; d.prior_ivar = npr ? dr : NULL;
+  d.L = dL; d.live = dlive; d.status = dstat; d.imap = dimap; d.tmap = dtmap; d.S = dS; d.avk = dK;
+  d.sigma = dvec; d.sigma_noise = dvec + NB; d.sigma_smooth = dvec + 2 * NB; d.avk_diag = dvec + 3 * NB; d.dofs = ddofs;
+  int const ti = scene_timed_begin(m, s);
+  int ek = jurk_scene_solve(&q, s);
+  if (!ek) ek = jurk_scene_diag(&d, ninv, ntile, nb, s);
+  scene_timed_end(m, ti, s);
+  if (ek) { jur_set_error("%s: diagnostics kernel launch failed", who); return JUR_EHIP; }
+  if (NB) {
+    e = hipMemcpyAsync(out->sigma, d.sigma, sizeof(double) * NB, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out->sigma_noise, d.sigma_noise, sizeof(double) * NB, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out->sigma_smooth, d.sigma_smooth, sizeof(double) * NB, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out->avk_diag, d.avk_diag, sizeof(double) * NB, hipMemcpyDeviceToHost, s);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out->dofs, ddofs, sizeof(double) * NS, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(out->status, dstat, sizeof(int) * NS, hipMemcpyDeviceToHost, s);
+  if (NA && out->S && e == hipSuccess) e = hipMemcpyAsync(out->S, dS, sizeof(double) * NA, hipMemcpyDeviceToHost, s);
+  if (NA && out->avk && e == hipSuccess) e = hipMemcpyAsync(out->avk, dK, sizeof(double) * NA, hipMemcpyDeviceToHost, s);
+  if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
+  return JUR_OK;
+}
+
+/* the block maps of nslice systems in one malloc'ed array imap | tmap (NULL with JUR_OK where there is no block) */
+static int diag_maps_make(char const *who, long nslice, long const *wptr, long *ninv, long *ntile, int **hmap) {
+  *hmap = NULL;
+  *ninv = jur_diag_maps(nslice, wptr, NULL, NULL, ntile);
+  if (*ninv > 0x7fffffffL || *ntile > 0x7fffffffL || wptr[nslice] / 4 >= 0x7fffffffL) {
+    jur_set_error("%s: 2^31 blocks: call with fewer systems at a time", who);
+    return JUR_EINVAL;
+  }
+  if (*ninv == 0) return JUR_OK;
+  *hmap = (int *)malloc(sizeof(int) * (2 * (size_t)*ninv + 3 * (size_t)*ntile));
+  if (!*hmap) { jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
+  (void)jur_diag_maps(nslice, wptr, *hmap, *hmap + 2 * *ninv, NULL);
+  return JUR_OK;
+}
+
 /* ---- trial states and the retrieval loop (jur_trial_scene_host, jur_retrieve_scene_host) ----------------------------- */
 /* Host image of what the trial kernels index by: two blocks, each uploaded with one copy.
  * longs: wptr[ns + 1] | off[ncopy + 1] | sptr[ns + 1];  ints: cdesc[3 ncopy] (first | prow = -1 | pip = 0 of every copy,
@@ -2067,11 +2137,12 @@ typedef struct { jur_retrieve_in_t const *in; jur_retrieve_out_t const *out; atm
  * then) the systems are solved where they lie after the last pass, and A and b go home only where they are given. */
 static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                              double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
-                             scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt) {
-  char const *const who = rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+                             scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt, scene_diag_t const *dg) {
+  char const *const who = rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
   if (rt) { int const rs = retrieve_check_args(who, rt->in, rt->out); if (rs) return rs; }
+  if (dg) { int const rs = jur_diag_check_out(who, dg->out); if (rs) return rs; }
   ctl_t const *ctl = m->ctl;
   if (ctl->hydz >= 0) {
     jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so every p, T or H2O element moves "
@@ -2099,8 +2170,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   long *off = NULL, *pass = NULL, *scopy = NULL, *nptr = NULL;
   int *cdesc = NULL, *iqa = NULL, *ipa = NULL;
   double *hbase = NULL, *rd = NULL;
-  int *ri = NULL, *hact = NULL;
-  long *hcomp = NULL;
+  int *ri = NULL, *hact = NULL, *dmap = NULL;
+  long *hcomp = NULL, ninv = 0, ndtile = 0;
   atm_t *ret_atm = NULL;
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
@@ -2165,7 +2236,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   long nlist = 0, ntiles = 0, na = 0, nb = 0;
   long *sptr = NULL, *tptr = NULL, *wptr = NULL, *aptr = NULL;
   if (nm && nslice > 0) {
-    if ((!sv && (!nm->A || !nm->b)) || !nm->cost || !nm->nlive) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
+    if ((!sv && !dg && (!nm->A || !nm->b)) || (!dg && (!nm->cost || !nm->nlive))) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
     nptr = (long *)calloc(4 * ((size_t)nslice + 1), sizeof(long));
     srays = (int *)malloc(sizeof(int) * NR);
     if (!nptr || !srays) { rc = JUR_ENOMEM; goto done; }
@@ -2184,6 +2255,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     nlist = sptr[nslice]; ntiles = tptr[nslice]; na = aptr[nslice]; nb = wptr[nslice];
     if (ntiles > 0x7fffffffL) { jur_set_error("%s: 2^31 tiles: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
     if (sv && !rt && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
+    if (dg && (rc = jur_diag_check_prior(who, nslice, wptr, dg->prior_ivar))) goto done;
+    if (dg && (rc = diag_maps_make(who, nslice, wptr, &ninv, &ndtile, &dmap))) goto done;
     if (rt) {
       if (rt->in->prior_ivar && (rc = prior_check_values(who, nslice, wptr, rt->in->prior_ivar, rt->in->prior_xa))) goto done;
       /* one atmosphere is the state of all slices only where no point lies in two of them */
@@ -2211,6 +2284,9 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   /* ... and the solve: one more copy of the matrices, the vectors of one damping, the outputs of all */
   size_t const nsv = (sv && ntiles) ? solve_doubles((size_t)na, (size_t)nb, (size_t)nslice, (size_t)sv->in->nlam, sv->in->prior_ivar != NULL) : 0;
   size_t const sv_bytes = sizeof(double) * nsv;
+  /* ... or the diagnostics: the factor, S, AVK and the vectors */
+  size_t const ndg = (dg && ntiles) ? diag_doubles((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, (size_t)ninv, (size_t)ndtile) : 0;
+  size_t const dg_bytes = sizeof(double) * ndg;
   long const ncopy = ncopies + 1;
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)nt;
   if (nt > 0x7fffffffL || (long)atm_bytes > m->ws_budget / 2) {
@@ -2228,6 +2304,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   if (sv_bytes > 0 && (double)atm_bytes + (double)acc_bytes + (double)sv_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the solver scratch (%zu bytes) does not fit beside the normal matrices (%ld doubles) and the stacked "
                   "atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, sv_bytes, na, atm_bytes);
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+  if (dg_bytes > 0 && (double)atm_bytes + (double)acc_bytes + (double)dg_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("%s: the factor, S, AVK and the vectors (%zu bytes) do not fit beside the normal matrices (%ld doubles) and the "
+                  "stacked atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, dg_bytes, na, atm_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
@@ -2257,7 +2339,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
      * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
      * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
-    long const avail = (m->ws_budget - (long)atm_bytes - (long)acc_bytes - (long)sv_bytes) / 16;
+    long const avail = (m->ws_budget - (long)atm_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes) / 16;
     cap = avail / (long)slot_bytes;
     if (cap < 4096) cap = 4096;
   }
@@ -2310,7 +2392,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   /* (the normal equations' part, empty without them: y, weight, the accumulators A | b | cost | nlive in one piece,
    * then sptr | tptr | wptr | aptr, then what the solve needs) */
   size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
-               o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_rt = o_sv + nsv, o_int = o_rt + rt_dbl + rt_lng;
+               o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_dg = o_sv + nsv, o_rt = o_dg + ndg, o_int = o_rt + rt_dbl + rt_lng;
   size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int;   /* (the loop's ints follow the others) */
   size_t const bytes = sizeof(double) * o_int + sizeof(int) * nint;
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
@@ -2543,6 +2625,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     }
     if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out,
                                    looping ? d_state : NULL))) goto done;
+    if (ndg && (rc = diag_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, D + o_dg, dg->prior_ivar, dg->out, ninv, ndtile, dmap))) goto done;
     if (!looping) break;
 
     /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
@@ -2639,8 +2722,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (ntiles && !rt) {                          /* the sums go home here, once */
       if (nm->A && e == hipSuccess) e = hipMemcpyAsync(nm->A, nq.A, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, s);
       if (nm->b && e == hipSuccess) e = hipMemcpyAsync(nm->b, nq.b, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(nm->cost, nq.cost, sizeof(double) * (size_t)nslice, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(nm->nlive, nq.nlive, sizeof(long) * (size_t)nslice, hipMemcpyDeviceToHost, s);
+      if (nm->cost && e == hipSuccess) e = hipMemcpyAsync(nm->cost, nq.cost, sizeof(double) * (size_t)nslice, hipMemcpyDeviceToHost, s);
+      if (nm->nlive && e == hipSuccess) e = hipMemcpyAsync(nm->nlive, nq.nlive, sizeof(long) * (size_t)nslice, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
@@ -2650,7 +2733,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
   free(first); free(rp); free(sid); free(srays); free(sl); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa);
-  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm);
+  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm); free(dmap);
   trial_plan_free(&pl);
   return rc;
 }
@@ -2670,7 +2753,7 @@ static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
 int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                           double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL, NULL));
 }
 
 int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -2678,7 +2761,7 @@ int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double cons
                           double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_normal_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, NULL));
 }
 
 int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -2688,7 +2771,17 @@ int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const 
   if (!m || !atm) { jur_set_error("jur_step_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_solve_t const sv = {in, out};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL, NULL));
+}
+
+int jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                            double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                            double const *prior_ivar, jur_diag_out_t const *out,
+                            double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
+  if (!m || !atm) { jur_set_error("jur_diagnose_scene_host: null argument"); return JUR_EINVAL; }
+  scene_normal_t const nm = {y, weight, A, b, cost, nlive};
+  scene_diag_t const dg = {prior_ivar, out};
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg));
 }
 
 int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, long nr, double const *const geom[7],
@@ -2698,7 +2791,7 @@ int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, l
   if (!m || !atm0 || !atm_ret) { jur_set_error("jur_retrieve_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, NULL, NULL, NULL, NULL};
   scene_retrieve_t const rt = {in, out, atm_ret};
-  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt);
+  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt, NULL);
   if (rc) return scene_restore_atm(m, atm0, rc);    /* (on success the model holds atm_ret) */
   if (nr != 0) return JUR_OK;
   if (atm_ret != atm0) memcpy(atm_ret, atm0, sizeof(atm_t));   /* no rays: nothing was retrieved */
@@ -2931,6 +3024,60 @@ int jur_solve_slices_host(jur_model_t *m, long nslice, long const *wptr, double 
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
   free(ptr);
+  return rc;
+}
+
+/* Systems the caller holds, as jur_solve_slices_host: wptr | aptr, A, then the diagnostics' part of the slab. */
+int jur_diagnose_slices_host(jur_model_t *m, long nslice, long const *wptr, double const *A, double const *prior_ivar,
+                             jur_diag_out_t const *out) {
+  char const *const who = "jur_diagnose_slices_host";
+  if (!m || nslice < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  int rc = jur_diag_check_out(who, out);
+  if (rc) return rc;
+  if (nslice == 0) return JUR_OK;
+  if (nslice > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 systems per call", who); return JUR_EINVAL; }
+  if (!wptr) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if ((rc = jur_diag_check_wptr(who, nslice, wptr))) return rc;
+  if (wptr[nslice] > 0 && !A) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if ((rc = jur_diag_check_prior(who, nslice, wptr, prior_ivar))) return rc;
+  size_t const NS = (size_t)nslice;
+  long *ptr = (long *)malloc(sizeof(long) * 2 * (NS + 1)), *aptr = ptr ? ptr + NS + 1 : NULL;
+  int *hmap = NULL;
+  long ninv = 0, ntile = 0;
+  if (!ptr) return JUR_ENOMEM;
+  int enqueued = 0;
+  memcpy(ptr, wptr, sizeof(long) * (NS + 1));
+  aptr[0] = 0;
+  for (long q = 0; q < nslice; q++) { long const w = wptr[q + 1] - wptr[q]; aptr[q + 1] = aptr[q] + w * w; }
+  if ((rc = diag_maps_make(who, nslice, wptr, &ninv, &ntile, &hmap))) goto done;
+  {
+    long const na = aptr[nslice], nb = wptr[nslice];
+    size_t const o_A = 2 * (NS + 1), o_dg = o_A + (size_t)na;
+    size_t const bytes = sizeof(double) * (o_dg + diag_doubles((size_t)na, (size_t)nb, NS, prior_ivar != NULL, (size_t)ninv, (size_t)ntile));
+    if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
+    hipStream_t const s = m->stream;
+    if ((rc = wait_done(m, s))) goto done;
+    if (bytes > m->scene_bytes) {
+      if (m->d_scene) (void)hipFree(m->d_scene);
+      m->d_scene = NULL; m->scene_bytes = 0;
+      if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
+        (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
+      }
+      m->scene_bytes = bytes;
+    }
+    double *const D = (double *)m->d_scene;
+    long *const L = (long *)m->d_scene;
+    enqueued = 1;
+    hipError_t e = hipMemcpyAsync(L, ptr, sizeof(long) * 2 * (NS + 1), hipMemcpyHostToDevice, s);
+    if (na && e == hipSuccess) e = hipMemcpyAsync(D + o_A, A, sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if ((rc = diag_enqueue(m, s, who, nslice, na, nb, L, L + NS + 1, D + o_A, D + o_dg, prior_ivar, out, ninv, ntile, hmap))) goto done;
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
+  }
+done:
+  if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
+  free(ptr); free(hmap);
   return rc;
 }
 

@@ -1,6 +1,7 @@
 /* jur_scene.c -- layout of the block Jacobian of a scene (jur_kernel_scene_host) and of its normal equations
  * (jur_normal_scene_host): which slice of the atmosphere every ray is traced through, which state elements lie in it
  * and which distinct slices a scene has.  Host arithmetic only: no GPU, no model. */
+#include <math.h>
 #include <stdlib.h>
 #include "jur_internal.h"
 
@@ -206,4 +207,89 @@ long jur_scene_slices(ctl_t const *ctl, atm_t const *atm, long nr, double const 
 done:
   free(first); free(rp); free(sl);
   return n;
+}
+
+/* ---- posterior diagnostics (jur_diagnose_slices_host, jur_diagnose_scene_host): the host arithmetic ------------------ */
+int jur_diag_check_out(char const *who, jur_diag_out_t const *out) {
+  if (!out) { jur_set_error("%s: null argument (out)", who); return JUR_EINVAL; }
+  char const *const missing = !out->sigma ? "sigma" : !out->sigma_noise ? "sigma_noise" : !out->sigma_smooth ? "sigma_smooth"
+                            : !out->avk_diag ? "avk_diag" : !out->dofs ? "dofs" : !out->status ? "status" : NULL;
+  if (missing) { jur_set_error("%s: null argument (%s)", who, missing); return JUR_EINVAL; }
+  return JUR_OK;
+}
+
+int jur_diag_check_wptr(char const *who, long nslice, long const *wptr) {
+  if (nslice < 0 || (nslice > 0 && !wptr)) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  for (long q = 0; q < nslice; q++) {
+    long const w = wptr[q + 1] - wptr[q];
+    if (wptr[0] != 0 || w < 0 || w > 0x7fffffffL) {
+      jur_set_error("%s: wptr is not an ascending running sum of widths from 0 (slice %ld)", who, q);
+      return JUR_EINVAL;
+    }
+  }
+  return JUR_OK;
+}
+
+int jur_diag_check_prior(char const *who, long nslice, long const *wptr, double const *prior_ivar) {
+  if (!prior_ivar) return JUR_OK;
+  for (long q = 0; q < nslice; q++)
+    for (long e = wptr[q]; e < wptr[q + 1]; e++) {
+      double const r = prior_ivar[e];
+      if (!(r >= 0) || r > 1.7976931348623157e308) {
+        jur_set_error("%s: prior_ivar of slice %ld, element %ld is %g: negative or not finite", who, q, e - wptr[q], r);
+        return JUR_EINVAL;
+      }
+    }
+  return JUR_OK;
+}
+
+/* Block b of the inverse is columns [c0, c0 + 16) of system s: imap[2 b] = s, imap[2 b + 1] = c0, systems ascending and
+ * columns ascending within a system.  Tile t of the product is rows [i0, i0 + 64) x columns [j0, j0 + 64) of system s:
+ * tmap[3 t] = s, then i0, j0, row-major within a system.  A system of width 0 has neither. */
+long jur_diag_maps(long nslice, long const *wptr, int *imap, int *tmap, long *ntile) {
+  long ninv = 0, nt = 0;
+  for (long q = 0; q < nslice; q++) {
+    long const w = wptr[q + 1] - wptr[q];
+    for (long c0 = 0; c0 < w; c0 += JUR_DIAG_NB, ninv++)
+      if (imap) { imap[2 * ninv] = (int)q; imap[2 * ninv + 1] = (int)c0; }
+    for (long i0 = 0; i0 < w; i0 += JUR_DIAG_TILE)
+      for (long j0 = 0; j0 < w; j0 += JUR_DIAG_TILE, nt++)
+        if (tmap) { tmap[3 * nt] = (int)q; tmap[3 * nt + 1] = (int)i0; tmap[3 * nt + 2] = (int)j0; }
+  }
+  if (ntile) *ntile = nt;
+  return ninv;
+}
+
+int jur_avk_summary(ctl_t const *ctl, atm_t const *atm, int first, int len, double const *avk, double *dofs_q, double *area,
+                    double *resolution) {
+  if (!ctl || !atm || first < 0 || len < 0 || (long)first + len > atm->np) {
+    jur_set_error("jur_avk_summary: slice [%d, %d + %d) outside the atmosphere", first, first, len);
+    return JUR_EINVAL;
+  }
+  if (!dofs_q) { jur_set_error("jur_avk_summary: null argument (dofs_q)"); return JUR_EINVAL; }
+  int const nquant = 2 + ctl->ng + ctl->nw;
+  for (int q = 0; q < nquant; q++) dofs_q[q] = 0.;
+  long const w = jur_scene_slice_elements(ctl, atm, first, len, NULL, NULL, NULL);
+  if (w == 0) return JUR_OK;
+  if (!avk || !area || !resolution) { jur_set_error("jur_avk_summary: null argument"); return JUR_EINVAL; }
+  int *iq = (int *)malloc(sizeof(int) * 2 * (size_t)w), *ip = iq ? iq + w : NULL;
+  if (!iq) { jur_set_error("jur_avk_summary: out of memory"); return JUR_ENOMEM; }
+  (void)jur_scene_slice_elements(ctl, atm, first, len, NULL, iq, ip);
+  /* the elements of one quantity are contiguous, their points ascending */
+  for (long i = 0; i < w; i++) {
+    double const d = avk[(size_t)i * (size_t)w + (size_t)i];
+    dofs_q[iq[i]] += d;
+    double sum = 0.;
+    for (long j = 0; j < w; j++)
+      if (iq[j] == iq[i]) sum += avk[(size_t)i * (size_t)w + (size_t)j];
+    area[i] = sum;
+    int const below = i > 0 && iq[i - 1] == iq[i], above = i + 1 < w && iq[i + 1] == iq[i];
+    double dz = 0.;
+    if (below && above) dz = fabs(atm->z[ip[i + 1]] - atm->z[ip[i - 1]]) / 2;
+    else if (above) dz = fabs(atm->z[ip[i + 1]] - atm->z[ip[i]]);
+    else if (below) dz = fabs(atm->z[ip[i]] - atm->z[ip[i - 1]]);
+    resolution[i] = d > 0 ? dz / d : INFINITY;
+  }
+  free(iq);
+  return JUR_OK;
 }

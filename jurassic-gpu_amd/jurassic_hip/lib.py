@@ -123,6 +123,11 @@ def lib():
         L.jur_solve_slices_host.argtypes = [C.c_void_p, C.c_long, lp_, dp, dp, C.c_void_p, C.c_void_p]
         L.jur_step_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
                                           dp, dp, C.c_void_p, C.c_void_p, dp, dp, dp, lp_, dp, C.c_long]
+        if hasattr(L, "jur_diagnose_slices_host"):   # (likewise)
+            L.jur_diagnose_slices_host.argtypes = [C.c_void_p, C.c_long, lp_, dp, dp, C.c_void_p]
+            L.jur_diagnose_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
+                                                  dp, dp, dp, C.c_void_p, dp, dp, dp, lp_, dp, C.c_long]
+            L.jur_avk_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, dp, dp, dp, dp]
         L.jur_trial_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, lp_, dp, dp, C.c_int, dp, dp, dp,
                                            dp, dp, C.c_long]
         L.jur_retrieve_decide.argtypes = [C.c_int, C.c_long, C.c_double, C.c_double, C.c_double, dp, dp, dp, ip_, dp, ip_, ip_, ip_]
@@ -601,6 +606,53 @@ class Model:
                                          C.byref(sout)))
         return res
 
+    def diagnose_slices(self, wptr, A, prior_ivar=None, want_S=False, want_avk=False):
+        """Posterior diagnostics of systems the caller holds (jur_diagnose_slices_host).  wptr, A: as solve_slices;
+        prior_ivar (n,) or None: the inverse a-priori variances.  No damping: M = A + diag(prior_ivar).
+        -> dict(sigma, sigma_noise, sigma_smooth, avk_diag (n,), dofs, status (nslice,)) and, where wanted, the flat S
+        (posterior covariance) and avk (averaging kernel S A), laid out as A."""
+        wp = np.ascontiguousarray(wptr, dtype=np.int64)
+        ns = len(wp) - 1
+        n, na = int(wp[-1]), int((np.diff(wp) ** 2).sum())
+        AA = np.ascontiguousarray(A, dtype=np.float64).ravel()
+        if AA.size != na:
+            raise ValueError("A must hold %d doubles" % na)
+        dout, res, keep = _diag_structs(ns, n, na, prior_ivar, want_S, want_avk)
+        _chk(lib().jur_diagnose_slices_host(self.h, ns, wp.ctypes.data_as(C.POINTER(C.c_long)), _p(AA),
+                                            None if keep is None else _p(keep), C.byref(dout)))
+        return res
+
+    def diagnose_scene(self, atm, geom, y, weight, prior_ivar=None, want_S=False, want_avk=False, want_normal=False,
+                       want_k=False, rad_in=None, max_rays_per_pass=0, rowptr=None):
+        """Posterior diagnostics of every slice of a scene (jur_diagnose_scene_host): normal_scene on atm followed by
+        the diagnostics on the device; meant for the atm of retrieve_scene's result, with that call's prior_ivar.
+        -> normal_scene's dict without A and b, plus diagnose_slices' dict laid out by scene_slices of these rays.
+        want_normal: also A and b; want_k: also the blocks.  What is not wanted never leaves the device."""
+        g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, rowptr)
+        nr, nd = g.shape[1], self.nd
+        tau = np.zeros((nr, nd))
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        ns, n, na = len(lay["sfirst"]), int(lay["wptr"][-1]), int(lay["aptr"][-1])
+        cost, nlive = np.zeros(ns), np.zeros(ns, dtype=np.int64)
+        A, b = (np.zeros(na), np.zeros(n)) if want_normal else (None, None)
+        k = np.zeros(int(lay["rowptr"][-1]) * nd) if want_k else None
+        dout, res, keep = _diag_structs(ns, n, na, prior_ivar, want_S, want_avk)
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
+        lp_ = C.POINTER(C.c_long)
+        _chk(lib().jur_diagnose_scene_host(self.h, C.byref(atm), nr, garr, _p(rad), _p(tau), tarr,
+                                           npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(lp_), _p(yy), _p(ww),
+                                           None if keep is None else _p(keep), C.byref(dout),
+                                           _p(A) if want_normal else None, _p(b) if want_normal else None, _p(cost),
+                                           nlive.ctypes.data_as(lp_), _p(k) if want_k else None, max_rays_per_pass))
+        out = dict(lay, rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, cost=cost, nlive=nlive, **res)
+        if want_normal:
+            out.update(A=A, b=b)
+        if want_k:
+            out["k"] = k
+        return out
+
     def scene_ms(self):
         """The share of kernel_scene's own kernels in the launches timed since the last call (call kernel_ms first)."""
         ms, n = C.c_double(0), C.c_long(0)
@@ -698,6 +750,12 @@ class SolveOut(C.Structure):
     _fields_ = [("dx", dp), ("pred", dp), ("status", C.POINTER(C.c_int)), ("L", dp)]
 
 
+class DiagOut(C.Structure):
+    """jur_diag_out_t"""
+    _fields_ = [("sigma", dp), ("sigma_noise", dp), ("sigma_smooth", dp), ("avk_diag", dp), ("dofs", dp),
+                ("status", C.POINTER(C.c_int)), ("S", dp), ("avk", dp)]
+
+
 RET_ACTIVE, RET_CONVERGED, RET_STALLED, RET_MAXITER = 0, 1, 2, 3      # JUR_RET_*
 
 
@@ -761,6 +819,38 @@ def _solve_structs(ns, n, na, lam, mode, prior_ivar, prior_dx, want_factor):
     sout = SolveOut(_p(res["dx"]), _p(res["pred"]), res["status"].ctypes.data_as(C.POINTER(C.c_int)),
                     _p(res["L"]) if want_factor else None)
     return sin, sout, res, (lm, pri)
+
+
+def _diag_structs(ns, n, na, prior_ivar, want_S, want_avk):
+    """(jur_diag_out_t, the result dict, prior_ivar as the array to keep alive or None) of ns systems with n elements
+    and na matrix entries in all.  Nothing is refused here that the library refuses."""
+    pri = None if prior_ivar is None else np.ascontiguousarray(prior_ivar, dtype=np.float64).ravel()
+    if pri is not None and pri.size != n:
+        raise ValueError("prior_ivar must hold %d doubles" % n)
+    res = dict(sigma=np.zeros(n), sigma_noise=np.zeros(n), sigma_smooth=np.zeros(n), avk_diag=np.zeros(n),
+               dofs=np.zeros(ns), status=np.zeros(ns, dtype=np.int32))
+    if want_S:
+        res["S"] = np.zeros(na)
+    if want_avk:
+        res["avk"] = np.zeros(na)
+    dout = DiagOut(_p(res["sigma"]), _p(res["sigma_noise"]), _p(res["sigma_smooth"]), _p(res["avk_diag"]), _p(res["dofs"]),
+                   res["status"].ctypes.data_as(C.POINTER(C.c_int)), _p(res["S"]) if want_S else None,
+                   _p(res["avk"]) if want_avk else None)
+    return dout, res, pri
+
+
+def avk_summary(ctl, atm, first, length, avk):
+    """jur_avk_summary (host arithmetic, no GPU): what is read off the averaging kernel avk (w, w) of the slice
+    [first, first + length) -> dict(dofs_q (2 + ng + nw,): the trace per quantity; area (w,): the row sums within the
+    element's quantity; resolution (w,): dz / AVK_ii, +inf where AVK_ii is not > 0; iq, ip: scene_elements')."""
+    el = scene_elements(ctl, atm, first, length)
+    w = len(el["iq"])
+    K = np.ascontiguousarray(avk, dtype=np.float64)
+    if K.size != w * w:
+        raise ValueError("avk must be (%d, %d)" % (w, w))
+    dofs_q, area, res = np.zeros(2 + ctl.ng + ctl.nw), np.zeros(w), np.zeros(w)
+    _chk(lib().jur_avk_summary(C.byref(ctl), C.byref(atm), int(first), int(length), _p(K), _p(dofs_q), _p(area), _p(res)))
+    return dict(dofs_q=dofs_q, area=area, resolution=res, iq=el["iq"], ip=el["ip"])
 
 
 def solve_slices(model, wptr, A, b, lam, **kw):
