@@ -125,7 +125,9 @@ int  jur_model_set_atm(jur_model_t *m, atm_t const *atm);
  * obslat, vpz, vplon, vplat}, each [nr].  rad/tau are [nr][nd] (nd = ctl->nd,
  * channel fastest); rad is read first: channels that hold a non-finite value
  * on input come back NaN (jr_common.h:193-210).  tp[3] = {tpz, tplon, tplat},
- * each [nr].  np_out (optional) receives the number of LOS points per ray. */
+ * each [nr].  np_out (optional) receives the number of LOS points per ray.
+ * Pencil beams: a shape set with jur_model_set_fov is not applied by this entry, jur_formod_device, the contribution
+ * entries or the drop-ins; their caller applies jur_fov_apply / jur_fov_apply_device. */
 int  jur_formod_host(jur_model_t *m, long nr, double const *const geom[7],
                      double *rad, double *tau, double *const tp[3], int *np_out);
 
@@ -202,7 +204,9 @@ int  jur_formod_device_multi(jur_model_t *const models[], int nmodel, long nr, l
  * obs returns the unperturbed result.  The reference's signature takes a gsl_matrix;
  * bind with k = matrix->data when matrix->tda == matrix->size2.
  * The model holds `atm` afterwards (as after jur_model_set_atm) -- after an error return (JUR_ENLOS, ...) too; if
- * that upload fails, it holds no atmosphere and refuses the next call. */
+ * that upload fails, it holds no atmosphere and refuses the next call.
+ * jur_kernel and kernel() difference pencil beams: a shape set with jur_model_set_fov is not applied; the caller applies
+ * jur_fov_apply to the columns there (or uses the scene entries, which honour it). */
 size_t jur_state_size(jur_model_t const *m, atm_t const *atm);
 size_t jur_measurement_size(jur_model_t const *m, obs_t const *obs);
 int    jur_kernel(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, size_t mrows, size_t ncols);
@@ -463,6 +467,41 @@ int  jur_fov_apply(int nd, long nr, double const *time, double const *vpz, doubl
  * arrays.  Returns after the work on `stream` has finished; JUR_EINVAL if a ray is alone in its scan. */
 int  jur_fov_apply_device(jur_model_t *m, long nr, double const *d_time, double const *d_vpz, double *d_rad,
                           double *d_tau, int n, double const *dz, double const *w, void *stream);
+
+/* The field of view inside the scene entries.  A limb sounder's radiance is the forward model of a tangent-height scan
+ * convolved with the instrument's field of view; with a shape set in the model the six scene entries --
+ * jur_kernel_scene_host, jur_normal_scene_host, jur_step_scene_host, jur_trial_scene_host, jur_retrieve_scene_host and
+ * jur_diagnose_scene_host -- apply that convolution on the device between the forward model and everything that reads
+ * its radiances.  Nothing else honours the shape: jur_formod_*, jur_kernel, kernel(), the contribution entries and the
+ * drop-ins compute pencil beams as before, and their caller applies jur_fov_apply / jur_fov_apply_device.
+ *
+ * jur_model_set_fov: n weights w at altitude offsets dz (what jur_fov_read_shape reads from the file ctl->fov names),
+ *   kept on host and device; n == 0 switches the convolution off (the default: the scene entries then compute the bits
+ *   and launch the kernels they did before).  JUR_EINVAL, naming the entry: n outside 0..JUR_NSHAPE; a dz or w that is
+ *   not finite; weights whose sum in ascending order is 0 or not finite.
+ * jur_model_fov: what is set; dz and w (room for JUR_NSHAPE each) may be NULL.
+ * jur_scene_fov_live (host arithmetic, no GPU): the rule the device follows.  A scan is a maximal run of consecutive rays
+ *   of the call with equal time stamps; the window of ray ir is the rays ir2 of [ir - JUR_NFOV, ir + JUR_NFOV] with
+ *   time[ir2] == time[ir] (formod_fov's window).  JUR_EINVAL, naming the ray: a time stamp that occurs in two separate
+ *   runs (the windows would change when the retrieval loop drops finished slices); a window of fewer than two rays
+ *   (upstream's "Cannot apply FOV convolution!").  Otherwise live[ir][id] ([nr][nd], may be NULL) is 1 exactly when
+ *   rad_in is finite in channel id on every ray of ir's window -- the effective mask, a superset of the channels where
+ *   the convolution can touch a NaN, and a function of the inputs alone -- and the number of live entries is returned.
+ * The scene entries while a shape is set:
+ *   rad and tau out are the doubles of jur_formod_host followed by jur_fov_apply(nd, nr, geom[0], geom[4], rad, tau, nd,
+ *   n, dz, w) on the call's rays in the caller's order (the input NaN mask applies to the pencil beams first; a NaN
+ *   spreads where jur_fov_apply spreads it); tp and np_out are unchanged.  Block entry (id, e) is (G1 - G0) / h with G0
+ *   that convolved radiance and G1 the same convolution of the forward model with element e raised: the quotient of
+ *   convolved radiances, as kernel() differences formod's output, with layout, rowptr and columns unchanged.  In the
+ *   sums and the costs F is G and "channel not masked on input" is the effective mask (a live measurement has a finite G;
+ *   a trial G that is not finite makes that one cost NaN).  A scan is never split between passes: a pass is extended to
+ *   the end of its scan, a scan beyond the cap goes alone, and no output depends on max_rays_per_pass.  What
+ *   jur_scene_fov_live refuses is JUR_EINVAL before anything is launched; the model holds atm (atm0) afterwards.  The
+ *   workspace accounting (JUR_ENOMEM) and the slots of a pass include the convolution's buffers.  The convolution kernel's
+ *   time counts into jur_model_last_scene_ms. */
+int  jur_model_set_fov(jur_model_t *m, int n, double const *dz, double const *w);
+int  jur_model_fov(jur_model_t const *m, int *n, double *dz, double *w);
+long jur_scene_fov_live(int nd, long nr, double const *time, double const *rad_in, unsigned char *live /* [nr][nd] or NULL */);
 
 /* intpol_atm with an error code instead of exit(): JUR_EINVAL for what upstream aborts on (profiles of one point,
  * profiles more than 10 degrees apart, unknown IP).  One lane per destination point on `device`. */

@@ -196,6 +196,8 @@ typedef struct {
   double *out_rad, *out_tau;    /* [nr][nd] unperturbed results by ray, written                            */
   double *out_tp;               /* [3][nr]                                                                 */
   int *out_np;                  /* [nr]                                                                    */
+  double const *fov_tau;        /* [r1 - r0][nd] convolved transmittances of copy 0 by ray of the pass (a field of view is
+                                   set: jurk_scene_fov), or NULL: out_tau is gathered from tau                */
 } jur_scene_pass_t;
 
 int jurk_scene_stack(jur_scene_stack_t const *a, void *stream);
@@ -323,8 +325,31 @@ typedef struct {
   int const *first, *len, *copy0, *tcopy0; /* [nr]                                                          */
   double *geom_c, *rad_c, *y_c, *weight_c; /* [7][n], [n][nd] x 3                                            */
   int *first_c, *len_c, *copy0_c, *tcopy0_c;   /* [n]                                                        */
+  double const *live;           /* [nr][nd] effective mask of a field of view, or NULL                      */
+  double *live_c;               /* [n][nd]                                                                  */
 } jur_scene_compact_t;
 int jurk_scene_compact(jur_scene_compact_t const *a, void *stream);
+
+/* Field of view of the scene entries (jur_model_set_fov): the forward model's results of one pass, replicated as the
+ * pass lays them out, convolved out of place with the shape of the model.  Ray r of [r0, r1) owns `count` consecutive
+ * slots from `slot`, nd values each: with ntrial == 0 (a Jacobian pass) slot = (rowptr[r] - rowptr[r0]) + (r - r0) and
+ * count = width + 1, with ntrial >= 1 (a trial pass, or plain rays with ntrial == 1) slot = (r - r0) * ntrial and count =
+ * ntrial.  Value v of the ray's count * nd is convolved with value v of the rays of its window: those of [r - JUR_NFOV,
+ * r + JUR_NFOV] inside the pass with its time stamp (a scan lies in one pass and its rays have one width). */
+typedef struct {
+  long nr, r0, r1;
+  int nd, ntrial;
+  long const *rowptr;           /* [nr + 1] (ntrial == 0)                                                   */
+  double const *time, *vpz;     /* [nr] the caller's time stamps and view-point altitudes                   */
+  double const *rad;            /* [n][nd] the forward model's                                              */
+  double const *tau;            /* [n][nd], or NULL                                                         */
+  double *rad_f;                /* [n][nd] written                                                          */
+  double *tau_f;                /* [r1 - r0][nd] written where tau is given: the first nd values of every ray */
+  int n;                        /* points of the shape                                                      */
+  double const *dz, *w;         /* [n]                                                                      */
+  int *status;                  /* bit 1: a window of fewer than two rays                                   */
+} jur_scene_fov_t;
+int jurk_scene_fov(jur_scene_fov_t const *a, void *stream);
 
 /* host arithmetic shared by jur_model.c and jur_scene.c (not exported) */
 #define JUR_HIDDEN __attribute__((visibility("hidden")))

@@ -29,6 +29,7 @@
 //                         wavefronts hand the line of sight on through rings in LDS while it is being traced; the
 //                         same device functions as the three batched kernels, bit-identical results.
 //   jur_fov_kernel        field-of-view convolution of device arrays (formod_fov, jurassic.c:214-258).
+//   jur_scene_fov_kernel  the same convolution on the replicated rays of a pass of the scene entries, a workgroup per ray.
 //   jur_intpol_kernel     regridding of a track / point-cloud atmosphere (intpol_atm, jurassic.c:675-804).
 //   jur_kat_*_kernel      known-answer hooks for tests: the device functions on arrays of inputs.
 //
@@ -2528,10 +2529,81 @@ __global__ __launch_bounds__(256) void jur_scene_gather_kernel(jur_scene_pass_t 
   long const r = a.r0 + t / a.nd, id = t - (r - a.r0) * a.nd;
   long const s0 = scene_slot(a, r);
   a.out_rad[r * a.nd + id] = a.rad[s0 * a.nd + id];
-  a.out_tau[r * a.nd + id] = a.tau[s0 * a.nd + id];
+  a.out_tau[r * a.nd + id] = a.fov_tau ? a.fov_tau[t] : a.tau[s0 * a.nd + id];
   if (id == 0) {
     for (int q = 0; q < 3; q++) a.out_tp[q * a.nr + r] = a.tp[q * a.n + s0];
     a.out_np[r] = a.np[s0];
+  }
+}
+
+// ---- field of view of the scene entries (jur_model_set_fov) ----------------------------------------------------------
+// One workgroup per ray of the pass.  Lane 0 gathers the window (the rays of the pass within JUR_NFOV positions that carry
+// the ray's time stamp: view-point altitude and first value of each) into LDS; the points of the shape are then taken
+// FOV_CH at a time: lane k of a chunk finds the bracket of vpz + dz[k] with locate_axis and leaves idx, zfov - z[idx],
+// z[idx + 1] - z[idx] and w[k] in LDS, so that what is staged does not grow with the shape.  The lanes run over the
+// ray's contiguous values (copy or trial major, channel inside), 256 at a time, and every neighbour is read as one
+// coalesced stretch.  The arithmetic is jur_fov_kernel's, operand for operand and in its order (ascending k, one division
+// by the sum of the weights at the end), so that a value is bit for bit what jur_fov_apply makes of the same radiances.
+// A shape of more than FOV_CH points is staged again for every 256 values.  No atomics but the status word.
+#define FOV_CH 64
+__global__ __launch_bounds__(256) void jur_scene_fov_kernel(jur_scene_fov_t a) {
+  __shared__ double z[2 * JUR_NFOV + 1], dzl[FOV_CH], dzw[FOV_CH], wk[FOV_CH];
+  __shared__ long src[2 * JUR_NFOV + 1];
+  __shared__ int ix[FOV_CH], nzs;
+  long const r = a.r0 + blockIdx.x;
+  int const nd = a.nd, lane = threadIdx.x;
+  long const base = a.ntrial > 0 ? 0 : a.rowptr[a.r0];
+  if (lane == 0) {
+    int nz = 0;
+    long const lo = r - JUR_NFOV > a.r0 ? r - JUR_NFOV : a.r0, hi = r + 1 + JUR_NFOV < a.r1 ? r + 1 + JUR_NFOV : a.r1;
+    for (long r2 = lo; r2 < hi; r2++)
+      if (a.time[r2] == a.time[r]) {
+        z[nz] = a.vpz[r2];
+        src[nz] = (a.ntrial > 0 ? (r2 - a.r0) * a.ntrial : (a.rowptr[r2] - base) + (r2 - a.r0)) * nd;
+        nz++;
+      }
+    nzs = nz;
+  }
+  __syncthreads();
+  int const nz = nzs;
+  if (nz < 2) {                                             // (uniform) "Cannot apply FOV convolution!" upstream
+    if (lane == 0) atomicOr(a.status, 2);
+    return;
+  }
+  long const mine = (a.ntrial > 0 ? (r - a.r0) * a.ntrial : (a.rowptr[r] - base) + (r - a.r0)) * nd;
+  long const L = (a.ntrial > 0 ? (long)a.ntrial : a.rowptr[r + 1] - a.rowptr[r] + 1) * nd;
+  double const vz = a.vpz[r];
+  bool const restage = a.n > FOV_CH;
+  for (long v0 = 0; v0 < L; v0 += 256) {
+    long const v = v0 + lane;
+    bool const on = v < L, with_tau = a.tau && v < nd;
+    double rr = 0, tt = 0, wsum = 0;
+    for (int k0 = 0; k0 < a.n; k0 += FOV_CH) {
+      int const nk = a.n - k0 < FOV_CH ? a.n - k0 : FOV_CH;
+      if (restage || v0 == 0) {
+        __syncthreads();                                    // (the readers of the chunk before)
+        if (lane < nk) {
+          double const zfov = vz + a.dz[k0 + lane];
+          int const idx = locate_axis((double const *)z, nz, zfov);
+          ix[lane] = idx; dzl[lane] = zfov - z[idx]; dzw[lane] = z[idx + 1] - z[idx]; wk[lane] = a.w[k0 + lane];
+        }
+        __syncthreads();
+      }
+      if (on)
+        for (int k = 0; k < nk; k++) {
+          int const idx = ix[k];
+          double const w = wk[k], dl = dzl[k], dw = dzw[k];
+          double const r0 = a.rad[src[idx] + v], r1 = a.rad[src[idx + 1] + v];
+          rr += w * (r0 + dl * (r1 - r0) / dw);
+          if (with_tau) {
+            double const t0 = a.tau[src[idx] + v], t1 = a.tau[src[idx + 1] + v];
+            tt += w * (t0 + dl * (t1 - t0) / dw);
+          }
+          wsum += w;
+        }
+    }
+    if (on) a.rad_f[mine + v] = rr / wsum;
+    if (with_tau) a.tau_f[(r - a.r0) * nd + v] = tt / wsum;
   }
 }
 
@@ -3119,6 +3191,7 @@ __global__ __launch_bounds__(256) void jur_scene_compact_kernel(jur_scene_compac
     a.rad_c[i * a.nd + id] = a.rad[r * a.nd + id];
     a.y_c[i * a.nd + id] = a.y[r * a.nd + id];
     a.weight_c[i * a.nd + id] = a.weight[r * a.nd + id];
+    if (a.live) a.live_c[i * a.nd + id] = a.live[r * a.nd + id];
   }
   a.first_c[i] = a.first[r]; a.len_c[i] = a.len[r]; a.copy0_c[i] = a.copy0[r]; a.tcopy0_c[i] = a.tcopy0[r];
 }
@@ -3152,6 +3225,12 @@ extern "C" int jurk_scene_quot(jur_scene_pass_t const *a, long nk, void *stream)
   if (nk > 0) hipLaunchKernelGGL(jur_scene_quot_kernel, dim3(scene_grid(nk)), dim3(256), 0, (hipStream_t)stream, *a);
   if (a->r1 > a->r0)
     hipLaunchKernelGGL(jur_scene_gather_kernel, dim3(scene_grid((a->r1 - a->r0) * a->nd)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_fov(jur_scene_fov_t const *a, void *stream) {
+  if (a->r1 <= a->r0 || a->n < 1) return 0;
+  hipLaunchKernelGGL(jur_scene_fov_kernel, dim3((unsigned)(a->r1 - a->r0)), dim3(256), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

@@ -88,6 +88,10 @@ struct jur_model {
   /* field-of-view convolution of device arrays: grow-only scratch and its own status word */
   double *d_fov;
   long fov_cap;
+  /* field of view of the scene entries (jur_model_set_fov): the shape on the host and dz | w on the device */
+  int fov_n;
+  double *fov_shape;            /* dz[JUR_NSHAPE] | w[JUR_NSHAPE], malloc'ed with the first shape */
+  double *d_fov_shape;
   double *d_kq, *h_kq;          /* jur_kernel: perturbation steps and dense difference quotients (device, pinned host) */
   long kq_cap;
   /* small calls: the fused kernel (jur_pencil_kernel) instead of sort + three batched kernels */
@@ -307,7 +311,7 @@ void jur_model_destroy(jur_model_t *m) {
   (void)hipSetDevice(m->device);
   if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_rec = NULL;
   void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp, m->d_blk_order,
-                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_kq, m->d_ctb, m->d_scene};
+                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_fov_shape, m->d_kq, m->d_ctb, m->d_scene};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
   if (m->h_io) (void)hipHostFree(m->h_io);
@@ -315,6 +319,7 @@ void jur_model_destroy(jur_model_t *m) {
   if (m->h_kq) (void)hipHostFree(m->h_kq);
   if (m->h_status) (void)hipHostFree(m->h_status);
   free(m->h_atm);
+  free(m->fov_shape);
   if (m->stream) (void)hipStreamDestroy(m->stream);
   if (m->stream2) (void)hipStreamDestroy(m->stream2);
   if (m->ev_mask) (void)hipEventDestroy(m->ev_mask);
@@ -1460,6 +1465,79 @@ int jur_fov_apply_device(jur_model_t *m, long nr, double const *d_time, double c
   return rc;
 }
 
+/* ---- field of view of the scene entries ---------------------------------------------- */
+int jur_model_set_fov(jur_model_t *m, int n, double const *dz, double const *w) {
+  char const *const who = "jur_model_set_fov";
+  if (!m) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if (n < 0 || n > JUR_NSHAPE) { jur_set_error("%s: n = %d: 0 (off) to %d points", who, n, JUR_NSHAPE); return JUR_EINVAL; }
+  if (n == 0) { m->fov_n = 0; return JUR_OK; }
+  if (!dz || !w) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  double wsum = 0;
+  for (int k = 0; k < n; k++) {
+    if (!isfinite(dz[k]) || !isfinite(w[k])) {
+      jur_set_error("%s: point %d of the shape is (%g, %g): not finite", who, k, dz[k], w[k]);
+      return JUR_EINVAL;
+    }
+    wsum += w[k];
+  }
+  if (!isfinite(wsum) || wsum == 0) { jur_set_error("%s: the weights sum to %g: 0 or not finite", who, wsum); return JUR_EINVAL; }
+  HIPCHK(hipSetDevice(m->device));
+  if (!m->fov_shape && !(m->fov_shape = (double *)calloc(2 * (size_t)JUR_NSHAPE, sizeof(double)))) {
+    jur_set_error("%s: out of memory", who);
+    return JUR_ENOMEM;
+  }
+  if (!m->d_fov_shape) HIPCHK(hipMalloc((void **)&m->d_fov_shape, sizeof(double) * 2 * (size_t)JUR_NSHAPE));
+  /* (a scene entry waits for its stream before it returns: nothing reads the old shape any more) */
+  m->fov_n = 0;
+  memcpy(m->fov_shape, dz, sizeof(double) * (size_t)n);
+  memcpy(m->fov_shape + JUR_NSHAPE, w, sizeof(double) * (size_t)n);
+  HIPCHK(hipMemcpy(m->d_fov_shape, m->fov_shape, sizeof(double) * 2 * (size_t)JUR_NSHAPE, hipMemcpyHostToDevice));
+  m->fov_n = n;
+  return JUR_OK;
+}
+
+int jur_model_fov(jur_model_t const *m, int *n, double *dz, double *w) {
+  if (!m || !n) { jur_set_error("jur_model_fov: null argument"); return JUR_EINVAL; }
+  *n = m->fov_n;
+  if (dz && m->fov_n) memcpy(dz, m->fov_shape, sizeof(double) * (size_t)m->fov_n);
+  if (w && m->fov_n) memcpy(w, m->fov_shape + JUR_NSHAPE, sizeof(double) * (size_t)m->fov_n);
+  return JUR_OK;
+}
+
+/* The scene entries' part of the convolution.  The buffer the convolved radiances of a pass go to (nval doubles, the
+ * model's grow-only scratch of jur_fov_apply_device, which holds nothing between calls) ... */
+static int scene_fov_reserve(jur_model_t *m, size_t nval) {
+  if ((long)nval > m->fov_cap) {
+    if (m->d_fov) (void)hipFree(m->d_fov);
+    m->d_fov = NULL; m->fov_cap = 0;
+    HIPCHK(hipMalloc((void **)&m->d_fov, sizeof(double) * nval));
+    m->fov_cap = (long)nval;
+  }
+  return JUR_OK;
+}
+
+/* ... and the effective mask of the call as the doubles the kernels test: +0.0 where live, NaN elsewhere (malloc'ed);
+ * what jur_scene_fov_live refuses is refused in the entry's name */
+static int scene_fov_mask(char const *who, int nd, long nr, double const *time, double const *rad_in, double **out) {
+  size_t const n = (size_t)nr * (size_t)nd;
+  unsigned char *live = (unsigned char *)malloc(n ? n : 1);
+  double *mask = (double *)malloc(sizeof(double) * (n ? n : 1));
+  *out = NULL;
+  if (!live || !mask) { free(live); free(mask); jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
+  long const rc = jur_scene_fov_live(nd, nr, time, rad_in, live);
+  if (rc < 0) {
+    char msg[400];
+    snprintf(msg, sizeof msg, "%s", jur_last_error());
+    jur_set_error("%s: %s", who, msg);
+    free(live); free(mask);
+    return (int)rc;
+  }
+  for (size_t i = 0; i < n; i++) mask[i] = live[i] ? 0. : NAN;
+  free(live);
+  *out = mask;
+  return JUR_OK;
+}
+
 /* ---- known-answer hooks ----------------------------------------------------------- */
 /* nin input arrays and nout in/out arrays of n doubles each go to the device as one slab [nin + nout][n] */
 static int kat_slab(jur_model_t *m, long n, int nin, double const *const in[], int nout, double *const out[], double **d) {
@@ -1996,27 +2074,35 @@ static int trial_plan_make(trial_plan_t *p, char const *who, ctl_t const *ctl, a
   return JUR_OK;
 }
 
-/* contiguous ranges of rays whose ntrial slots each stay within cap; one ray beyond it goes alone.  Returns the number
- * of passes, *nmax the slots of the largest; pass has room for nr + 1 entries. */
-static long trial_passes(long nr, int ntrial, long cap, long *pass, long *nmax) {
+/* contiguous ranges of rays whose ntrial slots each stay within cap; one ray beyond it goes alone.  With `time` (the time
+ * stamps of the rays; a field of view is set) a pass is extended to the end of its last scan.  Returns the number of
+ * passes (-1 for a pass of 2^31 slots), *nmax the slots of the largest; pass has room for nr + 1 entries. */
+static long trial_passes(long nr, int ntrial, long cap, double const *time, long *pass, long *nmax) {
   long per = cap / ntrial, npass = 0;
   if (per < 1) per = 1;
   if (per > 0x7fffffffL / ntrial) per = 0x7fffffffL / ntrial;
-  for (long r0 = 0; r0 < nr; r0 += per) {
-    long const r1 = r0 + per < nr ? r0 + per : nr;
+  for (long r0 = 0; r0 < nr;) {
+    long r1 = r0 + per < nr ? r0 + per : nr;
+    while (time && r1 < nr && time[r1] == time[r1 - 1]) r1++;   /* (a field of view is set: to the end of the scan) */
+    if ((r1 - r0) * ntrial > 0x7fffffffL) return -1;
     if ((r1 - r0) * ntrial > *nmax) *nmax = (r1 - r0) * ntrial;
     pass[npass++] = r0;
+    r0 = r1;
   }
   pass[npass] = nr;
   return npass;
 }
+
+/* a field of view in a call: the kernel's arguments (shape, status word and the rays' time stamps and view-point altitudes
+ * are the call's; the pass fills in the rest) and the effective mask [rays][nd] on the device */
+typedef struct { jur_scene_fov_t k; double const *live; } scene_fov_t;
 
 /* One trial pass over the device: stacks the trial copies from the base rows (st->base), moves the elements by st->dx,
  * forms the prior terms (or zeroes them), traces the rays of every pass and continues the cost chains.  ps carries the
  * ray arrays of the call (or of its gathered rays); its r0, r1, n, geom, rad, atm_time and `above` are set here.  The
  * model's view is left on the trial atmosphere.  Nothing is waited for after the stacking. */
 static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, jur_scene_stack_t *sk, jur_scene_trial_t *st,
-                     jur_scene_trial_pass_t *ps, long nb, long npass, long const *pass, long nmax) {
+                     jur_scene_trial_pass_t *ps, long nb, long npass, long const *pass, long nmax, scene_fov_t *fv) {
   size_t const nrow = (size_t)sk->nrow;
   int const nd = ps->nd;
   int rc;
@@ -2050,8 +2136,18 @@ static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const
     scene_timed_end(m, ti, s);
     if (ek) { jur_set_error("%s: trial replication kernel launch failed", who); return JUR_EHIP; }
     if ((rc = jur_formod_device(m, n, ps->geom, ps->rad, tau, tp, m->d_io_np, m->d_status, s))) return rc;
+    jur_scene_trial_pass_t pf = *ps;
+    if (fv) {                                    /* the costs read the convolved radiances under the effective mask */
+      fv->k.r0 = ps->r0; fv->k.r1 = ps->r1; fv->k.ntrial = ps->ntrial; fv->k.rowptr = NULL;
+      fv->k.rad = ps->rad; fv->k.tau = NULL; fv->k.rad_f = m->d_fov; fv->k.tau_f = NULL;
+      ti = scene_timed_begin(m, s);
+      ek = jurk_scene_fov(&fv->k, s);
+      scene_timed_end(m, ti, s);
+      if (ek) { jur_set_error("%s: field-of-view kernel launch failed", who); return JUR_EHIP; }
+      pf.rad = m->d_fov; pf.in_rad = fv->live;
+    }
     ti = scene_timed_begin(m, s);
-    ek = jurk_scene_trial_cost(ps, s);
+    ek = jurk_scene_trial_cost(&pf, s);
     scene_timed_end(m, ti, s);
     if (ek) { jur_set_error("%s: trial cost kernel launch failed", who); return JUR_EHIP; }
   }
@@ -2111,13 +2207,15 @@ static int prior_check_values(char const *who, long nslice, long const *wptr, do
 }
 
 /* Passes of the Jacobian entries: contiguous ranges of the nr rays with row pointer rp whose slots (width + 1 each) stay
- * within cap; one ray beyond it goes alone.  pass has room for nr + 1 entries; *nmax and *kmax grow to the slots and the
+ * within cap; one ray beyond it goes alone; with `time` (the time stamps of the rays; a field of view is set) a pass is
+ * extended to the end of its last scan.  pass has room for nr + 1 entries; *nmax and *kmax grow to the slots and the
  * block columns of the largest pass.  Returns the number of passes, -1 for a pass of 2^31 slots. */
-static long scene_passes(long nr, long const *rp, long cap, long *pass, long *nmax, long *kmax) {
+static long scene_passes(long nr, long const *rp, long cap, double const *time, long *pass, long *nmax, long *kmax) {
   long npass = 0;
   for (long r0 = 0; r0 < nr;) {
     long r1 = r0 + 1;
     while (r1 < nr && (rp[r1 + 1] - rp[r0]) + (r1 + 1 - r0) <= cap) r1++;
+    while (time && r1 < nr && time[r1] == time[r1 - 1]) r1++;   /* (a field of view is set: to the end of the scan) */
     long const n = (rp[r1] - rp[r0]) + (r1 - r0);
     if (n > 0x7fffffffL) return -1;
     if (n > *nmax) *nmax = n;
@@ -2173,6 +2271,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   int *ri = NULL, *hact = NULL, *dmap = NULL;
   long *hcomp = NULL, ninv = 0, ndtile = 0;
   atm_t *ret_atm = NULL;
+  int const fov = m->fov_n > 0;                     /* a field of view is set: the radiances of every pass are convolved */
+  double *hlive = NULL, *htimec = NULL;
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if (!first || !rp || !sid) { rc = JUR_ENOMEM; goto done; }
@@ -2195,6 +2295,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         }
       }
   }
+
+  if (fov && (rc = scene_fov_mask(who, nd, nr, geom[0], rad, &hlive))) goto done;
 
   /* the distinct slices that have state elements, in the order the rays meet them, and their copies: slice q is
    * raised element by element by the copies scopy[q] ... */
@@ -2287,6 +2389,10 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   /* ... or the diagnostics: the factor, S, AVK and the vectors */
   size_t const ndg = (dg && ntiles) ? diag_doubles((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, (size_t)ninv, (size_t)ndtile) : 0;
   size_t const dg_bytes = sizeof(double) * ndg;
+  /* ... and a field of view: the effective mask and the convolved transmittances by ray; for the loop the mask of the
+   * rays that remain and the convolved radiances of its last forward model */
+  size_t const nfov = fov ? (size_t)(rt ? 4 : 2) * NR * (size_t)nd : 0;
+  size_t const fov_bytes = sizeof(double) * nfov;
   long const ncopy = ncopies + 1;
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)nt;
   if (nt > 0x7fffffffL || (long)atm_bytes > m->ws_budget / 2) {
@@ -2295,19 +2401,25 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     rc = JUR_ENOMEM;
     goto done;
   }
-  if (acc_bytes > 0 && (double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
-    jur_set_error("%s: the normal matrices (%ld doubles) do not fit beside the stacked atmosphere (%zu bytes) "
-                  "in the workspace budget: call with the rays of fewer slices at a time", who, na, atm_bytes);
+  if (fov_bytes > 0 && (double)atm_bytes + (double)fov_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("%s: the field of view's arrays (%zu bytes) do not fit beside the stacked atmosphere (%zu bytes) "
+                  "in the workspace budget: call with fewer rays at a time", who, fov_bytes, atm_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
-  if (sv_bytes > 0 && (double)atm_bytes + (double)acc_bytes + (double)sv_bytes > (double)(m->ws_budget / 2)) {
+  if (acc_bytes > 0 && (double)atm_bytes + (double)fov_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("%s: the normal matrices (%ld doubles) do not fit beside the stacked atmosphere (%zu bytes) "
+                  "in the workspace budget: call with the rays of fewer slices at a time", who, na, atm_bytes + fov_bytes);
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+  if (sv_bytes > 0 && (double)atm_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the solver scratch (%zu bytes) does not fit beside the normal matrices (%ld doubles) and the stacked "
                   "atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, sv_bytes, na, atm_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
-  if (dg_bytes > 0 && (double)atm_bytes + (double)acc_bytes + (double)dg_bytes > (double)(m->ws_budget / 2)) {
+  if (dg_bytes > 0 && (double)atm_bytes + (double)fov_bytes + (double)acc_bytes + (double)dg_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the factor, S, AVK and the vectors (%zu bytes) do not fit beside the normal matrices (%ld doubles) and the "
                   "stacked atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, dg_bytes, na, atm_bytes);
     rc = JUR_ENOMEM;
@@ -2324,7 +2436,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist : 0;
   size_t const rt_atm_bytes = looping ? sizeof(double) * (nrow + 1) * (size_t)pl.nt : 0;
   size_t const rt_bytes = sizeof(double) * (rt_dbl + rt_lng) + sizeof(int) * rt_int;
-  if (looping && (double)atm_bytes + (double)acc_bytes + (double)sv_bytes + (double)rt_atm_bytes + (double)rt_bytes > (double)(m->ws_budget / 2)) {
+  if (looping && (double)atm_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes + (double)rt_atm_bytes + (double)rt_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and the loop's arrays (%zu bytes) do not fit beside the solver "
                   "scratch, the normal matrices and the stacked atmosphere (%zu bytes) in the workspace budget: call with the rays "
                   "of fewer slices at a time", who, pl.nt, rt_atm_bytes, rt_bytes, atm_bytes + acc_bytes + sv_bytes);
@@ -2333,13 +2445,13 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   }
 
   /* passes: contiguous ranges of rays whose slots (width + 1 each) stay within the cap; one ray beyond it goes alone */
-  size_t const slot_bytes = sizeof(double) * (10 + 3 * (size_t)nd) + sizeof(int);
+  size_t const slot_bytes = sizeof(double) * (10 + (size_t)(fov ? 4 : 3) * (size_t)nd) + sizeof(int);   /* (with the convolved radiances) */
   long cap = max_rays_per_pass;
   if (cap == 0) {
     /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
      * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
      * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
-    long const avail = (m->ws_budget - (long)atm_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes) / 16;
+    long const avail = (m->ws_budget - (long)atm_bytes - (long)fov_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes) / 16;
     cap = avail / (long)slot_bytes;
     if (cap < 4096) cap = 4096;
   }
@@ -2347,13 +2459,32 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   long npass = 0, nmax = 0, kmax = 0;
   pass = (long *)malloc(sizeof(long) * 2 * (NR + 1));       /* (second half: the trial passes of the retrieval loop) */
   if (!pass) { rc = JUR_ENOMEM; goto done; }
-  if ((npass = scene_passes(nr, rp, cap, pass, &nmax, &kmax)) < 0) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
+  double const *const scan_time = fov ? geom[0] : NULL;
+  if ((npass = scene_passes(nr, rp, cap, scan_time, pass, &nmax, &kmax)) < 0) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
   kmax *= nd;
   long *const tpass = pass + NR + 1;
   long ntpass = 0, ntmax = 0;
   if (looping) {
-    ntpass = trial_passes(nr, rt->in->nlam, cap, tpass, &ntmax);
+    if ((ntpass = trial_passes(nr, rt->in->nlam, cap, scan_time, tpass, &ntmax)) < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
     if (ntmax > nmax) nmax = ntmax;                  /* (the arrays of a pass serve both kinds) */
+    if (fov) {
+      /* once slices have ended the passes are cut anew, and a pass that is extended to the end of a scan can then be
+       * larger than any of the first cut: room for the cap and one more scan, of either kind */
+      long scan_slots = 0, scan_cols = 0, scan_rays = 0;
+      for (long r0 = 0, r1; r0 < nr; r0 = r1) {
+        for (r1 = r0 + 1; r1 < nr && geom[0][r1] == geom[0][r0]; r1++);
+        if ((rp[r1] - rp[r0]) + (r1 - r0) > scan_slots) scan_slots = (rp[r1] - rp[r0]) + (r1 - r0);
+        if (rp[r1] - rp[r0] > scan_cols) scan_cols = rp[r1] - rp[r0];
+        if (r1 - r0 > scan_rays) scan_rays = r1 - r0;
+      }
+      long const all = rp[nr] + nr, tall = nr * rt->in->nlam;
+      long const jb = cap < all - scan_slots ? cap + scan_slots : all, kb = cap < rp[nr] - scan_cols ? cap + scan_cols : rp[nr];
+      long const tb = cap / rt->in->nlam + 1 + scan_rays < nr ? (cap / rt->in->nlam + 1 + scan_rays) * rt->in->nlam : tall;
+      if (jb > nmax) nmax = jb;
+      if (tb > nmax) nmax = tb;
+      if (kb * nd > kmax) kmax = kb * nd;
+      if (nmax > 0x7fffffffL) { jur_set_error("%s: a pass of 2^31 slots", who); rc = JUR_EINVAL; goto done; }
+    }
   }
 
   /* descriptors of the copies (copy 0: the base) and the base rows */
@@ -2392,7 +2523,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   /* (the normal equations' part, empty without them: y, weight, the accumulators A | b | cost | nlive in one piece,
    * then sptr | tptr | wptr | aptr, then what the solve needs) */
   size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
-               o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_dg = o_sv + nsv, o_rt = o_dg + ndg, o_int = o_rt + rt_dbl + rt_lng;
+               o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_dg = o_sv + nsv, o_fov = o_dg + ndg, o_rt = o_fov + nfov,
+               o_int = o_rt + rt_dbl + rt_lng;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad) */
   size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int;   /* (the loop's ints follow the others) */
   size_t const bytes = sizeof(double) * o_int + sizeof(int) * nint;
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
@@ -2407,6 +2539,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     m->scene_bytes = bytes;
   }
   if ((rc = ensure_io(m, nmax, 0))) goto done;
+  if (fov && (rc = scene_fov_reserve(m, (size_t)nmax * (size_t)nd))) goto done;
   {
     double *const D = (double *)m->d_scene;
     long *const L = (long *)m->d_scene;
@@ -2428,8 +2561,15 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (e == hipSuccess) e = hipMemcpyAsync(d_cdesc + 3 * ncopy, srays, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, s);
       if (e == hipSuccess) e = hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
     }
+    if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_fov, hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
 
+    double *const d_live = D + o_fov, *const d_ftau = d_live + nrd, *const d_livec = d_ftau + nrd, *const d_frad = d_livec + nrd;
+    scene_fov_t fv;
+    memset(&fv, 0, sizeof fv);
+    fv.k.nr = nr; fv.k.nd = nd; fv.k.time = D + o_geom; fv.k.vpz = D + o_geom + 4 * NR;
+    fv.k.n = m->fov_n; fv.k.dz = m->d_fov_shape; fv.k.w = m->d_fov_shape + JUR_NSHAPE; fv.k.status = m->d_status;
+    fv.live = d_live;
     jur_scene_stack_t st;
     memset(&st, 0, sizeof st);
     st.ncopy = (int)ncopy; st.np0 = np0; st.nrow = (int)nrow; st.ng = ng; st.nt = nt;
@@ -2540,8 +2680,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         hsptrc[nslice] = nl;
         nr_cur = n; rp_cur = hrpc; nactive_built = nactive;
         long dummy_n = 0, dummy_k = 0;
-        npass = scene_passes(nr_cur, rp_cur, cap, pass, &dummy_n, &dummy_k);
-        ntpass = trial_passes(nr_cur, rin->nlam, cap, tpass, &dummy_n);
+        if (fov) {                                  /* (whole scans have left: the scans that remain are the call's) */
+          if (!htimec && !(htimec = (double *)malloc(sizeof(double) * NR))) { rc = JUR_ENOMEM; goto done; }
+          for (long i = 0; i < n; i++) htimec[i] = geom[0][act[i]];
+        }
+        npass = scene_passes(nr_cur, rp_cur, cap, fov ? htimec : NULL, pass, &dummy_n, &dummy_k);
+        ntpass = trial_passes(nr_cur, rin->nlam, cap, fov ? htimec : NULL, tpass, &dummy_n);
         e = hipMemcpyAsync(d_act, act, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_sraysc, sraysc, sizeof(int) * (size_t)(nl ? nl : 1), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_rpc, hrpc, sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
@@ -2554,6 +2698,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         cq.first = d_first; cq.len = d_len; cq.copy0 = d_copy0; cq.tcopy0 = Ir + (pl.tcopy0 - pl.ints);
         cq.geom_c = d_geomc; cq.rad_c = d_radc; cq.y_c = d_yc; cq.weight_c = d_wc;
         cq.first_c = d_firstc; cq.len_c = d_lenc; cq.copy0_c = d_copy0c; cq.tcopy0_c = d_tcopy0c;
+        if (fov) { cq.live = d_live; cq.live_c = d_livec; }
         ti = scene_timed_begin(m, s);
         ek = jurk_scene_compact(&cq, s);
         scene_timed_end(m, ti, s);
@@ -2562,6 +2707,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         nq.sptr = d_sptrc; nq.srays = d_sraysc; nq.y = d_yc; nq.weight = d_wc;
         tps.nr = n; tps.first = d_firstc; tps.len = d_lenc; tps.tcopy0 = d_tcopy0c; tps.in_geom = d_geomc; tps.in_rad = d_radc;
         tps.sptr = d_sptrc; tps.srays = d_sraysc; tps.y = d_yc; tps.weight = d_wc;
+        fv.k.nr = n; fv.k.time = d_geomc; fv.k.vpz = d_geomc + 4 * n; fv.live = d_livec;
       }
       /* the dampings of this iteration (the product is rounded first), the states, fresh accumulators, the prior */
       for (int l = 0; l < rin->nlam; l++)
@@ -2608,13 +2754,23 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       scene_timed_end(m, ti, s);
       if (ek) { jur_set_error("%s: replication kernel launch failed", who); rc = JUR_EHIP; goto done; }
       if ((rc = jur_formod_device(m, n, a.geom, a.rad, a.tau, a.tp, a.np, m->d_status, s))) goto done;
+      jur_scene_pass_t af = a;                     /* what reads the forward model's results ... */
+      if (fov) {                                   /* ... reads them convolved, the sums under the effective mask */
+        fv.k.r0 = r0; fv.k.r1 = r1; fv.k.ntrial = 0; fv.k.rowptr = a.rowptr;
+        fv.k.rad = a.rad; fv.k.tau = a.tau; fv.k.rad_f = m->d_fov; fv.k.tau_f = d_ftau;
+        ti = scene_timed_begin(m, s);
+        ek = jurk_scene_fov(&fv.k, s);
+        scene_timed_end(m, ti, s);
+        if (ek) { jur_set_error("%s: field-of-view kernel launch failed", who); rc = JUR_EHIP; goto done; }
+        af.rad = m->d_fov; af.fov_tau = d_ftau; af.in_rad = fv.live;
+      }
       ti = scene_timed_begin(m, s);
-      ek = jurk_scene_quot(&a, nk, s);
+      ek = jurk_scene_quot(&af, nk, s);
       scene_timed_end(m, ti, s);
       if (ek) { jur_set_error("%s: quotient kernel launch failed", who); rc = JUR_EHIP; goto done; }
       if (ntiles) {
         ti = scene_timed_begin(m, s);
-        ek = jurk_scene_normal(&a, &nq, ntiles, s);
+        ek = jurk_scene_normal(&af, &nq, ntiles, s);
         scene_timed_end(m, ti, s);
         if (ek) { jur_set_error("%s: normal-equation kernel launch failed", who); rc = JUR_EHIP; goto done; }
       }
@@ -2629,7 +2785,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (!looping) break;
 
     /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
-    if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax))) goto done;
+    if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax, fov ? &fv : NULL))) goto done;
     e = hipMemcpyAsync(hcost, nq.cost, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hnlive, nq.nlive, sizeof(long) * RS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hprior0, d_prior0, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
@@ -2639,6 +2795,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; goto done; }
+    if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); rc = JUR_EINVAL; goto done; }
     {
       long work = 0;
       for (long r = 0; r < nr_cur; r++) work += rp_cur[r + 1] - rp_cur[r] + 1;
@@ -2712,6 +2869,16 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (!rc) rc = jur_formod_device(m, nr, D + o_geom, D + o_rad, D + o_tau, D + o_tp, d_np, m->d_status, s);
       if (rc) { free(ret); goto done; }
       a.out_rad = D + o_rad; a.out_tau = D + o_tau; a.out_tp = D + o_tp; a.out_np = d_np;
+      if (fov) {                                    /* all rays of the call, one slot each */
+        fv.k.nr = nr; fv.k.time = D + o_geom; fv.k.vpz = D + o_geom + 4 * NR;
+        fv.k.r0 = 0; fv.k.r1 = nr; fv.k.ntrial = 1; fv.k.rowptr = NULL;
+        fv.k.rad = D + o_rad; fv.k.tau = D + o_tau; fv.k.rad_f = d_frad; fv.k.tau_f = d_ftau;
+        ti = scene_timed_begin(m, s);
+        ek = jurk_scene_fov(&fv.k, s);
+        scene_timed_end(m, ti, s);
+        if (ek) { free(ret); jur_set_error("%s: field-of-view kernel launch failed", who); rc = JUR_EHIP; goto done; }
+        a.out_rad = d_frad; a.out_tau = d_ftau;
+      }
       ret_atm = ret;
     }
     e = hipMemcpyAsync(rad, a.out_rad, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
@@ -2728,12 +2895,13 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
+    else if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); rc = JUR_EINVAL; }
     if (rt && !rc) memcpy(rt->atm_ret, ret_atm, sizeof(atm_t));
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
   free(first); free(rp); free(sid); free(srays); free(sl); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa);
-  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm); free(dmap);
+  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm); free(dmap); free(hlive); free(htimec);
   trial_plan_free(&pl);
   return rc;
 }
@@ -2834,7 +3002,8 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   int *first = (int *)malloc(sizeof(int) * 3 * NR), *len = first ? first + NR : NULL, *sid = first ? len + NR : NULL;
   long *rp = (long *)malloc(sizeof(long) * 2 * (NR + 1)), *pass = rp ? rp + NR + 1 : NULL;
   jur_scene_slice_t *sl = NULL;
-  double *hbase = NULL;
+  double *hbase = NULL, *hlive = NULL;
+  int const fov = m->fov_n > 0;                     /* a field of view is set: the trial radiances are convolved */
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if (!first || !rp) { rc = JUR_ENOMEM; goto done; }
@@ -2853,6 +3022,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
         goto done;
       }
     }
+  if (fov && (rc = scene_fov_mask(who, nd, nr, geom[0], rad_in, &hlive))) goto done;
   long const nslice = jur_scene_distinct(np0, nr, first, len, rp, sid, &sl);
   if (nslice < 0) { rc = JUR_ENOMEM; goto done; }
   if (nslice == 0) goto done;                         /* no state elements: nothing to write */
@@ -2872,21 +3042,23 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
 
   size_t const NB = (size_t)nb, NS = (size_t)nslice, NT = (size_t)ntrial, npr = prior_ivar ? NB : 0;
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)pl.nt;
-  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS);
+  size_t const nfov = fov ? nrd : 0;                  /* (the effective mask) */
+  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov);
   if ((double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and accumulators (%zu bytes) exceed the workspace budget: "
                   "call with fewer trials or the rays of fewer slices at a time", who, pl.nt, atm_bytes, acc_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
-  size_t const slot_bytes = sizeof(double) * (10 + 3 * (size_t)nd) + sizeof(int);
+  size_t const slot_bytes = sizeof(double) * (10 + (size_t)(fov ? 4 : 3) * (size_t)nd) + sizeof(int);
   long cap = max_rays_per_pass;
   if (cap == 0) {                                     /* as the Jacobian entries size their passes */
     cap = (m->ws_budget - (long)atm_bytes - (long)acc_bytes) / 16 / (long)slot_bytes;
     if (cap < 4096) cap = 4096;
   }
   long nmax = 0;
-  long const npass = trial_passes(nr, ntrial, cap, pass, &nmax);
+  long const npass = trial_passes(nr, ntrial, cap, fov ? geom[0] : NULL, pass, &nmax);
+  if (npass < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
 
   hbase = (double *)malloc(sizeof(double) * nrow * (size_t)np0);
   if (!hbase) { rc = JUR_ENOMEM; goto done; }
@@ -2898,7 +3070,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
 
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_y = o_inrad + nrd, o_w = o_y + nrd,
                o_dx = o_w + nrd, o_r = o_dx + NT * NB, o_xa = o_r + npr, o_cost = o_xa + npr, o_prior = o_cost + NT * NS,
-               o_long = o_prior + NT * NS, o_int = o_long + pl.nlong;
+               o_live = o_prior + NT * NS, o_long = o_live + nfov, o_int = o_long + pl.nlong;
   size_t const bytes = sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR);
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
   hipStream_t const s = m->stream;
@@ -2912,6 +3084,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     m->scene_bytes = bytes;
   }
   if ((rc = ensure_io(m, nmax, 0))) goto done;
+  if (fov && (rc = scene_fov_reserve(m, (size_t)nmax * (size_t)nd))) goto done;
   {
     double *const D = (double *)m->d_scene;
     long *const L = (long *)(D + o_long);
@@ -2929,8 +3102,14 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (e == hipSuccess) e = hipMemcpyAsync(I, pl.ints, sizeof(int) * pl.nint, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_first, first, sizeof(int) * 2 * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
+    if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_live, hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
 
+    scene_fov_t fv;
+    memset(&fv, 0, sizeof fv);
+    fv.k.nr = nr; fv.k.nd = nd; fv.k.time = D + o_geom; fv.k.vpz = D + o_geom + 4 * NR;
+    fv.k.n = m->fov_n; fv.k.dz = m->d_fov_shape; fv.k.w = m->d_fov_shape + JUR_NSHAPE; fv.k.status = m->d_status;
+    fv.live = D + o_live;
     jur_scene_stack_t sk;
     jur_scene_trial_t st;
     jur_scene_trial_pass_t ps;
@@ -2945,17 +3124,18 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     ps.nr = nr; ps.nd = nd; ps.ntrial = ntrial; ps.first = d_first; ps.len = d_len; ps.tcopy0 = I + (pl.tcopy0 - pl.ints); ps.off = d_off;
     ps.in_geom = D + o_geom; ps.in_rad = D + o_inrad; ps.nslice = nslice; ps.sptr = d_sptr; ps.srays = I + (pl.srays - pl.ints);
     ps.y = D + o_y; ps.weight = D + o_w; ps.cost = D + o_cost;
-    if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax))) goto done;
+    if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax, fov ? &fv : NULL))) goto done;
     e = hipMemcpyAsync(cost, D + o_cost, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(prior, D + o_prior, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
+    else if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); rc = JUR_EINVAL; }
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
-  free(first); free(rp); free(sl); free(hbase);
+  free(first); free(rp); free(sl); free(hbase); free(hlive);
   trial_plan_free(&pl);
   return rc;
 }
@@ -3119,7 +3299,7 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
   c->d_io = NULL; c->d_io_np = NULL; c->io_cap = 0;
   c->h_io = NULL; c->h_io_cap = 0; c->h_pkg = NULL; c->h_atm = NULL; c->h_atm_n = 0; c->h_atm_cap = 0; c->h_status = NULL;
   c->stream = NULL; c->stream2 = NULL; c->ev_mask = NULL; c->ev_trace = NULL;
-  c->host_call = 0; c->have_done = 0; c->ev_done = NULL; c->d_fov = NULL; c->fov_cap = 0; c->d_kq = NULL; c->h_kq = NULL; c->kq_cap = 0;
+  c->host_call = 0; c->have_done = 0; c->ev_done = NULL; c->d_fov = NULL; c->fov_cap = 0; c->fov_n = 0; c->fov_shape = NULL; c->d_fov_shape = NULL; c->d_kq = NULL; c->h_kq = NULL; c->kq_cap = 0;
   c->d_ctb = NULL; c->ctb_cap = 0;
   c->timing = 0; c->evpool = NULL; c->evkind = NULL; c->ntimed = 0;
   if (hipSetDevice(c->device) != hipSuccess || create_streams(c) != JUR_OK ||

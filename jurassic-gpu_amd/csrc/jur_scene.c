@@ -209,6 +209,56 @@ done:
   return n;
 }
 
+/* ---- field of view of the scene entries: scans, windows and the effective mask ---------------------------------------- */
+typedef struct { double time; long start; } fov_run_t;
+
+static int fov_run_cmp(void const *pa, void const *pb) {
+  fov_run_t const *a = (fov_run_t const *)pa, *b = (fov_run_t const *)pb;
+  if (a->time < b->time) return -1;
+  if (a->time > b->time) return 1;
+  return (a->start > b->start) - (a->start < b->start);
+}
+
+long jur_scene_fov_live(int nd, long nr, double const *time, double const *rad_in, unsigned char *live) {
+  if (nd < 1 || nr < 0 || (nr > 0 && (!time || !rad_in))) { jur_set_error("jur_scene_fov_live: bad arguments"); return JUR_EINVAL; }
+  if (nr == 0) return 0;
+  /* a time stamp in two separate runs: the runs sorted by time stamp, then by start (NaN equals nothing: a run of one) */
+  long nrun = 0;
+  for (long r = 0; r < nr; r++) nrun += (r == 0 || !(time[r] == time[r - 1]));
+  fov_run_t *run = (fov_run_t *)malloc(sizeof *run * (size_t)nrun);
+  if (!run) { jur_set_error("jur_scene_fov_live: out of memory"); return JUR_ENOMEM; }
+  long n = 0, again = -1;
+  for (long r = 0; r < nr; r++)
+    if ((r == 0 || !(time[r] == time[r - 1])) && time[r] == time[r]) { run[n].time = time[r]; run[n].start = r; n++; }
+  qsort(run, (size_t)n, sizeof *run, fov_run_cmp);
+  for (long i = 1; i < n; i++)
+    if (run[i].time == run[i - 1].time && (again < 0 || run[i].start < again)) again = run[i].start;
+  free(run);
+  if (again >= 0) {
+    jur_set_error("jur_scene_fov_live: ray %ld starts a second run of rays with the time stamp %.17g: the rays of a scan must "
+                  "follow one another", again, time[again]);
+    return JUR_EINVAL;
+  }
+  long count = 0;
+  for (long r = 0; r < nr; r++) {
+    long const lo = r - JUR_NFOV > 0 ? r - JUR_NFOV : 0, hi = r + 1 + JUR_NFOV < nr ? r + 1 + JUR_NFOV : nr;
+    int nz = 0;
+    for (long r2 = lo; r2 < hi; r2++) nz += time[r2] == time[r];
+    if (nz < 2) {
+      jur_set_error("jur_scene_fov_live: ray %ld is alone in its window: Cannot apply FOV convolution!", r);
+      return JUR_EINVAL;
+    }
+    for (int id = 0; id < nd; id++) {
+      int ok = 1;
+      for (long r2 = lo; r2 < hi && ok; r2++)
+        if (time[r2] == time[r] && !isfinite(rad_in[(size_t)r2 * (size_t)nd + (size_t)id])) ok = 0;
+      if (live) live[(size_t)r * (size_t)nd + (size_t)id] = (unsigned char)ok;
+      count += ok;
+    }
+  }
+  return count;
+}
+
 /* ---- posterior diagnostics (jur_diagnose_slices_host, jur_diagnose_scene_host): the host arithmetic ------------------ */
 int jur_diag_check_out(char const *who, jur_diag_out_t const *out) {
   if (!out) { jur_set_error("%s: null argument (out)", who); return JUR_EINVAL; }

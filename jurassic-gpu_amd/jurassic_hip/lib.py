@@ -133,6 +133,10 @@ def lib():
         L.jur_retrieve_decide.argtypes = [C.c_int, C.c_long, C.c_double, C.c_double, C.c_double, dp, dp, dp, ip_, dp, ip_, ip_, ip_]
         L.jur_retrieve_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp),
                                               ip_, lp_, dp, dp, C.c_void_p, C.c_void_p, C.c_long]
+        L.jur_model_set_fov.argtypes = [C.c_void_p, C.c_int, dp, dp]
+        L.jur_model_fov.argtypes = [C.c_void_p, ip_, dp, dp]
+        L.jur_scene_fov_live.restype = C.c_long
+        L.jur_scene_fov_live.argtypes = [C.c_int, C.c_long, dp, dp, C.POINTER(C.c_ubyte)]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -382,6 +386,25 @@ class Model:
         """Field-of-view convolution of device arrays in place (raw device addresses as for formod_device)."""
         dz, w = (np.ascontiguousarray(a, dtype=np.float64) for a in (dz, w))
         _chk(lib().jur_fov_apply_device(self.h, nr, d_time, d_vpz, d_rad, d_tau, len(dz), _p(dz), _p(w), stream))
+
+    def set_fov(self, dz, w=None):
+        """Field of view of the scene entries (jur_model_set_fov): weights w at altitude offsets dz, as fov_read_shape
+        returns them; set_fov(None) switches the convolution off.  Only kernel_scene, normal_scene, step_scene,
+        trial_scene, retrieve_scene and diagnose_scene honour it."""
+        if dz is None:
+            _chk(lib().jur_model_set_fov(self.h, 0, None, None))
+            return
+        dz, w = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (dz, w))
+        if len(dz) != len(w):
+            raise ValueError("dz holds %d entries, w %d" % (len(dz), len(w)))
+        _chk(lib().jur_model_set_fov(self.h, len(dz), _p(dz), _p(w)))
+
+    def fov(self):
+        """The shape that is set: (dz, w), or None."""
+        dz, w = np.zeros(abi.NSHAPE), np.zeros(abi.NSHAPE)
+        n = C.c_int(0)
+        _chk(lib().jur_model_fov(self.h, C.byref(n), _p(dz), _p(w)))
+        return (dz[:n.value].copy(), w[:n.value].copy()) if n.value else None
 
     def kernel(self, atm, obs):
         """Forward-difference Jacobian (m, n); obs receives the unperturbed forward model."""
@@ -1054,6 +1077,20 @@ def fov_apply(time, vpz, rad, tau, dz, w):
     assert rad.flags.c_contiguous and tau.flags.c_contiguous and rad.dtype == np.float64 and rad.shape == tau.shape
     nr, nd = rad.shape
     _chk(lib().jur_fov_apply(nd, nr, _p(time), _p(vpz), _p(rad), _p(tau), nd, len(dz), _p(dz), _p(w)))
+
+
+def scene_fov_live(time, rad_in):
+    """The effective mask of the scene entries under a field of view (jur_scene_fov_live; host arithmetic): time (nr,),
+    rad_in (nr, nd) -> live (nr, nd) bool, True where rad_in is finite in that channel on every ray of the ray's window.
+    Raises JurassicError for a time stamp in two separate runs or a window of fewer than two rays."""
+    time = np.ascontiguousarray(time, dtype=np.float64)
+    rad = np.ascontiguousarray(rad_in, dtype=np.float64)
+    if rad.ndim != 2 or rad.shape[0] != len(time) or rad.shape[1] < 1:
+        raise ValueError("rad_in must be (%d, nd)" % len(time))
+    live = np.zeros(rad.shape, dtype=np.uint8)
+    n = _chk(lib().jur_scene_fov_live(rad.shape[1], len(time), _p(time), _p(rad), live.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    assert n == int(live.sum())
+    return live.astype(bool)
 
 
 def formod_pencil(ctl, atm, obs, ir):
