@@ -503,6 +503,53 @@ int  jur_model_set_fov(jur_model_t *m, int n, double const *dz, double const *w)
 int  jur_model_fov(jur_model_t const *m, int *n, double *dz, double *w);
 long jur_scene_fov_live(int nd, long nr, double const *time, double const *rad_in, unsigned char *live /* [nr][nd] or NULL */);
 
+/* A correlated a-priori covariance: the full prior precision of the slices.  The model holds, as it holds the field of
+ * view, one symmetric matrix R_s per slice; while one is set the prior of the entries that take one --
+ * jur_solve_slices_host, jur_step_scene_host, jur_trial_scene_host, jur_retrieve_scene_host, jur_diagnose_slices_host and
+ * jur_diagnose_scene_host -- is P_s = R_s + diag(prior_ivar_s) in place of diag(prior_ivar_s).  Their prior_ivar (it may
+ * be all zeros) and prior_dx / prior_xa are then required.  jur_kernel_scene_host and jur_normal_scene_host take no prior
+ * and are unaffected.  With r = prior_ivar, d = prior_dx, every line reducing to the text of those entries when R = 0:
+ *   D_i = A_ii + P_ii, P_ii = R_ii + r_i;  element i is live when D_i > 0.  The row and column of a dead element in A and
+ *     in P are ignored; its dx, its rows and columns of S and AVK and its sigmas are +0.0.
+ *   M = A + P + lam Z on the live elements, Z = diag(D) (JUR_DAMP_MARQUARDT: M_ii = fma(lam, D_i, D_i)) or Z = P
+ *     (JUR_DAMP_PRIOR, the damping (1 + lam) Sa^-1 with its off-diagonals: M_ij = fma(lam, P_ij, A_ij + P_ij)).
+ *   g_i = fma(r_i, d_i, b_i) + sum_j R_ij d_j over the live j;  M = L L^T, dx the solution;  pred = dx^T (g + lam Z dx):
+ *     the solve's sum with Z = diag(D), and sum_i dx_i fma(lam r_i, dx_i, g_i) + lam (dx^T R dx) with Z = P.  Breakdown
+ *     as there: status 1 + column, that system's outputs all zeros.
+ *   jur_trial_scene_host: prior[t][s] = d^T P d, d = xa - (x + dx[t]), over all elements of the slice: the chain of the
+ *     diagonal prior plus d^T R d.  jur_retrieve_scene_host: J = cost + prior with that prior; prior_dx = xa - x is formed
+ *     on the device as before.
+ *   Diagnostics: M = A + P (lam = 0), S = M^-1, AVK = S A (still the product), sigma_smooth_i = sqrt(max((S P S)_ii, 0))
+ *     from the product S P; the rest as there.
+ *   Every sum over a row of R takes lane l of 64 over j = l, l + 64, ... ascending as a chain of fused multiply-adds and
+ *     then a fixed tree over the lanes; a quadratic form takes the rows i = k, k + 4, ... in four chains q_k = fma(v_i,
+ *     (R v)_i, q_k) and returns (q_0 + q_1) + (q_2 + q_3).  Every double of a system depends on that system's inputs and
+ *     on w alone: not on the batch, the order, nlam, max_rays_per_pass or the entry called.  No atomics.
+ * jur_model_set_prior_precision: R_s at R + aptr[s], [w_s][w_s], aptr the running sum of w_s^2 with w_s = wptr[s + 1] -
+ *   wptr[s]; symmetric, only its diagonal and lower triangle are read.  nslice == 0 or R == NULL: off (the default: every
+ *   entry then launches what it launched before).  R is copied to device memory of the model's GPU here (JUR_ENOMEM,
+ *   JUR_EHIP); after a refusal what was set before stays set.  Positive definiteness is not checked: a pivot that is not
+ *   > 0 is the solve's breakdown status.
+ * jur_model_prior_precision: returns nslice of what is set (0: off) and copies wptr and R where given.
+ * JUR_EINVAL, naming the slice or the element, before anything is launched: an entry of R that is read and not finite; an
+ *   R_ii < 0; wptr not ascending (set call); a call whose layout (nslice, widths) is not the one set, both counts named; a
+ *   prior-taking entry called without prior_ivar while R is set.  The scratch the full prior adds (the assembled matrices
+ *   and g; S P for the diagnostics; the differences of the trials) is part of each entry's JUR_ENOMEM accounting.
+ * jur_prior_corr_host: the upstream parametrisation, built and inverted on the device.  Per slice, with iq and the point
+ *   of every element from jur_scene_elements and z = atm->z[ip]:
+ *     Sa_ij = (sigma_i sigma_j) exp(-(|z_i - z_j| / cz[q])) for iq_i == iq_j == q and cz[q] > 0;  Sa_ii = sigma_i^2;  0
+ *     otherwise.  R_s = Sa_s^-1 by the solve's factorisation and the diagnostics' inverse: full, its two triangles
+ *     bit-identical; status[s] is the solve's breakdown status (two elements of one quantity at one altitude make Sa
+ *     singular: a breakdown where the rounded pivot is not > 0), R_s all +0.0 then.  Sa is optional.  JUR_EINVAL for a sigma
+ *     that is not > 0 or not finite, a cz that is negative or not finite, an iq outside 0..nq-1, a z that is not finite.
+ *   Correlation across slices is not modelled: slices are independent systems in this layer. */
+int  jur_model_set_prior_precision(jur_model_t *m, long nslice, long const *wptr, double const *R);
+long jur_model_prior_precision(jur_model_t const *m, long *wptr /* [nslice + 1] or NULL */, double *R /* or NULL */);
+int  jur_prior_corr_host(jur_model_t *m, long nslice, long const *wptr,
+                         int const *iq, double const *z, double const *sigma,   /* [wptr[nslice]] each */
+                         int nq, double const *cz,                              /* [nq] correlation length per quantity, 0: uncorrelated */
+                         double *R, double *Sa /* optional */, int *status /* [nslice] */);
+
 /* intpol_atm with an error code instead of exit(): JUR_EINVAL for what upstream aborts on (profiles of one point,
  * profiles more than 10 degrees apart, unknown IP).  One lane per destination point on `device`. */
 int  jur_intpol_atm(ctl_t const *ctl, atm_t *dest, atm_t const *src, int device);

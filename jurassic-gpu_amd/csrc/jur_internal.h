@@ -263,6 +263,12 @@ int jur_diag_check_out(char const *who, jur_diag_out_t const *out);
 int jur_diag_check_wptr(char const *who, long nslice, long const *wptr);
 int jur_diag_check_prior(char const *who, long nslice, long const *wptr, double const *prior_ivar);
 long jur_diag_maps(long nslice, long const *wptr, int *imap, int *tmap, long *ntile);
+/* host checks of the full prior precision (jur_scene.c; no GPU): what is read of R, the layout of a call against the one
+ * set, the arguments of jur_prior_corr_host */
+int jur_prior_check_R(char const *who, long nslice, long const *wptr, double const *R);
+int jur_prior_check_layout(char const *who, long set_nslice, long const *set_wptr, long nslice, long const *wptr);
+int jur_prior_check_corr(char const *who, long nslice, long const *wptr, int const *iq, double const *z, double const *sigma,
+                         int nq, double const *cz);
 
 /* Trial states of a scene (jur_trial_scene_host, jur_retrieve_scene_host): the state elements of the slices where they
  * lie in the base rows, and ntrial candidate steps of each.  The trial atmosphere is stacked like the Jacobian's: copy 0
@@ -329,6 +335,59 @@ typedef struct {
   double *live_c;               /* [n][nd]                                                                  */
 } jur_scene_compact_t;
 int jurk_scene_compact(jur_scene_compact_t const *a, void *stream);
+
+/* Full a-priori precision of the slices (jur_model_set_prior_precision): P_s = R_s + diag(r_s), R_s [w][w] of which the
+ * diagonal and the lower triangle are read, r = prior_ivar.  The existing kernels run unchanged on what these form.  All
+ * arrays are device memory; wptr, aptr lay out the systems as jur_scene_solve_t's. */
+typedef struct {
+  long nslice;
+  long const *wptr, *aptr;
+  double const *A;              /* [aptr[nslice]] diagonal and lower triangle read; NULL: P alone, nothing masked  */
+  double const *b;              /* [wptr[nslice]], or NULL: g is not formed                                         */
+  double const *R;              /* [aptr[nslice]]                                                                   */
+  double const *ivar, *d;       /* [wptr[nslice]] r and prior_dx (d is read with b only)                            */
+  double const *lam;            /* [nslice] JUR_DAMP_PRIOR: M = A + P + lam P; NULL: M = A + P                      */
+  double *M;                    /* [aptr[nslice]] written: diagonal and lower triangle; 0 in a dead row or column   */
+  double *g;                    /* [wptr[nslice]] written with b: fma(r_i, d_i, b_i) + (R d)_i over live j, 0 if dead */
+  int const *state;             /* [nslice] or NULL: a system whose state is not 0 is left alone                    */
+} jur_scene_pasm_t;
+/* one wavefront per row (nb = wptr[nslice] rows) */
+int jurk_scene_prior_assemble(jur_scene_pasm_t const *a, long nb, void *stream);
+
+/* quadratic forms v^T R v of nvec vectors per system, and what is made of them */
+typedef struct {
+  long nslice;
+  int nvec;
+  long const *wptr, *aptr;
+  double const *R;              /* [aptr[nslice]]                                                                   */
+  double const *v;              /* [nvec][wptr[nslice]]                                                             */
+  double *out;                  /* [nvec][nslice] read and written: out += v^T R v                                  */
+  int const *state;             /* [nslice] or NULL                                                                 */
+  /* jurk_scene_prior_pred (nvec == 1, v the step): out = sum_i v_i fma(lam r_i, v_i, g_i) over the live elements in the
+   * solve kernel's order, + lam v^T R v; a system with status != 0 keeps its 0 */
+  double const *lam, *ivar, *g, *live;
+  int const *status;
+} jur_scene_pquad_t;
+int jurk_scene_prior_quad(jur_scene_pquad_t const *a, void *stream);
+int jurk_scene_prior_pred(jur_scene_pquad_t const *a, void *stream);
+/* d[t][e] = xa[e] - (x_e + dx[t][e]) (dx == NULL: the one row xa - x) into a->out, one lane per trial and element */
+int jurk_scene_prior_diff(jur_scene_trial_t const *a, long nb, void *stream);
+/* sigma_smooth_i = sqrt(max(sum_j (S P)_ij S_ij, 0)): the product by jur_scene_avk_kernel with P (a->A) in A's place
+ * into a->avk, then one wavefront per row; a->sigma_smooth alone is written */
+int jurk_scene_prior_smooth(jur_scene_diag_t const *a, long ntile, long nb, void *stream);
+/* jur_scene_inverse_kernel alone: S from the factor (jur_prior_corr_host) */
+int jurk_scene_prior_inverse(jur_scene_diag_t const *a, long ninv, void *stream);
+/* Sa of jur_prior_corr_host: one lane per entry of the lower triangles, mirrored */
+typedef struct {
+  long nslice;
+  long const *wptr, *aptr;
+  int const *iq;                /* [wptr[nslice]] quantity of every element                                         */
+  double const *z, *sigma;      /* [wptr[nslice]]                                                                   */
+  int nq;
+  double const *cz;             /* [nq]                                                                             */
+  double *Sa;                   /* [aptr[nslice]] written, full                                                     */
+} jur_scene_pcov_t;
+int jurk_scene_prior_cov(jur_scene_pcov_t const *a, long na, void *stream);
 
 /* Field of view of the scene entries (jur_model_set_fov): the forward model's results of one pass, replicated as the
  * pass lays them out, convolved out of place with the shape of the model.  Ray r of [r0, r1) owns `count` consecutive

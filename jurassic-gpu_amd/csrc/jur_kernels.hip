@@ -3205,6 +3205,151 @@ extern "C" int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *str
   return (int)hipGetLastError();
 }
 
+// ---- full a-priori precision of the slices (jur_model_set_prior_precision) -------------------------------------------
+// P = R + diag(r); of R only the diagonal and the lower triangle are read (R_ij from R[max][min]).  These kernels form
+// what the solve, inverse and product kernels above then work on unchanged.  No atomics, no waits between workgroups,
+// every chain fixed by w alone.
+//
+// Assembly, one wavefront per row i of system s: D_j = A_jj + (R_jj + r_j) decides who is live; M_ij = A_ij + P_ij for
+// j <= i between live elements (+0.0 in a dead row or column, so that the solve kernel finds D'_i = M_ii not > 0 there),
+// then fma(lam, P_ij, M_ij) where lam is given (JUR_DAMP_PRIOR: a live D' stays > 0 since P_ii >= 0); g_i = fma(r_i, d_i,
+// b_i) + (R d)_i with (R d)_i over the live j: lane l takes j = l, l + 64, ... ascending as a chain of fused multiply-adds,
+// then the fixed tree of jur_scene_diag_rows_kernel runs over the 64 lanes.  With R = 0 that is the solve kernel's own g.
+// Without A (the P of the smoothing error) nothing is masked.  No LDS, no barrier.
+__global__ __launch_bounds__(256) void jur_scene_prior_assemble_kernel(jur_scene_pasm_t a) {
+  long const nb = a.wptr[a.nslice], e = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= nb) return;                                      // (uniform in the wavefront)
+  int const lane = threadIdx.x & 63;
+  long const s = scene_find<false>(a.wptr, 0, a.nslice, e);
+  if (a.state && a.state[s] != 0) return;                   // (uniform in the wavefront)
+  int const w = (int)(a.wptr[s + 1] - a.wptr[s]), i = (int)(e - a.wptr[s]);
+  double const *const A = a.A ? a.A + a.aptr[s] : nullptr, *const R = a.R + a.aptr[s], *const r = a.ivar + a.wptr[s];
+  double const *const d = a.b ? a.d + a.wptr[s] : nullptr;
+  double *const M = a.M + a.aptr[s];
+  double const lam = a.lam ? a.lam[s] : 0.;
+  double const Pii = R[(long)i * w + i] + r[i];
+  bool const li = !A || A[(long)i * w + i] + Pii > 0;
+  double acc = 0.;
+  for (int j = lane; j < w; j += 64) {
+    double const Rij = j <= i ? R[(long)i * w + j] : R[(long)j * w + i];
+    bool lj = li;
+    if (A && j != i) lj = A[(long)j * w + j] + (R[(long)j * w + j] + r[j]) > 0;
+    if (d && lj) acc = fma(Rij, d[j], acc);
+    if (j <= i) {
+      double const Pij = j == i ? Pii : Rij;
+      double v = 0.;
+      if (li && lj) {
+        v = A ? A[(long)i * w + j] + Pij : Pij;
+        if (a.lam) v = fma(lam, Pij, v);
+      }
+      M[(long)i * w + j] = v;
+    }
+  }
+  if (!d) return;
+  for (int h = 32; h > 0; h >>= 1) acc += __shfl_down(acc, h, 64);
+  if (lane == 0) a.g[e] = li ? fma(r[i], d[i], a.b[e]) + acc : 0.;
+}
+
+// v^T R v of one system by a workgroup of four wavefronts: wavefront k takes the rows i = k, k + 4, ... ascending, each row
+// as in the assembly (lanes j = l, l + 64, ..., then the tree), q_k = fma(v_i, (R v)_i, q_k); then (q_0 + q_1) + (q_2 + q_3).
+__device__ inline double scene_prior_quad(double const *__restrict__ R, double const *__restrict__ v, int w, double *part) {
+  int const wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double q = 0.;
+  for (int i = wave; i < w; i += 4) {
+    double acc = 0.;
+    for (int j = lane; j < w; j += 64) acc = fma(j <= i ? R[(long)i * w + j] : R[(long)j * w + i], v[j], acc);
+    for (int h = 32; h > 0; h >>= 1) acc += __shfl_down(acc, h, 64);
+    q = fma(v[i], acc, q);                                  // (lane 0 holds the row's sum)
+  }
+  if (lane == 0) part[wave] = q;
+  __syncthreads();
+  return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// out[t][s] += v_t^T R_s v_t, one workgroup per (vector, system): the part of d^T P d that the diagonal chain of
+// jur_scene_prior_kernel has not summed.  With R = 0 it adds +0.0.
+__global__ __launch_bounds__(256) void jur_scene_prior_quad_kernel(jur_scene_pquad_t a) {
+  __shared__ double part[4];
+  long const g = blockIdx.x, t = g / a.nslice, s = g - t * a.nslice;
+  int const w = (int)(a.wptr[s + 1] - a.wptr[s]);
+  if (w <= 0 || (a.state && a.state[s] != 0)) return;       // (uniform)
+  double const q = scene_prior_quad(a.R + a.aptr[s], a.v + t * a.wptr[a.nslice] + a.wptr[s], w, part);
+  if (threadIdx.x == 0) a.out[g] = a.out[g] + q;
+}
+
+// pred of JUR_DAMP_PRIOR after the solve kernel has run on the assembled system with lam = 0: the sum over the live
+// elements of dx_i fma(lam r_i, dx_i, g_i) in that kernel's order (every lane its elements ascending, then its tree over
+// the 256 lanes) plus lam (dx^T R dx), a product and a sum rounded on their own.  A dead element's dx is +0.0 and R is
+// finite: it adds exact zeros to the form.  A system that broke down keeps the 0 the solve kernel wrote.
+__global__ __launch_bounds__(256) void jur_scene_prior_pred_kernel(jur_scene_pquad_t a) {
+  __shared__ double red[256], part[4];
+  long const s = blockIdx.x;
+  int const tid = threadIdx.x, w = (int)(a.wptr[s + 1] - a.wptr[s]);
+  if (w <= 0 || (a.state && a.state[s] != 0) || a.status[s] != 0) return;   // (uniform)
+  double const *const dx = a.v + a.wptr[s], *const r = a.ivar + a.wptr[s], *const gg = a.g + a.wptr[s], *const lv = a.live + a.wptr[s];
+  double const lam = a.lam[s];
+  double sum = 0.;
+  for (int i = tid; i < w; i += 256)
+    if (lv[i] > 0) sum += dx[i] * fma(lam * r[i], dx[i], gg[i]);
+  red[tid] = sum;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  double const q = scene_prior_quad(a.R + a.aptr[s], dx, w, part);
+  if (tid == 0) a.out[s] = red[0] + lam * q;
+}
+
+// d[t][e] = xa_e - (x_e + dx[t][e]), the difference jur_scene_prior_kernel forms, one lane per trial and element
+__global__ __launch_bounds__(256) void jur_scene_prior_diff_kernel(jur_scene_trial_t a) {
+  long const g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long const nb = a.wptr[a.nslice];
+  if (g >= (a.dx ? nb * a.ntrial : nb)) return;
+  long const e = g % nb;
+  long const s = scene_find<false>(a.wptr, 0, a.nslice, e);
+  if (a.state && a.state[s] != 0) return;
+  double x = a.base[(long)a.erow[e] * a.np0 + a.eip[e]];
+  if (a.dx) x = x + a.dx[g];
+  a.out[g] = a.xa[e] - x;
+}
+
+// sigma_smooth_i = sqrt(max(sum_j (S P)_ij S_ij, 0)), one wavefront per row as jur_scene_diag_rows_kernel's noise sum
+// (a.avk holds S P here; the rows of dead elements and of a system that broke down are +0.0 there)
+__global__ __launch_bounds__(256) void jur_scene_prior_smooth_kernel(jur_scene_diag_t a) {
+  long const nb = a.wptr[a.nslice], e = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= nb) return;                                      // (uniform in the wavefront)
+  int const lane = threadIdx.x & 63;
+  long const s = scene_find<false>(a.wptr, 0, a.nslice, e);
+  int const w = (int)(a.wptr[s + 1] - a.wptr[s]), i = (int)(e - a.wptr[s]);
+  double const *const Si = a.S + a.aptr[s] + (long)i * w, *const Ki = a.avk + a.aptr[s] + (long)i * w;
+  double smooth = 0.;
+  for (int j = lane; j < w; j += 64) smooth = fma(Ki[j], Si[j], smooth);
+  for (int h = 32; h > 0; h >>= 1) smooth += __shfl_down(smooth, h, 64);
+  if (lane == 0) a.sigma_smooth[e] = sqrt(smooth > 0 ? smooth : 0.);
+}
+
+// Sa of jur_prior_corr_host, one lane per entry (i, j <= i) of a system, mirrored: sigma_i^2 on the diagonal; within a
+// quantity q with cz[q] > 0 the product (sigma_i sigma_j) exp(-(|z_i - z_j| / cz[q])), every operation rounded on its own;
+// +0.0 elsewhere.
+__global__ __launch_bounds__(256) void jur_scene_prior_cov_kernel(jur_scene_pcov_t a) {
+  long const g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= a.aptr[a.nslice]) return;
+  long const s = scene_find<false>(a.aptr, 0, a.nslice, g);
+  long const w = a.wptr[s + 1] - a.wptr[s], i = (g - a.aptr[s]) / w, j = (g - a.aptr[s]) - i * w;
+  if (j > i) return;
+  long const ei = a.wptr[s] + i, ej = a.wptr[s] + j;
+  double v = 0.;
+  if (i == j) v = a.sigma[ei] * a.sigma[ei];
+  else if (a.iq[ei] == a.iq[ej]) {
+    double const c = a.cz[a.iq[ei]];
+    if (c > 0) v = (a.sigma[ei] * a.sigma[ej]) * exp(-(fabs(a.z[ei] - a.z[ej]) / c));
+  }
+  double *const Sa = a.Sa + a.aptr[s];
+  Sa[i * w + j] = v;
+  if (i > j) Sa[j * w + i] = v;
+}
+
 static unsigned scene_grid(long lanes) { return (unsigned)((lanes + 255) / 256); }
 
 extern "C" int jurk_scene_stack(jur_scene_stack_t const *a, void *stream) {
@@ -3289,6 +3434,54 @@ extern "C" int jurk_scene_trial_cost(jur_scene_trial_pass_t const *a, void *stre
 extern "C" int jurk_scene_compact(jur_scene_compact_t const *a, void *stream) {
   if (a->n <= 0) return 0;
   hipLaunchKernelGGL(jur_scene_compact_kernel, dim3(scene_grid(a->n)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+// (wptr is device memory: the host passes nb = wptr[nslice], the number of rows)
+extern "C" int jurk_scene_prior_assemble(jur_scene_pasm_t const *a, long nb, void *stream) {
+  if (nb <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_prior_assemble_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_prior_quad(jur_scene_pquad_t const *a, void *stream) {
+  if (a->nslice <= 0 || a->nvec <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_prior_quad_kernel, dim3((unsigned)(a->nslice * a->nvec)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_prior_pred(jur_scene_pquad_t const *a, void *stream) {
+  if (a->nslice <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_prior_pred_kernel, dim3((unsigned)a->nslice), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_prior_diff(jur_scene_trial_t const *a, long nb, void *stream) {
+  long const lanes = a->dx ? nb * a->ntrial : nb;
+  if (lanes <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_prior_diff_kernel, dim3(scene_grid(lanes)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+// (S P by the product kernel as it stands, then the row sums)
+extern "C" int jurk_scene_prior_smooth(jur_scene_diag_t const *a, long ntile, long nb, void *stream) {
+  if (a->nslice <= 0 || nb <= 0) return 0;
+  hipStream_t const s = (hipStream_t)stream;
+  if (ntile > 0) hipLaunchKernelGGL(jur_scene_avk_kernel, dim3((unsigned)ntile), dim3(256), 0, s, *a);
+  hipLaunchKernelGGL(jur_scene_prior_smooth_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, *a);
+  return (int)hipGetLastError();
+}
+
+// (the inverse of jur_prior_corr_host: the inverse kernel alone, after jurk_scene_solve has left the factor)
+extern "C" int jurk_scene_prior_inverse(jur_scene_diag_t const *a, long ninv, void *stream) {
+  if (a->nslice <= 0 || ninv <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_inverse_kernel, dim3((unsigned)ninv), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_prior_cov(jur_scene_pcov_t const *a, long na, void *stream) {
+  if (na <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_prior_cov_kernel, dim3(scene_grid(na)), dim3(256), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

@@ -92,6 +92,12 @@ struct jur_model {
   int fov_n;
   double *fov_shape;            /* dz[JUR_NSHAPE] | w[JUR_NSHAPE], malloc'ed with the first shape */
   double *d_fov_shape;
+  /* full a-priori precision of the slices (jur_model_set_prior_precision): the layout on the host, wptr | aptr and R on
+   * the device; pp_nslice == 0: off */
+  long pp_nslice;
+  long *pp_wptr;                /* wptr[pp_nslice + 1] | aptr[pp_nslice + 1], malloc'ed */
+  double *pp_R;                 /* host copy, what jur_model_prior_precision returns */
+  void *d_pp;                   /* device: the same 2 (pp_nslice + 1) longs, then R */
   double *d_kq, *h_kq;          /* jur_kernel: perturbation steps and dense difference quotients (device, pinned host) */
   long kq_cap;
   /* small calls: the fused kernel (jur_pencil_kernel) instead of sort + three batched kernels */
@@ -311,7 +317,7 @@ void jur_model_destroy(jur_model_t *m) {
   (void)hipSetDevice(m->device);
   if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_rec = NULL;
   void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp, m->d_blk_order,
-                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_fov_shape, m->d_kq, m->d_ctb, m->d_scene};
+                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_fov_shape, m->d_kq, m->d_ctb, m->d_scene, m->d_pp};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
   if (m->h_io) (void)hipHostFree(m->h_io);
@@ -320,6 +326,8 @@ void jur_model_destroy(jur_model_t *m) {
   if (m->h_status) (void)hipHostFree(m->h_status);
   free(m->h_atm);
   free(m->fov_shape);
+  free(m->pp_wptr);
+  free(m->pp_R);
   if (m->stream) (void)hipStreamDestroy(m->stream);
   if (m->stream2) (void)hipStreamDestroy(m->stream2);
   if (m->ev_mask) (void)hipEventDestroy(m->ev_mask);
@@ -1504,6 +1512,79 @@ int jur_model_fov(jur_model_t const *m, int *n, double *dz, double *w) {
   return JUR_OK;
 }
 
+/* ---- full a-priori precision of the slices ------------------------------------------------ */
+static void prior_precision_drop(jur_model_t *m) {
+  m->pp_nslice = 0;
+  if (m->d_pp) (void)hipFree(m->d_pp);
+  m->d_pp = NULL;
+  free(m->pp_wptr); m->pp_wptr = NULL;
+  free(m->pp_R); m->pp_R = NULL;
+}
+
+int jur_model_set_prior_precision(jur_model_t *m, long nslice, long const *wptr, double const *R) {
+  char const *const who = "jur_model_set_prior_precision";
+  if (!m || nslice < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  HIPCHK(hipSetDevice(m->device));
+  /* (a scene entry waits for its stream before it returns: nothing reads the old matrices any more) */
+  if (nslice == 0 || !R) { prior_precision_drop(m); return JUR_OK; }
+  if (nslice > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 slices", who); return JUR_EINVAL; }
+  if (!wptr) { jur_set_error("%s: null argument (wptr)", who); return JUR_EINVAL; }
+  int rc = jur_prior_check_R(who, nslice, wptr, R);
+  if (rc) return rc;                                       /* (what was set stays set) */
+  size_t const NS = (size_t)nslice;
+  long *ptr = (long *)malloc(sizeof(long) * 2 * (NS + 1));
+  if (!ptr) { jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
+  long *const aptr = ptr + NS + 1;
+  memcpy(ptr, wptr, sizeof(long) * (NS + 1));
+  aptr[0] = 0;
+  for (long q = 0; q < nslice; q++) { long const w = wptr[q + 1] - wptr[q]; aptr[q + 1] = aptr[q] + w * w; }
+  size_t const NA = (size_t)aptr[nslice];
+  double *hR = (double *)malloc(sizeof(double) * (NA ? NA : 1));
+  void *d = NULL;
+  if (!hR) { free(ptr); jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
+  memcpy(hR, R, sizeof(double) * NA);
+  if (hipMalloc(&d, sizeof(long) * 2 * (NS + 1) + sizeof(double) * (NA ? NA : 1)) != hipSuccess) {
+    (void)hipGetLastError(); free(ptr); free(hR);
+    jur_set_error("%s: no device memory for %zu bytes", who, sizeof(long) * 2 * (NS + 1) + sizeof(double) * NA);
+    return JUR_ENOMEM;
+  }
+  hipError_t e = hipMemcpy(d, ptr, sizeof(long) * 2 * (NS + 1), hipMemcpyHostToDevice);
+  if (NA && e == hipSuccess) e = hipMemcpy((long *)d + 2 * (NS + 1), hR, sizeof(double) * NA, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d); free(ptr); free(hR);
+    jur_set_error("%s: %s", who, hipGetErrorString(e));
+    return JUR_EHIP;
+  }
+  prior_precision_drop(m);
+  m->pp_wptr = ptr; m->pp_R = hR; m->d_pp = d; m->pp_nslice = nslice;
+  return JUR_OK;
+}
+
+long jur_model_prior_precision(jur_model_t const *m, long *wptr, double *R) {
+  if (!m) { jur_set_error("jur_model_prior_precision: null argument"); return JUR_EINVAL; }
+  if (m->pp_nslice == 0) return 0;
+  size_t const NS = (size_t)m->pp_nslice;
+  if (wptr) memcpy(wptr, m->pp_wptr, sizeof(long) * (NS + 1));
+  if (R) memcpy(R, m->pp_R, sizeof(double) * (size_t)m->pp_wptr[2 * NS + 1]);
+  return m->pp_nslice;
+}
+
+/* the device's R of the model for a call laid out by (nslice, wptr), NULL where none is set; JUR_EINVAL for another layout
+ * or a missing prior_ivar */
+static int prior_precision_for(jur_model_t const *m, char const *who, long nslice, long const *wptr, int have_ivar,
+                               double const **d_R) {
+  *d_R = NULL;
+  if (m->pp_nslice == 0) return JUR_OK;
+  int const rc = jur_prior_check_layout(who, m->pp_nslice, m->pp_wptr, nslice, wptr);
+  if (rc) return rc;
+  if (!have_ivar) {
+    jur_set_error("%s: a prior precision is set in the model: prior_ivar (it may be all zeros) and its partner are required", who);
+    return JUR_EINVAL;
+  }
+  *d_R = (double const *)((long const *)m->d_pp + 2 * ((size_t)nslice + 1));
+  return JUR_OK;
+}
+
 /* The scene entries' part of the convolution.  The buffer the convolved radiances of a pass go to (nval doubles, the
  * model's grow-only scratch of jur_fov_apply_device, which holds nothing between calls) ... */
 static int scene_fov_reserve(jur_model_t *m, size_t nval) {
@@ -1901,14 +1982,18 @@ static int solve_check_values(char const *who, long nslice, long const *wptr, ju
 static size_t solve_doubles(size_t na, size_t nb, size_t ns, size_t nlam, int prior) {
   return na + nb + nlam * nb + 2 * nlam * ns + (prior ? 2 * nb : 0) + (nlam * ns + 1) / 2;
 }
+/* ... and with a full prior precision after those: the assembled matrices A + P (+ lam P), g, the zero dampings */
+static size_t solve_full_doubles(size_t na, size_t nb, size_t ns) { return na + nb + ns; }
 
 /* Enqueues on s: the uploads of the dampings and the prior, one launch per damping over the one scratch (stream order
  * protects the copy-out of L), the copies home.  The caller waits for the stream before the host arrays go. */
 static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nslice, long na, long nb, long const *d_wptr,
                          long const *d_aptr, double const *d_A, double const *d_b, double *W, jur_solve_in_t const *in,
-                         jur_solve_out_t const *out, int const *d_state) {
+                         jur_solve_out_t const *out, int const *d_state, double const *d_R) {
   /* d_state (jur_retrieve_scene_host): the prior pair is on the device already, the steps stay there, and a system
-   * whose state is not 0 is left alone */
+   * whose state is not 0 is left alone.  d_R (a full prior precision is set): the solve kernel runs on A + P and g as
+   * jurk_scene_prior_assemble forms them, without a prior of its own; under JUR_DAMP_PRIOR on A + P + lam P with lam = 0,
+   * and jurk_scene_prior_pred then writes pred */
   int const resident = d_state != NULL;
   size_t const NA = (size_t)na, NB = (size_t)nb, NS = (size_t)nslice, NL = (size_t)in->nlam, npr = in->prior_ivar ? NB : 0;
   double *const dM = W, *const dlive = dM + NA, *const ddx = dlive + NB, *const dpred = ddx + NL * NB, *const dlam = dpred + NL * NS,
@@ -1923,10 +2008,40 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
   q.nslice = nslice; q.wptr = d_wptr; q.aptr = d_aptr; q.A = d_A; q.b = d_b;
   q.prior_ivar = npr ? dr : NULL; q.prior_dx = npr ? dd : NULL; q.mode = in->mode;
   q.M = dM; q.live = dlive; q.state = d_state;
+  jur_scene_pasm_t pa;
+  jur_scene_pquad_t pq;
+  memset(&pa, 0, sizeof pa); memset(&pq, 0, sizeof pq);
+  int const by_prior = in->mode == JUR_DAMP_PRIOR;
+  if (d_R) {
+    double *const dAp = W + solve_doubles(NA, NB, NS, NL, npr != 0), *const dg = dAp + NA, *const dzl = dg + NB;
+    pa.nslice = nslice; pa.wptr = d_wptr; pa.aptr = d_aptr; pa.A = d_A; pa.b = d_b; pa.R = d_R; pa.ivar = dr; pa.d = dd;
+    pa.M = dAp; pa.g = dg; pa.state = d_state;
+    pq.nslice = nslice; pq.nvec = 1; pq.wptr = d_wptr; pq.aptr = d_aptr; pq.R = d_R; pq.state = d_state;
+    pq.ivar = dr; pq.g = dg; pq.live = dlive;
+    q.A = dAp; q.b = dg; q.prior_ivar = NULL; q.prior_dx = NULL; q.mode = JUR_DAMP_MARQUARDT;
+    if (by_prior && hipMemsetAsync(dzl, 0, sizeof(double) * NS, s) != hipSuccess) { (void)hipGetLastError(); jur_set_error("%s: memset failed", who); return JUR_EHIP; }
+    if (!by_prior) {                              /* one assembly serves every damping: fma(lam, D, D) is the solve kernel's */
+      int const ti = scene_timed_begin(m, s);
+      int const ek = jurk_scene_prior_assemble(&pa, nb, s);
+      scene_timed_end(m, ti, s);
+      if (ek) { jur_set_error("%s: prior assembly kernel launch failed", who); return JUR_EHIP; }
+    }
+  }
   for (size_t l = 0; l < NL; l++) {
     q.lam = dlam + l * NS; q.dx = ddx + l * NB; q.pred = dpred + l * NS; q.status = dstat + l * NS;
     int const ti = scene_timed_begin(m, s);
-    int const ek = jurk_scene_solve(&q, s);
+    int ek = 0;
+    if (d_R && by_prior) {
+      pa.lam = dlam + l * NS;
+      if (l > 0) { pa.b = NULL; pa.d = NULL; }      /* (g does not depend on the damping) */
+      ek = jurk_scene_prior_assemble(&pa, nb, s);
+      q.lam = pa.M + NA + NB;                       /* (the zero dampings) */
+    }
+    if (!ek) ek = jurk_scene_solve(&q, s);
+    if (!ek && d_R && by_prior) {
+      pq.v = q.dx; pq.out = q.pred; pq.lam = dlam + l * NS; pq.status = q.status;
+      ek = jurk_scene_prior_pred(&pq, s);
+    }
     scene_timed_end(m, ti, s);
     if (ek) { jur_set_error("%s: solve kernel launch failed", who); return JUR_EHIP; }
     if (out->L && NA) e = hipMemcpyAsync(out->L + l * NA, dM, sizeof(double) * NA, hipMemcpyDeviceToHost, s);
@@ -1949,12 +2064,17 @@ static size_t diag_doubles(size_t na, size_t nb, size_t ns, int prior, size_t ni
   return 3 * na + 3 * nb + (prior ? nb : 0) + 4 * nb + 3 * ns + (ns + 2 * ninv + 3 * ntile + 1) / 2;
 }
 
+/* ... and with a full prior precision after those: A + P (then P alone, for the smoothing error) and S P */
+static size_t diag_full_doubles(size_t na) { return 2 * na; }
+
 /* Enqueues on s: the uploads of the prior and the block maps (hmap: imap | tmap), the factorisation by the solve kernel
  * (lam = 0, zero right-hand side, zero prior_dx), the inverse, the product and the vectors, the copies home.  The caller
  * waits for the stream before the host arrays go. */
 static int diag_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nslice, long na, long nb, long const *d_wptr,
                         long const *d_aptr, double const *d_A, double *W, double const *prior_ivar, jur_diag_out_t const *out,
-                        long ninv, long ntile, int const *hmap) {
+                        long ninv, long ntile, int const *hmap, double const *d_R) {
+  /* d_R (a full prior precision is set): the factor is that of A + P as jurk_scene_prior_assemble forms it, and
+   * sigma_smooth comes from the product S P */
   size_t const NA = (size_t)na, NB = (size_t)nb, NS = (size_t)nslice, npr = prior_ivar ? NB : 0;
   double *const dL = W, *const dS = dL + NA, *const dK = dS + NA, *const dlive = dK + NA, *const dz = dlive + NB, *const dzero = dz + NB,
          *const dr = dzero + NB, *const dvec = dr + npr, *const dlam = dvec + 4 * NB, *const dpred = dlam + NS, *const ddofs = dpred + NS;
@@ -1976,8 +2096,25 @@ static int diag_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nsl
   d.L = dL; d.live = dlive; d.status = dstat; d.imap = dimap; d.tmap = dtmap; d.S = dS; d.avk = dK;
   d.sigma = dvec; d.sigma_noise = dvec + NB; d.sigma_smooth = dvec + 2 * NB; d.avk_diag = dvec + 3 * NB; d.dofs = ddofs;
   int const ti = scene_timed_begin(m, s);
-  int ek = jurk_scene_solve(&q, s);
+  int ek = 0;
+  jur_scene_pasm_t pa;
+  memset(&pa, 0, sizeof pa);
+  if (d_R) {
+    pa.nslice = nslice; pa.wptr = d_wptr; pa.aptr = d_aptr; pa.A = d_A; pa.R = d_R; pa.ivar = dr;
+    pa.M = W + diag_doubles(NA, NB, NS, npr != 0, (size_t)ninv, (size_t)ntile);
+    ek = jurk_scene_prior_assemble(&pa, nb, s);
+    q.A = pa.M; q.prior_ivar = NULL; q.prior_dx = NULL;
+    d.prior_ivar = NULL;                          /* (the rows kernel writes sqrt(0); jurk_scene_prior_smooth the value) */
+  }
+  if (!ek) ek = jurk_scene_solve(&q, s);
   if (!ek) ek = jurk_scene_diag(&d, ninv, ntile, nb, s);
+  if (!ek && d_R) {
+    pa.A = NULL;                                  /* P alone where A + P lay: the factor has been taken */
+    ek = jurk_scene_prior_assemble(&pa, nb, s);
+    jur_scene_diag_t d2 = d;
+    d2.A = pa.M; d2.avk = pa.M + NA;
+    if (!ek) ek = jurk_scene_prior_smooth(&d2, ntile, nb, s);
+  }
   scene_timed_end(m, ti, s);
   if (ek) { jur_set_error("%s: diagnostics kernel launch failed", who); return JUR_EHIP; }
   if (NB) {
@@ -2102,7 +2239,8 @@ typedef struct { jur_scene_fov_t k; double const *live; } scene_fov_t;
  * ray arrays of the call (or of its gathered rays); its r0, r1, n, geom, rad, atm_time and `above` are set here.  The
  * model's view is left on the trial atmosphere.  Nothing is waited for after the stacking. */
 static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, jur_scene_stack_t *sk, jur_scene_trial_t *st,
-                     jur_scene_trial_pass_t *ps, long nb, long npass, long const *pass, long nmax, scene_fov_t *fv) {
+                     jur_scene_trial_pass_t *ps, long nb, long npass, long const *pass, long nmax, scene_fov_t *fv,
+                     jur_scene_pquad_t const *tq) {
   size_t const nrow = (size_t)sk->nrow;
   int const nd = ps->nd;
   int rc;
@@ -2114,7 +2252,15 @@ static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const
   if (!ek) ek = jurk_scene_elements(st, JUR_ELEM_APPLY, nb, s);
   hipError_t e = hipMemsetAsync(ps->cost, 0, sizeof(double) * (size_t)ps->nslice * (size_t)ps->ntrial, s);
   if (!ek && e == hipSuccess) {
-    if (st->ivar) ek = jurk_scene_prior(st, s);
+    if (st->ivar) {
+      ek = jurk_scene_prior(st, s);
+      if (!ek && tq) {                              /* a full prior precision: + d^T R d, d = xa - (x + dx) in tq->v */
+        jur_scene_trial_t dq = *st;
+        dq.out = (double *)tq->v;
+        ek = jurk_scene_prior_diff(&dq, nb, s);
+        if (!ek) ek = jurk_scene_prior_quad(tq, s);
+      }
+    }
     else e = hipMemsetAsync(st->prior, 0, sizeof(double) * (size_t)ps->nslice * (size_t)ps->ntrial, s);
   }
   scene_timed_end(m, ti, s);
@@ -2273,6 +2419,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   atm_t *ret_atm = NULL;
   int const fov = m->fov_n > 0;                     /* a field of view is set: the radiances of every pass are convolved */
   double *hlive = NULL, *htimec = NULL;
+  double const *d_R = NULL;                         /* the model's full prior precision on the device, where one is set */
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if (!first || !rp || !sid) { rc = JUR_ENOMEM; goto done; }
@@ -2380,14 +2527,20 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if ((rc = trial_plan_make(&pl, who, ctl, atm, rt->in->nlam, nr, nslice, sl, sid))) goto done;
     }
   }
+  if ((sv || dg) && m->pp_nslice) {                 /* a full prior precision is set: of this layout, with prior_ivar */
+    long const none[1] = {0};
+    if ((rc = prior_precision_for(m, who, nslice, wptr ? wptr : none, sv ? sv->in->prior_ivar != NULL : dg->prior_ivar != NULL, &d_R))) goto done;
+  }
   /* what the sums add to the slab: the accumulators A | b | cost | nlive, y and weight, the four running sums, the ray lists */
   size_t const nacc = (size_t)na + (size_t)nb + 2 * (size_t)(ntiles ? nslice : 0);
   size_t const acc_bytes = ntiles ? sizeof(double) * (nacc + 2 * NR * (size_t)nd + 4 * ((size_t)nslice + 1)) + sizeof(int) * (size_t)nlist : 0;
   /* ... and the solve: one more copy of the matrices, the vectors of one damping, the outputs of all */
-  size_t const nsv = (sv && ntiles) ? solve_doubles((size_t)na, (size_t)nb, (size_t)nslice, (size_t)sv->in->nlam, sv->in->prior_ivar != NULL) : 0;
+  size_t const nsv = (sv && ntiles) ? solve_doubles((size_t)na, (size_t)nb, (size_t)nslice, (size_t)sv->in->nlam, sv->in->prior_ivar != NULL) +
+                                      (d_R ? solve_full_doubles((size_t)na, (size_t)nb, (size_t)nslice) : 0) : 0;
   size_t const sv_bytes = sizeof(double) * nsv;
   /* ... or the diagnostics: the factor, S, AVK and the vectors */
-  size_t const ndg = (dg && ntiles) ? diag_doubles((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, (size_t)ninv, (size_t)ndtile) : 0;
+  size_t const ndg = (dg && ntiles) ? diag_doubles((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, (size_t)ninv, (size_t)ndtile) +
+                                      (d_R ? diag_full_doubles((size_t)na) : 0) : 0;
   size_t const dg_bytes = sizeof(double) * ndg;
   /* ... and a field of view: the effective mask and the convolved transmittances by ray; for the loop the mask of the
    * rays that remain and the convolved radiances of its last forward model */
@@ -2431,7 +2584,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
    * (geometry, mask, y, weight; rowptr and sptr of their own), the plan's index arrays */
   int const looping = rt && ntiles;
   size_t const NRD = NR * (size_t)nd;
-  size_t const rt_dbl = looping ? 2 * RL * RS + RS + 2 * (size_t)nb + 7 * NR + 3 * NRD : 0;
+  size_t const rt_dbl = looping ? 2 * RL * RS + RS + 2 * (size_t)nb + 7 * NR + 3 * NRD + (d_R ? RL * (size_t)nb : 0) : 0;   /* (last: xa - (x + dx) of every trial) */
   size_t const rt_lng = looping ? pl.nlong + (NR + 1) + (RS + 1) : 0;
   size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist : 0;
   size_t const rt_atm_bytes = looping ? sizeof(double) * (nrow + 1) * (size_t)pl.nt : 0;
@@ -2599,7 +2752,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     jur_retrieve_out_t const *const ro = rt ? rt->out : NULL;
     double *const d_tcost = D + o_rt, *const d_tprior = d_tcost + RL * RS, *const d_prior0 = d_tprior + RL * RS, *const d_xout = d_prior0 + RS,
            *const d_xa = d_xout + nb, *const d_geomc = d_xa + nb, *const d_radc = d_geomc + 7 * NR, *const d_yc = d_radc + NRD,
-           *const d_wc = d_yc + NRD;
+           *const d_wc = d_yc + NRD, *const d_dvec = d_wc + NRD;
     long *const Lr = (long *)(D + o_rt + rt_dbl), *const d_rpc = Lr + pl.nlong, *const d_sptrc = d_rpc + NR + 1;
     int *const Ir = I + nint0, *const d_state = Ir + pl.nint, *const d_choice = d_state + RS, *const d_act = d_choice + RS,
         *const d_firstc = d_act + NR, *const d_lenc = d_firstc + NR, *const d_copy0c = d_lenc + NR, *const d_tcopy0c = d_copy0c + NR,
@@ -2615,6 +2768,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     jur_scene_trial_t tst;
     jur_scene_trial_pass_t tps;
     memset(&tsk, 0, sizeof tsk); memset(&tst, 0, sizeof tst); memset(&tps, 0, sizeof tps);
+    jur_scene_pquad_t tqd;                          /* d^T R d of the loop's states: of the trials, of the state as it stands */
+    memset(&tqd, 0, sizeof tqd);
     long *hrpc = NULL, *hsptrc = NULL, *hnlive = NULL;
     long const *rp_cur = rp;
     long nr_cur = nr, nactive_built = (nlist == nr) ? nslice : -1;   /* (rays without state elements are in no pass of the loop) */
@@ -2643,6 +2798,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       tps.nr = nr; tps.nd = nd; tps.ntrial = rin->nlam; tps.first = d_first; tps.len = d_len; tps.tcopy0 = Ir + (pl.tcopy0 - pl.ints);
       tps.off = t_off; tps.in_geom = D + o_geom; tps.in_rad = D + o_inrad; tps.nslice = nslice; tps.sptr = Lr + (pl.sptr - pl.longs);
       tps.srays = Ir + (pl.srays - pl.ints); tps.state = d_state; tps.y = D + o_y; tps.weight = D + o_w; tps.cost = d_tcost;
+      tqd.nslice = nslice; tqd.nvec = rin->nlam; tqd.wptr = Lr; tqd.aptr = nq.aptr; tqd.R = d_R; tqd.v = d_dvec; tqd.out = d_tprior;
+      tqd.state = d_state;
       for (int l = 0; l < rin->nlam; l++) fac_max = fmax(fac_max, rin->fac[l]);
       for (long q = 0; q < nslice; q++) { ro->lam[q] = rin->lam0; ro->state[q] = JUR_RET_ACTIVE; ro->iters[q] = 0; ro->cost[q] = ro->prior[q] = 0; ro->nlive[q] = 0; }
       if (ro->h_cost) {
@@ -2725,6 +2882,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         ti = scene_timed_begin(m, s);
         ek = jurk_scene_elements(&pq, JUR_ELEM_PRIOR_DX, nb, s);
         if (!ek) ek = jurk_scene_prior(&pq, s);
+        if (!ek && d_R) {                           /* (sv_d holds xa - x) */
+          jur_scene_pquad_t bq = tqd;
+          bq.nvec = 1; bq.v = sv_d; bq.out = d_prior0;
+          ek = jurk_scene_prior_quad(&bq, s);
+        }
         scene_timed_end(m, ti, s);
       } else if (hipMemsetAsync(d_prior0, 0, sizeof(double) * RS, s) != hipSuccess) ek = 1;
       if (ek) { (void)hipGetLastError(); jur_set_error("%s: prior kernel launch failed", who); rc = JUR_EHIP; goto done; }
@@ -2780,12 +2942,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     }
     if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out,
-                                   looping ? d_state : NULL))) goto done;
-    if (ndg && (rc = diag_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, D + o_dg, dg->prior_ivar, dg->out, ninv, ndtile, dmap))) goto done;
+                                   looping ? d_state : NULL, d_R))) goto done;
+    if (ndg && (rc = diag_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, D + o_dg, dg->prior_ivar, dg->out, ninv, ndtile, dmap, d_R))) goto done;
     if (!looping) break;
 
     /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
-    if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax, fov ? &fv : NULL))) goto done;
+    if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax, fov ? &fv : NULL, d_R ? &tqd : NULL))) goto done;
     e = hipMemcpyAsync(hcost, nq.cost, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hnlive, nq.nlive, sizeof(long) * RS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hprior0, d_prior0, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
@@ -3039,11 +3201,14 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
           goto done;
         }
   if (prior_ivar && (rc = prior_check_values(who, nslice, pl.wptr, prior_ivar, prior_xa))) goto done;
+  double const *d_R = NULL;
+  if ((rc = prior_precision_for(m, who, nslice, pl.wptr, prior_ivar != NULL, &d_R))) goto done;
 
   size_t const NB = (size_t)nb, NS = (size_t)nslice, NT = (size_t)ntrial, npr = prior_ivar ? NB : 0;
+  size_t const ndv = d_R ? NT * NB : 0;               /* (a full prior precision: xa - (x + dx) of every trial) */
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)pl.nt;
   size_t const nfov = fov ? nrd : 0;                  /* (the effective mask) */
-  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov);
+  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov + ndv);
   if ((double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and accumulators (%zu bytes) exceed the workspace budget: "
                   "call with fewer trials or the rays of fewer slices at a time", who, pl.nt, atm_bytes, acc_bytes);
@@ -3070,7 +3235,8 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
 
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_y = o_inrad + nrd, o_w = o_y + nrd,
                o_dx = o_w + nrd, o_r = o_dx + NT * NB, o_xa = o_r + npr, o_cost = o_xa + npr, o_prior = o_cost + NT * NS,
-               o_live = o_prior + NT * NS, o_long = o_live + nfov, o_int = o_long + pl.nlong;
+               o_live = o_prior + NT * NS, o_dv = o_live + nfov, o_long = o_dv + ndv,
+               o_int = o_long + pl.nlong;
   size_t const bytes = sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR);
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
   hipStream_t const s = m->stream;
@@ -3124,7 +3290,13 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     ps.nr = nr; ps.nd = nd; ps.ntrial = ntrial; ps.first = d_first; ps.len = d_len; ps.tcopy0 = I + (pl.tcopy0 - pl.ints); ps.off = d_off;
     ps.in_geom = D + o_geom; ps.in_rad = D + o_inrad; ps.nslice = nslice; ps.sptr = d_sptr; ps.srays = I + (pl.srays - pl.ints);
     ps.y = D + o_y; ps.weight = D + o_w; ps.cost = D + o_cost;
-    if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax, fov ? &fv : NULL))) goto done;
+    jur_scene_pquad_t tq;
+    memset(&tq, 0, sizeof tq);
+    if (d_R) {                                        /* (the running sums of w^2 are the model's own) */
+      tq.nslice = nslice; tq.nvec = ntrial; tq.wptr = d_wptr; tq.aptr = (long const *)m->d_pp + NS + 1; tq.R = d_R;
+      tq.v = D + o_dv; tq.out = D + o_prior;
+    }
+    if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax, fov ? &fv : NULL, d_R ? &tq : NULL))) goto done;
     e = hipMemcpyAsync(cost, D + o_cost, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(prior, D + o_prior, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
@@ -3175,10 +3347,13 @@ int jur_solve_slices_host(jur_model_t *m, long nslice, long const *wptr, double 
   }
   memcpy(ptr, wptr, sizeof(long) * (NS + 1));
   if ((rc = solve_check_values(who, nslice, wptr, in))) goto done;
+  double const *d_R = NULL;
+  if ((rc = prior_precision_for(m, who, nslice, wptr, in->prior_ivar != NULL, &d_R))) goto done;
   {
     long const na = aptr[nslice], nb = wptr[nslice];
     size_t const o_A = 2 * (NS + 1), o_b = o_A + (size_t)na, o_sv = o_b + (size_t)nb;
-    size_t const bytes = sizeof(double) * (o_sv + solve_doubles((size_t)na, (size_t)nb, NS, (size_t)in->nlam, in->prior_ivar != NULL));
+    size_t const bytes = sizeof(double) * (o_sv + solve_doubles((size_t)na, (size_t)nb, NS, (size_t)in->nlam, in->prior_ivar != NULL) +
+                                           (d_R ? solve_full_doubles((size_t)na, (size_t)nb, NS) : 0));
     if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
     hipStream_t const s = m->stream;
     if ((rc = wait_done(m, s))) goto done;
@@ -3197,7 +3372,7 @@ int jur_solve_slices_host(jur_model_t *m, long nslice, long const *wptr, double 
     if (na && e == hipSuccess) e = hipMemcpyAsync(D + o_A, A, sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s);
     if (nb && e == hipSuccess) e = hipMemcpyAsync(D + o_b, b, sizeof(double) * (size_t)nb, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if ((rc = solve_enqueue(m, s, who, nslice, na, nb, L, L + NS + 1, D + o_A, D + o_b, D + o_sv, in, out, NULL))) goto done;
+    if ((rc = solve_enqueue(m, s, who, nslice, na, nb, L, L + NS + 1, D + o_A, D + o_b, D + o_sv, in, out, NULL, d_R))) goto done;
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
   }
@@ -3230,10 +3405,13 @@ int jur_diagnose_slices_host(jur_model_t *m, long nslice, long const *wptr, doub
   aptr[0] = 0;
   for (long q = 0; q < nslice; q++) { long const w = wptr[q + 1] - wptr[q]; aptr[q + 1] = aptr[q] + w * w; }
   if ((rc = diag_maps_make(who, nslice, wptr, &ninv, &ntile, &hmap))) goto done;
+  double const *d_R = NULL;
+  if ((rc = prior_precision_for(m, who, nslice, wptr, prior_ivar != NULL, &d_R))) goto done;
   {
     long const na = aptr[nslice], nb = wptr[nslice];
     size_t const o_A = 2 * (NS + 1), o_dg = o_A + (size_t)na;
-    size_t const bytes = sizeof(double) * (o_dg + diag_doubles((size_t)na, (size_t)nb, NS, prior_ivar != NULL, (size_t)ninv, (size_t)ntile));
+    size_t const bytes = sizeof(double) * (o_dg + diag_doubles((size_t)na, (size_t)nb, NS, prior_ivar != NULL, (size_t)ninv, (size_t)ntile) +
+                                           (d_R ? diag_full_doubles((size_t)na) : 0));
     if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
     hipStream_t const s = m->stream;
     if ((rc = wait_done(m, s))) goto done;
@@ -3251,8 +3429,89 @@ int jur_diagnose_slices_host(jur_model_t *m, long nslice, long const *wptr, doub
     hipError_t e = hipMemcpyAsync(L, ptr, sizeof(long) * 2 * (NS + 1), hipMemcpyHostToDevice, s);
     if (na && e == hipSuccess) e = hipMemcpyAsync(D + o_A, A, sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if ((rc = diag_enqueue(m, s, who, nslice, na, nb, L, L + NS + 1, D + o_A, D + o_dg, prior_ivar, out, ninv, ntile, hmap))) goto done;
+    if ((rc = diag_enqueue(m, s, who, nslice, na, nb, L, L + NS + 1, D + o_A, D + o_dg, prior_ivar, out, ninv, ntile, hmap, d_R))) goto done;
     e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
+  }
+done:
+  if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
+  free(ptr); free(hmap);
+  return rc;
+}
+
+/* The upstream parametrisation of the prior, built and inverted on the device.  The slab of the scene entries serves:
+ * wptr | aptr, z | sigma | cz | zeros (the solve's b) | live | dx | lam (zeros) | pred, Sa | L | R, then the ints
+ * iq | status | imap. */
+int jur_prior_corr_host(jur_model_t *m, long nslice, long const *wptr, int const *iq, double const *z, double const *sigma,
+                        int nq, double const *cz, double *R, double *Sa, int *status) {
+  char const *const who = "jur_prior_corr_host";
+  if (!m || nslice < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  if (nslice == 0) return JUR_OK;
+  if (nslice > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 systems per call", who); return JUR_EINVAL; }
+  if (!wptr || !R || !status) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  int rc = jur_prior_check_corr(who, nslice, wptr, iq, z, sigma, nq, cz);
+  if (rc) return rc;
+  size_t const NS = (size_t)nslice, NQ = (size_t)nq;
+  long *ptr = (long *)malloc(sizeof(long) * 2 * (NS + 1)), *aptr = ptr ? ptr + NS + 1 : NULL;
+  int *hmap = NULL;
+  long ninv = 0, ntile = 0;
+  if (!ptr) return JUR_ENOMEM;
+  int enqueued = 0;
+  memcpy(ptr, wptr, sizeof(long) * (NS + 1));
+  aptr[0] = 0;
+  for (long q = 0; q < nslice; q++) { long const w = wptr[q + 1] - wptr[q]; aptr[q + 1] = aptr[q] + w * w; }
+  if ((rc = diag_maps_make(who, nslice, wptr, &ninv, &ntile, &hmap))) goto done;
+  {
+    size_t const NA = (size_t)aptr[nslice], NB = (size_t)wptr[nslice];
+    size_t const o_z = 2 * (NS + 1), o_sig = o_z + NB, o_cz = o_sig + NB, o_zero = o_cz + NQ, o_live = o_zero + NB, o_dx = o_live + NB,
+                 o_lam = o_dx + NB, o_pred = o_lam + NS, o_Sa = o_pred + NS, o_L = o_Sa + NA, o_R = o_L + NA, o_int = o_R + NA;
+    size_t const bytes = sizeof(double) * o_int + sizeof(int) * (NB + NS + 2 * (size_t)ninv + 1);
+    if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
+    hipStream_t const s = m->stream;
+    if ((rc = wait_done(m, s))) goto done;
+    if (bytes > m->scene_bytes) {
+      if (m->d_scene) (void)hipFree(m->d_scene);
+      m->d_scene = NULL; m->scene_bytes = 0;
+      if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
+        (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
+      }
+      m->scene_bytes = bytes;
+    }
+    double *const D = (double *)m->d_scene;
+    long *const L = (long *)m->d_scene;
+    int *const d_iq = (int *)(D + o_int), *const d_stat = d_iq + NB, *const d_imap = d_stat + NS;
+    enqueued = 1;
+    hipError_t e = hipMemcpyAsync(L, ptr, sizeof(long) * 2 * (NS + 1), hipMemcpyHostToDevice, s);
+    if (NB && e == hipSuccess) e = hipMemcpyAsync(D + o_z, z, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+    if (NB && e == hipSuccess) e = hipMemcpyAsync(D + o_sig, sigma, sizeof(double) * NB, hipMemcpyHostToDevice, s);
+    if (NQ && e == hipSuccess) e = hipMemcpyAsync(D + o_cz, cz, sizeof(double) * NQ, hipMemcpyHostToDevice, s);
+    if (NB && e == hipSuccess) e = hipMemcpyAsync(d_iq, iq, sizeof(int) * NB, hipMemcpyHostToDevice, s);
+    if (NB && e == hipSuccess) e = hipMemsetAsync(D + o_zero, 0, sizeof(double) * NB, s);
+    if (e == hipSuccess) e = hipMemsetAsync(D + o_lam, 0, sizeof(double) * NS, s);
+    if (ninv > 0 && e == hipSuccess) e = hipMemcpyAsync(d_imap, hmap, sizeof(int) * 2 * (size_t)ninv, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    jur_scene_pcov_t c;
+    memset(&c, 0, sizeof c);
+    c.nslice = nslice; c.wptr = L; c.aptr = L + NS + 1; c.iq = d_iq; c.z = D + o_z; c.sigma = D + o_sig; c.nq = nq; c.cz = D + o_cz;
+    c.Sa = D + o_Sa;
+    jur_scene_solve_t q;
+    memset(&q, 0, sizeof q);
+    q.nslice = nslice; q.wptr = c.wptr; q.aptr = c.aptr; q.A = c.Sa; q.b = D + o_zero; q.mode = JUR_DAMP_MARQUARDT;
+    q.M = D + o_L; q.live = D + o_live; q.lam = D + o_lam; q.dx = D + o_dx; q.pred = D + o_pred; q.status = d_stat;
+    jur_scene_diag_t d;
+    memset(&d, 0, sizeof d);
+    d.nslice = nslice; d.wptr = c.wptr; d.aptr = c.aptr; d.A = c.Sa; d.L = q.M; d.live = q.live; d.status = d_stat; d.imap = d_imap;
+    d.S = D + o_R;
+    int const ti = scene_timed_begin(m, s);
+    int ek = jurk_scene_prior_cov(&c, (long)NA, s);
+    if (!ek) ek = jurk_scene_solve(&q, s);
+    if (!ek) ek = jurk_scene_prior_inverse(&d, ninv, s);
+    scene_timed_end(m, ti, s);
+    if (ek) { jur_set_error("%s: kernel launch failed", who); rc = JUR_EHIP; goto done; }
+    if (NA) e = hipMemcpyAsync(R, d.S, sizeof(double) * NA, hipMemcpyDeviceToHost, s);
+    if (NA && Sa && e == hipSuccess) e = hipMemcpyAsync(Sa, c.Sa, sizeof(double) * NA, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(status, d_stat, sizeof(int) * NS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
   }
 done:
@@ -3299,7 +3558,7 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
   c->d_io = NULL; c->d_io_np = NULL; c->io_cap = 0;
   c->h_io = NULL; c->h_io_cap = 0; c->h_pkg = NULL; c->h_atm = NULL; c->h_atm_n = 0; c->h_atm_cap = 0; c->h_status = NULL;
   c->stream = NULL; c->stream2 = NULL; c->ev_mask = NULL; c->ev_trace = NULL;
-  c->host_call = 0; c->have_done = 0; c->ev_done = NULL; c->d_fov = NULL; c->fov_cap = 0; c->fov_n = 0; c->fov_shape = NULL; c->d_fov_shape = NULL; c->d_kq = NULL; c->h_kq = NULL; c->kq_cap = 0;
+  c->host_call = 0; c->have_done = 0; c->ev_done = NULL; c->d_fov = NULL; c->fov_cap = 0; c->fov_n = 0; c->fov_shape = NULL; c->d_fov_shape = NULL; c->pp_nslice = 0; c->pp_wptr = NULL; c->pp_R = NULL; c->d_pp = NULL; c->d_kq = NULL; c->h_kq = NULL; c->kq_cap = 0;
   c->d_ctb = NULL; c->ctb_cap = 0;
   c->timing = 0; c->evpool = NULL; c->evkind = NULL; c->ntimed = 0;
   if (hipSetDevice(c->device) != hipSuccess || create_streams(c) != JUR_OK ||

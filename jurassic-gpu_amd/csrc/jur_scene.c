@@ -293,6 +293,78 @@ int jur_diag_check_prior(char const *who, long nslice, long const *wptr, double 
   return JUR_OK;
 }
 
+/* ---- full a-priori precision (jur_model_set_prior_precision, jur_prior_corr_host): the host checks ------------------- */
+/* R_s at R + aptr[s], [w_s][w_s]: the diagonal and the lower triangle (what is read) finite, R_ii >= 0 */
+int jur_prior_check_R(char const *who, long nslice, long const *wptr, double const *R) {
+  int const rc = jur_diag_check_wptr(who, nslice, wptr);
+  if (rc) return rc;
+  if (nslice > 0 && wptr[nslice] > 0 && !R) { jur_set_error("%s: null argument (R)", who); return JUR_EINVAL; }
+  size_t at = 0;
+  for (long q = 0; q < nslice; q++) {
+    size_t const w = (size_t)(wptr[q + 1] - wptr[q]);
+    for (size_t i = 0; i < w; i++) {
+      for (size_t j = 0; j <= i; j++) {
+        double const v = R[at + i * w + j];
+        if (!(v - v == 0)) {
+          jur_set_error("%s: R of slice %ld, element (%zu, %zu) is %g: not finite", who, q, i, j, v);
+          return JUR_EINVAL;
+        }
+      }
+      if (R[at + i * w + i] < 0) {
+        jur_set_error("%s: R of slice %ld, element (%zu, %zu) is %g: a negative diagonal", who, q, i, i, R[at + i * w + i]);
+        return JUR_EINVAL;
+      }
+    }
+    at += w * w;
+  }
+  return JUR_OK;
+}
+
+/* the layout of a call against the one the precision was set with (set_wptr: [set_nslice + 1]) */
+int jur_prior_check_layout(char const *who, long set_nslice, long const *set_wptr, long nslice, long const *wptr) {
+  if (set_nslice != nslice) {
+    jur_set_error("%s: the call has %ld slices, the prior precision of the model was set for %ld", who, nslice, set_nslice);
+    return JUR_EINVAL;
+  }
+  for (long q = 0; q < nslice; q++) {
+    long const w = wptr[q + 1] - wptr[q], ws = set_wptr[q + 1] - set_wptr[q];
+    if (w != ws) {
+      jur_set_error("%s: slice %ld of the call has %ld elements, the prior precision of the model was set for %ld", who, q, w, ws);
+      return JUR_EINVAL;
+    }
+  }
+  return JUR_OK;
+}
+
+int jur_prior_check_corr(char const *who, long nslice, long const *wptr, int const *iq, double const *z, double const *sigma,
+                         int nq, double const *cz) {
+  int const rc = jur_diag_check_wptr(who, nslice, wptr);
+  if (rc) return rc;
+  if (nq < 0 || (nq > 0 && !cz)) { jur_set_error("%s: bad arguments (nq, cz)", who); return JUR_EINVAL; }
+  for (int q = 0; q < nq; q++)
+    if (!(cz[q] >= 0) || !(cz[q] - cz[q] == 0)) {
+      jur_set_error("%s: cz of quantity %d is %g: negative or not finite", who, q, cz[q]);
+      return JUR_EINVAL;
+    }
+  if (nslice > 0 && wptr[nslice] > 0 && (!iq || !z || !sigma)) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  for (long q = 0; q < nslice; q++)
+    for (long e = wptr[q]; e < wptr[q + 1]; e++) {
+      if (iq[e] < 0 || iq[e] >= nq) {
+        jur_set_error("%s: iq of slice %ld, element %ld is %d: outside 0..%d", who, q, e - wptr[q], iq[e], nq - 1);
+        return JUR_EINVAL;
+      }
+      if (!(sigma[e] > 0) || !(sigma[e] - sigma[e] == 0)) {
+        jur_set_error("%s: sigma of slice %ld, element %ld is %g: not positive or not finite", who, q, e - wptr[q], sigma[e]);
+        return JUR_EINVAL;
+      }
+      if (!(z[e] - z[e] == 0)) {
+        jur_set_error("%s: z of slice %ld, element %ld is %g: not finite", who, q, e - wptr[q], z[e]);
+        return JUR_EINVAL;
+      }
+    }
+  return JUR_OK;
+}
+
 /* Block b of the inverse is columns [c0, c0 + 16) of system s: imap[2 b] = s, imap[2 b + 1] = c0, systems ascending and
  * columns ascending within a system.  Tile t of the product is rows [i0, i0 + 64) x columns [j0, j0 + 64) of system s:
  * tmap[3 t] = s, then i0, j0, row-major within a system.  A system of width 0 has neither. */

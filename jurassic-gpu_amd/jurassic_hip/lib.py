@@ -135,6 +135,11 @@ def lib():
                                               ip_, lp_, dp, dp, C.c_void_p, C.c_void_p, C.c_long]
         L.jur_model_set_fov.argtypes = [C.c_void_p, C.c_int, dp, dp]
         L.jur_model_fov.argtypes = [C.c_void_p, ip_, dp, dp]
+        if hasattr(L, "jur_model_set_prior_precision"):   # (an A/B library from before the full prior has none of these)
+            L.jur_model_set_prior_precision.argtypes = [C.c_void_p, C.c_long, lp_, dp]
+            L.jur_model_prior_precision.restype = C.c_long
+            L.jur_model_prior_precision.argtypes = [C.c_void_p, lp_, dp]
+            L.jur_prior_corr_host.argtypes = [C.c_void_p, C.c_long, lp_, ip_, dp, dp, C.c_int, dp, dp, dp, ip_]
         L.jur_scene_fov_live.restype = C.c_long
         L.jur_scene_fov_live.argtypes = [C.c_int, C.c_long, dp, dp, C.POINTER(C.c_ubyte)]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
@@ -405,6 +410,37 @@ class Model:
         n = C.c_int(0)
         _chk(lib().jur_model_fov(self.h, C.byref(n), _p(dz), _p(w)))
         return (dz[:n.value].copy(), w[:n.value].copy()) if n.value else None
+
+    def set_prior_precision(self, wptr, R=None):
+        """Full a-priori precision of the slices (jur_model_set_prior_precision): R flat, R_s at the running sum of the
+        squared widths, [w][w], symmetric (its diagonal and lower triangle are read), laid out by wptr (nslice + 1,) as
+        scene_slices lays out A; set_prior_precision(None) switches it off.  While it is set, solve_slices, step_scene,
+        trial_scene, retrieve_scene, diagnose_slices and diagnose_scene take the prior as R + diag(prior_ivar) and need
+        prior_ivar (it may be zeros) and its partner."""
+        if wptr is None or R is None:
+            _chk(lib().jur_model_set_prior_precision(self.h, 0, None, None))
+            return
+        wp = np.ascontiguousarray(wptr, dtype=np.int64).ravel()
+        RR = np.ascontiguousarray(R, dtype=np.float64).ravel()
+        ns = len(wp) - 1
+        if ns < 0:
+            raise ValueError("wptr must hold nslice + 1 entries")
+        na = int((np.diff(wp) ** 2).sum())
+        if RR.size != na:
+            raise ValueError("R must hold %d doubles" % na)
+        _chk(lib().jur_model_set_prior_precision(self.h, ns, wp.ctypes.data_as(C.POINTER(C.c_long)), _p(RR)))
+
+    def prior_precision(self):
+        """The precision that is set: dict(wptr, aptr, R), or None."""
+        ns = _chk(lib().jur_model_prior_precision(self.h, None, None))
+        if ns == 0:
+            return None
+        wp = np.zeros(ns + 1, dtype=np.int64)
+        _chk(lib().jur_model_prior_precision(self.h, wp.ctypes.data_as(C.POINTER(C.c_long)), None))
+        ap = np.concatenate(([0], np.cumsum(np.diff(wp) ** 2))).astype(np.int64)
+        R = np.zeros(int(ap[-1]))
+        _chk(lib().jur_model_prior_precision(self.h, None, _p(R)))
+        return dict(wptr=wp, aptr=ap, R=R)
 
     def kernel(self, atm, obs):
         """Forward-difference Jacobian (m, n); obs receives the unperturbed forward model."""
@@ -948,6 +984,53 @@ def scene_elements(ctl, atm, first, length):
     _chk(lib().jur_scene_elements(C.byref(ctl), C.byref(atm), int(first), int(length), cols.ctypes.data_as(C.POINTER(C.c_long)),
                                   iq.ctypes.data_as(ip_), ip.ctypes.data_as(ip_)))
     return dict(cols=cols, iq=iq, ip=ip)
+
+
+def prior_corr_slices(model, wptr, iq, z, sigma, cz, want_Sa=True):
+    """jur_prior_corr_host on systems the caller lays out: iq, z, sigma (n,) per element, cz (nq,) the correlation length
+    of every quantity (0: uncorrelated) -> dict(R, Sa (flat, laid out as A), status (nslice,), wptr, aptr).  Sa_ij =
+    sigma_i sigma_j exp(-|z_i - z_j| / cz[q]) within a quantity, R = Sa^-1 per slice, both formed on the device."""
+    wp = np.ascontiguousarray(wptr, dtype=np.int64).ravel()
+    ns, n = len(wp) - 1, int(wp[-1])
+    ap = np.concatenate(([0], np.cumsum(np.diff(wp) ** 2))).astype(np.int64)
+    qq = np.ascontiguousarray(iq, dtype=np.int32).ravel()
+    zz, ss = (np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (z, sigma))
+    cc = np.ascontiguousarray(cz, dtype=np.float64).ravel()
+    if qq.size != n or zz.size != n or ss.size != n:
+        raise ValueError("iq, z and sigma must hold %d entries" % n)
+    R, Sa = np.zeros(int(ap[-1])), np.zeros(int(ap[-1]) if want_Sa else 0)
+    status = np.zeros(ns, dtype=np.int32)
+    ip_ = C.POINTER(C.c_int)
+    _chk(lib().jur_prior_corr_host(model.h, ns, wp.ctypes.data_as(C.POINTER(C.c_long)), qq.ctypes.data_as(ip_), _p(zz), _p(ss),
+                                   len(cc), _p(cc), _p(R), _p(Sa) if want_Sa else None, status.ctypes.data_as(ip_)))
+    return dict(R=R, Sa=Sa if want_Sa else None, status=status, wptr=wp, aptr=ap)
+
+
+def prior_corr(model, ctl, atm, time, sigma_q, cz_q):
+    """The upstream parametrisation of the a-priori covariance for the slices of a scene (jur_prior_corr_host): sigma_q
+    and cz_q (2 + ng + nw,) give every quantity (0 p, 1 T, 2 + g q, 2 + ng + w k) its standard deviation and its vertical
+    correlation length (0: uncorrelated); the altitudes are atm.z of the elements' points.  A sigma_q entry may be a
+    callable of (values of the quantity at the elements' points) for a relative error.  -> dict(R, Sa, status, wptr, aptr,
+    iq, ip, z, sigma), laid out by scene_slices of these time stamps: R goes to Model.set_prior_precision."""
+    sl = scene_slices(ctl, atm, time)
+    iq, ip = [], []
+    for f, l in zip(sl["sfirst"], sl["slen"]):
+        el = scene_elements(ctl, atm, int(f), int(l))
+        iq.append(el["iq"]); ip.append(el["ip"])
+    iq = np.concatenate(iq) if iq else np.zeros(0, dtype=np.int32)
+    ip = np.concatenate(ip) if ip else np.zeros(0, dtype=np.int32)
+    ng = ctl.ng
+    sigma = np.zeros(len(iq))
+    for e, (q, i) in enumerate(zip(iq, ip)):
+        sq = sigma_q[q]
+        if callable(sq):
+            val = atm.p[i] if q == 0 else atm.t[i] if q == 1 else atm.q[q - 2][i] if q < 2 + ng else atm.k[q - 2 - ng][i]
+            sq = sq(val)
+        sigma[e] = sq
+    z = np.array([atm.z[i] for i in ip], dtype=np.float64)
+    out = prior_corr_slices(model, sl["wptr"], iq, z, sigma, cz_q)
+    out.update(aptr=sl["aptr"], iq=iq, ip=ip, z=z, sigma=sigma)
+    return out
 
 
 def scene_blocks_to_dense(ctl, atm, out, n=None):
