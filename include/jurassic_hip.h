@@ -503,6 +503,26 @@ int  jur_model_set_fov(jur_model_t *m, int n, double const *dz, double const *w)
 int  jur_model_fov(jur_model_t const *m, int *n, double *dz, double *w);
 long jur_scene_fov_live(int nd, long nr, double const *time, double const *rad_in, unsigned char *live /* [nr][nd] or NULL */);
 
+/* The passes of the scene entries (host arithmetic, no GPU): the rules the entries follow when max_rays_per_pass (cap
+ * here, >= 1) or the workspace budget splits a call.  rowptr is jur_scene_layout's; time is the rays' time stamps while
+ * a field of view is set and NULL otherwise.  JUR_EINVAL for bad arguments.
+ * jur_scene_passes: the Jacobian entries.  A ray of width w takes w + 1 slots (itself and one copy per state element)
+ *   and w block columns.  A pass is a contiguous range of rays, extended while its slots stay within cap; one ray beyond
+ *   the cap goes alone; with time a pass is then extended to the end of its last scan.  pass (room for nr + 1 entries, or
+ *   NULL) receives the first ray of every pass and nr; *nmax and *kmax (either may be NULL) the slots and the block
+ *   columns of the largest pass.  Returns the number of passes, JUR_EINVAL (-1) for a pass of 2^31 slots.
+ * jur_trial_passes: the trial passes, ntrial slots per ray: max(cap / ntrial, 1) rays each, with time extended to the end
+ *   of the last scan.  Outputs and return value as above.
+ * jur_scene_pass_reserve: what jur_retrieve_scene_host allocates.  Its loop gathers the rays of the slices that are
+ *   still active and cuts both kinds of passes anew, and the cut of a subset can hold more than any pass of the first cut:
+ *   *slots and *cols are bounds for every pass of either kind on any subset of the rays that ended slices can leave, the
+ *   first cut among them.  Without time: slots = max(min(cap, all slots), widest ray + 1, trial slots of the first cut),
+ *   cols = max(min(cap - 1, all columns), widest ray).  With time: the cap and one more scan, never more than the whole
+ *   call.  With a cap under which the call is one pass of either kind they are the sizes of those passes. */
+long jur_scene_passes(long nr, long const *rowptr, long cap, double const *time, long *pass, long *nmax, long *kmax);
+long jur_trial_passes(long nr, int ntrial, long cap, double const *time, long *pass, long *nmax);
+int  jur_scene_pass_reserve(long nr, long const *rowptr, long cap, int ntrial, double const *time, long *slots, long *cols);
+
 /* A correlated a-priori covariance: the full prior precision of the slices.  The model holds, as it holds the field of
  * view, one symmetric matrix R_s per slice; while one is set the prior of the entries that take one --
  * jur_solve_slices_host, jur_step_scene_host, jur_trial_scene_host, jur_retrieve_scene_host, jur_diagnose_slices_host and

@@ -2211,25 +2211,6 @@ static int trial_plan_make(trial_plan_t *p, char const *who, ctl_t const *ctl, a
   return JUR_OK;
 }
 
-/* contiguous ranges of rays whose ntrial slots each stay within cap; one ray beyond it goes alone.  With `time` (the time
- * stamps of the rays; a field of view is set) a pass is extended to the end of its last scan.  Returns the number of
- * passes (-1 for a pass of 2^31 slots), *nmax the slots of the largest; pass has room for nr + 1 entries. */
-static long trial_passes(long nr, int ntrial, long cap, double const *time, long *pass, long *nmax) {
-  long per = cap / ntrial, npass = 0;
-  if (per < 1) per = 1;
-  if (per > 0x7fffffffL / ntrial) per = 0x7fffffffL / ntrial;
-  for (long r0 = 0; r0 < nr;) {
-    long r1 = r0 + per < nr ? r0 + per : nr;
-    while (time && r1 < nr && time[r1] == time[r1 - 1]) r1++;   /* (a field of view is set: to the end of the scan) */
-    if ((r1 - r0) * ntrial > 0x7fffffffL) return -1;
-    if ((r1 - r0) * ntrial > *nmax) *nmax = (r1 - r0) * ntrial;
-    pass[npass++] = r0;
-    r0 = r1;
-  }
-  pass[npass] = nr;
-  return npass;
-}
-
 /* a field of view in a call: the kernel's arguments (shape, status word and the rays' time stamps and view-point altitudes
  * are the call's; the pass fills in the rest) and the effective mask [rays][nd] on the device */
 typedef struct { jur_scene_fov_t k; double const *live; } scene_fov_t;
@@ -2350,27 +2331,6 @@ static int prior_check_values(char const *who, long nslice, long const *wptr, do
       }
     }
   return JUR_OK;
-}
-
-/* Passes of the Jacobian entries: contiguous ranges of the nr rays with row pointer rp whose slots (width + 1 each) stay
- * within cap; one ray beyond it goes alone; with `time` (the time stamps of the rays; a field of view is set) a pass is
- * extended to the end of its last scan.  pass has room for nr + 1 entries; *nmax and *kmax grow to the slots and the
- * block columns of the largest pass.  Returns the number of passes, -1 for a pass of 2^31 slots. */
-static long scene_passes(long nr, long const *rp, long cap, double const *time, long *pass, long *nmax, long *kmax) {
-  long npass = 0;
-  for (long r0 = 0; r0 < nr;) {
-    long r1 = r0 + 1;
-    while (r1 < nr && (rp[r1 + 1] - rp[r0]) + (r1 + 1 - r0) <= cap) r1++;
-    while (time && r1 < nr && time[r1] == time[r1 - 1]) r1++;   /* (a field of view is set: to the end of the scan) */
-    long const n = (rp[r1] - rp[r0]) + (r1 - r0);
-    if (n > 0x7fffffffL) return -1;
-    if (n > *nmax) *nmax = n;
-    if (rp[r1] - rp[r0] > *kmax) *kmax = rp[r1] - rp[r0];
-    pass[npass++] = r0;
-    r0 = r1;
-  }
-  pass[npass] = nr;
-  return npass;
 }
 
 /* what jur_retrieve_scene_host adds to jur_step_scene_host */
@@ -2613,32 +2573,17 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   pass = (long *)malloc(sizeof(long) * 2 * (NR + 1));       /* (second half: the trial passes of the retrieval loop) */
   if (!pass) { rc = JUR_ENOMEM; goto done; }
   double const *const scan_time = fov ? geom[0] : NULL;
-  if ((npass = scene_passes(nr, rp, cap, scan_time, pass, &nmax, &kmax)) < 0) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
-  kmax *= nd;
+  if ((npass = jur_scene_passes(nr, rp, cap, scan_time, pass, &nmax, &kmax)) < 0) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
   long *const tpass = pass + NR + 1;
-  long ntpass = 0, ntmax = 0;
+  long ntpass = 0;
   if (looping) {
-    if ((ntpass = trial_passes(nr, rt->in->nlam, cap, scan_time, tpass, &ntmax)) < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
-    if (ntmax > nmax) nmax = ntmax;                  /* (the arrays of a pass serve both kinds) */
-    if (fov) {
-      /* once slices have ended the passes are cut anew, and a pass that is extended to the end of a scan can then be
-       * larger than any of the first cut: room for the cap and one more scan, of either kind */
-      long scan_slots = 0, scan_cols = 0, scan_rays = 0;
-      for (long r0 = 0, r1; r0 < nr; r0 = r1) {
-        for (r1 = r0 + 1; r1 < nr && geom[0][r1] == geom[0][r0]; r1++);
-        if ((rp[r1] - rp[r0]) + (r1 - r0) > scan_slots) scan_slots = (rp[r1] - rp[r0]) + (r1 - r0);
-        if (rp[r1] - rp[r0] > scan_cols) scan_cols = rp[r1] - rp[r0];
-        if (r1 - r0 > scan_rays) scan_rays = r1 - r0;
-      }
-      long const all = rp[nr] + nr, tall = nr * rt->in->nlam;
-      long const jb = cap < all - scan_slots ? cap + scan_slots : all, kb = cap < rp[nr] - scan_cols ? cap + scan_cols : rp[nr];
-      long const tb = cap / rt->in->nlam + 1 + scan_rays < nr ? (cap / rt->in->nlam + 1 + scan_rays) * rt->in->nlam : tall;
-      if (jb > nmax) nmax = jb;
-      if (tb > nmax) nmax = tb;
-      if (kb * nd > kmax) kmax = kb * nd;
-      if (nmax > 0x7fffffffL) { jur_set_error("%s: a pass of 2^31 slots", who); rc = JUR_EINVAL; goto done; }
-    }
+    if ((ntpass = jur_trial_passes(nr, rt->in->nlam, cap, scan_time, tpass, NULL)) < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
+    /* once slices have ended the passes of both kinds are cut anew, and a pass of the rays that remain can be larger
+     * than any of the first cut: room for every such pass (the arrays of a pass serve both kinds) */
+    if ((rc = jur_scene_pass_reserve(nr, rp, cap, rt->in->nlam, scan_time, &nmax, &kmax))) goto done;
+    if (nmax > 0x7fffffffL) { jur_set_error("%s: a pass of 2^31 slots", who); rc = JUR_EINVAL; goto done; }
   }
+  kmax *= nd;
 
   /* descriptors of the copies (copy 0: the base) and the base rows */
   off = (long *)malloc(sizeof(long) * ((size_t)ncopy + 1));
@@ -2836,13 +2781,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         }
         hsptrc[nslice] = nl;
         nr_cur = n; rp_cur = hrpc; nactive_built = nactive;
-        long dummy_n = 0, dummy_k = 0;
         if (fov) {                                  /* (whole scans have left: the scans that remain are the call's) */
           if (!htimec && !(htimec = (double *)malloc(sizeof(double) * NR))) { rc = JUR_ENOMEM; goto done; }
           for (long i = 0; i < n; i++) htimec[i] = geom[0][act[i]];
         }
-        npass = scene_passes(nr_cur, rp_cur, cap, fov ? htimec : NULL, pass, &dummy_n, &dummy_k);
-        ntpass = trial_passes(nr_cur, rin->nlam, cap, fov ? htimec : NULL, tpass, &dummy_n);
+        npass = jur_scene_passes(nr_cur, rp_cur, cap, fov ? htimec : NULL, pass, NULL, NULL);   /* (within nmax, kmax: jur_scene_pass_reserve) */
+        ntpass = jur_trial_passes(nr_cur, rin->nlam, cap, fov ? htimec : NULL, tpass, NULL);
         e = hipMemcpyAsync(d_act, act, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_sraysc, sraysc, sizeof(int) * (size_t)(nl ? nl : 1), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_rpc, hrpc, sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
@@ -3222,7 +3166,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (cap < 4096) cap = 4096;
   }
   long nmax = 0;
-  long const npass = trial_passes(nr, ntrial, cap, fov ? geom[0] : NULL, pass, &nmax);
+  long const npass = jur_trial_passes(nr, ntrial, cap, fov ? geom[0] : NULL, pass, &nmax);
   if (npass < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
 
   hbase = (double *)malloc(sizeof(double) * nrow * (size_t)np0);

@@ -259,6 +259,91 @@ long jur_scene_fov_live(int nd, long nr, double const *time, double const *rad_i
   return count;
 }
 
+/* ---- passes of the scene entries: the two cuts and what a looping call reserves for them ----------------------------- */
+long jur_scene_passes(long nr, long const *rp, long cap, double const *time, long *pass, long *nmax, long *kmax) {
+  if (nr < 0 || cap < 1 || !rp) { jur_set_error("jur_scene_passes: bad arguments"); return JUR_EINVAL; }
+  long npass = 0, slots = 0, cols = 0;
+  for (long r0 = 0; r0 < nr;) {
+    long r1 = r0 + 1;
+    while (r1 < nr && (rp[r1 + 1] - rp[r0]) + (r1 + 1 - r0) <= cap) r1++;
+    while (time && r1 < nr && time[r1] == time[r1 - 1]) r1++;   /* (a field of view is set: to the end of the scan) */
+    long const n = (rp[r1] - rp[r0]) + (r1 - r0);
+    if (n > 0x7fffffffL) { jur_set_error("jur_scene_passes: a pass of 2^31 slots"); return JUR_EINVAL; }
+    if (n > slots) slots = n;
+    if (rp[r1] - rp[r0] > cols) cols = rp[r1] - rp[r0];
+    if (pass) pass[npass] = r0;
+    npass++;
+    r0 = r1;
+  }
+  if (pass) pass[npass] = nr;
+  if (nmax) *nmax = slots;
+  if (kmax) *kmax = cols;
+  return npass;
+}
+
+long jur_trial_passes(long nr, int ntrial, long cap, double const *time, long *pass, long *nmax) {
+  if (nr < 0 || ntrial < 1 || cap < 1) { jur_set_error("jur_trial_passes: bad arguments"); return JUR_EINVAL; }
+  long per = cap / ntrial, npass = 0, slots = 0;
+  if (per < 1) per = 1;
+  if (per > 0x7fffffffL / ntrial) per = 0x7fffffffL / ntrial;
+  for (long r0 = 0; r0 < nr;) {
+    long r1 = r0 + per < nr ? r0 + per : nr;
+    while (time && r1 < nr && time[r1] == time[r1 - 1]) r1++;   /* (a field of view is set: to the end of the scan) */
+    if ((r1 - r0) * ntrial > 0x7fffffffL) { jur_set_error("jur_trial_passes: a pass of 2^31 slots"); return JUR_EINVAL; }
+    if ((r1 - r0) * ntrial > slots) slots = (r1 - r0) * ntrial;
+    if (pass) pass[npass] = r0;
+    npass++;
+    r0 = r1;
+  }
+  if (pass) pass[npass] = nr;
+  if (nmax) *nmax = slots;
+  return npass;
+}
+
+int jur_scene_pass_reserve(long nr, long const *rp, long cap, int ntrial, double const *time, long *slots, long *cols) {
+  if (nr < 0 || cap < 1 || ntrial < 1 || !rp || !slots || !cols) { jur_set_error("jur_scene_pass_reserve: bad arguments"); return JUR_EINVAL; }
+  long const all = rp[nr] + nr, tall = nr * ntrial;
+  long jb, kb, tb;
+  if (time) {
+    /* A pass of the rays that remain is cut within the cap (or is one ray beyond it) and then extended to the end of its
+     * last scan, of which it already holds a ray: it grows by less than the largest scan.  Scans leave whole (a slice ends
+     * with all rays of its time stamp), so the scans that remain are the call's.  Room for the cap and one more scan, of
+     * either kind, and never more than all rays together; the first cut is one such cut. */
+    long scan_slots = 0, scan_cols = 0, scan_rays = 0;
+    for (long r0 = 0, r1; r0 < nr; r0 = r1) {
+      for (r1 = r0 + 1; r1 < nr && time[r1] == time[r0]; r1++);
+      if ((rp[r1] - rp[r0]) + (r1 - r0) > scan_slots) scan_slots = (rp[r1] - rp[r0]) + (r1 - r0);
+      if (rp[r1] - rp[r0] > scan_cols) scan_cols = rp[r1] - rp[r0];
+      if (r1 - r0 > scan_rays) scan_rays = r1 - r0;
+    }
+    jb = cap < all - scan_slots ? cap + scan_slots : all;
+    kb = cap < rp[nr] - scan_cols ? cap + scan_cols : rp[nr];
+    tb = cap / ntrial + 1 + scan_rays < nr ? (cap / ntrial + 1 + scan_rays) * ntrial : tall;
+  } else {
+    /* jur_scene_passes extends a pass only while its slots stay within the cap, so a pass of any subset of the rays is
+     * within the cap -- and within all rays together -- or is one ray whose width + 1 slots alone exceed the cap; that
+     * ray is in the call and went alone in the first cut too.  Hence slots <= max(min(cap, all), widest ray + 1).  A pass
+     * within the cap spends one slot per ray on the unperturbed ray, so its block columns are at most cap - 1, and at
+     * most all columns together; the one ray beyond the cap has its own width: columns <= max(min(cap - 1, rp[nr]),
+     * widest ray).  The greedy cut of a subset can reach these where the first cut does not: rays that it kept apart
+     * become neighbours once the rays between them have left.  jur_trial_passes takes max(cap / ntrial, 1) rays per pass,
+     * whatever they are, so on fewer rays no pass has more: min(that, nr) rays, as in the first cut. */
+    long wide = 0;
+    for (long r = 0; r < nr; r++) if (rp[r + 1] - rp[r] > wide) wide = rp[r + 1] - rp[r];
+    jb = cap < all ? cap : all;
+    if (nr > 0 && wide + 1 > jb) jb = wide + 1;
+    kb = cap - 1 < rp[nr] ? cap - 1 : rp[nr];
+    if (wide > kb) kb = wide;
+    long per = cap / ntrial;
+    if (per < 1) per = 1;
+    if (per > 0x7fffffffL / ntrial) per = 0x7fffffffL / ntrial;
+    tb = (per < nr ? per : nr) * ntrial;
+  }
+  *slots = jb > tb ? jb : tb;
+  *cols = kb;
+  return JUR_OK;
+}
+
 /* ---- posterior diagnostics (jur_diagnose_slices_host, jur_diagnose_scene_host): the host arithmetic ------------------ */
 int jur_diag_check_out(char const *who, jur_diag_out_t const *out) {
   if (!out) { jur_set_error("%s: null argument (out)", who); return JUR_EINVAL; }

@@ -142,6 +142,12 @@ def lib():
             L.jur_prior_corr_host.argtypes = [C.c_void_p, C.c_long, lp_, ip_, dp, dp, C.c_int, dp, dp, dp, ip_]
         L.jur_scene_fov_live.restype = C.c_long
         L.jur_scene_fov_live.argtypes = [C.c_int, C.c_long, dp, dp, C.POINTER(C.c_ubyte)]
+        if hasattr(L, "jur_scene_passes"):           # (an A/B library from before the pass rules were exported has none)
+            L.jur_scene_passes.restype = C.c_long
+            L.jur_scene_passes.argtypes = [C.c_long, lp_, C.c_long, dp, lp_, lp_, lp_]
+            L.jur_trial_passes.restype = C.c_long
+            L.jur_trial_passes.argtypes = [C.c_long, C.c_int, C.c_long, dp, lp_, lp_]
+            L.jur_scene_pass_reserve.argtypes = [C.c_long, lp_, C.c_long, C.c_int, dp, lp_, lp_]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -1174,6 +1180,50 @@ def scene_fov_live(time, rad_in):
     n = _chk(lib().jur_scene_fov_live(rad.shape[1], len(time), _p(time), _p(rad), live.ctypes.data_as(C.POINTER(C.c_ubyte))))
     assert n == int(live.sum())
     return live.astype(bool)
+
+
+def _pass_args(nr, time):
+    if time is None:
+        return None, None
+    time = np.ascontiguousarray(time, dtype=np.float64)
+    if time.shape != (nr,):
+        raise ValueError("time must be (%d,)" % nr)
+    return time, _p(time)
+
+
+def scene_passes(rowptr, cap, time=None):
+    """The passes of the Jacobian entries of a scene (jur_scene_passes; host arithmetic, no GPU): rowptr (nr + 1,) as
+    scene_layout gives it, cap >= 1 slots per pass, time (nr,) while a field of view is set -> (pass, nmax, kmax): the
+    boundaries (npass + 1,) int64, first 0 and last nr, and the slots and block columns of the largest pass."""
+    rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+    nr = len(rp) - 1
+    time, tp = _pass_args(nr, time)
+    lp_ = C.POINTER(C.c_long)
+    pas = np.zeros(nr + 1, dtype=np.int64)
+    nmax, kmax = C.c_long(0), C.c_long(0)
+    n = _chk(lib().jur_scene_passes(nr, rp.ctypes.data_as(lp_), int(cap), tp, pas.ctypes.data_as(lp_), C.byref(nmax), C.byref(kmax)))
+    return pas[:n + 1].copy(), nmax.value, kmax.value
+
+
+def trial_passes(nr, ntrial, cap, time=None):
+    """The trial passes of a scene (jur_trial_passes; host arithmetic, no GPU): ntrial slots per ray -> (pass, nmax) as
+    scene_passes."""
+    time, tp = _pass_args(nr, time)
+    pas = np.zeros(nr + 1, dtype=np.int64)
+    nmax = C.c_long(0)
+    n = _chk(lib().jur_trial_passes(nr, int(ntrial), int(cap), tp, pas.ctypes.data_as(C.POINTER(C.c_long)), C.byref(nmax)))
+    return pas[:n + 1].copy(), nmax.value
+
+
+def scene_pass_reserve(rowptr, cap, ntrial, time=None):
+    """What Model.retrieve_scene allocates for its passes (jur_scene_pass_reserve; host arithmetic, no GPU) -> (slots,
+    cols): bounds for every pass of either kind, cut anew on the rays that ended slices leave."""
+    rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+    nr = len(rp) - 1
+    time, tp = _pass_args(nr, time)
+    slots, cols = C.c_long(0), C.c_long(0)
+    _chk(lib().jur_scene_pass_reserve(nr, rp.ctypes.data_as(C.POINTER(C.c_long)), int(cap), int(ntrial), tp, C.byref(slots), C.byref(cols)))
+    return slots.value, cols.value
 
 
 def formod_pencil(ctl, atm, obs, ir):
