@@ -570,6 +570,61 @@ int  jur_prior_corr_host(jur_model_t *m, long nslice, long const *wptr,
                          int nq, double const *cz,                              /* [nq] correlation length per quantity, 0: uncorrelated */
                          double *R, double *Sa /* optional */, int *status /* [nslice] */);
 
+/* Hydrostatic balance per slice in the scene entries.  ctl->hydz >= 0 makes formod() balance all points of the atmosphere
+ * as ONE profile (hydrostatic_1d_h2o over 0..np), which couples every profile of a scene: the six scene entries refuse it,
+ * now as before.  A retrieval of a scene wants upstream's other routine, hydrostatic() (jurassic.c:263-276), which balances
+ * every profile on its own: a raised T element then moves the pressures of its own slice only, and the blocks, the sums
+ * per slice, the independent systems and the trial passes keep their structure.  The model holds the switch as it holds
+ * the field of view; off (the default) every entry launches what it launched before and returns the same bits.
+ *
+ * jur_scene_hydrostatic (host arithmetic, no GPU): the rule.  For every segment [sfirst[q], sfirst[q] + slen[q]) of two
+ *   points or more, hydrostatic_1d_h2o (jr_common.h:713-761) on those points in the reference's order: the reference
+ *   parcel ipref is the first point of the segment with the smallest |z - hydz| (strict <: a tie goes to the lower index),
+ *   lat is lat[ipref], every layer takes the 20-term mean (i ascending) and p[to] = p[from] * exp(-1000 * mean * (z[to] -
+ *   z[from])), the points above ipref upwards in index, then the points below downwards.  e is the H2O mixing ratio of
+ *   the emitter jur_model_set_atm's step reads: the one named "H2O" when ctl->ctm_h2o is set, otherwise e = 0.  Only
+ *   out->p is written (out may be in); p[ipref] keeps its value, so a second balance returns the same bits.  Segments of
+ *   fewer than two points are left alone.  JUR_EINVAL, naming what is wrong: hydz negative or not finite; a segment
+ *   outside 0..np; two segments of two points or more that share a point (both are named).
+ * jur_scene_ray_slices (host arithmetic, no GPU): the distinct slices (first, len >= 2) that rays with the time stamps
+ *   time[nr] are traced through, in the order the rays first meet them, whether or not they hold state elements (a ray
+ *   of width 0 is traced through the base atmosphere and sees balanced pressures too); outputs may be NULL, room for nr
+ *   entries each.  Returns their number.  This is the list the entries and jur_scene_hydrostatic_host balance.
+ * jur_model_set_scene_hydz: the reference altitude [km]; a negative value switches the balance off (the default), NaN
+ *   or infinity is JUR_EINVAL.  jur_model_scene_hydz: what is set (-1: off).  An atmosphere that jur_model_set_atm
+ *   uploaded under one setting is not taken for current under another.
+ * jur_scene_hydrostatic_host: atm_out = atm_in with p replaced by the balanced pressures on the ray slices of the rays
+ *   with time stamps time[nr], formed by the one device kernel every entry launches (jur_scene_hydro_kernel: a wavefront
+ *   per segment, the parcel from a fixed reduction over (|z - hydz|, index), the layers' factors dealt out over the lanes,
+ *   the two chains sequential products in the reference's order; no atomics, every double a function of its own segment's
+ *   inputs alone).  atm_out may be atm_in.  JUR_EINVAL when the switch is off; otherwise jur_scene_hydrostatic's
+ *   refusals.  The model's atmosphere and workspace are untouched; the call is ordered against the model's other calls as
+ *   jur_solve_slices_host is.  Against the host rule the pressures differ by the two exp and sin implementations alone
+ *   (below 1e-12 relative over 150 levels; DESIGN.md has the measured figure).
+ * The six scene entries while the switch is on, B(a) standing for jur_scene_hydrostatic_host(m, a, nr, geom[0], .):
+ *   Overlapping ray slices are JUR_EINVAL before anything is launched; the model holds atm (atm0) afterwards.  The base
+ *   rows on the device are balanced once over the ray slices before the first pass; the caller's atm is never written.
+ *   rad, tau, tp and np_out are the doubles of jur_formod_host on B(atm) (a field of view, if set, applied afterwards as
+ *   above).  After the stacking, the copies whose raised row is p, T or the H2O row are balanced again; the step h of a
+ *   copy is the usual rule on the balanced base value.  Block entry (id, e) is (y1 - y0) / h with y1 the forward model on
+ *   B(B(atm) with element e raised by h).  A p element that is not the reference parcel of its slice is overwritten by
+ *   the balance: its block column is exactly +0.0 and the element is dead under the solve's D_i > 0 rule unless a prior
+ *   holds it (upstream's kernel() behaves the same way): the sensible retrieval window for p holds the reference level
+ *   only.  The sums, costs, steps and diagnostics follow from these blocks as their text says.  Trial copies are balanced
+ *   after the elements have moved and before the trial rays: cost[t][s] is jur_normal_scene_host's cost on the atmosphere
+ *   with dx[t] written back, the switch on.  In jur_retrieve_scene_host the base segments are balanced again after the
+ *   accepted steps have been added; prior_dx = xa - x and x read the base rows as they then stand.  atm_ret is atm0 with
+ *   the retrieved elements replaced and p replaced by the balanced pressure at every point of a ray slice (slices that
+ *   ended early included; points in no ray slice untouched), so "rad is jur_formod_host on atm_ret" stays true without a
+ *   balance in the forward entries; the model holds atm_ret afterwards, and atm as given after every other entry.
+ *   Nothing depends on max_rays_per_pass; the field of view and the full prior precision work unchanged beside the
+ *   balance.  The segment lists enter every entry's JUR_ENOMEM accounting, the kernel's time jur_model_last_scene_ms. */
+int    jur_scene_hydrostatic(ctl_t const *ctl, double hydz, atm_t const *in, long nseg, int const *sfirst, int const *slen, atm_t *out);
+long   jur_scene_ray_slices(ctl_t const *ctl, atm_t const *atm, long nr, double const *time, int *sfirst, int *slen);
+int    jur_model_set_scene_hydz(jur_model_t *m, double hydz);
+double jur_model_scene_hydz(jur_model_t const *m);
+int    jur_scene_hydrostatic_host(jur_model_t *m, atm_t const *atm_in, long nr, double const *time, atm_t *atm_out);
+
 /* intpol_atm with an error code instead of exit(): JUR_EINVAL for what upstream aborts on (profiles of one point,
  * profiles more than 10 degrees apart, unknown IP).  One lane per destination point on `device`. */
 int  jur_intpol_atm(ctl_t const *ctl, atm_t *dest, atm_t const *src, int device);

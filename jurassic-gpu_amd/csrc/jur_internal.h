@@ -410,6 +410,20 @@ typedef struct {
 } jur_scene_fov_t;
 int jurk_scene_fov(jur_scene_fov_t const *a, void *stream);
 
+/* Hydrostatic balance of the segments of a scene (jur_model_set_scene_hydz): segment i is the points [at[i], at[i] +
+ * len[i]) of the rows given -- of the base rows [nrow][np0] or of the stacked rows [nrow][nt].  One wavefront per segment;
+ * p alone is written, and p of the segment's reference parcel is not.  All arrays are device memory. */
+typedef struct {
+  long nseg;
+  long const *at;               /* [nseg] first point of every segment within a row                        */
+  int const *len;               /* [nseg] points of every segment; fewer than 2: left alone                 */
+  double const *z, *lat, *t;    /* rows                                                                    */
+  double const *q;              /* the H2O row, or NULL: dry air                                           */
+  double *p;                    /* the pressure row, written                                               */
+  double hydz;
+} jur_scene_hydro_t;
+int jurk_scene_hydro(jur_scene_hydro_t const *a, void *stream);
+
 /* host arithmetic shared by jur_model.c and jur_scene.c (not exported) */
 #define JUR_HIDDEN __attribute__((visibility("hidden")))
 JUR_HIDDEN int jur_atm_slice(double const *time, long n, double t, long *first);
@@ -419,6 +433,15 @@ JUR_HIDDEN long jur_scene_slice_elements(ctl_t const *ctl, atm_t const *atm, int
  * share the first point */
 typedef struct { int first, len, next; long nel; } jur_scene_slice_t;
 JUR_HIDDEN long jur_scene_distinct(int np, long nr, int const *first, int const *len, long const *rp, int *sid, jur_scene_slice_t **out);
+
+/* hydrostatic_1d_h2o on one profile of n points (jur_scene.c): what jur_model_set_atm's step and jur_scene_hydrostatic
+ * both run; qh2o == NULL: dry air */
+JUR_HIDDEN void jur_hydrostatic_profile(double hydz, int n, double const *z, double const *lat, double const *t, double const *qh2o,
+                                        double *p);
+/* the refusals of a balance's segments (outside 0..np; two segments of two points or more that share a point), and the
+ * distinct slices of two points or more among the rays' (first, len) */
+JUR_HIDDEN int jur_scene_hydro_check(char const *who, int np, long nseg, int const *sfirst, int const *slen);
+JUR_HIDDEN long jur_scene_ray_slices_of(int np, long nr, int const *first, int const *len, int *sfirst, int *slen);
 
 /* internals of a model that jur_multi.c needs (jur_model.c) */
 /* jur_formod_device on rays that are part of larger arrays: geometry field k at d_geom + k * ldg, tangent-point field k

@@ -30,6 +30,7 @@
 //                         same device functions as the three batched kernels, bit-identical results.
 //   jur_fov_kernel        field-of-view convolution of device arrays (formod_fov, jurassic.c:214-258).
 //   jur_scene_fov_kernel  the same convolution on the replicated rays of a pass of the scene entries, a workgroup per ray.
+//   jur_scene_hydro_kernel  hydrostatic balance of the slices of a scene, one wavefront per segment (jur_model_set_scene_hydz).
 //   jur_intpol_kernel     regridding of a track / point-cloud atmosphere (intpol_atm, jurassic.c:675-804).
 //   jur_kat_*_kernel      known-answer hooks for tests: the device functions on arrays of inputs.
 //
@@ -2481,6 +2482,82 @@ __global__ __launch_bounds__(256) void jur_scene_stack_kernel(jur_scene_stack_t 
   }
 }
 
+// ---- hydrostatic balance of the slices of a scene (jur_model_set_scene_hydz) ------------------------------------------
+// One wavefront per segment [at, at + len) of the rows: hydrostatic_1d_h2o (jr_common.h:713-761) on that profile alone, the
+// host rule of jur_scene_hydrostatic operand for operand (this file is compiled without contraction).
+//  (a) the reference parcel: every lane keeps the first minimum of |z - hydz| over its points i = lane, lane + 64, ...
+//      (strict <, ascending i), then a fixed xor tree over (distance, index) in which the lower index wins a tie: the
+//      first minimal index of the segment, whatever the lanes' order -- the host's `if (dz < dzmin)` scan.
+//  (b) layer l joins the points l and l + 1.  From the parcel upwards it is integrated from l to l + 1, below it from
+//      l + 1 to l, as the reference's two loops do.  Lane j of a chunk takes the j-th layer above the parcel and the j-th
+//      below it and forms f = exp(-1000 * mean * dz) with the 20 terms of the mean ascending; the latitude's two sines
+//      and the altitude-free part of gravity() are formed once per segment.
+//  (c) the factors lie in LDS, 64 of either direction at a time.  Lane 0 runs the upward chain p[ip] = p[ip - 1] * f and
+//      lane 1 the downward one, each a sequential product in the reference's order (a scan would round differently), and
+//      leave the pressures in LDS; all lanes then store them.
+// p of the parcel is never written and no f depends on a pressure, so a second balance of a balanced segment gives the
+// same bits.  No atomics; a double depends on its own segment's inputs alone.
+__device__ inline double hydro_factor(jur_scene_hydro_t const &a, long base, int from, int to, double g0) {
+  double const mmair = 28.96456e-3, mmh2o = 18.0153e-3;
+  double const zf = a.z[base + from], zt = a.z[base + to], tf = a.t[base + from], tt = a.t[base + to];
+  double const qf = a.q ? a.q[base + from] : 0., qt = a.q ? a.q[base + to] : 0.;
+  double mean = 0., e = 0.;
+  for (int i = 0; i < 20; i++) {
+    double const x = (double)i;
+    double const zz = zf + (x - 0.0) * (zt - zf) / (19.0 - 0.0);
+    double const grav = g0 - 3.086e-3 * zz;
+    if (a.q) e = qf + (x - 0.0) * (qt - qf) / (19.0 - 0.0);
+    double const temp = tf + (x - 0.0) * (tt - tf) / (19.0 - 0.0);
+    mean += (e * mmh2o + (1 - e) * mmair) * grav / (JUR_MOLAR_GAS * temp * 20);
+  }
+  return exp(-1000 * mean * (zt - zf));
+}
+
+__global__ __launch_bounds__(64) void jur_scene_hydro_kernel(jur_scene_hydro_t a) {
+  __shared__ double up[64], down[64];
+  long const seg = blockIdx.x;
+  int const lane = threadIdx.x, n = a.len[seg];
+  if (n < 2) return;
+  long const base = a.at[seg];
+  // (a)
+  double best = 1e99;
+  int ipref = 0x7fffffff;
+  for (int i = lane; i < n; i += 64) {
+    double const dz = fabs(a.z[base + i] - a.hydz);
+    if (dz < best) { best = dz; ipref = i; }
+  }
+  for (int m = 1; m < 64; m <<= 1) {
+    double const ob = __shfl_xor(best, m, 64);
+    int const oi = __shfl_xor(ipref, m, 64);
+    if (ob < best || (ob == best && oi < ipref)) { best = ob; ipref = oi; }
+  }
+  if (ipref == 0x7fffffff) ipref = 0;               // (no distance below 1e99: the host's initial value)
+  // (b)
+  double const deg2rad = M_PI / 180., lat = a.lat[base + ipref];
+  double const sx = sin(lat * deg2rad), sy = sin(2 * lat * deg2rad);
+  double const g0 = 9.780318 * (1. + 0.0053024 * sx * sx - 5.8e-6 * sy * sy);
+  int const nup = n - 1 - ipref, ndown = ipref;     // layers above and below the parcel
+  double pu = a.p[base + ipref], pd = pu;           // (lanes 0 and 1 carry the chains)
+  for (int c = 0; c < nup || c < ndown; c += 64) {
+    int const j = c + lane;
+    if (j < nup) up[lane] = hydro_factor(a, base, ipref + j, ipref + j + 1, g0);
+    if (j < ndown) down[lane] = hydro_factor(a, base, ipref - j, ipref - j - 1, g0);
+    __syncthreads();
+    // (c)
+    if (lane < 2) {
+      double *const f = lane ? down : up;
+      int const left = (lane ? ndown : nup) - c, m = left < 64 ? left : 64;
+      double pr = lane ? pd : pu;
+      for (int i = 0; i < m; i++) { pr = pr * f[i]; f[i] = pr; }
+      if (lane) pd = pr; else pu = pr;
+    }
+    __syncthreads();
+    if (j < nup) a.p[base + ipref + j + 1] = up[lane];
+    if (j < ndown) a.p[base + ipref - j - 1] = down[lane];
+    __syncthreads();
+  }
+}
+
 // slot of ray r in the pass that starts at ray r0
 __device__ inline long scene_slot(jur_scene_pass_t const &a, long r) { return (a.rowptr[r] - a.rowptr[a.r0]) + (r - a.r0); }
 
@@ -3355,6 +3432,12 @@ static unsigned scene_grid(long lanes) { return (unsigned)((lanes + 255) / 256);
 extern "C" int jurk_scene_stack(jur_scene_stack_t const *a, void *stream) {
   if (a->nt <= 0) return 0;
   hipLaunchKernelGGL(jur_scene_stack_kernel, dim3(scene_grid(a->nt)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_hydro(jur_scene_hydro_t const *a, void *stream) {
+  if (a->nseg <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_hydro_kernel, dim3((unsigned)a->nseg), dim3(64), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

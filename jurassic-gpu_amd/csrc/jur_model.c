@@ -98,6 +98,8 @@ struct jur_model {
   long *pp_wptr;                /* wptr[pp_nslice + 1] | aptr[pp_nslice + 1], malloc'ed */
   double *pp_R;                 /* host copy, what jur_model_prior_precision returns */
   void *d_pp;                   /* device: the same 2 (pp_nslice + 1) longs, then R */
+  double scene_hydz;            /* hydrostatic balance of the scene entries per slice (jur_model_set_scene_hydz): the
+                                   reference altitude [km], negative: off                                   */
   double *d_kq, *h_kq;          /* jur_kernel: perturbation steps and dense difference quotients (device, pinned host) */
   long kq_cap;
   /* small calls: the fused kernel (jur_pencil_kernel) instead of sort + three batched kernels */
@@ -176,6 +178,7 @@ int jur_model_create(jur_model_t **out, ctl_t const *ctl, jur_tables_t const *tb
   jur_model_t *m = (jur_model_t *)calloc(1, sizeof *m);
   if (!m) return JUR_ENOMEM;
   m->device = device;
+  m->scene_hydz = -1;
   m->ctl = (ctl_t *)malloc(sizeof(ctl_t));
   if (!m->ctl) { free(m); return JUR_ENOMEM; }
   memcpy(m->ctl, ctl, sizeof(ctl_t));
@@ -343,39 +346,10 @@ void jur_model_destroy(jur_model_t *m) {
 }
 
 /* ---- hydrostatic adjustment on the host (jr_common.h:212-217, 713-761) ------ */
-static double gravity(double z, double lat) {
-  double const deg2rad = M_PI / 180., x = sin(lat * deg2rad), y = sin(2 * lat * deg2rad);
-  return 9.780318 * (1. + 0.0053024 * x * x - 5.8e-6 * y * y) - 3.086e-3 * z;
-}
-
-static double lin(double x0, double y0, double x1, double y1, double x) { return y0 + (x - x0) * (y1 - y0) / (x1 - x0); }
-
-static void layer_pressure(double const *z, double const *t, double const *qh2o, double *p, double lat, int from, int to) {
-  /* integrates the hydrostatic equation across one layer with 20 sub-points */
-  int const npts = 20;
-  double const mmair = 28.96456e-3, mmh2o = 18.0153e-3;
-  double mean = 0., e = 0.;
-  for (int i = 0; i < npts; i++) {
-    double const zz = lin(0.0, z[from], npts - 1.0, z[to], (double)i);
-    double const grav = gravity(zz, lat);
-    if (qh2o) e = lin(0.0, qh2o[from], npts - 1.0, qh2o[to], (double)i);
-    double const temp = lin(0.0, t[from], npts - 1.0, t[to], (double)i);
-    mean += (e * mmh2o + (1 - e) * mmair) * grav / (JUR_MOLAR_GAS * temp * npts);
-  }
-  p[to] = p[from] * exp(-1000 * mean * (z[to] - z[from]));
-}
-
+/* (the arithmetic is jur_hydrostatic_profile's, jur_scene.c: one text for formod()'s adjustment and the scene entries') */
 static void hydrostatic(ctl_t const *ctl, int ig_h2o, int n, double const *z, double const *lat, double const *t,
                         double const *qh2o, double *p) {
-  double dzmin = 1e99;
-  int ipref = 0;
-  for (int ip = 0; ip < n; ip++) {
-    double const dz = fabs(z[ip] - ctl->hydz);
-    if (dz < dzmin) { dzmin = dz; ipref = ip; }
-  }
-  double const *q = (ig_h2o >= 0) ? qh2o : NULL;
-  for (int ip = ipref + 1; ip < n; ip++) layer_pressure(z, t, q, p, lat[ipref], ip - 1, ip);
-  for (int ip = ipref - 1; ip >= 0; ip--) layer_pressure(z, t, q, p, lat[ipref], ip + 1, ip);
+  jur_hydrostatic_profile(ctl->hydz, n, z, lat, t, (ig_h2o >= 0) ? qh2o : NULL, p);
 }
 
 /* Host image of an atmosphere: rows time, z, lon, lat, p, T, q[ng], k[nw], each n long. */
@@ -1512,6 +1486,39 @@ int jur_model_fov(jur_model_t const *m, int *n, double *dz, double *w) {
   return JUR_OK;
 }
 
+/* ---- hydrostatic balance of the scene entries, slice by slice ------------------------------ */
+int jur_model_set_scene_hydz(jur_model_t *m, double hydz) {
+  char const *const who = "jur_model_set_scene_hydz";
+  if (!m) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if (!(hydz - hydz == 0)) { jur_set_error("%s: hydz is %g: not finite (a negative value switches the balance off)", who, hydz); return JUR_EINVAL; }
+  double const v = hydz >= 0 ? hydz : -1;
+  /* what set_atm last uploaded was uploaded under the old setting: never taken for current under the new one */
+  if (v != m->scene_hydz) m->h_atm_n = 0;
+  m->scene_hydz = v;
+  return JUR_OK;
+}
+
+double jur_model_scene_hydz(jur_model_t const *m) { return m ? m->scene_hydz : -1; }
+
+static int scene_timed_begin(jur_model_t *m, hipStream_t s);
+static void scene_timed_end(jur_model_t *m, int ti, hipStream_t s);
+
+/* jur_scene_hydro_kernel on nseg segments (d_at, d_len: device) of rows [nrow][ld] as the model lays an atmosphere out:
+ * time, z, lon, lat, p, T, q[ng], k[nw].  Timed with the scene entries' kernels. */
+static int scene_hydro_launch(jur_model_t *m, hipStream_t s, long nseg, long const *d_at, int const *d_len, double *rows, size_t ld) {
+  if (nseg <= 0) return 0;
+  int const ig = m->view.ig_h2o;
+  jur_scene_hydro_t hq;
+  memset(&hq, 0, sizeof hq);
+  hq.nseg = nseg; hq.at = d_at; hq.len = d_len; hq.hydz = m->scene_hydz;
+  hq.z = rows + 1 * ld; hq.lat = rows + 3 * ld; hq.p = rows + 4 * ld; hq.t = rows + 5 * ld;
+  hq.q = ig >= 0 ? rows + (6 + (size_t)ig) * ld : NULL;
+  int const ti = scene_timed_begin(m, s);
+  int const ek = jurk_scene_hydro(&hq, s);
+  scene_timed_end(m, ti, s);
+  return ek;
+}
+
 /* ---- full a-priori precision of the slices ------------------------------------------------ */
 static void prior_precision_drop(jur_model_t *m) {
   m->pp_nslice = 0;
@@ -2219,9 +2226,10 @@ typedef struct { jur_scene_fov_t k; double const *live; } scene_fov_t;
  * forms the prior terms (or zeroes them), traces the rays of every pass and continues the cost chains.  ps carries the
  * ray arrays of the call (or of its gathered rays); its r0, r1, n, geom, rad, atm_time and `above` are set here.  The
  * model's view is left on the trial atmosphere.  Nothing is waited for after the stacking. */
+/* nhy > 0 (the hydrostatic balance is on): the segments of the trial copies, balanced after the elements have moved. */
 static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, jur_scene_stack_t *sk, jur_scene_trial_t *st,
                      jur_scene_trial_pass_t *ps, long nb, long npass, long const *pass, long nmax, scene_fov_t *fv,
-                     jur_scene_pquad_t const *tq) {
+                     jur_scene_pquad_t const *tq, long nhy, long const *d_hyat, int const *d_hylen) {
   size_t const nrow = (size_t)sk->nrow;
   int const nd = ps->nd;
   int rc;
@@ -2231,6 +2239,11 @@ static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const
   int ti = scene_timed_begin(m, s);
   int ek = jurk_scene_stack(sk, s);
   if (!ek) ek = jurk_scene_elements(st, JUR_ELEM_APPLY, nb, s);
+  if (nhy > 0) {                                   /* (a timed launch of its own, between the two halves of this one) */
+    scene_timed_end(m, ti, s);
+    if (!ek) ek = scene_hydro_launch(m, s, nhy, d_hyat, d_hylen, (double *)m->d_atm, (size_t)sk->nt);
+    ti = scene_timed_begin(m, s);
+  }
   hipError_t e = hipMemsetAsync(ps->cost, 0, sizeof(double) * (size_t)ps->nslice * (size_t)ps->ntrial, s);
   if (!ek && e == hipSuccess) {
     if (st->ivar) {
@@ -2380,6 +2393,9 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   int const fov = m->fov_n > 0;                     /* a field of view is set: the radiances of every pass are convolved */
   double *hlive = NULL, *htimec = NULL;
   double const *d_R = NULL;                         /* the model's full prior precision on the device, where one is set */
+  int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: every slice is balanced on its own */
+  int *hyf = NULL;                                  /* the ray slices: first | len */
+  long *hyat = NULL, nrs = 0;                       /* the segment lists of the balance on the host: at | len (ints behind) */
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if (!first || !rp || !sid) { rc = JUR_ENOMEM; goto done; }
@@ -2404,6 +2420,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   }
 
   if (fov && (rc = scene_fov_mask(who, nd, nr, geom[0], rad, &hlive))) goto done;
+  if (hyd) {                                        /* the slices the rays are traced through, with or without elements */
+    if (!(hyf = (int *)malloc(sizeof(int) * 2 * NR))) { rc = JUR_ENOMEM; goto done; }
+    if ((nrs = jur_scene_ray_slices_of(np0, nr, first, len, hyf, hyf + NR)) < 0) { rc = JUR_ENOMEM; goto done; }
+    if ((rc = jur_scene_hydro_check(who, np0, nrs, hyf, hyf + NR))) goto done;
+  }
 
   /* the distinct slices that have state elements, in the order the rays meet them, and their copies: slice q is
    * raised element by element by the copies scopy[q] ... */
@@ -2508,31 +2529,41 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const fov_bytes = sizeof(double) * nfov;
   long const ncopy = ncopies + 1;
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)nt;
+  /* ... and the hydrostatic balance: its segment lists (first point and length each) of the base rows' ray slices, of
+   * the copies that raise p, T or H2O (at most all) and, in the loop, of the trial copies */
+  size_t const NH = hyd ? (size_t)nrs + (size_t)ncopies + (rt ? RL * RS : 0) : 0;
+  size_t const hy_bytes = (sizeof(long) + sizeof(int)) * NH;
   if (nt > 0x7fffffffL || (long)atm_bytes > m->ws_budget / 2) {
     jur_set_error("%s: the stacked atmosphere (%ld points, %zu bytes) exceeds the workspace budget: "
                   "call with the rays of fewer slices at a time", who, nt, atm_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
-  if (fov_bytes > 0 && (double)atm_bytes + (double)fov_bytes > (double)(m->ws_budget / 2)) {
+  if (hy_bytes > 0 && (double)atm_bytes + (double)hy_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("%s: the segment lists of the hydrostatic balance (%zu bytes) do not fit beside the stacked atmosphere (%zu "
+                  "bytes) in the workspace budget: call with the rays of fewer slices at a time", who, hy_bytes, atm_bytes);
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+  if (fov_bytes > 0 && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the field of view's arrays (%zu bytes) do not fit beside the stacked atmosphere (%zu bytes) "
                   "in the workspace budget: call with fewer rays at a time", who, fov_bytes, atm_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
-  if (acc_bytes > 0 && (double)atm_bytes + (double)fov_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
+  if (acc_bytes > 0 && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the normal matrices (%ld doubles) do not fit beside the stacked atmosphere (%zu bytes) "
                   "in the workspace budget: call with the rays of fewer slices at a time", who, na, atm_bytes + fov_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
-  if (sv_bytes > 0 && (double)atm_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes > (double)(m->ws_budget / 2)) {
+  if (sv_bytes > 0 && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the solver scratch (%zu bytes) does not fit beside the normal matrices (%ld doubles) and the stacked "
                   "atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, sv_bytes, na, atm_bytes);
     rc = JUR_ENOMEM;
     goto done;
   }
-  if (dg_bytes > 0 && (double)atm_bytes + (double)fov_bytes + (double)acc_bytes + (double)dg_bytes > (double)(m->ws_budget / 2)) {
+  if (dg_bytes > 0 && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes + (double)dg_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the factor, S, AVK and the vectors (%zu bytes) do not fit beside the normal matrices (%ld doubles) and the "
                   "stacked atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, dg_bytes, na, atm_bytes);
     rc = JUR_ENOMEM;
@@ -2549,7 +2580,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist : 0;
   size_t const rt_atm_bytes = looping ? sizeof(double) * (nrow + 1) * (size_t)pl.nt : 0;
   size_t const rt_bytes = sizeof(double) * (rt_dbl + rt_lng) + sizeof(int) * rt_int;
-  if (looping && (double)atm_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes + (double)rt_atm_bytes + (double)rt_bytes > (double)(m->ws_budget / 2)) {
+  if (looping && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes + (double)rt_atm_bytes + (double)rt_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and the loop's arrays (%zu bytes) do not fit beside the solver "
                   "scratch, the normal matrices and the stacked atmosphere (%zu bytes) in the workspace budget: call with the rays "
                   "of fewer slices at a time", who, pl.nt, rt_atm_bytes, rt_bytes, atm_bytes + acc_bytes + sv_bytes);
@@ -2564,7 +2595,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
      * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
      * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
-    long const avail = (m->ws_budget - (long)atm_bytes - (long)fov_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes) / 16;
+    long const avail = (m->ws_budget - (long)atm_bytes - (long)hy_bytes - (long)fov_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes) / 16;
     cap = avail / (long)slot_bytes;
     if (cap < 4096) cap = 4096;
   }
@@ -2612,6 +2643,19 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   for (int i = 0; i < np0; i++) { tmin = fmin(tmin, atm->time[i]); tmax = fmax(tmax, atm->time[i]); }
   for (long i = 0; i < nr; i++) { tmin = fmin(tmin, geom[0][i]); tmax = fmax(tmax, geom[0][i]); }
   double const span = (tmax - tmin) + 1.0;
+  /* the balance's segments: the ray slices in the base rows; the copies whose raised row the pressures depend on, in the
+   * stacked rows (the others inherit the balanced base: a second balance would return the same bits); every trial copy */
+  long nhc = 0, ntc = 0;
+  if (hyd) {
+    if (!(hyat = (long *)malloc((sizeof(long) + sizeof(int)) * (NH ? NH : 1)))) { rc = JUR_ENOMEM; goto done; }
+    int *const hylen = (int *)(hyat + NH);
+    int const row_h2o = m->view.ig_h2o >= 0 ? 6 + m->view.ig_h2o : -1;
+    for (long q = 0; q < nrs; q++) { hyat[q] = hyf[q]; hylen[q] = hyf[NR + (size_t)q]; }
+    for (long j = 1; j < ncopy; j++)
+      if (prow[j] == 4 || prow[j] == 5 || prow[j] == row_h2o) { hyat[nrs + nhc] = off[j]; hylen[nrs + nhc] = (int)(off[j + 1] - off[j]); nhc++; }
+    if (rt && ntiles)
+      for (long j = 1; j < pl.ncopy; j++) { hyat[nrs + nhc + ntc] = pl.off[j]; hylen[nrs + nhc + ntc] = (int)(pl.off[j + 1] - pl.off[j]); ntc++; }
+  }
 
   /* the device slab: doubles, then 64-bit integers, then 32-bit ones */
   size_t const nrd = NR * (size_t)nd;
@@ -2622,8 +2666,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
    * then sptr | tptr | wptr | aptr, then what the solve needs) */
   size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
                o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_dg = o_sv + nsv, o_fov = o_dg + ndg, o_rt = o_fov + nfov,
-               o_int = o_rt + rt_dbl + rt_lng;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad) */
-  size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int;   /* (the loop's ints follow the others) */
+               o_hy = o_rt + rt_dbl + rt_lng, o_int = o_hy + NH;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad; o_hy: the balance's first points) */
+  size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int + NH;   /* (the loop's ints follow the others, the balance's lengths those) */
   size_t const bytes = sizeof(double) * o_int + sizeof(int) * nint;
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
   hipStream_t const s = m->stream;
@@ -2660,7 +2704,15 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (e == hipSuccess) e = hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
     }
     if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_fov, hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    long const *const d_hyat = L + o_hy;
+    int const *const d_hylen = I + nint0 + rt_int;
+    if (NH && e == hipSuccess) e = hipMemcpyAsync(L + o_hy, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
+    if (NH && e == hipSuccess) e = hipMemcpyAsync(I + nint0 + rt_int, hyat + NH, sizeof(int) * NH, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    /* the base rows are balanced once, over the ray slices, before the first pass: the caller's atm is never written */
+    if (hyd && scene_hydro_launch(m, s, nrs, d_hyat, d_hylen, D + o_base, (size_t)np0)) {
+      jur_set_error("%s: hydrostatic kernel launch failed", who); rc = JUR_EHIP; goto done;
+    }
 
     double *const d_live = D + o_fov, *const d_ftau = d_live + nrd, *const d_livec = d_ftau + nrd, *const d_frad = d_livec + nrd;
     scene_fov_t fv;
@@ -2842,6 +2894,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     ti = scene_timed_begin(m, s);
     ek = jurk_scene_stack(&st, s);
     scene_timed_end(m, ti, s);
+    if (!ek && hyd) ek = scene_hydro_launch(m, s, nhc, d_hyat + nrs, d_hylen + nrs, (double *)m->d_atm, (size_t)nt);
     if (!ek) ek = jurk_prepare_atm(&m->view, (double *)m->d_atm + nrow * (size_t)nt, s);
     /* the one wait before the passes: the uploads have left the host arrays, the stacked rows stand */
     if (ek || hipStreamSynchronize(s) != hipSuccess) {
@@ -2891,7 +2944,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (!looping) break;
 
     /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
-    if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax, fov ? &fv : NULL, d_R ? &tqd : NULL))) goto done;
+    if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax, fov ? &fv : NULL, d_R ? &tqd : NULL,
+                        ntc, d_hyat + nrs + nhc, d_hylen + nrs + nhc))) goto done;
     e = hipMemcpyAsync(hcost, nq.cost, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hnlive, nq.nlive, sizeof(long) * RS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hprior0, d_prior0, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
@@ -2936,6 +2990,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       ti = scene_timed_begin(m, s);
       ek = jurk_scene_elements(&aq, JUR_ELEM_ACCEPT, nb, s);
       scene_timed_end(m, ti, s);
+      /* the base segments of the accepted slices are balanced; the others come back with the bits they have */
+      if (!ek && hyd) ek = scene_hydro_launch(m, s, nrs, d_hyat, d_hylen, D + o_base, (size_t)np0);
       if (ek || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); jur_set_error("%s: accepting the steps failed", who); rc = JUR_EHIP; goto done; }
     }
     }                                             /* (iterations) */
@@ -2946,6 +3002,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       atm_t *ret = (atm_t *)malloc(sizeof(atm_t));
       if (!ret) { rc = JUR_ENOMEM; goto done; }
       memcpy(ret, atm, sizeof(atm_t));
+      if (hyd) {                                    /* the balanced pressures of the base rows; outside the ray slices the caller's */
+        e = hipMemcpyAsync(ret->p, D + o_base + 4 * (size_t)np0, sizeof(double) * (size_t)np0, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipGetLastError(); free(ret); jur_set_error("%s: bringing the pressures home failed", who); rc = JUR_EHIP; goto done; }
+      }
       if (looping) {
         for (long q = 0; q < nslice; q++) if (ro->state[q] == JUR_RET_ACTIVE) ro->state[q] = JUR_RET_MAXITER;
         if (ro->h_cost)
@@ -3007,7 +3068,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
   free(first); free(rp); free(sid); free(srays); free(sl); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa);
-  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm); free(dmap); free(hlive); free(htimec);
+  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm); free(dmap); free(hlive); free(htimec); free(hyf); free(hyat);
   trial_plan_free(&pl);
   return rc;
 }
@@ -3110,6 +3171,9 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   jur_scene_slice_t *sl = NULL;
   double *hbase = NULL, *hlive = NULL;
   int const fov = m->fov_n > 0;                     /* a field of view is set: the trial radiances are convolved */
+  int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: base rows and trial copies are balanced */
+  int *hyf = NULL;
+  long *hyat = NULL, nrs = 0;
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if (!first || !rp) { rc = JUR_ENOMEM; goto done; }
@@ -3129,6 +3193,11 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
       }
     }
   if (fov && (rc = scene_fov_mask(who, nd, nr, geom[0], rad_in, &hlive))) goto done;
+  if (hyd) {                                        /* the slices the rays are traced through, with or without elements */
+    if (!(hyf = (int *)malloc(sizeof(int) * 2 * NR))) { rc = JUR_ENOMEM; goto done; }
+    if ((nrs = jur_scene_ray_slices_of(np0, nr, first, len, hyf, hyf + NR)) < 0) { rc = JUR_ENOMEM; goto done; }
+    if ((rc = jur_scene_hydro_check(who, np0, nrs, hyf, hyf + NR))) goto done;
+  }
   long const nslice = jur_scene_distinct(np0, nr, first, len, rp, sid, &sl);
   if (nslice < 0) { rc = JUR_ENOMEM; goto done; }
   if (nslice == 0) goto done;                         /* no state elements: nothing to write */
@@ -3152,7 +3221,8 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   size_t const ndv = d_R ? NT * NB : 0;               /* (a full prior precision: xa - (x + dx) of every trial) */
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)pl.nt;
   size_t const nfov = fov ? nrd : 0;                  /* (the effective mask) */
-  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov + ndv);
+  size_t const NH = hyd ? (size_t)nrs + NT * NS : 0;  /* (the balance's segments: the ray slices, every trial copy) */
+  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov + ndv) + (sizeof(long) + sizeof(int)) * NH;
   if ((double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and accumulators (%zu bytes) exceed the workspace budget: "
                   "call with fewer trials or the rays of fewer slices at a time", who, pl.nt, atm_bytes, acc_bytes);
@@ -3176,12 +3246,18 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   double tmin = atm->time[0], tmax = atm->time[0];
   for (int i = 0; i < np0; i++) { tmin = fmin(tmin, atm->time[i]); tmax = fmax(tmax, atm->time[i]); }
   for (long i = 0; i < nr; i++) { tmin = fmin(tmin, geom[0][i]); tmax = fmax(tmax, geom[0][i]); }
+  if (hyd) {
+    if (!(hyat = (long *)malloc((sizeof(long) + sizeof(int)) * (NH ? NH : 1)))) { rc = JUR_ENOMEM; goto done; }
+    int *const hylen = (int *)(hyat + NH);
+    for (long q = 0; q < nrs; q++) { hyat[q] = hyf[q]; hylen[q] = hyf[NR + (size_t)q]; }
+    for (long j = 1; j < pl.ncopy; j++) { hyat[nrs + j - 1] = pl.off[j]; hylen[nrs + j - 1] = (int)(pl.off[j + 1] - pl.off[j]); }
+  }
 
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_y = o_inrad + nrd, o_w = o_y + nrd,
                o_dx = o_w + nrd, o_r = o_dx + NT * NB, o_xa = o_r + npr, o_cost = o_xa + npr, o_prior = o_cost + NT * NS,
                o_live = o_prior + NT * NS, o_dv = o_live + nfov, o_long = o_dv + ndv,
-               o_int = o_long + pl.nlong;
-  size_t const bytes = sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR);
+               o_int = o_long + pl.nlong + NH;   /* (the balance's first points behind the plan's longs, its lengths behind the ints) */
+  size_t const bytes = sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR + NH);
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
   hipStream_t const s = m->stream;
   if ((rc = wait_done(m, s))) goto done;
@@ -3213,7 +3289,14 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (e == hipSuccess) e = hipMemcpyAsync(d_first, first, sizeof(int) * 2 * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
     if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_live, hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    long const *const d_hyat = L + pl.nlong;
+    int const *const d_hylen = d_len + NR;
+    if (NH && e == hipSuccess) e = hipMemcpyAsync(L + pl.nlong, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
+    if (NH && e == hipSuccess) e = hipMemcpyAsync(d_len + NR, hyat + NH, sizeof(int) * NH, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if (hyd && scene_hydro_launch(m, s, nrs, d_hyat, d_hylen, D + o_base, (size_t)np0)) {   /* the base rows, once */
+      jur_set_error("%s: hydrostatic kernel launch failed", who); rc = JUR_EHIP; goto done;
+    }
 
     scene_fov_t fv;
     memset(&fv, 0, sizeof fv);
@@ -3240,7 +3323,8 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
       tq.nslice = nslice; tq.nvec = ntrial; tq.wptr = d_wptr; tq.aptr = (long const *)m->d_pp + NS + 1; tq.R = d_R;
       tq.v = D + o_dv; tq.out = D + o_prior;
     }
-    if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax, fov ? &fv : NULL, d_R ? &tq : NULL))) goto done;
+    if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax, fov ? &fv : NULL, d_R ? &tq : NULL,
+                        hyd ? (long)(NT * NS) : 0, d_hyat + nrs, d_hylen + nrs))) goto done;
     e = hipMemcpyAsync(cost, D + o_cost, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(prior, D + o_prior, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
@@ -3251,7 +3335,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
-  free(first); free(rp); free(sl); free(hbase); free(hlive);
+  free(first); free(rp); free(sl); free(hbase); free(hlive); free(hyf); free(hyat);
   trial_plan_free(&pl);
   return rc;
 }
@@ -3262,6 +3346,81 @@ int jur_trial_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const
   if (!m || !atm) { jur_set_error("jur_trial_scene_host: null argument"); return JUR_EINVAL; }
   return scene_restore_atm(m, atm, trial_scene_body(m, atm, nr, geom, rad_in, rowptr, y, weight, ntrial, dx, prior_ivar, prior_xa,
                                                     cost, prior, max_rays_per_pass));
+}
+
+/* The balance alone, on an atmosphere the caller holds.  The device slab of the scene entries serves (it holds nothing
+ * between calls): the rows z | lat | p | T | q_H2O, then the segments' first points and lengths.  Neither the model's
+ * atmosphere nor the forward model's workspace is touched. */
+int jur_scene_hydrostatic_host(jur_model_t *m, atm_t const *atm_in, long nr, double const *time, atm_t *atm_out) {
+  char const *const who = "jur_scene_hydrostatic_host";
+  if (!m || !atm_in || !atm_out || nr < 0 || (nr > 0 && !time)) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  if (!(m->scene_hydz >= 0)) { jur_set_error("%s: the hydrostatic balance of the model is switched off (jur_model_set_scene_hydz)", who); return JUR_EINVAL; }
+  int const np = atm_in->np;
+  if (np < 2 || np > JUR_NP) { jur_set_error("%s: need 2..%d atmospheric points", who, JUR_NP); return JUR_EINVAL; }
+  size_t const NR = (size_t)(nr > 0 ? nr : 1), N = (size_t)np;
+  int rc = JUR_OK, enqueued = 0;
+  int *first = (int *)malloc(sizeof(int) * 4 * NR), *len = first ? first + NR : NULL, *sf = first ? len + NR : NULL, *sn = first ? sf + NR : NULL;
+  long *at = NULL;
+  double *h = NULL;
+  if (!first) { jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
+  for (long r = 0; r < nr; r++) {
+    long lo;
+    len[r] = jur_atm_slice(atm_in->time, np, time[r], &lo);
+    first[r] = (int)lo;
+  }
+  long const nseg = jur_scene_ray_slices_of(np, nr, first, len, sf, sn);
+  if (nseg < 0) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+  if ((rc = jur_scene_hydro_check(who, np, nseg, sf, sn))) goto done;
+  {
+    int const ig = m->view.ig_h2o;
+    size_t const NS = (size_t)nseg, o_at = 5 * N, o_len = o_at + NS;
+    size_t const bytes = sizeof(double) * o_len + sizeof(int) * (NS + 1);
+    at = (long *)malloc(sizeof(long) * (NS + 1));
+    h = (double *)malloc(sizeof(double) * 5 * N);
+    if (!at || !h) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+    for (long q = 0; q < nseg; q++) at[q] = sf[q];
+    memcpy(h, atm_in->z, sizeof(double) * N);
+    memcpy(h + N, atm_in->lat, sizeof(double) * N);
+    memcpy(h + 2 * N, atm_in->p, sizeof(double) * N);
+    memcpy(h + 3 * N, atm_in->t, sizeof(double) * N);
+    if (ig >= 0) memcpy(h + 4 * N, atm_in->q[ig], sizeof(double) * N);
+    if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
+    hipStream_t const s = m->stream;
+    if ((rc = wait_done(m, s))) goto done;
+    if (bytes > m->scene_bytes) {
+      if (m->d_scene) (void)hipFree(m->d_scene);
+      m->d_scene = NULL; m->scene_bytes = 0;
+      if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
+        (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
+      }
+      m->scene_bytes = bytes;
+    }
+    double *const D = (double *)m->d_scene;
+    long *const d_at = (long *)(D + o_at);
+    int *const d_len = (int *)(D + o_len);
+    enqueued = 1;
+    hipError_t e = hipMemcpyAsync(D, h, sizeof(double) * (ig >= 0 ? 5 : 4) * N, hipMemcpyHostToDevice, s);
+    if (nseg && e == hipSuccess) e = hipMemcpyAsync(d_at, at, sizeof(long) * NS, hipMemcpyHostToDevice, s);
+    if (nseg && e == hipSuccess) e = hipMemcpyAsync(d_len, sn, sizeof(int) * NS, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    jur_scene_hydro_t hq;
+    memset(&hq, 0, sizeof hq);
+    hq.nseg = nseg; hq.at = d_at; hq.len = d_len; hq.hydz = m->scene_hydz;
+    hq.z = D; hq.lat = D + N; hq.p = D + 2 * N; hq.t = D + 3 * N; hq.q = ig >= 0 ? D + 4 * N : NULL;
+    int const ti = scene_timed_begin(m, s);
+    int const ek = jurk_scene_hydro(&hq, s);
+    scene_timed_end(m, ti, s);
+    if (ek) { jur_set_error("%s: hydrostatic kernel launch failed", who); rc = JUR_EHIP; goto done; }
+    e = hipMemcpyAsync(h + 2 * N, D + 2 * N, sizeof(double) * N, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if (atm_out != atm_in) memcpy(atm_out, atm_in, sizeof(atm_t));
+    memcpy(atm_out->p, h + 2 * N, sizeof(double) * N);
+  }
+done:
+  if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
+  free(first); free(at); free(h);
+  return rc;
 }
 
 /* Systems the caller holds.  The device slab of the scene entries serves (it holds nothing between calls): wptr | aptr,

@@ -3,6 +3,8 @@
  * and which distinct slices a scene has.  Host arithmetic only: no GPU, no model. */
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
+#include <strings.h>
 #include "jur_internal.h"
 
 /* locate_atm (jr_common.h:127-154): the slice [*first, *first + return) of the n points with time stamps `time` that
@@ -499,4 +501,132 @@ int jur_avk_summary(ctl_t const *ctl, atm_t const *atm, int first, int len, doub
   }
   free(iq);
   return JUR_OK;
+}
+
+/* ---- hydrostatic balance: one profile (formod()'s adjustment) and the segments of a scene ---------------------------- */
+/* (jr_common.h:212-217) */
+static double gravity(double z, double lat) {
+  double const deg2rad = M_PI / 180., x = sin(lat * deg2rad), y = sin(2 * lat * deg2rad);
+  return 9.780318 * (1. + 0.0053024 * x * x - 5.8e-6 * y * y) - 3.086e-3 * z;
+}
+
+static double lin(double x0, double y0, double x1, double y1, double x) { return y0 + (x - x0) * (y1 - y0) / (x1 - x0); }
+
+static void layer_pressure(double const *z, double const *t, double const *qh2o, double *p, double lat, int from, int to) {
+  /* integrates the hydrostatic equation across one layer with 20 sub-points */
+  int const npts = 20;
+  double const mmair = 28.96456e-3, mmh2o = 18.0153e-3;
+  double mean = 0., e = 0.;
+  for (int i = 0; i < npts; i++) {
+    double const zz = lin(0.0, z[from], npts - 1.0, z[to], (double)i);
+    double const grav = gravity(zz, lat);
+    if (qh2o) e = lin(0.0, qh2o[from], npts - 1.0, qh2o[to], (double)i);
+    double const temp = lin(0.0, t[from], npts - 1.0, t[to], (double)i);
+    mean += (e * mmh2o + (1 - e) * mmair) * grav / (JUR_MOLAR_GAS * temp * npts);
+  }
+  p[to] = p[from] * exp(-1000 * mean * (z[to] - z[from]));
+}
+
+/* hydrostatic_1d_h2o (jr_common.h:713-761) on the n points of one profile: the pressures above and below the point
+ * nearest to hydz (the first of several) follow from it; qh2o == NULL: dry air */
+void jur_hydrostatic_profile(double hydz, int n, double const *z, double const *lat, double const *t, double const *qh2o,
+                             double *p) {
+  double dzmin = 1e99;
+  int ipref = 0;
+  for (int ip = 0; ip < n; ip++) {
+    double const dz = fabs(z[ip] - hydz);
+    if (dz < dzmin) { dzmin = dz; ipref = ip; }
+  }
+  for (int ip = ipref + 1; ip < n; ip++) layer_pressure(z, t, qh2o, p, lat[ipref], ip - 1, ip);
+  for (int ip = ipref - 1; ip >= 0; ip--) layer_pressure(z, t, qh2o, p, lat[ipref], ip + 1, ip);
+}
+
+/* the segments of a balance: inside 0..np, and no point in two segments of two points or more */
+int jur_scene_hydro_check(char const *who, int np, long nseg, int const *sfirst, int const *slen) {
+  if (np < 0 || nseg < 0 || (nseg > 0 && (!sfirst || !slen))) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  for (long q = 0; q < nseg; q++)
+    if (sfirst[q] < 0 || slen[q] < 0 || (long)sfirst[q] + slen[q] > np) {
+      jur_set_error("%s: segment %ld, [%d, %d + %d), lies outside the %d points of the atmosphere", who, q, sfirst[q], sfirst[q],
+                    slen[q], np);
+      return JUR_EINVAL;
+    }
+  long *owner = (long *)malloc(sizeof(long) * (size_t)(np > 0 ? np : 1));
+  if (!owner) { jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
+  for (int i = 0; i < np; i++) owner[i] = -1;
+  int rc = JUR_OK;
+  for (long q = 0; q < nseg && !rc; q++) {
+    if (slen[q] < 2) continue;
+    for (int i = sfirst[q]; i < sfirst[q] + slen[q]; i++) {
+      if (owner[i] >= 0) {
+        long const o = owner[i];
+        jur_set_error("%s: the segments %ld, [%d, %d), and %ld, [%d, %d), share point %d of the atmosphere: a hydrostatic balance "
+                      "of each would move the other's pressures", who, o, sfirst[o], sfirst[o] + slen[o], q, sfirst[q],
+                      sfirst[q] + slen[q], i);
+        rc = JUR_EINVAL;
+        break;
+      }
+      owner[i] = q;
+    }
+  }
+  free(owner);
+  return rc;
+}
+
+int jur_scene_hydrostatic(ctl_t const *ctl, double hydz, atm_t const *in, long nseg, int const *sfirst, int const *slen,
+                          atm_t *out) {
+  char const *const who = "jur_scene_hydrostatic";
+  if (!ctl || !in || !out) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if (!(hydz >= 0) || !(hydz - hydz == 0)) { jur_set_error("%s: hydz is %g: negative or not finite", who, hydz); return JUR_EINVAL; }
+  if (in->np < 0 || in->np > JUR_NP) { jur_set_error("%s: np = %d outside 0..%d", who, in->np, JUR_NP); return JUR_EINVAL; }
+  int const rc = jur_scene_hydro_check(who, in->np, nseg, sfirst, slen);
+  if (rc) return rc;
+  /* the emitter jur_model_set_atm's step reads */
+  int ig = -1;
+  if (ctl->ctm_h2o)
+    for (int g = 0; g < ctl->ng && ig < 0; g++)
+      if (0 == strcasecmp(ctl->emitter[g], "H2O")) ig = g;
+  if (out != in) memmove(out->p, in->p, sizeof(double) * (size_t)in->np);
+  for (long q = 0; q < nseg; q++) {
+    if (slen[q] < 2) continue;
+    int const a = sfirst[q];
+    jur_hydrostatic_profile(hydz, slen[q], in->z + a, in->lat + a, in->t + a, ig >= 0 ? in->q[ig] + a : NULL, out->p + a);
+  }
+  return JUR_OK;
+}
+
+/* the distinct slices of two points or more among (first[r], len[r]), in the order the rays first meet them */
+long jur_scene_ray_slices_of(int np, long nr, int const *first, int const *len, int *sfirst, int *slen) {
+  long *rp = (long *)malloc(sizeof(long) * ((size_t)nr + 1));
+  int *sid = (int *)malloc(sizeof(int) * (size_t)(nr > 0 ? nr : 1));
+  jur_scene_slice_t *sl = NULL;
+  long n = JUR_ENOMEM;
+  if (rp && sid) {
+    rp[0] = 0;
+    for (long r = 0; r < nr; r++) rp[r + 1] = rp[r] + (len[r] >= 2);   /* (jur_scene_distinct skips rays of width 0) */
+    n = jur_scene_distinct(np, nr, first, len, rp, sid, &sl);
+    for (long q = 0; q < n; q++) {
+      if (sfirst) sfirst[q] = sl[q].first;
+      if (slen) slen[q] = sl[q].len;
+    }
+  }
+  free(rp); free(sid); free(sl);
+  return n;
+}
+
+long jur_scene_ray_slices(ctl_t const *ctl, atm_t const *atm, long nr, double const *time, int *sfirst, int *slen) {
+  if (!ctl || !atm || nr < 0 || (nr > 0 && !time)) { jur_set_error("scene_ray_slices: bad arguments"); return JUR_EINVAL; }
+  int const np = atm->np;
+  if (np < 2 || np > JUR_NP) { jur_set_error("scene_ray_slices: need 2..%d atmospheric points", JUR_NP); return JUR_EINVAL; }
+  size_t const NR = (size_t)(nr > 0 ? nr : 1);
+  int *first = (int *)malloc(sizeof(int) * 2 * NR), *len = first ? first + NR : NULL;
+  if (!first) { jur_set_error("scene_ray_slices: out of memory"); return JUR_ENOMEM; }
+  for (long r = 0; r < nr; r++) {
+    long lo;
+    len[r] = jur_atm_slice(atm->time, np, time[r], &lo);
+    first[r] = (int)lo;
+  }
+  long const n = jur_scene_ray_slices_of(np, nr, first, len, sfirst, slen);
+  if (n < 0) jur_set_error("scene_ray_slices: out of memory");
+  free(first);
+  return n;
 }

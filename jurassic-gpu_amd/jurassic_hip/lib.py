@@ -140,6 +140,14 @@ def lib():
             L.jur_model_prior_precision.restype = C.c_long
             L.jur_model_prior_precision.argtypes = [C.c_void_p, lp_, dp]
             L.jur_prior_corr_host.argtypes = [C.c_void_p, C.c_long, lp_, ip_, dp, dp, C.c_int, dp, dp, dp, ip_]
+        if hasattr(L, "jur_scene_hydrostatic"):
+            L.jur_scene_hydrostatic.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_long, ip_, ip_, C.c_void_p]
+            L.jur_scene_ray_slices.restype = C.c_long
+            L.jur_scene_ray_slices.argtypes = [C.c_void_p, C.c_void_p, C.c_long, dp, ip_, ip_]
+            L.jur_model_set_scene_hydz.argtypes = [C.c_void_p, C.c_double]
+            L.jur_model_scene_hydz.restype = C.c_double
+            L.jur_model_scene_hydz.argtypes = [C.c_void_p]
+            L.jur_scene_hydrostatic_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, dp, C.c_void_p]
         L.jur_scene_fov_live.restype = C.c_long
         L.jur_scene_fov_live.argtypes = [C.c_int, C.c_long, dp, dp, C.POINTER(C.c_ubyte)]
         if hasattr(L, "jur_scene_passes"):           # (an A/B library from before the pass rules were exported has none)
@@ -447,6 +455,27 @@ class Model:
         R = np.zeros(int(ap[-1]))
         _chk(lib().jur_model_prior_precision(self.h, None, _p(R)))
         return dict(wptr=wp, aptr=ap, R=R)
+
+    def set_scene_hydz(self, hydz):
+        """Hydrostatic balance per slice in the scene entries (jur_model_set_scene_hydz): the reference altitude [km];
+        None or a negative value switches it off (the default).  While it is set kernel_scene, normal_scene, step_scene,
+        trial_scene, retrieve_scene and diagnose_scene run on the atmosphere scene_hydrostatic returns and balance every
+        perturbed and trial copy again (include/jurassic_hip.h)."""
+        _chk(lib().jur_model_set_scene_hydz(self.h, -1.0 if hydz is None else float(hydz)))
+
+    def scene_hydz(self):
+        """The reference altitude that is set, or None."""
+        v = lib().jur_model_scene_hydz(self.h)
+        return v if v >= 0 else None
+
+    def scene_hydrostatic(self, atm, time):
+        """jur_scene_hydrostatic_host: a new atm_t, atm with p balanced on the device over the slices that rays with the
+        time stamps `time` are traced through -- the atmosphere the scene entries work on while set_scene_hydz is on."""
+        t = np.ascontiguousarray(time, dtype=np.float64).ravel()
+        out = abi.atm_t()
+        C.memmove(C.byref(out), C.byref(atm), C.sizeof(abi.atm_t))
+        _chk(lib().jur_scene_hydrostatic_host(self.h, C.byref(atm), len(t), _p(t), C.byref(out)))
+        return out
 
     def kernel(self, atm, obs):
         """Forward-difference Jacobian (m, n); obs receives the unperturbed forward model."""
@@ -979,6 +1008,31 @@ def scene_slices(ctl, atm, time):
     _chk(lib().jur_scene_slices(C.byref(ctl), C.byref(atm), nr, _p(t), sid.ctypes.data_as(ip_), sfirst.ctypes.data_as(ip_),
                                 slen.ctypes.data_as(ip_), wptr.ctypes.data_as(lp_), aptr.ctypes.data_as(lp_)))
     return dict(sid=sid, sfirst=sfirst, slen=slen, wptr=wptr, aptr=aptr)
+
+
+def scene_ray_slices(ctl, atm, time):
+    """jur_scene_ray_slices (host arithmetic, no GPU): the distinct slices of two points or more that rays with these time
+    stamps are traced through, with or without state elements, in the order the rays first meet them
+    -> dict(sfirst, slen)."""
+    t = np.ascontiguousarray(time, dtype=np.float64).ravel()
+    ip_ = C.POINTER(C.c_int)
+    sfirst, slen = np.zeros(len(t), dtype=np.int32), np.zeros(len(t), dtype=np.int32)
+    n = _chk(lib().jur_scene_ray_slices(C.byref(ctl), C.byref(atm), len(t), _p(t), sfirst.ctypes.data_as(ip_), slen.ctypes.data_as(ip_)))
+    return dict(sfirst=sfirst[:n].copy(), slen=slen[:n].copy())
+
+
+def scene_hydrostatic(ctl, hydz, atm, sfirst, slen):
+    """jur_scene_hydrostatic (host arithmetic, no GPU): a new atm_t, atm with every segment [sfirst, sfirst + slen) of two
+    points or more balanced on its own around the point nearest to hydz (upstream's hydrostatic_1d_h2o per profile)."""
+    sf, sn = (np.ascontiguousarray(a, dtype=np.int32).ravel() for a in (sfirst, slen))
+    if len(sf) != len(sn):
+        raise ValueError("sfirst holds %d entries, slen %d" % (len(sf), len(sn)))
+    ip_ = C.POINTER(C.c_int)
+    out = abi.atm_t()
+    C.memmove(C.byref(out), C.byref(atm), C.sizeof(abi.atm_t))
+    _chk(lib().jur_scene_hydrostatic(C.byref(ctl), float(hydz), C.byref(atm), len(sf), sf.ctypes.data_as(ip_),
+                                     sn.ctypes.data_as(ip_), C.byref(out)))
+    return out
 
 
 def scene_elements(ctl, atm, first, length):
