@@ -625,6 +625,53 @@ int    jur_model_set_scene_hydz(jur_model_t *m, double hydz);
 double jur_model_scene_hydz(jur_model_t const *m);
 int    jur_scene_hydrostatic_host(jur_model_t *m, atm_t const *atm_in, long nr, double const *time, atm_t *atm_out);
 
+/* The scene Jacobian reused between the iterations of a retrieval (upstream's KERNEL_RECOMP).  The model holds the switch
+ * as it holds the field of view; with every == 1 (the default) jur_retrieve_scene_host allocates and launches what it did
+ * before and returns the same bits.  Only jur_retrieve_scene_host honours it.
+ *
+ * jur_model_set_kernel_recomp: the Jacobian is recomputed every `every`-th iteration; every < 1 is JUR_EINVAL.
+ *   jur_model_kernel_recomp: what is set.  Iteration `it` (0-based, the loop's own counter, one schedule for all slices) is a
+ *   Jacobian iteration when it % every == 0 and a reuse iteration otherwise.
+ * jur_gradient_scene_host: the gradient and the cost of a scene from blocks the caller holds.  geom, rad (read first for
+ *   the NaN mask), tau, tp, np_out and rowptr as jur_normal_scene_host; k holds the blocks as jur_kernel_scene_host lays
+ *   them out (block of ray r at k + rowptr[r] * nd, [nd][width]).  The forward model runs on atm for the nr rays alone, one
+ *   slot per ray, every ray traced through the stacked base rows under the time stamp copy 0 of a Jacobian pass carries:
+ *   rad, tau, tp and np_out are the doubles of jur_normal_scene_host on the same arguments, with a field of view set and
+ *   with the hydrostatic balance on too.  Over the live measurements of slice s (jur_normal_scene_host's rule: the input
+ *   radiance -- with a field of view the effective mask --, F and y finite, weight > 0), in ascending rays of the slice and
+ *   within a ray in ascending channels, each from +0.0:
+ *     d = y - F;  wd = weight * d;  b_s[i] = fma(K_r[id][i], wd, b_s[i]);  cost[s] = fma(wd, d, cost[s]);  nlive[s]++
+ *   the chains of jur_normal_scene_host, so with k the blocks jur_kernel_scene_host returns on the same atm and rays, b, cost
+ *   and nlive are jur_normal_scene_host's bit for bit.  One lane per state element (jur_scene_gradient_kernel), no atomics;
+ *   the accumulators stay on the device across the passes, and nothing depends on max_rays_per_pass or on the other
+ *   slices of the call.  Rows of k of measurements that are not live are never read (masked channels hold NaN there); the
+ *   values of k are not checked, and a NaN in a live row reaches b of that slice only.  max_rays_per_pass caps the rays of
+ *   a pass: the passes are jur_trial_passes(nr, 1, cap, ...), so a scan is never cut.  Refusals are those of
+ *   jur_normal_scene_host, and k == NULL while the state has elements; JUR_ENOMEM before anything is launched when the
+ *   blocks do not fit beside the stacked slices in half the workspace budget.  The model holds atm afterwards; the kernels'
+ *   time counts into jur_model_last_scene_ms.
+ * jur_retrieve_scene_host while every > 1: room for the blocks of all rays (rowptr[nr] * nd doubles) is reserved in the
+ *   device slab (JUR_ENOMEM before anything is launched if they do not fit in half the budget), and a Jacobian iteration
+ *   leaves its blocks -- with a field of view the convolved ones -- and its A there.  A reuse iteration zeroes b, cost and
+ *   nlive only, runs forward-only passes (jur_trial_passes(n, 1, cap, ...)) over the rays of the slices that are still
+ *   active, then the field of view, then jur_scene_gradient_kernel on the retained blocks, and goes on with the unchanged
+ *   solve on the retained A (it factors a copy), the trial pass, the policy and the accepted steps.  h_work[2 it] of a
+ *   reuse iteration is the number of rays traced for the gradient, the active rays; everything else is as with every == 1.
+ *   A reuse iteration is jur_gradient_scene_host on the blocks of the active rays followed by jur_solve_slices_host on the
+ *   A of the last Jacobian iteration, bit for bit.
+ * jur_scene_recomp_offsets (host arithmetic, no GPU): where a reuse iteration finds the blocks.  A Jacobian iteration
+ *   writes the blocks of the rays it traced -- the rays r with sid[r] >= 0 whose slice had then[sid[r]] == 0 (active) --
+ *   back to back in ray order.  For the rays whose slice is active now (now[sid[r]] == 0), in ray order, koff receives the
+ *   first double of each one's block: nd times the widths of the rays traced then that precede it.  Returns their number;
+ *   JUR_EINVAL when a slice is active now that was not then. */
+int  jur_model_set_kernel_recomp(jur_model_t *m, int every);
+int  jur_model_kernel_recomp(jur_model_t const *m);
+int  jur_gradient_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                             double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                             double const *k /* blocks, as jur_kernel_scene_host lays them out */,
+                             double *b, double *cost, long *nlive, long max_rays_per_pass);
+long jur_scene_recomp_offsets(long nr, long const *rowptr, int const *sid, int const *then, int const *now, int nd, long *koff);
+
 /* intpol_atm with an error code instead of exit(): JUR_EINVAL for what upstream aborts on (profiles of one point,
  * profiles more than 10 degrees apart, unknown IP).  One lane per destination point on `device`. */
 int  jur_intpol_atm(ctl_t const *ctl, atm_t *dest, atm_t const *src, int device);

@@ -219,6 +219,17 @@ typedef struct {
 /* the terms of the rays [a->r0, a->r1) from the blocks a->k and the results a->out_rad of the pass (after jurk_scene_quot) */
 int jurk_scene_normal(jur_scene_pass_t const *a, jur_scene_normal_t const *n, long ntiles, void *stream);
 
+/* Gradient of a scene from blocks that are held (jur_gradient_scene_host, the reuse iterations of jur_retrieve_scene_host):
+ * b, cost and nlive of jur_scene_normal_t alone, from the results a->out_rad of a forward-only pass (after
+ * jurk_scene_quot) and the block of ray r of the call at k + koff[r], [nd][w].  gptr cuts every slice into workgroups of
+ * 256 state elements. */
+typedef struct {
+  double const *k;              /* the blocks, wherever the Jacobian pass or the caller left them           */
+  long const *koff;             /* [nr] first double of the block of every ray of the call                  */
+  long const *gptr;             /* [nslice + 1] running sum of ceil(w_s / 256)                              */
+} jur_scene_grad_t;
+int jurk_scene_gradient(jur_scene_pass_t const *a, jur_scene_normal_t const *n, jur_scene_grad_t const *g, long ngroups, void *stream);
+
 /* Levenberg-Marquardt step of a scene (jur_solve_slices_host, jur_step_scene_host): the damped, optionally regularised
  * system of every slice under one damping each, one workgroup per system.  All arrays are device memory. */
 typedef struct {

@@ -31,6 +31,7 @@
 //   jur_fov_kernel        field-of-view convolution of device arrays (formod_fov, jurassic.c:214-258).
 //   jur_scene_fov_kernel  the same convolution on the replicated rays of a pass of the scene entries, a workgroup per ray.
 //   jur_scene_hydro_kernel  hydrostatic balance of the slices of a scene, one wavefront per segment (jur_model_set_scene_hydz).
+//   jur_scene_gradient_kernel  b, cost and nlive of a scene's slices from held blocks, a lane per state element (jur_gradient_scene_host).
 //   jur_intpol_kernel     regridding of a track / point-cloud atmosphere (intpol_atm, jurassic.c:675-804).
 //   jur_kat_*_kernel      known-answer hooks for tests: the device functions on arrays of inputs.
 //
@@ -2765,6 +2766,64 @@ __global__ __launch_bounds__(256) void jur_scene_normal_kernel(jur_scene_pass_t 
   if (with_cost) { n.cost[s] = acc_c; n.nlive[s] = count; }
 }
 
+// ---- gradient of a scene from held blocks (jur_gradient_scene_host, reuse iterations of jur_retrieve_scene_host) -----
+// A matrix-vector sum over ragged blocks.  One workgroup per 256 consecutive state elements of one slice; lane i owns
+// element e = 256 g + i and carries its chain b_e = fma(K[id][e], weight * (y - F), b_e) over the slice's rays of the pass,
+// ascending, and their channels, ascending -- jur_scene_normal_kernel's acc_b, operand for operand, from the value the
+// earlier passes left.  The measurements are taken GRAD_CH at a time: lane c of the first GRAD_CH stages weight (0: not
+// live, by jur_scene_normal_kernel's rule; the measurement is then skipped by all lanes, so that the NaN row of a masked
+// channel is never read), y - F and the first double of the block row in one of two LDS buffers (one barrier per group);
+// what is staged does not grow with the slice.  The lanes then read entry (id, e) of each live row: consecutive doubles,
+// one coalesced stretch per row.  Lane 0 of the slice's first workgroup carries cost and nlive.  No atomics.
+#define GRAD_CH 64
+__global__ __launch_bounds__(256) void jur_scene_gradient_kernel(jur_scene_pass_t a, jur_scene_normal_t n, jur_scene_grad_t g) {
+  __shared__ double wl[2][GRAD_CH], dl[2][GRAD_CH];
+  __shared__ long kl[2][GRAD_CH];
+  long const s = scene_find<false>(g.gptr, 0, n.nslice, (long)blockIdx.x);
+  long const q0 = scene_lower(n.srays, n.sptr[s], n.sptr[s + 1], a.r0), q1 = scene_lower(n.srays, q0, n.sptr[s + 1], a.r1);
+  if (q1 == q0) return;                                   // (uniform: before any barrier)
+  int const w = (int)(n.wptr[s + 1] - n.wptr[s]), nd = a.nd;
+  long const grp = (long)blockIdx.x - g.gptr[s];
+  int const lane = threadIdx.x, i = (int)(grp * 256) + lane;
+  bool const with_b = i < w, with_cost = grp == 0 && lane == 0;
+  double acc_b = with_b ? n.b[n.wptr[s] + i] : 0.;
+  double acc_c = with_cost ? n.cost[s] : 0.;
+  long count = with_cost ? n.nlive[s] : 0;
+  long const M = (q1 - q0) * nd;
+  for (long m0 = 0; m0 < M; m0 += GRAD_CH) {
+    int const buf = (int)(m0 / GRAD_CH) & 1;
+    if (lane < GRAD_CH) {
+      long const mm = m0 + lane;
+      double ww = 0., d = 0.;
+      long at_k = 0;
+      if (mm < M) {
+        long const q = mm / nd;
+        int const id = (int)(mm - q * nd);
+        long const r = n.srays[q0 + q], at = r * nd + id;
+        double const yy = n.y[at], wt = n.weight[at];
+        double const f = a.out_rad[at];
+        if (isfinite(a.in_rad[at]) && isfinite(f) && isfinite(yy) && wt > 0) {
+          ww = wt;
+          d = yy - f;
+          at_k = g.koff[r] + (long)id * w;
+        }
+      }
+      wl[buf][lane] = ww; dl[buf][lane] = d; kl[buf][lane] = at_k;
+    }
+    __syncthreads();
+    int const nc = M - m0 < GRAD_CH ? (int)(M - m0) : GRAD_CH;
+    for (int c = 0; c < nc; c++) {
+      double const wc = wl[buf][c];
+      if (!(wc > 0)) continue;                            // (uniform)
+      double const dc = dl[buf][c], wd = wc * dc;
+      if (with_b) acc_b = fma(g.k[kl[buf][c] + i], wd, acc_b);
+      if (with_cost) { acc_c = fma(wd, dc, acc_c); count++; }
+    }
+  }
+  if (with_b) n.b[n.wptr[s] + i] = acc_b;
+  if (with_cost) { n.cost[s] = acc_c; n.nlive[s] = count; }
+}
+
 // ---- Levenberg-Marquardt step of a scene (jur_solve_slices_host, jur_step_scene_host) -------------------------------
 // One workgroup per system: M = L L^T in place in the system's part of the scratch a.M (global memory, L2-resident),
 // L z = g and L^T dx = z in a.dx, pred.  Nothing waits on another workgroup, no atomics; every chain of operations is
@@ -3466,6 +3525,13 @@ extern "C" int jurk_scene_fov(jur_scene_fov_t const *a, void *stream) {
 extern "C" int jurk_scene_normal(jur_scene_pass_t const *a, jur_scene_normal_t const *n, long ntiles, void *stream) {
   if (ntiles <= 0 || a->r1 <= a->r0) return 0;
   hipLaunchKernelGGL(jur_scene_normal_kernel, dim3((unsigned)ntiles), dim3(256), 0, (hipStream_t)stream, *a, *n);
+  return (int)hipGetLastError();
+}
+
+// (the workgroup counts are the host's: ngroups = gptr[nslice])
+extern "C" int jurk_scene_gradient(jur_scene_pass_t const *a, jur_scene_normal_t const *n, jur_scene_grad_t const *g, long ngroups, void *stream) {
+  if (ngroups <= 0 || a->r1 <= a->r0) return 0;
+  hipLaunchKernelGGL(jur_scene_gradient_kernel, dim3((unsigned)ngroups), dim3(256), 0, (hipStream_t)stream, *a, *n, *g);
   return (int)hipGetLastError();
 }
 

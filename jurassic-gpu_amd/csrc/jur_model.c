@@ -100,6 +100,7 @@ struct jur_model {
   void *d_pp;                   /* device: the same 2 (pp_nslice + 1) longs, then R */
   double scene_hydz;            /* hydrostatic balance of the scene entries per slice (jur_model_set_scene_hydz): the
                                    reference altitude [km], negative: off                                   */
+  int kernel_recomp;            /* jur_retrieve_scene_host recomputes the Jacobian every n-th iteration (jur_model_set_kernel_recomp) */
   double *d_kq, *h_kq;          /* jur_kernel: perturbation steps and dense difference quotients (device, pinned host) */
   long kq_cap;
   /* small calls: the fused kernel (jur_pencil_kernel) instead of sort + three batched kernels */
@@ -179,6 +180,7 @@ int jur_model_create(jur_model_t **out, ctl_t const *ctl, jur_tables_t const *tb
   if (!m) return JUR_ENOMEM;
   m->device = device;
   m->scene_hydz = -1;
+  m->kernel_recomp = 1;
   m->ctl = (ctl_t *)malloc(sizeof(ctl_t));
   if (!m->ctl) { free(m); return JUR_ENOMEM; }
   memcpy(m->ctl, ctl, sizeof(ctl_t));
@@ -1500,6 +1502,17 @@ int jur_model_set_scene_hydz(jur_model_t *m, double hydz) {
 
 double jur_model_scene_hydz(jur_model_t const *m) { return m ? m->scene_hydz : -1; }
 
+/* ---- the Jacobian of the retrieval loop, reused between iterations ------------------------- */
+int jur_model_set_kernel_recomp(jur_model_t *m, int every) {
+  char const *const who = "jur_model_set_kernel_recomp";
+  if (!m) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if (every < 1) { jur_set_error("%s: every is %d: the Jacobian is recomputed every n-th iteration, n >= 1", who, every); return JUR_EINVAL; }
+  m->kernel_recomp = every;
+  return JUR_OK;
+}
+
+int jur_model_kernel_recomp(jur_model_t const *m) { return m ? m->kernel_recomp : 1; }
+
 static int scene_timed_begin(jur_model_t *m, hipStream_t s);
 static void scene_timed_end(jur_model_t *m, int ti, hipStream_t s);
 
@@ -2348,14 +2361,19 @@ static int prior_check_values(char const *who, long nslice, long const *wptr, do
 
 /* what jur_retrieve_scene_host adds to jur_step_scene_host */
 typedef struct { jur_retrieve_in_t const *in; jur_retrieve_out_t const *out; atm_t *atm_ret; } scene_retrieve_t;
+/* what jur_gradient_scene_host brings: the blocks of all rays, laid out by rowptr */
+typedef struct { double const *k; } scene_grad_t;
 
 /* nm == NULL: jur_kernel_scene_host.  Otherwise the normal equations of the slices are accumulated on the device after
  * the quotients of every pass, and the blocks go home only where k is given.  With sv (jur_step_scene_host; nm is given
- * then) the systems are solved where they lie after the last pass, and A and b go home only where they are given. */
+ * then) the systems are solved where they lie after the last pass, and A and b go home only where they are given.  With
+ * gd (jur_gradient_scene_host; nm is given then, without A) the passes are forward-only and b, cost and nlive are summed
+ * from the caller's blocks. */
 static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                              double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
-                             scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt, scene_diag_t const *dg) {
-  char const *const who = rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+                             scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt, scene_diag_t const *dg,
+                             scene_grad_t const *gd) {
+  char const *const who = gd ? "jur_gradient_scene_host" : rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
   if (rt) { int const rs = retrieve_check_args(who, rt->in, rt->out); if (rs) return rs; }
@@ -2389,6 +2407,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   double *hbase = NULL, *rd = NULL;
   int *ri = NULL, *hact = NULL, *dmap = NULL;
   long *hcomp = NULL, ninv = 0, ndtile = 0;
+  long *hkoff = NULL;                               /* held blocks: the first double of every ray's | the gradient's workgroups by slice */
+  int *hjac = NULL;                                 /* ... and the states of the slices at the last Jacobian iteration */
   atm_t *ret_atm = NULL;
   int const fov = m->fov_n > 0;                     /* a field of view is set: the radiances of every pass are convolved */
   double *hlive = NULL, *htimec = NULL;
@@ -2406,6 +2426,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     goto done;
   }
   if (rp[nr] > 0 && !k && !nm) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
+  if (rp[nr] > 0 && gd && !gd->k) { jur_set_error("%s: null argument (k): the state has elements", who); rc = JUR_EINVAL; goto done; }
   if (nm) {
     if (!nm->y || !nm->weight) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
     for (long r = 0; r < nr; r++)
@@ -2466,7 +2487,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   long nlist = 0, ntiles = 0, na = 0, nb = 0;
   long *sptr = NULL, *tptr = NULL, *wptr = NULL, *aptr = NULL;
   if (nm && nslice > 0) {
-    if ((!sv && !dg && (!nm->A || !nm->b)) || (!dg && (!nm->cost || !nm->nlive))) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
+    if ((!sv && !dg && ((!gd && !nm->A) || !nm->b)) || (!dg && (!nm->cost || !nm->nlive))) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
     nptr = (long *)calloc(4 * ((size_t)nslice + 1), sizeof(long));
     srays = (int *)malloc(sizeof(int) * NR);
     if (!nptr || !srays) { rc = JUR_ENOMEM; goto done; }
@@ -2483,6 +2504,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     for (long q = nslice; q > 0; q--) sptr[q] = sptr[q - 1];                          /* ... and starts it again      */
     sptr[0] = 0;
     nlist = sptr[nslice]; ntiles = tptr[nslice]; na = aptr[nslice]; nb = wptr[nslice];
+    if (gd) na = 0;                                 /* (the gradient has no A: b, cost and nlive alone are accumulated) */
     if (ntiles > 0x7fffffffL) { jur_set_error("%s: 2^31 tiles: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
     if (sv && !rt && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
     if (dg && (rc = jur_diag_check_prior(who, nslice, wptr, dg->prior_ivar))) goto done;
@@ -2588,6 +2610,23 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     goto done;
   }
 
+  /* ... and the blocks that are held: the caller's (jur_gradient_scene_host), or those a Jacobian iteration of the loop
+   * leaves for the reuse iterations (jur_model_set_kernel_recomp).  They take the place of the blocks of a pass; beside
+   * them an all-zero rowptr (a forward-only pass has one slot per ray), the first double of every ray's block and the
+   * workgroups of the gradient kernel by slice */
+  int const every = looping ? m->kernel_recomp : 1;
+  int const retain = gd || every > 1;
+  size_t const nkret = retain ? (size_t)rp[nr] * (size_t)nd : 0;
+  size_t const nrc = retain ? (NR + 1) + NR + (RS + 1) : 0;
+  size_t const kret_bytes = sizeof(double) * (nkret + nrc);
+  if (retain && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes + (double)rt_atm_bytes + (double)rt_bytes + (double)kret_bytes > (double)(m->ws_budget / 2)) {
+    jur_set_error("%s: the blocks of all rays (%ld columns, %zu bytes) do not fit beside the stacked atmosphere (%zu bytes)%s in the "
+                  "workspace budget: call with the rays of fewer slices at a time", who, rp[nr], kret_bytes, atm_bytes,
+                  gd ? "" : ", the normal matrices and the loop's arrays");
+    rc = JUR_ENOMEM;
+    goto done;
+  }
+
   /* passes: contiguous ranges of rays whose slots (width + 1 each) stay within the cap; one ray beyond it goes alone */
   size_t const slot_bytes = sizeof(double) * (10 + (size_t)(fov ? 4 : 3) * (size_t)nd) + sizeof(int);   /* (with the convolved radiances) */
   long cap = max_rays_per_pass;
@@ -2595,24 +2634,34 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
      * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
      * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
-    long const avail = (m->ws_budget - (long)atm_bytes - (long)hy_bytes - (long)fov_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes) / 16;
+    long const avail = (m->ws_budget - (long)atm_bytes - (long)hy_bytes - (long)fov_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes - (long)kret_bytes) / 16;
     cap = avail / (long)slot_bytes;
     if (cap < 4096) cap = 4096;
   }
   if (cap > 0x7fffffffL) cap = 0x7fffffffL;
   long npass = 0, nmax = 0, kmax = 0;
-  pass = (long *)malloc(sizeof(long) * 2 * (NR + 1));       /* (second half: the trial passes of the retrieval loop) */
+  pass = (long *)malloc(sizeof(long) * 3 * (NR + 1));       /* (second part: the trial passes of the retrieval loop, third: its forward-only passes) */
   if (!pass) { rc = JUR_ENOMEM; goto done; }
   double const *const scan_time = fov ? geom[0] : NULL;
-  if ((npass = jur_scene_passes(nr, rp, cap, scan_time, pass, &nmax, &kmax)) < 0) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
-  long *const tpass = pass + NR + 1;
-  long ntpass = 0;
+  if (gd) {                                         /* forward-only: one slot per ray, no blocks of a pass */
+    if ((npass = jur_trial_passes(nr, 1, cap, scan_time, pass, &nmax)) < 0) { rc = JUR_EINVAL; goto done; }
+  } else if ((npass = jur_scene_passes(nr, rp, cap, scan_time, pass, &nmax, &kmax)) < 0) { jur_set_error("%s: a ray with 2^31 state elements", who); rc = JUR_EINVAL; goto done; }
+  long *const tpass = pass + NR + 1, *const fpass = tpass + NR + 1;
+  long ntpass = 0, nfpass = 0;
   if (looping) {
     if ((ntpass = jur_trial_passes(nr, rt->in->nlam, cap, scan_time, tpass, NULL)) < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
     /* once slices have ended the passes of both kinds are cut anew, and a pass of the rays that remain can be larger
      * than any of the first cut: room for every such pass (the arrays of a pass serve both kinds) */
     if ((rc = jur_scene_pass_reserve(nr, rp, cap, rt->in->nlam, scan_time, &nmax, &kmax))) goto done;
     if (nmax > 0x7fffffffL) { jur_set_error("%s: a pass of 2^31 slots", who); rc = JUR_EINVAL; goto done; }
+    if (every > 1) {
+      /* the forward-only passes of the reuse iterations take one slot per ray where a Jacobian pass takes width + 1 >= 2
+       * and a trial pass nlam >= 1: on any subset of the rays they stay within what is reserved.  Not assumed: the first
+       * cut is measured here, the re-cuts where they are made. */
+      long fmax = 0;
+      if ((nfpass = jur_trial_passes(nr, 1, cap, scan_time, fpass, &fmax)) < 0) { rc = JUR_EINVAL; goto done; }
+      if (fmax > nmax) { jur_set_error("%s: a forward-only pass of %ld slots, %ld reserved", who, fmax, nmax); rc = JUR_EINVAL; goto done; }
+    }
   }
   kmax *= nd;
 
@@ -2661,12 +2710,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const nrd = NR * (size_t)nd;
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_rad = o_inrad + nrd,
                o_tau = o_rad + nrd, o_tp = o_tau + nrd, o_h = o_tp + 3 * NR, o_k = o_h + (size_t)ncopy,
-               o_rowptr = o_k + (size_t)kmax, o_off = o_rowptr + NR + 1, o_y = o_off + (size_t)ncopy + 1;
+               o_rowptr = o_k + (retain ? nkret : (size_t)kmax), o_off = o_rowptr + NR + 1, o_y = o_off + (size_t)ncopy + 1;
   /* (the normal equations' part, empty without them: y, weight, the accumulators A | b | cost | nlive in one piece,
    * then sptr | tptr | wptr | aptr, then what the solve needs) */
   size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
                o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_dg = o_sv + nsv, o_fov = o_dg + ndg, o_rt = o_fov + nfov,
-               o_hy = o_rt + rt_dbl + rt_lng, o_int = o_hy + NH;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad; o_hy: the balance's first points) */
+               o_hy = o_rt + rt_dbl + rt_lng, o_rc = o_hy + NH, o_int = o_rc + nrc;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad; o_hy: the balance's first points) */
   size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int + NH;   /* (the loop's ints follow the others, the balance's lengths those) */
   size_t const bytes = sizeof(double) * o_int + sizeof(int) * nint;
   if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
@@ -2708,6 +2757,24 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     int const *const d_hylen = I + nint0 + rt_int;
     if (NH && e == hipSuccess) e = hipMemcpyAsync(L + o_hy, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
     if (NH && e == hipSuccess) e = hipMemcpyAsync(I + nint0 + rt_int, hyat + NH, sizeof(int) * NH, hipMemcpyHostToDevice, s);
+    /* held blocks: the caller's go up as they are laid out, ray r's at rowptr[r] * nd */
+    long *const d_zrp = L + o_rc, *const d_koff = d_zrp + NR + 1, *const d_gptr = d_koff + NR;
+    long ngroups = 0;
+    if (retain) {
+      hkoff = (long *)malloc(sizeof(long) * (NR + RS + 1));
+      hjac = (int *)malloc(sizeof(int) * (RS + 1));
+      if (!hkoff || !hjac) { rc = JUR_ENOMEM; goto done; }
+      long *const hgptr = hkoff + NR;
+      hgptr[0] = 0;
+      for (long q = 0; q < nslice; q++) hgptr[q + 1] = hgptr[q] + (sl[q].nel + 255) / 256;
+      ngroups = ntiles ? hgptr[nslice] : 0;
+      if (ngroups > 0x7fffffffL) { jur_set_error("%s: 2^31 workgroups: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
+      for (long r = 0; r < nr; r++) hkoff[r] = rp[r] * nd;
+      if (e == hipSuccess) e = hipMemsetAsync(d_zrp, 0, sizeof(long) * (NR + 1), s);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_gptr, hgptr, sizeof(long) * (RS + 1), hipMemcpyHostToDevice, s);
+      if (gd && e == hipSuccess) e = hipMemcpyAsync(d_koff, hkoff, sizeof(long) * NR, hipMemcpyHostToDevice, s);
+      if (gd && nkret && e == hipSuccess) e = hipMemcpyAsync(D + o_k, gd->k, sizeof(double) * nkret, hipMemcpyHostToDevice, s);
+    }
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     /* the base rows are balanced once, over the ray slices, before the first pass: the caller's atm is never written */
     if (hyd && scene_hydro_launch(m, s, nrs, d_hyat, d_hylen, D + o_base, (size_t)np0)) {
@@ -2743,6 +2810,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       nq.y = D + o_y; nq.weight = D + o_w;
       nq.A = D + o_acc; nq.b = nq.A + na; nq.cost = nq.b + nb; nq.nlive = (long *)(nq.cost + nslice);
     }
+
+    jur_scene_grad_t gq;
+    memset(&gq, 0, sizeof gq);
+    gq.k = D + o_k; gq.koff = d_koff; gq.gptr = d_gptr;
+    long const *d_rp_cur = L + o_rowptr;            /* rowptr of the rays of a Jacobian pass: of all rays, or of those that remain */
 
     /* the retrieval loop: what it adds on the device (uploaded once) and on the host */
     jur_retrieve_in_t const *const rin = rt ? rt->in : NULL;
@@ -2807,6 +2879,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       }
     }
     int ti, ek;
+    int reuse = 0, regathered = 0;                  /* a reuse iteration; the rays were gathered anew in this iteration */
     int const niter = rt ? (looping ? rin->max_iter : 0) : 1;
     for (int it = 0; it < niter; it++) {
     if (looping) {
@@ -2814,6 +2887,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       long nactive = 0;
       for (long q = 0; q < nslice; q++) nactive += ro->state[q] == JUR_RET_ACTIVE;
       if (nactive == 0) break;
+      reuse = every > 1 && it % every != 0;
+      regathered = 0;
       if (nactive != nactive_built) {
         int *const act = hact, *const pos = hact + NR, *const sraysc = pos + NR;
         long n = 0;
@@ -2839,6 +2914,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         }
         npass = jur_scene_passes(nr_cur, rp_cur, cap, fov ? htimec : NULL, pass, NULL, NULL);   /* (within nmax, kmax: jur_scene_pass_reserve) */
         ntpass = jur_trial_passes(nr_cur, rin->nlam, cap, fov ? htimec : NULL, tpass, NULL);
+        if (every > 1) {
+          long fmax = 0;
+          nfpass = jur_trial_passes(nr_cur, 1, cap, fov ? htimec : NULL, fpass, &fmax);
+          if (nfpass < 0 || fmax > nmax) { jur_set_error("%s: a forward-only pass of %ld slots, %ld reserved", who, fmax, nmax); rc = JUR_EINVAL; goto done; }
+        }
+        regathered = 1;
         e = hipMemcpyAsync(d_act, act, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_sraysc, sraysc, sizeof(int) * (size_t)(nl ? nl : 1), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_rpc, hrpc, sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
@@ -2856,7 +2937,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         ek = jurk_scene_compact(&cq, s);
         scene_timed_end(m, ti, s);
         if (ek) { jur_set_error("%s: gathering kernel launch failed", who); rc = JUR_EHIP; goto done; }
-        a.nr = n; a.rowptr = d_rpc; a.first = d_firstc; a.len = d_lenc; a.copy0 = d_copy0c; a.in_geom = d_geomc; a.in_rad = d_radc;
+        a.nr = n; a.rowptr = d_rp_cur = d_rpc; a.first = d_firstc; a.len = d_lenc; a.copy0 = d_copy0c; a.in_geom = d_geomc; a.in_rad = d_radc;
         nq.sptr = d_sptrc; nq.srays = d_sraysc; nq.y = d_yc; nq.weight = d_wc;
         tps.nr = n; tps.first = d_firstc; tps.len = d_lenc; tps.tcopy0 = d_tcopy0c; tps.in_geom = d_geomc; tps.in_rad = d_radc;
         tps.sptr = d_sptrc; tps.srays = d_sraysc; tps.y = d_yc; tps.weight = d_wc;
@@ -2869,7 +2950,16 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
           lamt[(size_t)l * RS + (size_t)q] = fmin(fmax(v, rin->lam_min), rin->lam_max);
         }
       e = hipMemcpyAsync(d_state, ro->state, sizeof(int) * RS, hipMemcpyHostToDevice, s);
-      if (it > 0 && e == hipSuccess) e = hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
+      /* (a reuse iteration keeps A of the last Jacobian iteration: b, cost and nlive alone start again) */
+      if (it > 0 && e == hipSuccess) e = reuse ? hipMemsetAsync(D + o_acc + na, 0, sizeof(double) * (nacc - (size_t)na), s)
+                                               : hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
+      if (every > 1 && (!reuse || regathered)) {
+        /* where the blocks of the rays that remain lie: a Jacobian iteration writes those of its rays back to back */
+        if (!reuse) memcpy(hjac, ro->state, sizeof(int) * RS);
+        long const nk = jur_scene_recomp_offsets(nr, rp, sid, hjac, ro->state, nd, hkoff);
+        if (nk != nr_cur) { if (nk >= 0) jur_set_error("%s: retained blocks out of step", who); rc = JUR_EINVAL; goto done; }
+        if (e == hipSuccess) e = hipMemcpyAsync(d_koff, hkoff, sizeof(long) * (size_t)nk, hipMemcpyHostToDevice, s);
+      }
       if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
       ek = 0;
       if (npr) {
@@ -2903,10 +2993,17 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if ((rc = jur_model_reserve(m, nmax))) goto done;   /* the forward model's workspace for the largest pass, before the first */
 
     long const *const rp = rp_cur;               /* (the passes below: of all rays, or of those that remain) */
-    for (long p = 0; p < npass; p++) {
-      long const r0 = pass[p], r1 = pass[p + 1], n = (rp[r1] - rp[r0]) + (r1 - r0), nk = (rp[r1] - rp[r0]) * nd;
+    /* forward-only passes (the gradient entry, a reuse iteration): one slot per ray, which the kernels of a pass make of
+     * the all-zero rowptr; copy 0 of every ray as in a Jacobian pass */
+    int const fwd = gd || reuse;
+    long const *const cut = reuse ? fpass : pass;
+    long const ncut = reuse ? nfpass : npass;
+    for (long p = 0; p < ncut; p++) {
+      long const r0 = cut[p], r1 = cut[p + 1], n = fwd ? r1 - r0 : (rp[r1] - rp[r0]) + (r1 - r0), nk = fwd ? 0 : (rp[r1] - rp[r0]) * nd;
       size_t const N = (size_t)n;
       a.r0 = r0; a.r1 = r1; a.n = n;
+      a.rowptr = fwd ? d_zrp : d_rp_cur;
+      if (every > 1 && !fwd) a.k = D + o_k + (size_t)rp[r0] * (size_t)nd;   /* (the blocks stay where the pass leaves them) */
       a.geom = m->d_io; a.rad = a.geom + 7 * N; a.tau = a.rad + N * nd; a.tp = a.tau + N * nd; a.np = m->d_io_np;
       ti = scene_timed_begin(m, s);
       ek = jurk_scene_rays(&a, s);
@@ -2927,11 +3024,17 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       ek = jurk_scene_quot(&af, nk, s);
       scene_timed_end(m, ti, s);
       if (ek) { jur_set_error("%s: quotient kernel launch failed", who); rc = JUR_EHIP; goto done; }
-      if (ntiles) {
+      if (ntiles && !fwd) {
         ti = scene_timed_begin(m, s);
         ek = jurk_scene_normal(&af, &nq, ntiles, s);
         scene_timed_end(m, ti, s);
         if (ek) { jur_set_error("%s: normal-equation kernel launch failed", who); rc = JUR_EHIP; goto done; }
+      }
+      if (ngroups && fwd) {
+        ti = scene_timed_begin(m, s);
+        ek = jurk_scene_gradient(&af, &nq, &gq, ngroups, s);
+        scene_timed_end(m, ti, s);
+        if (ek) { jur_set_error("%s: gradient kernel launch failed", who); rc = JUR_EHIP; goto done; }
       }
       /* the blocks of the pass go home (where asked for); the one wait of the pass */
       e = (nk > 0 && k) ? hipMemcpyAsync(k + (size_t)rp[r0] * nd, a.k, sizeof(double) * (size_t)nk, hipMemcpyDeviceToHost, s) : hipSuccess;
@@ -2958,7 +3061,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); rc = JUR_EINVAL; goto done; }
     {
       long work = 0;
-      for (long r = 0; r < nr_cur; r++) work += rp_cur[r + 1] - rp_cur[r] + 1;
+      for (long r = 0; r < nr_cur; r++) work += reuse ? 1 : rp_cur[r + 1] - rp_cur[r] + 1;
       for (long q = 0; q < nslice; q++) {
         if (ro->state[q] != JUR_RET_ACTIVE) continue;
         ro->cost[q] = hcost[q]; ro->prior[q] = hprior0[q]; ro->nlive[q] = hnlive[q]; ro->iters[q]++;
@@ -3068,7 +3171,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
   free(first); free(rp); free(sid); free(srays); free(sl); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa);
-  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm); free(dmap); free(hlive); free(htimec); free(hyf); free(hyat);
+  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm); free(dmap); free(hlive); free(htimec); free(hyf); free(hyat); free(hkoff); free(hjac);
   trial_plan_free(&pl);
   return rc;
 }
@@ -3088,7 +3191,7 @@ static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
 int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                           double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL, NULL, NULL));
 }
 
 int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3096,7 +3199,16 @@ int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double cons
                           double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_normal_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, NULL, NULL));
+}
+
+int jur_gradient_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                            double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                            double const *k, double *b, double *cost, long *nlive, long max_rays_per_pass) {
+  if (!m || !atm) { jur_set_error("jur_gradient_scene_host: null argument"); return JUR_EINVAL; }
+  scene_normal_t const nm = {y, weight, NULL, b, cost, nlive};
+  scene_grad_t const gd = {k};
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, NULL, NULL, &gd));
 }
 
 int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3106,7 +3218,7 @@ int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const 
   if (!m || !atm) { jur_set_error("jur_step_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_solve_t const sv = {in, out};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL, NULL, NULL));
 }
 
 int jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3116,7 +3228,7 @@ int jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double co
   if (!m || !atm) { jur_set_error("jur_diagnose_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_diag_t const dg = {prior_ivar, out};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL));
 }
 
 int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, long nr, double const *const geom[7],
@@ -3126,7 +3238,7 @@ int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, l
   if (!m || !atm0 || !atm_ret) { jur_set_error("jur_retrieve_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, NULL, NULL, NULL, NULL};
   scene_retrieve_t const rt = {in, out, atm_ret};
-  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt, NULL);
+  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt, NULL, NULL);
   if (rc) return scene_restore_atm(m, atm0, rc);    /* (on success the model holds atm_ret) */
   if (nr != 0) return JUR_OK;
   if (atm_ret != atm0) memcpy(atm_ret, atm0, sizeof(atm_t));   /* no rays: nothing was retrieved */

@@ -346,6 +346,25 @@ int jur_scene_pass_reserve(long nr, long const *rp, long cap, int ntrial, double
   return JUR_OK;
 }
 
+/* ---- the Jacobian reused between iterations (jur_model_set_kernel_recomp): where the retained blocks lie -------------- */
+long jur_scene_recomp_offsets(long nr, long const *rp, int const *sid, int const *then, int const *now, int nd, long *koff) {
+  if (nr < 0 || nd < 1 || (nr > 0 && (!rp || !sid || !then || !now || !koff))) { jur_set_error("jur_scene_recomp_offsets: bad arguments"); return JUR_EINVAL; }
+  long n = 0, at = 0;                               /* the rays active now, the block columns written before this ray */
+  for (long r = 0; r < nr; r++) {
+    if (sid[r] < 0) continue;
+    int const was = then[sid[r]] == JUR_RET_ACTIVE;
+    if (now[sid[r]] == JUR_RET_ACTIVE) {
+      if (!was) {
+        jur_set_error("jur_scene_recomp_offsets: slice %d of ray %ld is active but was not when the Jacobian was computed", sid[r], r);
+        return JUR_EINVAL;
+      }
+      koff[n++] = at * nd;
+    }
+    if (was) at += rp[r + 1] - rp[r];
+  }
+  return n;
+}
+
 /* ---- posterior diagnostics (jur_diagnose_slices_host, jur_diagnose_scene_host): the host arithmetic ------------------ */
 int jur_diag_check_out(char const *who, jur_diag_out_t const *out) {
   if (!out) { jur_set_error("%s: null argument (out)", who); return JUR_EINVAL; }

@@ -156,6 +156,13 @@ def lib():
             L.jur_trial_passes.restype = C.c_long
             L.jur_trial_passes.argtypes = [C.c_long, C.c_int, C.c_long, dp, lp_, lp_]
             L.jur_scene_pass_reserve.argtypes = [C.c_long, lp_, C.c_long, C.c_int, dp, lp_, lp_]
+        if hasattr(L, "jur_gradient_scene_host"):    # (an A/B library from before the Jacobian could be reused has none)
+            L.jur_model_set_kernel_recomp.argtypes = [C.c_void_p, C.c_int]
+            L.jur_model_kernel_recomp.argtypes = [C.c_void_p]
+            L.jur_gradient_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
+                                                  dp, dp, dp, dp, dp, lp_, C.c_long]
+            L.jur_scene_recomp_offsets.restype = C.c_long
+            L.jur_scene_recomp_offsets.argtypes = [C.c_long, lp_, ip_, ip_, ip_, C.c_int, lp_]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -548,6 +555,43 @@ class Model:
             out["k"] = k
         return out
 
+    def set_kernel_recomp(self, every):
+        """retrieve_scene recomputes the Jacobian every `every`-th iteration (jur_model_set_kernel_recomp; 1, the default:
+        in every one).  The iterations in between keep the blocks and A and renew F, b and the cost alone."""
+        _chk(lib().jur_model_set_kernel_recomp(self.h, int(every)))
+
+    def kernel_recomp(self):
+        """What set_kernel_recomp set."""
+        return int(lib().jur_model_kernel_recomp(self.h))
+
+    def gradient_scene(self, atm, geom, y, weight, k, rad_in=None, max_rays_per_pass=0, rowptr=None):
+        """Gradient and cost of a scene per slice from blocks the caller holds (jur_gradient_scene_host): the forward model
+        alone, one ray per ray.  k: the flat blocks as kernel_scene returns them (None only for a state without elements)
+        -> normal_scene's dict without A; with k from kernel_scene on the same atmosphere b, cost and nlive are
+        normal_scene's bit for bit.  max_rays_per_pass caps the rays of a pass here."""
+        g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, rowptr)
+        nr, nd = g.shape[1], self.nd
+        nk = int(lay["rowptr"][-1]) * nd
+        kk = None
+        if k is not None:
+            kk = np.ascontiguousarray(k, dtype=np.float64)
+            if kk.shape != (nk,):
+                raise ValueError("k must be the flat blocks of these rays: (%d,), not %r" % (nk, kk.shape))
+        tau = np.zeros((nr, nd))
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        ns = len(lay["sfirst"])
+        b = np.zeros(int(lay["wptr"][-1]))
+        cost, nlive = np.zeros(ns), np.zeros(ns, dtype=np.int64)
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
+        lp_ = C.POINTER(C.c_long)
+        _chk(lib().jur_gradient_scene_host(self.h, C.byref(atm), nr, garr, _p(rad), _p(tau), tarr,
+                                           npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(lp_), _p(yy), _p(ww),
+                                           _p(kk) if kk is not None else None, _p(b), _p(cost), nlive.ctypes.data_as(lp_),
+                                           max_rays_per_pass))
+        return dict(lay, rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, b=b, cost=cost, nlive=nlive)
+
     def step_scene(self, atm, geom, y, weight, lam, mode=0, prior_ivar=None, prior_dx=None, want_normal=False, want_k=False,
                    want_factor=False, rad_in=None, max_rays_per_pass=0, rowptr=None):
         """Levenberg-Marquardt step of every slice of a scene (jur_step_scene_host): normal_scene followed by the solve
@@ -642,7 +686,9 @@ class Model:
         lam, cost, prior, nlive, state (RET_*), iters (nslice,) and, with history, h_cost, h_prior (max_iter, nslice),
         h_lam, h_tcost, h_tprior, h_status (max_iter, nlam, nslice), h_best, h_accept (max_iter, nslice) and h_work
         (max_iter, 2): the replicated rays of the Jacobian and of the trial passes.  Where a slice took no part in an
-        iteration its h_lam, h_tcost, h_tprior are NaN and its h_status, h_best, h_accept -1."""
+        iteration its h_lam, h_tcost, h_tprior are NaN and its h_status, h_best, h_accept -1.  Under
+        set_kernel_recomp(every > 1) the iterations it % every != 0 reuse the blocks and A of the last Jacobian iteration;
+        their h_work[it, 0] is the number of rays traced for the gradient."""
         g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, rowptr)
         nr, nd = g.shape[1], self.nd
         ns, n = len(lay["sfirst"]), int(lay["wptr"][-1])
@@ -1278,6 +1324,23 @@ def scene_pass_reserve(rowptr, cap, ntrial, time=None):
     slots, cols = C.c_long(0), C.c_long(0)
     _chk(lib().jur_scene_pass_reserve(nr, rp.ctypes.data_as(C.POINTER(C.c_long)), int(cap), int(ntrial), tp, C.byref(slots), C.byref(cols)))
     return slots.value, cols.value
+
+
+def scene_recomp_offsets(rowptr, sid, then, now, nd):
+    """Where a reuse iteration of Model.retrieve_scene finds the retained blocks (jur_scene_recomp_offsets; host
+    arithmetic, no GPU): rowptr (nr + 1,), sid (nr,) as scene_layout and scene_slices give them, then and now (nslice,)
+    the states of the slices (0: active) at the Jacobian iteration and now -> the first double of the block of every ray
+    that is active now, in ray order."""
+    rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+    nr = len(rp) - 1
+    sd, th, nw = (np.ascontiguousarray(x, dtype=np.int32) for x in (sid, then, now))
+    if sd.shape != (nr,) or th.shape != nw.shape:
+        raise ValueError("sid must be (%d,), then and now of one shape" % nr)
+    koff = np.zeros(max(nr, 1), dtype=np.int64)
+    ip_, lp_ = C.POINTER(C.c_int), C.POINTER(C.c_long)
+    n = _chk(lib().jur_scene_recomp_offsets(nr, rp.ctypes.data_as(lp_), sd.ctypes.data_as(ip_), th.ctypes.data_as(ip_),
+                                            nw.ctypes.data_as(ip_), int(nd), koff.ctypes.data_as(lp_)))
+    return koff[:n].copy()
 
 
 def formod_pencil(ctl, atm, obs, ir):
