@@ -735,6 +735,24 @@ void jur_tune_block_order(int mode);
 /* The block order of the model's last batched call, for tests and tools: copies up to `cap` entries to `out` (a
  * permutation of 0 .. n - 1) and returns n = (rays + 255) / 256, 0 if the call built none, JUR_EHIP on failure. */
 long jur_model_block_order(jur_model_t *m, int *out, long cap);
+/* Process-wide: whether the look-up kernel takes that block order too, where its launch covers the slots of the trace
+ * launch (the nd * ng pair workgroups of a ray block still follow each other on one XCD).  1 = yes, 0 = the look-up in
+ * slot order (default: the order was measured to leave the look-up's time where it is), < 0 = back to the environment's
+ * JUR_BLOCK_ORDER_EGA.  Placement only: same results bit for bit (tests/test_ega_block_order_gpu.py). */
+void jur_tune_block_order_ega(int mode);
+/* Extinction of an atmosphere without any.  Where every extinction value of the atmosphere a caller has set is +0.0 and
+ * the atmosphere is sorted (time stamps non-decreasing, z strictly monotone in every profile), the ray tracer neither
+ * interpolates nor stores the nw extinction fields of a LOS point and the kernels that would read them take 0.0: the
+ * value the interpolation of two zeros gives, so every result stays what it was bit for bit
+ * (tests/test_extinction_elision_gpu.py).  jur_atm_k_zero is that decision for `count` extinction values `k` of rows
+ * of the given origin: only JUR_ATM_CALLER rows qualify -- never the perturbed atmospheres of kernel() or of the
+ * hydrostatic contribution variants, never rows stacked on the device (scene Jacobian, retrieval).
+ * jur_model_k_zero: whether the model's next launch leaves the extinction out (0 without an atmosphere).
+ * jur_tune_k_elision, process-wide: 1 = as above (default), 0 = never, < 0 = back to the environment's JUR_K_ELISION. */
+enum { JUR_ATM_CALLER = 0, JUR_ATM_PERTURBED = 1, JUR_ATM_DEVICE = 2 };
+int  jur_atm_k_zero(double const *k, long count, int atm_sorted, int origin);
+int  jur_model_k_zero(jur_model_t *m);
+void jur_tune_k_elision(int mode);
 /* Process-wide tuning of the radiance-update kernel of the batched path: up to `channels_per_group` (0 .. 6, default
  * 4; 0 = one channel per workgroup always) channels of a ray block share a workgroup, with a barrier every
  * `sync_segments` segments (default 8; <= 0 none), for launches of at least `min_lanes` rays x channels (default

@@ -73,6 +73,9 @@ typedef struct {
   /* atmosphere, compact SoA of atm_np points */
   int atm_np;
   int atm_sorted;               /* time stamps non-decreasing and z strictly monotone inside every slice */
+  int atm_k_zero;               /* every atm_k[iw][ip] is +0.0 (all bits clear) on a sorted atmosphere: the tracer writes no
+                                   extinction fields and their readers take 0.0 (jur_atm_k_zero; never set for rows
+                                   the host has not seen)                                                         */
   double const *atm_time, *atm_z, *atm_lon, *atm_lat, *atm_p, *atm_t;
   double const *atm_q;          /* [ng][atm_np] */
   double const *atm_k;          /* [nw][atm_np] */

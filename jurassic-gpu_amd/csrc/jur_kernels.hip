@@ -536,6 +536,11 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
           L.put(f_u + ig, np, div_rcp(10. * qv * p, kt, rkt) * dsn);
           if (ig == v.ig_h2o) L.put(JUR_F_QH2O, np, qv);
         }
+        // An atmosphere without extinction (v.atm_k_zero: every k is +0.0 and every bracket of a slice has a finite,
+        // non-zero width) gets no extinction fields: for finite z the interpolation below is 0 + (z - za) * (0 - 0) /
+        // (zb - za) = 0 + (+-0) = +0.0 (round to nearest), which is what the fields' readers take in place of a load.
+        // The rows stay in the layout, never touched.  Wave-uniform (a kernel argument).
+        if (!v.atm_k_zero)
         for (int iw = 0; iw < v.nw; iw++) {
           auto const k = A.k(iw);
           if (zdir) L.put(f_k + iw, np, lip_rcp(za, k[ia], zb, k[ia + 1], z, rdz));
@@ -1498,8 +1503,10 @@ __global__ __launch_bounds__(256, RCPB ? JUR_REC_WAVES : 5) void jur_ega_kernel(
   static_assert(WARM || !RCPB, "reciprocal widths need strictly increasing axes");
   int const npair = v.nd * v.ng;
   BlockItem const bi = xcd_block_item((int)blockIdx.x, nrb, npair);
-  int const rb = bi.rb, pr = bi.item;                                       // ray block, pair: uniform
-  if (rb < 0) return;
+  if (bi.rb < 0) return;
+  // (the launch's block order, as in jur_combine_kernel: which ray block the group of workgroups works on, longest paths
+  // first; its pairs still follow each other on one XCD.  With an order the grid covers whole blocks: r < c.n is tested.)
+  int const rb = ordered_block<1>(c.blk_order, bi.rb), pr = bi.item;         // ray block, pair: uniform
   int const d = pr / v.ng, g = pr - d * v.ng;
   int const r = rb * blockDim.x + threadIdx.x;
   int const pair_idx = g * v.nd + d;
@@ -1554,12 +1561,14 @@ __global__ __launch_bounds__(256, RCPB ? JUR_REC_WAVES : 5) void jur_ega_kernel(
 // at half the bandwidth it asks for with idle vector units.)  Gases beyond the first eight take a second batch.
 struct SegmentIn { double p, t, ds, k, u_co2, q_h2o, u_h2o, pcur; };
 __device__ __forceinline__ SegmentIn load_segment(double const *__restrict__ row, double const *__restrict__ trow, unsigned lane,
-                                                  int f_k, int f_co2, int f_h2o, int ng, unsigned has_table) {
+                                                  int f_k, int f_co2, int f_h2o, int ng, unsigned has_table, bool k_zero) {
   SegmentIn in;
   in.p = ldg<double>(row + JUR_F_P * 64, lane);
   in.t = ldg<double>(row + JUR_F_T * 64, lane);
   in.ds = ldg<double>(row + JUR_F_DS * 64, lane);
-  in.k = ldg<double>(row + (size_t)f_k * 64, lane);
+  // (k_zero: the tracer wrote no extinction fields, jur_view_t::atm_k_zero; the +0.0 it would have written goes through
+  // the same `k * ds` as a loaded one, so beta_ds starts from the same double whatever ds is.  Uniform.)
+  in.k = k_zero ? 0.0 : ldg<double>(row + (size_t)f_k * 64, lane);
   in.u_co2 = ldg<double>(row + (size_t)f_co2 * 64, lane);
   in.q_h2o = ldg<double>(row + JUR_F_QH2O * 64, lane);
   in.u_h2o = ldg<double>(row + (size_t)f_h2o * 64, lane);
@@ -1620,7 +1629,7 @@ __global__ __launch_bounds__(256, 6) void jur_combine_kernel(jur_view_t v, jur_c
   for (int g = 0; g < ng && g < 32; g++) has_table |= (v.pair[g * nd + d].a >= 2 ? 1u : 0u) << g;
   int const f_co2 = do_co2 ? f_u + v.ig_co2 : JUR_F_P, f_h2o = do_h2o ? f_u + v.ig_h2o : JUR_F_P;   // (a field that always exists when the continuum is off)
   for (int ip = 0; ip < np; ++ip) {
-    SegmentIn const in = load_segment(los + (size_t)ip * R, epsb + (size_t)ip * Re, lane, f_k, f_co2, f_h2o, ng, has_table);
+    SegmentIn const in = load_segment(los + (size_t)ip * R, epsb + (size_t)ip * Re, lane, f_k, f_co2, f_h2o, ng, has_table, v.atm_k_zero != 0);
     double beta_ds = in.k * in.ds;
     if (do_co2) beta_ds += ctm_co2(ch, in.p, in.t, in.u_co2);
     double const rt = rcp_t(in.t);
@@ -1699,7 +1708,7 @@ __global__ __launch_bounds__(512, JUR_COMBINE_WAVES) void jur_combine_group_kern
   int const f_co2 = do_co2 ? f_u + v.ig_co2 : JUR_F_P, f_h2o = do_h2o ? f_u + v.ig_h2o : JUR_F_P;   // (a field that always exists when the continuum is off)
   for (int ip = 0; ip < npmax; ++ip) {
     if (ip < np) {
-      SegmentIn const in = load_segment(los + (size_t)ip * R, epsb + (size_t)ip * Re, (unsigned)lane, f_k, f_co2, f_h2o, ng, has_table);
+      SegmentIn const in = load_segment(los + (size_t)ip * R, epsb + (size_t)ip * Re, (unsigned)lane, f_k, f_co2, f_h2o, ng, has_table, v.atm_k_zero != 0);
       double beta_ds = in.k * in.ds;
       if (do_co2) beta_ds += ctm_co2(ch, in.p, in.t, in.u_co2);
       double const rt = rcp_t(in.t);
@@ -1767,7 +1776,7 @@ __global__ __launch_bounds__(256, 8) void jur_contrib_kernel(jur_view_t v, jur_c
     double const *const row = los + (size_t)ip * R;
     double const p = ldg<double>(row + JUR_F_P * 64, lane), t = ldg<double>(row + JUR_F_T * 64, lane),
                  ds = ldg<double>(row + JUR_F_DS * 64, lane);
-    double const k = ext ? ldg<double>(row + (size_t)f_k * 64, lane) : 0.;
+    double const k = (ext && !v.atm_k_zero) ? ldg<double>(row + (size_t)f_k * 64, lane) : 0.;   // (no fields written: +0.0)
     double const ug = (do_co2 || do_h2o) ? ldg<double>(row + (size_t)f_g * 64, lane) : 0.;
     double const qh = do_h2o ? ldg<double>(row + JUR_F_QH2O * 64, lane) : 0.;
     double const pcur = has ? ld_stream(epsb + (size_t)ip * Re, lane) : 1.0;
@@ -2075,7 +2084,7 @@ __global__ __launch_bounds__(1024) void jur_pencil_kernel(jur_view_t v, jur_chun
         jur_chan_t const ch = v.chan[d];
         auto L = [&](int field) { return slot[field * RB + r]; };
         double const p = L(JUR_F_P), t = L(JUR_F_T), ds = L(JUR_F_DS);
-        double beta_ds = L(JUR_F_K + ch.window) * ds;
+        double beta_ds = (v.atm_k_zero ? 0.0 : L(JUR_F_K + ch.window)) * ds;   // (the tracer role put no extinction into the ring)
         if ((v.fourbit & 8) && ch.co2_on) beta_ds += ctm_co2(ch, p, t, L(f_u + v.ig_co2));
         double const rt = rcp_t(t);
         if ((v.fourbit & 4) && ch.h2o_on) beta_ds += ctm_h2o(e2t, ch, p, t, rt, L(JUR_F_QH2O), L(f_u + v.ig_h2o));
@@ -2439,7 +2448,8 @@ __global__ __launch_bounds__(256) void jur_kat_los_kernel(jur_view_t v, jur_chun
   double const *const src = c.los + (size_t)(r >> 6) * los_tile_doubles(nfield) + (size_t)ip * nfield * 64 + (r & 63);
   double *const dst = los + (size_t)ray * nfield * NLOS + ip;
   for (int f = 0; f < nfield; f++) {
-    bool const written = ip < np && !(f == JUR_F_QH2O && v.ig_h2o < 0);
+    // (an atmosphere without extinction: the tracer leaves the extinction fields alone, and they are the +0.0 it would write)
+    bool const written = ip < np && !(f == JUR_F_QH2O && v.ig_h2o < 0) && !(v.atm_k_zero && f >= JUR_F_K && f < JUR_F_K + v.nw);
     dst[(size_t)f * NLOS] = written ? src[(size_t)f * 64] : 0.;
   }
   if (ip == 0) tsurf[ray] = c.tsurf[r];

@@ -37,6 +37,7 @@ struct jur_model {
   void *d_atm;                  /* one slab for the compact atmosphere           */
   int atm_cap;
   int atm_slices;               /* distinct time stamps in the atmosphere        */
+  int atm_k_zero;               /* jur_atm_k_zero of the rows on the device (view.atm_k_zero: this, where the switch is on) */
   double atm_zmin, atm_zmax;    /* altitude range of the atmosphere on the device */
   /* per-call workspace */
   int chunk_rays;               /* R                                             */
@@ -425,13 +426,41 @@ static void derive_atm_facts(jur_model_t *m, double const *time, double const *z
   }
 }
 
-/* upload packed rows [6+ng+nw][n] and derive what the kernels want to know about them */
-static int upload_atm_rows(jur_model_t *m, double const *h, long n) {
+/* May the kernels leave the extinction out (jur_view_t::atm_k_zero)?  Only for rows the host holds as the caller set
+ * them (origin JUR_ATM_CALLER), on a sorted atmosphere, with every one of the `count` extinction values +0.0 bit for
+ * bit: -0.0, a denormal or a NaN clears it.  The rows of a perturbed stack (kernel(), the hydrostatic contribution
+ * variants) and rows a kernel writes on the device never qualify, whatever they hold.  The sorted atmosphere is what
+ * makes the tracer's interpolation of two zeros a +0.0 (see trace_ray): its brackets have a finite width that is not 0. */
+int jur_atm_k_zero(double const *k, long count, int atm_sorted, int origin) {
+  if (origin != JUR_ATM_CALLER || !atm_sorted || count < 0 || (count > 0 && !k)) return 0;
+  for (long i = 0; i < count; i++) {
+    unsigned long long bits;
+    memcpy(&bits, &k[i], sizeof bits);
+    if (bits) return 0;
+  }
+  return 1;
+}
+
+static int g_k_elision = -1;           /* 1: on, 0: off, -1: nothing set -- JUR_K_ELISION (A/B switch, read once) */
+static int g_k_elision_env = -1;
+void jur_tune_k_elision(int mode) { g_k_elision = mode < 0 ? -1 : (mode != 0); }
+static int k_elision_on(void) {
+  if (g_k_elision_env < 0) g_k_elision_env = getenv("JUR_K_ELISION") ? atoi(getenv("JUR_K_ELISION")) != 0 : 1;
+  return g_k_elision >= 0 ? g_k_elision : g_k_elision_env;
+}
+/* what the kernels of the next launches see: before every launch that traces, so that a call's tracer and the readers
+ * of its LOS rows agree even where the switch has been turned between two calls */
+static void view_set_k_zero(jur_model_t *m) { m->view.atm_k_zero = m->atm_k_zero && k_elision_on(); }
+int jur_model_k_zero(jur_model_t *m) { if (!m || m->view.atm_np < 2) return 0; view_set_k_zero(m); return m->view.atm_k_zero; }
+
+/* upload packed rows [6+ng+nw][n] and derive what the kernels want to know about them; origin: JUR_ATM_* */
+static int upload_atm_rows(jur_model_t *m, double const *h, long n, int origin) {
   HIPCHK(hipSetDevice(m->device));
   jur_view_t *v = &m->view;
   int const ng = v->ng, nw = v->nw;
   size_t const nrow = 6 + (size_t)ng + nw;
   v->atm_np = 0;                /* until the rows are up: a failure below leaves the model without atmosphere */
+  m->atm_k_zero = 0; v->atm_k_zero = 0;
   if (n > m->atm_cap) {
     if (m->d_atm) (void)hipFree(m->d_atm);
     m->d_atm = NULL;
@@ -449,6 +478,8 @@ static int upload_atm_rows(jur_model_t *m, double const *h, long n) {
   HIPCHK(hipMemcpyAsync(m->d_atm, h, sizeof(double) * nrow * (size_t)n, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   derive_atm_facts(m, h, h + (size_t)n, n);
+  m->atm_k_zero = jur_atm_k_zero(h + (6 + (size_t)ng) * (size_t)n, (long)nw * n, v->atm_sorted, origin);
+  view_set_k_zero(m);
   double const *d = (double const *)m->d_atm;
   v->atm_np = (int)n;           /* (jurk_prepare_atm reads it) */
   v->atm_time = d; v->atm_z = d + (size_t)n; v->atm_lon = d + 2 * (size_t)n; v->atm_lat = d + 3 * (size_t)n;
@@ -483,7 +514,7 @@ int jur_model_set_atm(jur_model_t *m, atm_t const *atm) {
   m->h_atm_n = 0;
   if (m->h_atm) { memcpy(m->h_atm, h, sizeof(double) * nrow * n); m->h_atm_n = n; m->h_atm_hydz = m->ctl->hydz; }
   hydrostatic_rows(m, h, (size_t)n, 0, n);   /* on the private copy; the caller's atm is not modified */
-  int const rc = upload_atm_rows(m, h, n);
+  int const rc = upload_atm_rows(m, h, n, JUR_ATM_CALLER);
   if (rc) m->h_atm_n = 0;
   free(h);
   return rc;
@@ -661,6 +692,16 @@ static int block_order_mode(void) {
   return g_block_order ? g_block_order : g_block_order_env;
 }
 
+/* the look-up's share of the block order (it needs one built: jur_tune_block_order): 1 on, 0 the look-up in slot order,
+ * < 0 back to JUR_BLOCK_ORDER_EGA (A/B switch, read once).  Off by default: measured, the look-up's event time does not
+ * move with it (profiles/README.md, round 8) */
+static int g_block_order_ega = -1, g_block_order_ega_env = -1;
+void jur_tune_block_order_ega(int mode) { g_block_order_ega = mode < 0 ? -1 : (mode != 0); }
+static int block_order_ega_on(void) {
+  if (g_block_order_ega_env < 0) g_block_order_ega_env = getenv("JUR_BLOCK_ORDER_EGA") ? atoi(getenv("JUR_BLOCK_ORDER_EGA")) != 0 : 0;
+  return g_block_order_ega >= 0 ? g_block_order_ega : g_block_order_ega_env;
+}
+
 void jur_tune_combine(int channels_per_group, int sync_segments, long min_lanes) {
   jurk_tune_combine(channels_per_group, sync_segments, min_lanes);
 }
@@ -826,6 +867,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
   if (nr == 0) return JUR_OK;
   if (nr > 0x7fffffffL) { jur_set_error("formod_device: at most 2^31-1 rays per call"); return JUR_EINVAL; }
   if (m->view.atm_np < 2) { jur_set_error("formod_device: no atmosphere set"); return JUR_EINVAL; }
+  view_set_k_zero(m);
   HIPCHK(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
   int rc = wait_done(m, s);
@@ -872,7 +914,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
   /* Sorted slots ascend in tangent altitude within each profile, so a launch over them is a sawtooth of workgroup costs
    * (a limb ray at 3 km has four times the points of one at 68 km), handed out in blockIdx order: it ends with the long
    * workgroups of the last profiles on a mostly empty chip.  When the call is ONE trace launch, its blocks of 256 slots
-   * are ordered by the tangent altitude of their lowest ray and the ray tracer and the radiance update start them in
+   * are ordered by the tangent altitude of their lowest ray and the ray tracer, the look-up and the radiance update start them in
    * that order, longest first.  By default for launches the size of the slice tracer's (262 144 rays): below that the
    * chip is not filled several times over and the second sort is not paid for. */
   int const *blk_order = NULL;
@@ -983,10 +1025,13 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
       c.np = m->d_np + s0;
       c.tsurf = m->d_tsurf + s0;
       c.los = m->d_los + (size_t)s0 * JUR_NLOS * m->nfield;   /* tiles of 64 slots, [tile][point][field][64]: s0 is a multiple of 64 */
+      /* the look-up and the radiance update take the trace launch's block order where they cover the same slots */
+      int const same_slots = blk_order && s0 == 0 && c.n == nt;
+      if (same_slots && block_order_ega_on()) c.blk_order = blk_order;
       TIMED(1, jurk_launch_ega(&m->view, &c, s), "ega");
+      c.blk_order = NULL;
       if (co) TIMED(4, jurk_launch_contrib(&m->view, &c, nr, co->rad, co->tau, s), "contribution");
-      /* the radiance update takes the trace launch's block order where it covers the same slots */
-      if (blk_order && g_block_order_combine && s0 == 0 && c.n == nt) c.blk_order = blk_order;
+      if (same_slots && g_block_order_combine) c.blk_order = blk_order;
       TIMED(2, jurk_launch_combine(&m->view, &c, s), "combine");
       c.blk_order = NULL;
       m->n_launch_ega++;
@@ -1237,7 +1282,7 @@ static int contrib_hydrostatic(jur_model_t *m, long nr, int naff, double const *
     if (e != hipSuccess) goto done;
     m->h_atm_n = 0;                               /* the device no longer holds the caller's atmosphere */
     moved = 1;
-    if ((rc = upload_atm_rows(m, h, (long)NT))) goto done;
+    if ((rc = upload_atm_rows(m, h, (long)NT, JUR_ATM_PERTURBED))) goto done;
     if ((rc = jur_formod_device(m, (long)N, fb_geom, fb_rad, fb_tau, fb_tp, NULL, d_status ? d_status : m->d_status, s))) goto done;
     for (int v = 0, j = 0; v <= ng && e == hipSuccess; v++) {
       if (v == m->view.ig_h2o) continue;
@@ -1252,7 +1297,7 @@ done:
   if (moved && h) {                               /* the caller's atmosphere back, hydrostatic step and all */
     memcpy(h, m->h_atm, sizeof(double) * nrow * n0);
     hydrostatic_rows(m, h, (size_t)n0, 0, n0);
-    int const r2 = upload_atm_rows(m, h, n0);
+    int const r2 = upload_atm_rows(m, h, n0, JUR_ATM_CALLER);
     if (!r2) m->h_atm_n = n0;
     else m->view.atm_np = 0;                      /* never the stacked one: the next call is refused ("no atmosphere set") */
     if (!rc) rc = r2;
@@ -1347,6 +1392,7 @@ int jur_curtis_godson_host(jur_model_t *m, long nr, double const *const geom[7],
                            double *const tp[3], int *np_out) {
   if (!m || nr < 1 || !cgp || !cgt || !cgu) { jur_set_error("curtis_godson: bad arguments"); return JUR_EINVAL; }
   if (m->view.atm_np < 2) { jur_set_error("curtis_godson: no atmosphere set"); return JUR_EINVAL; }
+  view_set_k_zero(m);
   HIPCHK(hipSetDevice(m->device));
   int const ng = m->view.ng;
   int rc = ensure_workspace(m, nr);
@@ -1700,6 +1746,7 @@ int jur_kat_traceray(jur_model_t *m, long nr, double const *const geom[7], doubl
                      int *np_out) {
   if (!m || nr < 1 || !geom || !los || !tsurf) { jur_set_error("kat_traceray: bad arguments"); return JUR_EINVAL; }
   if (m->view.atm_np < 2) { jur_set_error("kat_traceray: no atmosphere set"); return JUR_EINVAL; }
+  view_set_k_zero(m);
   HIPCHK(hipSetDevice(m->device));
   int rc = ensure_workspace(m, nr);
   if (rc) return rc;
@@ -1824,7 +1871,7 @@ static int kernel_ld(jur_model_t *m, atm_t const *atm, obs_t *obs, double *k, si
     }
     m->h_atm_n = 0;                            /* the device no longer holds the caller's atmosphere */
     stacked = 1;
-    rc = upload_atm_rows(m, h, (long)NT);
+    rc = upload_atm_rows(m, h, (long)NT, JUR_ATM_PERTURBED);
     if (rc) goto done;
     double *geom[7], *tp[3], *rad, *tau;
     for (int q = 0; q < 7; q++) geom[q] = g + (size_t)q * NRT;
@@ -1920,6 +1967,7 @@ static int install_stacked_rows(jur_model_t *m, atm_t const *base, long nt, long
   jur_view_t *v = &m->view;
   size_t const ng = (size_t)v->ng, nrow = 6 + ng + (size_t)v->nw, n = (size_t)nt;
   v->atm_np = 0;
+  m->atm_k_zero = 0; v->atm_k_zero = 0;   /* JUR_ATM_DEVICE: no host image of these rows, and they may raise an extinction */
   if (nt > m->atm_cap) {
     if (m->d_atm) (void)hipFree(m->d_atm);
     m->d_atm = NULL;
@@ -3765,7 +3813,7 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
   c->ctl = (ctl_t *)malloc(sizeof(ctl_t));
   if (!c->ctl) { free(c); return NULL; }
   memcpy(c->ctl, m->ctl, sizeof(ctl_t));
-  c->d_atm = NULL; c->atm_cap = 0; c->atm_slices = 0;
+  c->d_atm = NULL; c->atm_cap = 0; c->atm_slices = 0; c->atm_k_zero = 0; c->view.atm_k_zero = 0;
   c->view.atm_np = 0;
   c->d_los = NULL; c->d_eps = NULL; c->d_np = NULL; c->d_tsurf = NULL; c->d_status = NULL;
   c->los_bytes = 0; c->ws_rays = 0; c->ws_trace_rays = 0;

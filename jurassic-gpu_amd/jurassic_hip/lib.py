@@ -102,6 +102,13 @@ def lib():
             L.jur_tune_block_order.restype = None
             L.jur_model_block_order.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_long]
             L.jur_model_block_order.restype = C.c_long
+        if hasattr(L, "jur_tune_k_elision"):         # (likewise)
+            L.jur_tune_block_order_ega.argtypes = [C.c_int]
+            L.jur_tune_block_order_ega.restype = None
+            L.jur_tune_k_elision.argtypes = [C.c_int]
+            L.jur_tune_k_elision.restype = None
+            L.jur_model_k_zero.argtypes = [C.c_void_p]
+            L.jur_atm_k_zero.argtypes = [dp, C.c_long, C.c_int, C.c_int]
         L.jur_state_size.restype = C.c_size_t
         L.jur_state_size.argtypes = [C.c_void_p, C.c_void_p]
         L.jur_measurement_size.restype = C.c_size_t
@@ -329,6 +336,10 @@ class Model:
 
     def set_trace_multiple(self, mult):
         _chk(lib().jur_model_set_trace_multiple(self.h, mult))
+
+    def k_zero(self):
+        """Whether the model's next launch leaves the extinction out (jur_model_k_zero)."""
+        return bool(lib().jur_model_k_zero(self.h))
 
     def block_order(self):
         """The block order of the last batched call (jur_model_block_order): an int32 array, empty if it built none."""
@@ -1361,6 +1372,27 @@ def tune_block_order(mode=0):
     """Process-wide: longest blocks of a sorted launch first (0: chosen per call, 1: never, 2: whenever the rays were sorted
     and the call is one trace launch)."""
     lib().jur_tune_block_order(mode)
+
+
+def tune_block_order_ega(mode=-1):
+    """Process-wide: the look-up kernel takes the launch's block order too (1), or runs in slot order (0, the default);
+    < 0: back to JUR_BLOCK_ORDER_EGA."""
+    lib().jur_tune_block_order_ega(mode)
+
+
+def tune_k_elision(mode=-1):
+    """Process-wide: no extinction work for an atmosphere without extinction (1, the default), or always the full work
+    (0); < 0: back to JUR_K_ELISION."""
+    lib().jur_tune_k_elision(mode)
+
+
+ATM_CALLER, ATM_PERTURBED, ATM_DEVICE = 0, 1, 2
+
+
+def atm_k_zero(k, atm_sorted=True, origin=ATM_CALLER):
+    """jur_atm_k_zero: may the kernels leave the extinction values `k` (any shape, float64) out?"""
+    k = np.ascontiguousarray(k, dtype=np.float64)
+    return bool(lib().jur_atm_k_zero(k.ctypes.data_as(C.POINTER(C.c_double)), k.size, int(bool(atm_sorted)), int(origin)))
 
 
 def tune_combine(channels_per_group=4, sync_segments=8, min_lanes=1_000_000):
