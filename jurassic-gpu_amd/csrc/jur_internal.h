@@ -456,6 +456,14 @@ JUR_HIDDEN void jur_hydrostatic_profile(double hydz, int n, double const *z, dou
  * distinct slices of two points or more among the rays' (first, len) */
 JUR_HIDDEN int jur_scene_hydro_check(char const *who, int np, long nseg, int const *sfirst, int const *slen);
 JUR_HIDDEN long jur_scene_ray_slices_of(int np, long nr, int const *first, int const *len, int *sfirst, int *slen);
+/* the rays of every slice as one CSR (sid[r] < 0: a ray without state elements, in no list): sptr[nslice + 1], srays[up
+ * to nr], the rays of a slice ascending; returns the length of the lists */
+JUR_HIDDEN long jur_scene_rays_by_slice(long nr, long nslice, int const *sid, long *sptr, int *srays);
+/* the rays of the slices whose state is JUR_RET_ACTIVE, in arrays of their own: act[n] the rays in their order, pos[nr]
+ * where each went (-1: it left), rpc[n + 1] their rowptr, sptrc[nslice + 1] | sraysc[sptrc[nslice]] the lists of sptr |
+ * srays in the new positions (an ended slice's is empty); returns n */
+JUR_HIDDEN long jur_scene_gather_active(long nr, long nslice, long const *rp, int const *sid, int const *state, long const *sptr,
+                                        int const *srays, int *act, int *pos, long *rpc, long *sptrc, int *sraysc);
 
 /* internals of a model that jur_multi.c needs (jur_model.c) */
 /* jur_formod_device on rays that are part of larger arrays: geometry field k at d_geom + k * ldg, tangent-point field k

@@ -1685,6 +1685,39 @@ static int scene_fov_mask(char const *who, int nd, long nr, double const *time, 
   return JUR_OK;
 }
 
+/* The device slab of the scene entries (grow-only; it holds nothing between calls): selects the device, waits for the
+ * model's earlier calls, as every entry does, and leaves at least `bytes` in m->d_scene; *stream: the model's */
+static int scene_slab_reserve(jur_model_t *m, char const *who, size_t bytes, hipStream_t *stream) {
+  if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); return JUR_EHIP; }
+  *stream = m->stream;
+  int const rc = wait_done(m, m->stream);
+  if (rc) return rc;
+  if (bytes > m->scene_bytes) {
+    if (m->d_scene) (void)hipFree(m->d_scene);
+    m->d_scene = NULL; m->scene_bytes = 0;
+    if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
+      (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); return JUR_ENOMEM;
+    }
+    m->scene_bytes = bytes;
+  }
+  return JUR_OK;
+}
+
+/* one more part of the slab: does it fit beside the *used bytes in the half of the workspace budget the slab may take?
+ * (sums in double, term by term in the order the parts join); where it does it is counted */
+static int scene_fits(jur_model_t const *m, double *used, size_t add) {
+  if (*used + (double)add > (double)(m->ws_budget / 2)) return 0;
+  *used += (double)add;
+  return 1;
+}
+
+/* what the status word that has come home (m->h_status) says of the forward models of a scene entry */
+static int scene_status_rc(jur_model_t const *m, char const *who) {
+  if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); return JUR_ENLOS; }
+  if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); return JUR_EINVAL; }
+  return JUR_OK;
+}
+
 /* ---- known-answer hooks ----------------------------------------------------------- */
 /* nin input arrays and nout in/out arrays of n doubles each go to the device as one slab [nin + nout][n] */
 static int kat_slab(jur_model_t *m, long n, int nin, double const *const in[], int nout, double *const out[], double **d) {
@@ -2045,13 +2078,20 @@ static int solve_check_values(char const *who, long nslice, long const *wptr, ju
   return JUR_OK;
 }
 
-/* doubles of device memory the solve needs beside A and b: the scratch copy of the matrices, the liveness of one
- * damping, then for all dampings dx | pred | lam, the prior pair, status (ints, rounded up) */
-static size_t solve_doubles(size_t na, size_t nb, size_t ns, size_t nlam, int prior) {
-  return na + nb + nlam * nb + 2 * nlam * ns + (prior ? 2 * nb : 0) + (nlam * ns + 1) / 2;
+/* The solver's part of the slab beside A and b, as offsets in doubles from its start: M, the scratch copy of the
+ * matrices; live, the liveness of one damping; for all dampings dx | pred | lam; the prior pair r | d (empty without a
+ * prior); stat (ints, rounded up to doubles); with a full prior precision behind those Ap, the assembled matrices A + P
+ * (+ lam P), g and zl, the zero dampings.  end: the doubles of the part.  Whoever sizes or reads the part asks here. */
+typedef struct { size_t M, live, dx, pred, lam, r, d, stat, Ap, g, zl, end; } solve_layout_t;
+
+static solve_layout_t solve_layout(size_t na, size_t nb, size_t ns, size_t nlam, int prior, int full) {
+  size_t const npr = prior ? nb : 0;
+  solve_layout_t o;
+  o.M = 0; o.live = o.M + na; o.dx = o.live + nb; o.pred = o.dx + nlam * nb; o.lam = o.pred + nlam * ns; o.r = o.lam + nlam * ns;
+  o.d = o.r + npr; o.stat = o.d + npr; o.Ap = o.stat + (nlam * ns + 1) / 2; o.g = o.Ap + (full ? na : 0); o.zl = o.g + (full ? nb : 0);
+  o.end = o.zl + (full ? ns : 0);
+  return o;
 }
-/* ... and with a full prior precision after those: the assembled matrices A + P (+ lam P), g, the zero dampings */
-static size_t solve_full_doubles(size_t na, size_t nb, size_t ns) { return na + nb + ns; }
 
 /* Enqueues on s: the uploads of the dampings and the prior, one launch per damping over the one scratch (stream order
  * protects the copy-out of L), the copies home.  The caller waits for the stream before the host arrays go. */
@@ -2064,9 +2104,10 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
    * and jurk_scene_prior_pred then writes pred */
   int const resident = d_state != NULL;
   size_t const NA = (size_t)na, NB = (size_t)nb, NS = (size_t)nslice, NL = (size_t)in->nlam, npr = in->prior_ivar ? NB : 0;
-  double *const dM = W, *const dlive = dM + NA, *const ddx = dlive + NB, *const dpred = ddx + NL * NB, *const dlam = dpred + NL * NS,
-         *const dr = dlam + NL * NS, *const dd = dr + npr;
-  int *const dstat = (int *)(dd + npr);
+  solve_layout_t const o = solve_layout(NA, NB, NS, NL, npr != 0, d_R != NULL);
+  double *const dM = W + o.M, *const dlive = W + o.live, *const ddx = W + o.dx, *const dpred = W + o.pred, *const dlam = W + o.lam,
+         *const dr = W + o.r, *const dd = W + o.d;
+  int *const dstat = (int *)(W + o.stat);
   hipError_t e = hipMemcpyAsync(dlam, in->lam, sizeof(double) * NL * NS, hipMemcpyHostToDevice, s);
   if (npr && !resident && e == hipSuccess) e = hipMemcpyAsync(dr, in->prior_ivar, sizeof(double) * NB, hipMemcpyHostToDevice, s);
   if (npr && !resident && e == hipSuccess) e = hipMemcpyAsync(dd, in->prior_dx, sizeof(double) * NB, hipMemcpyHostToDevice, s);
@@ -2081,7 +2122,7 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
   memset(&pa, 0, sizeof pa); memset(&pq, 0, sizeof pq);
   int const by_prior = in->mode == JUR_DAMP_PRIOR;
   if (d_R) {
-    double *const dAp = W + solve_doubles(NA, NB, NS, NL, npr != 0), *const dg = dAp + NA, *const dzl = dg + NB;
+    double *const dAp = W + o.Ap, *const dg = W + o.g, *const dzl = W + o.zl;
     pa.nslice = nslice; pa.wptr = d_wptr; pa.aptr = d_aptr; pa.A = d_A; pa.b = d_b; pa.R = d_R; pa.ivar = dr; pa.d = dd;
     pa.M = dAp; pa.g = dg; pa.state = d_state;
     pq.nslice = nslice; pq.nvec = 1; pq.wptr = d_wptr; pq.aptr = d_aptr; pq.R = d_R; pq.state = d_state;
@@ -2103,7 +2144,7 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
       pa.lam = dlam + l * NS;
       if (l > 0) { pa.b = NULL; pa.d = NULL; }      /* (g does not depend on the damping) */
       ek = jurk_scene_prior_assemble(&pa, nb, s);
-      q.lam = pa.M + NA + NB;                       /* (the zero dampings) */
+      q.lam = W + o.zl;                             /* (the zero dampings) */
     }
     if (!ek) ek = jurk_scene_solve(&q, s);
     if (!ek && d_R && by_prior) {
@@ -2126,14 +2167,19 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
 /* what jur_diagnose_scene_host adds to jur_normal_scene_host */
 typedef struct { double const *prior_ivar; jur_diag_out_t const *out; } scene_diag_t;
 
-/* doubles of device memory the diagnostics need beside A: L | S | AVK, then live | z | zeros (the solve's b and
- * prior_dx) | prior_ivar, the four vectors, lam (zeros) | pred | dofs, and the ints status | imap | tmap (rounded up) */
-static size_t diag_doubles(size_t na, size_t nb, size_t ns, int prior, size_t ninv, size_t ntile) {
-  return 3 * na + 3 * nb + (prior ? nb : 0) + 4 * nb + 3 * ns + (ns + 2 * ninv + 3 * ntile + 1) / 2;
-}
+/* The diagnostics' part of the slab beside A, as offsets in doubles from its start: L | S | K (the AVK), then live | z |
+ * zero (the solve's b and prior_dx) | r (prior_ivar, empty without a prior), vec (the four vectors), lam (zeros) | pred |
+ * dofs, stat (the ints status [ns] | imap [2 ninv] | tmap [3 ntile], rounded up to doubles); with a full prior precision
+ * behind those P (A + P, then P alone, for the smoothing error) and SP (S P).  end: the doubles of the part. */
+typedef struct { size_t L, S, K, live, z, zero, r, vec, lam, pred, dofs, stat, P, SP, end; } diag_layout_t;
 
-/* ... and with a full prior precision after those: A + P (then P alone, for the smoothing error) and S P */
-static size_t diag_full_doubles(size_t na) { return 2 * na; }
+static diag_layout_t diag_layout(size_t na, size_t nb, size_t ns, int prior, int full, size_t ninv, size_t ntile) {
+  diag_layout_t o;
+  o.L = 0; o.S = o.L + na; o.K = o.S + na; o.live = o.K + na; o.z = o.live + nb; o.zero = o.z + nb; o.r = o.zero + nb;
+  o.vec = o.r + (prior ? nb : 0); o.lam = o.vec + 4 * nb; o.pred = o.lam + ns; o.dofs = o.pred + ns; o.stat = o.dofs + ns;
+  o.P = o.stat + (ns + 2 * ninv + 3 * ntile + 1) / 2; o.SP = o.P + (full ? na : 0); o.end = o.SP + (full ? na : 0);
+  return o;
+}
 
 /* Enqueues on s: the uploads of the prior and the block maps (hmap: imap | tmap), the factorisation by the solve kernel
  * (lam = 0, zero right-hand side, zero prior_dx), the inverse, the product and the vectors, the copies home.  The caller
@@ -2144,9 +2190,10 @@ static int diag_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nsl
   /* d_R (a full prior precision is set): the factor is that of A + P as jurk_scene_prior_assemble forms it, and
    * sigma_smooth comes from the product S P */
   size_t const NA = (size_t)na, NB = (size_t)nb, NS = (size_t)nslice, npr = prior_ivar ? NB : 0;
-  double *const dL = W, *const dS = dL + NA, *const dK = dS + NA, *const dlive = dK + NA, *const dz = dlive + NB, *const dzero = dz + NB,
-         *const dr = dzero + NB, *const dvec = dr + npr, *const dlam = dvec + 4 * NB, *const dpred = dlam + NS, *const ddofs = dpred + NS;
-  int *const dstat = (int *)(ddofs + NS), *const dimap = dstat + NS, *const dtmap = dimap + 2 * (size_t)ninv;
+  diag_layout_t const o = diag_layout(NA, NB, NS, npr != 0, d_R != NULL, (size_t)ninv, (size_t)ntile);
+  double *const dL = W + o.L, *const dS = W + o.S, *const dK = W + o.K, *const dlive = W + o.live, *const dz = W + o.z, *const dzero = W + o.zero,
+         *const dr = W + o.r, *const dvec = W + o.vec, *const dlam = W + o.lam, *const dpred = W + o.pred, *const ddofs = W + o.dofs;
+  int *const dstat = (int *)(W + o.stat), *const dimap = dstat + NS, *const dtmap = dimap + 2 * (size_t)ninv;
   hipError_t e = hipMemsetAsync(dlam, 0, sizeof(double) * NS, s);
   if (NB && e == hipSuccess) e = hipMemsetAsync(dzero, 0, sizeof(double) * NB, s);
   if (npr && e == hipSuccess) e = hipMemcpyAsync(dr, prior_ivar, sizeof(double) * NB, hipMemcpyHostToDevice, s);
@@ -2169,7 +2216,7 @@ static int diag_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nsl
   memset(&pa, 0, sizeof pa);
   if (d_R) {
     pa.nslice = nslice; pa.wptr = d_wptr; pa.aptr = d_aptr; pa.A = d_A; pa.R = d_R; pa.ivar = dr;
-    pa.M = W + diag_doubles(NA, NB, NS, npr != 0, (size_t)ninv, (size_t)ntile);
+    pa.M = W + o.P;
     ek = jurk_scene_prior_assemble(&pa, nb, s);
     q.A = pa.M; q.prior_ivar = NULL; q.prior_dx = NULL;
     d.prior_ivar = NULL;                          /* (the rows kernel writes sqrt(0); jurk_scene_prior_smooth the value) */
@@ -2180,7 +2227,7 @@ static int diag_enqueue(jur_model_t *m, hipStream_t s, char const *who, long nsl
     pa.A = NULL;                                  /* P alone where A + P lay: the factor has been taken */
     ek = jurk_scene_prior_assemble(&pa, nb, s);
     jur_scene_diag_t d2 = d;
-    d2.A = pa.M; d2.avk = pa.M + NA;
+    d2.A = W + o.P; d2.avk = W + o.SP;
     if (!ek) ek = jurk_scene_prior_smooth(&d2, ntile, nb, s);
   }
   scene_timed_end(m, ti, s);
@@ -2215,6 +2262,13 @@ static int diag_maps_make(char const *who, long nslice, long const *wptr, long *
 }
 
 /* ---- trial states and the retrieval loop (jur_trial_scene_host, jur_retrieve_scene_host) ----------------------------- */
+/* The row of the stacked atmosphere that holds state quantity iq (jur_state_vector's: 0 p, 1 T, then the gases, then the
+ * windows): p and T are rows 4 and 5, the q rows start at 6, the k rows follow.  And back: the array of atm a row is. */
+static int scene_row_of(int iq) { return (iq == 0) ? 4 : (iq == 1) ? 5 : 4 + iq; }
+static double *scene_row_array(atm_t *atm, int ng, int row) {
+  return row == 4 ? atm->p : row == 5 ? atm->t : row < 6 + ng ? atm->q[row - 6] : atm->k[row - 6 - ng];
+}
+
 /* Host image of what the trial kernels index by: two blocks, each uploaded with one copy.
  * longs: wptr[ns + 1] | off[ncopy + 1] | sptr[ns + 1];  ints: cdesc[3 ncopy] (first | prow = -1 | pip = 0 of every copy,
  * for jur_scene_stack_kernel) | sfirst[ns] | erow[nb] | eip[nb] | tcopy0[nr] | srays[nlist] */
@@ -2255,8 +2309,7 @@ static int trial_plan_make(trial_plan_t *p, char const *who, ctl_t const *ctl, a
     long const n = jur_scene_slice_elements(ctl, atm, sl[q].first, sl[q].len, NULL, scratch, scratch + nb);
     if (n != sl[q].nel) { jur_set_error("%s: layout out of step", who); rc = JUR_EINVAL; break; }
     for (long e = 0; e < n; e++) {
-      int const iq = scratch[e];
-      p->erow[p->wptr[q] + e] = (iq == 0) ? 4 : (iq == 1) ? 5 : 4 + iq;   /* q rows start at 6, k rows follow */
+      p->erow[p->wptr[q] + e] = scene_row_of(scratch[e]);
       p->eip[p->wptr[q] + e] = scratch[nb + e];
     }
     for (int t = 0; t < ntrial; t++) {
@@ -2267,15 +2320,8 @@ static int trial_plan_make(trial_plan_t *p, char const *who, ctl_t const *ctl, a
   }
   free(scratch);
   if (rc) { trial_plan_free(p); return rc; }
-  for (long r = 0; r < nr; r++) {
-    p->tcopy0[r] = sid[r] >= 0 ? (int)(1 + (long)sid[r] * ntrial) : 0;
-    if (sid[r] >= 0) p->sptr[sid[r] + 1]++;
-  }
-  for (long q = 0; q < nslice; q++) p->sptr[q + 1] += p->sptr[q];
-  for (long r = 0; r < nr; r++) if (sid[r] >= 0) p->srays[p->sptr[sid[r]]++] = (int)r;
-  for (long q = nslice; q > 0; q--) p->sptr[q] = p->sptr[q - 1];
-  p->sptr[0] = 0;
-  p->nlist = p->sptr[nslice];
+  for (long r = 0; r < nr; r++) p->tcopy0[r] = sid[r] >= 0 ? (int)(1 + (long)sid[r] * ntrial) : 0;
+  p->nlist = jur_scene_rays_by_slice(nr, nslice, sid, p->sptr, p->srays);
   return JUR_OK;
 }
 
@@ -2412,11 +2458,96 @@ typedef struct { jur_retrieve_in_t const *in; jur_retrieve_out_t const *out; atm
 /* what jur_gradient_scene_host brings: the blocks of all rays, laid out by rowptr */
 typedef struct { double const *k; } scene_grad_t;
 
+/* ---- what jur_kernel_scene_host's family and jur_trial_scene_host open with ------------------------------------------- */
+/* the atmosphere a scene entry can take: no global balance (hydz_tail: why not, in the entry's words), 2..JUR_NP points,
+ * ascending time stamps */
+static int scene_atm_check(jur_model_t const *m, char const *who, char const *hydz_tail, atm_t const *atm) {
+  if (m->ctl->hydz >= 0) {
+    jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so %s", who, m->ctl->hydz, hydz_tail);
+    return JUR_EINVAL;
+  }
+  if (atm->np < 2 || atm->np > JUR_NP) { jur_set_error("%s: need 2..%d atmospheric points", who, JUR_NP); return JUR_EINVAL; }
+  for (int i = 1; i < atm->np; i++)
+    if (!(atm->time[i] >= atm->time[i - 1])) {
+      jur_set_error("%s: the time stamps of the atmosphere are not ascending (point %d): the slices of a "
+                    "stacked atmosphere cannot reproduce locate_atm there", who, i);
+      return JUR_EINVAL;
+    }
+  return JUR_OK;
+}
+
+/* The host products of a call's rays and atmosphere, before the entries diverge: the slice of every ray (first | len,
+ * and behind them nr ints that are the caller's), jur_scene_layout's rowptr, the distinct slices with state elements
+ * and the slice of every ray (sid), the ray slices of the hydrostatic balance (hyf: first | len, nrs of them; balance on),
+ * the effective mask of a field of view (hlive; one is set), the base rows with their stacked time stamps, and the
+ * largest time stamp and the span of atmosphere and rays together. */
+typedef struct {
+  int *first, *len, *sid, *hyf;
+  long *rp, nslice, nrs;
+  jur_scene_slice_t *sl;
+  double *hlive, *hbase, tmax, span;
+} scene_open_t;
+
+static void scene_open_free(scene_open_t *o) {
+  free(o->first); free(o->rp); free(o->sid); free(o->sl); free(o->hyf); free(o->hlive); free(o->hbase);
+  memset(o, 0, sizeof *o);
+}
+
+/* no_k: the refusal of a state that has elements, where the caller has brought no array for its blocks; sums: the sums
+ * over the rays are formed, so y is needed and the weights are checked.  On an error the caller frees what stands. */
+static int scene_open(scene_open_t *o, jur_model_t *m, char const *who, atm_t const *atm, long nr, double const *const geom[7],
+                      double const *rad_in, long const *rowptr, char const *no_k, int sums, double const *y, double const *weight) {
+  int const np0 = atm->np, nd = m->ctl->nd;
+  size_t const NR = (size_t)nr, nrow = 6 + (size_t)m->view.ng + m->view.nw;
+  int rc;
+  memset(o, 0, sizeof *o);
+  o->first = (int *)malloc(sizeof(int) * 3 * NR);
+  o->rp = (long *)malloc(sizeof(long) * (NR + 1));
+  o->sid = (int *)malloc(sizeof(int) * NR);
+  if (!o->first || !o->rp || !o->sid) return JUR_ENOMEM;
+  o->len = o->first + NR;
+  if ((rc = jur_scene_layout(m->ctl, atm, nr, geom[0], o->first, o->len, o->rp))) return rc;
+  if (memcmp(o->rp, rowptr, sizeof(long) * (NR + 1))) {
+    jur_set_error("%s: rowptr is not jur_scene_layout's for these rays, this atmosphere and these windows", who);
+    return JUR_EINVAL;
+  }
+  if (o->rp[nr] > 0 && no_k) { jur_set_error(no_k, who); return JUR_EINVAL; }
+  if (sums) {
+    if (!y || !weight) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+    for (long r = 0; r < nr; r++)
+      for (int id = 0; id < nd; id++) {
+        double const w = weight[(size_t)r * nd + id];
+        if (!(w >= 0) || isinf(w)) {
+          jur_set_error("%s: the weight of ray %ld, channel %d is %g: negative or not finite", who, r, id, w);
+          return JUR_EINVAL;
+        }
+      }
+  }
+  if (m->fov_n > 0 && (rc = scene_fov_mask(who, nd, nr, geom[0], rad_in, &o->hlive))) return rc;
+  if (m->scene_hydz >= 0) {                         /* the slices the rays are traced through, with or without elements */
+    if (!(o->hyf = (int *)malloc(sizeof(int) * 2 * NR))) return JUR_ENOMEM;
+    if ((o->nrs = jur_scene_ray_slices_of(np0, nr, o->first, o->len, o->hyf, o->hyf + NR)) < 0) return JUR_ENOMEM;
+    if ((rc = jur_scene_hydro_check(who, np0, o->nrs, o->hyf, o->hyf + NR))) return rc;
+  }
+  /* the distinct slices that have state elements, in the order the rays meet them */
+  if ((o->nslice = jur_scene_distinct(np0, nr, o->first, o->len, o->rp, o->sid, &o->sl)) < 0) return JUR_ENOMEM;
+  if (!(o->hbase = (double *)malloc(sizeof(double) * nrow * (size_t)np0))) return JUR_ENOMEM;
+  pack_atm_rows(m, atm, o->hbase, (size_t)np0, 0);
+  stack_times(o->hbase, atm->time, np0, 0.0);
+  double tmin = atm->time[0];
+  o->tmax = atm->time[0];
+  for (int i = 0; i < np0; i++) { tmin = fmin(tmin, atm->time[i]); o->tmax = fmax(o->tmax, atm->time[i]); }
+  for (long i = 0; i < nr; i++) { tmin = fmin(tmin, geom[0][i]); o->tmax = fmax(o->tmax, geom[0][i]); }
+  o->span = (o->tmax - tmin) + 1.0;
+  return JUR_OK;
+}
+
 /* nm == NULL: jur_kernel_scene_host.  Otherwise the normal equations of the slices are accumulated on the device after
  * the quotients of every pass, and the blocks go home only where k is given.  With sv (jur_step_scene_host; nm is given
  * then) the systems are solved where they lie after the last pass, and A and b go home only where they are given.  With
  * gd (jur_gradient_scene_host; nm is given then, without A) the passes are forward-only and b, cost and nlive are summed
- * from the caller's blocks. */
+ * from the caller's blocks.  What the call opens with is scene_open's; of the device slab (scene_slab_reserve) the
+ * solver's part is laid out by solve_layout and the diagnostics' by diag_layout, which the loop reads too. */
 static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                              double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
                              scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt, scene_diag_t const *dg,
@@ -2427,79 +2558,39 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   if (rt) { int const rs = retrieve_check_args(who, rt->in, rt->out); if (rs) return rs; }
   if (dg) { int const rs = jur_diag_check_out(who, dg->out); if (rs) return rs; }
   ctl_t const *ctl = m->ctl;
-  if (ctl->hydz >= 0) {
-    jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so every p, T or H2O element moves "
-                  "every pressure and the Jacobian has no blocks: use jur_kernel", who, ctl->hydz);
-    return JUR_EINVAL;
-  }
+  int rc = scene_atm_check(m, who, "every p, T or H2O element moves every pressure and the Jacobian has no blocks: use jur_kernel", atm);
+  if (rc) return rc;
   int const np0 = atm->np, nd = ctl->nd, ng = m->view.ng, nw = m->view.nw;
-  if (np0 < 2 || np0 > JUR_NP) { jur_set_error("%s: need 2..%d atmospheric points", who, JUR_NP); return JUR_EINVAL; }
-  for (int i = 1; i < np0; i++)
-    if (!(atm->time[i] >= atm->time[i - 1])) {
-      jur_set_error("%s: the time stamps of the atmosphere are not ascending (point %d): the slices of a "
-                    "stacked atmosphere cannot reproduce locate_atm there", who, i);
-      return JUR_EINVAL;
-    }
   if (nr == 0) return JUR_OK;
   if (nr > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 rays per call", who); return JUR_EINVAL; }
   if (!geom || !rad || !tau || !tp || !rowptr) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
 
   size_t const NR = (size_t)nr, nrow = 6 + (size_t)ng + nw;
-  int rc = JUR_OK, enqueued = 0;
-  int *first = (int *)malloc(sizeof(int) * 3 * NR), *len = first ? first + NR : NULL, *copy0 = first ? len + NR : NULL;
-  long *rp = (long *)malloc(sizeof(long) * (NR + 1));
-  int *sid = (int *)malloc(sizeof(int) * NR), *srays = NULL;
-  jur_scene_slice_t *sl = NULL;
+  int enqueued = 0;
+  scene_open_t op;
   long *off = NULL, *pass = NULL, *scopy = NULL, *nptr = NULL;
-  int *cdesc = NULL, *iqa = NULL, *ipa = NULL;
-  double *hbase = NULL, *rd = NULL;
+  int *cdesc = NULL, *iqa = NULL, *ipa = NULL, *srays = NULL;
+  double *rd = NULL, *htimec = NULL;
   int *ri = NULL, *hact = NULL, *dmap = NULL;
   long *hcomp = NULL, ninv = 0, ndtile = 0;
   long *hkoff = NULL;                               /* held blocks: the first double of every ray's | the gradient's workgroups by slice */
   int *hjac = NULL;                                 /* ... and the states of the slices at the last Jacobian iteration */
   atm_t *ret_atm = NULL;
   int const fov = m->fov_n > 0;                     /* a field of view is set: the radiances of every pass are convolved */
-  double *hlive = NULL, *htimec = NULL;
   double const *d_R = NULL;                         /* the model's full prior precision on the device, where one is set */
   int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: every slice is balanced on its own */
-  int *hyf = NULL;                                  /* the ray slices: first | len */
-  long *hyat = NULL, nrs = 0;                       /* the segment lists of the balance on the host: at | len (ints behind) */
+  long *hyat = NULL;                                /* the segment lists of the balance on the host: at | len (ints behind) */
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
-  if (!first || !rp || !sid) { rc = JUR_ENOMEM; goto done; }
-  if ((rc = jur_scene_layout(ctl, atm, nr, geom[0], first, len, rp))) goto done;
-  if (memcmp(rp, rowptr, sizeof(long) * (NR + 1))) {
-    jur_set_error("%s: rowptr is not jur_scene_layout's for these rays, this atmosphere and these windows", who);
-    rc = JUR_EINVAL;
-    goto done;
-  }
-  if (rp[nr] > 0 && !k && !nm) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
-  if (rp[nr] > 0 && gd && !gd->k) { jur_set_error("%s: null argument (k): the state has elements", who); rc = JUR_EINVAL; goto done; }
-  if (nm) {
-    if (!nm->y || !nm->weight) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
-    for (long r = 0; r < nr; r++)
-      for (int id = 0; id < nd; id++) {
-        double const w = nm->weight[(size_t)r * nd + id];
-        if (!(w >= 0) || isinf(w)) {
-          jur_set_error("%s: the weight of ray %ld, channel %d is %g: negative or not finite", who, r, id, w);
-          rc = JUR_EINVAL;
-          goto done;
-        }
-      }
-  }
-
-  if (fov && (rc = scene_fov_mask(who, nd, nr, geom[0], rad, &hlive))) goto done;
-  if (hyd) {                                        /* the slices the rays are traced through, with or without elements */
-    if (!(hyf = (int *)malloc(sizeof(int) * 2 * NR))) { rc = JUR_ENOMEM; goto done; }
-    if ((nrs = jur_scene_ray_slices_of(np0, nr, first, len, hyf, hyf + NR)) < 0) { rc = JUR_ENOMEM; goto done; }
-    if ((rc = jur_scene_hydro_check(who, np0, nrs, hyf, hyf + NR))) goto done;
-  }
-
-  /* the distinct slices that have state elements, in the order the rays meet them, and their copies: slice q is
-   * raised element by element by the copies scopy[q] ... */
-  long const nslice = jur_scene_distinct(np0, nr, first, len, rp, sid, &sl);
+  if ((rc = scene_open(&op, m, who, atm, nr, geom, rad, rowptr,
+                       (!k && !nm) ? "%s: null argument" : (gd && !gd->k) ? "%s: null argument (k): the state has elements" : NULL,
+                       nm != NULL, nm ? nm->y : NULL, nm ? nm->weight : NULL))) goto done;
+  int *const copy0 = op.len + NR, *const sid = op.sid;   /* (copy0: the ints that scene_open leaves to its caller) */
+  long const *const rp = op.rp, nslice = op.nslice, nrs = op.nrs;
+  jur_scene_slice_t const *const sl = op.sl;
+  double const tmax = op.tmax, span = op.span;
+  /* the copies of the slices: slice q is raised element by element by the copies scopy[q] ... */
   long ncopies = 0, nt = np0;
-  if (nslice < 0) { rc = JUR_ENOMEM; goto done; }
   /* the retrieval loop is the step entry driven from here: its dampings, costs, predictions and statuses are host
    * arrays of this call (rd: lamt | pred | tcost | tprior | Jt [nlam][ns] each, cost | prior | J [ns] each; ri: status
    * [nlam][ns], best | accept | choice | active-before [ns] each) */
@@ -2540,18 +2631,14 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     srays = (int *)malloc(sizeof(int) * NR);
     if (!nptr || !srays) { rc = JUR_ENOMEM; goto done; }
     sptr = nptr; tptr = sptr + nslice + 1; wptr = tptr + nslice + 1; aptr = wptr + nslice + 1;
-    for (long r = 0; r < nr; r++) if (sid[r] >= 0) sptr[sid[r] + 1]++;
+    nlist = jur_scene_rays_by_slice(nr, nslice, sid, sptr, srays);
     for (long q = 0; q < nslice; q++) {
       long const w = sl[q].nel, T = (w + 15) / 16;
-      sptr[q + 1] += sptr[q];
       tptr[q + 1] = tptr[q] + T * (T + 1) / 2;
       wptr[q + 1] = wptr[q] + w;
       aptr[q + 1] = aptr[q] + w * w;
     }
-    for (long r = 0; r < nr; r++) if (sid[r] >= 0) srays[sptr[sid[r]]++] = (int)r;   /* (sptr[q] now ends slice q ...) */
-    for (long q = nslice; q > 0; q--) sptr[q] = sptr[q - 1];                          /* ... and starts it again      */
-    sptr[0] = 0;
-    nlist = sptr[nslice]; ntiles = tptr[nslice]; na = aptr[nslice]; nb = wptr[nslice];
+    ntiles = tptr[nslice]; na = aptr[nslice]; nb = wptr[nslice];
     if (gd) na = 0;                                 /* (the gradient has no A: b, cost and nlive alone are accumulated) */
     if (ntiles > 0x7fffffffL) { jur_set_error("%s: 2^31 tiles: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
     if (sv && !rt && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
@@ -2586,12 +2673,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const nacc = (size_t)na + (size_t)nb + 2 * (size_t)(ntiles ? nslice : 0);
   size_t const acc_bytes = ntiles ? sizeof(double) * (nacc + 2 * NR * (size_t)nd + 4 * ((size_t)nslice + 1)) + sizeof(int) * (size_t)nlist : 0;
   /* ... and the solve: one more copy of the matrices, the vectors of one damping, the outputs of all */
-  size_t const nsv = (sv && ntiles) ? solve_doubles((size_t)na, (size_t)nb, (size_t)nslice, (size_t)sv->in->nlam, sv->in->prior_ivar != NULL) +
-                                      (d_R ? solve_full_doubles((size_t)na, (size_t)nb, (size_t)nslice) : 0) : 0;
+  solve_layout_t const svl = solve_layout((size_t)na, (size_t)nb, (size_t)nslice, sv ? (size_t)sv->in->nlam : 0, sv && sv->in->prior_ivar, d_R != NULL);
+  size_t const nsv = (sv && ntiles) ? svl.end : 0;
   size_t const sv_bytes = sizeof(double) * nsv;
   /* ... or the diagnostics: the factor, S, AVK and the vectors */
-  size_t const ndg = (dg && ntiles) ? diag_doubles((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, (size_t)ninv, (size_t)ndtile) +
-                                      (d_R ? diag_full_doubles((size_t)na) : 0) : 0;
+  size_t const ndg = (dg && ntiles) ? diag_layout((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, d_R != NULL, (size_t)ninv, (size_t)ndtile).end : 0;
   size_t const dg_bytes = sizeof(double) * ndg;
   /* ... and a field of view: the effective mask and the convolved transmittances by ray; for the loop the mask of the
    * rays that remain and the convolved radiances of its last forward model */
@@ -2606,38 +2692,35 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   if (nt > 0x7fffffffL || (long)atm_bytes > m->ws_budget / 2) {
     jur_set_error("%s: the stacked atmosphere (%ld points, %zu bytes) exceeds the workspace budget: "
                   "call with the rays of fewer slices at a time", who, nt, atm_bytes);
-    rc = JUR_ENOMEM;
-    goto done;
+    rc = JUR_ENOMEM; goto done;
   }
-  if (hy_bytes > 0 && (double)atm_bytes + (double)hy_bytes > (double)(m->ws_budget / 2)) {
+  /* what follows joins the slab part by part, each refused where it no longer fits beside those before it (an entry
+   * with diagnostics has no solve, no loop and no held blocks) */
+  double used = (double)atm_bytes;
+  if (hy_bytes > 0 && !scene_fits(m, &used, hy_bytes)) {
     jur_set_error("%s: the segment lists of the hydrostatic balance (%zu bytes) do not fit beside the stacked atmosphere (%zu "
                   "bytes) in the workspace budget: call with the rays of fewer slices at a time", who, hy_bytes, atm_bytes);
-    rc = JUR_ENOMEM;
-    goto done;
+    rc = JUR_ENOMEM; goto done;
   }
-  if (fov_bytes > 0 && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes > (double)(m->ws_budget / 2)) {
+  if (fov_bytes > 0 && !scene_fits(m, &used, fov_bytes)) {
     jur_set_error("%s: the field of view's arrays (%zu bytes) do not fit beside the stacked atmosphere (%zu bytes) "
                   "in the workspace budget: call with fewer rays at a time", who, fov_bytes, atm_bytes);
-    rc = JUR_ENOMEM;
-    goto done;
+    rc = JUR_ENOMEM; goto done;
   }
-  if (acc_bytes > 0 && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
+  if (acc_bytes > 0 && !scene_fits(m, &used, acc_bytes)) {
     jur_set_error("%s: the normal matrices (%ld doubles) do not fit beside the stacked atmosphere (%zu bytes) "
                   "in the workspace budget: call with the rays of fewer slices at a time", who, na, atm_bytes + fov_bytes);
-    rc = JUR_ENOMEM;
-    goto done;
+    rc = JUR_ENOMEM; goto done;
   }
-  if (sv_bytes > 0 && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes > (double)(m->ws_budget / 2)) {
+  if (sv_bytes > 0 && !scene_fits(m, &used, sv_bytes)) {
     jur_set_error("%s: the solver scratch (%zu bytes) does not fit beside the normal matrices (%ld doubles) and the stacked "
                   "atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, sv_bytes, na, atm_bytes);
-    rc = JUR_ENOMEM;
-    goto done;
+    rc = JUR_ENOMEM; goto done;
   }
-  if (dg_bytes > 0 && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes + (double)dg_bytes > (double)(m->ws_budget / 2)) {
+  if (dg_bytes > 0 && !scene_fits(m, &used, dg_bytes)) {
     jur_set_error("%s: the factor, S, AVK and the vectors (%zu bytes) do not fit beside the normal matrices (%ld doubles) and the "
                   "stacked atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, dg_bytes, na, atm_bytes);
-    rc = JUR_ENOMEM;
-    goto done;
+    rc = JUR_ENOMEM; goto done;
   }
 
   /* ... and the retrieval loop: the trial copies (counted beside the stacked rows, whose memory they share in turn), the
@@ -2650,12 +2733,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist : 0;
   size_t const rt_atm_bytes = looping ? sizeof(double) * (nrow + 1) * (size_t)pl.nt : 0;
   size_t const rt_bytes = sizeof(double) * (rt_dbl + rt_lng) + sizeof(int) * rt_int;
-  if (looping && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes + (double)rt_atm_bytes + (double)rt_bytes > (double)(m->ws_budget / 2)) {
+  used += (double)rt_atm_bytes;
+  if (looping && !scene_fits(m, &used, rt_bytes)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and the loop's arrays (%zu bytes) do not fit beside the solver "
                   "scratch, the normal matrices and the stacked atmosphere (%zu bytes) in the workspace budget: call with the rays "
                   "of fewer slices at a time", who, pl.nt, rt_atm_bytes, rt_bytes, atm_bytes + acc_bytes + sv_bytes);
-    rc = JUR_ENOMEM;
-    goto done;
+    rc = JUR_ENOMEM; goto done;
   }
 
   /* ... and the blocks that are held: the caller's (jur_gradient_scene_host), or those a Jacobian iteration of the loop
@@ -2667,12 +2750,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const nkret = retain ? (size_t)rp[nr] * (size_t)nd : 0;
   size_t const nrc = retain ? (NR + 1) + NR + (RS + 1) : 0;
   size_t const kret_bytes = sizeof(double) * (nkret + nrc);
-  if (retain && (double)atm_bytes + (double)hy_bytes + (double)fov_bytes + (double)acc_bytes + (double)sv_bytes + (double)rt_atm_bytes + (double)rt_bytes + (double)kret_bytes > (double)(m->ws_budget / 2)) {
+  if (retain && !scene_fits(m, &used, kret_bytes)) {
     jur_set_error("%s: the blocks of all rays (%ld columns, %zu bytes) do not fit beside the stacked atmosphere (%zu bytes)%s in the "
                   "workspace budget: call with the rays of fewer slices at a time", who, rp[nr], kret_bytes, atm_bytes,
                   gd ? "" : ", the normal matrices and the loop's arrays");
-    rc = JUR_ENOMEM;
-    goto done;
+    rc = JUR_ENOMEM; goto done;
   }
 
   /* passes: contiguous ranges of rays whose slots (width + 1 each) stay within the cap; one ray beyond it goes alone */
@@ -2713,12 +2795,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   }
   kmax *= nd;
 
-  /* descriptors of the copies (copy 0: the base) and the base rows */
+  /* descriptors of the copies (copy 0: the base) */
   off = (long *)malloc(sizeof(long) * ((size_t)ncopy + 1));
   cdesc = (int *)malloc(sizeof(int) * 3 * (size_t)ncopy);
   iqa = (int *)malloc(sizeof(int) * 2 * (size_t)np0 * (2 + (size_t)ng + nw));
-  hbase = (double *)malloc(sizeof(double) * nrow * (size_t)np0);
-  if (!off || !cdesc || !iqa || !hbase) { rc = JUR_ENOMEM; goto done; }
+  if (!off || !cdesc || !iqa) { rc = JUR_ENOMEM; goto done; }
   ipa = iqa + (size_t)np0 * (2 + (size_t)ng + nw);
   int *const cfirst = cdesc, *const prow = cdesc + ncopy, *const pip = cdesc + 2 * ncopy;
   off[0] = 0; cfirst[0] = 0; prow[0] = -1; pip[0] = 0;
@@ -2729,17 +2810,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     for (long e = 0; e < n; e++) {
       long const j = scopy[q] + e;
       cfirst[j] = sl[q].first;
-      prow[j] = (iqa[e] == 0) ? 4 : (iqa[e] == 1) ? 5 : 4 + iqa[e];   /* q rows start at 6, k rows follow */
+      prow[j] = scene_row_of(iqa[e]);
       pip[j] = ipa[e];
       off[j + 1] = off[j] + sl[q].len;
     }
   }
-  pack_atm_rows(m, atm, hbase, (size_t)np0, 0);
-  stack_times(hbase, atm->time, np0, 0.0);
-  double tmin = atm->time[0], tmax = atm->time[0];
-  for (int i = 0; i < np0; i++) { tmin = fmin(tmin, atm->time[i]); tmax = fmax(tmax, atm->time[i]); }
-  for (long i = 0; i < nr; i++) { tmin = fmin(tmin, geom[0][i]); tmax = fmax(tmax, geom[0][i]); }
-  double const span = (tmax - tmin) + 1.0;
   /* the balance's segments: the ray slices in the base rows; the copies whose raised row the pressures depend on, in the
    * stacked rows (the others inherit the balanced base: a second balance would return the same bits); every trial copy */
   long nhc = 0, ntc = 0;
@@ -2747,7 +2822,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (!(hyat = (long *)malloc((sizeof(long) + sizeof(int)) * (NH ? NH : 1)))) { rc = JUR_ENOMEM; goto done; }
     int *const hylen = (int *)(hyat + NH);
     int const row_h2o = m->view.ig_h2o >= 0 ? 6 + m->view.ig_h2o : -1;
-    for (long q = 0; q < nrs; q++) { hyat[q] = hyf[q]; hylen[q] = hyf[NR + (size_t)q]; }
+    for (long q = 0; q < nrs; q++) { hyat[q] = op.hyf[q]; hylen[q] = op.hyf[NR + (size_t)q]; }
     for (long j = 1; j < ncopy; j++)
       if (prow[j] == 4 || prow[j] == 5 || prow[j] == row_h2o) { hyat[nrs + nhc] = off[j]; hylen[nrs + nhc] = (int)(off[j + 1] - off[j]); nhc++; }
     if (rt && ntiles)
@@ -2765,18 +2840,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
                o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_dg = o_sv + nsv, o_fov = o_dg + ndg, o_rt = o_fov + nfov,
                o_hy = o_rt + rt_dbl + rt_lng, o_rc = o_hy + NH, o_int = o_rc + nrc;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad; o_hy: the balance's first points) */
   size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int + NH;   /* (the loop's ints follow the others, the balance's lengths those) */
-  size_t const bytes = sizeof(double) * o_int + sizeof(int) * nint;
-  if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
-  hipStream_t const s = m->stream;
-  if ((rc = wait_done(m, s))) goto done;
-  if (bytes > m->scene_bytes) {
-    if (m->d_scene) (void)hipFree(m->d_scene);
-    m->d_scene = NULL; m->scene_bytes = 0;
-    if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
-      (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
-    }
-    m->scene_bytes = bytes;
-  }
+  hipStream_t s;
+  if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * nint, &s))) goto done;
   if ((rc = ensure_io(m, nmax, 0))) goto done;
   if (fov && (rc = scene_fov_reserve(m, (size_t)nmax * (size_t)nd))) goto done;
   {
@@ -2785,12 +2850,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     int *const I = (int *)(D + o_int);
     int *const d_first = I, *const d_len = I + NR, *const d_copy0 = I + 2 * NR, *const d_np = I + 3 * NR, *const d_cdesc = I + 4 * NR;
     enqueued = 1;
-    hipError_t e = hipMemcpyAsync(D + o_base, hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(D + o_base, op.hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
     for (int q = 0; q < 7 && e == hipSuccess; q++) e = hipMemcpyAsync(D + o_geom + (size_t)q * NR, geom[q], sizeof(double) * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(D + o_inrad, rad, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(L + o_rowptr, rp, sizeof(long) * (NR + 1), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(L + o_off, off, sizeof(long) * ((size_t)ncopy + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_first, first, sizeof(int) * 3 * NR, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_first, op.first, sizeof(int) * 3 * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_cdesc, cdesc, sizeof(int) * 3 * (size_t)ncopy, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
     if (ntiles) {                                 /* the accumulators are zeroed here, once */
@@ -2800,7 +2865,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (e == hipSuccess) e = hipMemcpyAsync(d_cdesc + 3 * ncopy, srays, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, s);
       if (e == hipSuccess) e = hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
     }
-    if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_fov, hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_fov, op.hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     long const *const d_hyat = L + o_hy;
     int const *const d_hylen = I + nint0 + rt_int;
     if (NH && e == hipSuccess) e = hipMemcpyAsync(L + o_hy, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
@@ -2875,8 +2940,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         *const d_firstc = d_act + NR, *const d_lenc = d_firstc + NR, *const d_copy0c = d_lenc + NR, *const d_tcopy0c = d_copy0c + NR,
         *const d_sraysc = d_tcopy0c + NR;
     size_t const npr = (looping && rin->prior_ivar) ? (size_t)nb : 0;
-    /* (the solver's part of the slab, as solve_enqueue lays it out) */
-    double *const sv_dx = D + o_sv + (size_t)na + (size_t)nb, *const sv_r = sv_dx + RL * (size_t)nb + 2 * RL * RS, *const sv_d = sv_r + npr;
+    double *const sv_dx = D + o_sv + svl.dx, *const sv_r = D + o_sv + svl.r, *const sv_d = D + o_sv + svl.d;   /* (the solver's part of the slab) */
     double *const lamt = rd, *const htcost = rd ? rd + 2 * RL * RS : NULL, *const htprior = rd ? rd + 3 * RL * RS : NULL,
            *const Jt = rd ? rd + 4 * RL * RS : NULL, *const hcost = rd ? rd + 5 * RL * RS : NULL, *const hprior0 = hcost ? hcost + RS : NULL,
            *const J = hprior0 ? hprior0 + RS : NULL;
@@ -2939,22 +3003,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       regathered = 0;
       if (nactive != nactive_built) {
         int *const act = hact, *const pos = hact + NR, *const sraysc = pos + NR;
-        long n = 0;
-        hrpc[0] = 0;
-        for (long r = 0; r < nr; r++) {
-          pos[r] = -1;
-          if (sid[r] < 0 || ro->state[sid[r]] != JUR_RET_ACTIVE) continue;
-          act[n] = (int)r; pos[r] = (int)n;
-          hrpc[n + 1] = hrpc[n] + (rp[r + 1] - rp[r]);
-          n++;
-        }
-        long nl = 0;
-        for (long q = 0; q < nslice; q++) {
-          hsptrc[q] = nl;
-          if (ro->state[q] == JUR_RET_ACTIVE)
-            for (long i = sptr[q]; i < sptr[q + 1]; i++) sraysc[nl++] = pos[srays[i]];
-        }
-        hsptrc[nslice] = nl;
+        long const n = jur_scene_gather_active(nr, nslice, rp, sid, ro->state, sptr, srays, act, pos, hrpc, hsptrc, sraysc);
+        long const nl = hsptrc[nslice];
         nr_cur = n; rp_cur = hrpc; nactive_built = nactive;
         if (fov) {                                  /* (whole scans have left: the scans that remain are the call's) */
           if (!htimec && !(htimec = (double *)malloc(sizeof(double) * NR))) { rc = JUR_ENOMEM; goto done; }
@@ -3105,8 +3155,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; goto done; }
-    if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); rc = JUR_EINVAL; goto done; }
+    if ((rc = scene_status_rc(m, who))) goto done;
     {
       long work = 0;
       for (long r = 0; r < nr_cur; r++) work += reuse ? 1 : rp_cur[r + 1] - rp_cur[r] + 1;
@@ -3172,11 +3221,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         e = ek ? hipErrorUnknown : hipMemcpyAsync(ro->x, d_xout, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { (void)hipGetLastError(); free(ret); jur_set_error("%s: bringing the state home failed", who); rc = JUR_EHIP; goto done; }
-        for (long i = 0; i < nb; i++) {
-          int const row = pl.erow[i], ip = pl.eip[i];
-          double *const dst = row == 4 ? ret->p : row == 5 ? ret->t : row < 6 + ng ? ret->q[row - 6] : ret->k[row - 6 - ng];
-          dst[ip] = ro->x[i];
-        }
+        for (long i = 0; i < nb; i++) scene_row_array(ret, ng, pl.erow[i])[pl.eip[i]] = ro->x[i];
       }
       rc = jur_model_set_atm(m, ret);
       if (!rc) {
@@ -3212,14 +3257,14 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
-    else if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); rc = JUR_EINVAL; }
+    rc = scene_status_rc(m, who);
     if (rt && !rc) memcpy(rt->atm_ret, ret_atm, sizeof(atm_t));
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
-  free(first); free(rp); free(sid); free(srays); free(sl); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa);
-  free(hbase); free(rd); free(ri); free(hact); free(hcomp); free(ret_atm); free(dmap); free(hlive); free(htimec); free(hyf); free(hyat); free(hkoff); free(hjac);
+  free(srays); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa); free(rd); free(ri); free(hact); free(hcomp);
+  free(ret_atm); free(dmap); free(htimec); free(hyat); free(hkoff); free(hjac);
+  scene_open_free(&op);
   trial_plan_free(&pl);
   return rc;
 }
@@ -3307,62 +3352,27 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     return JUR_EINVAL;
   }
   ctl_t const *ctl = m->ctl;
-  if (ctl->hydz >= 0) {
-    jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so a step of one slice moves every pressure: "
-                  "the slices are no independent problems", who, ctl->hydz);
-    return JUR_EINVAL;
-  }
+  int rc = scene_atm_check(m, who, "a step of one slice moves every pressure: the slices are no independent problems", atm);
+  if (rc) return rc;
   int const np0 = atm->np, nd = ctl->nd, ng = m->view.ng, nw = m->view.nw;
-  if (np0 < 2 || np0 > JUR_NP) { jur_set_error("%s: need 2..%d atmospheric points", who, JUR_NP); return JUR_EINVAL; }
-  for (int i = 1; i < np0; i++)
-    if (!(atm->time[i] >= atm->time[i - 1])) {
-      jur_set_error("%s: the time stamps of the atmosphere are not ascending (point %d): the slices of a "
-                    "stacked atmosphere cannot reproduce locate_atm there", who, i);
-      return JUR_EINVAL;
-    }
   if (nr == 0) return JUR_OK;
   if (nr > 0x7fffffffL / ntrial) { jur_set_error("%s: at most 2^31-1 trial rays per call", who); return JUR_EINVAL; }
   if (!geom || !rad_in || !rowptr || !y || !weight) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
 
   size_t const NR = (size_t)nr, nrow = 6 + (size_t)ng + nw, nrd = NR * (size_t)nd;
-  int rc = JUR_OK, enqueued = 0;
-  int *first = (int *)malloc(sizeof(int) * 3 * NR), *len = first ? first + NR : NULL, *sid = first ? len + NR : NULL;
-  long *rp = (long *)malloc(sizeof(long) * 2 * (NR + 1)), *pass = rp ? rp + NR + 1 : NULL;
-  jur_scene_slice_t *sl = NULL;
-  double *hbase = NULL, *hlive = NULL;
+  int enqueued = 0;
+  scene_open_t op;
+  long *pass = NULL;
   int const fov = m->fov_n > 0;                     /* a field of view is set: the trial radiances are convolved */
   int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: base rows and trial copies are balanced */
-  int *hyf = NULL;
-  long *hyat = NULL, nrs = 0;
+  long *hyat = NULL;
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
-  if (!first || !rp) { rc = JUR_ENOMEM; goto done; }
-  if ((rc = jur_scene_layout(ctl, atm, nr, geom[0], first, len, rp))) goto done;
-  if (memcmp(rp, rowptr, sizeof(long) * (NR + 1))) {
-    jur_set_error("%s: rowptr is not jur_scene_layout's for these rays, this atmosphere and these windows", who);
-    rc = JUR_EINVAL;
-    goto done;
-  }
-  for (long r = 0; r < nr; r++)
-    for (int id = 0; id < nd; id++) {
-      double const w = weight[(size_t)r * nd + id];
-      if (!(w >= 0) || isinf(w)) {
-        jur_set_error("%s: the weight of ray %ld, channel %d is %g: negative or not finite", who, r, id, w);
-        rc = JUR_EINVAL;
-        goto done;
-      }
-    }
-  if (fov && (rc = scene_fov_mask(who, nd, nr, geom[0], rad_in, &hlive))) goto done;
-  if (hyd) {                                        /* the slices the rays are traced through, with or without elements */
-    if (!(hyf = (int *)malloc(sizeof(int) * 2 * NR))) { rc = JUR_ENOMEM; goto done; }
-    if ((nrs = jur_scene_ray_slices_of(np0, nr, first, len, hyf, hyf + NR)) < 0) { rc = JUR_ENOMEM; goto done; }
-    if ((rc = jur_scene_hydro_check(who, np0, nrs, hyf, hyf + NR))) goto done;
-  }
-  long const nslice = jur_scene_distinct(np0, nr, first, len, rp, sid, &sl);
-  if (nslice < 0) { rc = JUR_ENOMEM; goto done; }
+  if ((rc = scene_open(&op, m, who, atm, nr, geom, rad_in, rowptr, NULL, 1, y, weight))) goto done;
+  long const nslice = op.nslice, nrs = op.nrs;
   if (nslice == 0) goto done;                         /* no state elements: nothing to write */
   if (!dx || !cost || !prior) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
-  if ((rc = trial_plan_make(&pl, who, ctl, atm, ntrial, nr, nslice, sl, sid))) goto done;
+  if ((rc = trial_plan_make(&pl, who, ctl, atm, ntrial, nr, nslice, op.sl, op.sid))) goto done;
   long const nb = pl.nb;
   for (int t = 0; t < ntrial; t++)
     for (long q = 0; q < nslice; q++)
@@ -3396,20 +3406,14 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (cap < 4096) cap = 4096;
   }
   long nmax = 0;
+  if (!(pass = (long *)malloc(sizeof(long) * (NR + 1)))) { rc = JUR_ENOMEM; goto done; }
   long const npass = jur_trial_passes(nr, ntrial, cap, fov ? geom[0] : NULL, pass, &nmax);
   if (npass < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
 
-  hbase = (double *)malloc(sizeof(double) * nrow * (size_t)np0);
-  if (!hbase) { rc = JUR_ENOMEM; goto done; }
-  pack_atm_rows(m, atm, hbase, (size_t)np0, 0);
-  stack_times(hbase, atm->time, np0, 0.0);
-  double tmin = atm->time[0], tmax = atm->time[0];
-  for (int i = 0; i < np0; i++) { tmin = fmin(tmin, atm->time[i]); tmax = fmax(tmax, atm->time[i]); }
-  for (long i = 0; i < nr; i++) { tmin = fmin(tmin, geom[0][i]); tmax = fmax(tmax, geom[0][i]); }
   if (hyd) {
     if (!(hyat = (long *)malloc((sizeof(long) + sizeof(int)) * (NH ? NH : 1)))) { rc = JUR_ENOMEM; goto done; }
     int *const hylen = (int *)(hyat + NH);
-    for (long q = 0; q < nrs; q++) { hyat[q] = hyf[q]; hylen[q] = hyf[NR + (size_t)q]; }
+    for (long q = 0; q < nrs; q++) { hyat[q] = op.hyf[q]; hylen[q] = op.hyf[NR + (size_t)q]; }
     for (long j = 1; j < pl.ncopy; j++) { hyat[nrs + j - 1] = pl.off[j]; hylen[nrs + j - 1] = (int)(pl.off[j + 1] - pl.off[j]); }
   }
 
@@ -3417,18 +3421,8 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
                o_dx = o_w + nrd, o_r = o_dx + NT * NB, o_xa = o_r + npr, o_cost = o_xa + npr, o_prior = o_cost + NT * NS,
                o_live = o_prior + NT * NS, o_dv = o_live + nfov, o_long = o_dv + ndv,
                o_int = o_long + pl.nlong + NH;   /* (the balance's first points behind the plan's longs, its lengths behind the ints) */
-  size_t const bytes = sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR + NH);
-  if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
-  hipStream_t const s = m->stream;
-  if ((rc = wait_done(m, s))) goto done;
-  if (bytes > m->scene_bytes) {
-    if (m->d_scene) (void)hipFree(m->d_scene);
-    m->d_scene = NULL; m->scene_bytes = 0;
-    if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
-      (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
-    }
-    m->scene_bytes = bytes;
-  }
+  hipStream_t s;
+  if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR + NH), &s))) goto done;
   if ((rc = ensure_io(m, nmax, 0))) goto done;
   if (fov && (rc = scene_fov_reserve(m, (size_t)nmax * (size_t)nd))) goto done;
   {
@@ -3436,7 +3430,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     long *const L = (long *)(D + o_long);
     int *const I = (int *)(D + o_int), *const d_first = I + pl.nint, *const d_len = d_first + NR;
     enqueued = 1;
-    hipError_t e = hipMemcpyAsync(D + o_base, hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(D + o_base, op.hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
     for (int q = 0; q < 7 && e == hipSuccess; q++) e = hipMemcpyAsync(D + o_geom + (size_t)q * NR, geom[q], sizeof(double) * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(D + o_inrad, rad_in, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(D + o_y, y, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
@@ -3446,9 +3440,9 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (e == hipSuccess && npr) e = hipMemcpyAsync(D + o_xa, prior_xa, sizeof(double) * NB, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(L, pl.longs, sizeof(long) * pl.nlong, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(I, pl.ints, sizeof(int) * pl.nint, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_first, first, sizeof(int) * 2 * NR, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_first, op.first, sizeof(int) * 2 * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
-    if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_live, hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_live, op.hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     long const *const d_hyat = L + pl.nlong;
     int const *const d_hylen = d_len + NR;
     if (NH && e == hipSuccess) e = hipMemcpyAsync(L + pl.nlong, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
@@ -3470,7 +3464,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     long const *const d_wptr = L, *const d_off = L + (pl.off - pl.longs), *const d_sptr = L + (pl.sptr - pl.longs);
     sk.ncopy = (int)pl.ncopy; sk.np0 = np0; sk.nrow = (int)nrow; sk.ng = ng; sk.nt = pl.nt;
     sk.off = d_off; sk.first = I; sk.prow = I + pl.ncopy; sk.pip = I + 2 * pl.ncopy;
-    sk.base = D + o_base; sk.h = NULL; sk.tmax = tmax; sk.span = (tmax - tmin) + 1.0;
+    sk.base = D + o_base; sk.h = NULL; sk.tmax = op.tmax; sk.span = op.span;
     st.nslice = nslice; st.ntrial = ntrial; st.np0 = np0; st.nt = pl.nt;
     st.wptr = d_wptr; st.off = d_off; st.sfirst = I + (pl.sfirst - pl.ints); st.erow = I + (pl.erow - pl.ints); st.eip = I + (pl.eip - pl.ints);
     st.base = D + o_base; st.dx = D + o_dx; st.ivar = npr ? D + o_r : NULL; st.xa = npr ? D + o_xa : NULL; st.prior = D + o_prior;
@@ -3490,12 +3484,12 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); rc = JUR_ENLOS; }
-    else if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); rc = JUR_EINVAL; }
+    rc = scene_status_rc(m, who);
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
-  free(first); free(rp); free(sl); free(hbase); free(hlive); free(hyf); free(hyat);
+  free(pass); free(hyat);
+  scene_open_free(&op);
   trial_plan_free(&pl);
   return rc;
 }
@@ -3544,17 +3538,8 @@ int jur_scene_hydrostatic_host(jur_model_t *m, atm_t const *atm_in, long nr, dou
     memcpy(h + 2 * N, atm_in->p, sizeof(double) * N);
     memcpy(h + 3 * N, atm_in->t, sizeof(double) * N);
     if (ig >= 0) memcpy(h + 4 * N, atm_in->q[ig], sizeof(double) * N);
-    if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
-    hipStream_t const s = m->stream;
-    if ((rc = wait_done(m, s))) goto done;
-    if (bytes > m->scene_bytes) {
-      if (m->d_scene) (void)hipFree(m->d_scene);
-      m->d_scene = NULL; m->scene_bytes = 0;
-      if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
-        (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
-      }
-      m->scene_bytes = bytes;
-    }
+    hipStream_t s;
+    if ((rc = scene_slab_reserve(m, who, bytes, &s))) goto done;
     double *const D = (double *)m->d_scene;
     long *const d_at = (long *)(D + o_at);
     int *const d_len = (int *)(D + o_len);
@@ -3615,19 +3600,9 @@ int jur_solve_slices_host(jur_model_t *m, long nslice, long const *wptr, double 
   {
     long const na = aptr[nslice], nb = wptr[nslice];
     size_t const o_A = 2 * (NS + 1), o_b = o_A + (size_t)na, o_sv = o_b + (size_t)nb;
-    size_t const bytes = sizeof(double) * (o_sv + solve_doubles((size_t)na, (size_t)nb, NS, (size_t)in->nlam, in->prior_ivar != NULL) +
-                                           (d_R ? solve_full_doubles((size_t)na, (size_t)nb, NS) : 0));
-    if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
-    hipStream_t const s = m->stream;
-    if ((rc = wait_done(m, s))) goto done;
-    if (bytes > m->scene_bytes) {
-      if (m->d_scene) (void)hipFree(m->d_scene);
-      m->d_scene = NULL; m->scene_bytes = 0;
-      if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
-        (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
-      }
-      m->scene_bytes = bytes;
-    }
+    size_t const nsv = solve_layout((size_t)na, (size_t)nb, NS, (size_t)in->nlam, in->prior_ivar != NULL, d_R != NULL).end;
+    hipStream_t s;
+    if ((rc = scene_slab_reserve(m, who, sizeof(double) * (o_sv + nsv), &s))) goto done;
     double *const D = (double *)m->d_scene;
     long *const L = (long *)m->d_scene;
     enqueued = 1;
@@ -3673,19 +3648,9 @@ int jur_diagnose_slices_host(jur_model_t *m, long nslice, long const *wptr, doub
   {
     long const na = aptr[nslice], nb = wptr[nslice];
     size_t const o_A = 2 * (NS + 1), o_dg = o_A + (size_t)na;
-    size_t const bytes = sizeof(double) * (o_dg + diag_doubles((size_t)na, (size_t)nb, NS, prior_ivar != NULL, (size_t)ninv, (size_t)ntile) +
-                                           (d_R ? diag_full_doubles((size_t)na) : 0));
-    if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
-    hipStream_t const s = m->stream;
-    if ((rc = wait_done(m, s))) goto done;
-    if (bytes > m->scene_bytes) {
-      if (m->d_scene) (void)hipFree(m->d_scene);
-      m->d_scene = NULL; m->scene_bytes = 0;
-      if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
-        (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
-      }
-      m->scene_bytes = bytes;
-    }
+    size_t const ndg = diag_layout((size_t)na, (size_t)nb, NS, prior_ivar != NULL, d_R != NULL, (size_t)ninv, (size_t)ntile).end;
+    hipStream_t s;
+    if ((rc = scene_slab_reserve(m, who, sizeof(double) * (o_dg + ndg), &s))) goto done;
     double *const D = (double *)m->d_scene;
     long *const L = (long *)m->d_scene;
     enqueued = 1;
@@ -3729,17 +3694,8 @@ int jur_prior_corr_host(jur_model_t *m, long nslice, long const *wptr, int const
     size_t const o_z = 2 * (NS + 1), o_sig = o_z + NB, o_cz = o_sig + NB, o_zero = o_cz + NQ, o_live = o_zero + NB, o_dx = o_live + NB,
                  o_lam = o_dx + NB, o_pred = o_lam + NS, o_Sa = o_pred + NS, o_L = o_Sa + NA, o_R = o_L + NA, o_int = o_R + NA;
     size_t const bytes = sizeof(double) * o_int + sizeof(int) * (NB + NS + 2 * (size_t)ninv + 1);
-    if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); rc = JUR_EHIP; goto done; }
-    hipStream_t const s = m->stream;
-    if ((rc = wait_done(m, s))) goto done;
-    if (bytes > m->scene_bytes) {
-      if (m->d_scene) (void)hipFree(m->d_scene);
-      m->d_scene = NULL; m->scene_bytes = 0;
-      if (hipMalloc(&m->d_scene, bytes) != hipSuccess) {
-        (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); rc = JUR_ENOMEM; goto done;
-      }
-      m->scene_bytes = bytes;
-    }
+    hipStream_t s;
+    if ((rc = scene_slab_reserve(m, who, bytes, &s))) goto done;
     double *const D = (double *)m->d_scene;
     long *const L = (long *)m->d_scene;
     int *const d_iq = (int *)(D + o_int), *const d_stat = d_iq + NB, *const d_imap = d_stat + NS;

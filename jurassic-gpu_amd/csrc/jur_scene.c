@@ -365,6 +365,37 @@ long jur_scene_recomp_offsets(long nr, long const *rp, int const *sid, int const
   return n;
 }
 
+/* ---- the rays of the slices: their lists, and the rays that remain once slices of a retrieval have ended ------------- */
+long jur_scene_rays_by_slice(long nr, long nslice, int const *sid, long *sptr, int *srays) {
+  for (long q = 0; q <= nslice; q++) sptr[q] = 0;
+  for (long r = 0; r < nr; r++) if (sid[r] >= 0) sptr[sid[r] + 1]++;
+  for (long q = 0; q < nslice; q++) sptr[q + 1] += sptr[q];
+  for (long r = 0; r < nr; r++) if (sid[r] >= 0) srays[sptr[sid[r]]++] = (int)r;   /* (sptr[q] now ends slice q ...) */
+  for (long q = nslice; q > 0; q--) sptr[q] = sptr[q - 1];                          /* ... and starts it again      */
+  sptr[0] = 0;
+  return sptr[nslice];
+}
+
+long jur_scene_gather_active(long nr, long nslice, long const *rp, int const *sid, int const *state, long const *sptr,
+                             int const *srays, int *act, int *pos, long *rpc, long *sptrc, int *sraysc) {
+  long n = 0, nl = 0;
+  rpc[0] = 0;
+  for (long r = 0; r < nr; r++) {
+    pos[r] = -1;
+    if (sid[r] < 0 || state[sid[r]] != JUR_RET_ACTIVE) continue;
+    act[n] = (int)r; pos[r] = (int)n;
+    rpc[n + 1] = rpc[n] + (rp[r + 1] - rp[r]);
+    n++;
+  }
+  for (long q = 0; q < nslice; q++) {
+    sptrc[q] = nl;
+    if (state[q] == JUR_RET_ACTIVE)
+      for (long i = sptr[q]; i < sptr[q + 1]; i++) sraysc[nl++] = pos[srays[i]];
+  }
+  sptrc[nslice] = nl;
+  return n;
+}
+
 /* ---- posterior diagnostics (jur_diagnose_slices_host, jur_diagnose_scene_host): the host arithmetic ------------------ */
 int jur_diag_check_out(char const *who, jur_diag_out_t const *out) {
   if (!out) { jur_set_error("%s: null argument (out)", who); return JUR_EINVAL; }
