@@ -625,6 +625,50 @@ int    jur_model_set_scene_hydz(jur_model_t *m, double hydz);
 double jur_model_scene_hydz(jur_model_t const *m);
 int    jur_scene_hydrostatic_host(jur_model_t *m, atm_t const *atm_in, long nr, double const *time, atm_t *atm_out);
 
+/* A box on the state of the scene retrieval.  After every update of the state, before the forward model runs on it,
+ * upstream's retrieval forces the atmosphere back into its physical range: p = min(max(p, 5e-7), 5e4), T = min(max(T, 100),
+ * 400), q = min(max(q, 0), 1), k = max(k, 0).  Here the model holds one interval per quantity, off by default, and the two
+ * entries that move a state honour it; with the box off every entry allocates, copies and launches what it did before and
+ * returns the same bits.
+ *
+ * jur_state_bound: the rule, one text for host and device:  c = x > lo ? x : lo;  c = c < hi ? c : hi.  A NaN x gives lo
+ *   (as upstream's GSL_MAX / GSL_MIN do); lo = -inf or hi = +inf leaves that side open.  Only state elements are bounded
+ *   (the points inside the ret*_zmin/zmax windows, in jur_scene_elements' order); nothing else in the atmosphere is
+ *   touched.  A first guess outside the box is not moved by itself: it enters the box with the first trial and the first
+ *   accepted step.
+ * jur_model_set_state_bounds: lo[nq], hi[nq] for the nq = 2 + ng + nw quantities in the iq numbering of
+ *   jur_scene_elements (0 p, 1 T, 2 + g q, 2 + ng + w k).  nq == 0 or a NULL pointer switches the box off.  JUR_EINVAL,
+ *   naming the quantity, for an nq that is not the model's, a NaN, or lo > hi (lo == hi holds the quantity fixed); after a
+ *   refusal whatever was set before stays set.
+ * jur_model_state_bounds: what is set into lo and hi (either may be NULL); returns nq, 0 when off.
+ * jur_state_bounds_upstream (host arithmetic, no GPU): upstream's box above for the control's quantities (k: [0, +inf]);
+ *   outputs may be NULL; returns nq.
+ * jur_state_on_bounds (host arithmetic, no GPU): side[e] = -1 / 0 / +1 for an element x[e] of quantity iq[e] that equals
+ *   its lower bound, neither bound, or its upper bound (lo == hi and x equal to both: -1); side may be NULL.  Returns the
+ *   number of non-zero entries; JUR_EINVAL for an iq outside 0..nq-1.  This is how a caller finds the elements of out->x
+ *   that the box holds: the diagnostics describe the unconstrained problem and do not know about the box.
+ * jur_trial_scene_host while a box is set: the trial state of element e under trial t is bound(x_e + dx[t][e]) in every
+ *   place the state is formed -- the stacked copy that is traced, the diagonal prior term, and the difference xa - state
+ *   that the quadratic form of a full prior precision reads.  The contract keeps its form: cost[t][s] is, bit for bit, what
+ *   jur_normal_scene_host returns on the atmosphere with the bounded step written back, prior[t][s] the documented chain
+ *   on the bounded state.
+ * jur_retrieve_scene_host while a box is set: the trial pass as above; an accepted slice moves to bound(x + dx[best]) in
+ *   the base rows, so the next iteration's prior_dx = xa - x, the reuse iterations of jur_model_set_kernel_recomp, out->x,
+ *   atm_ret and the final forward model all see the bounded state.  With jur_model_set_scene_hydz on the order is
+ *   upstream's: bound first, then the balance, for trial copies and accepted base rows alike.  pred and the steps dx of
+ *   the solver stay unbounded, and jur_retrieve_decide is unchanged.  A trial whose rays still leave the traceable range
+ *   ends the call with JUR_ENLOS as before.
+ * The box is expanded on the host into two arrays per element when a call starts, uploaded once, and counted in the
+ *   entry's JUR_ENOMEM accounting before anything is launched; no launch is added (jur_scene_elements_kernel,
+ *   jur_scene_prior_kernel and jur_scene_prior_diff_kernel apply the rule where they form x + dx).
+ * Every other entry (jur_step_scene_host, jur_gradient_scene_host, jur_normal_scene_host, jur_kernel_scene_host, the
+ *   diagnostics, jur_kernel) moves no state and ignores the setting. */
+int    jur_model_set_state_bounds(jur_model_t *m, int nq, double const *lo, double const *hi);
+int    jur_model_state_bounds(jur_model_t const *m, double *lo, double *hi);
+int    jur_state_bounds_upstream(ctl_t const *ctl, double *lo, double *hi);
+double jur_state_bound(double x, double lo, double hi);
+long   jur_state_on_bounds(int nq, double const *lo, double const *hi, long n, int const *iq, double const *x, signed char *side);
+
 /* The scene Jacobian reused between the iterations of a retrieval (upstream's KERNEL_RECOMP).  The model holds the switch
  * as it holds the field of view; with every == 1 (the default) jur_retrieve_scene_host allocates and launches what it did
  * before and returns the same bits.  Only jur_retrieve_scene_host honours it.

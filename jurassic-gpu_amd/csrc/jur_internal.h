@@ -304,7 +304,11 @@ typedef struct {
   double const *ivar, *xa;      /* [wptr[nslice]] diagonal prior (jurk_scene_prior, JUR_ELEM_PRIOR_DX)      */
   double *prior;                /* [ntrial][nslice] written by jurk_scene_prior ([nslice] with dx == NULL)  */
   double *out;                  /* [wptr[nslice]] written by JUR_ELEM_PRIOR_DX (xa - x) and JUR_ELEM_STATE (x) */
+  double const *lo, *hi;        /* [wptr[nslice]] the box of every element (jur_model_set_state_bounds), or both NULL:
+                                 * where x + dx is formed, JUR_STATE_BOUND of it takes its place                    */
 } jur_scene_trial_t;
+/* the rule of jur_state_bound, one text for host and device: a NaN x gives lo, an infinite bound does not bind */
+#define JUR_STATE_BOUND(c, x, lo, hi) do { (c) = (x) > (lo) ? (x) : (lo); (c) = (c) < (hi) ? (c) : (hi); } while (0)
 enum { JUR_ELEM_APPLY = 0, JUR_ELEM_PRIOR_DX = 1, JUR_ELEM_ACCEPT = 2, JUR_ELEM_STATE = 3 };
 /* one lane per state element (JUR_ELEM_APPLY: per trial and element) of the nb = wptr[nslice]: what `op` says */
 int jurk_scene_elements(jur_scene_trial_t const *a, int op, long nb, void *stream);
@@ -447,6 +451,11 @@ JUR_HIDDEN long jur_scene_slice_elements(ctl_t const *ctl, atm_t const *atm, int
  * share the first point */
 typedef struct { int first, len, next; long nel; } jur_scene_slice_t;
 JUR_HIDDEN long jur_scene_distinct(int np, long nr, int const *first, int const *len, long const *rp, int *sid, jur_scene_slice_t **out);
+/* the per-quantity box of jur_model_set_state_bounds laid out per element (jur_scene.c; no GPU): elo[e] = lo[iq], ehi[e] =
+ * hi[iq] with iq = erow[e] - 4, the quantity of the row that jur_scene_trial_t's erow names; and the check of a box
+ * (JUR_EINVAL naming the quantity: nq is not nq_model, a NaN, lo > hi) */
+JUR_HIDDEN void jur_state_bounds_expand(double const *lo, double const *hi, long n, int const *erow, double *elo, double *ehi);
+JUR_HIDDEN int jur_state_bounds_check(char const *who, int ng, int nw, int nq, double const *lo, double const *hi);
 
 /* hydrostatic_1d_h2o on one profile of n points (jur_scene.c): what jur_model_set_atm's step and jur_scene_hydrostatic
  * both run; qh2o == NULL: dry air */

@@ -3232,6 +3232,8 @@ __global__ __launch_bounds__(256) void jur_scene_dofs_kernel(jur_scene_diag_t a)
 //   JUR_ELEM_PRIOR_DX  out[e] = xa[e] - x_e
 //   JUR_ELEM_ACCEPT    x_e += dx[choice[s]][e] in the base rows where choice[s] >= 0
 //   JUR_ELEM_STATE     out[e] = x_e
+// With a box on the state (a.lo, a.hi: jur_model_set_state_bounds) the sum of JUR_ELEM_APPLY and JUR_ELEM_ACCEPT is bounded
+// by JUR_STATE_BOUND, the host's text, before it is stored: the branch is uniform over the launch.
 __global__ __launch_bounds__(256) void jur_scene_elements_kernel(jur_scene_trial_t a, int op) {
   long const g = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long const nb = a.wptr[a.nslice];
@@ -3243,16 +3245,23 @@ __global__ __launch_bounds__(256) void jur_scene_elements_kernel(jur_scene_trial
   double const x = a.base[at];
   if (op == JUR_ELEM_APPLY) {
     long const copy = 1 + s * a.ntrial + t;
-    a.rows[(long)a.erow[e] * a.nt + a.off[copy] + (a.eip[e] - a.sfirst[s])] = x + a.dx[g];
+    double v = x + a.dx[g];
+    if (a.lo) JUR_STATE_BOUND(v, v, a.lo[e], a.hi[e]);
+    a.rows[(long)a.erow[e] * a.nt + a.off[copy] + (a.eip[e] - a.sfirst[s])] = v;
   } else if (op == JUR_ELEM_PRIOR_DX) a.out[e] = a.xa[e] - x;
   else if (op == JUR_ELEM_ACCEPT) {
     int const c = a.choice[s];
-    if (c >= 0) a.base[at] = x + a.dx[(long)c * nb + e];
+    if (c >= 0) {
+      double v = x + a.dx[(long)c * nb + e];
+      if (a.lo) JUR_STATE_BOUND(v, v, a.lo[e], a.hi[e]);
+      a.base[at] = v;
+    }
   } else a.out[e] = x;
 }
 
 // One lane per (trial, slice): the prior term as the fixed chain d = xa - (x + dx); t = r * d; t = t * d; acc = acc + t
-// over the slice's elements ascending (this file is compiled without contraction: four roundings per element).
+// over the slice's elements ascending (this file is compiled without contraction: four roundings per element).  With a box
+// on the state the sum x + dx is bounded first, as JUR_ELEM_APPLY bounds it; the state as it stands (dx == NULL) never is.
 __global__ __launch_bounds__(64) void jur_scene_prior_kernel(jur_scene_trial_t a) {
   long const g = (long)blockIdx.x * blockDim.x + threadIdx.x;
   int const nrow = a.dx ? a.ntrial : 1;
@@ -3263,7 +3272,10 @@ __global__ __launch_bounds__(64) void jur_scene_prior_kernel(jur_scene_trial_t a
   double acc = 0.;
   for (long e = a.wptr[s]; e < a.wptr[s + 1]; e++) {
     double x = a.base[(long)a.erow[e] * a.np0 + a.eip[e]];
-    if (a.dx) x = x + a.dx[t * nb + e];
+    if (a.dx) {
+      x = x + a.dx[t * nb + e];
+      if (a.lo) JUR_STATE_BOUND(x, x, a.lo[e], a.hi[e]);   // (the trial state as JUR_ELEM_APPLY stores it)
+    }
     double const d = a.xa[e] - x;
     double term = a.ivar[e] * d;
     term = term * d;
@@ -3447,7 +3459,8 @@ __global__ __launch_bounds__(256) void jur_scene_prior_pred_kernel(jur_scene_pqu
   if (tid == 0) a.out[s] = red[0] + lam * q;
 }
 
-// d[t][e] = xa_e - (x_e + dx[t][e]), the difference jur_scene_prior_kernel forms, one lane per trial and element
+// d[t][e] = xa_e - (x_e + dx[t][e]), the difference jur_scene_prior_kernel forms (of the bounded sum where a box is set),
+// one lane per trial and element
 __global__ __launch_bounds__(256) void jur_scene_prior_diff_kernel(jur_scene_trial_t a) {
   long const g = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long const nb = a.wptr[a.nslice];
@@ -3456,7 +3469,10 @@ __global__ __launch_bounds__(256) void jur_scene_prior_diff_kernel(jur_scene_tri
   long const s = scene_find<false>(a.wptr, 0, a.nslice, e);
   if (a.state && a.state[s] != 0) return;
   double x = a.base[(long)a.erow[e] * a.np0 + a.eip[e]];
-  if (a.dx) x = x + a.dx[g];
+  if (a.dx) {
+    x = x + a.dx[g];
+    if (a.lo) JUR_STATE_BOUND(x, x, a.lo[e], a.hi[e]);
+  }
   a.out[g] = a.xa[e] - x;
 }
 

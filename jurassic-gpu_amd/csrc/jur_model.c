@@ -102,6 +102,8 @@ struct jur_model {
   double scene_hydz;            /* hydrostatic balance of the scene entries per slice (jur_model_set_scene_hydz): the
                                    reference altitude [km], negative: off                                   */
   int kernel_recomp;            /* jur_retrieve_scene_host recomputes the Jacobian every n-th iteration (jur_model_set_kernel_recomp) */
+  int sb_nq;                    /* the box on the state (jur_model_set_state_bounds): 2 + ng + nw quantities, 0: off */
+  double sb_lo[2 + JUR_NG + JUR_NW], sb_hi[2 + JUR_NG + JUR_NW];
   double *d_kq, *h_kq;          /* jur_kernel: perturbation steps and dense difference quotients (device, pinned host) */
   long kq_cap;
   /* small calls: the fused kernel (jur_pencil_kernel) instead of sort + three batched kernels */
@@ -1548,6 +1550,26 @@ int jur_model_set_scene_hydz(jur_model_t *m, double hydz) {
 
 double jur_model_scene_hydz(jur_model_t const *m) { return m ? m->scene_hydz : -1; }
 
+/* the box on the state: held by value, expanded per element by the entries that move a state when a call starts */
+int jur_model_set_state_bounds(jur_model_t *m, int nq, double const *lo, double const *hi) {
+  char const *const who = "jur_model_set_state_bounds";
+  if (!m) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if (nq == 0 || !lo || !hi) { m->sb_nq = 0; return JUR_OK; }
+  int const rc = jur_state_bounds_check(who, m->view.ng, m->view.nw, nq, lo, hi);
+  if (rc) return rc;                                /* (what was set before stays set) */
+  memcpy(m->sb_lo, lo, sizeof(double) * (size_t)nq);
+  memcpy(m->sb_hi, hi, sizeof(double) * (size_t)nq);
+  m->sb_nq = nq;
+  return JUR_OK;
+}
+
+int jur_model_state_bounds(jur_model_t const *m, double *lo, double *hi) {
+  if (!m) return 0;
+  if (lo) memcpy(lo, m->sb_lo, sizeof(double) * (size_t)m->sb_nq);
+  if (hi) memcpy(hi, m->sb_hi, sizeof(double) * (size_t)m->sb_nq);
+  return m->sb_nq;
+}
+
 /* ---- the Jacobian of the retrieval loop, reused between iterations ------------------------- */
 int jur_model_set_kernel_recomp(jur_model_t *m, int every) {
   char const *const who = "jur_model_set_kernel_recomp";
@@ -2570,7 +2592,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   scene_open_t op;
   long *off = NULL, *pass = NULL, *scopy = NULL, *nptr = NULL;
   int *cdesc = NULL, *iqa = NULL, *ipa = NULL, *srays = NULL;
-  double *rd = NULL, *htimec = NULL;
+  double *rd = NULL, *htimec = NULL, *hbd = NULL;   /* (hbd: the box on the state per element, lo | hi) */
   int *ri = NULL, *hact = NULL, *dmap = NULL;
   long *hcomp = NULL, ninv = 0, ndtile = 0;
   long *hkoff = NULL;                               /* held blocks: the first double of every ray's | the gradient's workgroups by slice */
@@ -2728,7 +2750,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
    * (geometry, mask, y, weight; rowptr and sptr of their own), the plan's index arrays */
   int const looping = rt && ntiles;
   size_t const NRD = NR * (size_t)nd;
-  size_t const rt_dbl = looping ? 2 * RL * RS + RS + 2 * (size_t)nb + 7 * NR + 3 * NRD + (d_R ? RL * (size_t)nb : 0) : 0;   /* (last: xa - (x + dx) of every trial) */
+  size_t const nbd = (looping && m->sb_nq) ? 2 * (size_t)nb : 0;   /* a box on the state: lo | hi of every element */
+  size_t const rt_dbl = looping ? 2 * RL * RS + RS + 2 * (size_t)nb + 7 * NR + 3 * NRD + (d_R ? RL * (size_t)nb : 0) + nbd : 0;   /* (xa - (x + dx) of every trial; last: the box) */
   size_t const rt_lng = looping ? pl.nlong + (NR + 1) + (RS + 1) : 0;
   size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist : 0;
   size_t const rt_atm_bytes = looping ? sizeof(double) * (nrow + 1) * (size_t)pl.nt : 0;
@@ -2934,7 +2957,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     jur_retrieve_out_t const *const ro = rt ? rt->out : NULL;
     double *const d_tcost = D + o_rt, *const d_tprior = d_tcost + RL * RS, *const d_prior0 = d_tprior + RL * RS, *const d_xout = d_prior0 + RS,
            *const d_xa = d_xout + nb, *const d_geomc = d_xa + nb, *const d_radc = d_geomc + 7 * NR, *const d_yc = d_radc + NRD,
-           *const d_wc = d_yc + NRD, *const d_dvec = d_wc + NRD;
+           *const d_wc = d_yc + NRD, *const d_dvec = d_wc + NRD, *const d_bd = d_dvec + (d_R ? RL * (size_t)nb : 0);
     long *const Lr = (long *)(D + o_rt + rt_dbl), *const d_rpc = Lr + pl.nlong, *const d_sptrc = d_rpc + NR + 1;
     int *const Ir = I + nint0, *const d_state = Ir + pl.nint, *const d_choice = d_state + RS, *const d_act = d_choice + RS,
         *const d_firstc = d_act + NR, *const d_lenc = d_firstc + NR, *const d_copy0c = d_lenc + NR, *const d_tcopy0c = d_copy0c + NR,
@@ -2967,6 +2990,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (e == hipSuccess) e = hipMemcpyAsync(Ir, pl.ints, sizeof(int) * pl.nint, hipMemcpyHostToDevice, s);
       if (npr && e == hipSuccess) e = hipMemcpyAsync(sv_r, rin->prior_ivar, sizeof(double) * npr, hipMemcpyHostToDevice, s);
       if (npr && e == hipSuccess) e = hipMemcpyAsync(d_xa, rin->prior_xa, sizeof(double) * npr, hipMemcpyHostToDevice, s);
+      if (nbd) {                                    /* (the host array lives to the end of the call) */
+        if (!(hbd = (double *)malloc(sizeof(double) * nbd))) { rc = JUR_ENOMEM; goto done; }
+        jur_state_bounds_expand(m->sb_lo, m->sb_hi, nb, pl.erow, hbd, hbd + nb);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_bd, hbd, sizeof(double) * nbd, hipMemcpyHostToDevice, s);
+      }
       if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
       long const *const t_off = Lr + (pl.off - pl.longs);
       tsk.ncopy = (int)pl.ncopy; tsk.np0 = np0; tsk.nrow = (int)nrow; tsk.ng = ng; tsk.nt = pl.nt;
@@ -2976,6 +3004,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       tst.wptr = Lr; tst.off = t_off; tst.sfirst = Ir + (pl.sfirst - pl.ints); tst.erow = Ir + (pl.erow - pl.ints);
       tst.eip = Ir + (pl.eip - pl.ints); tst.state = d_state; tst.choice = d_choice;
       tst.base = D + o_base; tst.dx = sv_dx; tst.ivar = npr ? sv_r : NULL; tst.xa = npr ? d_xa : NULL; tst.prior = d_tprior;
+      if (nbd) { tst.lo = d_bd; tst.hi = d_bd + nb; }
       tps.nr = nr; tps.nd = nd; tps.ntrial = rin->nlam; tps.first = d_first; tps.len = d_len; tps.tcopy0 = Ir + (pl.tcopy0 - pl.ints);
       tps.off = t_off; tps.in_geom = D + o_geom; tps.in_rad = D + o_inrad; tps.nslice = nslice; tps.sptr = Lr + (pl.sptr - pl.longs);
       tps.srays = Ir + (pl.srays - pl.ints); tps.state = d_state; tps.y = D + o_y; tps.weight = D + o_w; tps.cost = d_tcost;
@@ -3263,7 +3292,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
   free(srays); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa); free(rd); free(ri); free(hact); free(hcomp);
-  free(ret_atm); free(dmap); free(htimec); free(hyat); free(hkoff); free(hjac);
+  free(ret_atm); free(dmap); free(htimec); free(hyat); free(hkoff); free(hjac); free(hbd);
   scene_open_free(&op);
   trial_plan_free(&pl);
   return rc;
@@ -3363,6 +3392,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   int enqueued = 0;
   scene_open_t op;
   long *pass = NULL;
+  double *hbd = NULL;                               /* the box per element on the host: lo | hi */
   int const fov = m->fov_n > 0;                     /* a field of view is set: the trial radiances are convolved */
   int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: base rows and trial copies are balanced */
   long *hyat = NULL;
@@ -3389,10 +3419,11 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
 
   size_t const NB = (size_t)nb, NS = (size_t)nslice, NT = (size_t)ntrial, npr = prior_ivar ? NB : 0;
   size_t const ndv = d_R ? NT * NB : 0;               /* (a full prior precision: xa - (x + dx) of every trial) */
+  size_t const nbd = m->sb_nq ? 2 * NB : 0;           /* (a box on the state: lo | hi of every element) */
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)pl.nt;
   size_t const nfov = fov ? nrd : 0;                  /* (the effective mask) */
   size_t const NH = hyd ? (size_t)nrs + NT * NS : 0;  /* (the balance's segments: the ray slices, every trial copy) */
-  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov + ndv) + (sizeof(long) + sizeof(int)) * NH;
+  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov + ndv + nbd) + (sizeof(long) + sizeof(int)) * NH;
   if ((double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and accumulators (%zu bytes) exceed the workspace budget: "
                   "call with fewer trials or the rays of fewer slices at a time", who, pl.nt, atm_bytes, acc_bytes);
@@ -3410,6 +3441,10 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   long const npass = jur_trial_passes(nr, ntrial, cap, fov ? geom[0] : NULL, pass, &nmax);
   if (npass < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
 
+  if (nbd) {
+    if (!(hbd = (double *)malloc(sizeof(double) * nbd))) { rc = JUR_ENOMEM; goto done; }
+    jur_state_bounds_expand(m->sb_lo, m->sb_hi, nb, pl.erow, hbd, hbd + NB);
+  }
   if (hyd) {
     if (!(hyat = (long *)malloc((sizeof(long) + sizeof(int)) * (NH ? NH : 1)))) { rc = JUR_ENOMEM; goto done; }
     int *const hylen = (int *)(hyat + NH);
@@ -3419,7 +3454,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
 
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_y = o_inrad + nrd, o_w = o_y + nrd,
                o_dx = o_w + nrd, o_r = o_dx + NT * NB, o_xa = o_r + npr, o_cost = o_xa + npr, o_prior = o_cost + NT * NS,
-               o_live = o_prior + NT * NS, o_dv = o_live + nfov, o_long = o_dv + ndv,
+               o_live = o_prior + NT * NS, o_dv = o_live + nfov, o_bd = o_dv + ndv, o_long = o_bd + nbd,
                o_int = o_long + pl.nlong + NH;   /* (the balance's first points behind the plan's longs, its lengths behind the ints) */
   hipStream_t s;
   if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR + NH), &s))) goto done;
@@ -3443,6 +3478,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (e == hipSuccess) e = hipMemcpyAsync(d_first, op.first, sizeof(int) * 2 * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
     if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_live, op.hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    if (nbd && e == hipSuccess) e = hipMemcpyAsync(D + o_bd, hbd, sizeof(double) * nbd, hipMemcpyHostToDevice, s);
     long const *const d_hyat = L + pl.nlong;
     int const *const d_hylen = d_len + NR;
     if (NH && e == hipSuccess) e = hipMemcpyAsync(L + pl.nlong, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
@@ -3468,6 +3504,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     st.nslice = nslice; st.ntrial = ntrial; st.np0 = np0; st.nt = pl.nt;
     st.wptr = d_wptr; st.off = d_off; st.sfirst = I + (pl.sfirst - pl.ints); st.erow = I + (pl.erow - pl.ints); st.eip = I + (pl.eip - pl.ints);
     st.base = D + o_base; st.dx = D + o_dx; st.ivar = npr ? D + o_r : NULL; st.xa = npr ? D + o_xa : NULL; st.prior = D + o_prior;
+    if (nbd) { st.lo = D + o_bd; st.hi = D + o_bd + NB; }
     ps.nr = nr; ps.nd = nd; ps.ntrial = ntrial; ps.first = d_first; ps.len = d_len; ps.tcopy0 = I + (pl.tcopy0 - pl.ints); ps.off = d_off;
     ps.in_geom = D + o_geom; ps.in_rad = D + o_inrad; ps.nslice = nslice; ps.sptr = d_sptr; ps.srays = I + (pl.srays - pl.ints);
     ps.y = D + o_y; ps.weight = D + o_w; ps.cost = D + o_cost;
@@ -3488,7 +3525,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
-  free(pass); free(hyat);
+  free(pass); free(hyat); free(hbd);
   scene_open_free(&op);
   trial_plan_free(&pl);
   return rc;

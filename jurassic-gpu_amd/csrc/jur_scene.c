@@ -2,6 +2,7 @@
  * (jur_normal_scene_host): which slice of the atmosphere every ray is traced through, which state elements lie in it
  * and which distinct slices a scene has.  Host arithmetic only: no GPU, no model. */
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <strings.h>
@@ -679,4 +680,69 @@ long jur_scene_ray_slices(ctl_t const *ctl, atm_t const *atm, long nr, double co
   if (n < 0) jur_set_error("scene_ray_slices: out of memory");
   free(first);
   return n;
+}
+
+/* ---- the box on the state (jur_model_set_state_bounds) ------------------------------------------------------------------ */
+double jur_state_bound(double x, double lo, double hi) {
+  double c;
+  JUR_STATE_BOUND(c, x, lo, hi);
+  return c;
+}
+
+/* the name of quantity iq for a message: p, T, q[g] (with the emitter where the control is at hand), k[w] */
+static char const *quantity_name(int ng, int iq, char buf[32]) {
+  if (iq == 0) return "p";
+  if (iq == 1) return "T";
+  if (iq < 2 + ng) snprintf(buf, 32, "q[%d]", iq - 2);
+  else snprintf(buf, 32, "k[%d]", iq - 2 - ng);
+  return buf;
+}
+
+int jur_state_bounds_check(char const *who, int ng, int nw, int nq, double const *lo, double const *hi) {
+  char name[32];
+  if (nq != 2 + ng + nw) {
+    jur_set_error("%s: nq = %d, the model has %d quantities (p, T, %d q, %d k)", who, nq, 2 + ng + nw, ng, nw);
+    return JUR_EINVAL;
+  }
+  for (int iq = 0; iq < nq; iq++) {
+    if (lo[iq] != lo[iq] || hi[iq] != hi[iq]) {
+      jur_set_error("%s: the %s bound of quantity %d (%s) is NaN (-inf or +inf leaves a side open)", who, lo[iq] != lo[iq] ? "lower" : "upper",
+                    iq, quantity_name(ng, iq, name));
+      return JUR_EINVAL;
+    }
+    if (lo[iq] > hi[iq]) {
+      jur_set_error("%s: quantity %d (%s): lo = %g > hi = %g", who, iq, quantity_name(ng, iq, name), lo[iq], hi[iq]);
+      return JUR_EINVAL;
+    }
+  }
+  return JUR_OK;
+}
+
+void jur_state_bounds_expand(double const *lo, double const *hi, long n, int const *erow, double *elo, double *ehi) {
+  for (long e = 0; e < n; e++) { elo[e] = lo[erow[e] - 4]; ehi[e] = hi[erow[e] - 4]; }
+}
+
+int jur_state_bounds_upstream(ctl_t const *ctl, double *lo, double *hi) {
+  if (!ctl || ctl->ng < 0 || ctl->ng > JUR_NG || ctl->nw < 0 || ctl->nw > JUR_NW) { jur_set_error("jur_state_bounds_upstream: bad arguments"); return JUR_EINVAL; }
+  int const nq = 2 + ctl->ng + ctl->nw;
+  for (int iq = 0; iq < nq; iq++) {
+    double const l = iq == 0 ? 5e-7 : iq == 1 ? 100. : 0., h = iq == 0 ? 5e4 : iq == 1 ? 400. : iq < 2 + ctl->ng ? 1. : INFINITY;
+    if (lo) lo[iq] = l;
+    if (hi) hi[iq] = h;
+  }
+  return nq;
+}
+
+long jur_state_on_bounds(int nq, double const *lo, double const *hi, long n, int const *iq, double const *x, signed char *side) {
+  char const *const who = "jur_state_on_bounds";
+  if (nq < 0 || n < 0 || (nq > 0 && (!lo || !hi)) || (n > 0 && (!iq || !x))) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  for (long e = 0; e < n; e++)
+    if (iq[e] < 0 || iq[e] >= nq) { jur_set_error("%s: element %ld is of quantity %d, the box has %d", who, e, iq[e], nq); return JUR_EINVAL; }
+  long count = 0;
+  for (long e = 0; e < n; e++) {
+    int const s = x[e] == lo[iq[e]] ? -1 : x[e] == hi[iq[e]] ? 1 : 0;
+    if (side) side[e] = (signed char)s;
+    count += s != 0;
+  }
+  return count;
 }

@@ -170,6 +170,14 @@ def lib():
                                                   dp, dp, dp, dp, dp, lp_, C.c_long]
             L.jur_scene_recomp_offsets.restype = C.c_long
             L.jur_scene_recomp_offsets.argtypes = [C.c_long, lp_, ip_, ip_, ip_, C.c_int, lp_]
+        if hasattr(L, "jur_model_set_state_bounds"):   # (an A/B library from before the box on the state has none of these)
+            L.jur_model_set_state_bounds.argtypes = [C.c_void_p, C.c_int, dp, dp]
+            L.jur_model_state_bounds.argtypes = [C.c_void_p, dp, dp]
+            L.jur_state_bounds_upstream.argtypes = [C.c_void_p, dp, dp]
+            L.jur_state_bound.restype = C.c_double
+            L.jur_state_bound.argtypes = [C.c_double, C.c_double, C.c_double]
+            L.jur_state_on_bounds.restype = C.c_long
+            L.jur_state_on_bounds.argtypes = [C.c_int, dp, dp, C.c_long, ip_, dp, C.POINTER(C.c_byte)]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -486,6 +494,27 @@ class Model:
         v = lib().jur_model_scene_hydz(self.h)
         return v if v >= 0 else None
 
+    def set_state_bounds(self, lo, hi=None):
+        """A box on the state (jur_model_set_state_bounds): lo, hi per quantity in scene_elements' iq numbering (0 p, 1 T,
+        2 + g q, 2 + ng + w k); -inf / +inf leaves a side open; lo None switches it off (the default).  While it is set
+        trial_scene and retrieve_scene form state_bound(x + dx) wherever they formed x + dx; no other entry reads it."""
+        if lo is None:
+            _chk(lib().jur_model_set_state_bounds(self.h, 0, None, None))
+            return
+        l, h = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (lo, hi))
+        if len(l) != len(h):
+            raise ValueError("lo and hi must have one entry per quantity each")
+        _chk(lib().jur_model_set_state_bounds(self.h, len(l), _p(l), _p(h)))
+
+    def state_bounds(self):
+        """What set_state_bounds set as (lo, hi), or None."""
+        nq = lib().jur_model_state_bounds(self.h, None, None)
+        if nq == 0:
+            return None
+        lo, hi = np.zeros(nq), np.zeros(nq)
+        lib().jur_model_state_bounds(self.h, _p(lo), _p(hi))
+        return lo, hi
+
     def scene_hydrostatic(self, atm, time):
         """jur_scene_hydrostatic_host: a new atm_t, atm with p balanced on the device over the slices that rays with the
         time stamps `time` are traced through -- the atmosphere the scene entries work on while set_scene_hydz is on."""
@@ -699,11 +728,12 @@ class Model:
         (max_iter, 2): the replicated rays of the Jacobian and of the trial passes.  Where a slice took no part in an
         iteration its h_lam, h_tcost, h_tprior are NaN and its h_status, h_best, h_accept -1.  Under
         set_kernel_recomp(every > 1) the iterations it % every != 0 reuse the blocks and A of the last Jacobian iteration;
-        their h_work[it, 0] is the number of rays traced for the gradient."""
+        their h_work[it, 0] is the number of rays traced for the gradient.  Under set_state_bounds every trial state and
+        every accepted state is state_bound(x + dx); state_on_bounds of x tells which elements the box holds."""
         g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, rowptr)
         nr, nd = g.shape[1], self.nd
         ns, n = len(lay["sfirst"]), int(lay["wptr"][-1])
-        ff = np.ascontiguousarray(fac, dtype=np.float64).ravel()
+        ff =np.ascontiguousarray(fac, dtype=np.float64).ravel()
         nlam, mi = len(ff), max(int(max_iter), 0)
         pri = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (prior_ivar, prior_xa)]
         if any(x is not None and x.size != n for x in pri):
@@ -732,9 +762,13 @@ class Model:
             C.memmove(C.byref(ret), C.byref(atm), C.sizeof(abi.atm_t))
         garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
         tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
-        _chk(lib().jur_retrieve_scene_host(self.h, C.byref(atm), C.byref(ret), nr, garr, _p(rad), _p(tau), tarr,
-                                           npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(C.POINTER(C.c_long)),
-                                           _p(yy), _p(ww), C.byref(rin), C.byref(rout), max_rays_per_pass))
+        try:
+            _chk(lib().jur_retrieve_scene_host(self.h, C.byref(atm), C.byref(ret), nr, garr, _p(rad), _p(tau), tarr,
+                                               npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(C.POINTER(C.c_long)),
+                                               _p(yy), _p(ww), C.byref(rin), C.byref(rout), max_rays_per_pass))
+        except JurassicError as e:                      # (what the iterations that completed left in the per-slice arrays)
+            e.partial = dict(res, **(hist if history is True else {}))
+            raise
         out = dict(lay, atm=ret, rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, **res)
         if history is True:
             out.update(hist)
@@ -946,6 +980,39 @@ def retrieve_decide(J, Jt, lamt, status, lam, state, tol, lam_max, fac_max):
     _chk(lib().jur_retrieve_decide(nlam, ns, tol, lam_max, fac_max, _p(JJ), _p(T), _p(LT), S.ctypes.data_as(ip_), _p(lm),
                                    st.ctypes.data_as(ip_), best.ctypes.data_as(ip_), accept.ctypes.data_as(ip_)))
     return dict(lam=lm, state=st, best=best, accept=accept)
+
+
+def state_bounds_upstream(ctl):
+    """jur_state_bounds_upstream: (lo, hi) of upstream's box for the control's quantities -- p in [5e-7, 5e4], T in
+    [100, 400], q in [0, 1], k in [0, +inf]."""
+    nq = _chk(lib().jur_state_bounds_upstream(C.byref(ctl), None, None))
+    lo, hi = np.zeros(nq), np.zeros(nq)
+    _chk(lib().jur_state_bounds_upstream(C.byref(ctl), _p(lo), _p(hi)))
+    return lo, hi
+
+
+def state_bound(x, lo, hi):
+    """jur_state_bound on scalars or arrays (broadcast): the library's own arithmetic, element by element."""
+    xs, ls, hs = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64))
+    f = lib().jur_state_bound
+    out = np.array([f(float(a), float(b), float(c)) for a, b, c in zip(xs.ravel(), ls.ravel(), hs.ravel())], dtype=np.float64).reshape(xs.shape)
+    return out if out.ndim else float(out)
+
+
+def state_on_bounds(lo, hi, iq, x):
+    """jur_state_on_bounds: side (int8, -1 / 0 / +1 per element: at its lower bound, at neither, at its upper bound) for
+    the elements x of the quantities iq under the box (lo, hi) per quantity, and their number -> dict(side, count)."""
+    l, h = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (lo, hi))
+    if len(l) != len(h):
+        raise ValueError("lo and hi must have one entry per quantity each")
+    q = np.ascontiguousarray(iq, dtype=np.int32).ravel()
+    xs = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    if len(q) != len(xs):
+        raise ValueError("iq and x must have one entry per element each")
+    side = np.zeros(len(xs), dtype=np.int8)
+    n = _chk(lib().jur_state_on_bounds(len(l), _p(l), _p(h), len(xs), q.ctypes.data_as(C.POINTER(C.c_int)), _p(xs),
+                                       side.ctypes.data_as(C.POINTER(C.c_byte))))
+    return dict(side=side, count=int(n))
 
 
 def _solve_structs(ns, n, na, lam, mode, prior_ivar, prior_dx, want_factor):
