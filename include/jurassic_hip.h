@@ -447,6 +447,58 @@ int  jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double c
 int  jur_avk_summary(ctl_t const *ctl, atm_t const *atm, int first, int len, double const *avk /* [w][w] */,
                      double *dofs_q /* [2 + ng + nw] */, double *area /* [w] */, double *resolution /* [w] */);
 
+/* Gain matrix and per-source error budget of the slices, on the device (upstream's matrix_gain.tab, atm_err_noise.tab and
+ * atm_err_formod.tab).  G = S K^T Se^-1 maps a perturbation of the measurements into the state: dx = G dy.
+ * Measurements and weights.  The measurements (r, id) of slice s (width w) are those of the rays with sid[r] == s, in
+ *   ascending ray order and within a ray in ascending channel order.  The effective weight omega of a measurement is
+ *   weight[r][id] where the measurement is live and 0 otherwise; live is jur_normal_scene_host's rule (input radiance --
+ *   with a field of view the effective mask --, F and y finite, weight > 0, and the ray has a slice).
+ * S_s is the posterior covariance of jur_diagnose_scene_host in every configuration (with the model's full prior
+ *   precision where one is set).  Element j is dead when S_jj is not > 0 (NaN included).
+ * The gain.  G_s[i][(r, id)] = omega * c, c the chain over j = 0 .. w - 1 ascending from +0.0 of fma(S_ij, K_r[id][j], c).
+ *   A dead j is skipped: its block entry is never multiplied, so a NaN there goes nowhere.  A dead i gives +0.0.  A
+ *   measurement that is not live gives a row of +0.0 and its block row is never read (a masked channel holds NaN there).
+ *   A system whose diagnostics broke down (status != 0) gives +0.0 throughout.
+ * Layout.  The gain block of ray r lies at gain + rowptr[r] * nd as [nd][width]: where and how jur_kernel_scene_host puts
+ *   K_r, so G is stored measurement-major like the blocks (entry (id, i) of the block is G_s[i][(r, id)]).
+ * Budget.  For component c < ncomp with variances var[c][r][id]:
+ *   sigma_comp[c][wptr[s] + i] = sqrt(q), q the chain over the live measurements of s, ascending, from +0.0 of
+ *   fma(g * g, var, q), g = G_s[i][(r, id)], g * g rounded first.  var is read on live measurements only; a value there
+ *   that is negative or not finite is JUR_EINVAL naming component, ray and channel, before anything is launched (the
+ *   scene entry decides this before the forward model has run: from the input mask, y, the weight and the slice).
+ *   ncomp is 0 to 8; 0 means the gain only.  out->gain is optional, out->sigma_comp required when ncomp > 0.
+ * Every double depends on its own slice's inputs and on w alone: not on the other slices, their order,
+ *   max_rays_per_pass or the entry called.  No atomics; every chain is fixed by the slice.
+ * jur_gain_slices_host: systems and blocks the caller holds, under the contract of jur_diagnose_slices_host (the model
+ *   supplies device and stream; its atmosphere and workspace are not touched).  S as jur_diagnose_slices_host lays it out,
+ *   status its breakdowns or NULL (all 0), k and rowptr as jur_kernel_scene_host's, sid[r] the slice of ray r (-1: none;
+ *   the width of a ray must be that of its slice), weight_eff omega directly: anything not > 0 is "not live".  nslice == 0
+ *   or nr == 0 is JUR_OK and writes nothing.
+ * jur_gain_scene_host: jur_diagnose_scene_host -- rad, tau, tp, np_out, A, b, cost, nlive, k and every field of diag are
+ *   that entry's bit for bit, and its refusals are the same -- with the blocks of all rays kept in the device slab (with a
+ *   field of view the convolved ones), the effective weights formed on the device, and the two kernels run once S exists.
+ *   The gain is written to an array of its own beside the retained blocks, never over them: k and gain may both be asked
+ *   for.  Only what was asked for is copied home.  JUR_ENOMEM before anything is launched when the retained blocks, the
+ *   gain and the budget's arrays do not fit beside everything else in half the workspace budget.  The model holds atm
+ *   afterwards, after an error too; the kernels' time counts into jur_model_last_scene_ms.
+ * jur_error_components (host arithmetic, no GPU; upstream's set_cov_meas): var[0][r][id] = err_noise[id]^2, var[1][r][id]
+ *   = (err_formod[id] / 100 * y[r][id])^2, weight = 1 / (their sum) where that sum is finite and > 0; otherwise weight = 0
+ *   and both variances +0.0 (a y that is not finite among them).  JUR_EINVAL for a negative or non-finite err_*. */
+typedef struct { int ncomp; double const *var; /* [ncomp][nr][nd] */ } jur_gain_in_t;
+typedef struct {
+  double *gain;                 /* optional, [rowptr[nr] * nd], laid out as the blocks */
+  double *sigma_comp;           /* [ncomp][wptr[nslice]], required when ncomp > 0 */
+} jur_gain_out_t;
+int  jur_gain_slices_host(jur_model_t *m, long nslice, long const *wptr, double const *S, int const *status /* or NULL */,
+                          long nr, int nd, long const *rowptr, int const *sid, double const *k, double const *weight_eff,
+                          jur_gain_in_t const *in, jur_gain_out_t const *out);
+int  jur_gain_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                         double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                         double const *prior_ivar, jur_diag_out_t const *diag, jur_gain_in_t const *in, jur_gain_out_t const *out,
+                         double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass);
+int  jur_error_components(int nd, long nr, double const *y, double const *err_noise /* [nd] */, double const *err_formod /* [nd], per cent */,
+                          double *var /* [2][nr][nd]: noise, formod */, double *weight /* [nr][nd] */);
+
 /* Curtis-Godson means along each line of sight (reference curtis_godson(), jr_common.h:455-473, which
  * upstream compiles only with -DCURTIS_GODSON for FORMOD=1): per ray, emitter and LOS point the
  * column-weighted pressure cgp, temperature cgt and the cumulative column cgu.  Host arrays

@@ -277,6 +277,43 @@ int jur_diag_check_out(char const *who, jur_diag_out_t const *out);
 int jur_diag_check_wptr(char const *who, long nslice, long const *wptr);
 int jur_diag_check_prior(char const *who, long nslice, long const *wptr, double const *prior_ivar);
 long jur_diag_maps(long nslice, long const *wptr, int *imap, int *tmap, long *ntile);
+/* Gain matrix and error budget of a scene (jur_gain_slices_host, jur_gain_scene_host), after the diagnostics have left
+ * S_s and the breakdowns on the device.  Measurement m of slice s is channel m % nd of ray srays[sptr[s] + m / nd]; its
+ * block row lies at k + koff[ray] + channel * w_s and its gain row at the same place in `gain`.  All arrays are device
+ * memory. */
+typedef struct {
+  long nslice;
+  int nd, ncomp;
+  long const *wptr, *aptr;      /* [nslice + 1] running sums of w_s and of w_s^2                             */
+  long const *sptr;             /* [nslice + 1] rays of every slice in srays                                */
+  int const *srays;             /* the rays of every slice, ascending                                       */
+  long const *koff;             /* [nr] first double of the block of every ray of the call                  */
+  long const *gptr;             /* [nslice + 1] running sum of ceil(w_s / 256): the budget's workgroups      */
+  int const *gmap;              /* [ntile][3] gain tile -> (slice, first measurement, first element), 64 x 64 */
+  int const *status;            /* [nslice] or NULL: a system whose status is not 0 is all +0.0              */
+  double const *S;              /* [aptr[nslice]] posterior covariances                                     */
+  double const *k;              /* the blocks                                                               */
+  double const *weff;           /* [nr][nd] effective weights: anything not > 0 is "not live"                */
+  double const *var;            /* [ncomp][nrd] variances per component                                     */
+  long nrd, nb;                 /* nr * nd; wptr[nslice]                                                     */
+  double *gain;                 /* laid out as k, written                                                   */
+  double *sigc;                 /* [ncomp][nb] written                                                      */
+} jur_scene_gain_t;
+/* the gain, then (ncomp > 0) the budget, in stream order */
+int jurk_scene_gain(jur_scene_gain_t const *a, long ntile, long ngroups, void *stream);
+/* weff = weight where mask, f and y are finite and weight > 0, else 0; n values each */
+typedef struct { long n; double const *mask, *f, *y, *weight; double *weff; } jur_scene_weff_t;
+int jurk_scene_weff(jur_scene_weff_t const *a, void *stream);
+enum { JUR_GAIN_TILE = 64, JUR_GAIN_MAXCOMP = 8 };
+/* host arithmetic of the gain entries (jur_scene.c; no GPU): the refusals and the tile map.  jur_gain_check_layout: sid in
+ * -1 .. nslice - 1 and the width of every ray that of its slice (0 without one).  jur_gain_check_var: every variance of a
+ * measurement with live[r * nd + id] != 0 is >= 0 and finite.  jur_gain_maps: tile t of the product is the measurements
+ * [m0, m0 + 64) x the elements [i0, i0 + 64) of slice s, gmap[3 t] = s, then m0, i0, slices ascending, row-major within
+ * a slice; gmap may be NULL (a first call counts); returns the number of tiles, -1 for a slice with 2^31 measurements. */
+int jur_gain_check_args(char const *who, jur_gain_in_t const *in, jur_gain_out_t const *out);
+int jur_gain_check_layout(char const *who, long nslice, long const *wptr, long nr, long const *rowptr, int const *sid);
+int jur_gain_check_var(char const *who, int ncomp, long nr, int nd, double const *var, unsigned char const *live);
+long jur_gain_maps(long nslice, long const *wptr, long const *sptr, int nd, int *gmap);
 /* host checks of the full prior precision (jur_scene.c; no GPU): what is read of R, the layout of a call against the one
  * set, the arguments of jur_prior_corr_host */
 int jur_prior_check_R(char const *who, long nslice, long const *wptr, double const *R);

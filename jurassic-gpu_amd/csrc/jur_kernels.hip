@@ -32,6 +32,8 @@
 //   jur_scene_fov_kernel  the same convolution on the replicated rays of a pass of the scene entries, a workgroup per ray.
 //   jur_scene_hydro_kernel  hydrostatic balance of the slices of a scene, one wavefront per segment (jur_model_set_scene_hydz).
 //   jur_scene_gradient_kernel  b, cost and nlive of a scene's slices from held blocks, a lane per state element (jur_gradient_scene_host).
+//   jur_scene_gain_kernel  gain matrix G = S K^T W of a scene's slices over the ragged blocks, a workgroup per 64 x 64 tile;
+//   jur_scene_budget_kernel  the row sums of G^2 var per error source, a lane per state element (jur_gain_scene_host).
 //   jur_intpol_kernel     regridding of a track / point-cloud atmosphere (intpol_atm, jurassic.c:675-804).
 //   jur_kat_*_kernel      known-answer hooks for tests: the device functions on arrays of inputs.
 //
@@ -3224,6 +3226,144 @@ __global__ __launch_bounds__(256) void jur_scene_dofs_kernel(jur_scene_diag_t a)
   if (tid == 0) a.dofs[s] = red[0];
 }
 
+// ---- gain matrix and error budget of a scene (jur_gain_slices_host, jur_gain_scene_host) ----------------------------
+// The effective weights of a scene: the weight where the measurement is live by jur_scene_normal_kernel's rule (mask: the
+// caller's radiances, with a field of view the effective mask), 0 otherwise.  One lane per measurement.
+__global__ __launch_bounds__(256) void jur_scene_weff_kernel(jur_scene_weff_t a) {
+  long const g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= a.n) return;
+  double const wt = a.weight[g];
+  a.weff[g] = (isfinite(a.mask[g]) && isfinite(a.f[g]) && isfinite(a.y[g]) && wt > 0) ? wt : 0.;
+}
+
+// G = S K^T W, a ragged batched product.  One workgroup per tile of 64 measurements x 64 state elements of one slice
+// (gmap: slice, first measurement, first element).  Measurement m of the slice is channel m % nd of its ray m / nd, the
+// rays ascending (srays, sptr); its block row starts at k + koff[ray] + channel * w, and its gain row at the same place in
+// `gain`.  Lane (tr, tc) holds the 4 x 4 micro-tile of the measurements m0 + tr + 16 p and the elements i0 + tc + 16 q and
+// carries each as one chain c = fma(S_ij, K_m[j], c) over j = 0 .. w - 1, ascending (padded with exact zeros to a multiple
+// of 16), the operands staged through LDS 16 values of j at a time: SI the tile's rows of S, KM the tile's block rows.  A
+// dead j (S_jj not > 0) is staged as zeros on both sides and a measurement that is not live (omega not > 0) as a row of
+// zeros: their block entries are never read.  Rows of measurements that are not live, columns of dead elements and a
+// system that broke down are written as +0.0; everything else as omega * c.  LDS: 18 KB, two barriers per 16 values of j.
+#define GAIN_TILE 64
+#define GAIN_NB 16
+__global__ __launch_bounds__(256) void jur_scene_gain_kernel(jur_scene_gain_t a) {
+  __shared__ double SI[GAIN_NB][GAIN_TILE + 1], KM[GAIN_NB][GAIN_TILE + 1];
+  __shared__ double om[GAIN_TILE], dj[GAIN_NB];
+  __shared__ long row[GAIN_TILE];
+  long const s = a.gmap[3 * (long)blockIdx.x];
+  int const m0 = a.gmap[3 * (long)blockIdx.x + 1], i0 = a.gmap[3 * (long)blockIdx.x + 2];
+  int const tid = threadIdx.x, tr = tid >> 4, tc = tid & 15, w = (int)(a.wptr[s + 1] - a.wptr[s]), nd = a.nd;
+  double const *const S = a.S + a.aptr[s];
+  long const q0 = a.sptr[s], M = (a.sptr[s + 1] - q0) * nd;
+  bool const bad = a.status && a.status[s] != 0;            // (uniform)
+  if (tid < GAIN_TILE) {
+    long const mm = (long)m0 + tid;
+    long at = -1;
+    double ww = 0.;
+    if (mm < M) {
+      long const q = mm / nd;
+      int const id = (int)(mm - q * nd);
+      long const r = a.srays[q0 + q];
+      double const wt = a.weff[r * nd + id];
+      at = a.koff[r] + (long)id * w;
+      if (wt > 0) ww = wt;
+    }
+    row[tid] = at; om[tid] = ww;
+  }
+  double acc[4][4];
+#pragma unroll
+  for (int p = 0; p < 4; p++)
+#pragma unroll
+    for (int q = 0; q < 4; q++) acc[p][q] = 0.;
+  for (int j0 = 0; j0 < w && !bad; j0 += GAIN_NB) {
+    if (tid < GAIN_NB) { int const j = j0 + tid; dj[tid] = j < w ? S[(long)j * w + j] : 0.; }
+    __syncthreads();                                        // (also: the micro-tiles of the last 16 have been taken)
+    for (int e = tid; e < GAIN_NB * GAIN_TILE; e += 256) {
+      int const rr = e >> 4, jj = e & 15, i = i0 + rr, j = j0 + jj;
+      SI[jj][rr] = (i < w && dj[jj] > 0) ? S[(long)i * w + j] : 0.;
+      KM[jj][rr] = (om[rr] > 0 && dj[jj] > 0) ? a.k[row[rr] + j] : 0.;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < GAIN_NB; j++) {
+      double km[4], si[4];
+#pragma unroll
+      for (int p = 0; p < 4; p++) { km[p] = KM[j][tr + 16 * p]; si[p] = SI[j][tc + 16 * p]; }
+#pragma unroll
+      for (int p = 0; p < 4; p++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[p][q] = fma(si[q], km[p], acc[p][q]);
+    }
+  }
+  if (bad || w <= 0) __syncthreads();                       // (row and om are read below; the loop's barriers did not run)
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+    int const ml = tr + 16 * p;
+    long const at = row[ml];
+    if (at < 0) continue;
+    double const ww = om[ml];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      int const i = i0 + tc + 16 * q;
+      if (i < w) a.gain[at + i] = (bad || !(ww > 0) || !(S[(long)i * w + i] > 0)) ? 0. : ww * acc[p][q];
+    }
+  }
+}
+
+// The error budget: sigma_comp[c][e] = sqrt(sum over the live measurements m of the slice, ascending, of G_em^2 var_c[m]).
+// One workgroup per 256 consecutive state elements of one slice (gptr, as jur_scene_gradient_kernel); lane i owns element
+// 256 g + i and up to 8 chains q_c = fma(g * g, var_c, q_c), g * g rounded first.  The measurements are taken GRAD_CH at a
+// time: the first double of the gain row (-1: not live, the measurement is skipped by all lanes and its variances are
+// never read) and the ncomp variances are staged in one of two LDS buffers, one barrier per group; what is staged does
+// not grow with the slice.  The lanes then read entry e of each live gain row: one coalesced stretch per row.
+__global__ __launch_bounds__(256) void jur_scene_budget_kernel(jur_scene_gain_t a) {
+  __shared__ double vl[2][8][GRAD_CH];
+  __shared__ long kl[2][GRAD_CH];
+  long const s = scene_find<false>(a.gptr, 0, a.nslice, (long)blockIdx.x);
+  int const w = (int)(a.wptr[s + 1] - a.wptr[s]), nd = a.nd, ncomp = a.ncomp;
+  long const grp = (long)blockIdx.x - a.gptr[s];
+  int const lane = threadIdx.x, i = (int)(grp * 256) + lane;
+  bool const inside = i < w;
+  long const q0 = a.sptr[s], M = (a.sptr[s + 1] - q0) * nd;
+  double q[8];
+#pragma unroll
+  for (int c = 0; c < 8; c++) q[c] = 0.;
+  for (long m0 = 0; m0 < M; m0 += GRAD_CH) {
+    int const buf = (int)(m0 / GRAD_CH) & 1;
+    for (int e = lane; e < GRAD_CH * ncomp; e += 256) {
+      int const c = e / GRAD_CH, ml = e % GRAD_CH;
+      long const mm = m0 + ml;
+      long at_k = -1;
+      double v = 0.;
+      if (mm < M) {
+        long const qq = mm / nd;
+        int const id = (int)(mm - qq * nd);
+        long const r = a.srays[q0 + qq], at = r * nd + id;
+        if (a.weff[at] > 0) {
+          at_k = a.koff[r] + (long)id * w;
+          v = a.var[(long)c * a.nrd + at];
+        }
+      }
+      vl[buf][c][ml] = v;
+      if (c == 0) kl[buf][ml] = at_k;
+    }
+    __syncthreads();
+    int const nc = M - m0 < GRAD_CH ? (int)(M - m0) : GRAD_CH;
+    for (int m = 0; m < nc; m++) {
+      long const at = kl[buf][m];
+      if (at < 0) continue;                                 // (uniform)
+      double const g = inside ? a.gain[at + i] : 0., gg = g * g;
+#pragma unroll
+      for (int c = 0; c < 8; c++)
+        if (c < ncomp) q[c] = fma(gg, vl[buf][c][m], q[c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 8; c++)
+    if (c < ncomp && inside) a.sigc[(long)c * a.nb + a.wptr[s] + i] = sqrt(q[c]);
+}
+
 // ---- trial states of a scene (jur_trial_scene_host, jur_retrieve_scene_host) -----------------------------------------
 // One lane per state element e of slice s (JUR_ELEM_APPLY: per trial t and element).  The value of element e is
 // base[erow[e]][eip[e]]; its place in trial copy 1 + s * ntrial + t is the same row at off[copy] + (eip[e] - sfirst[s]).
@@ -3576,6 +3716,20 @@ extern "C" int jurk_scene_diag(jur_scene_diag_t const *a, long ninv, long ntile,
   if (ntile > 0) hipLaunchKernelGGL(jur_scene_avk_kernel, dim3((unsigned)ntile), dim3(256), 0, s, *a);
   if (nb > 0) hipLaunchKernelGGL(jur_scene_diag_rows_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, *a);
   hipLaunchKernelGGL(jur_scene_dofs_kernel, dim3((unsigned)a->nslice), dim3(256), 0, s, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_weff(jur_scene_weff_t const *a, void *stream) {
+  if (a->n <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_weff_kernel, dim3(scene_grid(a->n)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+// (the tile and workgroup counts are the host's: jur_gain_maps and gptr[nslice]; the budget only with components)
+extern "C" int jurk_scene_gain(jur_scene_gain_t const *a, long ntile, long ngroups, void *stream) {
+  hipStream_t const s = (hipStream_t)stream;
+  if (ntile > 0) hipLaunchKernelGGL(jur_scene_gain_kernel, dim3((unsigned)ntile), dim3(256), 0, s, *a);
+  if (a->ncomp > 0 && ngroups > 0) hipLaunchKernelGGL(jur_scene_budget_kernel, dim3((unsigned)ngroups), dim3(256), 0, s, *a);
   return (int)hipGetLastError();
 }
 

@@ -2187,7 +2187,8 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
 
 /* ---- posterior diagnostics of the slices (jur_diagnose_slices_host, jur_diagnose_scene_host) ------------------------ */
 /* what jur_diagnose_scene_host adds to jur_normal_scene_host */
-typedef struct { double const *prior_ivar; jur_diag_out_t const *out; } scene_diag_t;
+/* ... and what jur_gain_scene_host adds to that (gin == NULL: the diagnostics alone) */
+typedef struct { double const *prior_ivar; jur_diag_out_t const *out; jur_gain_in_t const *gin; jur_gain_out_t const *gout; } scene_diag_t;
 
 /* The diagnostics' part of the slab beside A, as offsets in doubles from its start: L | S | K (the AVK), then live | z |
  * zero (the solve's b and prior_dx) | r (prior_ivar, empty without a prior), vec (the four vectors), lam (zeros) | pred |
@@ -2280,6 +2281,57 @@ static int diag_maps_make(char const *who, long nslice, long const *wptr, long *
   *hmap = (int *)malloc(sizeof(int) * (2 * (size_t)*ninv + 3 * (size_t)*ntile));
   if (!*hmap) { jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
   (void)jur_diag_maps(nslice, wptr, *hmap, *hmap + 2 * *ninv, NULL);
+  return JUR_OK;
+}
+
+/* ---- gain matrix and error budget of the slices (jur_gain_slices_host, jur_gain_scene_host) --------------------------- */
+/* The gain's part of the slab, as offsets in doubles from its start: gain (nk doubles, laid out as the blocks: never the
+ * blocks themselves, which the tiles of other elements still read) | sigc [ncomp][nb] | var [ncomp][nrd] | weff [nrd] |
+ * map (the ints of the tile map [3 ntile], rounded up to doubles).  end: the doubles of the part. */
+typedef struct { size_t gain, sigc, var, weff, map, end; } gain_layout_t;
+
+static gain_layout_t gain_layout(size_t nk, size_t nb, size_t nrd, size_t ncomp, size_t ntile) {
+  gain_layout_t o;
+  o.gain = 0; o.sigc = o.gain + nk; o.var = o.sigc + ncomp * nb; o.weff = o.var + ncomp * nrd; o.map = o.weff + nrd;
+  o.end = o.map + (3 * ntile + 1) / 2;
+  return o;
+}
+
+/* the tile map of the gain kernel in one malloc'ed array (NULL with JUR_OK where there is no tile) */
+static int gain_maps_make(char const *who, long nslice, long const *wptr, long const *sptr, int nd, long *ntile, int **hmap) {
+  *hmap = NULL;
+  *ntile = jur_gain_maps(nslice, wptr, sptr, nd, NULL);
+  if (*ntile < 0 || *ntile > 0x7fffffffL) {
+    jur_set_error("%s: 2^31 gain tiles or measurements of one slice: call with the rays of fewer slices at a time", who);
+    return JUR_EINVAL;
+  }
+  if (*ntile == 0) return JUR_OK;
+  *hmap = (int *)malloc(sizeof(int) * 3 * (size_t)*ntile);
+  if (!*hmap) { jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
+  (void)jur_gain_maps(nslice, wptr, sptr, nd, *hmap);
+  return JUR_OK;
+}
+
+/* Enqueues on s: the uploads of the variances and the tile map, the gain and budget kernels, the copies home of what was
+ * asked for.  q comes with everything but weff, var, gmap, gain and sigc, which lie in the part W of the slab (weff
+ * filled by the caller); nk: the doubles of all blocks.  The caller waits for the stream before the host arrays go. */
+static int gain_enqueue(jur_model_t *m, hipStream_t s, char const *who, jur_scene_gain_t *q, double *W, size_t nk, long ntile,
+                        long ngroups, int const *hmap, jur_gain_in_t const *in, jur_gain_out_t const *out) {
+  size_t const NB = (size_t)q->nb, NRD = (size_t)q->nrd, NC = (size_t)in->ncomp;
+  gain_layout_t const o = gain_layout(nk, NB, NRD, NC, (size_t)ntile);
+  hipError_t e = hipSuccess;
+  if (NC && NRD) e = hipMemcpyAsync(W + o.var, in->var, sizeof(double) * NC * NRD, hipMemcpyHostToDevice, s);
+  if (ntile > 0 && e == hipSuccess) e = hipMemcpyAsync(W + o.map, hmap, sizeof(int) * 3 * (size_t)ntile, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
+  q->ncomp = in->ncomp;
+  q->weff = W + o.weff; q->var = W + o.var; q->gmap = (int const *)(W + o.map); q->gain = W + o.gain; q->sigc = W + o.sigc;
+  int const ti = scene_timed_begin(m, s);
+  int const ek = jurk_scene_gain(q, ntile, ngroups, s);
+  scene_timed_end(m, ti, s);
+  if (ek) { jur_set_error("%s: gain kernel launch failed", who); return JUR_EHIP; }
+  if (nk && out->gain) e = hipMemcpyAsync(out->gain, q->gain, sizeof(double) * nk, hipMemcpyDeviceToHost, s);
+  if (NC && NB && e == hipSuccess) e = hipMemcpyAsync(out->sigma_comp, q->sigc, sizeof(double) * NC * NB, hipMemcpyDeviceToHost, s);
+  if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
   return JUR_OK;
 }
 
@@ -2574,11 +2626,13 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
                              double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
                              scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt, scene_diag_t const *dg,
                              scene_grad_t const *gd) {
-  char const *const who = gd ? "jur_gradient_scene_host" : rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+  char const *const who = gd ? "jur_gradient_scene_host" : rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : (dg && dg->gin) ? "jur_gain_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
   if (rt) { int const rs = retrieve_check_args(who, rt->in, rt->out); if (rs) return rs; }
   if (dg) { int const rs = jur_diag_check_out(who, dg->out); if (rs) return rs; }
+  int const gn = dg && dg->gin;                     /* jur_gain_scene_host: the blocks are held, the gain follows the diagnostics */
+  if (gn) { int const rs = jur_gain_check_args(who, dg->gin, dg->gout); if (rs) return rs; }
   ctl_t const *ctl = m->ctl;
   int rc = scene_atm_check(m, who, "every p, T or H2O element moves every pressure and the Jacobian has no blocks: use jur_kernel", atm);
   if (rc) return rc;
@@ -2593,8 +2647,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   long *off = NULL, *pass = NULL, *scopy = NULL, *nptr = NULL;
   int *cdesc = NULL, *iqa = NULL, *ipa = NULL, *srays = NULL;
   double *rd = NULL, *htimec = NULL, *hbd = NULL;   /* (hbd: the box on the state per element, lo | hi) */
-  int *ri = NULL, *hact = NULL, *dmap = NULL;
-  long *hcomp = NULL, ninv = 0, ndtile = 0;
+  int *ri = NULL, *hact = NULL, *dmap = NULL, *gmap = NULL;
+  long *hcomp = NULL, ninv = 0, ndtile = 0, ngtile = 0;
   long *hkoff = NULL;                               /* held blocks: the first double of every ray's | the gradient's workgroups by slice */
   int *hjac = NULL;                                 /* ... and the states of the slices at the last Jacobian iteration */
   atm_t *ret_atm = NULL;
@@ -2666,6 +2720,20 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (sv && !rt && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
     if (dg && (rc = jur_diag_check_prior(who, nslice, wptr, dg->prior_ivar))) goto done;
     if (dg && (rc = diag_maps_make(who, nslice, wptr, &ninv, &ndtile, &dmap))) goto done;
+    if (gn) {
+      /* the variances are read where a measurement can be live: the forward model has not run, F counts as finite */
+      if (dg->gin->ncomp > 0) {
+        unsigned char *hl = (unsigned char *)malloc(NR * (size_t)nd);
+        if (!hl) { rc = JUR_ENOMEM; goto done; }
+        double const *const mask = fov ? op.hlive : rad;
+        for (size_t at = 0; at < NR * (size_t)nd; at++)
+          hl[at] = sid[at / (size_t)nd] >= 0 && isfinite(mask[at]) && isfinite(nm->y[at]) && nm->weight[at] > 0;
+        rc = jur_gain_check_var(who, dg->gin->ncomp, nr, nd, dg->gin->var, hl);
+        free(hl);
+        if (rc) goto done;
+      }
+      if ((rc = gain_maps_make(who, nslice, wptr, sptr, nd, &ngtile, &gmap))) goto done;
+    }
     if (rt) {
       if (rt->in->prior_ivar && (rc = prior_check_values(who, nslice, wptr, rt->in->prior_ivar, rt->in->prior_xa))) goto done;
       /* one atmosphere is the state of all slices only where no point lies in two of them */
@@ -2769,11 +2837,19 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
    * them an all-zero rowptr (a forward-only pass has one slot per ray), the first double of every ray's block and the
    * workgroups of the gradient kernel by slice */
   int const every = looping ? m->kernel_recomp : 1;
-  int const retain = gd || every > 1;
+  int const held = gn && ntiles;                    /* (an entry with the gain has no loop: the blocks of its one Jacobian pass stay) */
+  int const retain = gd || every > 1 || held;
   size_t const nkret = retain ? (size_t)rp[nr] * (size_t)nd : 0;
   size_t const nrc = retain ? (NR + 1) + NR + (RS + 1) : 0;
-  size_t const kret_bytes = sizeof(double) * (nkret + nrc);
-  if (retain && !scene_fits(m, &used, kret_bytes)) {
+  size_t const ngn = held ? gain_layout(nkret, (size_t)nb, NRD, (size_t)dg->gin->ncomp, (size_t)ngtile).end : 0;
+  size_t const kret_bytes = sizeof(double) * (nkret + nrc + ngn);
+  if (held && !scene_fits(m, &used, kret_bytes)) {
+    jur_set_error("%s: the retained blocks of all rays (%ld columns, %zu bytes), the gain and the budget's arrays (%zu bytes) do not "
+                  "fit beside the stacked atmosphere (%zu bytes), the normal matrices and the diagnostics in the workspace budget: "
+                  "call with the rays of fewer slices at a time", who, rp[nr], sizeof(double) * (nkret + nrc), sizeof(double) * ngn, atm_bytes);
+    rc = JUR_ENOMEM; goto done;
+  }
+  if (retain && !held && !scene_fits(m, &used, kret_bytes)) {
     jur_set_error("%s: the blocks of all rays (%ld columns, %zu bytes) do not fit beside the stacked atmosphere (%zu bytes)%s in the "
                   "workspace budget: call with the rays of fewer slices at a time", who, rp[nr], kret_bytes, atm_bytes,
                   gd ? "" : ", the normal matrices and the loop's arrays");
@@ -2861,7 +2937,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
    * then sptr | tptr | wptr | aptr, then what the solve needs) */
   size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
                o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_dg = o_sv + nsv, o_fov = o_dg + ndg, o_rt = o_fov + nfov,
-               o_hy = o_rt + rt_dbl + rt_lng, o_rc = o_hy + NH, o_int = o_rc + nrc;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad; o_hy: the balance's first points) */
+               o_hy = o_rt + rt_dbl + rt_lng, o_rc = o_hy + NH, o_gn = o_rc + nrc, o_int = o_gn + ngn;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad; o_hy: the balance's first points) */
   size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int + NH;   /* (the loop's ints follow the others, the balance's lengths those) */
   hipStream_t s;
   if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * nint, &s))) goto done;
@@ -2908,7 +2984,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       for (long r = 0; r < nr; r++) hkoff[r] = rp[r] * nd;
       if (e == hipSuccess) e = hipMemsetAsync(d_zrp, 0, sizeof(long) * (NR + 1), s);
       if (e == hipSuccess) e = hipMemcpyAsync(d_gptr, hgptr, sizeof(long) * (RS + 1), hipMemcpyHostToDevice, s);
-      if (gd && e == hipSuccess) e = hipMemcpyAsync(d_koff, hkoff, sizeof(long) * NR, hipMemcpyHostToDevice, s);
+      if ((gd || held) && e == hipSuccess) e = hipMemcpyAsync(d_koff, hkoff, sizeof(long) * NR, hipMemcpyHostToDevice, s);
       if (gd && nkret && e == hipSuccess) e = hipMemcpyAsync(D + o_k, gd->k, sizeof(double) * nkret, hipMemcpyHostToDevice, s);
     }
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
@@ -3130,7 +3206,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       size_t const N = (size_t)n;
       a.r0 = r0; a.r1 = r1; a.n = n;
       a.rowptr = fwd ? d_zrp : d_rp_cur;
-      if (every > 1 && !fwd) a.k = D + o_k + (size_t)rp[r0] * (size_t)nd;   /* (the blocks stay where the pass leaves them) */
+      if ((every > 1 || held) && !fwd) a.k = D + o_k + (size_t)rp[r0] * (size_t)nd;   /* (the blocks stay where the pass leaves them) */
       a.geom = m->d_io; a.rad = a.geom + 7 * N; a.tau = a.rad + N * nd; a.tp = a.tau + N * nd; a.np = m->d_io_np;
       ti = scene_timed_begin(m, s);
       ek = jurk_scene_rays(&a, s);
@@ -3171,6 +3247,25 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out,
                                    looping ? d_state : NULL, d_R))) goto done;
     if (ndg && (rc = diag_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, D + o_dg, dg->prior_ivar, dg->out, ninv, ndtile, dmap, d_R))) goto done;
+    if (held) {
+      /* S and the breakdowns lie where the diagnostics left them, the blocks of all rays where the passes left them; the
+       * effective weights are formed from the results of the passes, under the mask the sums were formed under */
+      diag_layout_t const dl = diag_layout((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, d_R != NULL, (size_t)ninv, (size_t)ndtile);
+      gain_layout_t const gl = gain_layout(nkret, (size_t)nb, NRD, (size_t)dg->gin->ncomp, (size_t)ngtile);
+      jur_scene_weff_t wq;
+      wq.n = (long)NRD; wq.mask = fov ? d_live : D + o_inrad; wq.f = D + o_rad; wq.y = D + o_y; wq.weight = D + o_w;
+      wq.weff = D + o_gn + gl.weff;
+      ti = scene_timed_begin(m, s);
+      ek = jurk_scene_weff(&wq, s);
+      scene_timed_end(m, ti, s);
+      if (ek) { jur_set_error("%s: effective-weight kernel launch failed", who); rc = JUR_EHIP; goto done; }
+      jur_scene_gain_t gq2;
+      memset(&gq2, 0, sizeof gq2);
+      gq2.nslice = nslice; gq2.nd = nd; gq2.wptr = nq.wptr; gq2.aptr = nq.aptr; gq2.sptr = nq.sptr; gq2.srays = nq.srays;
+      gq2.koff = d_koff; gq2.gptr = d_gptr; gq2.status = (int const *)(D + o_dg + dl.stat); gq2.S = D + o_dg + dl.S; gq2.k = D + o_k;
+      gq2.nrd = (long)NRD; gq2.nb = nb;
+      if ((rc = gain_enqueue(m, s, who, &gq2, D + o_gn, nkret, ngtile, ngroups, gmap, dg->gin, dg->gout))) goto done;
+    }
     if (!looping) break;
 
     /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
@@ -3292,7 +3387,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
   free(srays); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa); free(rd); free(ri); free(hact); free(hcomp);
-  free(ret_atm); free(dmap); free(htimec); free(hyat); free(hkoff); free(hjac); free(hbd);
+  free(ret_atm); free(dmap); free(gmap); free(htimec); free(hyat); free(hkoff); free(hjac); free(hbd);
   scene_open_free(&op);
   trial_plan_free(&pl);
   return rc;
@@ -3349,7 +3444,17 @@ int jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double co
                             double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_diagnose_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
-  scene_diag_t const dg = {prior_ivar, out};
+  scene_diag_t const dg = {prior_ivar, out, NULL, NULL};
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL));
+}
+
+int jur_gain_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                        double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                        double const *prior_ivar, jur_diag_out_t const *diag, jur_gain_in_t const *in, jur_gain_out_t const *out,
+                        double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
+  if (!m || !atm || !in || !out) { jur_set_error("jur_gain_scene_host: null argument"); return JUR_EINVAL; }
+  scene_normal_t const nm = {y, weight, A, b, cost, nlive};
+  scene_diag_t const dg = {prior_ivar, diag, in, out};
   return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL));
 }
 
@@ -3701,6 +3806,75 @@ int jur_diagnose_slices_host(jur_model_t *m, long nslice, long const *wptr, doub
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
   free(ptr); free(hmap);
+  return rc;
+}
+
+/* Systems and blocks the caller holds: wptr | aptr | sptr | gptr | koff, S, k, then the gain's part of the slab, then the
+ * ints status | srays. */
+int jur_gain_slices_host(jur_model_t *m, long nslice, long const *wptr, double const *S, int const *status, long nr, int nd,
+                         long const *rowptr, int const *sid, double const *k, double const *weight_eff,
+                         jur_gain_in_t const *in, jur_gain_out_t const *out) {
+  char const *const who = "jur_gain_slices_host";
+  if (!m || nslice < 0 || nr < 0 || nd < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  int rc = jur_gain_check_args(who, in, out);
+  if (rc) return rc;
+  if (nslice == 0 || nr == 0) return JUR_OK;
+  if (nslice > 0x7fffffffL || nr > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 systems and rays per call", who); return JUR_EINVAL; }
+  if (!wptr || !rowptr || !sid) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if ((rc = jur_diag_check_wptr(who, nslice, wptr))) return rc;
+  if ((rc = jur_gain_check_layout(who, nslice, wptr, nr, rowptr, sid))) return rc;
+  size_t const NS = (size_t)nslice, NR = (size_t)nr, NRD = NR * (size_t)nd, nk = (size_t)rowptr[nr] * (size_t)nd;
+  if ((wptr[nslice] > 0 && !S) || (nk > 0 && !k) || (NRD > 0 && !weight_eff)) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  long *ptr = (long *)malloc(sizeof(long) * (4 * (NS + 1) + NR));
+  int *srays = (int *)malloc(sizeof(int) * NR), *hmap = NULL;
+  unsigned char *hl = (unsigned char *)malloc(NRD ? NRD : 1);
+  int enqueued = 0;
+  if (!ptr || !srays || !hl) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+  {
+    long *const aptr = ptr + NS + 1, *const sptr = aptr + NS + 1, *const gptr = sptr + NS + 1, *const koff = gptr + NS + 1;
+    long ntile = 0;
+    memcpy(ptr, wptr, sizeof(long) * (NS + 1));
+    aptr[0] = 0; gptr[0] = 0;
+    for (long q = 0; q < nslice; q++) {
+      long const w = wptr[q + 1] - wptr[q];
+      aptr[q + 1] = aptr[q] + w * w;
+      gptr[q + 1] = gptr[q] + (w + 255) / 256;
+    }
+    for (long r = 0; r < nr; r++) koff[r] = rowptr[r] * nd;
+    long const nlist = jur_scene_rays_by_slice(nr, nslice, sid, sptr, srays);
+    for (size_t at = 0; at < NRD; at++) hl[at] = sid[at / (size_t)nd] >= 0 && weight_eff[at] > 0;
+    if (in->ncomp > 0 && (rc = jur_gain_check_var(who, in->ncomp, nr, nd, in->var, hl))) goto done;
+    if ((rc = gain_maps_make(who, nslice, wptr, sptr, nd, &ntile, &hmap))) goto done;
+    long const na = aptr[nslice], nb = wptr[nslice], ngroups = gptr[nslice];
+    if (ngroups > 0x7fffffffL) { jur_set_error("%s: 2^31 workgroups: call with fewer systems at a time", who); rc = JUR_EINVAL; goto done; }
+    size_t const nlong = 4 * (NS + 1) + NR, o_S = nlong, o_k = o_S + (size_t)na, o_gn = o_k + nk;
+    gain_layout_t const gl = gain_layout(nk, (size_t)nb, NRD, (size_t)in->ncomp, (size_t)ntile);
+    size_t const o_int = o_gn + gl.end;
+    hipStream_t s;
+    if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * (NS + (size_t)nlist + 1), &s))) goto done;
+    double *const D = (double *)m->d_scene;
+    long *const L = (long *)m->d_scene;
+    int *const d_stat = (int *)(D + o_int), *const d_srays = d_stat + NS;
+    enqueued = 1;
+    hipError_t e = hipMemcpyAsync(L, ptr, sizeof(long) * nlong, hipMemcpyHostToDevice, s);
+    if (na && e == hipSuccess) e = hipMemcpyAsync(D + o_S, S, sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s);
+    if (nk && e == hipSuccess) e = hipMemcpyAsync(D + o_k, k, sizeof(double) * nk, hipMemcpyHostToDevice, s);
+    if (NRD && e == hipSuccess) e = hipMemcpyAsync(D + o_gn + gl.weff, weight_eff, sizeof(double) * NRD, hipMemcpyHostToDevice, s);
+    if (status && e == hipSuccess) e = hipMemcpyAsync(d_stat, status, sizeof(int) * NS, hipMemcpyHostToDevice, s);
+    if (nlist && e == hipSuccess) e = hipMemcpyAsync(d_srays, srays, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    jur_scene_gain_t q;
+    memset(&q, 0, sizeof q);
+    q.nslice = nslice; q.nd = nd; q.wptr = L; q.aptr = L + (NS + 1); q.sptr = L + 2 * (NS + 1); q.gptr = L + 3 * (NS + 1);
+    q.koff = L + 4 * (NS + 1); q.srays = d_srays; q.status = status ? d_stat : NULL; q.S = D + o_S; q.k = D + o_k;
+    q.nrd = (long)NRD; q.nb = nb;
+    if ((rc = gain_enqueue(m, s, who, &q, D + o_gn, nk, ntile, ngroups, hmap, in, out))) goto done;
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
+  }
+done:
+  if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
+  free(ptr); free(srays); free(hmap); free(hl);
   return rc;
 }
 

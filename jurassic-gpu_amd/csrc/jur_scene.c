@@ -520,6 +520,93 @@ long jur_diag_maps(long nslice, long const *wptr, int *imap, int *tmap, long *nt
   return ninv;
 }
 
+/* ---- gain matrix and error budget (jur_gain_slices_host, jur_gain_scene_host): the host arithmetic ------------------- */
+int jur_gain_check_args(char const *who, jur_gain_in_t const *in, jur_gain_out_t const *out) {
+  if (!in || !out) { jur_set_error("%s: null argument (%s)", who, !in ? "in" : "out"); return JUR_EINVAL; }
+  if (in->ncomp < 0 || in->ncomp > JUR_GAIN_MAXCOMP) {
+    jur_set_error("%s: ncomp = %d: 0 to %d components per call", who, in->ncomp, JUR_GAIN_MAXCOMP);
+    return JUR_EINVAL;
+  }
+  if (in->ncomp > 0 && !out->sigma_comp) { jur_set_error("%s: null argument (sigma_comp) with ncomp = %d", who, in->ncomp); return JUR_EINVAL; }
+  if (in->ncomp > 0 && !in->var) { jur_set_error("%s: null argument (var) with ncomp = %d", who, in->ncomp); return JUR_EINVAL; }
+  return JUR_OK;
+}
+
+int jur_gain_check_layout(char const *who, long nslice, long const *wptr, long nr, long const *rowptr, int const *sid) {
+  if (rowptr[0] != 0) { jur_set_error("%s: rowptr does not start at 0", who); return JUR_EINVAL; }
+  for (long r = 0; r < nr; r++) {
+    if (sid[r] < -1 || sid[r] >= nslice) {
+      jur_set_error("%s: sid of ray %ld is %d: outside -1..%ld", who, r, sid[r], nslice - 1);
+      return JUR_EINVAL;
+    }
+    long const w = sid[r] < 0 ? 0 : wptr[sid[r] + 1] - wptr[sid[r]];
+    if (rowptr[r + 1] - rowptr[r] != w) {
+      jur_set_error("%s: the block of ray %ld has %ld columns, its slice %d has %ld elements", who, r, rowptr[r + 1] - rowptr[r], sid[r], w);
+      return JUR_EINVAL;
+    }
+  }
+  return JUR_OK;
+}
+
+int jur_gain_check_var(char const *who, int ncomp, long nr, int nd, double const *var, unsigned char const *live) {
+  size_t const nrd = (size_t)nr * (size_t)nd;
+  for (int c = 0; c < ncomp; c++)
+    for (long r = 0; r < nr; r++)
+      for (int id = 0; id < nd; id++) {
+        size_t const at = (size_t)r * (size_t)nd + (size_t)id;
+        if (!live[at]) continue;
+        double const v = var[(size_t)c * nrd + at];
+        if (!(v >= 0) || !(v - v == 0)) {
+          jur_set_error("%s: the variance of component %d, ray %ld, channel %d is %g: negative or not finite", who, c, r, id, v);
+          return JUR_EINVAL;
+        }
+      }
+  return JUR_OK;
+}
+
+long jur_gain_maps(long nslice, long const *wptr, long const *sptr, int nd, int *gmap) {
+  long nt = 0;
+  for (long q = 0; q < nslice; q++) {
+    long const w = wptr[q + 1] - wptr[q], M = (sptr[q + 1] - sptr[q]) * nd;
+    if (M > 0x7fffffffL) return -1;
+    for (long m0 = 0; m0 < M; m0 += JUR_GAIN_TILE)
+      for (long i0 = 0; i0 < w; i0 += JUR_GAIN_TILE, nt++)
+        if (gmap) { gmap[3 * nt] = (int)q; gmap[3 * nt + 1] = (int)m0; gmap[3 * nt + 2] = (int)i0; }
+  }
+  return nt;
+}
+
+/* upstream's set_cov_meas: the two variances of every measurement and the weight under their sum */
+int jur_error_components(int nd, long nr, double const *y, double const *err_noise, double const *err_formod, double *var,
+                         double *weight) {
+  char const *const who = "jur_error_components";
+  if (nd < 0 || nr < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  if (nd > 0 && (!err_noise || !err_formod)) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  for (int id = 0; id < nd; id++) {
+    if (!(err_noise[id] >= 0) || !(err_noise[id] - err_noise[id] == 0)) {
+      jur_set_error("%s: err_noise of channel %d is %g: negative or not finite", who, id, err_noise[id]);
+      return JUR_EINVAL;
+    }
+    if (!(err_formod[id] >= 0) || !(err_formod[id] - err_formod[id] == 0)) {
+      jur_set_error("%s: err_formod of channel %d is %g: negative or not finite", who, id, err_formod[id]);
+      return JUR_EINVAL;
+    }
+  }
+  size_t const nrd = (size_t)nr * (size_t)nd;
+  if (nrd == 0) return JUR_OK;
+  if (!y || !var || !weight) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  for (long r = 0; r < nr; r++)
+    for (int id = 0; id < nd; id++) {
+      size_t const at = (size_t)r * (size_t)nd + (size_t)id;
+      double const vn = err_noise[id] * err_noise[id], f = err_formod[id] / 100 * y[at], vf = f * f, sum = vn + vf;
+      int const ok = sum > 0 && sum - sum == 0;
+      var[at] = ok ? vn : 0.;
+      var[nrd + at] = ok ? vf : 0.;
+      weight[at] = ok ? 1 / sum : 0.;
+    }
+  return JUR_OK;
+}
+
 int jur_avk_summary(ctl_t const *ctl, atm_t const *atm, int first, int len, double const *avk, double *dofs_q, double *area,
                     double *resolution) {
   if (!ctl || !atm || first < 0 || len < 0 || (long)first + len > atm->np) {

@@ -178,6 +178,12 @@ def lib():
             L.jur_state_bound.argtypes = [C.c_double, C.c_double, C.c_double]
             L.jur_state_on_bounds.restype = C.c_long
             L.jur_state_on_bounds.argtypes = [C.c_int, dp, dp, C.c_long, ip_, dp, C.POINTER(C.c_byte)]
+        if hasattr(L, "jur_gain_scene_host"):        # (an A/B library from before the gain matrix has none of these)
+            L.jur_gain_slices_host.argtypes = [C.c_void_p, C.c_long, lp_, dp, ip_, C.c_long, C.c_int, lp_, ip_, dp, dp, C.c_void_p,
+                                               C.c_void_p]
+            L.jur_gain_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
+                                              dp, dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, dp, dp, dp, lp_, dp, C.c_long]
+            L.jur_error_components.argtypes = [C.c_int, C.c_long, dp, dp, dp, dp, dp]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -838,6 +844,68 @@ class Model:
             out["k"] = k
         return out
 
+    def gain_slices(self, wptr, S, rowptr, sid, k, weight_eff, var=None, status=None, want_gain=True):
+        """Gain matrix and error budget of systems and blocks the caller holds (jur_gain_slices_host).  wptr, S: as
+        diagnose_slices' wptr and S; status (nslice,) its breakdowns or None; rowptr (nr + 1,), sid (nr,) and the flat k:
+        the blocks as kernel_scene lays them out and the slice of every ray (-1: none); weight_eff (nr, nd): the effective
+        weights, anything not > 0 is "not live"; var (ncomp, nr, nd) or None: the variances per error source.
+        -> dict(gain: flat, laid out as k (with want_gain); sigma_comp (ncomp, n))."""
+        wp = np.ascontiguousarray(wptr, dtype=np.int64)
+        rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+        sd = np.ascontiguousarray(sid, dtype=np.int32)
+        ns, nr, n, na = len(wp) - 1, len(rp) - 1, int(wp[-1]), int((np.diff(wp) ** 2).sum())
+        ww = np.ascontiguousarray(weight_eff, dtype=np.float64)
+        if ww.ndim != 2 or ww.shape[0] != nr or sd.shape != (nr,):
+            raise ValueError("weight_eff must be (%d, nd) and sid (%d,)" % (nr, nr))
+        nd = ww.shape[1]
+        SS, kk = (np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (S, k))
+        if SS.size != na or kk.size != int(rp[-1]) * nd:
+            raise ValueError("S must hold %d doubles and k %d" % (na, int(rp[-1]) * nd))
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        if st is not None and st.shape != (ns,):
+            raise ValueError("status must be (%d,)" % ns)
+        gin, gout, res, keep = _gain_structs(n, nr, nd, int(rp[-1]) * nd, var, want_gain)
+        ip_, lp_ = C.POINTER(C.c_int), C.POINTER(C.c_long)
+        _chk(lib().jur_gain_slices_host(self.h, ns, wp.ctypes.data_as(lp_), _p(SS), None if st is None else st.ctypes.data_as(ip_),
+                                        nr, nd, rp.ctypes.data_as(lp_), sd.ctypes.data_as(ip_), _p(kk), _p(ww), C.byref(gin),
+                                        C.byref(gout)))
+        return res
+
+    def gain_scene(self, atm, geom, y, weight, var=None, prior_ivar=None, want_gain=False, want_S=False, want_avk=False,
+                   want_normal=False, want_k=False, rad_in=None, max_rays_per_pass=0, rowptr=None):
+        """diagnose_scene plus the gain matrix G = S K^T Se^-1 and the retrieval error per source (jur_gain_scene_host):
+        var (ncomp, nr, nd) or None, the variances of up to 8 error sources (error_components makes upstream's two).
+        -> diagnose_scene's dict, plus sigma_comp (ncomp, n) and, with want_gain, gain: flat, the block of ray r at
+        rowptr[r] * nd as [nd][width], entry (id, i) the response of element i to measurement (r, id).  What is not
+        wanted never leaves the device."""
+        g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, rowptr)
+        nr, nd = g.shape[1], self.nd
+        tau = np.zeros((nr, nd))
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        ns, n, na = len(lay["sfirst"]), int(lay["wptr"][-1]), int(lay["aptr"][-1])
+        cost, nlive = np.zeros(ns), np.zeros(ns, dtype=np.int64)
+        A, b = (np.zeros(na), np.zeros(n)) if want_normal else (None, None)
+        nk = int(lay["rowptr"][-1]) * nd
+        k = np.zeros(nk) if want_k else None
+        dout, res, keep = _diag_structs(ns, n, na, prior_ivar, want_S, want_avk)
+        gin, gout, gres, gkeep = _gain_structs(n, nr, nd, nk, var, want_gain)
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
+        lp_ = C.POINTER(C.c_long)
+        _chk(lib().jur_gain_scene_host(self.h, C.byref(atm), nr, garr, _p(rad), _p(tau), tarr,
+                                       npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(lp_), _p(yy), _p(ww),
+                                       None if keep is None else _p(keep), C.byref(dout), C.byref(gin), C.byref(gout),
+                                       _p(A) if want_normal else None, _p(b) if want_normal else None, _p(cost),
+                                       nlive.ctypes.data_as(lp_), _p(k) if want_k else None, max_rays_per_pass))
+        out = dict(lay, rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, cost=cost, nlive=nlive, **res)
+        out.update(gres)
+        if want_normal:
+            out.update(A=A, b=b)
+        if want_k:
+            out["k"] = k
+        return out
+
     def scene_ms(self):
         """The share of kernel_scene's own kernels in the launches timed since the last call (call kernel_ms first)."""
         ms, n = C.c_double(0), C.c_long(0)
@@ -939,6 +1007,16 @@ class DiagOut(C.Structure):
     """jur_diag_out_t"""
     _fields_ = [("sigma", dp), ("sigma_noise", dp), ("sigma_smooth", dp), ("avk_diag", dp), ("dofs", dp),
                 ("status", C.POINTER(C.c_int)), ("S", dp), ("avk", dp)]
+
+
+class GainIn(C.Structure):
+    """jur_gain_in_t"""
+    _fields_ = [("ncomp", C.c_int), ("var", dp)]
+
+
+class GainOut(C.Structure):
+    """jur_gain_out_t"""
+    _fields_ = [("gain", dp), ("sigma_comp", dp)]
 
 
 RET_ACTIVE, RET_CONVERGED, RET_STALLED, RET_MAXITER = 0, 1, 2, 3      # JUR_RET_*
@@ -1055,6 +1133,37 @@ def _diag_structs(ns, n, na, prior_ivar, want_S, want_avk):
                    res["status"].ctypes.data_as(C.POINTER(C.c_int)), _p(res["S"]) if want_S else None,
                    _p(res["avk"]) if want_avk else None)
     return dout, res, pri
+
+
+def _gain_structs(n, nr, nd, nk, var, want_gain):
+    """(jur_gain_in_t, jur_gain_out_t, the result dict, var as the array to keep alive or None) of a call with n state
+    elements, nr rays of nd channels and nk block doubles.  Nothing is refused here that the library refuses."""
+    vv = None if var is None else np.ascontiguousarray(var, dtype=np.float64)
+    if vv is not None and (vv.ndim != 3 or vv.shape[1:] != (nr, nd)):
+        raise ValueError("var must be (ncomp, %d, %d)" % (nr, nd))
+    ncomp = 0 if vv is None else vv.shape[0]
+    res = dict(sigma_comp=np.zeros((ncomp, n)))
+    if want_gain:
+        res["gain"] = np.zeros(nk)
+    gin = GainIn(ncomp, None if vv is None else _p(vv))
+    gout = GainOut(_p(res["gain"]) if want_gain else None, _p(res["sigma_comp"]) if ncomp else None)
+    return gin, gout, res, vv
+
+
+def error_components(y, err_noise, err_formod):
+    """jur_error_components (host arithmetic, no GPU; upstream's set_cov_meas): y (nr, nd) radiances, err_noise (nd,) in
+    radiance units, err_formod (nd,) in per cent of the radiance -> (var (2, nr, nd): noise, forward model; weight (nr,
+    nd) = 1 / their sum, 0 with both variances +0.0 where that sum is not finite and > 0)."""
+    yy = np.ascontiguousarray(y, dtype=np.float64)
+    if yy.ndim != 2:
+        raise ValueError("y must be (nr, nd)")
+    nr, nd = yy.shape
+    en, ef = (np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (err_noise, err_formod))
+    if en.size != nd or ef.size != nd:
+        raise ValueError("err_noise and err_formod must hold %d doubles" % nd)
+    var, weight = np.zeros((2, nr, nd)), np.zeros((nr, nd))
+    _chk(lib().jur_error_components(nd, nr, _p(yy), _p(en), _p(ef), _p(var), _p(weight)))
+    return var, weight
 
 
 def avk_summary(ctl, atm, first, length, avk):
