@@ -499,6 +499,73 @@ int  jur_gain_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const
 int  jur_error_components(int nd, long nr, double const *y, double const *err_noise /* [nd] */, double const *err_formod /* [nd], per cent */,
                           double *var /* [2][nr][nd]: noise, formod */, double *weight /* [nr][nd] */);
 
+/* Parameter errors of the slices, on the device: the error of quantities b that are not retrieved (a temperature profile
+ * under a trace-gas retrieval, an interfering gas, the pressure at the reference level, an extinction) reaches the
+ * measurements through their Jacobian K_b, fully correlated across the channels and rays of a slice, and the state
+ * through C_s = G_s^T K_b,s = dx^/db, the cross-state matrix of slice s ([w_s][wb_s]); its covariance in the state is
+ * C_s Sigma_b C_s^T.  With K_b = K, C_s is the averaging kernel.
+ * Inputs.  sid, wptr, rowptr, gain and weight_eff are what jur_gain_slices_host takes and writes for the retrieved state.
+ *   kb and rowptr_b are blocks of jur_kernel_scene_host on the same rays under other retrieval windows (with a field of
+ *   view or the hydrostatic balance set, the convolved or balanced ones): the block of ray r lies at kb + rowptr_b[r] * nd
+ *   as [nd][wb].  wb_s is the width in rowptr_b of the rays of slice s (0 for a slice without rays), bwptr its running
+ *   sum, cptr and bbptr the running sums of w_s * wb_s and wb_s^2 (jur_param_layout makes the three).  The width in
+ *   rowptr_b of a ray without a slice is not looked at.
+ * Measurements.  As jur_gain_slices_host: the rays with sid[r] == s ascending, the channels of a ray ascending; a
+ *   measurement is live exactly when its weight_eff > 0.  A row that is not live is never read, in gain or in kb (kb
+ *   holds NaN on masked channels).
+ * The cross-state matrix.  C_s[i][j] = c, the chain over the live measurements m of s, ascending, from +0.0 of
+ *   fma(G_m,i, Kb_m,j, c).  A dead state element has a zero gain column and so a row of +0.0 -- or of NaN where column j
+ *   is: a NaN in a live row of kb reaches column j of that slice's C, all of it, and nothing else.  A slice with wb_s == 0
+ *   has an empty C_s and a sigma_param of +0.0.
+ * The budget.  Component c < nvar is diagonal, Sigma = diag(var[c][bwptr[s] + j]): q_i is the chain over j = 0 .. wb_s - 1
+ *   ascending from +0.0 of fma(C_ij * C_ij, var_j, q), the square rounded first.  Component nvar + c, c < ncov, is full,
+ *   Sigma_s = cov[c] at bbptr[s] as [wb_s][wb_s], of which the diagonal and the lower triangle are read (Sigma_jl for l > j
+ *   is read as Sigma_lj): t_j is the chain over l ascending from +0.0 of fma(Sigma_jl, C_il, t), then q_i the chain over j
+ *   ascending from +0.0 of fma(C_ij, t_j, q).  sigma_param[c][wptr[s] + i] = sqrt(q_i) where q_i > 0, NaN where q_i is
+ *   NaN, +0.0 otherwise (a Sigma that is not positive semidefinite can give q_i < 0).  Messages count the components as
+ *   sigma_param does: the diagonal ones first.
+ * Every double depends on its own slice's inputs, w_s and wb_s alone: not on the other slices, their order, where the
+ *   rays of a slice sit in the call, which components accompany it or whether C was asked for.  No atomics, no
+ *   measurement chain split across workgroups, no MFMA.
+ * jur_param_slices_host: under the contract of jur_gain_slices_host (the model supplies device and stream; its atmosphere
+ *   and workspace are not touched; ordered against the model's other calls as that entry is).  nslice == 0 or nr == 0 is
+ *   JUR_OK and writes nothing.  out->C is optional, out->sigma_param required when nvar + ncov > 0.  JUR_EINVAL, naming
+ *   slice, ray, component or element, before anything is launched, for: a required pointer that is NULL; nvar, ncov
+ *   negative or nvar + ncov > 8; wptr or bwptr not an ascending running sum from 0; a ray whose width in rowptr is not
+ *   that of its slice; two rays of one slice with different widths in rowptr_b; a bwptr that does not agree with those
+ *   widths; a var that is negative or not finite; an entry of cov that is read and not finite; a negative diagonal of
+ *   cov.  JUR_ENOMEM, JUR_EHIP as jur_gain_slices_host.
+ * jur_param_layout (host arithmetic, no GPU): bwptr, cptr, bbptr [nslice + 1] from the widths; any of the three may be
+ *   NULL (a first call counts).  Returns cptr[nslice], or JUR_EINVAL with the layout refusals above. */
+typedef struct {
+  int nvar, ncov;            /* nvar + ncov in 0..8 */
+  double const *var;         /* [nvar][bwptr[nslice]]   diagonal parameter covariances */
+  double const *cov;         /* [ncov][bbptr[nslice]]   full ones, Sigma_s at bbptr[s], [wb_s][wb_s]; diagonal and lower triangle read */
+} jur_param_in_t;
+typedef struct {
+  double *C;                 /* optional, [cptr[nslice]]: C_s at cptr[s], [w_s][wb_s] row-major */
+  double *sigma_param;       /* [nvar + ncov][wptr[nslice]], the var components first; required when nvar + ncov > 0 */
+} jur_param_out_t;
+int  jur_param_slices_host(jur_model_t *m, long nslice, long const *wptr, long const *bwptr,
+                           long nr, int nd, long const *rowptr, long const *rowptr_b, int const *sid,
+                           double const *gain, double const *kb, double const *weight_eff,
+                           jur_param_in_t const *in, jur_param_out_t const *out);
+long jur_param_layout(long nslice, long const *wptr, long nr, long const *rowptr, long const *rowptr_b, int const *sid,
+                      long *bwptr, long *cptr, long *bbptr);
+void jur_param_abi_sizes(size_t out[2]);   /* sizeof jur_param_in_t, jur_param_out_t: for bindings that mirror them */
+
+/* The retrieval windows of a model.  A model keeps a copy of the control block it was created with, and every entry that
+ * derives its state from it -- the scene entries (jur_kernel_scene_host ... jur_gain_scene_host) and jur_kernel, with
+ * jur_state_size -- reads the windows there.  jur_model_set_ret_windows copies retp_zmin/zmax, rett_zmin/zmax,
+ * retq_zmin/zmax[ng] and retk_zmin/zmax[nw], and nothing else, from ctl into that copy: from the next call on those
+ * entries see the new windows, so one model (one upload of the tables) serves the Jacobian K and the Jacobian K_b of
+ * quantities that are not retrieved.  No device work; nothing the model caches depends on the windows.  A prior
+ * precision that is set (jur_model_set_prior_precision) is still checked against the layout of each call, as before.
+ * JUR_EINVAL for a NULL or a window bound that is NaN; after a refusal what was set stays set.
+ * jur_model_ret_windows copies the same fields out into ctl and leaves the rest of it alone. */
+int  jur_model_set_ret_windows(jur_model_t *m, ctl_t const *ctl);
+int  jur_model_ret_windows(jur_model_t const *m, ctl_t *ctl);
+
 /* Curtis-Godson means along each line of sight (reference curtis_godson(), jr_common.h:455-473, which
  * upstream compiles only with -DCURTIS_GODSON for FORMOD=1): per ray, emitter and LOS point the
  * column-weighted pressure cgp, temperature cgt and the cumulative column cgu.  Host arrays

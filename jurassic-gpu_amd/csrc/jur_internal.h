@@ -314,6 +314,41 @@ int jur_gain_check_args(char const *who, jur_gain_in_t const *in, jur_gain_out_t
 int jur_gain_check_layout(char const *who, long nslice, long const *wptr, long nr, long const *rowptr, int const *sid);
 int jur_gain_check_var(char const *who, int ncomp, long nr, int nd, double const *var, unsigned char const *live);
 long jur_gain_maps(long nslice, long const *wptr, long const *sptr, int nd, int *gmap);
+/* Parameter errors of a scene (jur_param_slices_host): C_s = G_s^T Kb_s over the live measurements of every slice, then
+ * the quadratic forms on it.  Measurements and the rows of `gain` as in jur_scene_gain_t; the row of kb of the same
+ * measurement lies at kb + koffb[ray] + channel * wb_s.  All arrays are device memory. */
+typedef struct {
+  long nslice;
+  int nd, nvar, ncov;
+  long const *wptr, *bwptr;     /* [nslice + 1] running sums of w_s and of wb_s                              */
+  long const *cptr, *bbptr;     /* [nslice + 1] running sums of w_s * wb_s and of wb_s^2                     */
+  long const *sptr;             /* [nslice + 1] rays of every slice in srays                                */
+  long const *pptr;             /* [nslice + 1] running sum of ceil(w_s / 64): the quadratic forms' workgroups */
+  int const *srays;             /* the rays of every slice, ascending                                       */
+  long const *koff, *koffb;     /* [nr] first double of the gain block and of the kb block of every ray     */
+  int const *cmap;              /* [ntile][3] tile of C -> (slice, first i, first j), 64 x 64                */
+  double const *gain, *kb;      /* the blocks                                                               */
+  double const *weff;           /* [nr][nd] effective weights: anything not > 0 is "not live"                */
+  double const *var;            /* [nvar][nbw] diagonal parameter covariances                               */
+  double const *cov;            /* [ncov][nbb] full ones                                                    */
+  long nb, nbw, nbb;            /* wptr[nslice], bwptr[nslice], bbptr[nslice]                                */
+  double *C;                    /* [cptr[nslice]] written                                                   */
+  double *sig;                  /* [nvar + ncov][nb] written                                                */
+} jur_scene_param_t;
+/* the cross-state matrices, then (nvar + ncov > 0) the quadratic forms, in stream order */
+int jurk_scene_param(jur_scene_param_t const *a, long ntile, long ngroups, void *stream);
+enum { JUR_PARAM_TILE = 64, JUR_PARAM_ROWS = 64, JUR_PARAM_MAXCOMP = 8 };
+/* host arithmetic of jur_param_slices_host (jur_scene.c; no GPU).  jur_param_layout_as: jur_param_layout under the name
+ * `who` in its messages.  jur_param_check_args: the structs.  jur_param_check_bwptr: bwptr against the widths of the rays.
+ * jur_param_check_values: var >= 0 and finite; what is read of cov finite, its diagonal >= 0.  jur_param_maps: tile t of C
+ * is the elements [i0, i0 + 64) x the parameters [j0, j0 + 64) of slice s, cmap[3 t] = s, then i0, j0, slices ascending,
+ * row-major within a slice; cmap may be NULL (a first call counts); returns the number of tiles. */
+long jur_param_layout_as(char const *who, long nslice, long const *wptr, long nr, long const *rowptr, long const *rowptr_b,
+                         int const *sid, long *bwptr, long *cptr, long *bbptr);
+int jur_param_check_args(char const *who, jur_param_in_t const *in, jur_param_out_t const *out);
+int jur_param_check_bwptr(char const *who, long nslice, long const *bwptr, long const *bw);
+int jur_param_check_values(char const *who, long nslice, long const *bwptr, long const *bbptr, jur_param_in_t const *in);
+long jur_param_maps(long nslice, long const *wptr, long const *bwptr, int *cmap);
 /* host checks of the full prior precision (jur_scene.c; no GPU): what is read of R, the layout of a call against the one
  * set, the arguments of jur_prior_corr_host */
 int jur_prior_check_R(char const *who, long nslice, long const *wptr, double const *R);

@@ -34,6 +34,8 @@
 //   jur_scene_gradient_kernel  b, cost and nlive of a scene's slices from held blocks, a lane per state element (jur_gradient_scene_host).
 //   jur_scene_gain_kernel  gain matrix G = S K^T W of a scene's slices over the ragged blocks, a workgroup per 64 x 64 tile;
 //   jur_scene_budget_kernel  the row sums of G^2 var per error source, a lane per state element (jur_gain_scene_host).
+//   jur_scene_cross_kernel  cross-state matrix C = G^T Kb of a scene's slices over the ragged blocks, a workgroup per 64 x 64 tile;
+//   jur_scene_param_kernel  diag(C Sigma C^T) per parameter covariance, a workgroup per 64 rows of C (jur_param_slices_host).
 //   jur_intpol_kernel     regridding of a track / point-cloud atmosphere (intpol_atm, jurassic.c:675-804).
 //   jur_kat_*_kernel      known-answer hooks for tests: the device functions on arrays of inputs.
 //
@@ -3364,6 +3366,159 @@ __global__ __launch_bounds__(256) void jur_scene_budget_kernel(jur_scene_gain_t 
     if (c < ncomp && inside) a.sigc[(long)c * a.nb + a.wptr[s] + i] = sqrt(q[c]);
 }
 
+// ---- parameter errors of a scene (jur_param_slices_host) --------------------------------------------------------------
+// C_s = G_s^T Kb_s, a ragged batched contraction over the measurements.  One workgroup per tile of 64 state elements x 64
+// parameters of one slice (cmap: slice, first element, first parameter).  Measurement m of the slice is channel m % nd of
+// its ray m / nd, the rays ascending (srays, sptr); its gain row starts at gain + koff[ray] + channel * w and its kb row
+// at kb + koffb[ray] + channel * wb.  Lane (tr, tc) holds the 4 x 4 micro-tile of the elements i0 + tr + 16 p and the
+// parameters j0 + tc + 16 q and carries each as one chain c = fma(G_m,i, Kb_m,j, c) over all measurements of the slice,
+// ascending, the operands staged through LDS 16 measurements at a time: GI the tile's 64 gain entries of each, KB its 64
+// kb entries.  Wavefront v stages the measurements v, v + 4, v + 8, v + 12 of the 16, a lane per entry: the row address
+// and the liveness are uniform in the wavefront and the 64 entries one contiguous stretch.  A measurement that is not
+// live (omega not > 0), and what lies beyond the slice's measurements or beyond w or wb, is staged as exact zeros and
+// never loaded; fma(+0, +0, c) leaves every chain as it was.  The lanes of a wavefront read two neighbouring doubles of a
+// GI row (broadcast to 16 lanes each) and 16 consecutive doubles of a KB row: no bank conflicts, so the rows need none
+// of the padding jur_scene_gain_kernel's transposed staging needs.  LDS: 16 KB, two barriers per 16 measurements.
+#define CROSS_TILE 64
+#define CROSS_NB 16
+__global__ __launch_bounds__(256) void jur_scene_cross_kernel(jur_scene_param_t a) {
+  __shared__ double GI[CROSS_NB][CROSS_TILE], KB[CROSS_NB][CROSS_TILE];
+  long const s = a.cmap[3 * (long)blockIdx.x];
+  int const i0 = a.cmap[3 * (long)blockIdx.x + 1], j0 = a.cmap[3 * (long)blockIdx.x + 2];
+  int const tid = threadIdx.x, tr = tid >> 4, tc = tid & 15, col = tid & 63, wv = tid >> 6, nd = a.nd;
+  int const w = (int)(a.wptr[s + 1] - a.wptr[s]), wb = (int)(a.bwptr[s + 1] - a.bwptr[s]);
+  long const q0 = a.sptr[s], M = (a.sptr[s + 1] - q0) * nd;
+  bool const gi_in = i0 + col < w, kb_in = j0 + col < wb;
+  double acc[4][4];
+#pragma unroll
+  for (int p = 0; p < 4; p++)
+#pragma unroll
+    for (int q = 0; q < 4; q++) acc[p][q] = 0.;
+  for (long m0 = 0; m0 < M; m0 += CROSS_NB) {
+    __syncthreads();                                        // (the micro-tiles of the last 16 have been taken)
+#pragma unroll
+    for (int t = 0; t < CROSS_NB / 4; t++) {
+      int const ml = wv + 4 * t;
+      long const mm = m0 + ml;
+      double g = 0., kb = 0.;
+      if (mm < M) {                                         // (uniform in the wavefront, as is the liveness)
+        long const qq = mm / nd;
+        int const id = (int)(mm - qq * nd);
+        long const r = a.srays[q0 + qq];
+        if (a.weff[r * nd + id] > 0) {
+          if (gi_in) g = a.gain[a.koff[r] + (long)id * w + i0 + col];
+          if (kb_in) kb = a.kb[a.koffb[r] + (long)id * wb + j0 + col];
+        }
+      }
+      GI[ml][col] = g; KB[ml][col] = kb;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < CROSS_NB; m++) {
+      double gi[4], kj[4];
+#pragma unroll
+      for (int p = 0; p < 4; p++) { gi[p] = GI[m][tr + 16 * p]; kj[p] = KB[m][tc + 16 * p]; }
+#pragma unroll
+      for (int p = 0; p < 4; p++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[p][q] = fma(gi[p], kj[q], acc[p][q]);
+    }
+  }
+  double *const C = a.C + a.cptr[s];
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+    int const i = i0 + tr + 16 * p;
+    if (i >= w) continue;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      int const j = j0 + tc + 16 * q;
+      if (j < wb) C[(long)i * wb + j] = acc[p][q];
+    }
+  }
+}
+
+// The quadratic forms on C_s: sigma_param[c][e] = sqrt(diag(C Sigma_c C^T)) for up to 8 components, the diagonal ones
+// first.  One workgroup of four wavefronts per 64 consecutive state elements (rows of C_s) of one slice (pptr); lane l of
+// every wavefront has row 64 g + l.  What is staged is 64 rows x 16 columns of C (CL, and CJ for the outer index of a
+// full component), 16 x 16 of Sigma (SG), the 16 variances of every diagonal component (VL) and 64 x 16 partial
+// vectors (TT), whatever the slice.  Rows are padded to 17 doubles: the lanes of a wavefront read one column of 64 rows.
+// Diagonal component c: wavefront c % 4 carries q = fma(C_ij * C_ij, var_j, q) over j ascending, the square rounded first.
+// Full component c: for every 16 values of j the four wavefronts carry four each of the chains t_j = fma(Sigma_jl, C_il, t)
+// over l ascending (Sigma_jl for l > j read as Sigma_lj; its entry is uniform in the wavefront: a broadcast), leave them
+// in TT, and wavefront c % 4 extends q = fma(C_ij, t_j, q) over these j, ascending.  Columns beyond wb are staged as
+// exact zeros and never loaded.  sqrt(q) where q > 0 or q is NaN, +0.0 otherwise.
+#define PARAM_ROWS 64
+#define PARAM_NB 16
+__device__ inline void param_stage_rows(double (*T)[PARAM_NB + 1], double const *C, int i0, int c0, int w, int wb, int tid) {
+  for (int e = tid; e < PARAM_ROWS * PARAM_NB; e += 256) {
+    int const rr = e >> 4, cc = e & 15, i = i0 + rr, j = c0 + cc;
+    T[rr][cc] = (i < w && j < wb) ? C[(long)i * wb + j] : 0.;
+  }
+}
+__global__ __launch_bounds__(256) void jur_scene_param_kernel(jur_scene_param_t a) {
+  __shared__ double CL[PARAM_ROWS][PARAM_NB + 1], CJ[PARAM_ROWS][PARAM_NB + 1], TT[PARAM_ROWS][PARAM_NB + 1];
+  __shared__ double SG[PARAM_NB][PARAM_NB + 1], VL[8][PARAM_NB];
+  long const s = scene_find<false>(a.pptr, 0, a.nslice, (long)blockIdx.x);
+  int const w = (int)(a.wptr[s + 1] - a.wptr[s]), wb = (int)(a.bwptr[s + 1] - a.bwptr[s]);
+  int const tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nvar = a.nvar, ncov = a.ncov;
+  int const i0 = (int)(((long)blockIdx.x - a.pptr[s]) * PARAM_ROWS), i = i0 + lane;
+  bool const inside = i < w;
+  double const *const C = a.C + a.cptr[s];
+  double *const out = a.sig + a.wptr[s] + i;
+  if (nvar > 0) {
+    double qa = 0., qb = 0.;                                // (the components wv and wv + 4)
+    for (int j0 = 0; j0 < wb; j0 += PARAM_NB) {
+      __syncthreads();                                      // (the last 16 columns have been taken)
+      param_stage_rows(CL, C, i0, j0, w, wb, tid);
+      if (tid < nvar * PARAM_NB) {
+        int const c = tid >> 4, j = j0 + (tid & 15);
+        VL[c][tid & 15] = j < wb ? a.var[(long)c * a.nbw + a.bwptr[s] + j] : 0.;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int jj = 0; jj < PARAM_NB; jj++) {
+        double const cij = CL[lane][jj], cc = cij * cij;
+        if (wv < nvar) qa = fma(cc, VL[wv][jj], qa);
+        if (wv + 4 < nvar) qb = fma(cc, VL[wv + 4][jj], qb);
+      }
+    }
+    if (inside && wv < nvar) out[(long)wv * a.nb] = (qa > 0 || qa != qa) ? sqrt(qa) : 0.;
+    if (inside && wv + 4 < nvar) out[(long)(wv + 4) * a.nb] = (qb > 0 || qb != qb) ? sqrt(qb) : 0.;
+  }
+  for (int c = 0; c < ncov; c++) {
+    double const *const Sg = a.cov + (long)c * a.nbb + a.bbptr[s];
+    bool const mine = wv == ((nvar + c) & 3);               // (the wavefront that carries q of this component)
+    double q = 0.;
+    for (int j0 = 0; j0 < wb; j0 += PARAM_NB) {
+      double t[4] = {0., 0., 0., 0.};                       // (t_j of j = j0 + 4 wv + u)
+      for (int l0 = 0; l0 < wb; l0 += PARAM_NB) {
+        __syncthreads();                                    // (the last tiles, and TT and CJ of the last j0, have been taken)
+        param_stage_rows(CL, C, i0, l0, w, wb, tid);
+        if (l0 == 0) param_stage_rows(CJ, C, i0, j0, w, wb, tid);
+        {
+          int const jj = tid >> 4, ll = tid & 15, j = j0 + jj, l = l0 + ll;
+          SG[jj][ll] = (j < wb && l < wb) ? (l <= j ? Sg[(long)j * wb + l] : Sg[(long)l * wb + j]) : 0.;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ll = 0; ll < PARAM_NB; ll++) {
+          double const cil = CL[lane][ll];
+#pragma unroll
+          for (int u = 0; u < 4; u++) t[u] = fma(SG[4 * wv + u][ll], cil, t[u]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) TT[lane][4 * wv + u] = t[u];
+      __syncthreads();
+      if (mine) {
+#pragma unroll
+        for (int jj = 0; jj < PARAM_NB; jj++) q = fma(CJ[lane][jj], TT[lane][jj], q);
+      }
+    }
+    if (mine && inside) out[(long)(nvar + c) * a.nb] = (q > 0 || q != q) ? sqrt(q) : 0.;
+  }
+}
+
 // ---- trial states of a scene (jur_trial_scene_host, jur_retrieve_scene_host) -----------------------------------------
 // One lane per state element e of slice s (JUR_ELEM_APPLY: per trial t and element).  The value of element e is
 // base[erow[e]][eip[e]]; its place in trial copy 1 + s * ntrial + t is the same row at off[copy] + (eip[e] - sfirst[s]).
@@ -3730,6 +3885,14 @@ extern "C" int jurk_scene_gain(jur_scene_gain_t const *a, long ntile, long ngrou
   hipStream_t const s = (hipStream_t)stream;
   if (ntile > 0) hipLaunchKernelGGL(jur_scene_gain_kernel, dim3((unsigned)ntile), dim3(256), 0, s, *a);
   if (a->ncomp > 0 && ngroups > 0) hipLaunchKernelGGL(jur_scene_budget_kernel, dim3((unsigned)ngroups), dim3(256), 0, s, *a);
+  return (int)hipGetLastError();
+}
+
+// (the tile and workgroup counts are the host's: jur_param_maps and pptr[nslice]; the quadratic forms only with components)
+extern "C" int jurk_scene_param(jur_scene_param_t const *a, long ntile, long ngroups, void *stream) {
+  hipStream_t const s = (hipStream_t)stream;
+  if (ntile > 0) hipLaunchKernelGGL(jur_scene_cross_kernel, dim3((unsigned)ntile), dim3(256), 0, s, *a);
+  if (a->nvar + a->ncov > 0 && ngroups > 0) hipLaunchKernelGGL(jur_scene_param_kernel, dim3((unsigned)ngroups), dim3(256), 0, s, *a);
   return (int)hipGetLastError();
 }
 

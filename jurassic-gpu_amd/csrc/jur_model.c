@@ -1581,6 +1581,36 @@ int jur_model_set_kernel_recomp(jur_model_t *m, int every) {
 
 int jur_model_kernel_recomp(jur_model_t const *m) { return m ? m->kernel_recomp : 1; }
 
+/* The retrieval windows live in the model's copy of the control block and nowhere else: every entry that derives a state
+ * reads them there when it is called (jur_scene_layout, jur_scene_slices, jur_state_vector), and neither the view, the
+ * uploaded atmosphere nor the tables were made from them. */
+static void ret_windows_copy(ctl_t *to, ctl_t const *from, int ng, int nw) {
+  to->retp_zmin = from->retp_zmin; to->retp_zmax = from->retp_zmax;
+  to->rett_zmin = from->rett_zmin; to->rett_zmax = from->rett_zmax;
+  for (int g = 0; g < ng; g++) { to->retq_zmin[g] = from->retq_zmin[g]; to->retq_zmax[g] = from->retq_zmax[g]; }
+  for (int w = 0; w < nw; w++) { to->retk_zmin[w] = from->retk_zmin[w]; to->retk_zmax[w] = from->retk_zmax[w]; }
+}
+
+int jur_model_set_ret_windows(jur_model_t *m, ctl_t const *ctl) {
+  char const *const who = "jur_model_set_ret_windows";
+  if (!m || !ctl) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  int const ng = m->view.ng, nw = m->view.nw;
+  if (ctl->retp_zmin != ctl->retp_zmin || ctl->retp_zmax != ctl->retp_zmax) { jur_set_error("%s: the window of p is NaN", who); return JUR_EINVAL; }
+  if (ctl->rett_zmin != ctl->rett_zmin || ctl->rett_zmax != ctl->rett_zmax) { jur_set_error("%s: the window of T is NaN", who); return JUR_EINVAL; }
+  for (int g = 0; g < ng; g++)
+    if (ctl->retq_zmin[g] != ctl->retq_zmin[g] || ctl->retq_zmax[g] != ctl->retq_zmax[g]) { jur_set_error("%s: the window of gas %d is NaN", who, g); return JUR_EINVAL; }
+  for (int w = 0; w < nw; w++)
+    if (ctl->retk_zmin[w] != ctl->retk_zmin[w] || ctl->retk_zmax[w] != ctl->retk_zmax[w]) { jur_set_error("%s: the window of extinction %d is NaN", who, w); return JUR_EINVAL; }
+  ret_windows_copy(m->ctl, ctl, ng, nw);               /* (after every check: what was set stays set on a refusal) */
+  return JUR_OK;
+}
+
+int jur_model_ret_windows(jur_model_t const *m, ctl_t *ctl) {
+  if (!m || !ctl) { jur_set_error("jur_model_ret_windows: null argument"); return JUR_EINVAL; }
+  ret_windows_copy(ctl, m->ctl, m->view.ng, m->view.nw);
+  return JUR_OK;
+}
+
 static int scene_timed_begin(jur_model_t *m, hipStream_t s);
 static void scene_timed_end(jur_model_t *m, int ti, hipStream_t s);
 
@@ -3875,6 +3905,96 @@ int jur_gain_slices_host(jur_model_t *m, long nslice, long const *wptr, double c
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
   free(ptr); free(srays); free(hmap); free(hl);
+  return rc;
+}
+
+/* ---- parameter errors of the slices (jur_param_slices_host) ----------------------------------------------------------- */
+/* Gains and parameter blocks the caller holds.  The slab: the longs wptr | bwptr | cptr | bbptr | sptr | pptr | koff |
+ * koffb, then the doubles gain | kb | weff | C | var | cov | sig, then the ints cmap | srays. */
+int jur_param_slices_host(jur_model_t *m, long nslice, long const *wptr, long const *bwptr, long nr, int nd, long const *rowptr,
+                          long const *rowptr_b, int const *sid, double const *gain, double const *kb, double const *weight_eff,
+                          jur_param_in_t const *in, jur_param_out_t const *out) {
+  char const *const who = "jur_param_slices_host";
+  if (!m || nslice < 0 || nr < 0 || nd < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  int rc = jur_param_check_args(who, in, out);
+  if (rc) return rc;
+  if (nslice == 0 || nr == 0) return JUR_OK;
+  if (nslice > 0x7fffffffL || nr > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 systems and rays per call", who); return JUR_EINVAL; }
+  if (!wptr || !bwptr || !rowptr || !rowptr_b || !sid) {
+    jur_set_error("%s: null argument (%s)", who, !wptr ? "wptr" : !bwptr ? "bwptr" : !rowptr ? "rowptr" : !rowptr_b ? "rowptr_b" : "sid");
+    return JUR_EINVAL;
+  }
+  size_t const NS = (size_t)nslice, NR = (size_t)nr, NRD = NR * (size_t)nd, NC = (size_t)(in->nvar + in->ncov);
+  long *ptr = (long *)malloc(sizeof(long) * (6 * (NS + 1) + 2 * NR));
+  int *srays = (int *)malloc(sizeof(int) * NR), *hmap = NULL;
+  int enqueued = 0;
+  if (!ptr || !srays) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+  {
+    long *const bw = ptr + NS + 1, *const cptr = bw + NS + 1, *const bbptr = cptr + NS + 1, *const sptr = bbptr + NS + 1,
+         *const pptr = sptr + NS + 1, *const koff = pptr + NS + 1, *const koffb = koff + NR;
+    long const nc = jur_param_layout_as(who, nslice, wptr, nr, rowptr, rowptr_b, sid, bw, cptr, bbptr);
+    if (nc < 0) { rc = (int)nc; goto done; }
+    if ((rc = jur_param_check_bwptr(who, nslice, bwptr, bw))) goto done;
+    size_t const nk = (size_t)rowptr[nr] * (size_t)nd, nkb = (size_t)rowptr_b[nr] * (size_t)nd;
+    if ((nk > 0 && !gain) || (nkb > 0 && !kb) || (NRD > 0 && !weight_eff)) {
+      jur_set_error("%s: null argument (%s)", who, (nk > 0 && !gain) ? "gain" : (nkb > 0 && !kb) ? "kb" : "weight_eff");
+      rc = JUR_EINVAL; goto done;
+    }
+    if ((rc = jur_param_check_values(who, nslice, bw, bbptr, in))) goto done;
+    memcpy(ptr, wptr, sizeof(long) * (NS + 1));
+    pptr[0] = 0;
+    for (long q = 0; q < nslice; q++) pptr[q + 1] = pptr[q] + (wptr[q + 1] - wptr[q] + JUR_PARAM_ROWS - 1) / JUR_PARAM_ROWS;
+    for (long r = 0; r < nr; r++) { koff[r] = rowptr[r] * nd; koffb[r] = rowptr_b[r] * nd; }
+    long const nlist = jur_scene_rays_by_slice(nr, nslice, sid, sptr, srays);
+    for (long q = 0; q < nslice; q++)
+      if ((sptr[q + 1] - sptr[q]) * nd > 0x7fffffffL) {
+        jur_set_error("%s: 2^31 measurements of slice %ld: call with the rays of fewer slices at a time", who, q);
+        rc = JUR_EINVAL; goto done;
+      }
+    long const ntile = jur_param_maps(nslice, wptr, bw, NULL), ngroups = pptr[nslice];
+    if (ntile > 0x7fffffffL || ngroups > 0x7fffffffL) { jur_set_error("%s: 2^31 workgroups: call with fewer systems at a time", who); rc = JUR_EINVAL; goto done; }
+    if (ntile > 0) {
+      hmap = (int *)malloc(sizeof(int) * 3 * (size_t)ntile);
+      if (!hmap) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+      (void)jur_param_maps(nslice, wptr, bw, hmap);
+    }
+    size_t const nb = (size_t)wptr[nslice], nbw = (size_t)bw[nslice], nbb = (size_t)bbptr[nslice], NV = (size_t)in->nvar, NF = (size_t)in->ncov;
+    size_t const nlong = 6 * (NS + 1) + 2 * NR, o_g = nlong, o_kb = o_g + nk, o_we = o_kb + nkb, o_C = o_we + NRD, o_var = o_C + (size_t)nc,
+                 o_cov = o_var + NV * nbw, o_sig = o_cov + NF * nbb, o_int = o_sig + NC * nb;
+    hipStream_t s;
+    if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * (3 * (size_t)ntile + (size_t)nlist + 1), &s))) goto done;
+    double *const D = (double *)m->d_scene;
+    long *const L = (long *)m->d_scene;
+    int *const d_map = (int *)(D + o_int), *const d_srays = d_map + 3 * (size_t)ntile;
+    enqueued = 1;
+    hipError_t e = hipMemcpyAsync(L, ptr, sizeof(long) * nlong, hipMemcpyHostToDevice, s);
+    if (nk && e == hipSuccess) e = hipMemcpyAsync(D + o_g, gain, sizeof(double) * nk, hipMemcpyHostToDevice, s);
+    if (nkb && e == hipSuccess) e = hipMemcpyAsync(D + o_kb, kb, sizeof(double) * nkb, hipMemcpyHostToDevice, s);
+    if (NRD && e == hipSuccess) e = hipMemcpyAsync(D + o_we, weight_eff, sizeof(double) * NRD, hipMemcpyHostToDevice, s);
+    if (NV * nbw > 0 && e == hipSuccess) e = hipMemcpyAsync(D + o_var, in->var, sizeof(double) * NV * nbw, hipMemcpyHostToDevice, s);
+    if (NF * nbb > 0 && e == hipSuccess) e = hipMemcpyAsync(D + o_cov, in->cov, sizeof(double) * NF * nbb, hipMemcpyHostToDevice, s);
+    if (ntile && e == hipSuccess) e = hipMemcpyAsync(d_map, hmap, sizeof(int) * 3 * (size_t)ntile, hipMemcpyHostToDevice, s);
+    if (nlist && e == hipSuccess) e = hipMemcpyAsync(d_srays, srays, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    jur_scene_param_t q;
+    memset(&q, 0, sizeof q);
+    q.nslice = nslice; q.nd = nd; q.nvar = in->nvar; q.ncov = in->ncov;
+    q.wptr = L; q.bwptr = L + (NS + 1); q.cptr = L + 2 * (NS + 1); q.bbptr = L + 3 * (NS + 1); q.sptr = L + 4 * (NS + 1);
+    q.pptr = L + 5 * (NS + 1); q.koff = L + 6 * (NS + 1); q.koffb = q.koff + NR;
+    q.srays = d_srays; q.cmap = d_map; q.gain = D + o_g; q.kb = D + o_kb; q.weff = D + o_we; q.var = D + o_var; q.cov = D + o_cov;
+    q.nb = (long)nb; q.nbw = (long)nbw; q.nbb = (long)nbb; q.C = D + o_C; q.sig = D + o_sig;
+    int const ti = scene_timed_begin(m, s);
+    int const ek = jurk_scene_param(&q, ntile, ngroups, s);
+    scene_timed_end(m, ti, s);
+    if (ek) { jur_set_error("%s: kernel launch failed", who); rc = JUR_EHIP; goto done; }
+    if (nc && out->C) e = hipMemcpyAsync(out->C, q.C, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost, s);
+    if (NC * nb > 0 && e == hipSuccess) e = hipMemcpyAsync(out->sigma_param, q.sig, sizeof(double) * NC * nb, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
+  }
+done:
+  if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
+  free(ptr); free(srays); free(hmap);
   return rc;
 }
 

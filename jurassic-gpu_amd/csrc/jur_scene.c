@@ -607,6 +607,129 @@ int jur_error_components(int nd, long nr, double const *y, double const *err_noi
   return JUR_OK;
 }
 
+/* ---- parameter errors (jur_param_slices_host): the host arithmetic ---------------------------------------------------- */
+int jur_param_check_args(char const *who, jur_param_in_t const *in, jur_param_out_t const *out) {
+  if (!in || !out) { jur_set_error("%s: null argument (%s)", who, !in ? "in" : "out"); return JUR_EINVAL; }
+  if (in->nvar < 0 || in->ncov < 0 || (long)in->nvar + in->ncov > JUR_PARAM_MAXCOMP) {
+    jur_set_error("%s: nvar = %d, ncov = %d: 0 to %d components per call", who, in->nvar, in->ncov, JUR_PARAM_MAXCOMP);
+    return JUR_EINVAL;
+  }
+  if (in->nvar + in->ncov > 0 && !out->sigma_param) {
+    jur_set_error("%s: null argument (sigma_param) with nvar + ncov = %d", who, in->nvar + in->ncov);
+    return JUR_EINVAL;
+  }
+  return JUR_OK;
+}
+
+/* The width wb_s of a slice is that of its rays in rowptr_b, 0 without rays; the ray that fixed it is named with the one
+ * that disagrees. */
+long jur_param_layout_as(char const *who, long nslice, long const *wptr, long nr, long const *rowptr, long const *rowptr_b,
+                         int const *sid, long *bwptr, long *cptr, long *bbptr) {
+  if (nslice < 0 || nr < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  if ((nslice > 0 && !wptr) || !rowptr || !rowptr_b || (nr > 0 && !sid)) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  int rc = jur_diag_check_wptr(who, nslice, wptr);
+  if (rc) return rc;
+  if ((rc = jur_gain_check_layout(who, nslice, wptr, nr, rowptr, sid))) return rc;
+  if (rowptr_b[0] != 0) { jur_set_error("%s: rowptr_b does not start at 0", who); return JUR_EINVAL; }
+  size_t const NS = (size_t)nslice;
+  long *bw = (long *)malloc(sizeof(long) * 2 * (NS ? NS : 1)), *by = bw ? bw + NS : NULL;   /* the width of a slice, the ray that fixed it */
+  if (!bw) { jur_set_error("%s: out of memory", who); return JUR_ENOMEM; }
+  long total = JUR_EINVAL;
+  for (long q = 0; q < nslice; q++) { bw[q] = 0; by[q] = -1; }
+  for (long r = 0; r < nr; r++) {
+    long const wb = rowptr_b[r + 1] - rowptr_b[r];
+    if (wb < 0 || wb > 0x7fffffffL) { jur_set_error("%s: rowptr_b is not ascending at ray %ld", who, r); goto done; }
+    int const q = sid[r];
+    if (q < 0) continue;
+    if (by[q] < 0) { by[q] = r; bw[q] = wb; }
+    else if (bw[q] != wb) {
+      jur_set_error("%s: rays %ld and %ld of slice %d have %ld and %ld columns in rowptr_b", who, by[q], r, q, bw[q], wb);
+      goto done;
+    }
+  }
+  long nbw = 0, nc = 0, nbb = 0;
+  for (long q = 0; q <= nslice; q++) {
+    if (bwptr) bwptr[q] = nbw;
+    if (cptr) cptr[q] = nc;
+    if (bbptr) bbptr[q] = nbb;
+    if (q == nslice) break;
+    nbw += bw[q]; nc += (wptr[q + 1] - wptr[q]) * bw[q]; nbb += bw[q] * bw[q];
+  }
+  total = nc;
+done:
+  free(bw);
+  return total;
+}
+
+long jur_param_layout(long nslice, long const *wptr, long nr, long const *rowptr, long const *rowptr_b, int const *sid,
+                      long *bwptr, long *cptr, long *bbptr) {
+  return jur_param_layout_as("jur_param_layout", nslice, wptr, nr, rowptr, rowptr_b, sid, bwptr, cptr, bbptr);
+}
+
+void jur_param_abi_sizes(size_t out[2]) { out[0] = sizeof(jur_param_in_t); out[1] = sizeof(jur_param_out_t); }
+
+/* bw: the running sum the layout made from rowptr_b */
+int jur_param_check_bwptr(char const *who, long nslice, long const *bwptr, long const *bw) {
+  for (long q = 0; q < nslice; q++) {
+    long const wb = bwptr[q + 1] - bwptr[q];
+    if (bwptr[0] != 0 || wb < 0 || wb > 0x7fffffffL) {
+      jur_set_error("%s: bwptr is not an ascending running sum of widths from 0 (slice %ld)", who, q);
+      return JUR_EINVAL;
+    }
+    if (wb != bw[q + 1] - bw[q]) {
+      jur_set_error("%s: bwptr gives slice %ld %ld columns, its rays have %ld in rowptr_b", who, q, wb, bw[q + 1] - bw[q]);
+      return JUR_EINVAL;
+    }
+  }
+  return JUR_OK;
+}
+
+int jur_param_check_values(char const *who, long nslice, long const *bwptr, long const *bbptr, jur_param_in_t const *in) {
+  size_t const nbw = (size_t)bwptr[nslice], nbb = (size_t)bbptr[nslice];
+  if ((in->nvar > 0 && nbw > 0 && !in->var) || (in->ncov > 0 && nbb > 0 && !in->cov)) {
+    jur_set_error("%s: null argument (%s)", who, (in->nvar > 0 && nbw > 0 && !in->var) ? "var" : "cov");
+    return JUR_EINVAL;
+  }
+  for (int c = 0; c < in->nvar; c++)
+    for (long q = 0; q < nslice; q++)
+      for (long j = bwptr[q]; j < bwptr[q + 1]; j++) {
+        double const v = in->var[(size_t)c * nbw + (size_t)j];
+        if (!(v >= 0) || !(v - v == 0)) {
+          jur_set_error("%s: the variance of component %d, slice %ld, element %ld is %g: negative or not finite", who, c, q, j - bwptr[q], v);
+          return JUR_EINVAL;
+        }
+      }
+  for (int c = 0; c < in->ncov; c++)
+    for (long q = 0; q < nslice; q++) {
+      long const wb = bwptr[q + 1] - bwptr[q];
+      double const *const sg = in->cov + (size_t)c * nbb + (size_t)bbptr[q];
+      for (long j = 0; j < wb; j++)
+        for (long l = 0; l <= j; l++) {
+          double const v = sg[j * wb + l];
+          if (!(v - v == 0)) {
+            jur_set_error("%s: cov of component %d, slice %ld, element (%ld, %ld) is %g: not finite", who, in->nvar + c, q, j, l, v);
+            return JUR_EINVAL;
+          }
+          if (l == j && !(v >= 0)) {
+            jur_set_error("%s: the diagonal of cov of component %d, slice %ld, element %ld is %g: negative", who, in->nvar + c, q, j, v);
+            return JUR_EINVAL;
+          }
+        }
+    }
+  return JUR_OK;
+}
+
+long jur_param_maps(long nslice, long const *wptr, long const *bwptr, int *cmap) {
+  long nt = 0;
+  for (long q = 0; q < nslice; q++) {
+    long const w = wptr[q + 1] - wptr[q], wb = bwptr[q + 1] - bwptr[q];
+    for (long i0 = 0; i0 < w; i0 += JUR_PARAM_TILE)
+      for (long j0 = 0; j0 < wb; j0 += JUR_PARAM_TILE, nt++)
+        if (cmap) { cmap[3 * nt] = (int)q; cmap[3 * nt + 1] = (int)i0; cmap[3 * nt + 2] = (int)j0; }
+  }
+  return nt;
+}
+
 int jur_avk_summary(ctl_t const *ctl, atm_t const *atm, int first, int len, double const *avk, double *dofs_q, double *area,
                     double *resolution) {
   if (!ctl || !atm || first < 0 || len < 0 || (long)first + len > atm->np) {

@@ -184,6 +184,15 @@ def lib():
             L.jur_gain_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
                                               dp, dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, dp, dp, dp, lp_, dp, C.c_long]
             L.jur_error_components.argtypes = [C.c_int, C.c_long, dp, dp, dp, dp, dp]
+        if hasattr(L, "jur_param_slices_host"):      # (an A/B library from before the parameter errors has none of these)
+            L.jur_param_slices_host.argtypes = [C.c_void_p, C.c_long, lp_, lp_, C.c_long, C.c_int, lp_, lp_, ip_, dp, dp, dp,
+                                                C.c_void_p, C.c_void_p]
+            L.jur_param_layout.restype = C.c_long
+            L.jur_param_layout.argtypes = [C.c_long, lp_, C.c_long, lp_, lp_, ip_, lp_, lp_, lp_]
+            L.jur_param_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
+            L.jur_param_abi_sizes.restype = None
+            L.jur_model_set_ret_windows.argtypes = [C.c_void_p, C.c_void_p]
+            L.jur_model_ret_windows.argtypes = [C.c_void_p, C.c_void_p]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -544,7 +553,8 @@ class Model:
         k[rowptr[r] * nd : rowptr[r + 1] * nd].reshape(nd, width[r]), its columns those of scene_columns(first[r],
         len[r]).  rowptr: pass one to have it checked instead of the layout's own.
         The layout is made with the ctl_t the Model was created with, of which the model keeps a copy of its own: change
-        that ctl_t afterwards (retrieval windows, say) and the call is refused with EINVAL (rowptr) -- make a new Model."""
+        that ctl_t afterwards (retrieval windows, say) and the call is refused with EINVAL (rowptr) -- make a new Model,
+        or give the model other windows with set_ret_windows."""
         g = np.ascontiguousarray(np.asarray(geom, dtype=np.float64).T)
         nr, nd = g.shape[1], self.nd
         lay = _scene_layout(self.ctl, atm, g[0] if nr else np.zeros(0))
@@ -906,6 +916,62 @@ class Model:
             out["k"] = k
         return out
 
+    def param_slices(self, wptr, rowptr, rowptr_b, sid, gain, kb, weight_eff, var=None, cov=None, want_C=True):
+        """Cross-state matrix and parameter-error budget of gains and parameter blocks the caller holds
+        (jur_param_slices_host).  wptr, rowptr, sid, gain, weight_eff: what gain_slices takes and returns; kb, rowptr_b:
+        the flat blocks and the rowptr of kernel_scene on the same rays under other retrieval windows; var (nvar, nbw) or
+        None: diagonal parameter covariances, laid out by bwptr; cov (ncov, nbb) or None: full ones, Sigma_s flat at
+        bbptr[s] as (wb_s, wb_s), its diagonal and lower triangle read.
+        -> dict(C: flat, C_s at cptr[s] as (w_s, wb_s) (with want_C); sigma_param (nvar + ncov, n), the var components
+        first; bwptr, cptr, bbptr of param_layout)."""
+        wp = np.ascontiguousarray(wptr, dtype=np.int64)
+        rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+        rb = np.ascontiguousarray(rowptr_b, dtype=np.int64)
+        sd = np.ascontiguousarray(sid, dtype=np.int32)
+        ns, nr, n = len(wp) - 1, len(rp) - 1, int(wp[-1])
+        ww = np.ascontiguousarray(weight_eff, dtype=np.float64)
+        if ww.ndim != 2 or ww.shape[0] != nr or sd.shape != (nr,) or rb.shape != rp.shape:
+            raise ValueError("weight_eff must be (%d, nd), sid (%d,) and rowptr_b (%d,)" % (nr, nr, nr + 1))
+        nd = ww.shape[1]
+        lay = param_layout(wp, rp, rb, sd)
+        gg, kk = (np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (gain, kb))
+        if gg.size != int(rp[-1]) * nd or kk.size != int(rb[-1]) * nd:
+            raise ValueError("gain must hold %d doubles and kb %d" % (int(rp[-1]) * nd, int(rb[-1]) * nd))
+        nbw, nbb, nc = int(lay["bwptr"][-1]), int(lay["bbptr"][-1]), int(lay["cptr"][-1])
+        vv = None if var is None else np.ascontiguousarray(var, dtype=np.float64)
+        cc = None if cov is None else np.ascontiguousarray(cov, dtype=np.float64)
+        if vv is not None and (vv.ndim != 2 or vv.shape[1] != nbw):
+            raise ValueError("var must be (nvar, %d)" % nbw)
+        if cc is not None and (cc.ndim != 2 or cc.shape[1] != nbb):
+            raise ValueError("cov must be (ncov, %d)" % nbb)
+        nvar, ncov = 0 if vv is None else vv.shape[0], 0 if cc is None else cc.shape[0]
+        res = dict(lay, sigma_param=np.zeros((nvar + ncov, n)))
+        if want_C:
+            res["C"] = np.zeros(nc)
+        pin = ParamIn(nvar, ncov, _p(vv) if nvar else None, _p(cc) if ncov else None)
+        pout = ParamOut(_p(res["C"]) if want_C else None, _p(res["sigma_param"]) if nvar + ncov else None)
+        ip_, lp_ = C.POINTER(C.c_int), C.POINTER(C.c_long)
+        _chk(lib().jur_param_slices_host(self.h, ns, wp.ctypes.data_as(lp_), lay["bwptr"].ctypes.data_as(lp_), nr, nd,
+                                         rp.ctypes.data_as(lp_), rb.ctypes.data_as(lp_), sd.ctypes.data_as(ip_), _p(gg), _p(kk),
+                                         _p(ww), C.byref(pin), C.byref(pout)))
+        return res
+
+    def set_ret_windows(self, ctl):
+        """The retrieval windows of ctl (retp, rett, retq[ng], retk[nw] _zmin/_zmax, nothing else) become the model's
+        (jur_model_set_ret_windows): from the next call on kernel_scene and the other scene entries, kernel and
+        state_size derive their state from them.  No device work.  The layouts made on the Python side follow: the Model
+        then holds a ctl_t of its own, the one it was created with plus these windows."""
+        _chk(lib().jur_model_set_ret_windows(self.h, C.byref(ctl)))
+        self.ctl = self.ret_windows(base=self.ctl)
+
+    def ret_windows(self, base=None):
+        """The retrieval windows that are set (jur_model_ret_windows) -> a new ctl_t: a copy of base (default: the ctl_t
+        the Model lays its blocks out with) with the model's windows written into it."""
+        out = abi.ctl_t()
+        C.memmove(C.byref(out), C.byref(self.ctl if base is None else base), C.sizeof(abi.ctl_t))
+        _chk(lib().jur_model_ret_windows(self.h, C.byref(out)))
+        return out
+
     def scene_ms(self):
         """The share of kernel_scene's own kernels in the launches timed since the last call (call kernel_ms first)."""
         ms, n = C.c_double(0), C.c_long(0)
@@ -1017,6 +1083,16 @@ class GainIn(C.Structure):
 class GainOut(C.Structure):
     """jur_gain_out_t"""
     _fields_ = [("gain", dp), ("sigma_comp", dp)]
+
+
+class ParamIn(C.Structure):
+    """jur_param_in_t"""
+    _fields_ = [("nvar", C.c_int), ("ncov", C.c_int), ("var", dp), ("cov", dp)]
+
+
+class ParamOut(C.Structure):
+    """jur_param_out_t"""
+    _fields_ = [("C", dp), ("sigma_param", dp)]
 
 
 RET_ACTIVE, RET_CONVERGED, RET_STALLED, RET_MAXITER = 0, 1, 2, 3      # JUR_RET_*
@@ -1164,6 +1240,59 @@ def error_components(y, err_noise, err_formod):
     var, weight = np.zeros((2, nr, nd)), np.zeros((nr, nd))
     _chk(lib().jur_error_components(nd, nr, _p(yy), _p(en), _p(ef), _p(var), _p(weight)))
     return var, weight
+
+
+def param_layout(wptr, rowptr, rowptr_b, sid):
+    """jur_param_layout (host arithmetic, no GPU): the layout of param_slices' arrays.  wptr (nslice + 1,), rowptr (nr + 1,)
+    and sid (nr,) of the retrieved state, rowptr_b (nr + 1,) of the parameter blocks on the same rays -> dict(bwptr, cptr,
+    bbptr (nslice + 1,)): the running sums of wb_s, the width in rowptr_b of the rays of slice s (0 without rays), of
+    w_s * wb_s and of wb_s^2.  Raises JurassicError where the widths do not fit together."""
+    wp, rp, rb = (np.ascontiguousarray(x, dtype=np.int64).ravel() for x in (wptr, rowptr, rowptr_b))
+    sd = np.ascontiguousarray(sid, dtype=np.int32).ravel()
+    ns, nr = len(wp) - 1, len(rp) - 1
+    if ns < 0 or nr < 0 or len(rb) != nr + 1 or len(sd) != nr:
+        raise ValueError("rowptr and rowptr_b must hold one entry more than sid, and wptr one at least")
+    ip_, lp_ = C.POINTER(C.c_int), C.POINTER(C.c_long)
+    bw, cp, bb = (np.zeros(ns + 1, dtype=np.int64) for _ in range(3))
+    _chk(lib().jur_param_layout(ns, wp.ctypes.data_as(lp_), nr, rp.ctypes.data_as(lp_), rb.ctypes.data_as(lp_),
+                                sd.ctypes.data_as(ip_), bw.ctypes.data_as(lp_), cp.ctypes.data_as(lp_), bb.ctypes.data_as(lp_)))
+    return dict(bwptr=bw, cptr=cp, bbptr=bb)
+
+
+def param_error_scene(model, ctl_b, atm, geom, y, weight, var_b=None, cov_b=None, prior_ivar=None, rad_in=None,
+                      max_rays_per_pass=0):
+    """The error that quantities b which are not retrieved leave in the retrieved state of a scene, with one model:
+    gain_scene(want_gain=True) under the model's own retrieval windows, the effective weights by that entry's liveness
+    rule (with a field of view set: scene_fov_live), kernel_scene under the windows of ctl_b for K_b -- the model's own
+    are put back afterwards, after an error too -- and param_slices.  var_b (nvar, bwptr[-1]) / cov_b (ncov, bbptr[-1]):
+    the covariances of b, laid out over elements_b; prior_corr_slices(model, bwptr, iq, z, sigma, cz, want_Sa=True)["Sa"]
+    is one cov_b row.
+    -> gain_scene's dict (with gain), plus C, cptr, bwptr, bbptr, sigma_param of param_slices, rowptr_b, weight_eff and
+    elements_b: per slice scene_elements(ctl_b, atm, sfirst[s], slen[s]), the parameters the columns of C_s stand for."""
+    out = model.gain_scene(atm, geom, y, weight, prior_ivar=prior_ivar, want_gain=True, rad_in=rad_in,
+                           max_rays_per_pass=max_rays_per_pass)
+    g = np.asarray(geom, dtype=np.float64)
+    yy, ww = (np.asarray(x, dtype=np.float64) for x in (y, weight))
+    if rad_in is None:
+        seen = np.ones(yy.shape, dtype=bool)
+    elif model.fov() is not None:
+        seen = scene_fov_live(g[:, 0], rad_in)
+    else:
+        seen = np.isfinite(np.asarray(rad_in, dtype=np.float64))
+    live = seen & np.isfinite(out["rad"]) & np.isfinite(yy) & (ww > 0) & (out["sid"] >= 0)[:, None]
+    weff = np.where(live, ww, 0.0)
+    own = model.ret_windows()
+    model.set_ret_windows(ctl_b)
+    try:
+        kb = model.kernel_scene(atm, geom, rad_in=rad_in, max_rays_per_pass=max_rays_per_pass)
+    finally:
+        model.set_ret_windows(own)
+    res = model.param_slices(out["wptr"], out["rowptr"], kb["rowptr"], out["sid"], out["gain"], kb["k"], weff, var=var_b,
+                             cov=cov_b)
+    out.update(res)
+    out.update(rowptr_b=kb["rowptr"], weight_eff=weff,
+               elements_b=[scene_elements(ctl_b, atm, int(f), int(l)) for f, l in zip(out["sfirst"], out["slen"])])
+    return out
 
 
 def avk_summary(ctl, atm, first, length, avk):
