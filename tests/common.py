@@ -12,6 +12,16 @@ LIMB_NU = [792.0, 832.0]
 NADIR_EMITTERS = ["CO2"]
 NADIR_NU = [667.782, 668.541, 669.811]
 CTM4_NU = [792.0, 832.0, 1450.0, 2150.0]     # keeps all four continua switched on
+ND3_NU = [792.0, 832.0, 1450.0]
+ND7_NU = [650.0, 792.0, 832.0, 1100.0, 1450.0, 2150.0, 2450.0]   # CO2 band, the two windows, O2 and N2 continua
+# Channel configurations on the limb emitters, name -> keywords of limb_case: the smallest count (1), the smallest odd
+# one (3: chunks of 8 / 64 / 256 measurements straddle rays), the same in brightness temperatures, a count coprime to
+# every chunk size (7) and one that exceeds a chunk of 64 (65, on small tables so that a case stays quick)
+CHANNELS = {"nd1": dict(nu=[792.0]),
+            "nd3": dict(nu=ND3_NU),
+            "nd3bbt": dict(nu=ND3_NU, write_bbt=1),
+            "nd7": dict(nu=ND7_NU),
+            "nd65": dict(nu=[650.0 + 28.125 * i for i in range(65)], table_kw=dict(nlev=5, ntemp=3))}
 
 
 class Case:

@@ -90,13 +90,16 @@ def _builders():
 FORMOD = _builders()
 SCENE_CASES = [n for n in FORMOD if n.startswith("scene_")]
 # (extinction: the retk columns, 10 .. 20 km, perturb the non-zero values of common.extinction_profile)
-JACOBIANS = {"jacobian": dict(), "jacobian_hydz10": dict(hydz=10.0), "jacobian_extinction": dict(extinction=True)}
+# (nd3_bbt: three channels in brightness temperatures -- the epilogue's log1p inside every difference quotient)
+JACOBIANS = {"jacobian": dict(), "jacobian_hydz10": dict(hydz=10.0), "jacobian_extinction": dict(extinction=True),
+             "jacobian_nd3_bbt": dict(channels="nd3bbt")}
 
 
 def jacobian_case(name):
     """-> (case, obs with one measurement masked) as test_jacobian_matches_reference_kernel."""
     kw = dict(JACOBIANS[name])
     extinction = kw.pop("extinction", False)
+    kw.update(common.CHANNELS[kw.pop("channels")] if "channels" in kw else {})
     case = common.retrieval_case(**kw)
     if extinction:
         common.extinction_profile(case.atm)
@@ -184,7 +187,8 @@ def pack(res):
 
 
 def store(name, arr):
-    """One .npy per case; a Jacobian (131 x 69 doubles = 72 KB) goes in two halves of its rows, each under 64 KB."""
+    """One .npy per case; a Jacobian (131 x 69 doubles = 72 KB, 197 x 69 = 109 KB with three channels) goes in two halves
+    of its rows, each under 64 KB."""
     parts = {name: arr} if name not in JACOBIANS else {name + ".rows_a": arr[:len(arr) // 2], name + ".rows_b": arr[len(arr) // 2:]}
     for k, a in parts.items():
         np.save(os.path.join(STORE, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))

@@ -710,27 +710,30 @@ _retrieval_case = common.retrieval_case
 
 
 @pytest.mark.parametrize("arith", ["fast", "exact"])
-@pytest.mark.parametrize("kw", [dict(), dict(hydz=10.0), dict(extinction=True)])
+@pytest.mark.parametrize("kw", [dict(), dict(hydz=10.0), dict(extinction=True)]
+                         + [pytest.param(dict(channels=c), id=c) for c in ("nd1", "nd3bbt", "nd7")])
 def test_jacobian_matches_reference_kernel(hip, oracle, kw, arith):
     """jur_kernel (one batched call over n+1 stacked atmospheres) against the restated
     kernel() loop of n+1 formod calls (jurassic.c:812-857), under both arithmetics of the look-up
     (jur_model_set_arithmetic).  Columns are difference quotients (y1-y0)/h: compared relative to the largest entry of
-    each column."""
+    each column.  channels: one of common.CHANNELS instead of the example's two radiance channels."""
     kw = dict(kw)
     extinction = kw.pop("extinction", False)
+    kw.update(common.CHANNELS[kw.pop("channels")] if "channels" in kw else {})
     case = _retrieval_case(**kw)
     if extinction:                                        # the retk columns (10 .. 20 km) perturb non-zero values
         common.extinction_profile(case.atm)
-    obs_ref = _obs_from_geom(case.geom, 2)
-    obs = _obs_from_geom(case.geom, 2)
+    nd = case.ctl.nd
+    obs_ref = _obs_from_geom(case.geom, nd)
+    obs = _obs_from_geom(case.geom, nd)
     for o in (obs_ref, obs):
-        o.rad[5][1] = float("nan")                        # a masked measurement drops its row
+        o.rad[5][min(1, nd - 1)] = float("nan")           # a masked measurement drops its row
     k_ref = oracle.kernel(case.ctl, case.atm, obs_ref, case.oracle_tables(oracle))
     model = hip.Model(case.ctl, case.lib_tables())
     model.set_arithmetic(hip.ARITH_EXACT if arith == "exact" else hip.ARITH_FAST)
     model.set_atm(case.atm)
     k = model.kernel(case.atm, obs)
-    assert k.shape == k_ref.shape == (66 * 2 - 1, 6 + 31 + 21 + 11)
+    assert len(case.geom) == 66 and k.shape == k_ref.shape == (66 * nd - 1, 6 + 31 + 21 + 11)
     scale = np.abs(k_ref).max(axis=0)
     live = scale > 0          # with HYDZ >= 0 the pressure columns away from the reference level vanish
     assert live.sum() >= 31 + 21 + 11 and np.all(k[:, ~live] == 0)
@@ -738,7 +741,7 @@ def test_jacobian_matches_reference_kernel(hip, oracle, kw, arith):
     if extinction:
         assert np.all(live[-11:]) and np.all(np.abs(k[:, -11:]).max(axis=0) > 0)      # the extinction columns are live
     n = obs.nr
-    a, b = np.ctypeslib.as_array(obs.rad)[:n, :2], np.ctypeslib.as_array(obs_ref.rad)[:n, :2]
+    a, b = np.ctypeslib.as_array(obs.rad)[:n, :nd], np.ctypeslib.as_array(obs_ref.rad)[:n, :nd]
     fin = np.isfinite(b)
     assert np.array_equal(fin, np.isfinite(a)) and common.rel_err(a[fin], b[fin]).max() < RTOL
     # the model is left with the caller's atmosphere

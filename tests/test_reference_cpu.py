@@ -140,7 +140,7 @@ def jacobian_pair(name, oracle, d):
     case.write_files(d)
     obs_o = abi.obs_t.from_buffer_copy(bytes(obs))
     k = oracle.kernel(case.ctl, case.atm, obs_o, R.oracle_tables(oracle, case))
-    assert k.shape == (66 * 2 - 1, 6 + 31 + 21 + 11)
+    assert len(case.geom) == 66 and k.shape == (66 * case.ctl.nd - 1, 6 + 31 + 21 + 11)
     return case, obs, obs_o, k
 
 

@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 import sequences
 from jurassic_hip import synth
-from test_scene_jacobian_gpu import bits, formod_on, fresh_formod, scene_case
+import common
+from test_scene_jacobian_gpu import bits, channels_of, formod_on, fresh_formod, scene_case
 from test_scene_normal_gpu import U, bumped, copy_atm, slice_of, sums_in_longdouble
 from test_scene_retrieve_gpu import elements, prior_chain, rows_of, slice_mask, state_of, written_back
 
@@ -89,14 +90,16 @@ def scan_geometry(case):
 _scene = {}
 
 
-def scene(hip):
-    """(case, geom, y, weight, lay, iq, ip, x0), made once: y the convolved forward model on the bumped atmosphere"""
-    if not _scene:
-        case = scene_case("ragged", windows=windows)
+def scene(hip, name="ragged"):
+    """(case, geom, y, weight, lay, iq, ip, x0), made once per name (`ragged`, or `ragged@channels` on one of
+    common.CHANNELS): y the convolved forward model on the bumped atmosphere"""
+    if name not in _scene:
+        assert channels_of(name)[0] == "ragged"
+        case = scene_case(name, windows=windows)
         geom = scan_geometry(case)
-        _scene["v"] = scene_of(hip, case, geom)
-        assert np.diff(_scene["v"][4]["wptr"]).max() <= 48
-    return _scene["v"]
+        _scene[name] = scene_of(hip, case, geom)
+        assert np.diff(_scene[name][4]["wptr"]).max() <= 48
+    return _scene[name]
 
 
 def scene_of(hip, case, geom, shape=None):
@@ -139,9 +142,9 @@ def with_shape(hip, case):
 
 
 def masked_input(lay, shape):
-    """rad_in with a NaN on the seventh ray of the first scan, channel 1"""
+    """rad_in with a NaN on the seventh ray of the first scan, in the last channel"""
     rad_in = np.zeros(shape)
-    rad_in[6, 1] = np.nan
+    rad_in[6, shape[1] - 1] = np.nan
     assert lay["sid"][6] >= 0
     return rad_in
 
@@ -149,21 +152,21 @@ def masked_input(lay, shape):
 _normal = {}
 
 
-def normal_with_mask(hip):
-    """normal_scene(want_k=True) with the shape set and masked_input, once"""
-    if not _normal:
-        case, geom, y, weight, lay = scene(hip)[:5]
+def normal_with_mask(hip, name="ragged"):
+    """normal_scene(want_k=True) with the shape set and masked_input, once per name"""
+    if name not in _normal:
+        case, geom, y, weight, lay = scene(hip, name)[:5]
         model = with_shape(hip, case)
         try:
-            _normal["v"] = model.normal_scene(case.atm, geom, y, weight, rad_in=masked_input(lay, y.shape), want_k=True)
+            _normal[name] = model.normal_scene(case.atm, geom, y, weight, rad_in=masked_input(lay, y.shape), want_k=True)
         finally:
             model.close()
-    return _normal["v"]
+    return _normal[name]
 
 
-def seeded_prior(hip):
-    case, geom, y, weight, lay, iq, ip, x0 = scene(hip)
-    out = normal_with_mask(hip)
+def seeded_prior(hip, name="ragged"):
+    case, geom, y, weight, lay, iq, ip, x0 = scene(hip, name)
+    out = normal_with_mask(hip, name)
     rng = np.random.default_rng(3)
     r = [10.0 ** rng.uniform(-3.0, -1.0, len(np.diag(slice_of(out, s)[0]))) * np.diag(slice_of(out, s)[0]).mean()
          for s in range(len(lay["sfirst"]))]
@@ -180,9 +183,10 @@ def step_of(iq, x):
     return max(abs(0.01 * x), 1e-15) if iq < 2 + 5 else 1e-4
 
 
-def test_kernel_scene_against_the_host_replay(hip):
-    case, geom, y, weight, lay, iq, ip, x0 = scene(hip)
-    assert case.ctl.ng == 5 and case.ctl.nd == 2
+def test_kernel_scene_against_the_host_replay(hip, name="ragged"):
+    case, geom, y, weight, lay, iq, ip, x0 = scene(hip, name)
+    channels = channels_of(name)[1]
+    assert case.ctl.ng == 5 and case.ctl.nd == (len(common.CHANNELS[channels]["nu"]) if channels else 2)
     nd = case.ctl.nd
     model = with_shape(hip, case)
     try:
@@ -227,13 +231,13 @@ def test_kernel_scene_against_the_host_replay(hip):
         plain.close()
 
 
-def test_a_long_shape_and_wide_slices(hip):
+def test_a_long_shape_and_wide_slices(hip, name="ragged"):
     """A shape of 150 points is staged 64 points at a time, and a slice of 150 elements gives a ray 302 values, more than
     the 256 lanes of its workgroup take at once: rad and tau, and the blocks of the first, the middle and the last
     element of every slice, against the host replay; the sums in passes of a scan against the default."""
     rng = np.random.default_rng(8)
     shape = (rng.uniform(-2.0, 2.0, 150), rng.uniform(0.0, 1.0, 150))
-    case = scene_case("ragged", windows=wide_windows)
+    case = scene_case(name, windows=wide_windows)
     case, geom, y, weight, lay, iq, ip, x0 = scene_of(hip, case, scan_geometry(case), shape)
     nd = case.ctl.nd
     assert (np.diff(lay["rowptr"]).max() + 1) * nd > 256 and np.all(iq == 1)
@@ -271,17 +275,18 @@ def test_a_long_shape_and_wide_slices(hip):
 
 
 # ---- 2. the sums against the blocks -------------------------------------------------------------------------------------
-def test_normal_scene_against_its_blocks(hip):
-    case, geom, y, weight, lay = scene(hip)[:5]
-    out = normal_with_mask(hip)
+def test_normal_scene_against_its_blocks(hip, name="ragged"):
+    case, geom, y, weight, lay = scene(hip, name)[:5]
+    out = normal_with_mask(hip, name)
     rad_in = masked_input(lay, y.shape)
     live = hip.scene_fov_live(geom[:, 0], rad_in)
-    # the ray, five before it and five after it in its scan of 13, in channel 1 alone
-    assert live[:, 0].all() and np.array_equal(np.flatnonzero(~live[:, 1]), np.arange(1, 12))
+    last = y.shape[1] - 1
+    # the ray, five before it and five after it in its scan of 13, in the last channel alone
+    assert live[:, :last].all() and np.array_equal(np.flatnonzero(~live[:, last]), np.arange(1, 12))
     host = convolved(hip, case, case.atm, geom, rad_in)
     bits(out["rad"], host["rad"], "rad: the NaN spreads where fov_apply spreads it")
     bits(out["tau"], host["tau"], "tau")
-    assert np.isnan(out["rad"][:, 1]).sum() >= 2 and not np.isnan(out["rad"][:, 0]).any()
+    assert np.isnan(out["rad"][:, last]).sum() >= 2 and not np.isnan(out["rad"][:, :last]).any()
     assert not np.any(live & np.isnan(out["rad"])), "the effective mask covers every NaN of G"
     ref = sums_in_longdouble(out, out["k"], y, weight, live)
     worst = 0.0
@@ -298,7 +303,7 @@ def test_normal_scene_against_its_blocks(hip):
             worst = max(worst, float(np.max(err / np.maximum(bound, np.finfo(np.longdouble).tiny))))
             assert np.all(err <= bound), (s, float(err.max()), float(np.max(bound)))
         assert np.abs(A).max() > 0 and np.abs(b).max() > 0 and out["cost"][s] > 0
-    print("FOV NORMAL: worst error / allowed %.3f" % worst)
+    print("FOV NORMAL %s: worst error / allowed %.3f" % (name, worst))
     s0 = out["sid"][6]
     assert out["nlive"][s0] == (out["sid"] == s0).sum() * case.ctl.nd - 11
     model = with_shape(hip, case)
@@ -328,8 +333,8 @@ def test_the_convolved_forward_model_of_the_truth_costs_nothing(hip):
 
 
 # ---- 4. the trial entry -------------------------------------------------------------------------------------------------
-def test_trial_costs_are_normal_scene_on_the_written_back_atmosphere(hip):
-    case, geom, y, weight, lay, iq, ip, x0 = scene(hip)
+def test_trial_costs_are_normal_scene_on_the_written_back_atmosphere(hip, name="ragged"):
+    case, geom, y, weight, lay, iq, ip, x0 = scene(hip, name)
     ns = len(lay["sfirst"])
     rad_in = masked_input(lay, y.shape)
     model = with_shape(hip, case)

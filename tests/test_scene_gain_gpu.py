@@ -324,16 +324,17 @@ def components(hip, y):
     return hip.error_components(y, np.full(y.shape[1], 1e-5), np.full(y.shape[1], 1.0))[0]
 
 
-def test_scene_entry_against_its_pieces(hip):
-    case, geom, y, weight = inputs(hip, "ragged")
-    _, clear = blocks_and_sums(hip, "ragged")
+def test_scene_entry_against_its_pieces(hip, name="ragged"):
+    case, geom, y, weight = inputs(hip, name)
+    _, clear = blocks_and_sums(hip, name)
     nr, nd = y.shape
+    last = nd - 1
     live, dead = np.flatnonzero(clear["sid"] >= 0), np.flatnonzero(clear["sid"] < 0)
     assert len(dead) > 0                                            # rays without a slice
     rad_in = np.zeros((nr, nd))
     rad_in[live[1], 0] = rad_in[dead[0], 0] = np.nan                # a masked channel
     w2 = weight.copy()
-    w2[live[5], 1] = 0.0                                            # a zero weight
+    w2[live[5], last] = 0.0                                         # a zero weight, in the last channel
     var = components(hip, y)
     var[:, live[1], 0] = np.nan                                     # not live: never read
     want = fresh_formod(hip, case, case.atm, case.geom)
@@ -348,7 +349,7 @@ def test_scene_entry_against_its_pieces(hip):
         assert np.all(diag["status"] == 0) and np.all(np.isfinite(full["gain"]))
         assert np.all(full["sigma_comp"] >= 0) and full["sigma_comp"].max() > 0
         rp = diag["rowptr"]
-        for r, i in ((live[1], 0), (live[5], 1)):
+        for r, i in ((live[1], 0), (live[5], last)):
             w = int(rp[r + 1] - rp[r])
             assert w > 0 and is_plus_zero(full["gain"][rp[r] * nd + i * w:rp[r] * nd + (i + 1) * w])
         assert np.all(np.isnan(diag["k"][rp[live[1]] * nd:rp[live[1]] * nd + int(rp[live[1] + 1] - rp[live[1]])]))
@@ -358,7 +359,7 @@ def test_scene_entry_against_its_pieces(hip):
         worst = {}
         for s in range(ns):
             check_slice(p, full, s, worst)
-        report("scene ragged", worst)
+        report("scene %s" % name, worst)
     finally:
         model.close()
 

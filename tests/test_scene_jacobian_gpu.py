@@ -34,16 +34,48 @@ def retrieval_windows(c):
     c.retk_zmin[0], c.retk_zmax[0] = 10.0, 20.0
 
 
+def narrow_windows(c):
+    """T and one gas over a few kilometres: what keeps a case of many channels quick"""
+    c.rett_zmin, c.rett_zmax = 10.0, 30.0
+    for g in range(c.ng):
+        c.retq_zmin[g], c.retq_zmax[g] = -999.0, -999.0
+    c.retq_zmin[2], c.retq_zmax[2] = 18.0, 24.0
+
+
+# what a channel configuration changes besides the channels: nd65 takes five rays per time stamp and narrow_windows
+# in place of retrieval_windows (the widest slice of `ragged` then has 42 elements, that of `lone_ends` 19, and the
+# rays and columns of either scene still exceed a pass of 257)
+REDUCED = {"nd65": dict(per_time_stamp=5, windows=narrow_windows)}
+
+
+def channels_of(name):
+    """'ragged@nd3' -> ('ragged', 'nd3'): a scene's name may carry one of common.CHANNELS; 'ragged' -> ('ragged', '')"""
+    base, _, channels = name.partition("@")
+    return base, channels
+
+
 def scene_case(name, nrays=180, windows=retrieval_windows):
-    case = common.limb_case()
-    case.atm, case.geom, _ = synth.scene(name, case.ctl, case.atm, nrays=nrays)
+    """The named scene of synth.SCENES on the limb example's two channels, or, as 'name@channels', on one of
+    common.CHANNELS: every helper and cache keyed by the name carries the configuration with it."""
+    base, channels = channels_of(name)
+    reduced = REDUCED.get(channels, {})
+    case = common.limb_case(**common.CHANNELS[channels]) if channels else common.limb_case()
+    case.atm, case.geom, _ = synth.scene(base, case.ctl, case.atm, nrays=nrays)
+    if "per_time_stamp" in reduced:
+        case.geom = per_time_stamp(case.geom, reduced["per_time_stamp"])
+    if windows is retrieval_windows:
+        windows = reduced.get("windows", windows)
     if windows:
         windows(case.ctl)
     return case
 
 
+def per_time_stamp(geom, n):
+    return np.vstack([geom[geom[:, 0] == t][:n] for t in np.unique(geom[:, 0])])
+
+
 def six_per_time_stamp(geom):
-    return np.vstack([geom[geom[:, 0] == t][:6] for t in np.unique(geom[:, 0])])
+    return per_time_stamp(geom, 6)
 
 
 def obs_result(obs, nd):
@@ -175,13 +207,13 @@ def test_beyond_one_package(hip):
         model.close()
 
 
-def test_nan_mask(hip):
-    case, geom, _, _, clear = dense_and_blocks(hip, "ragged", "fast")
+def test_nan_mask(hip, name="ragged"):
+    case, geom, _, _, clear = dense_and_blocks(hip, name, "fast")
     nd, nr = case.ctl.nd, len(geom)
     rad_in = np.zeros((nr, nd))
     live = np.flatnonzero(np.diff(clear["rowptr"]))                  # two masked rays that have a block, one that has none
-    assert np.diff(clear["rowptr"])[nr - 1] == 0
-    rad_in[live[1], 0] = rad_in[live[7], 1] = rad_in[nr - 1, 0] = np.nan
+    assert np.diff(clear["rowptr"])[nr - 1] == 0                     # (the first channel, the last, the first)
+    rad_in[live[1], 0] = rad_in[live[7], nd - 1] = rad_in[nr - 1, 0] = np.nan
     obs = common.obs_from_geom(geom, nd)
     np.ctypeslib.as_array(obs.rad)[:nr, :nd] = rad_in
     model = hip.Model(case.ctl, case.lib_tables())
@@ -220,7 +252,7 @@ def test_blocks_against_stored_reference(hip, tmp_path, name, arith):
     finally:
         model.close()
     k = hip.scene_blocks_to_dense(case.ctl, case.atm, out)[np.isfinite(out["rad"]).ravel()]
-    assert k.shape == k_ref.shape == (66 * 2 - 1, 6 + 31 + 21 + 11)
+    assert nr == 66 and k.shape == k_ref.shape == (66 * nd - 1, 6 + 31 + 21 + 11)
     scale = np.abs(k_ref).max(axis=0)
     live = scale > 0
     assert live.sum() >= 31 + 21 + 11 and np.all(k[:, ~live] == 0)

@@ -185,20 +185,27 @@ def test_arrangements(hip, name):
         model.close()
 
 
-def test_live_rule(hip):
-    case, geom, y, weight = inputs(hip, "ragged")
-    _, clear = blocks_and_sums(hip, "ragged")
+def test_live_rule(hip, name="ragged"):
+    case, geom, y, weight = inputs(hip, name)
+    _, clear = blocks_and_sums(hip, name)
     nr, nd = y.shape
     live = np.flatnonzero(clear["sid"] >= 0)
     dead = np.flatnonzero(clear["sid"] < 0)
     assert len(dead) > 0
     # masked with NaN, masked with NaN, y = NaN, weight 0, masked with +inf, masked with -inf (the forward model masks
-    # every channel whose input is not finite)
-    gone = [(live[1], 0), (live[7], 1), (live[3], 0), (live[5], 1), (live[9], 0), (live[11], 1)]
-    masks = gone[:2] + gone[4:]
+    # every channel whose input is not finite), in turn on the first and on the last channel; with more than two
+    # channels every channel between them is masked with NaN on a further ray
+    last = nd - 1
+    gone = [(live[1], 0), (live[7], last), (live[3], 0), (live[5], last), (live[9], 0), (live[11], last)]
+    between = [(live[13 + 2 * j], 1 + j) for j in range(nd - 2)]
+    assert len(live) > 11 + 2 * max(nd - 2, 0) and {i for _, i in gone + between} == set(range(nd))
+    masks = gone[:2] + gone[4:] + between
     rad_in = np.zeros((nr, nd))
     rad_in[gone[0]] = rad_in[gone[1]] = rad_in[dead[0], 0] = np.nan
     rad_in[gone[4]], rad_in[gone[5]] = np.inf, -np.inf
+    for g in between:
+        rad_in[g] = np.nan
+    gone = gone + between
     y2, w2 = y.copy(), weight.copy()
     y2[gone[2]] = np.nan
     w2[gone[3]] = 0.0
@@ -219,7 +226,7 @@ def test_live_rule(hip):
     removed = np.zeros(len(clear["nlive"]), dtype=np.int64)
     for r, _ in gone:
         removed[clear["sid"][r]] += 1
-    assert removed.sum() == 6 and np.array_equal(out["nlive"], clear["nlive"] - removed)
+    assert removed.sum() == len(gone) == 6 + max(nd - 2, 0) and np.array_equal(out["nlive"], clear["nlive"] - removed)
     assert np.array_equal(np.isnan(out["rad"]), ~np.isfinite(rad_in))
     rp = out["rowptr"]
     for r, i in masks:                                           # the masked channel's row of the block is NaN, as kernel_scene's
@@ -264,7 +271,7 @@ def test_refusals_and_state(hip):
     try:
         model.set_atm(unsorted.atm)
         with pytest.raises(hip.JurassicError, match=r"error %d: .*ascending" % hip.EINVAL):
-            model.normal_scene(unsorted.atm, g, np.zeros((len(g), 2)), np.ones((len(g), 2)))
+            model.normal_scene(unsorted.atm, g, np.zeros((len(g), unsorted.ctl.nd)), np.ones((len(g), unsorted.ctl.nd)))
         sequences.same_bits(formod_on(model, unsorted.geom), want, "after unsorted time stamps")
     finally:
         model.close()

@@ -424,13 +424,13 @@ def window_fields(c):
 
 
 @pytest.mark.parametrize("fov", [False, True], ids=["pencil", "fov"])
-def test_a_real_parameter(hip, fov):
+def test_a_real_parameter(hip, fov, name="ragged"):
     """One gas retrieved, T the parameter; with fov the scene of tests/test_scene_fov_gpu.py under its shape"""
     import test_scene_fov_gpu as F
     if fov:
-        case, geom = F.scene(hip)[:2]
+        case, geom = F.scene(hip, name)[:2]
     else:
-        case = scene_case("ragged")
+        case = scene_case(name)
         geom = six_per_time_stamp(case.geom)
     ctl_x, ctl_b = copy_ctl(case.ctl), copy_ctl(case.ctl)
     no_windows(ctl_x)
@@ -525,7 +525,7 @@ def test_a_real_parameter(hip, fov):
         el = pe["elements_b"][s]
         assert len(el["iq"]) == np.diff(lay["bwptr"])[s] and np.all(el["iq"] == 1)
     assert pe["sigma_param"].max() > 0
-    report("a real parameter%s" % (", a field of view" if fov else ""), worst)
+    report("a real parameter%s%s" % (", a field of view" if fov else "", "" if name == "ragged" else ", " + name), worst)
 
 
 # ---- 7. refusals -------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Writes tests/golden/reference_runs/: what the reference's own CPU forward model (oracle/_ref/libjurassic_ref.so,
 `make -C oracle ref`) returns on every case of tests/refcases.py -- per formod case one float64 .npy
-(rad | tau | tpz tplon tplat side by side, one row per ray), per Jacobian case the (131, 69) matrix in two halves of its rows -- and
+(rad | tau | tpz tplon tplat side by side, one row per ray), per Jacobian case the matrix ((131, 69); (197, 69) for the three channels of
+jacobian_nd3_bbt) in two halves of its rows -- and
 manifest.json with one line per case: name, shape, sha256 over the case's inputs (refcases.input_hash).
 
 Needs the reference tree (JUR_REFERENCE) to have been present at build time; the results are data the reference's
