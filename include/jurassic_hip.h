@@ -362,7 +362,8 @@ int  jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const
  *   and choices go up (and, when slices have ended, the list of the remaining rays); x and the forward results come home
  *   once.  atm_ret is a copy of atm0 with the retrieved elements replaced (it may be atm0 itself; written only on
  *   success); rad, tau, tp, np_out are the doubles of jur_formod_host on atm_ret (rad in: the NaN mask), and the model
- *   holds atm_ret.  On any error (JUR_ENLOS from a trial ray included) the model holds atm0 and atm_ret is untouched.
+ *   holds atm_ret.  On any error (JUR_ENLOS from a trial ray included, unless jur_model_set_scene_overflow isolates such
+ *   rays: see there) the model holds atm0 and atm_ret is untouched.
  *   The slices of a scene must be disjoint in atmosphere points (JUR_EINVAL names the two that are not).
  * The kernels' time counts into jur_model_last_scene_ms. */
 int  jur_trial_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double const *rad_in,
@@ -388,7 +389,7 @@ typedef struct {
   /* optional history, all or none: */
   double *h_cost, *h_prior;            /* [max_iter][nslice] at the iteration's start (a slice that has ended: its last) */
   double *h_lam, *h_tcost, *h_tprior;  /* [max_iter][nlam][nslice]; NaN where the slice took no part */
-  int *h_status;                       /* [max_iter][nlam][nslice]; -1 where the slice took no part */
+  int *h_status;                       /* [max_iter][nlam][nslice]; -1 where the slice took no part (JUR_TRIAL_OVERFLOW: see jur_model_set_scene_overflow) */
   int *h_best, *h_accept;              /* [max_iter][nslice]; -1 where the slice took no part */
   long *h_work;                        /* [max_iter][2] replicated rays of the Jacobian passes, of the trial passes */
 } jur_retrieve_out_t;
@@ -834,6 +835,50 @@ int  jur_gradient_scene_host(jur_model_t *m, atm_t const *atm, long nr, double c
                              double const *k /* blocks, as jur_kernel_scene_host lays them out */,
                              double *b, double *cost, long *nlive, long max_rays_per_pass);
 long jur_scene_recomp_offsets(long nr, long const *rowptr, int const *sid, int const *then, int const *now, int nd, long *koff);
+
+/* Untraceable rays in the scene retrieval: a trial whose rays overflow is a rejected step, not an error.  The model holds
+ * the switch as it holds the field of view; with JUR_OVERFLOW_ERROR (the default) every entry allocates and launches what
+ * it did before and returns the same bits.  Only jur_trial_scene_host and jur_retrieve_scene_host honour it; the other
+ * scene entries and jur_formod_* keep JUR_ENLOS.
+ *
+ * jur_model_set_scene_overflow: JUR_OVERFLOW_ERROR (a ray that needs JUR_NLOS points or more ends the call with
+ *   JUR_ENLOS) or JUR_OVERFLOW_ISOLATE; any other mode is JUR_EINVAL.  jur_model_scene_overflow: what is set.
+ * jur_np_overflows (host arithmetic, no GPU; one text with the device): np >= JUR_NLOS - 1.  The tracer clamps a ray that
+ *   needs more to JUR_NLOS - 1 points and keeps no flag per ray, so a ray that fills the array counts as untraceable
+ *   whether or not it was clamped: the rule errs towards rejection, and it depends on the ray alone -- not on the status
+ *   word, which all rays of a call share.
+ * With JUR_OVERFLOW_ISOLATE, on the device (jur_scene_overflow_kernel after the forward model of every pass, one fold
+ *   per kind of pass; no atomics, no host wait of their own):
+ *   Trial passes (jur_trial_scene_host, the trial pass of the loop): where a ray of (slice s, trial t) overflows,
+ *     cost[t][s] is NaN; prior[t][s] and every other double of the call are bit for bit what they are without that
+ *     trial's overflow, and the entry returns JUR_OK.  In the loop that trial's h_status is JUR_TRIAL_OVERFLOW and its
+ *     h_tcost NaN; jur_retrieve_decide is unchanged (a NaN Jt is no candidate), so the step is rejected and lam grows.
+ *     A ray without state elements belongs to no slice and poisons nothing.
+ *   Jacobian, reuse and gradient passes of the loop: where a slot of a slice's rays overflows (copy 0 or a raised copy)
+ *     the slice becomes JUR_RET_FAILED once all passes of the iteration are done and before its solve; the solve, the
+ *     trial copies, the prior terms and the trial costs skip it as they skip every ended slice.  (The passes of that
+ *     iteration have by then added the slice's rays, clamped ones included, to its own A, b, cost and nlive on the
+ *     device: those sums are never read -- not by the solve, not by the host, not by another slice -- and the slice's
+ *     rays are in no later pass.)  A reuse or gradient pass traces the current state alone, which the pass that accepted
+ *     it has traced already with the same result, so in practice only a Jacobian pass flags a slice.  iters is not incremented, the history cells of that iteration read
+ *     "took no part", x stays the last accepted state (the first guess at iteration 0), cost, prior and nlive are those
+ *     of the last completed iteration (NaN, NaN and 0 at iteration 0), and its rays are in no later pass.  All other
+ *     slices proceed, every output of theirs bit for bit that of the call without the failed slice's rays.
+ *   The call returns JUR_OK and atm_ret is written as on success; rad, tau, tp and np_out are what jur_formod_host writes
+ *     for atm_ret (for a ray with jur_np_overflows(np_out): before it returns JUR_ENLOS); the model holds atm_ret and the
+ *     status word is clean for the next call.  "Cannot apply FOV convolution!" and every JUR_EHIP, JUR_EINVAL and
+ *     JUR_ENOMEM path end the call as before.  The flags and the partial counts are part of the slab's JUR_ENOMEM
+ *     accounting, made before anything is launched.
+ * jur_model_last_scene_overflow: of the last jur_trial_scene_host or jur_retrieve_scene_host call, the (trial, slice)
+ *   cells whose cost was made NaN (summed over the iterations of a loop) and the slices that ended JUR_RET_FAILED; both 0
+ *   with JUR_OVERFLOW_ERROR.  Either output may be NULL. */
+enum { JUR_OVERFLOW_ERROR = 0, JUR_OVERFLOW_ISOLATE = 1 };
+enum { JUR_RET_FAILED = 4 };              /* joins JUR_RET_ACTIVE .. JUR_RET_MAXITER */
+enum { JUR_TRIAL_OVERFLOW = -2 };         /* a value of h_status: -1 took no part, 0 solved, > 0 the solver's */
+int  jur_model_set_scene_overflow(jur_model_t *m, int mode);
+int  jur_model_scene_overflow(jur_model_t const *m);
+int  jur_model_last_scene_overflow(jur_model_t const *m, long *trial_cells, long *failed_slices);
+int  jur_np_overflows(int np);
 
 /* intpol_atm with an error code instead of exit(): JUR_EINVAL for what upstream aborts on (profiles of one point,
  * profiles more than 10 degrees apart, unknown IP).  One lane per destination point on `device`. */

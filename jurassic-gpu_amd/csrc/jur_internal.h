@@ -426,6 +426,39 @@ typedef struct {
 } jur_scene_compact_t;
 int jurk_scene_compact(jur_scene_compact_t const *a, void *stream);
 
+/* Untraceable rays of a pass (jur_model_set_scene_overflow): the rule of jur_np_overflows, one text for host and device --
+ * the tracer clamps a ray that needs JUR_NLOS points or more to JUR_NLOS - 1 and keeps no flag of its own, so a ray that
+ * fills the array counts, clamped or not */
+#define JUR_NP_OVERFLOWS(np) ((np) >= JUR_NLOS - 1)
+#define JUR_OVERFLOW_PARTS 256  /* the most workgroups of the fold kernel: one partial count each */
+/* one lane per slot of a pass, after its forward model: flag[t][s] = 1 where slot (ray r of slice s, trial t) holds such a
+ * ray.  A trial pass has ntrial slots per ray, slot (r - r0) * ntrial + t; a Jacobian or forward-only pass (ntrial == 0)
+ * has the slots of rowptr (width + 1 per ray, one with the all-zero rowptr) and one row of flags.  The slice of ray r is
+ * (tcopy0[r] - 1) / per, tcopy0 as jur_scene_trial_pass_t's; a ray without state elements (tcopy0 == 0) sets nothing. */
+typedef struct {
+  long n, r0, r1;               /* slots of the pass, its rays                                              */
+  int ntrial, per;
+  long nslice;
+  long const *rowptr;           /* ntrial == 0: as jur_scene_pass_t                                         */
+  int const *tcopy0;            /* [nr]                                                                     */
+  int const *np;                /* [n] LOS points of every slot (the forward model's)                       */
+  int *flag;                    /* [max(ntrial, 1)][nslice]; written with 1 only, zeroed by the caller      */
+} jur_scene_ovf_t;
+int jurk_scene_overflow(jur_scene_ovf_t const *a, void *stream);
+/* the fold, one lane per flag (at most JUR_OVERFLOW_PARTS workgroups, each striding over the flags): with cost given,
+ * cost[t][s] = NaN where flag[t][s] and slice s takes part (state NULL or state[s] == 0); without, state[s] =
+ * JUR_RET_FAILED where flag[s] and state[s] == 0.  part[g] is the number of cells workgroup g changed. */
+typedef struct {
+  long nslice;
+  int ntrial;
+  int const *flag;
+  int *state;                   /* [nslice]; written only without cost                                      */
+  double *cost;                 /* [ntrial][nslice] or NULL                                                 */
+  long *part;                   /* [jur_scene_overflow_parts(lanes)]                                        */
+} jur_scene_ovfold_t;
+int jurk_scene_overflow_fold(jur_scene_ovfold_t const *a, void *stream);
+long jur_scene_overflow_parts(long lanes);   /* workgroups of the fold over that many flags (jur_scene.c) */
+
 /* Full a-priori precision of the slices (jur_model_set_prior_precision): P_s = R_s + diag(r_s), R_s [w][w] of which the
  * diagonal and the lower triangle are read, r = prior_ivar.  The existing kernels run unchanged on what these form.  All
  * arrays are device memory; wptr, aptr lay out the systems as jur_scene_solve_t's. */

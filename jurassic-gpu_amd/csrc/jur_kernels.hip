@@ -32,6 +32,8 @@
 //   jur_scene_fov_kernel  the same convolution on the replicated rays of a pass of the scene entries, a workgroup per ray.
 //   jur_scene_hydro_kernel  hydrostatic balance of the slices of a scene, one wavefront per segment (jur_model_set_scene_hydz).
 //   jur_scene_gradient_kernel  b, cost and nlive of a scene's slices from held blocks, a lane per state element (jur_gradient_scene_host).
+//   jur_scene_overflow_kernel  untraceable rays of a pass of the scene retrieval, a lane per slot, and
+//   jur_scene_overflow_fold_kernel  their fold into NaN trial costs and failed slices (jur_model_set_scene_overflow).
 //   jur_scene_gain_kernel  gain matrix G = S K^T W of a scene's slices over the ragged blocks, a workgroup per 64 x 64 tile;
 //   jur_scene_budget_kernel  the row sums of G^2 var per error source, a lane per state element (jur_gain_scene_host).
 //   jur_scene_cross_kernel  cross-state matrix C = G^T Kb of a scene's slices over the ragged blocks, a workgroup per 64 x 64 tile;
@@ -3649,6 +3651,49 @@ __global__ __launch_bounds__(256) void jur_scene_compact_kernel(jur_scene_compac
   a.first_c[i] = a.first[r]; a.len_c[i] = a.len[r]; a.copy0_c[i] = a.copy0[r]; a.tcopy0_c[i] = a.tcopy0[r];
 }
 
+// Untraceable rays of a pass (jur_model_set_scene_overflow), one lane per slot, after the pass's forward model and before
+// the next pass overwrites np: where JUR_NP_OVERFLOWS(np[slot]) the flag of the slot's (trial, slice) is set.  No atomics:
+// every store is the same constant, so the lanes of one cell may store in any order.  The rule reads the ray's own count
+// alone -- not the status word, which all slices share.
+__global__ __launch_bounds__(256) void jur_scene_overflow_kernel(jur_scene_ovf_t a) {
+  long const i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  if (!JUR_NP_OVERFLOWS(a.np[i])) return;
+  long r, t = 0;
+  if (a.ntrial > 0) { r = a.r0 + i / a.ntrial; t = i - (r - a.r0) * a.ntrial; }
+  else r = scene_find<true>(a.rowptr, a.r0, a.r1, i + a.rowptr[a.r0] + a.r0);
+  int const c = a.tcopy0[r];
+  if (c <= 0) return;                                       // a ray without state elements belongs to no slice
+  long const s = (long)(c - 1) / a.per;
+  a.flag[t * a.nslice + s] = 1;
+}
+
+// The fold of the flags into what the loop and the policy read, workgroup g striding over the flags g * 256 + lane,
+// + gridDim.x * 256, ...: a flagged trial of a slice that takes part gets cost NaN (trial passes, cost given); a flagged
+// slice that is active becomes JUR_RET_FAILED (Jacobian, reuse and gradient passes: before the solve, which then skips it
+// as every later kernel does).  A lane reads and writes the state of its own slice only.  part[g]: how many cells the
+// workgroup changed, a fixed tree over its lanes in LDS; the host adds the parts.
+__global__ __launch_bounds__(256) void jur_scene_overflow_fold_kernel(jur_scene_ovfold_t a) {
+  __shared__ long cnt[256];
+  long const n = a.cost ? a.nslice * a.ntrial : a.nslice;
+  long c = 0;
+  for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < n; g += (long)gridDim.x * 256) {
+    if (!a.flag[g]) continue;
+    long const s = a.cost ? g - (g / a.nslice) * a.nslice : g;
+    if (a.state && a.state[s] != 0) continue;
+    if (a.cost) a.cost[g] = __builtin_nan("");
+    else a.state[s] = JUR_RET_FAILED;
+    c++;
+  }
+  cnt[threadIdx.x] = c;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) cnt[threadIdx.x] += cnt[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) a.part[blockIdx.x] = cnt[0];
+}
+
 }  // namespace
 
 extern "C" int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream) {
@@ -3926,6 +3971,19 @@ extern "C" int jurk_scene_trial_cost(jur_scene_trial_pass_t const *a, void *stre
 extern "C" int jurk_scene_compact(jur_scene_compact_t const *a, void *stream) {
   if (a->n <= 0) return 0;
   hipLaunchKernelGGL(jur_scene_compact_kernel, dim3(scene_grid(a->n)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_overflow(jur_scene_ovf_t const *a, void *stream) {
+  if (a->n <= 0 || a->nslice <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_overflow_kernel, dim3(scene_grid(a->n)), dim3(256), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_scene_overflow_fold(jur_scene_ovfold_t const *a, void *stream) {
+  long const lanes = a->cost ? a->nslice * a->ntrial : a->nslice;
+  if (lanes <= 0) return 0;
+  hipLaunchKernelGGL(jur_scene_overflow_fold_kernel, dim3((unsigned)jur_scene_overflow_parts(lanes)), dim3(256), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

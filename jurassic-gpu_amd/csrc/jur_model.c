@@ -102,6 +102,8 @@ struct jur_model {
   double scene_hydz;            /* hydrostatic balance of the scene entries per slice (jur_model_set_scene_hydz): the
                                    reference altitude [km], negative: off                                   */
   int kernel_recomp;            /* jur_retrieve_scene_host recomputes the Jacobian every n-th iteration (jur_model_set_kernel_recomp) */
+  int scene_overflow;           /* JUR_OVERFLOW_*: what jur_trial_scene_host and jur_retrieve_scene_host make of an untraceable ray */
+  long ov_cells, ov_failed;     /* ... and what the last of their calls counted (jur_model_last_scene_overflow) */
   int sb_nq;                    /* the box on the state (jur_model_set_state_bounds): 2 + ng + nw quantities, 0: off */
   double sb_lo[2 + JUR_NG + JUR_NW], sb_hi[2 + JUR_NG + JUR_NW];
   double *d_kq, *h_kq;          /* jur_kernel: perturbation steps and dense difference quotients (device, pinned host) */
@@ -1581,6 +1583,27 @@ int jur_model_set_kernel_recomp(jur_model_t *m, int every) {
 
 int jur_model_kernel_recomp(jur_model_t const *m) { return m ? m->kernel_recomp : 1; }
 
+/* ---- untraceable rays in jur_trial_scene_host and jur_retrieve_scene_host ------------------ */
+int jur_model_set_scene_overflow(jur_model_t *m, int mode) {
+  char const *const who = "jur_model_set_scene_overflow";
+  if (!m) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  if (mode != JUR_OVERFLOW_ERROR && mode != JUR_OVERFLOW_ISOLATE) {
+    jur_set_error("%s: unknown mode %d: JUR_OVERFLOW_ERROR (%d) or JUR_OVERFLOW_ISOLATE (%d)", who, mode, JUR_OVERFLOW_ERROR, JUR_OVERFLOW_ISOLATE);
+    return JUR_EINVAL;
+  }
+  m->scene_overflow = mode;
+  return JUR_OK;
+}
+
+int jur_model_scene_overflow(jur_model_t const *m) { return m ? m->scene_overflow : JUR_OVERFLOW_ERROR; }
+
+int jur_model_last_scene_overflow(jur_model_t const *m, long *trial_cells, long *failed_slices) {
+  if (!m) { jur_set_error("jur_model_last_scene_overflow: null argument"); return JUR_EINVAL; }
+  if (trial_cells) *trial_cells = m->ov_cells;
+  if (failed_slices) *failed_slices = m->ov_failed;
+  return JUR_OK;
+}
+
 /* The retrieval windows live in the model's copy of the control block and nowhere else: every entry that derives a state
  * reads them there when it is called (jur_scene_layout, jur_scene_slices, jur_state_vector), and neither the view, the
  * uploaded atmosphere nor the tables were made from them. */
@@ -1763,9 +1786,10 @@ static int scene_fits(jur_model_t const *m, double *used, size_t add) {
   return 1;
 }
 
-/* what the status word that has come home (m->h_status) says of the forward models of a scene entry */
-static int scene_status_rc(jur_model_t const *m, char const *who) {
-  if (*m->h_status & 1) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); return JUR_ENLOS; }
+/* what the status word that has come home (m->h_status) says of the forward models of a scene entry; isolate: the
+ * entry deals with untraceable rays itself (JUR_OVERFLOW_ISOLATE) and bit 1 does not end it */
+static int scene_status_rc(jur_model_t const *m, char const *who, int isolate) {
+  if ((*m->h_status & 1) && !isolate) { jur_set_error("Too many LOS points! (a ray needs %d or more)", JUR_NLOS); return JUR_ENLOS; }
   if (*m->h_status & 2) { jur_set_error("%s: Cannot apply FOV convolution!", who); return JUR_EINVAL; }
   return JUR_OK;
 }
@@ -2437,10 +2461,12 @@ typedef struct { jur_scene_fov_t k; double const *live; } scene_fov_t;
  * forms the prior terms (or zeroes them), traces the rays of every pass and continues the cost chains.  ps carries the
  * ray arrays of the call (or of its gathered rays); its r0, r1, n, geom, rad, atm_time and `above` are set here.  The
  * model's view is left on the trial atmosphere.  Nothing is waited for after the stacking. */
-/* nhy > 0 (the hydrostatic balance is on): the segments of the trial copies, balanced after the elements have moved. */
+/* nhy > 0 (the hydrostatic balance is on): the segments of the trial copies, balanced after the elements have moved.
+ * of (JUR_OVERFLOW_ISOLATE): the untraceable rays of every pass are flagged in of->flag (zeroed by the caller) before the
+ * next pass overwrites the counts, and folded into the costs after the last. */
 static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, jur_scene_stack_t *sk, jur_scene_trial_t *st,
                      jur_scene_trial_pass_t *ps, long nb, long npass, long const *pass, long nmax, scene_fov_t *fv,
-                     jur_scene_pquad_t const *tq, long nhy, long const *d_hyat, int const *d_hylen) {
+                     jur_scene_pquad_t const *tq, long nhy, long const *d_hyat, int const *d_hylen, jur_scene_ovfold_t const *of) {
   size_t const nrow = (size_t)sk->nrow;
   int const nd = ps->nd;
   int rc;
@@ -2501,6 +2527,22 @@ static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const
     ek = jurk_scene_trial_cost(&pf, s);
     scene_timed_end(m, ti, s);
     if (ek) { jur_set_error("%s: trial cost kernel launch failed", who); return JUR_EHIP; }
+    if (of) {
+      jur_scene_ovf_t oq;
+      memset(&oq, 0, sizeof oq);
+      oq.n = n; oq.r0 = ps->r0; oq.r1 = ps->r1; oq.ntrial = ps->ntrial; oq.per = ps->ntrial; oq.nslice = ps->nslice;
+      oq.tcopy0 = ps->tcopy0; oq.np = m->d_io_np; oq.flag = (int *)of->flag;
+      ti = scene_timed_begin(m, s);
+      ek = jurk_scene_overflow(&oq, s);
+      scene_timed_end(m, ti, s);
+      if (ek) { jur_set_error("%s: overflow kernel launch failed", who); return JUR_EHIP; }
+    }
+  }
+  if (of) {
+    ti = scene_timed_begin(m, s);
+    ek = jurk_scene_overflow_fold(of, s);
+    scene_timed_end(m, ti, s);
+    if (ek) { jur_set_error("%s: overflow fold kernel launch failed", who); return JUR_EHIP; }
   }
   return JUR_OK;
 }
@@ -2659,6 +2701,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   char const *const who = gd ? "jur_gradient_scene_host" : rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : (dg && dg->gin) ? "jur_gain_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
+  if (rt) m->ov_cells = m->ov_failed = 0;           /* (the counts of jur_model_last_scene_overflow are this call's) */
   if (rt) { int const rs = retrieve_check_args(who, rt->in, rt->out); if (rs) return rs; }
   if (dg) { int const rs = jur_diag_check_out(who, dg->out); if (rs) return rs; }
   int const gn = dg && dg->gin;                     /* jur_gain_scene_host: the blocks are held, the gain follows the diagnostics */
@@ -2686,6 +2729,9 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   double const *d_R = NULL;                         /* the model's full prior precision on the device, where one is set */
   int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: every slice is balanced on its own */
   long *hyat = NULL;                                /* the segment lists of the balance on the host: at | len (ints behind) */
+  int const ov = rt && m->scene_overflow == JUR_OVERFLOW_ISOLATE;   /* untraceable rays fail their trial or their slice, not the call */
+  int *hov = NULL;                                  /* ... what comes home of that per iteration: state [ns] | trial flags [nlam][ns] */
+  long *hovp = NULL;                                /* ... and the fold's partial counts: failed slices | trial cells */
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if ((rc = scene_open(&op, m, who, atm, nr, geom, rad, rowptr,
@@ -2850,8 +2896,10 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const NRD = NR * (size_t)nd;
   size_t const nbd = (looping && m->sb_nq) ? 2 * (size_t)nb : 0;   /* a box on the state: lo | hi of every element */
   size_t const rt_dbl = looping ? 2 * RL * RS + RS + 2 * (size_t)nb + 7 * NR + 3 * NRD + (d_R ? RL * (size_t)nb : 0) + nbd : 0;   /* (xa - (x + dx) of every trial; last: the box) */
-  size_t const rt_lng = looping ? pl.nlong + (NR + 1) + (RS + 1) : 0;
-  size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist : 0;
+  int const ovl = ov && looping;                    /* JUR_OVERFLOW_ISOLATE: the flags of the slices and of the trials, the partial counts of the two folds */
+  size_t const nov_int = ovl ? RS + RL * RS : 0, nov_lng = ovl ? 2 * (size_t)JUR_OVERFLOW_PARTS : 0;
+  size_t const rt_lng = looping ? pl.nlong + (NR + 1) + (RS + 1) + nov_lng : 0;
+  size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist + nov_int : 0;
   size_t const rt_atm_bytes = looping ? sizeof(double) * (nrow + 1) * (size_t)pl.nt : 0;
   size_t const rt_bytes = sizeof(double) * (rt_dbl + rt_lng) + sizeof(int) * rt_int;
   used += (double)rt_atm_bytes;
@@ -3068,6 +3116,11 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     int *const Ir = I + nint0, *const d_state = Ir + pl.nint, *const d_choice = d_state + RS, *const d_act = d_choice + RS,
         *const d_firstc = d_act + NR, *const d_lenc = d_firstc + NR, *const d_copy0c = d_lenc + NR, *const d_tcopy0c = d_copy0c + NR,
         *const d_sraysc = d_tcopy0c + NR;
+    int *const d_oflag = d_sraysc + nlist, *const d_otflag = d_oflag + RS;   /* (JUR_OVERFLOW_ISOLATE: the flags, zeroed every iteration) */
+    long *const d_ovp = d_sptrc + RS + 1;                                    /* (... and the partial counts) */
+    long const novj = jur_scene_overflow_parts((long)RS), novt = jur_scene_overflow_parts((long)(RL * RS));
+    jur_scene_ovfold_t ofj, oft;
+    memset(&ofj, 0, sizeof ofj); memset(&oft, 0, sizeof oft);
     size_t const npr = (looping && rin->prior_ivar) ? (size_t)nb : 0;
     double *const sv_dx = D + o_sv + svl.dx, *const sv_r = D + o_sv + svl.r, *const sv_d = D + o_sv + svl.d;   /* (the solver's part of the slab) */
     double *const lamt = rd, *const htcost = rd ? rd + 2 * RL * RS : NULL, *const htprior = rd ? rd + 3 * RL * RS : NULL,
@@ -3116,6 +3169,14 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       tps.srays = Ir + (pl.srays - pl.ints); tps.state = d_state; tps.y = D + o_y; tps.weight = D + o_w; tps.cost = d_tcost;
       tqd.nslice = nslice; tqd.nvec = rin->nlam; tqd.wptr = Lr; tqd.aptr = nq.aptr; tqd.R = d_R; tqd.v = d_dvec; tqd.out = d_tprior;
       tqd.state = d_state;
+      if (ovl) {
+        hov = (int *)malloc(sizeof(int) * (RS + RL * RS));
+        hovp = (long *)malloc(sizeof(long) * 2 * JUR_OVERFLOW_PARTS);
+        if (!hov || !hovp) { rc = JUR_ENOMEM; goto done; }
+        ofj.nslice = nslice; ofj.ntrial = 1; ofj.flag = d_oflag; ofj.state = d_state; ofj.part = d_ovp;
+        oft.nslice = nslice; oft.ntrial = rin->nlam; oft.flag = d_otflag; oft.state = d_state; oft.cost = d_tcost;
+        oft.part = d_ovp + JUR_OVERFLOW_PARTS;
+      }
       for (int l = 0; l < rin->nlam; l++) fac_max = fmax(fac_max, rin->fac[l]);
       for (long q = 0; q < nslice; q++) { ro->lam[q] = rin->lam0; ro->state[q] = JUR_RET_ACTIVE; ro->iters[q] = 0; ro->cost[q] = ro->prior[q] = 0; ro->nlive[q] = 0; }
       if (ro->h_cost) {
@@ -3183,6 +3244,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
           lamt[(size_t)l * RS + (size_t)q] = fmin(fmax(v, rin->lam_min), rin->lam_max);
         }
       e = hipMemcpyAsync(d_state, ro->state, sizeof(int) * RS, hipMemcpyHostToDevice, s);
+      if (ovl && e == hipSuccess) e = hipMemsetAsync(d_oflag, 0, sizeof(int) * nov_int, s);
       /* (a reuse iteration keeps A of the last Jacobian iteration: b, cost and nlive alone start again) */
       if (it > 0 && e == hipSuccess) e = reuse ? hipMemsetAsync(D + o_acc + na, 0, sizeof(double) * (nacc - (size_t)na), s)
                                                : hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
@@ -3243,6 +3305,16 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       scene_timed_end(m, ti, s);
       if (ek) { jur_set_error("%s: replication kernel launch failed", who); rc = JUR_EHIP; goto done; }
       if ((rc = jur_formod_device(m, n, a.geom, a.rad, a.tau, a.tp, a.np, m->d_status, s))) goto done;
+      if (ovl) {                                   /* the untraceable slots of the pass, before the next one overwrites the counts */
+        jur_scene_ovf_t oq;
+        memset(&oq, 0, sizeof oq);
+        oq.n = n; oq.r0 = r0; oq.r1 = r1; oq.ntrial = 0; oq.per = rin->nlam; oq.nslice = nslice;
+        oq.rowptr = a.rowptr; oq.tcopy0 = tps.tcopy0; oq.np = a.np; oq.flag = d_oflag;
+        ti = scene_timed_begin(m, s);
+        ek = jurk_scene_overflow(&oq, s);
+        scene_timed_end(m, ti, s);
+        if (ek) { jur_set_error("%s: overflow kernel launch failed", who); rc = JUR_EHIP; goto done; }
+      }
       jur_scene_pass_t af = a;                     /* what reads the forward model's results ... */
       if (fov) {                                   /* ... reads them convolved, the sums under the effective mask */
         fv.k.r0 = r0; fv.k.r1 = r1; fv.k.ntrial = 0; fv.k.rowptr = a.rowptr;
@@ -3274,6 +3346,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (e == hipSuccess) e = hipStreamSynchronize(s);
       if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     }
+    if (ovl) {                                     /* all passes are done: the flagged slices fail before the solve, on the device */
+      ti = scene_timed_begin(m, s);
+      ek = jurk_scene_overflow_fold(&ofj, s);
+      scene_timed_end(m, ti, s);
+      if (ek) { jur_set_error("%s: overflow fold kernel launch failed", who); rc = JUR_EHIP; goto done; }
+    }
     if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out,
                                    looping ? d_state : NULL, d_R))) goto done;
     if (ndg && (rc = diag_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, D + o_dg, dg->prior_ivar, dg->out, ninv, ndtile, dmap, d_R))) goto done;
@@ -3300,8 +3378,14 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
 
     /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
     if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax, fov ? &fv : NULL, d_R ? &tqd : NULL,
-                        ntc, d_hyat + nrs + nhc, d_hylen + nrs + nhc))) goto done;
+                        ntc, d_hyat + nrs + nhc, d_hylen + nrs + nhc, ovl ? &oft : NULL))) goto done;
     e = hipMemcpyAsync(hcost, nq.cost, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
+    if (ovl) {                                     /* the states and the trial flags come home with the scalars */
+      if (e == hipSuccess) e = hipMemcpyAsync(hov, d_state, sizeof(int) * RS, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(hov + RS, d_otflag, sizeof(int) * RL * RS, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(hovp, d_ovp, sizeof(long) * (size_t)novj, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(hovp + JUR_OVERFLOW_PARTS, d_ovp + JUR_OVERFLOW_PARTS, sizeof(long) * (size_t)novt, hipMemcpyDeviceToHost, s);
+    }
     if (e == hipSuccess) e = hipMemcpyAsync(hnlive, nq.nlive, sizeof(long) * RS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hprior0, d_prior0, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(htcost, d_tcost, sizeof(double) * RL * RS, hipMemcpyDeviceToHost, s);
@@ -3309,7 +3393,17 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if ((rc = scene_status_rc(m, who))) goto done;
+    if ((rc = scene_status_rc(m, who, ov))) goto done;
+    if (ovl) {
+      /* a slice that failed in this iteration took no part in it: what it holds is of its last completed iteration */
+      for (long q = 0; q < nslice; q++)
+        if (ro->state[q] == JUR_RET_ACTIVE && hov[q] == JUR_RET_FAILED) {
+          ro->state[q] = JUR_RET_FAILED;
+          if (ro->iters[q] == 0) { ro->cost[q] = ro->prior[q] = NAN; ro->nlive[q] = 0; }
+        }
+      for (long g = 0; g < novj; g++) m->ov_failed += hovp[g];
+      for (long g = 0; g < novt; g++) m->ov_cells += hovp[JUR_OVERFLOW_PARTS + g];
+    }
     {
       long work = 0;
       for (long r = 0; r < nr_cur; r++) work += reuse ? 1 : rp_cur[r + 1] - rp_cur[r] + 1;
@@ -3326,7 +3420,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
           if (ro->state[q] != JUR_RET_ACTIVE) continue;
           for (size_t l = 0; l < RL; l++) {
             size_t const i = l * RS + (size_t)q;
-            ro->h_lam[at2 + i] = lamt[i]; ro->h_tcost[at2 + i] = htcost[i]; ro->h_tprior[at2 + i] = htprior[i]; ro->h_status[at2 + i] = hstatus[i];
+            ro->h_lam[at2 + i] = lamt[i]; ro->h_tcost[at2 + i] = htcost[i]; ro->h_tprior[at2 + i] = htprior[i];
+            ro->h_status[at2 + i] = (ovl && hov[RS + i]) ? JUR_TRIAL_OVERFLOW : hstatus[i];
           }
         }
         ro->h_work[2 * it] = work; ro->h_work[2 * it + 1] = nr_cur * rin->nlam;
@@ -3411,13 +3506,14 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    rc = scene_status_rc(m, who);
+    rc = scene_status_rc(m, who, ov);
+    if (ov && !rc) *m->h_status &= ~1;             /* (the rays that could not be traced are the caller's to read off np_out) */
     if (rt && !rc) memcpy(rt->atm_ret, ret_atm, sizeof(atm_t));
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
   free(srays); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa); free(rd); free(ri); free(hact); free(hcomp);
-  free(ret_atm); free(dmap); free(gmap); free(htimec); free(hyat); free(hkoff); free(hjac); free(hbd);
+  free(ret_atm); free(dmap); free(gmap); free(htimec); free(hyat); free(hkoff); free(hjac); free(hbd); free(hov); free(hovp);
   scene_open_free(&op);
   trial_plan_free(&pl);
   return rc;
@@ -3508,6 +3604,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
                             long const *rowptr, double const *y, double const *weight, int ntrial, double const *dx,
                             double const *prior_ivar, double const *prior_xa, double *cost, double *prior, long max_rays_per_pass) {
   char const *const who = "jur_trial_scene_host";
+  m->ov_cells = m->ov_failed = 0;                   /* (the counts of jur_model_last_scene_overflow are this call's) */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (ntrial < 1 || ntrial > 64) { jur_set_error("%s: ntrial = %d: 1 to 64 trials per call", who, ntrial); return JUR_EINVAL; }
   if (!prior_ivar != !prior_xa) {
@@ -3531,6 +3628,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   int const fov = m->fov_n > 0;                     /* a field of view is set: the trial radiances are convolved */
   int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: base rows and trial copies are balanced */
   long *hyat = NULL;
+  int const ov = m->scene_overflow == JUR_OVERFLOW_ISOLATE;   /* an untraceable ray makes its trial's cost NaN, not the call fail */
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if ((rc = scene_open(&op, m, who, atm, nr, geom, rad_in, rowptr, NULL, 1, y, weight))) goto done;
@@ -3558,7 +3656,9 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)pl.nt;
   size_t const nfov = fov ? nrd : 0;                  /* (the effective mask) */
   size_t const NH = hyd ? (size_t)nrs + NT * NS : 0;  /* (the balance's segments: the ray slices, every trial copy) */
-  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov + ndv + nbd) + (sizeof(long) + sizeof(int)) * NH;
+  size_t const nov_int = ov ? NT * NS : 0, nov_lng = ov ? (size_t)JUR_OVERFLOW_PARTS : 0;   /* (the trials' flags, the fold's partial counts) */
+  size_t const acc_bytes = sizeof(double) * (NT * NB + 2 * npr + 2 * NT * NS + nfov + ndv + nbd) + (sizeof(long) + sizeof(int)) * NH +
+                           sizeof(long) * nov_lng + sizeof(int) * nov_int;
   if ((double)atm_bytes + (double)acc_bytes > (double)(m->ws_budget / 2)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and accumulators (%zu bytes) exceed the workspace budget: "
                   "call with fewer trials or the rays of fewer slices at a time", who, pl.nt, atm_bytes, acc_bytes);
@@ -3590,9 +3690,9 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_y = o_inrad + nrd, o_w = o_y + nrd,
                o_dx = o_w + nrd, o_r = o_dx + NT * NB, o_xa = o_r + npr, o_cost = o_xa + npr, o_prior = o_cost + NT * NS,
                o_live = o_prior + NT * NS, o_dv = o_live + nfov, o_bd = o_dv + ndv, o_long = o_bd + nbd,
-               o_int = o_long + pl.nlong + NH;   /* (the balance's first points behind the plan's longs, its lengths behind the ints) */
+               o_int = o_long + pl.nlong + NH + nov_lng;   /* (the balance's first points behind the plan's longs, its lengths behind the ints; the fold's counts and the flags behind those) */
   hipStream_t s;
-  if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR + NH), &s))) goto done;
+  if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * (pl.nint + 2 * NR + NH + nov_int), &s))) goto done;
   if ((rc = ensure_io(m, nmax, 0))) goto done;
   if (fov && (rc = scene_fov_reserve(m, (size_t)nmax * (size_t)nd))) goto done;
   {
@@ -3618,6 +3718,9 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     int const *const d_hylen = d_len + NR;
     if (NH && e == hipSuccess) e = hipMemcpyAsync(L + pl.nlong, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
     if (NH && e == hipSuccess) e = hipMemcpyAsync(d_len + NR, hyat + NH, sizeof(int) * NH, hipMemcpyHostToDevice, s);
+    long *const d_ovp = L + pl.nlong + NH;
+    int *const d_otflag = d_len + NR + NH;
+    if (ov && e == hipSuccess) e = hipMemsetAsync(d_otflag, 0, sizeof(int) * nov_int, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     if (hyd && scene_hydro_launch(m, s, nrs, d_hyat, d_hylen, D + o_base, (size_t)np0)) {   /* the base rows, once */
       jur_set_error("%s: hydrostatic kernel launch failed", who); rc = JUR_EHIP; goto done;
@@ -3649,14 +3752,24 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
       tq.nslice = nslice; tq.nvec = ntrial; tq.wptr = d_wptr; tq.aptr = (long const *)m->d_pp + NS + 1; tq.R = d_R;
       tq.v = D + o_dv; tq.out = D + o_prior;
     }
+    jur_scene_ovfold_t of;                            /* (JUR_OVERFLOW_ISOLATE: every slice of the call takes part) */
+    memset(&of, 0, sizeof of);
+    of.nslice = nslice; of.ntrial = ntrial; of.flag = d_otflag; of.cost = D + o_cost; of.part = d_ovp;
+    long const novt = jur_scene_overflow_parts((long)(NT * NS));
+    long hovp[JUR_OVERFLOW_PARTS];
     if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax, fov ? &fv : NULL, d_R ? &tq : NULL,
-                        hyd ? (long)(NT * NS) : 0, d_hyat + nrs, d_hylen + nrs))) goto done;
+                        hyd ? (long)(NT * NS) : 0, d_hyat + nrs, d_hylen + nrs, ov ? &of : NULL))) goto done;
     e = hipMemcpyAsync(cost, D + o_cost, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
+    if (ov && e == hipSuccess) e = hipMemcpyAsync(hovp, d_ovp, sizeof(long) * (size_t)novt, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(prior, D + o_prior, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    rc = scene_status_rc(m, who);
+    rc = scene_status_rc(m, who, ov);
+    if (ov && !rc) {
+      *m->h_status &= ~1;
+      for (long g = 0; g < novt; g++) m->ov_cells += hovp[g];
+    }
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);

@@ -899,6 +899,15 @@ double jur_state_bound(double x, double lo, double hi) {
   return c;
 }
 
+/* ---- untraceable rays in the scene retrieval (jur_model_set_scene_overflow) --------------------------------------------- */
+int jur_np_overflows(int np) { return JUR_NP_OVERFLOWS(np); }
+
+/* the workgroups (of 256 lanes) the fold runs with over `lanes` flags, and with them its partial counts */
+long jur_scene_overflow_parts(long lanes) {
+  long const g = (lanes + 255) / 256;
+  return g < 1 ? 1 : g > JUR_OVERFLOW_PARTS ? JUR_OVERFLOW_PARTS : g;
+}
+
 /* the name of quantity iq for a message: p, T, q[g] (with the emitter where the control is at hand), k[w] */
 static char const *quantity_name(int ng, int iq, char buf[32]) {
   if (iq == 0) return "p";

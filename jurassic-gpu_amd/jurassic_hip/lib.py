@@ -193,6 +193,11 @@ def lib():
             L.jur_param_abi_sizes.restype = None
             L.jur_model_set_ret_windows.argtypes = [C.c_void_p, C.c_void_p]
             L.jur_model_ret_windows.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "jur_model_set_scene_overflow"):   # (an A/B library from before untraceable rays were isolated has none)
+            L.jur_model_set_scene_overflow.argtypes = [C.c_void_p, C.c_int]
+            L.jur_model_scene_overflow.argtypes = [C.c_void_p]
+            L.jur_model_last_scene_overflow.argtypes = [C.c_void_p, lp_, lp_]
+            L.jur_np_overflows.argtypes = [C.c_int]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
@@ -620,6 +625,24 @@ class Model:
         """What set_kernel_recomp set."""
         return int(lib().jur_model_kernel_recomp(self.h))
 
+    def set_scene_overflow(self, mode):
+        """What trial_scene and retrieve_scene make of a ray that needs NLOS points or more (jur_model_set_scene_overflow):
+        OVERFLOW_ERROR (the default) ends the call with "Too many LOS points"; OVERFLOW_ISOLATE makes the cost of that
+        trial NaN -- a rejected step -- and ends a slice whose current state cannot be traced as RET_FAILED, while every
+        other slice proceeds."""
+        _chk(lib().jur_model_set_scene_overflow(self.h, int(mode)))
+
+    def scene_overflow(self):
+        """What set_scene_overflow set."""
+        return int(lib().jur_model_scene_overflow(self.h))
+
+    def last_scene_overflow(self):
+        """(trial cells made NaN, slices ended RET_FAILED) of the last trial_scene or retrieve_scene call
+        (jur_model_last_scene_overflow); (0, 0) with OVERFLOW_ERROR."""
+        a, b = C.c_long(0), C.c_long(0)
+        _chk(lib().jur_model_last_scene_overflow(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def gradient_scene(self, atm, geom, y, weight, k, rad_in=None, max_rays_per_pass=0, rowptr=None):
         """Gradient and cost of a scene per slice from blocks the caller holds (jur_gradient_scene_host): the forward model
         alone, one ray per ray.  k: the flat blocks as kernel_scene returns them (None only for a state without elements)
@@ -745,7 +768,9 @@ class Model:
         iteration its h_lam, h_tcost, h_tprior are NaN and its h_status, h_best, h_accept -1.  Under
         set_kernel_recomp(every > 1) the iterations it % every != 0 reuse the blocks and A of the last Jacobian iteration;
         their h_work[it, 0] is the number of rays traced for the gradient.  Under set_state_bounds every trial state and
-        every accepted state is state_bound(x + dx); state_on_bounds of x tells which elements the box holds."""
+        every accepted state is state_bound(x + dx); state_on_bounds of x tells which elements the box holds.  Under
+        set_scene_overflow(OVERFLOW_ISOLATE) a trial that cannot be traced has h_status TRIAL_OVERFLOW and h_tcost NaN, a
+        slice whose current state cannot be traced ends RET_FAILED, and last_scene_overflow() counts both."""
         g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, rowptr)
         nr, nd = g.shape[1], self.nd
         ns, n = len(lay["sfirst"]), int(lay["wptr"][-1])
@@ -1096,6 +1121,14 @@ class ParamOut(C.Structure):
 
 
 RET_ACTIVE, RET_CONVERGED, RET_STALLED, RET_MAXITER = 0, 1, 2, 3      # JUR_RET_*
+RET_FAILED = 4                         # JUR_RET_FAILED: the slice's current state could not be traced (OVERFLOW_ISOLATE)
+OVERFLOW_ERROR, OVERFLOW_ISOLATE = 0, 1                               # JUR_OVERFLOW_*
+TRIAL_OVERFLOW = -2                    # JUR_TRIAL_OVERFLOW, a value of h_status: a ray of that trial could not be traced
+
+
+def np_overflows(npts):
+    """jur_np_overflows (host arithmetic, no GPU): does a ray with that many LOS points count as untraceable?"""
+    return bool(lib().jur_np_overflows(int(npts)))
 
 
 class RetrieveIn(C.Structure):
