@@ -555,6 +555,60 @@ long jur_param_layout(long nslice, long const *wptr, long nr, long const *rowptr
                       long *bwptr, long *cptr, long *bbptr);
 void jur_param_abi_sizes(size_t out[2]);   /* sizeof jur_param_in_t, jur_param_out_t: for bindings that mirror them */
 
+/* Parameter errors of a scene in one call: jur_gain_scene_host, jur_kernel_scene_host under the parameters' windows and
+ * jur_param_slices_host with the gain and K_b left on the device.  Every argument of jur_gain_scene_host as there, plus
+ * jur_param_scene_in_t: ctl_b, of which the ret*_zmin/zmax windows define the parameters b and nothing else is read;
+ *   rowptr_b [nr + 1], jur_scene_layout's for these rays and this atmosphere under those windows (JUR_EINVAL otherwise);
+ *   in, laid out by jur_param_layout of (wptr, rowptr, rowptr_b, sid) as for jur_param_slices_host; bwptr [nslice + 1],
+ *   that layout's, or NULL: where given it is checked against the widths.
+ * jur_param_scene_out_t: out (C optional, sigma_param required when nvar + ncov > 0); kb optional, [rowptr_b[nr] * nd],
+ *   the blocks of jur_kernel_scene_host under ctl_b; weight_eff optional, [nr][nd].
+ * Contract: the doubles of the three calls, bit for bit.  rad, tau, tp, np_out, A, b, cost, nlive, k, every field of diag,
+ *   gain and sigma_comp are jur_gain_scene_host's on the same arguments.  kb is jur_kernel_scene_host's k on a model whose
+ *   windows are ctl_b's, with the same input mask.  weight_eff is the effective weight of jur_gain_scene_host (weight where
+ *   the measurement is live -- with a field of view under the effective mask --, +0.0 elsewhere).  C and sigma_param are
+ *   jur_param_slices_host's on those arrays.  Nothing depends on max_rays_per_pass, on which optional outputs were asked
+ *   for or on the other slices.  A field of view, the hydrostatic balance per slice and a full prior precision of the
+ *   model are honoured as the three entries honour them: the same code runs.
+ *   One corner.  jur_param_slices_host pads the measurements of a slice to a multiple of 16 with exact zeros, and
+ *   fma(+0, +0, c) turns a chain that stands at -0.0 into +0.0.  Here the chains of C are cut where the passes are, and each
+ *   stretch is padded: an element of C can differ from jur_param_slices_host's in the sign of a zero, and only where a
+ *   partial chain is exactly -0.0 at a pass boundary or at the end -- which takes products G * K_b that underflow to zero.
+ * On the device.  Phase 1 is the body of jur_gain_scene_host; the gain and the effective weights are written to a buffer
+ *   the model owns beside the slab of the scene entries.  Phase 2 runs the Jacobian passes under ctl_b's windows, cut by
+ *   jur_scene_passes (rowptr_b, the cap; with a field of view whole scans); after the quotients of a pass the chains of C
+ *   are continued over the live measurements of its rays, in accumulators that stay in that buffer; the blocks of a pass
+ *   go home only where kb is given.  Phase 3 is the quadratic forms on the finished C.  No K_b beyond one pass is ever
+ *   resident; the gain is copied home only where gout->gain is given.  The buffer (gain, weights, C, the parameter
+ *   covariances, sigma_param, the layout) is counted against the workspace budget before everything else: JUR_ENOMEM
+ *   before anything is launched where it does not fit in half of it, and max_rays_per_pass == 0 is derived from what is
+ *   left.  jur_model_scene_bytes: the device bytes the scene entries hold at present, the slab and this buffer.
+ * Refusals: what the three entries refuse, in their words under this entry's name.  Before anything is launched: the
+ *   checks of jur_param_slices_host on nvar, ncov, var and cov, bwptr against the widths, rowptr and rowptr_b against the
+ *   layouts, a NaN window in ctl_b.
+ * The model's own retrieval windows are in force afterwards, after an error too, and it holds atm.  The kernels' time
+ *   counts into jur_model_last_scene_ms. */
+typedef struct {
+  ctl_t const *ctl_b;
+  long const *rowptr_b;        /* [nr + 1] */
+  long const *bwptr;           /* [nslice + 1] or NULL */
+  jur_param_in_t const *in;
+} jur_param_scene_in_t;
+typedef struct {
+  jur_param_out_t const *out;
+  double *kb;                  /* optional, [rowptr_b[nr] * nd] */
+  double *weight_eff;          /* optional, [nr][nd] */
+} jur_param_scene_out_t;
+int  jur_param_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                          double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                          double const *prior_ivar, jur_diag_out_t const *diag, jur_gain_in_t const *gin, jur_gain_out_t const *gout,
+                          jur_param_scene_in_t const *pin, jur_param_scene_out_t const *pout,
+                          double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass);
+void jur_param_scene_abi_sizes(size_t out[2]);   /* sizeof jur_param_scene_in_t, jur_param_scene_out_t */
+long jur_model_scene_bytes(jur_model_t const *m);
+/* the share of the per-pass kernel of phase 2 within jur_model_last_scene_ms (after jur_model_last_kernel_ms, as that) */
+int  jur_model_last_cross_ms(jur_model_t *m, double *out_ms, long *out_launches);
+
 /* The retrieval windows of a model.  A model keeps a copy of the control block it was created with, and every entry that
  * derives its state from it -- the scene entries (jur_kernel_scene_host ... jur_gain_scene_host) and jur_kernel, with
  * jur_state_size -- reads the windows there.  jur_model_set_ret_windows copies retp_zmin/zmax, rett_zmin/zmax,

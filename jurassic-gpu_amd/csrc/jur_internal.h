@@ -337,6 +337,10 @@ typedef struct {
 } jur_scene_param_t;
 /* the cross-state matrices, then (nvar + ncov > 0) the quadratic forms, in stream order */
 int jurk_scene_param(jur_scene_param_t const *a, long ntile, long ngroups, void *stream);
+/* jur_param_scene_host: the chains of C continued over the rays of one pass, C read and written in place.  pmap: [ntile][5]
+ * as jur_param_pass_maps makes it; the kb row of a ray lies in a->kb at koffb[ray] - kb0 (the buffer of the pass); of *a
+ * cmap, pptr, var, cov and sig are not read. */
+int jurk_scene_cross_pass(jur_scene_param_t const *a, int const *pmap, long ntile, long kb0, void *stream);
 enum { JUR_PARAM_TILE = 64, JUR_PARAM_ROWS = 64, JUR_PARAM_MAXCOMP = 8 };
 /* host arithmetic of jur_param_slices_host (jur_scene.c; no GPU).  jur_param_layout_as: jur_param_layout under the name
  * `who` in its messages.  jur_param_check_args: the structs.  jur_param_check_bwptr: bwptr against the widths of the rays.
@@ -349,6 +353,16 @@ int jur_param_check_args(char const *who, jur_param_in_t const *in, jur_param_ou
 int jur_param_check_bwptr(char const *who, long nslice, long const *bwptr, long const *bw);
 int jur_param_check_values(char const *who, long nslice, long const *bwptr, long const *bbptr, jur_param_in_t const *in);
 long jur_param_maps(long nslice, long const *wptr, long const *bwptr, int *cmap);
+/* the passes of jur_param_scene_host (jur_scene.c; no GPU).  jur_param_pass_range: the stretch [*lo, *hi) of srays (the
+ * ascending ray list of slice s at sptr[s] .. sptr[s + 1]) that holds its rays inside [r0, r1); empty: *lo == *hi.
+ * jur_param_pass_maps: the tiles of C of the slices that have rays in [r0, r1), in the order the rays of the pass first
+ * meet them, row-major within a slice: pmap[5 t] = s, then i0, j0 as jur_param_maps, then lo, hi of jur_param_pass_range.
+ * mark [nslice] is the caller's scratch, all zeros before the first pass of a call and carried from pass to pass (passes
+ * are told apart by r0: each is mapped once); pmap has room for the tiles of all slices, jur_param_maps' count.  Returns
+ * the number of tiles. */
+void jur_param_pass_range(long const *sptr, int const *srays, long s, long r0, long r1, long *lo, long *hi);
+long jur_param_pass_maps(long const *wptr, long const *bwptr, long const *sptr, int const *srays, int const *sid, long r0, long r1,
+                         long *mark, int *pmap);
 /* host checks of the full prior precision (jur_scene.c; no GPU): what is read of R, the layout of a call against the one
  * set, the arguments of jur_prior_corr_host */
 int jur_prior_check_R(char const *who, long nslice, long const *wptr, double const *R);

@@ -37,6 +37,7 @@
 //   jur_scene_gain_kernel  gain matrix G = S K^T W of a scene's slices over the ragged blocks, a workgroup per 64 x 64 tile;
 //   jur_scene_budget_kernel  the row sums of G^2 var per error source, a lane per state element (jur_gain_scene_host).
 //   jur_scene_cross_kernel  cross-state matrix C = G^T Kb of a scene's slices over the ragged blocks, a workgroup per 64 x 64 tile;
+//   jur_scene_cross_pass_kernel  the same chains continued over the rays of one pass (jur_param_scene_host);
 //   jur_scene_param_kernel  diag(C Sigma C^T) per parameter covariance, a workgroup per 64 rows of C (jur_param_slices_host).
 //   jur_intpol_kernel     regridding of a track / point-cloud atmosphere (intpol_atm, jurassic.c:675-804).
 //   jur_kat_*_kernel      known-answer hooks for tests: the device functions on arrays of inputs.
@@ -3381,21 +3382,33 @@ __global__ __launch_bounds__(256) void jur_scene_budget_kernel(jur_scene_gain_t 
 // never loaded; fma(+0, +0, c) leaves every chain as it was.  The lanes of a wavefront read two neighbouring doubles of a
 // GI row (broadcast to 16 lanes each) and 16 consecutive doubles of a KB row: no bank conflicts, so the rows need none
 // of the padding jur_scene_gain_kernel's transposed staging needs.  LDS: 16 KB, two barriers per 16 measurements.
+//
+// PASS (jur_param_scene_host): the same chains over the rays of one pass.  The tile comes with the stretch [lo, hi) of
+// srays that holds the rays of its slice inside the pass (pmap: slice, first element, first parameter, lo, hi); every
+// chain starts from the value C holds -- +0.0 before the first pass -- and is stored back, and the kb row of a ray lies
+// in the buffer of the pass, kb0 doubles before where koffb puts it.  The measurements of a slice are taken in the same
+// ascending order, 16 at a time from lo: only the exact zeros that pad a stretch to 16 move with the cuts.
 #define CROSS_TILE 64
 #define CROSS_NB 16
-__global__ __launch_bounds__(256) void jur_scene_cross_kernel(jur_scene_param_t a) {
+template <bool PASS>
+__device__ __forceinline__ void scene_cross_body(jur_scene_param_t const &a, int const *map, long kb0) {
   __shared__ double GI[CROSS_NB][CROSS_TILE], KB[CROSS_NB][CROSS_TILE];
-  long const s = a.cmap[3 * (long)blockIdx.x];
-  int const i0 = a.cmap[3 * (long)blockIdx.x + 1], j0 = a.cmap[3 * (long)blockIdx.x + 2];
+  int const *const tile = map + (PASS ? 5 : 3) * (long)blockIdx.x;
+  long const s = tile[0];
+  int const i0 = tile[1], j0 = tile[2];
   int const tid = threadIdx.x, tr = tid >> 4, tc = tid & 15, col = tid & 63, wv = tid >> 6, nd = a.nd;
   int const w = (int)(a.wptr[s + 1] - a.wptr[s]), wb = (int)(a.bwptr[s + 1] - a.bwptr[s]);
-  long const q0 = a.sptr[s], M = (a.sptr[s + 1] - q0) * nd;
+  long const q0 = PASS ? (long)tile[3] : a.sptr[s], M = ((PASS ? (long)tile[4] : a.sptr[s + 1]) - q0) * nd;
   bool const gi_in = i0 + col < w, kb_in = j0 + col < wb;
+  double *const C = a.C + a.cptr[s];
   double acc[4][4];
 #pragma unroll
   for (int p = 0; p < 4; p++)
 #pragma unroll
-    for (int q = 0; q < 4; q++) acc[p][q] = 0.;
+    for (int q = 0; q < 4; q++) {
+      int const i = i0 + tr + 16 * p, j = j0 + tc + 16 * q;
+      acc[p][q] = (PASS && i < w && j < wb) ? C[(long)i * wb + j] : 0.;
+    }
   for (long m0 = 0; m0 < M; m0 += CROSS_NB) {
     __syncthreads();                                        // (the micro-tiles of the last 16 have been taken)
 #pragma unroll
@@ -3409,7 +3422,7 @@ __global__ __launch_bounds__(256) void jur_scene_cross_kernel(jur_scene_param_t 
         long const r = a.srays[q0 + qq];
         if (a.weff[r * nd + id] > 0) {
           if (gi_in) g = a.gain[a.koff[r] + (long)id * w + i0 + col];
-          if (kb_in) kb = a.kb[a.koffb[r] + (long)id * wb + j0 + col];
+          if (kb_in) kb = a.kb[a.koffb[r] - kb0 + (long)id * wb + j0 + col];
         }
       }
       GI[ml][col] = g; KB[ml][col] = kb;
@@ -3426,7 +3439,6 @@ __global__ __launch_bounds__(256) void jur_scene_cross_kernel(jur_scene_param_t 
         for (int q = 0; q < 4; q++) acc[p][q] = fma(gi[p], kj[q], acc[p][q]);
     }
   }
-  double *const C = a.C + a.cptr[s];
 #pragma unroll
   for (int p = 0; p < 4; p++) {
     int const i = i0 + tr + 16 * p;
@@ -3437,6 +3449,10 @@ __global__ __launch_bounds__(256) void jur_scene_cross_kernel(jur_scene_param_t 
       if (j < wb) C[(long)i * wb + j] = acc[p][q];
     }
   }
+}
+__global__ __launch_bounds__(256) void jur_scene_cross_kernel(jur_scene_param_t a) { scene_cross_body<false>(a, a.cmap, 0); }
+__global__ __launch_bounds__(256) void jur_scene_cross_pass_kernel(jur_scene_param_t a, int const *pmap, long kb0) {
+  scene_cross_body<true>(a, pmap, kb0);
 }
 
 // The quadratic forms on C_s: sigma_param[c][e] = sqrt(diag(C Sigma_c C^T)) for up to 8 components, the diagonal ones
@@ -3934,6 +3950,12 @@ extern "C" int jurk_scene_gain(jur_scene_gain_t const *a, long ntile, long ngrou
 }
 
 // (the tile and workgroup counts are the host's: jur_param_maps and pptr[nslice]; the quadratic forms only with components)
+extern "C" int jurk_scene_cross_pass(jur_scene_param_t const *a, int const *pmap, long ntile, long kb0, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ntile > 0) hipLaunchKernelGGL(jur_scene_cross_pass_kernel, dim3((unsigned)ntile), dim3(256), 0, s, *a, pmap, kb0);
+  return (int)hipGetLastError();
+}
+
 extern "C" int jurk_scene_param(jur_scene_param_t const *a, long ntile, long ngroups, void *stream) {
   hipStream_t const s = (hipStream_t)stream;
   if (ntile > 0) hipLaunchKernelGGL(jur_scene_cross_kernel, dim3((unsigned)ntile), dim3(256), 0, s, *a);

@@ -114,7 +114,7 @@ struct jur_model {
   /* timing */
   int timing;
   hipEvent_t *evpool;           /* 2 events per timed launch                     */
-  unsigned char *evkind;        /* 0 trace, 1 ega, 2 combine, 3 fused (pencil), 4 contributions, 5 scene Jacobian */
+  unsigned char *evkind;        /* 0 trace, 1 ega, 2 combine, 3 fused (pencil), 4 contributions, 5 scene Jacobian, 6 the chains of C per pass */
   int ntimed;
   double pencil_ms;
   long pencil_launches;
@@ -124,8 +124,13 @@ struct jur_model {
   long ctb_cap;
   void *d_scene;                /* jur_kernel_scene_host: grow-only device slab (base rows, descriptors, per-ray arrays, blocks of a pass) */
   size_t scene_bytes;
-  double scene_ms;              /* its kernels' share (kind 5), collected with the others */
+  void *d_side;                 /* jur_param_scene_host: grow-only device buffer beside the slab, for what outlives the body's
+                                   calls (gain, effective weights, C, the parameter covariances, sigma_param, the layout) */
+  size_t side_bytes;
+  double scene_ms;              /* its kernels' share (kinds 5 and 6), collected with the others */
   long scene_launches;
+  double cross_ms;              /* ... of which jur_scene_cross_pass_kernel's (kind 6) */
+  long cross_launches;
 };
 
 #define JUR_MAX_TIMED 4096
@@ -327,7 +332,7 @@ void jur_model_destroy(jur_model_t *m) {
   (void)hipSetDevice(m->device);
   if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_rec = NULL;
   void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp, m->d_blk_order,
-                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_fov_shape, m->d_kq, m->d_ctb, m->d_scene, m->d_pp};
+                  m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_fov_shape, m->d_kq, m->d_ctb, m->d_scene, m->d_side, m->d_pp};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
   if (m->h_io) (void)hipHostFree(m->h_io);
@@ -615,6 +620,7 @@ static int ensure_workspace(jur_model_t *m, long nr) {
 }
 
 long jur_model_workspace_bytes(jur_model_t const *m) { return m->los_bytes; }
+long jur_model_scene_bytes(jur_model_t const *m) { return m ? (long)(m->scene_bytes + m->side_bytes) : 0; }
 long jur_model_table_bytes(jur_model_t const *m) { return m->table_bytes; }
 
 /* What a caller that plans its memory wants to know about a device before it allocates: PCI bus id (text), free and
@@ -737,7 +743,10 @@ int jur_model_last_kernel_ms(jur_model_t *m, double out_ms[3], long out_launches
     if (m->evkind[i] < 3) { out_ms[m->evkind[i]] += ms; out_launches[m->evkind[i]]++; }
     else if (m->evkind[i] == 3) { m->pencil_ms += ms; m->pencil_launches++; }
     else if (m->evkind[i] == 4) { m->contrib_ms += ms; m->contrib_launches++; }
-    else { m->scene_ms += ms; m->scene_launches++; }
+    else {
+      m->scene_ms += ms; m->scene_launches++;
+      if (m->evkind[i] == 6) { m->cross_ms += ms; m->cross_launches++; }
+    }
   }
   m->ntimed = 0;
   return JUR_OK;
@@ -768,6 +777,15 @@ int jur_model_last_scene_ms(jur_model_t *m, double *out_ms, long *out_launches) 
   *out_launches = m->scene_launches;
   m->scene_ms = 0;
   m->scene_launches = 0;
+  return JUR_OK;
+}
+
+/* ... and, within that share, of jur_scene_cross_pass_kernel (jur_param_scene_host; same protocol) */
+int jur_model_last_cross_ms(jur_model_t *m, double *out_ms, long *out_launches) {
+  *out_ms = m->cross_ms;
+  *out_launches = m->cross_launches;
+  m->cross_ms = 0;
+  m->cross_launches = 0;
   return JUR_OK;
 }
 
@@ -1614,17 +1632,23 @@ static void ret_windows_copy(ctl_t *to, ctl_t const *from, int ng, int nw) {
   for (int w = 0; w < nw; w++) { to->retk_zmin[w] = from->retk_zmin[w]; to->retk_zmax[w] = from->retk_zmax[w]; }
 }
 
-int jur_model_set_ret_windows(jur_model_t *m, ctl_t const *ctl) {
-  char const *const who = "jur_model_set_ret_windows";
-  if (!m || !ctl) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
-  int const ng = m->view.ng, nw = m->view.nw;
+static int ret_windows_check(char const *who, int ng, int nw, ctl_t const *ctl) {
   if (ctl->retp_zmin != ctl->retp_zmin || ctl->retp_zmax != ctl->retp_zmax) { jur_set_error("%s: the window of p is NaN", who); return JUR_EINVAL; }
   if (ctl->rett_zmin != ctl->rett_zmin || ctl->rett_zmax != ctl->rett_zmax) { jur_set_error("%s: the window of T is NaN", who); return JUR_EINVAL; }
   for (int g = 0; g < ng; g++)
     if (ctl->retq_zmin[g] != ctl->retq_zmin[g] || ctl->retq_zmax[g] != ctl->retq_zmax[g]) { jur_set_error("%s: the window of gas %d is NaN", who, g); return JUR_EINVAL; }
   for (int w = 0; w < nw; w++)
     if (ctl->retk_zmin[w] != ctl->retk_zmin[w] || ctl->retk_zmax[w] != ctl->retk_zmax[w]) { jur_set_error("%s: the window of extinction %d is NaN", who, w); return JUR_EINVAL; }
-  ret_windows_copy(m->ctl, ctl, ng, nw);               /* (after every check: what was set stays set on a refusal) */
+  return JUR_OK;
+}
+
+int jur_model_set_ret_windows(jur_model_t *m, ctl_t const *ctl) {
+  char const *const who = "jur_model_set_ret_windows";
+  if (!m || !ctl) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  int const ng = m->view.ng, nw = m->view.nw;
+  int const rc = ret_windows_check(who, ng, nw, ctl);
+  if (rc) return rc;
+  ret_windows_copy(m->ctl, ctl, ng, nw);              /* (after every check: what was set stays set on a refusal) */
   return JUR_OK;
 }
 
@@ -2368,17 +2392,18 @@ static int gain_maps_make(char const *who, long nslice, long const *wptr, long c
 
 /* Enqueues on s: the uploads of the variances and the tile map, the gain and budget kernels, the copies home of what was
  * asked for.  q comes with everything but weff, var, gmap, gain and sigc, which lie in the part W of the slab (weff
- * filled by the caller); nk: the doubles of all blocks.  The caller waits for the stream before the host arrays go. */
+ * filled by the caller); nk: the doubles of all blocks.  gain_at (jur_param_scene_host): the gain is written there and the
+ * part has no room for it.  The caller waits for the stream before the host arrays go. */
 static int gain_enqueue(jur_model_t *m, hipStream_t s, char const *who, jur_scene_gain_t *q, double *W, size_t nk, long ntile,
-                        long ngroups, int const *hmap, jur_gain_in_t const *in, jur_gain_out_t const *out) {
+                        long ngroups, int const *hmap, jur_gain_in_t const *in, jur_gain_out_t const *out, double *gain_at) {
   size_t const NB = (size_t)q->nb, NRD = (size_t)q->nrd, NC = (size_t)in->ncomp;
-  gain_layout_t const o = gain_layout(nk, NB, NRD, NC, (size_t)ntile);
+  gain_layout_t const o = gain_layout(gain_at ? 0 : nk, NB, NRD, NC, (size_t)ntile);
   hipError_t e = hipSuccess;
   if (NC && NRD) e = hipMemcpyAsync(W + o.var, in->var, sizeof(double) * NC * NRD, hipMemcpyHostToDevice, s);
   if (ntile > 0 && e == hipSuccess) e = hipMemcpyAsync(W + o.map, hmap, sizeof(int) * 3 * (size_t)ntile, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
   q->ncomp = in->ncomp;
-  q->weff = W + o.weff; q->var = W + o.var; q->gmap = (int const *)(W + o.map); q->gain = W + o.gain; q->sigc = W + o.sigc;
+  q->weff = W + o.weff; q->var = W + o.var; q->gmap = (int const *)(W + o.map); q->gain = gain_at ? gain_at : W + o.gain; q->sigc = W + o.sigc;
   int const ti = scene_timed_begin(m, s);
   int const ek = jurk_scene_gain(q, ntile, ngroups, s);
   scene_timed_end(m, ti, s);
@@ -2603,6 +2628,38 @@ static int prior_check_values(char const *who, long nslice, long const *wptr, do
 typedef struct { jur_retrieve_in_t const *in; jur_retrieve_out_t const *out; atm_t *atm_ret; } scene_retrieve_t;
 /* what jur_gradient_scene_host brings: the blocks of all rays, laid out by rowptr */
 typedef struct { double const *k; } scene_grad_t;
+/* what jur_param_scene_host brings to its two calls of the body.  Phase 1 is jur_gain_scene_host's, with the gain and the
+ * effective weights written to the model's side buffer (gain, weff).  Phase 2 is jur_kernel_scene_host's under the
+ * parameters' windows, where after the quotients of every pass the chains of C are continued: q holds the kernel's
+ * arguments (all in the side buffer but kb, the blocks of the pass); wptr .. sid are the host's layout of the retrieved
+ * state, mark and hmap its scratch for the tiles of a pass and d_pmap their place on the device.  bytes: the side buffer,
+ * counted against the budget before the parts of the slab. */
+typedef struct {
+  int phase;
+  size_t bytes;
+  double *gain, *weff;
+  jur_scene_param_t q;
+  long const *wptr, *bwptr, *sptr;
+  int const *srays, *sid;
+  long *mark;
+  int *hmap, *d_pmap;
+} scene_param_t;
+
+/* the tiles of C that the rays [r0, r1) of a pass reach, and the kernel on them; kb: the blocks of the pass, the first of
+ * them kb0 doubles into the blocks of all rays.  The host's map is free again once the stream has been waited for. */
+static int param_pass_extend(jur_model_t *m, hipStream_t s, char const *who, scene_param_t *pm, long r0, long r1, double const *kb, long kb0) {
+  long const nt = jur_param_pass_maps(pm->wptr, pm->bwptr, pm->sptr, pm->srays, pm->sid, r0, r1, pm->mark, pm->hmap);
+  if (nt == 0) return JUR_OK;
+  hipError_t const e = hipMemcpyAsync(pm->d_pmap, pm->hmap, sizeof(int) * 5 * (size_t)nt, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
+  pm->q.kb = kb;
+  int const ti = scene_timed_begin(m, s);
+  if (ti >= 0) m->evkind[ti] = 6;
+  int const ek = jurk_scene_cross_pass(&pm->q, pm->d_pmap, nt, kb0, s);
+  scene_timed_end(m, ti, s);
+  if (ek) { jur_set_error("%s: cross-state kernel launch failed", who); return JUR_EHIP; }
+  return JUR_OK;
+}
 
 /* ---- what jur_kernel_scene_host's family and jur_trial_scene_host open with ------------------------------------------- */
 /* the atmosphere a scene entry can take: no global balance (hydz_tail: why not, in the entry's words), 2..JUR_NP points,
@@ -2692,13 +2749,14 @@ static int scene_open(scene_open_t *o, jur_model_t *m, char const *who, atm_t co
  * the quotients of every pass, and the blocks go home only where k is given.  With sv (jur_step_scene_host; nm is given
  * then) the systems are solved where they lie after the last pass, and A and b go home only where they are given.  With
  * gd (jur_gradient_scene_host; nm is given then, without A) the passes are forward-only and b, cost and nlive are summed
- * from the caller's blocks.  What the call opens with is scene_open's; of the device slab (scene_slab_reserve) the
+ * from the caller's blocks.  With pm (jur_param_scene_host) the call is that entry's phase 1 (dg with the gain is given
+ * then) or phase 2 (nothing else is given; k may be NULL).  What the call opens with is scene_open's; of the device slab (scene_slab_reserve) the
  * solver's part is laid out by solve_layout and the diagnostics' by diag_layout, which the loop reads too. */
 static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                              double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
                              scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt, scene_diag_t const *dg,
-                             scene_grad_t const *gd) {
-  char const *const who = gd ? "jur_gradient_scene_host" : rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : (dg && dg->gin) ? "jur_gain_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+                             scene_grad_t const *gd, scene_param_t *pm) {
+  char const *const who = pm ? "jur_param_scene_host" : gd ? "jur_gradient_scene_host" : rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : (dg && dg->gin) ? "jur_gain_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
   if (rt) m->ov_cells = m->ov_failed = 0;           /* (the counts of jur_model_last_scene_overflow are this call's) */
@@ -2735,7 +2793,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if ((rc = scene_open(&op, m, who, atm, nr, geom, rad, rowptr,
-                       (!k && !nm) ? "%s: null argument" : (gd && !gd->k) ? "%s: null argument (k): the state has elements" : NULL,
+                       (!k && !nm && !pm) ? "%s: null argument" : (gd && !gd->k) ? "%s: null argument (k): the state has elements" : NULL,
                        nm != NULL, nm ? nm->y : NULL, nm ? nm->weight : NULL))) goto done;
   int *const copy0 = op.len + NR, *const sid = op.sid;   /* (copy0: the ints that scene_open leaves to its caller) */
   long const *const rp = op.rp, nslice = op.nslice, nrs = op.nrs;
@@ -2863,6 +2921,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   /* what follows joins the slab part by part, each refused where it no longer fits beside those before it (an entry
    * with diagnostics has no solve, no loop and no held blocks) */
   double used = (double)atm_bytes;
+  size_t const side_bytes = pm ? pm->bytes : 0;     /* (what jur_param_scene_host holds beside the slab) */
+  if (side_bytes > 0 && !scene_fits(m, &used, side_bytes)) {
+    jur_set_error("%s: the gain, the effective weights, C and the parameter covariances (%zu bytes) do not fit beside the stacked "
+                  "atmosphere (%zu bytes) in the workspace budget: call with the rays of fewer slices at a time", who, side_bytes, atm_bytes);
+    rc = JUR_ENOMEM; goto done;
+  }
   if (hy_bytes > 0 && !scene_fits(m, &used, hy_bytes)) {
     jur_set_error("%s: the segment lists of the hydrostatic balance (%zu bytes) do not fit beside the stacked atmosphere (%zu "
                   "bytes) in the workspace budget: call with the rays of fewer slices at a time", who, hy_bytes, atm_bytes);
@@ -2919,7 +2983,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   int const retain = gd || every > 1 || held;
   size_t const nkret = retain ? (size_t)rp[nr] * (size_t)nd : 0;
   size_t const nrc = retain ? (NR + 1) + NR + (RS + 1) : 0;
-  size_t const ngn = held ? gain_layout(nkret, (size_t)nb, NRD, (size_t)dg->gin->ncomp, (size_t)ngtile).end : 0;
+  size_t const ngn = held ? gain_layout(pm ? 0 : nkret, (size_t)nb, NRD, (size_t)dg->gin->ncomp, (size_t)ngtile).end : 0;
   size_t const kret_bytes = sizeof(double) * (nkret + nrc + ngn);
   if (held && !scene_fits(m, &used, kret_bytes)) {
     jur_set_error("%s: the retained blocks of all rays (%ld columns, %zu bytes), the gain and the budget's arrays (%zu bytes) do not "
@@ -2941,7 +3005,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
      * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
      * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
-    long const avail = (m->ws_budget - (long)atm_bytes - (long)hy_bytes - (long)fov_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes - (long)kret_bytes) / 16;
+    long const avail = (m->ws_budget - (long)atm_bytes - (long)hy_bytes - (long)fov_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes - (long)kret_bytes - (long)side_bytes) / 16;
     cap = avail / (long)slot_bytes;
     if (cap < 4096) cap = 4096;
   }
@@ -3341,6 +3405,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         scene_timed_end(m, ti, s);
         if (ek) { jur_set_error("%s: gradient kernel launch failed", who); rc = JUR_EHIP; goto done; }
       }
+      if (pm && pm->phase == 2 && (rc = param_pass_extend(m, s, who, pm, r0, r1, a.k, rp[r0] * nd))) goto done;
       /* the blocks of the pass go home (where asked for); the one wait of the pass */
       e = (nk > 0 && k) ? hipMemcpyAsync(k + (size_t)rp[r0] * nd, a.k, sizeof(double) * (size_t)nk, hipMemcpyDeviceToHost, s) : hipSuccess;
       if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -3359,7 +3424,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       /* S and the breakdowns lie where the diagnostics left them, the blocks of all rays where the passes left them; the
        * effective weights are formed from the results of the passes, under the mask the sums were formed under */
       diag_layout_t const dl = diag_layout((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, d_R != NULL, (size_t)ninv, (size_t)ndtile);
-      gain_layout_t const gl = gain_layout(nkret, (size_t)nb, NRD, (size_t)dg->gin->ncomp, (size_t)ngtile);
+      gain_layout_t const gl = gain_layout(pm ? 0 : nkret, (size_t)nb, NRD, (size_t)dg->gin->ncomp, (size_t)ngtile);
       jur_scene_weff_t wq;
       wq.n = (long)NRD; wq.mask = fov ? d_live : D + o_inrad; wq.f = D + o_rad; wq.y = D + o_y; wq.weight = D + o_w;
       wq.weff = D + o_gn + gl.weff;
@@ -3372,7 +3437,10 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       gq2.nslice = nslice; gq2.nd = nd; gq2.wptr = nq.wptr; gq2.aptr = nq.aptr; gq2.sptr = nq.sptr; gq2.srays = nq.srays;
       gq2.koff = d_koff; gq2.gptr = d_gptr; gq2.status = (int const *)(D + o_dg + dl.stat); gq2.S = D + o_dg + dl.S; gq2.k = D + o_k;
       gq2.nrd = (long)NRD; gq2.nb = nb;
-      if ((rc = gain_enqueue(m, s, who, &gq2, D + o_gn, nkret, ngtile, ngroups, gmap, dg->gin, dg->gout))) goto done;
+      if ((rc = gain_enqueue(m, s, who, &gq2, D + o_gn, nkret, ngtile, ngroups, gmap, dg->gin, dg->gout, pm ? pm->gain : NULL))) goto done;
+      if (pm && NRD && hipMemcpyAsync(pm->weff, wq.weff, sizeof(double) * NRD, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+        (void)hipGetLastError(); jur_set_error("%s: keeping the effective weights failed", who); rc = JUR_EHIP; goto done;
+      }
     }
     if (!looping) break;
 
@@ -3534,7 +3602,7 @@ static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
 int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                           double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL, NULL, NULL, NULL));
 }
 
 int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3542,7 +3610,7 @@ int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double cons
                           double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_normal_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, NULL, NULL, NULL));
 }
 
 int jur_gradient_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3551,7 +3619,7 @@ int jur_gradient_scene_host(jur_model_t *m, atm_t const *atm, long nr, double co
   if (!m || !atm) { jur_set_error("jur_gradient_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, NULL, b, cost, nlive};
   scene_grad_t const gd = {k};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, NULL, NULL, &gd));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, NULL, NULL, &gd, NULL));
 }
 
 int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3561,7 +3629,7 @@ int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const 
   if (!m || !atm) { jur_set_error("jur_step_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_solve_t const sv = {in, out};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL, NULL, NULL, NULL));
 }
 
 int jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3571,7 +3639,7 @@ int jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double co
   if (!m || !atm) { jur_set_error("jur_diagnose_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_diag_t const dg = {prior_ivar, out, NULL, NULL};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, NULL));
 }
 
 int jur_gain_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3581,7 +3649,7 @@ int jur_gain_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const 
   if (!m || !atm || !in || !out) { jur_set_error("jur_gain_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_diag_t const dg = {prior_ivar, diag, in, out};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, NULL));
 }
 
 int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, long nr, double const *const geom[7],
@@ -3591,7 +3659,7 @@ int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, l
   if (!m || !atm0 || !atm_ret) { jur_set_error("jur_retrieve_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, NULL, NULL, NULL, NULL};
   scene_retrieve_t const rt = {in, out, atm_ret};
-  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt, NULL, NULL);
+  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt, NULL, NULL, NULL);
   if (rc) return scene_restore_atm(m, atm0, rc);    /* (on success the model holds atm_ret) */
   if (nr != 0) return JUR_OK;
   if (atm_ret != atm0) memcpy(atm_ret, atm0, sizeof(atm_t));   /* no rays: nothing was retrieved */
@@ -4011,7 +4079,7 @@ int jur_gain_slices_host(jur_model_t *m, long nslice, long const *wptr, double c
     q.nslice = nslice; q.nd = nd; q.wptr = L; q.aptr = L + (NS + 1); q.sptr = L + 2 * (NS + 1); q.gptr = L + 3 * (NS + 1);
     q.koff = L + 4 * (NS + 1); q.srays = d_srays; q.status = status ? d_stat : NULL; q.S = D + o_S; q.k = D + o_k;
     q.nrd = (long)NRD; q.nb = nb;
-    if ((rc = gain_enqueue(m, s, who, &q, D + o_gn, nk, ntile, ngroups, hmap, in, out))) goto done;
+    if ((rc = gain_enqueue(m, s, who, &q, D + o_gn, nk, ntile, ngroups, hmap, in, out, NULL))) goto done;
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
   }
@@ -4109,6 +4177,193 @@ done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
   free(ptr); free(srays); free(hmap);
   return rc;
+}
+
+/* ---- parameter errors of a scene in one call (jur_param_scene_host) --------------------------------------------------- */
+/* The model's side buffer (grow-only; it holds nothing between calls): selects the device and waits for the model's earlier
+ * calls as scene_slab_reserve does, which may free and grow the slab between the phases and so cannot hold what this does. */
+static int scene_side_reserve(jur_model_t *m, char const *who, size_t bytes) {
+  if (hipSetDevice(m->device) != hipSuccess) { jur_set_error("%s: cannot select the device", who); return JUR_EHIP; }
+  int const rc = wait_done(m, m->stream);
+  if (rc) return rc;
+  if (bytes > m->side_bytes) {
+    if (m->d_side) (void)hipFree(m->d_side);
+    m->d_side = NULL; m->side_bytes = 0;
+    if (hipMalloc(&m->d_side, bytes) != hipSuccess) {
+      (void)hipGetLastError(); jur_set_error("%s: no device memory for %zu bytes", who, bytes); return JUR_ENOMEM;
+    }
+    m->side_bytes = bytes;
+  }
+  return JUR_OK;
+}
+
+/* The side buffer: the longs wptr | bwptr | cptr | bbptr | sptr | pptr | koff | koffb, then the doubles gain | weff | C |
+ * var | cov | sig, then the ints pmap (the tiles of one pass) | srays.  The model's windows are the caller's to put back. */
+static int param_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                            double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                            double const *prior_ivar, jur_diag_out_t const *diag, jur_gain_in_t const *gin, jur_gain_out_t const *gout,
+                            jur_param_scene_in_t const *pin, jur_param_scene_out_t const *pout,
+                            double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
+  char const *const who = "jur_param_scene_host";
+  if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
+  int rc = jur_param_check_args(who, pin->in, pout->out);
+  if (rc) return rc;
+  if (!pin->ctl_b || !pin->rowptr_b) { jur_set_error("%s: null argument (%s)", who, !pin->ctl_b ? "ctl_b" : "rowptr_b"); return JUR_EINVAL; }
+  int const nd = m->ctl->nd, ng = m->view.ng, nw = m->view.nw;
+  if ((rc = ret_windows_check(who, ng, nw, pin->ctl_b))) return rc;
+  if ((rc = scene_atm_check(m, who, "every p, T or H2O element moves every pressure and the Jacobian has no blocks: use jur_kernel", atm))) return rc;
+  if (nr == 0) return JUR_OK;
+  if (nr > 0x7fffffffL) { jur_set_error("%s: at most 2^31-1 rays per call", who); return JUR_EINVAL; }
+  if (!geom || !rad || !tau || !tp || !rowptr) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  jur_param_in_t const *const in = pin->in;
+  jur_param_out_t const *const out = pout->out;
+  size_t const NR = (size_t)nr, NRD = NR * (size_t)nd, NC = (size_t)(in->nvar + in->ncov), nrow = 6 + (size_t)ng + nw;
+  int *first = (int *)malloc(sizeof(int) * 4 * NR), *len = first ? first + NR : NULL, *sid = len ? len + NR : NULL, *srays = sid ? sid + NR : NULL;
+  long *rp = (long *)malloc(sizeof(long) * 2 * (NR + 1)), *rpb = rp ? rp + NR + 1 : NULL, *ptr = NULL, *mark = NULL;
+  ctl_t *cb = (ctl_t *)malloc(sizeof(ctl_t));
+  jur_scene_slice_t *sl = NULL, *slb = NULL;
+  double *hrad = NULL;                              /* the input mask, then the outputs of phase 2 that nobody reads: rad | tau | tp */
+  int *hmap = NULL;
+  int enqueued = 0;
+  if (!first || !rp || !cb) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+  /* the two layouts: the retrieved state under the model's windows, the parameters under ctl_b's */
+  if ((rc = jur_scene_layout(m->ctl, atm, nr, geom[0], first, len, rp))) goto done;
+  if (memcmp(rp, rowptr, sizeof(long) * (NR + 1))) {
+    jur_set_error("%s: rowptr is not jur_scene_layout's for these rays, this atmosphere and these windows", who);
+    rc = JUR_EINVAL; goto done;
+  }
+  long const nslice = jur_scene_distinct(atm->np, nr, first, len, rp, sid, &sl);
+  if (nslice < 0) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+  memcpy(cb, m->ctl, sizeof(ctl_t));
+  ret_windows_copy(cb, pin->ctl_b, ng, nw);
+  if ((rc = jur_scene_layout(cb, atm, nr, geom[0], first, len, rpb))) goto done;
+  if (memcmp(rpb, pin->rowptr_b, sizeof(long) * (NR + 1))) {
+    jur_set_error("%s: rowptr_b is not jur_scene_layout's for these rays, this atmosphere and the windows of ctl_b", who);
+    rc = JUR_EINVAL; goto done;
+  }
+  size_t const NS = (size_t)nslice, nlong = 6 * (NS + 1) + 2 * NR;
+  ptr = (long *)calloc(nlong, sizeof(long));
+  mark = (long *)calloc(NS ? NS : 1, sizeof(long));
+  hrad = (double *)malloc(sizeof(double) * (2 * NRD + 3 * NR));
+  if (!ptr || !mark || !hrad) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+  {
+    long *const wptr = ptr, *const bw = wptr + NS + 1, *const cptr = bw + NS + 1, *const bbptr = cptr + NS + 1, *const sptr = bbptr + NS + 1,
+         *const pptr = sptr + NS + 1, *const koff = pptr + NS + 1, *const koffb = koff + NR;
+    for (long q = 0; q < nslice; q++) {
+      wptr[q + 1] = wptr[q] + sl[q].nel;
+      pptr[q + 1] = pptr[q] + (sl[q].nel + JUR_PARAM_ROWS - 1) / JUR_PARAM_ROWS;
+    }
+    long const nc = jur_param_layout_as(who, nslice, wptr, nr, rp, rpb, sid, bw, cptr, bbptr);
+    if (nc < 0) { rc = (int)nc; goto done; }
+    if (pin->bwptr && (rc = jur_param_check_bwptr(who, nslice, pin->bwptr, bw))) goto done;
+    if ((rc = jur_param_check_values(who, nslice, bw, bbptr, in))) goto done;
+    for (long r = 0; r < nr; r++) { koff[r] = rp[r] * nd; koffb[r] = rpb[r] * nd; }
+    long const nlist = jur_scene_rays_by_slice(nr, nslice, sid, sptr, srays);
+    for (long q = 0; q < nslice; q++)
+      if ((sptr[q + 1] - sptr[q]) * nd > 0x7fffffffL) {
+        jur_set_error("%s: 2^31 measurements of slice %ld: call with the rays of fewer slices at a time", who, q);
+        rc = JUR_EINVAL; goto done;
+      }
+    long const ntile = jur_param_maps(nslice, wptr, bw, NULL), ngroups = pptr[nslice];
+    if (ntile > 0x7fffffffL / 5 || ngroups > 0x7fffffffL) { jur_set_error("%s: 2^31 workgroups: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
+    size_t const nk = (size_t)rp[nr] * (size_t)nd, nb = (size_t)wptr[nslice], nbw = (size_t)bw[nslice], nbb = (size_t)bbptr[nslice],
+                 NV = (size_t)in->nvar, NF = (size_t)in->ncov;
+    size_t const o_g = nlong, o_we = o_g + nk, o_C = o_we + NRD, o_var = o_C + (size_t)nc, o_cov = o_var + NV * nbw, o_sig = o_cov + NF * nbb,
+                 o_int = o_sig + NC * nb;
+    size_t const side_bytes = sizeof(double) * o_int + sizeof(int) * (5 * (size_t)ntile + (size_t)nlist + 1);
+    /* what phase 2 stacks under ctl_b's windows is known here: both phases are refused before the first is launched */
+    long const nsb = jur_scene_distinct(atm->np, nr, first, len, rpb, srays, &slb);   /* (srays: scratch until the lists are made again below) */
+    if (nsb < 0) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+    double ntb = (double)atm->np;
+    for (long q = 0; q < nsb; q++) ntb += (double)slb[q].nel * (double)slb[q].len;
+    double const atm_b_bytes = sizeof(double) * (double)(nrow + 1) * ntb;
+    if ((double)side_bytes + atm_b_bytes > (double)(m->ws_budget / 2)) {
+      jur_set_error("%s: the gain, the effective weights, C and the parameter covariances (%zu bytes) do not fit beside the atmosphere "
+                    "stacked under the windows of ctl_b (%.0f bytes) in the workspace budget: call with the rays of fewer slices at a time",
+                    who, side_bytes, atm_b_bytes);
+      rc = JUR_ENOMEM; goto done;
+    }
+    (void)jur_scene_rays_by_slice(nr, nslice, sid, sptr, srays);
+    if (ntile > 0 && !(hmap = (int *)malloc(sizeof(int) * 5 * (size_t)ntile))) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
+    memcpy(hrad, rad, sizeof(double) * NRD);
+    if ((rc = scene_side_reserve(m, who, side_bytes))) goto done;
+    double *const D = (double *)m->d_side;
+    long *const L = (long *)m->d_side;
+    int *const d_pmap = (int *)(D + o_int), *const d_srays = d_pmap + 5 * (size_t)ntile;
+    hipStream_t const s = m->stream;
+
+    /* phase 1: the body of jur_gain_scene_host; the gain and the effective weights stay in the side buffer */
+    scene_normal_t const nm = {y, weight, A, b, cost, nlive};
+    scene_diag_t const dg = {prior_ivar, diag, gin, gout};
+    scene_param_t pm;
+    memset(&pm, 0, sizeof pm);
+    pm.phase = 1; pm.bytes = side_bytes; pm.gain = D + o_g; pm.weff = D + o_we;
+    if ((rc = kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, &pm))) goto done;
+    enqueued = 1;
+    hipError_t e = hipSuccess;
+    if (pout->weight_eff) {
+      /* jurk_scene_weff does not look at the slices (a ray without one is in no list): such a ray's measurements are
+       * not live, and the array that goes home says so */
+      if (nslice > 0) e = hipMemcpyAsync(pout->weight_eff, pm.weff, sizeof(double) * NRD, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      for (long r = 0; r < nr && e == hipSuccess; r++)
+        if (sid[r] < 0) memset(pout->weight_eff + (size_t)r * (size_t)nd, 0, sizeof(double) * (size_t)nd);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(L, ptr, sizeof(long) * nlong, hipMemcpyHostToDevice, s);
+    if (NV * nbw > 0 && e == hipSuccess) e = hipMemcpyAsync(D + o_var, in->var, sizeof(double) * NV * nbw, hipMemcpyHostToDevice, s);
+    if (NF * nbb > 0 && e == hipSuccess) e = hipMemcpyAsync(D + o_cov, in->cov, sizeof(double) * NF * nbb, hipMemcpyHostToDevice, s);
+    if (nlist && e == hipSuccess) e = hipMemcpyAsync(d_srays, srays, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, s);
+    if (nc && e == hipSuccess) e = hipMemsetAsync(D + o_C, 0, sizeof(double) * (size_t)nc, s);   /* (every chain starts from +0.0) */
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    jur_scene_param_t *const q = &pm.q;
+    q->nslice = nslice; q->nd = nd; q->nvar = in->nvar; q->ncov = in->ncov;
+    q->wptr = L; q->bwptr = L + (NS + 1); q->cptr = L + 2 * (NS + 1); q->bbptr = L + 3 * (NS + 1); q->sptr = L + 4 * (NS + 1);
+    q->pptr = L + 5 * (NS + 1); q->koff = L + 6 * (NS + 1); q->koffb = q->koff + NR;
+    q->srays = d_srays; q->gain = D + o_g; q->weff = D + o_we; q->var = D + o_var; q->cov = D + o_cov;
+    q->nb = (long)nb; q->nbw = (long)nbw; q->nbb = (long)nbb; q->C = D + o_C; q->sig = D + o_sig;
+
+    /* phase 2: the Jacobian passes under ctl_b's windows, the chains of C continued after each; rad (the input mask),
+     * tau and tp of this call are the forward model's once more and go nowhere */
+    if (ntile > 0 || pout->kb) {
+      pm.phase = 2; pm.wptr = wptr; pm.bwptr = bw; pm.sptr = sptr; pm.srays = srays; pm.sid = sid; pm.mark = mark; pm.hmap = hmap; pm.d_pmap = d_pmap;
+      double *const tp2[3] = {hrad + 2 * NRD, hrad + 2 * NRD + NR, hrad + 2 * NRD + 2 * NR};
+      ret_windows_copy(m->ctl, pin->ctl_b, ng, nw);
+      if ((rc = kernel_scene_body(m, atm, nr, geom, hrad, hrad + NRD, tp2, NULL, rpb, pout->kb, max_rays_per_pass, NULL, NULL, NULL, NULL, NULL, &pm))) goto done;
+    }
+
+    /* phase 3: the quadratic forms on the finished C; what was asked for comes home */
+    if (NC * nb > 0) {
+      int const ti = scene_timed_begin(m, s);
+      int const ek = jurk_scene_param(q, 0, ngroups, s);
+      scene_timed_end(m, ti, s);
+      if (ek) { jur_set_error("%s: kernel launch failed", who); rc = JUR_EHIP; goto done; }
+    }
+    if (nc && out->C) e = hipMemcpyAsync(out->C, q->C, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost, s);
+    if (NC * nb > 0 && e == hipSuccess) e = hipMemcpyAsync(out->sigma_param, q->sig, sizeof(double) * NC * nb, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    enqueued = 0;
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
+  }
+done:
+  if (enqueued) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
+  free(first); free(rp); free(ptr); free(mark); free(cb); free(sl); free(slb); free(hrad); free(hmap);
+  return rc;
+}
+
+int jur_param_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
+                         double *const tp[3], int *np_out, long const *rowptr, double const *y, double const *weight,
+                         double const *prior_ivar, jur_diag_out_t const *diag, jur_gain_in_t const *gin, jur_gain_out_t const *gout,
+                         jur_param_scene_in_t const *pin, jur_param_scene_out_t const *pout,
+                         double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
+  if (!m || !atm || !gin || !gout || !pin || !pout) { jur_set_error("jur_param_scene_host: null argument"); return JUR_EINVAL; }
+  ctl_t *own = (ctl_t *)malloc(sizeof(ctl_t));      /* the model's own windows, in force again whatever happens */
+  if (!own) { jur_set_error("jur_param_scene_host: out of memory"); return JUR_ENOMEM; }
+  ret_windows_copy(own, m->ctl, m->view.ng, m->view.nw);
+  int const rc = param_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, y, weight, prior_ivar, diag, gin, gout, pin, pout,
+                                  A, b, cost, nlive, k, max_rays_per_pass);
+  ret_windows_copy(m->ctl, own, m->view.ng, m->view.nw);
+  free(own);
+  return scene_restore_atm(m, atm, rc);
 }
 
 /* The upstream parametrisation of the prior, built and inverted on the device.  The slab of the scene entries serves:
@@ -4222,7 +4477,7 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
   c->h_io = NULL; c->h_io_cap = 0; c->h_pkg = NULL; c->h_atm = NULL; c->h_atm_n = 0; c->h_atm_cap = 0; c->h_status = NULL;
   c->stream = NULL; c->stream2 = NULL; c->ev_mask = NULL; c->ev_trace = NULL;
   c->host_call = 0; c->have_done = 0; c->ev_done = NULL; c->d_fov = NULL; c->fov_cap = 0; c->fov_n = 0; c->fov_shape = NULL; c->d_fov_shape = NULL; c->pp_nslice = 0; c->pp_wptr = NULL; c->pp_R = NULL; c->d_pp = NULL; c->d_kq = NULL; c->h_kq = NULL; c->kq_cap = 0;
-  c->d_ctb = NULL; c->ctb_cap = 0;
+  c->d_ctb = NULL; c->ctb_cap = 0; c->d_side = NULL; c->side_bytes = 0;
   c->timing = 0; c->evpool = NULL; c->evkind = NULL; c->ntimed = 0;
   if (hipSetDevice(c->device) != hipSuccess || create_streams(c) != JUR_OK ||
       hipMalloc((void **)&c->d_status, sizeof(int)) != hipSuccess || hipMemset(c->d_status, 0, sizeof(int)) != hipSuccess) {

@@ -730,6 +730,42 @@ long jur_param_maps(long nslice, long const *wptr, long const *bwptr, int *cmap)
   return nt;
 }
 
+/* ---- parameter errors of a scene in one call (jur_param_scene_host): the tiles of a pass ----------------------------- */
+void jur_param_scene_abi_sizes(size_t out[2]) { out[0] = sizeof(jur_param_scene_in_t); out[1] = sizeof(jur_param_scene_out_t); }
+
+/* the first position in [a, b) of the ascending list whose ray is >= r */
+static long rays_lower_bound(int const *srays, long a, long b, long r) {
+  while (a < b) {
+    long const mid = a + (b - a) / 2;
+    if (srays[mid] < r) a = mid + 1; else b = mid;
+  }
+  return a;
+}
+
+void jur_param_pass_range(long const *sptr, int const *srays, long s, long r0, long r1, long *lo, long *hi) {
+  *lo = rays_lower_bound(srays, sptr[s], sptr[s + 1], r0);
+  *hi = rays_lower_bound(srays, *lo, sptr[s + 1], r1);
+}
+
+long jur_param_pass_maps(long const *wptr, long const *bwptr, long const *sptr, int const *srays, int const *sid, long r0, long r1,
+                         long *mark, int *pmap) {
+  long nt = 0;
+  for (long r = r0; r < r1; r++) {
+    long const q = sid[r];
+    if (q < 0 || mark[q] == r0 + 1) continue;
+    mark[q] = r0 + 1;
+    long const w = wptr[q + 1] - wptr[q], wb = bwptr[q + 1] - bwptr[q];
+    long lo, hi;
+    jur_param_pass_range(sptr, srays, q, r0, r1, &lo, &hi);
+    for (long i0 = 0; i0 < w; i0 += JUR_PARAM_TILE)
+      for (long j0 = 0; j0 < wb; j0 += JUR_PARAM_TILE, nt++) {
+        int *const t = pmap + 5 * nt;
+        t[0] = (int)q; t[1] = (int)i0; t[2] = (int)j0; t[3] = (int)lo; t[4] = (int)hi;
+      }
+  }
+  return nt;
+}
+
 int jur_avk_summary(ctl_t const *ctl, atm_t const *atm, int first, int len, double const *avk, double *dofs_q, double *area,
                     double *resolution) {
   if (!ctl || !atm || first < 0 || len < 0 || (long)first + len > atm->np) {

@@ -193,6 +193,19 @@ def lib():
             L.jur_param_abi_sizes.restype = None
             L.jur_model_set_ret_windows.argtypes = [C.c_void_p, C.c_void_p]
             L.jur_model_ret_windows.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "jur_param_scene_host"):       # (an A/B library from before the one-call parameter errors has none of these)
+            L.jur_param_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), ip_, lp_,
+                                               dp, dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, dp, dp, dp,
+                                               lp_, dp, C.c_long]
+            L.jur_param_scene_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
+            L.jur_param_scene_abi_sizes.restype = None
+            L.jur_model_scene_bytes.restype = C.c_long
+            L.jur_model_scene_bytes.argtypes = [C.c_void_p]
+            L.jur_model_last_cross_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), lp_]
+            L.jur_param_pass_range.argtypes = [lp_, ip_, C.c_long, C.c_long, C.c_long, lp_, lp_]
+            L.jur_param_pass_range.restype = None
+            L.jur_param_pass_maps.restype = C.c_long
+            L.jur_param_pass_maps.argtypes = [lp_, lp_, lp_, ip_, ip_, C.c_long, C.c_long, lp_, ip_]
         if hasattr(L, "jur_model_set_scene_overflow"):   # (an A/B library from before untraceable rays were isolated has none)
             L.jur_model_set_scene_overflow.argtypes = [C.c_void_p, C.c_int]
             L.jur_model_scene_overflow.argtypes = [C.c_void_p]
@@ -981,6 +994,70 @@ class Model:
                                          _p(ww), C.byref(pin), C.byref(pout)))
         return res
 
+    def param_scene(self, ctl_b, atm, geom, y, weight, var_b=None, cov_b=None, prior_ivar=None, rad_in=None, var=None,
+                    want_gain=False, want_kb=False, want_C=True, max_rays_per_pass=0):
+        """The error that quantities b which are not retrieved leave in the retrieved state of a scene, in one call
+        (jur_param_scene_host): what param_error_scene computes, bit for bit, with the gain and the blocks K_b of the
+        parameters left on the device.  ctl_b: its retrieval windows define the parameters; var_b (nvar, bwptr[-1]) /
+        cov_b (ncov, bbptr[-1]) as for param_slices; var (ncomp, nr, nd) as for gain_scene.
+        -> the dict of param_error_scene (gain only with want_gain, C only with want_C), plus kb with want_kb: the flat
+        blocks of kernel_scene under ctl_b, laid out by rowptr_b."""
+        g, lay, rp, yy, ww, rad = self._scene_inputs(atm, geom, y, weight, rad_in, None)
+        nr, nd = g.shape[1], self.nd
+        cb = abi.ctl_t()
+        C.memmove(C.byref(cb), C.byref(self.ctl), C.sizeof(abi.ctl_t))
+        for name in ("retp_zmin", "retp_zmax", "rett_zmin", "rett_zmax", "retq_zmin", "retq_zmax", "retk_zmin", "retk_zmax"):
+            setattr(cb, name, getattr(ctl_b, name))
+        rb = _scene_layout(cb, atm, g[0] if nr else np.zeros(0))["rowptr"]
+        play = param_layout(lay["wptr"], rp, rb, lay["sid"])
+        ns, n, na = len(lay["sfirst"]), int(lay["wptr"][-1]), int(lay["aptr"][-1])
+        nbw, nbb, nc = int(play["bwptr"][-1]), int(play["bbptr"][-1]), int(play["cptr"][-1])
+        vv = None if var_b is None else np.ascontiguousarray(var_b, dtype=np.float64)
+        cc = None if cov_b is None else np.ascontiguousarray(cov_b, dtype=np.float64)
+        if vv is not None and (vv.ndim != 2 or vv.shape[1] != nbw):
+            raise ValueError("var_b must be (nvar, %d)" % nbw)
+        if cc is not None and (cc.ndim != 2 or cc.shape[1] != nbb):
+            raise ValueError("cov_b must be (ncov, %d)" % nbb)
+        nvar, ncov = 0 if vv is None else vv.shape[0], 0 if cc is None else cc.shape[0]
+        tau = np.zeros((nr, nd))
+        tp = np.zeros((3, nr))
+        npts = np.zeros(nr, dtype=np.int32)
+        cost, nlive = np.zeros(ns), np.zeros(ns, dtype=np.int64)
+        dout, res, keep = _diag_structs(ns, n, na, prior_ivar, False, False)
+        gin, gout, gres, gkeep = _gain_structs(n, nr, nd, int(rp[-1]) * nd, var, want_gain)
+        pres = dict(play, sigma_param=np.zeros((nvar + ncov, n)), rowptr_b=rb, weight_eff=np.zeros((nr, nd)))
+        if want_C:
+            pres["C"] = np.zeros(nc)
+        if want_kb:
+            pres["kb"] = np.zeros(int(rb[-1]) * nd)
+        lp_ = C.POINTER(C.c_long)
+        pin = ParamIn(nvar, ncov, _p(vv) if nvar else None, _p(cc) if ncov else None)
+        pout = ParamOut(_p(pres["C"]) if want_C else None, _p(pres["sigma_param"]) if nvar + ncov else None)
+        sin = ParamSceneIn(C.addressof(ctl_b), rb.ctypes.data_as(lp_), play["bwptr"].ctypes.data_as(lp_), C.pointer(pin))
+        sout = ParamSceneOut(C.pointer(pout), _p(pres["kb"]) if want_kb else None, _p(pres["weight_eff"]))
+        garr = (dp * 7)(*[_p(g[i]) for i in range(7)])
+        tarr = (dp * 3)(*[_p(tp[i]) for i in range(3)])
+        _chk(lib().jur_param_scene_host(self.h, C.byref(atm), nr, garr, _p(rad), _p(tau), tarr,
+                                        npts.ctypes.data_as(C.POINTER(C.c_int)), rp.ctypes.data_as(lp_), _p(yy), _p(ww),
+                                        None if keep is None else _p(keep), C.byref(dout), C.byref(gin), C.byref(gout),
+                                        C.byref(sin), C.byref(sout), None, None, _p(cost), nlive.ctypes.data_as(lp_), None,
+                                        max_rays_per_pass))
+        out = dict(lay, rad=rad, tau=tau, tp=np.ascontiguousarray(tp.T), np=npts, cost=cost, nlive=nlive, **res)
+        out.update(gres)
+        out.update(pres)
+        out["elements_b"] = [scene_elements(ctl_b, atm, int(f), int(l)) for f, l in zip(out["sfirst"], out["slen"])]
+        return out
+
+    def cross_ms(self):
+        """The share of param_scene's per-pass kernel within scene_ms (call kernel_ms first)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        _chk(lib().jur_model_last_cross_ms(self.h, C.byref(ms), C.byref(n)))
+        return dict(cross_ms=ms.value, cross_launches=n.value)
+
+    def scene_bytes(self):
+        """The device bytes the scene entries hold at present: their slab and param_scene's buffer beside it."""
+        return lib().jur_model_scene_bytes(self.h)
+
     def set_ret_windows(self, ctl):
         """The retrieval windows of ctl (retp, rett, retq[ng], retk[nw] _zmin/_zmax, nothing else) become the model's
         (jur_model_set_ret_windows): from the next call on kernel_scene and the other scene entries, kernel and
@@ -1118,6 +1195,17 @@ class ParamIn(C.Structure):
 class ParamOut(C.Structure):
     """jur_param_out_t"""
     _fields_ = [("C", dp), ("sigma_param", dp)]
+
+
+class ParamSceneIn(C.Structure):
+    """jur_param_scene_in_t"""
+    _fields_ = [("ctl_b", C.c_void_p), ("rowptr_b", C.POINTER(C.c_long)), ("bwptr", C.POINTER(C.c_long)),
+                ("in_", C.POINTER(ParamIn))]
+
+
+class ParamSceneOut(C.Structure):
+    """jur_param_scene_out_t"""
+    _fields_ = [("out", C.POINTER(ParamOut)), ("kb", dp), ("weight_eff", dp)]
 
 
 RET_ACTIVE, RET_CONVERGED, RET_STALLED, RET_MAXITER = 0, 1, 2, 3      # JUR_RET_*
