@@ -974,7 +974,9 @@ int  jur_model_set_workspace_budget(jur_model_t *m, long bytes);
  * and radiance update of a ray as producer/consumer wavefronts of one workgroup, the line of sight handed on through
  * LDS -- instead of the three batched kernels: the sizes the reference's callers use (packages of <= NR rays).
  * rays_per_group: rays per workgroup, 0 = chosen from the call size.  Configurations with more (channel, gas)
- * chains per ray than the LDS rings hold use the batched kernels whatever the size.  Same results bit for bit. */
+ * chains per ray than the LDS rings hold use the batched kernels whatever the size.  Same results bit for bit.
+ * The fused kernel is emissivity growth only: a model whose control block says FORMOD 1 accepts the call and runs
+ * every size through the batched kernels (jur_model_last_pencil_ms reports no launch). */
 int  jur_model_set_pencil(jur_model_t *m, long max_rays, int rays_per_group);
 /* Process-wide: lanes per ray of the batched ray tracer (1 or 4; 0 = chosen per launch: a quad of lanes per ray for
  * launches of up to 65 536 rays with at least three emitters, one lane otherwise).  With four lanes the refraction
@@ -1037,6 +1039,28 @@ enum { JUR_ARITH_FAST = 0, JUR_ARITH_EXACT = 1 };
 int  jur_model_set_arithmetic(jur_model_t *m, int mode);
 int  jur_model_arithmetic(jur_model_t const *m);
 
+/* Band model, ctl->formod (FORMOD in a control file): 2 (default) the emissivity-growth approximation, 1 the
+ * Curtis-Godson approximation (CGA).  Upstream computes the Curtis-Godson means and asserts FORMOD 1 out
+ * (jr_common.h:701-707); here it runs, through every entry, with one rule.  For one ray, gas g, channel d, LOS points
+ * ip = 0 .. np - 1 with p, T and the gas's column u (the records jur_kat_traceray shows):
+ *   means   a += u p, b += u T, w += u from 0, products and sums rounded separately (no fma), in the order of
+ *           curtis_godson() (jr_common.h:455-473); cgp = a / w, cgt = b / w, cgu = w by true divisions;
+ *   path transmittance tau of the gas after segment ip, from tau_prev (1 before the first segment):
+ *     1. tau_prev < 1e-9: 0 (the opaque gate of ega_eps, jr_common.h:239);
+ *     2. no table for (g, d), or one of the nt < 2 / nu < 2 rules of ega_eps (:240-246) at (cgp, cgt): tau_prev;
+ *     3. w == 0 (nothing of the gas on the path so far): tau_prev, tested before any bracket search;
+ *     4. otherwise ipr = locate_id(p axis, cgp), it0 / it1 = locate_id(T axes of levels ipr, ipr + 1, cgt), the four
+ *        corners e = c01(get_eps(curve, cgu)), two blends in T at cgt and one in p at cgp, each c01(lip(...)) as in
+ *        ega_eps (:259-265): tau = 1 - eps_t.
+ *   tau is not limited to tau_prev: a Curtis-Godson path transmittance may rise from one segment to the next.  The
+ *   radiance update (segment transmittance of all gases as the quotient of the products of path transmittances,
+ *   continua, source, surface, brightness temperature) is the one of FORMOD 2.
+ * jur_model_set_arithmetic chooses between the reference's divisions and the strict-table arithmetic as for the
+ * emissivity-growth look-up.  The look-up runs in the batched kernels only: the fused kernel of small calls does not
+ * know the Curtis-Godson rule, so FORMOD 1 calls of any size take the ray sort and the three batched kernels
+ * (jur_model_set_pencil stays accepted and has no effect).  Slot [1] of jur_model_last_kernel_ms counts whichever
+ * look-up kernel ran. */
+
 /* Frees the process-global state behind formod() / formod_GPU() / formod_pencil(): the lanes (streams, atmosphere,
  * workspaces, pinned images) and the emissivity tables loaded by the first call.  Upstream keeps its counterparts for
  * the life of the process (GPUdrivers.cu:263-273, 309; jr_common.h:60-78).  Waits for calls in flight; returns the
@@ -1060,6 +1084,9 @@ int  jur_model_last_contrib_ms(jur_model_t *m, double *out_ms, long *out_launche
  *   1 = warm-started searches, 2 = + descriptors in LDS, 3 = + reciprocal bracket widths (what the bench runs);
  *   JUR_EINVAL when the tables do not admit the mode.  chain != 0: one lane evaluates the n inputs in order,
  *   carrying the search state from one to the next as the kernel does along a ray.
+ * jur_kat_cga_eps: the Curtis-Godson look-up of pair (ig, id) (FORMOD 1, see there): out[i] = the new path transmittance
+ *   by steps 1, 2 and 4 from tau[i] and the means cgt[i], cgu[i], cgp[i]; modes and chain as for jur_kat_ega_eps
+ *   (0 = the reference's bisections and divisions, 3 = what jur_cga_kernel runs on strict tables).
  * jur_kat_continua: out[4][n] = continua_ctmco2/h2o/n2/o2 (jr_common.h:315-390) of channel id (0 outside a window).
  * jur_kat_update: what 0: src[i] = src_planck_core(a[i]); (rad, tau)[i] updated by new_obs_core with
  *   tau_gas = b[i], beta_ds = c[i] (jr_common.h:220-224, 293-300); what 1: add_surface_core with surface
@@ -1074,6 +1101,8 @@ int  jur_model_last_contrib_ms(jur_model_t *m, double *out_ms, long *out_launche
  *   records on through LDS and cannot be read this way. */
 int jur_kat_ega_eps(jur_model_t *m, int ig, int id, long n, double const *tau, double const *t, double const *u,
                     double const *p, int mode, int chain, double *out);
+int jur_kat_cga_eps(jur_model_t *m, int ig, int id, long n, double const *tau, double const *cgt, double const *cgu,
+                    double const *cgp, int mode, int chain, double *out);
 int jur_kat_continua(jur_model_t *m, int id, long n, double const *p, double const *t, double const *q,
                      double const *u_co2, double const *u_h2o, double *out);
 int jur_kat_update(jur_model_t *m, int id, long n, int what, double const *a, double const *b, double const *c,

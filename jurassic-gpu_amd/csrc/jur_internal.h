@@ -112,7 +112,8 @@ typedef struct {
 /* kernel launchers (jur_kernels.hip); return hipError_t as int */
 int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream);   /* fills atm_pslope */
 int jurk_launch_trace(jur_view_t const *v, jur_chunk_t const *c, void *stream);
-int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, void *stream);
+/* the look-up kernel of the model's band model: cga == 0 emissivity growth (FORMOD 2), != 0 Curtis-Godson (FORMOD 1) */
+int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, int cga, void *stream);
 int jurk_launch_combine(jur_view_t const *v, jur_chunk_t const *c, void *stream);
 /* contributions of the emitters from the transmittance plane of the chunk (after jurk_launch_ega, before the plane is
  * reused; reads c->rad as the NaN mask, so before jurk_launch_combine): rad_c / tau_c [ng + 1][nr][nd] by ray id */
@@ -150,6 +151,8 @@ int jurk_launch_intpol(int ip, int ng, int nw, int ns, int nd_, int nx, double c
 
 /* known-answer hooks (tests): device functions on arrays, see jurassic_hip.h */
 int jurk_kat_ega(jur_view_t const *v, int g, int d, long n, double const *tau, double const *t, double const *u, double const *p,
+                 int mode, int chain, double *out, void *stream);
+int jurk_kat_cga(jur_view_t const *v, int g, int d, long n, double const *tau, double const *cgt, double const *cgu, double const *cgp,
                  int mode, int chain, double *out, void *stream);
 int jurk_kat_continua(jur_view_t const *v, int d, long n, double const *p, double const *t, double const *q, double const *u_co2,
                       double const *u_h2o, double *out, void *stream);

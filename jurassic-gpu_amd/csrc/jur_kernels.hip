@@ -9,6 +9,9 @@
 //                         emissivity-growth recurrence along the line of sight with its band
 //                         table look-ups (jr_common.h:237-280); writes the gas's transmittance of the
 //                         path up to and including every segment.
+//   jur_cga_kernel        the same launch for a model with FORMOD 1: the Curtis-Godson means of the path so far as
+//                         three running sums per lane (jr_common.h:455-473) and one table look-up at the means per
+//                         segment; writes the same plane.
 //   jur_combine_kernel    one lane per ray, one channel per workgroup: continua
 //                         (jr_common.h:315-390), product over gases, Planck source (:220-224),
 //                         radiance update (:293-300); surface term, brightness temperature and
@@ -1321,6 +1324,150 @@ __device__ __forceinline__ double ega_eps_warm_quad(jur_view_t const &v, jur_int
   }
 }
 
+// ---- Curtis-Godson look-up (FORMOD 1) ---------------------------------------------------------------------------
+// The gas's transmittance of the path up to and including a segment, read off the tables at the Curtis-Godson means
+// of that path: t = cgt, u = cgu (the whole column so far), p = cgp.  The brackets and the two blends are those of
+// ega_eps (jr_common.h:241-246, :259-265); the four corners are c01(get_eps(curve, cgu)) -- one forward evaluation per
+// curve where the emissivity-growth look-up inverts the curve first (get_u) and then evaluates it.  Answers 0 once the
+// path has gone opaque (tau < 1e-9, :239) and tau, "no change", where ega_eps answers 1 (no table, nt < 2, nu < 2).
+// The result is NOT limited to tau: a Curtis-Godson path transmittance may rise from one segment to the next.
+//
+// cga_tau_exact: the reference's bisections probe for probe and its divisions operand for operand (any table).
+template <bool LDS>
+__device__ __forceinline__ double cga_tau_exact(jur_int2 const pr, PairDesc<LDS> const &D, double tau, double t, double u, double p) {
+  if (tau < 1e-9) return 0.;
+  if (pr.a < 2) return tau;
+  void const *const ueb = D.ueb;
+  int ilo = 0, ihi = pr.a - 1;
+  while (ihi > ilo + 1) {
+    int const i = (ihi + ilo) >> 1;
+    if (D.lvl(i).p > p) ihi = i; else ilo = i;
+  }
+  Lvl const l0 = D.lvl(ilo), l1 = D.lvl(ilo + 1);
+  if (l0.nt < 2 || l1.nt < 2) return tau;
+  unsigned const k0 = (unsigned)l0.c0, k1 = (unsigned)l1.c0;
+  ilo = 0; ihi = l0.nt - 1;
+  while (ihi > ilo + 1) {
+    int const i = (ihi + ilo) >> 1;
+    if (D.crv(k0 + i).t > t) ihi = i; else ilo = i;
+  }
+  Crv const c00 = D.crv(k0 + ilo), c01_ = D.crv(k0 + ilo + 1);
+  if (c00.nu < 2 || c01_.nu < 2) return tau;
+  ilo = 0; ihi = l1.nt - 1;
+  while (ihi > ilo + 1) {
+    int const i = (ihi + ilo) >> 1;
+    if (D.crv(k1 + i).t > t) ihi = i; else ilo = i;
+  }
+  Crv const c10 = D.crv(k1 + ilo), c11 = D.crv(k1 + ilo + 1);
+  if (c10.nu < 2 || c11.nu < 2) return tau;
+  unsigned const e0[4] = {(unsigned)c00.e0, (unsigned)c01_.e0, (unsigned)c10.e0, (unsigned)c11.e0};
+  int const n[4] = {c00.nu, c01_.nu, c10.nu, c11.nu};
+  double ec[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    Ue a, b;
+    ld_pair(ueb, e0[k] + bisect_curve<false>(ueb, e0[k], n[k], u), a, b);
+    ec[k] = c01(lip((double)a.u, (double)a.eps, (double)b.u, (double)b.eps, u));
+  }
+  double const eps_p0 = c01(lip(c00.t, ec[0], c01_.t, ec[1], t));
+  double const eps_p1 = c01(lip(c10.t, ec[2], c11.t, ec[3], t));
+  return 1. - c01(lip(l0.p, eps_p0, l1.p, eps_p1, p));
+}
+
+// cga_tau_warm: sorted tables, search state (br, ia, ib) carried as in ega_eps_warm -- the column only grows along a
+// ray, so the curve searches move one way.  Without RCPB the reference's divisions (the same doubles as
+// cga_tau_exact); with RCPB the strict-table arithmetic described at lip_slope: bracket records, the curve's slope,
+// reciprocal widths for the blends -- the forward half of ega_eps_warm<.., true, true>.
+template <bool LDS, bool RCPB>
+__device__ __forceinline__ double cga_tau_warm(jur_int2 const pr, PairDesc<LDS> const &D, double tau, double t, double u, double p,
+                                               unsigned &br, unsigned &ia, unsigned &ib) {
+  if (tau < 1e-9) return 0.;
+  if (pr.a < 2) return tau;
+  void const *const ueb = D.ueb;
+  int ipr = min((int)(br & 0xffu), pr.a - 2);
+  Lvl l0 = D.lvl(ipr), l1 = D.lvl(ipr + 1);
+  if ((p < l0.p) | (p >= l1.p)) {
+    while (p < l0.p && ipr > 0) { --ipr; l1 = l0; l0 = D.lvl(ipr); }
+    while (p >= l1.p && ipr < pr.a - 2) { ++ipr; l0 = l1; l1 = D.lvl(ipr + 1); }
+  }
+  br = (br & ~0xffu) | (unsigned)ipr;
+  if (l0.nt < 2 || l1.nt < 2) return tau;
+  unsigned const k0 = (unsigned)l0.c0, k1 = (unsigned)l1.c0;
+  int it0 = min((int)((br >> 8) & 0xffu), l0.nt - 2), it1 = min((int)((br >> 16) & 0xffu), l1.nt - 2);
+  {
+    Crv c00 = D.crv(k0 + it0), c01_ = D.crv(k0 + it0 + 1), c10 = D.crv(k1 + it1), c11 = D.crv(k1 + it1 + 1);
+    if ((t < c00.t) | (t >= c01_.t) | (t < c10.t) | (t >= c11.t)) {
+      while (t < c00.t && it0 > 0) { --it0; c01_ = c00; c00 = D.crv(k0 + it0); }
+      while (t >= c01_.t && it0 < l0.nt - 2) { ++it0; c00 = c01_; c01_ = D.crv(k0 + it0 + 1); }
+      while (t < c10.t && it1 > 0) { --it1; c11 = c10; c10 = D.crv(k1 + it1); }
+      while (t >= c11.t && it1 < l1.nt - 2) { ++it1; c10 = c11; c11 = D.crv(k1 + it1 + 1); }
+    }
+    br = (unsigned)ipr | ((unsigned)it0 << 8) | ((unsigned)it1 << 16);
+    if (c00.nu < 2 || c01_.nu < 2 || c10.nu < 2 || c11.nu < 2) return tau;
+  }
+  // (as ega_eps_warm: the clamp modifiers below would turn a NaN into 0; tau is not among their operands -- past the
+  // gate the rule does not use it, and a NaN there changes nothing in the reference's arithmetic either)
+  if (RCPB && (t != t || u != u || p != p)) return __builtin_nan("");
+  double eps_p0 = 0, eps_p1 = 0;
+#pragma unroll 1
+  for (int h = 0; h < 2; h++) {  // pressure level l0, then l1: two curves live at a time, as in ega_eps_warm
+    unsigned const kc = h ? k1 + (unsigned)it1 : k0 + (unsigned)it0;
+    Crv const ca = D.crv(kc), cb = D.crv(kc + 1);
+    unsigned const packed = h ? ib : ia;
+    unsigned const e0[2] = {(unsigned)ca.e0, (unsigned)cb.e0};
+    int const n[2] = {ca.nu, cb.nu};
+    int i[2] = {(int)(packed & 0xffffu), (int)(packed >> 16)};
+#pragma unroll
+    for (int k = 0; k < 2; k++) i[k] = min(i[k], n[k] - 2);
+    double ec[2];
+    if constexpr (RCPB) {
+      Rec r[2];
+      ld_rec2(D.recb, e0[0] + i[0], e0[1] + i[1], r[0], r[1]);
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        double ka, kb;
+        seek_rec<false, false>(D.recb, e0[k], n[k], u, i[k], r[k], ka, kb);
+        ec[k] = lip_slope_c01(ka, (double)r[k].e0, r[k].de_du, u);
+      }
+    } else {
+      Ue a[2], b[2];
+#pragma unroll
+      for (int k = 0; k < 2; k++) ld_pair(ueb, e0[k] + i[k], a[k], b[k]);
+#pragma unroll
+      for (int k = 0; k < 2; k++) seek_curve<false>(ueb, e0[k], n[k], u, i[k], a[k], b[k]);
+#pragma unroll
+      for (int k = 0; k < 2; k++) ec[k] = c01(lip((double)a[k].u, (double)a[k].eps, (double)b[k].u, (double)b[k].eps, u));
+    }
+    unsigned const last = (unsigned)i[0] | ((unsigned)i[1] << 16);
+    if (h) ib = last; else ia = last;
+    double e;
+    if constexpr (RCPB) e = lip_mulr_c01(ca.t, ec[0], ec[1], t, D.rt(kc));
+    else e = c01(lip(ca.t, ec[0], cb.t, ec[1], t));
+    if (h) eps_p1 = e; else eps_p0 = e;
+  }
+  if constexpr (RCPB) {
+    int q = ipr;
+    asm volatile("" : "+v"(q));           // the level pressures read again, not kept through both levels (ega_eps_warm)
+    return 1. - lip_mulr_c01(D.lvl(q).p, eps_p0, eps_p1, p, D.rp(q));
+  }
+  return 1. - c01(lip(l0.p, eps_p0, l1.p, eps_p1, p));
+}
+
+// One segment of a ray under FORMOD 1: the running sums of curtis_godson() (jr_common.h:455-473; products and sums
+// rounded separately, the file is compiled without contraction), the means by true divisions, the look-up.  With
+// nothing of the gas on the path so far (w == 0: the means would be 0 / 0) the path transmittance stays as it is.
+template <bool WARM, bool LDS, bool RCPB>
+__device__ __forceinline__ double cga_segment(jur_int2 const pr, PairDesc<LDS> const &D, double tau, double t, double u, double p,
+                                              double &sa, double &sb, double &sw, unsigned &br, unsigned &ia, unsigned &ib) {
+  double const up = u * p, ut = u * t;
+  sa = sa + up; sb = sb + ut; sw = sw + u;
+  if (tau < 1e-9) return 0.;
+  if (sw == 0.) return tau;
+  double const cgp = sa / sw, cgt = sb / sw;
+  if constexpr (WARM) return cga_tau_warm<LDS, RCPB>(pr, D, tau, cgt, sw, cgp, br, ia, ib);
+  else return cga_tau_exact<LDS>(pr, D, tau, cgt, sw, cgp);
+}
+
 // ---------------------------------------------------------------------------------------
 // continua; the channel-only factors come precomputed in jur_chan_t
 // ---------------------------------------------------------------------------------------
@@ -1556,6 +1703,53 @@ __global__ __launch_bounds__(256, RCPB ? JUR_REC_WAVES : 5) void jur_ega_kernel(
     if constexpr (RCPB) tau_path = ega_eps_warm<LDS, true, true>(v, pd, D, tau_path, t, u, p, br, ia, ib);
     else if constexpr (WARM) tau_path *= ega_eps_warm<LDS, false>(v, pd, D, tau_path, t, u, p, br, ia, ib);
     else tau_path *= ega_eps_exact<LDS>(v, pd, D, tau_path, t, u, p);
+    st_stream(out + (size_t)ip * Re, lane, tau_path);
+  }
+}
+
+// jur_cga_kernel: the same launch under FORMOD 1 -- grid, XCD mapping, block order, staged descriptors, tile
+// addressing and output plane of jur_ega_kernel; per lane the three running sums of the Curtis-Godson means and one
+// look-up at the means per segment (cga_segment) in place of the emissivity-growth recurrence.  The radiance update
+// reads the plane unchanged.
+template <bool WARM, bool LDS, bool RCPB>
+__global__ __launch_bounds__(256, RCPB ? JUR_REC_WAVES : 5) void jur_cga_kernel(jur_view_t v, jur_chunk_t c, int nrb) {
+  static_assert(WARM || !RCPB, "reciprocal widths need strictly increasing axes");
+  int const npair = v.nd * v.ng;
+  BlockItem const bi = xcd_block_item((int)blockIdx.x, nrb, npair);
+  if (bi.rb < 0) return;
+  int const rb = ordered_block<1>(c.blk_order, bi.rb), pr = bi.item;         // ray block, pair: uniform
+  int const d = pr / v.ng, g = pr - d * v.ng;
+  int const r = rb * blockDim.x + threadIdx.x;
+  int const pair_idx = g * v.nd + d;
+  jur_int2 const pd = v.pair[pair_idx];
+  if (pd.a < 2) return;                          // no table: transmittance 1, the combine kernel knows
+  PairDesc<LDS> D{v.lvl, v.crv, v.ue + v.pair_e0[pair_idx], (unsigned)pd.b, 0u, 0u, 0u};
+  if constexpr (RCPB) D.recb = v.rec + v.pair_e0[pair_idx];
+  stage_pair<LDS, RCPB>(v, pd, D);
+  if (r >= c.n) return;
+  int const nfield = JUR_F_K + v.nw + v.ng;
+  int const tile = __builtin_amdgcn_readfirstlane(r >> 6);
+  unsigned const lane = (unsigned)(r & 63);
+  size_t const R = (size_t)nfield * 64;
+  double const *const los_tile = c.los + (size_t)tile * los_tile_doubles(nfield);
+  double const *const los_p = los_tile + JUR_F_P * 64, *const los_t = los_tile + JUR_F_T * 64,
+               *const los_u = los_tile + (size_t)(JUR_F_K + v.nw + g) * 64;
+  size_t const Re = (size_t)npair * 64;
+  double *const out = c.eps + eps_tile_point0(c, tile) * Re + (size_t)pr * 64;
+  int const np = c.np[r];
+  double tau_path = 1.0, sa = 0., sb = 0., sw = 0.;
+  unsigned br = 0, ia = 0, ib = 0;
+  // all three fields feed the sums before anything else: requested together, one segment ahead
+  double p_next = 0., t_next = 0., u_next = 0.;
+  if (np > 0) { p_next = ldg<double>(los_p, lane); t_next = ldg<double>(los_t, lane); u_next = ldg<double>(los_u, lane); }
+
+  for (int ip = 0; ip < np; ++ip) {
+    size_t const o = (size_t)ip * R;
+    double const p = p_next, t = t_next, u = u_next;
+    if (ip + 1 < np) {
+      p_next = ldg<double>(los_p + o + R, lane); t_next = ldg<double>(los_t + o + R, lane); u_next = ldg<double>(los_u + o + R, lane);
+    }
+    tau_path = cga_segment<WARM, LDS, RCPB>(pd, D, tau_path, t, u, p, sa, sb, sw, br, ia, ib);
     st_stream(out + (size_t)ip * Re, lane, tau_path);
   }
 }
@@ -2398,6 +2592,30 @@ __global__ __launch_bounds__(256) void jur_kat_ega_kernel(jur_view_t v, int g, i
   auto one = [&](long i) {
     if constexpr (WARM) out[i] = ega_eps_warm<LDS, RCPB>(v, pd, D, tau[i], t[i], u[i], p[i], br, ia, ib);
     else out[i] = ega_eps_exact<LDS>(v, pd, D, tau[i], t[i], u[i], p[i]);
+  };
+  if (chain) {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+      for (long i = 0; i < n; i++) one(i);
+  } else {
+    long const i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) one(i);
+  }
+}
+
+// the Curtis-Godson look-up on arrays of (tau, cgt, cgu, cgp): the new path transmittance (cga_tau_*; the running sums
+// and the w == 0 rule belong to the ray, not to the look-up)
+template <bool WARM, bool LDS, bool RCPB>
+__global__ __launch_bounds__(256) void jur_kat_cga_kernel(jur_view_t v, int g, int d, long n, double const *__restrict__ tau,
+                                                          double const *__restrict__ t, double const *__restrict__ u,
+                                                          double const *__restrict__ p, int chain, double *__restrict__ out) {
+  jur_int2 const pd = v.pair[g * v.nd + d];
+  PairDesc<LDS> D{v.lvl, v.crv, v.ue + v.pair_e0[g * v.nd + d], (unsigned)pd.b, 0u, 0u, 0u};
+  if constexpr (RCPB) D.recb = v.rec + v.pair_e0[g * v.nd + d];
+  if (pd.a >= 2) stage_pair<LDS, RCPB>(v, pd, D);       // uniform branch; stage_pair ends in a barrier
+  unsigned br = 0, ia = 0, ib = 0;
+  auto one = [&](long i) {
+    if constexpr (WARM) out[i] = cga_tau_warm<LDS, RCPB>(pd, D, tau[i], t[i], u[i], p[i], br, ia, ib);
+    else out[i] = cga_tau_exact<LDS>(pd, D, tau[i], t[i], u[i], p[i]);
   };
   if (chain) {
     if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -4113,7 +4331,9 @@ static int raise_lds_limit(std::mutex &mu, unsigned long long &raised, void cons
   return 0;
 }
 
-extern "C" int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, void *stream) {
+// cga != 0: the model runs FORMOD 1 -- jur_cga_kernel in the variant the same rules choose (the switch stays on the
+// host: jur_view_t is an argument of every kernel)
+extern "C" int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, int cga, void *stream) {
   if (c->n <= 0 || v->ng <= 0) return 0;
   int const block = 256;   // (128 rays per workgroup: 34.6 against 33.7 ms; 64: the staged descriptors limit the occupancy, 45 ms)
   int const nrb = (c->n + block - 1) / block, npair = v->nd * v->ng;
@@ -4124,6 +4344,17 @@ extern "C" int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, void *
   size_t const lds = (sizeof(jur_lvl_t) + 8) * JUR_TBLNP + (sizeof(jur_crv_t) + 8) * (size_t)v->max_pair_curves;
   bool const use_lds = v->max_pair_curves > 0 && lds <= 48 * 1024;
   bool const rcpb = use_lds && v->fast_arith;
+  if (cga) {
+    if (v->sorted_tables) {
+      if (rcpb) hipLaunchKernelGGL((jur_cga_kernel<true, true, true>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
+      else if (use_lds) hipLaunchKernelGGL((jur_cga_kernel<true, true, false>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
+      else hipLaunchKernelGGL((jur_cga_kernel<true, false, false>), dim3(grid), dim3(block), 0, s, *v, *c, nrb);
+    } else {
+      if (use_lds) hipLaunchKernelGGL((jur_cga_kernel<false, true, false>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
+      else hipLaunchKernelGGL((jur_cga_kernel<false, false, false>), dim3(grid), dim3(block), 0, s, *v, *c, nrb);
+    }
+    return (int)hipGetLastError();
+  }
   if (v->sorted_tables) {
     if (rcpb) hipLaunchKernelGGL((jur_ega_kernel<true, true, true>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
     else if (use_lds) hipLaunchKernelGGL((jur_ega_kernel<true, true, false>), dim3(grid), dim3(block), lds, s, *v, *c, nrb);
@@ -4298,6 +4529,25 @@ extern "C" int jurk_kat_ega(jur_view_t const *v, int g, int d, long n, double co
   } else if (mode == 1) hipLaunchKernelGGL((jur_kat_ega_kernel<true, false, false>), grid, block, 0, s, *v, g, d, n, tau, t, u, p, chain, out);
   else if (mode == 2) hipLaunchKernelGGL((jur_kat_ega_kernel<true, true, false>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);
   else hipLaunchKernelGGL((jur_kat_ega_kernel<true, true, true>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);   // what the batched kernel runs
+  return (int)hipGetLastError();
+}
+
+// the same modes for the Curtis-Godson look-up (3: what jur_cga_kernel runs on strict tables)
+extern "C" int jurk_kat_cga(jur_view_t const *v, int g, int d, long n, double const *tau, double const *t, double const *u,
+                            double const *p, int mode, int chain, double *out, void *stream) {
+  if (n <= 0) return 0;
+  size_t const lds = (sizeof(jur_lvl_t) + 8) * JUR_TBLNP + (sizeof(jur_crv_t) + 8) * (size_t)v->max_pair_curves;
+  bool const lds_ok = v->max_pair_curves > 0 && lds <= 48 * 1024;
+  if ((mode >= 1 && !v->sorted_tables) || (mode >= 2 && !lds_ok) || (mode == 3 && !v->strict_tables) || mode < 0 || mode > 3)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 const grid(chain ? 1u : (unsigned)((n + 255) / 256)), block(256);
+  if (mode == 0) {
+    if (lds_ok) hipLaunchKernelGGL((jur_kat_cga_kernel<false, true, false>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);
+    else hipLaunchKernelGGL((jur_kat_cga_kernel<false, false, false>), grid, block, 0, s, *v, g, d, n, tau, t, u, p, chain, out);
+  } else if (mode == 1) hipLaunchKernelGGL((jur_kat_cga_kernel<true, false, false>), grid, block, 0, s, *v, g, d, n, tau, t, u, p, chain, out);
+  else if (mode == 2) hipLaunchKernelGGL((jur_kat_cga_kernel<true, true, false>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);
+  else hipLaunchKernelGGL((jur_kat_cga_kernel<true, true, true>), grid, block, lds, s, *v, g, d, n, tau, t, u, p, chain, out);
   return (int)hipGetLastError();
 }
 

@@ -155,7 +155,6 @@ static int check_ctl(ctl_t const *ctl) {
   if (ctl->nd < 1 || ctl->nd > JUR_ND) { jur_set_error("ctl->nd=%d outside 1..%d", ctl->nd, JUR_ND); return JUR_EINVAL; }
   if (ctl->nw < 0 || ctl->nw > JUR_NW) { jur_set_error("ctl->nw=%d outside 0..%d", ctl->nw, JUR_NW); return JUR_EINVAL; }
   if (ctl->ip != 1) { jur_set_error("only 1-D profile interpolation is supported (ctl->ip == 1, as upstream asserts)"); return JUR_EINVAL; }
-  if (ctl->formod == 1) { jur_set_error("FORMOD=1 (CGA) has no integrator upstream either"); return JUR_EINVAL; }
   for (int id = 0; id < ctl->nd; id++)
     if (ctl->window[id] < 0 || ctl->window[id] >= (ctl->nw > 0 ? ctl->nw : 1)) { jur_set_error("ctl->window[%d] out of range", id); return JUR_EINVAL; }
   return JUR_OK;
@@ -819,6 +818,7 @@ int jur_model_reserve(jur_model_t *m, long nr) {
 /* Rays per workgroup of the fused kernel for a call of nr rays, or 0 when the call goes to the batched kernels
  * (too many rays, or more (channel, gas) chains per ray than the LDS rings hold). */
 static int pencil_rays_per_group(jur_model_t const *m, long nr) {
+  if (m->ctl->formod == 1) return 0;                        /* the fused kernel is emissivity growth only */
   if (m->pencil_rays <= 0 || nr > m->pencil_rays) return 0;
   long const npair = (long)m->view.nd * (m->view.ng > 0 ? m->view.ng : 1);
   int rb = m->pencil_rb;
@@ -1031,7 +1031,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
         c.tsurf = m->d_tsurf + s0;
         c.los = m->d_los + (size_t)s0 * JUR_NLOS * m->nfield;
         c.eps_off = m->d_eps_off + t0c;
-        TIMED(1, jurk_launch_ega(&m->view, &c, s), "ega");
+        TIMED(1, jurk_launch_ega(&m->view, &c, m->ctl->formod == 1, s), "ega");
         if (co) TIMED(4, jurk_launch_contrib(&m->view, &c, nr, co->rad, co->tau, s), "contribution");
         TIMED(2, jurk_launch_combine(&m->view, &c, s), "combine");
         m->n_launch_ega++;
@@ -1050,7 +1050,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
       /* the look-up and the radiance update take the trace launch's block order where they cover the same slots */
       int const same_slots = blk_order && s0 == 0 && c.n == nt;
       if (same_slots && block_order_ega_on()) c.blk_order = blk_order;
-      TIMED(1, jurk_launch_ega(&m->view, &c, s), "ega");
+      TIMED(1, jurk_launch_ega(&m->view, &c, m->ctl->formod == 1, s), "ega");
       c.blk_order = NULL;
       if (co) TIMED(4, jurk_launch_contrib(&m->view, &c, nr, co->rad, co->tau, s), "contribution");
       if (same_slots && g_block_order_combine) c.blk_order = blk_order;
@@ -1847,6 +1847,17 @@ int jur_kat_ega_eps(jur_model_t *m, int ig, int id, long n, double const *tau, d
   int rc = kat_slab(m, n, 4, in, 1, io, &d);
   if (rc) { if (d) (void)hipFree(d); return rc; }
   int const ek = jurk_kat_ega(&m->view, ig, id, n, d, d + n, d + 2 * n, d + 3 * n, mode, chain, d + 4 * n, m->stream);
+  return kat_finish(m, ek, n, 4, 1, io, d);
+}
+
+int jur_kat_cga_eps(jur_model_t *m, int ig, int id, long n, double const *tau, double const *cgt, double const *cgu,
+                    double const *cgp, int mode, int chain, double *out) {
+  if (!m || n < 1 || ig < 0 || ig >= m->view.ng || id < 0 || id >= m->view.nd) { jur_set_error("kat_cga_eps: bad arguments"); return JUR_EINVAL; }
+  double const *in[4] = {tau, cgt, cgu, cgp};
+  double *io[1] = {out}, *d;
+  int rc = kat_slab(m, n, 4, in, 1, io, &d);
+  if (rc) { if (d) (void)hipFree(d); return rc; }
+  int const ek = jurk_kat_cga(&m->view, ig, id, n, d, d + n, d + 2 * n, d + 3 * n, mode, chain, d + 4 * n, m->stream);
   return kat_finish(m, ek, n, 4, 1, io, d);
 }
 

@@ -213,6 +213,8 @@ def lib():
             L.jur_np_overflows.argtypes = [C.c_int]
         L.jur_abi_sizes.argtypes = [C.POINTER(C.c_size_t)]
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
+        if hasattr(L, "jur_kat_cga_eps"):            # (an older build selected with JURASSIC_HIP_SO for an A/B run has none)
+            L.jur_kat_cga_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
         L.jur_kat_update.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int] + [dp] * 6
         L.jur_kat_traceray.argtypes = [C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), C.POINTER(C.c_int)]
@@ -1085,6 +1087,13 @@ class Model:
         a = [np.ascontiguousarray(x, dtype=np.float64) for x in (tau, t, u, p)]
         out = np.zeros(len(a[0]))
         _chk(lib().jur_kat_ega_eps(self.h, ig, id_, len(out), *[_p(x) for x in a], mode, int(chain), _p(out)))
+        return out
+
+    def kat_cga_eps(self, ig, id_, tau, cgt, cgu, cgp, mode=3, chain=False):
+        """Curtis-Godson look-up (FORMOD 1): the new path transmittance from tau and the means -> [n]"""
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (tau, cgt, cgu, cgp)]
+        out = np.zeros(len(a[0]))
+        _chk(lib().jur_kat_cga_eps(self.h, ig, id_, len(out), *[_p(x) for x in a], mode, int(chain), _p(out)))
         return out
 
     def kat_continua(self, id_, p, t, q, u_co2, u_h2o):
