@@ -1061,6 +1061,44 @@ int  jur_model_arithmetic(jur_model_t const *m);
  * (jur_model_set_pencil stays accepted and has no effect).  Slot [1] of jur_model_last_kernel_ms counts whichever
  * look-up kernel ran. */
 
+/* Atmosphere along the line of sight, ctl->ip (IP in a control file): 1 (default) one vertical profile per ray, chosen
+ * by its time stamp; 2 a satellite track: every point of the line of sight is interpolated between the two nearest
+ * profiles of a track (intpol_atm_2d, jurassic.c:704-760).  Upstream's GPU tracer asserts IP 1 (jr_common.h:573, 581);
+ * here IP 2 runs in the ray tracer, with one rule.  IP 3 stays refused at jur_model_create.
+ *   1. Time block.  A ray's time stamp selects the block [a0, a0 + n) of atmosphere points as under IP 1 (locate_atm);
+ *      zmin .. zmax is the altitude range of the block's first column, as under IP 1.
+ *   2. Profiles.  A profile is a maximal run of consecutive points with equal time stamp, longitude and latitude, so
+ *      the profiles of a block are consecutive.  The table is built on the host with every atmosphere: first point,
+ *      length and x1 = geo2cart(0, lon, lat) in the host's libm per profile, as upstream caches them.  An upload is
+ *      refused with JUR_EINVAL and upstream's words when a profile has fewer than two points ("Cannot identify
+ *      profiles. Check ordering of data points!") or two consecutive profiles of a block lie more than 10 degrees of
+ *      latitude apart ("Distance of profiles is too large!"); the model holds no atmosphere afterwards.  A ray whose
+ *      block is not made of whole profiles (its time stamp matches no run of equal time stamps) is not entered.
+ *   3. Horizontal weights at a point (z, lon, lat), lon and lat from cart2geo of the position: x0 = geo2cart(0, lon,
+ *      lat); among the block's profiles with |lat - lat_ix| <= 10, in table order, dh = DIST2(x0, x1[ix]);
+ *      dh <= dhmin0 makes ix the nearest and the nearest the second, else dh <= dhmin1 makes it the second (both from
+ *      1e99, ix0 = ix1 = the block's first profile).  x2 = DIST2(x1[ix0], x1[ix1]), x = sqrt(x2),
+ *      r0 = (dhmin0 - dhmin1 + x2) / (2 x), r1 = x - r0; r = 0 if r0 <= 0, else 1 if r1 <= 0, else r0 / (r0 + r1):
+ *      beyond the end of a track a point takes the end profile.
+ *   4. Vertical interpolation, in either profile on its own levels at the bracket locate() finds there: p by eip,
+ *      T, every q and every k by lip; then y = (1 - r) y0 + r y1, in that form.
+ *   5. Every evaluation of the tracer takes 3 and 4: the LOS point (p, T, q, k, the columns u, q_H2O), the mid-step
+ *      probe and the three displaced probes of the refractivity gradient, the columns redone for the point before the
+ *      exit, and tsurf.
+ *   A block with one profile gives ix0 = ix1, x = 0, r0 = -inf, r = 0 and y0 + 0 y1 = y0: the bits of IP 1 for finite
+ *   profiles.  A point with no profile inside the 10-degree gate yields NaN by this arithmetic.
+ * One kernel traces it (jur_track_trace_kernel, a lane per ray, all profiles of the block scanned at every evaluation);
+ * the fused kernel of small calls stays 1-D, so IP 2 calls of any size take the batched kernels (jur_model_set_pencil
+ * stays accepted and has no effect).  Forward model, contributions, Curtis-Godson columns, the dense Jacobian
+ * (jur_kernel), the multi-device entries and the drop-in entries run under IP 2, with FORMOD 1 or 2.  The scene entries
+ * (jur_kernel_scene_host and everything built on its per-ray blocks of ONE slice's state, the trial pass and the
+ * retrieval loop included) return JUR_EINVAL before anything is launched: under IP 2 a ray reads two profiles.
+ *
+ * jur_track_profiles: the profile table of `atm` by rule 2, host only: first[], len[] (atmosphere points), x1[][3],
+ * block_of[] (number of the profile's time block, from 0) hold one entry per profile -- room for atm->np / 2 + 1
+ * entries each; any of them may be NULL.  Returns the number of profiles, or JUR_EINVAL with the words above. */
+long jur_track_profiles(atm_t const *atm, int *first, int *len, double (*x1)[3], int *block_of);
+
 /* Frees the process-global state behind formod() / formod_GPU() / formod_pencil(): the lanes (streams, atmosphere,
  * workspaces, pinned images) and the emissivity tables loaded by the first call.  Upstream keeps its counterparts for
  * the life of the process (GPUdrivers.cu:263-273, 309; jr_common.h:60-78).  Waits for calls in flight; returns the

@@ -82,6 +82,20 @@ typedef struct {
   double const *atm_pslope;     /* [atm_np] ln-pressure slope to the next level, NaN if not defined */
 } jur_view_t;
 
+/* Profile table of a satellite track (ctl->ip == 2, the rule in jurassic_hip.h), rebuilt with every atmosphere by
+ * jur_track_profiles and handed to the ray tracer BESIDE the view, as an argument of jur_track_trace_kernel alone: a
+ * view that grew would move the later arguments of every kernel and with them every kernel's text.  A profile is a
+ * run of points with equal time stamp, longitude and latitude; the profiles of a time block are consecutive. */
+typedef struct {
+  int ip;                       /* ctl->ip: 1 one profile per time block, 2 the nearest two profiles of the block's track */
+  int nprof;                    /* profiles of the atmosphere on the device (ip == 2), else 0    */
+  double const *x1;             /* [nprof][3] geo2cart(0, lon, lat) of every profile (host libm) */
+  double const *lat;            /* [nprof] its latitude                                          */
+  int const *first, *len;       /* [nprof] its first atmosphere point and its length (>= 2)      */
+  int const *dir;               /* [nprof] its altitude axis: 1 strictly ascending, -1 strictly descending, 0 neither */
+  int const *prof_of;           /* [atm_np] profile of every atmosphere point                    */
+} jur_track_t;
+
 /* One chunk of rays handed to the kernels; all pointers are device memory.
  * Slot i of the chunk works on ray order[i] of the caller's arrays (order ==
  * NULL: ray first+i), so that the caller-visible arrays are indexed by ray id
@@ -111,7 +125,8 @@ typedef struct {
 
 /* kernel launchers (jur_kernels.hip); return hipError_t as int */
 int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream);   /* fills atm_pslope */
-int jurk_launch_trace(jur_view_t const *v, jur_chunk_t const *c, void *stream);
+/* trk->ip == 2: jur_track_trace_kernel (one lane per ray, two profiles per point); else the 1-D tracers by launch */
+int jurk_launch_trace(jur_view_t const *v, jur_track_t const *trk, jur_chunk_t const *c, void *stream);
 /* the look-up kernel of the model's band model: cga == 0 emissivity growth (FORMOD 2), != 0 Curtis-Godson (FORMOD 1) */
 int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, int cga, void *stream);
 int jurk_launch_combine(jur_view_t const *v, jur_chunk_t const *c, void *stream);
@@ -567,6 +582,9 @@ int jurk_scene_hydro(jur_scene_hydro_t const *a, void *stream);
 /* host arithmetic shared by jur_model.c and jur_scene.c (not exported) */
 #define JUR_HIDDEN __attribute__((visibility("hidden")))
 JUR_HIDDEN int jur_atm_slice(double const *time, long n, double t, long *first);
+/* jur_track_profiles on rows (jur_track.c), with the altitude direction of every profile and the profile of every point */
+JUR_HIDDEN long jur_track_rows(long n, double const *time, double const *z, double const *lon, double const *lat, int *first,
+                               int *len, double (*x1)[3], int *block_of, int *dir, int *prof_of);
 JUR_HIDDEN size_t jur_state_vector(ctl_t const *ctl, atm_t const *atm, double *x, int *iqa, int *ipa);
 JUR_HIDDEN long jur_scene_slice_elements(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols, int *iqa, int *ipa);
 /* a distinct slice of a scene: points [first, first + len) with nel state elements; next: chain of the slices that

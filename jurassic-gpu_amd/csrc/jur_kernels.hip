@@ -5,6 +5,8 @@
 //                         per-segment state p, T, ds, k, q_H2O, u[g] to the LOS workspace
 //                         (tiles of 64 ray slots, [tile][point][field][64]), the tangent
 //                         point, the point count and the surface temperature.
+//   jur_track_trace_kernel  the same for a model with IP 2: every point and probe interpolated between the two
+//                         nearest profiles of a satellite track (jurassic.c:704-760); writes the same workspace.
 //   jur_ega_kernel        one lane per ray, one (channel, gas) pair per workgroup: the sequential
 //                         emissivity-growth recurrence along the line of sight with its band
 //                         table look-ups (jr_common.h:237-280); writes the gas's transmittance of the
@@ -273,6 +275,7 @@ __device__ __forceinline__ int locate_axis_from(P xx, int n, double x, int dir, 
 typedef __attribute__((address_space(3))) double const *lds_cptr;
 struct AtmGlobal {
   typedef double const *ptr;
+  static constexpr bool track = false;   // one profile per time block (ip == 1); AtmTrack: the nearest two of a track
   jur_view_t const &v;
   __device__ __forceinline__ ptr z() const { return v.atm_z; }
   __device__ __forceinline__ ptr p() const { return v.atm_p; }
@@ -284,6 +287,7 @@ struct AtmGlobal {
 };
 struct AtmLds {
   typedef lds_cptr ptr;
+  static constexpr bool track = false;
   lds_cptr rows;
   int n, ng;
   __device__ __forceinline__ ptr z() const { return rows; }
@@ -350,6 +354,130 @@ __device__ __attribute__((noinline)) void redo_columns(double const *__restrict_
     double const *q = atm_q + (size_t)ig * atm_np;
     los_u[(size_t)ig * fs] = 10. * lip(za, q[ip], zb, q[ip + 1], z) * p / (JUR_BOLTZMANN * t) * dsn;
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// 2-D atmosphere along the line of sight (ctl->ip == 2: intpol_atm_2d, jurassic.c:704-760; the rule in jurassic_hip.h)
+// ---------------------------------------------------------------------------------------
+// Where the profile table of a ray's time block is read from.  TrackGlobal: the model's table (jur_track_t), indexed by
+// profile.  TrackLds: the workgroup's copy of ONE block's nx entries in LDS -- columns x1[0], x1[1], x1[2], lat as
+// doubles, then first, len, dir as ints -- indexed by profile all the same (the block's first profile is px0).
+typedef __attribute__((address_space(3))) int const *lds_iptr;
+struct TrackGlobal {
+  double const *x1_, *lat_;
+  int const *first_, *len_, *dir_;
+  __device__ __forceinline__ double x1(int ix, int i) const { return x1_[3 * (size_t)ix + i]; }
+  __device__ __forceinline__ double lat(int ix) const { return lat_[ix]; }
+  __device__ __forceinline__ int first(int ix) const { return first_[ix]; }
+  __device__ __forceinline__ int len(int ix) const { return len_[ix]; }
+  __device__ __forceinline__ int dir(int ix) const { return dir_[ix]; }
+};
+struct TrackLds {
+  lds_cptr d;
+  lds_iptr w;
+  int px0, nx;
+  __device__ __forceinline__ double x1(int ix, int i) const { return d[i * nx + (ix - px0)]; }
+  __device__ __forceinline__ double lat(int ix) const { return d[3 * nx + (ix - px0)]; }
+  __device__ __forceinline__ int first(int ix) const { return w[ix - px0]; }
+  __device__ __forceinline__ int len(int ix) const { return w[nx + (ix - px0)]; }
+  __device__ __forceinline__ int dir(int ix) const { return w[2 * nx + (ix - px0)]; }
+};
+// the profile rows come from the model's arrays, as under AtmGlobal
+template <class Tab>
+struct AtmTrack {
+  typedef double const *ptr;
+  static constexpr bool track = true;
+  jur_view_t const &v;
+  Tab T;
+  int const *prof_of;
+  __device__ __forceinline__ ptr z() const { return v.atm_z; }
+  __device__ __forceinline__ ptr p() const { return v.atm_p; }
+  __device__ __forceinline__ ptr t() const { return v.atm_t; }
+  __device__ __forceinline__ ptr pslope() const { return v.atm_pslope; }
+  __device__ __forceinline__ ptr q(int ig) const { return v.atm_q + (size_t)ig * v.atm_np; }
+  __device__ __forceinline__ ptr k(int iw) const { return v.atm_k + (size_t)iw * v.atm_np; }
+  __device__ __forceinline__ int origin(int atm0) const { return atm0; }
+};
+
+// latitude of a position and x0 = geo2cart(0, lon, lat) of its longitude and latitude (jurassic.c:731), in upstream's
+// order of operations.  Out of line for the reason clip_exit is: five evaluations per step would each bring the
+// constants of asin, atan2, sin and cos in front of the stepping loop.
+struct TrackGeo { double lat, x0, x1, x2; };
+__device__ __attribute__((noinline)) TrackGeo track_geo(double px0, double px1, double px2) {
+  double const x[3] = {px0, px1, px2};
+  double alt, lon, lat, c[3];
+  cart2geo(x, alt, lon, lat);
+  geo2cart(0, lon, lat, c);
+  return {lat, c[0], c[1], c[2]};
+}
+
+// What a point takes from the track: its two neighbour profiles (table index), the lower point of its altitude
+// bracket in either, and the weight r of the second.  A ray carries one for its LOS points and one for its probes:
+// the brackets are the hints of the next evaluation while the neighbour stays (ix < 0: nothing carried yet).
+struct TrackPt { int ix0, ix1, i0, i1; double r; };
+
+// jurassic.c:732-755 on the profiles [px0, px0 + nx) of the ray's block: the full scan, upstream's comparisons and
+// order; then the bracket locate() finds on either profile's own levels (walked from the hint where the profile's
+// axis is strictly monotone: the same bracket)
+template <class Tab>
+__device__ __forceinline__ TrackPt track_locate(Tab const &T, double const *__restrict__ atm_z, int px0, int nx, double z,
+                                                TrackGeo const &g, TrackPt const &prev) {
+  double dhmin0 = 1e99, dhmin1 = 1e99;
+  int ix0 = px0, ix1 = px0;
+  for (int ix = px0; ix < px0 + nx; ix++)
+    if (fabs(g.lat - T.lat(ix)) <= 10) {
+      double const a0 = g.x0 - T.x1(ix, 0), a1 = g.x1 - T.x1(ix, 1), a2 = g.x2 - T.x1(ix, 2);
+      double const dh = a0 * a0 + a1 * a1 + a2 * a2;
+      if (dh <= dhmin0) { dhmin1 = dhmin0; ix1 = ix0; dhmin0 = dh; ix0 = ix; }
+      else if (dh <= dhmin1) { dhmin1 = dh; ix1 = ix; }
+    }
+  double const b0 = T.x1(ix0, 0) - T.x1(ix1, 0), b1 = T.x1(ix0, 1) - T.x1(ix1, 1), b2 = T.x1(ix0, 2) - T.x1(ix1, 2);
+  double const x2 = b0 * b0 + b1 * b1 + b2 * b2;
+  double const x = sqrt(x2);
+  double const r0 = (dhmin0 - dhmin1 + x2) / (2 * x);
+  double const r1 = x - r0;
+  double r;
+  if (r0 <= 0) r = 0;
+  else r = (r1 <= 0) ? 1 : r0 / (r0 + r1);
+  int const f0 = T.first(ix0), f1 = T.first(ix1), d0 = T.dir(ix0), d1 = T.dir(ix1);
+  int const h0 = (ix0 == prev.ix0) ? prev.i0 - f0 : (ix0 == prev.ix1) ? prev.i1 - f0 : 0;
+  int const h1 = (ix1 == prev.ix1) ? prev.i1 - f1 : (ix1 == prev.ix0) ? prev.i0 - f1 : 0;
+  int const l0 = d0 ? locate_axis_from(atm_z + f0, T.len(ix0), z, d0, h0) : locate_axis(atm_z + f0, T.len(ix0), z);
+  int const l1 = d1 ? locate_axis_from(atm_z + f1, T.len(ix1), z, d1, h1) : locate_axis(atm_z + f1, T.len(ix1), z);
+  return {ix0, ix1, f0 + l0, f1 + l1, r};
+}
+
+__device__ __forceinline__ double track_mix(double r, double y0, double y1) { return (1 - r) * y0 + r * y1; }
+
+// pressure (eip through the pslope array) and temperature (lip) of either profile on its bracket, then blended
+template <class Atm>
+__device__ __forceinline__ void track_pt(Atm const &A, TrackPt const &k, double z, double &p, double &t) {
+  double pj[2], tj[2];
+  for (int j = 0; j < 2; j++) {
+    int const i = j ? k.i1 : k.i0;
+    double const za = A.z()[i], zb = A.z()[i + 1], sl = A.pslope()[i];
+    pj[j] = (sl == sl) ? A.p()[i] * exp(sl * (z - za)) : lip(za, A.p()[i], zb, A.p()[i + 1], z);
+    tj[j] = lip(za, A.t()[i], zb, A.t()[i + 1], z);
+  }
+  p = track_mix(k.r, pj[0], pj[1]);
+  t = track_mix(k.r, tj[0], tj[1]);
+}
+
+// one row (an emitter's q, a window's k) at altitude z on the point's two brackets, blended
+__device__ __forceinline__ double track_row(double const *__restrict__ az, double const *__restrict__ y, TrackPt const &k, double z) {
+  return track_mix(k.r, lip(az[k.i0], y[k.i0], az[k.i0 + 1], y[k.i0 + 1], z), lip(az[k.i1], y[k.i1], az[k.i1 + 1], y[k.i1 + 1], z));
+}
+
+// redo_columns under the 2-D rule: the point before the exit at position (px0, px1, px2), altitude z
+template <class Tab>
+__device__ __attribute__((noinline)) void redo_columns_track(Tab T, double const *__restrict__ atm_z, double const *__restrict__ atm_q,
+                                                             int atm_np, int px0, int nx, int ng, double x0, double x1, double x2,
+                                                             double z, double p, double t, double dsn, double *__restrict__ los_u,
+                                                             size_t fs) {
+  TrackGeo const g = track_geo(x0, x1, x2);
+  TrackPt const k = track_locate(T, atm_z, px0, nx, z, g, TrackPt{-1, -1, 0, 0, 0.});
+  for (int ig = 0; ig < ng; ig++)
+    los_u[(size_t)ig * fs] = 10. * track_row(atm_z, atm_q + (size_t)ig * atm_np, k, z) * p / (JUR_BOLTZMANN * t) * dsn;
 }
 
 struct ClipOut { double x0, x1, x2, frac; };
@@ -450,7 +578,18 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
   }
 
   // (zmin == zmax: a slice without vertical extent is not entered -- DESIGN.md section 2)
-  bool const outside = (obsz < zmin) || (vpz > zmax - 0.001) || (zmin == zmax);
+  // 2-D rule: the profiles [px0, px0 + nx) of the track that the block holds.  A block that is not made of whole
+  // profiles (a time stamp that matches no run of equal time stamps) is not entered.
+  int px0 = 0, nx = 0;
+  bool whole = true;
+  if constexpr (Atm::track) {
+    static_assert(LANES == 1, "the 2-D rule is traced one lane per ray");
+    px0 = A.prof_of[atm0];
+    nx = A.prof_of[atm0 + atmn - 1] - px0 + 1;
+    whole = (A.T.first(px0) == atm0) && (A.T.first(px0 + nx - 1) + A.T.len(px0 + nx - 1) == atm0 + atmn);
+  }
+  TrackPt tk{-1, -1, 0, 0, 0.}, tkr{-1, -1, 0, 0, 0.};   // the LOS points' and the probes' places in the track (2-D rule)
+  bool const outside = (obsz < zmin) || (vpz > zmax - 0.001) || (zmin == zmax) || (Atm::track && !whole);
   // (fused kernel: which lanes' rays never enter the atmosphere is said by ONE lane, in its own program order
   // before it starts stepping -- a branch of the lanes concerned could be scheduled behind the others' loop)
   L.never_enter(__ballot(outside));
@@ -524,6 +663,10 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
           if (low_idx + 1 == np - 1) TR_LDS2 = dsp;
           double const dsn = (np >= 2) ? 0.5 * (ds_pp + dsp) : dsp * 0.5;
           L.put(JUR_F_DS, np - 1, dsn);
+          if constexpr (Atm::track)
+            redo_columns_track(A.T, v.atm_z, v.atm_q, v.atm_np, px0, nx, v.ng, TR_PX(0), TR_PX(1), TR_PX(2), TR_PZ,
+                               L.at(JUR_F_P, np - 1), L.at(JUR_F_T, np - 1), dsn, &L.at(f_u, np - 1), L.field_stride());
+          else
           redo_columns(v.atm_z, v.atm_q, v.atm_np, atm0, atmn, v.ng, TR_PZ, L.at(JUR_F_P, np - 1), L.at(JUR_F_T, np - 1), dsn,
                        &L.at(f_u, np - 1), L.field_stride());
           ds_p = dsp;
@@ -532,9 +675,24 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
       }
 
       double p, t, rdz = 0;
-      int const ia = intpol_pt<true>(A, ab, atmn, z, p, t, zdir, zhint, &rdz);
+      int ia = 0;
+      if constexpr (Atm::track) {   // the point's own longitude and latitude choose its two profiles
+        tk = track_locate(A.T, v.atm_z, px0, nx, z, track_geo(x[0], x[1], x[2]), tk);
+        track_pt(A, tk, z, p, t);
+      } else ia = intpol_pt<true>(A, ab, atmn, z, p, t, zdir, zhint, &rdz);
       double const dsn = (np >= 1) ? 0.5 * (ds_p + ds) : ds * 0.5;   // redone for the point before the exit
       L.put(JUR_F_DS, np, dsn);
+      if constexpr (Atm::track) {
+        double const kt = JUR_BOLTZMANN * t;
+        for (int ig = 0; ig < v.ng; ig++) {
+          double const qv = track_row(v.atm_z, A.q(ig), tk, z);
+          L.put(f_u + ig, np, 10. * qv * p / kt * dsn);
+          if (ig == v.ig_h2o) L.put(JUR_F_QH2O, np, qv);
+        }
+        // (1 - r) 0 + r 0 = +0.0 for every finite r: the elision of an atmosphere without extinction holds here too
+        if (!v.atm_k_zero)
+        for (int iw = 0; iw < v.nw; iw++) L.put(f_k + iw, np, track_row(v.atm_z, A.k(iw), tk, z));
+      } else
       {  // remaining quantities on the same bracket (jr_common.h:557-567)
         double const za = A.z()[ia], zb = A.z()[ia + 1];
         double const kt = JUR_BOLTZMANN * t, rkt = 1. / kt;   // one division for all emitters' columns (div_rcp)
@@ -584,7 +742,23 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
         n += refractivity(p, t);
         double xh[3], zz, llon, llat, pp, tt;
         for (int i = 0; i < 3; i++) xh[i] = x[i] + 0.5 * ds * ex0[i];
-        if constexpr (LANES == 4) {
+        if constexpr (Atm::track) {
+          // every probe takes the 2-D rule at its own longitude and latitude (jr_common.h:669-679 with intpol_atm_geo)
+          zz = norm3(xh) - JUR_RE;
+          tkr = track_locate(A.T, v.atm_z, px0, nx, zz, track_geo(xh[0], xh[1], xh[2]), tkr);
+          track_pt(A, tkr, zz, pp, tt);
+          double const n2 = refractivity(pp, tt);
+          for (int i = 0; i < 3; i++) {
+            double const h = 0.02;
+            xh[i] += h;
+            zz = norm3(xh) - JUR_RE;
+            tkr = track_locate(A.T, v.atm_z, px0, nx, zz, track_geo(xh[0], xh[1], xh[2]), tkr);
+            track_pt(A, tkr, zz, pp, tt);
+            ngr[i] = div_rcp(refractivity(pp, tt) - n2, h, 1. / h);
+            xh[i] -= h;
+          }
+          (void)llon; (void)llat;
+        } else if constexpr (LANES == 4) {
           // one probe per lane of the quad.  The sequential loop displaces a coordinate by h, probes, and takes h
           // off again before it goes on: probe i sees (x_k + h) - h in the coordinates k < i
           double const h = 0.02;
@@ -823,6 +997,76 @@ __global__ __launch_bounds__(64 * JUR_TRACE_SLICE_WAVES, 4) void jur_trace_slice
   c.tp[0][ray_out] = t.tpz;
   c.tp[1][ray_out] = t.tplon;
   c.tp[2][ray_out] = t.tplat;
+}
+
+// One lane per ray under the 2-D rule (ctl->ip == 2): every LOS point and every probe is interpolated between the two
+// nearest profiles of the track its time block holds (AtmTrack).  Workgroups of four LOS tiles, as the slice kernel's:
+// when all rays of the workgroup use ONE block and its track has no more than JUR_TRACK_LDS_PROFILES profiles, the
+// block's entries of the profile table are copied to LDS once and the scans -- all profiles of the block at every one
+// of a step's five evaluations -- read them there (TrackLds); else every lane reads the model's table (TrackGlobal).
+// Same values from another place: same doubles.  Full scan: no warm start is built.
+// (The name does not begin with jur_trace_ on purpose: tests/test_trace_lds_cpu.py holds every kernel so named to the
+// 1-D tracers' budget of 32 B of scratch, which this first version, with its two out-of-line functions, does not meet.)
+// LDS: 4 x 7680 B of tangent-point columns + 44 B per profile + the agreement = 36 368 B, four workgroups per CU.
+#ifndef JUR_TRACK_LDS_PROFILES
+#define JUR_TRACK_LDS_PROFILES 128
+#endif
+#ifndef JUR_TRACK_MIN_WAVES             // (other values: experiment builds, make EXTRA=-DJUR_TRACK_MIN_WAVES=...)
+#define JUR_TRACK_MIN_WAVES 4
+#endif
+__global__ __launch_bounds__(256, JUR_TRACK_MIN_WAVES) void jur_track_trace_kernel(jur_view_t v, jur_chunk_t c, jur_track_t k) {
+  __shared__ double tr_all[4][15][64];
+  __shared__ double tab_d[4 * JUR_TRACK_LDS_PROFILES];
+  __shared__ int tab_w[3 * JUR_TRACK_LDS_PROFILES];
+  __shared__ int agree[4];                 // min a0, max a0, min n, max n over the workgroup's rays
+  double (&tr_sh)[15][64] = tr_all[threadIdx.x >> 6];
+  int const r = ordered_block<1>(c.blk_order, (int)blockIdx.x) * blockDim.x + threadIdx.x;   // slot in the chunk
+  bool const live = r < c.n;
+  if (threadIdx.x == 0) { agree[0] = 0x7fffffff; agree[1] = -1; agree[2] = 0x7fffffff; agree[3] = -1; }
+  __syncthreads();
+  if (live) {
+    int a, m;
+    find_slice(v, c.geom[0][c.order ? (long)c.order[r] : c.first + r], a, m);   // what trace_ray finds for this ray
+    atomicMin(&agree[0], a); atomicMax(&agree[1], a);
+    atomicMin(&agree[2], m); atomicMax(&agree[3], m);
+  }
+  __syncthreads();
+  int const a0 = __builtin_amdgcn_readfirstlane(agree[0]), n = __builtin_amdgcn_readfirstlane(agree[2]);
+  bool const agreed = (a0 == agree[1]) && (n == agree[3]) && (n >= 1);      // (no live ray: a0 = 0x7fffffff, agree[1] = -1)
+  int px0 = 0, nx = 0;
+  if (agreed) {                             // (a0 + n <= atm_np: find_slice)
+    px0 = k.prof_of[a0];
+    nx = k.prof_of[a0 + n - 1] - px0 + 1;
+  }
+  bool const staged = __builtin_amdgcn_readfirstlane(agreed && nx >= 1 && nx <= JUR_TRACK_LDS_PROFILES);
+  px0 = __builtin_amdgcn_readfirstlane(px0);
+  nx = __builtin_amdgcn_readfirstlane(nx);
+  if (staged) {
+    for (int i = threadIdx.x; i < nx; i += blockDim.x) {     // (px0 + i < px0 + nx <= k.nprof; i < JUR_TRACK_LDS_PROFILES)
+      for (int j = 0; j < 3; j++) tab_d[j * nx + i] = k.x1[3 * (size_t)(px0 + i) + j];
+      tab_d[3 * nx + i] = k.lat[px0 + i];
+      tab_w[i] = k.first[px0 + i];
+      tab_w[nx + i] = k.len[px0 + i];
+      tab_w[2 * nx + i] = k.dir[px0 + i];
+    }
+    __syncthreads();                        // (uniform branch: every thread of the workgroup is here)
+  }
+  if (!live) return;
+  long const ray = c.order ? (long)c.order[r] : c.first + r;
+  LosWorkspace L{c.los + (size_t)(r >> 6) * los_tile_doubles(JUR_F_K + v.nw + v.ng) + (r & 63), JUR_F_K + v.nw + v.ng};
+  TraceResult t;
+  if (staged)
+    t = trace_ray(v, AtmTrack<TrackLds>{v, TrackLds{(lds_cptr)tab_d, (lds_iptr)tab_w, px0, nx}, k.prof_of}, c.geom[0][ray],
+                  c.geom[1][ray], c.geom[2][ray], c.geom[3][ray], c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
+  else
+    t = trace_ray(v, AtmTrack<TrackGlobal>{v, TrackGlobal{k.x1, k.lat, k.first, k.len, k.dir}, k.prof_of}, c.geom[0][ray],
+                  c.geom[1][ray], c.geom[2][ray], c.geom[3][ray], c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
+  c.np[r] = t.np;
+  c.tsurf[r] = t.tsurf;
+  if (c.np_out) c.np_out[ray] = t.np;
+  c.tp[0][ray] = t.tpz;
+  c.tp[1][ray] = t.tplon;
+  c.tp[2][ray] = t.tplat;
 }
 
 #undef TR_PZ
@@ -4285,8 +4529,13 @@ extern "C" void jurk_tune_trace_slice(int mode) { g_trace_slice = (mode == 1 || 
 #define JUR_TRACE_SLAB_DOUBLES 1280
 #endif
 
-extern "C" int jurk_launch_trace(jur_view_t const *v, jur_chunk_t const *c, void *stream) {
+extern "C" int jurk_launch_trace(jur_view_t const *v, jur_track_t const *trk, jur_chunk_t const *c, void *stream) {
   if (c->n <= 0) return 0;
+  if (trk && trk->ip == 2) {             // the 2-D rule has one instance: a lane per ray, workgroups of 256 slots
+    if (trk->nprof < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(jur_track_trace_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *v, *c, *trk);
+    return (int)hipGetLastError();
+  }
   int const block = 64;
   // a quad of lanes per ray where the launch stays within the chip's 4096 tracer wavefront slots with it AND the rays
   // have several emitters' columns to share (see jur_trace_lanes_kernel)

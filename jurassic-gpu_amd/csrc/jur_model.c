@@ -35,6 +35,9 @@ struct jur_model {
   void *d_chan, *d_sr, *d_pair, *d_pair_e0, *d_lvl, *d_crv, *d_ue, *d_rec;
   int arith;                    /* JUR_ARITH_*                                   */
   void *d_atm;                  /* one slab for the compact atmosphere           */
+  jur_track_t track;            /* ctl->ip and, under ip == 2, the profile table of the atmosphere on the device */
+  void *d_track;                /* its grow-only slab: x1 | lat as doubles, then first | len | dir | prof_of as ints */
+  size_t track_bytes;
   int atm_cap;
   int atm_slices;               /* distinct time stamps in the atmosphere        */
   int atm_k_zero;               /* jur_atm_k_zero of the rows on the device (view.atm_k_zero: this, where the switch is on) */
@@ -154,7 +157,8 @@ static int check_ctl(ctl_t const *ctl) {
   if (ctl->ng < 0 || ctl->ng > JUR_NG) { jur_set_error("ctl->ng=%d outside 0..%d", ctl->ng, JUR_NG); return JUR_EINVAL; }
   if (ctl->nd < 1 || ctl->nd > JUR_ND) { jur_set_error("ctl->nd=%d outside 1..%d", ctl->nd, JUR_ND); return JUR_EINVAL; }
   if (ctl->nw < 0 || ctl->nw > JUR_NW) { jur_set_error("ctl->nw=%d outside 0..%d", ctl->nw, JUR_NW); return JUR_EINVAL; }
-  if (ctl->ip != 1) { jur_set_error("only 1-D profile interpolation is supported (ctl->ip == 1, as upstream asserts)"); return JUR_EINVAL; }
+  if (ctl->ip == 3) { jur_set_error("IP 3 (3-D interpolation of a point cloud) is not supported along the line of sight: ctl->ip is 1 (profile) or 2 (satellite track)"); return JUR_EINVAL; }
+  if (ctl->ip != 1 && ctl->ip != 2) { jur_set_error("Unknown interpolation method, check IP! (ctl->ip == %d; 1 or 2)", ctl->ip); return JUR_EINVAL; }
   for (int id = 0; id < ctl->nd; id++)
     if (ctl->window[id] < 0 || ctl->window[id] >= (ctl->nw > 0 ? ctl->nw : 1)) { jur_set_error("ctl->window[%d] out of range", id); return JUR_EINVAL; }
   return JUR_OK;
@@ -193,6 +197,7 @@ int jur_model_create(jur_model_t **out, ctl_t const *ctl, jur_tables_t const *tb
   m->ctl = (ctl_t *)malloc(sizeof(ctl_t));
   if (!m->ctl) { free(m); return JUR_ENOMEM; }
   memcpy(m->ctl, ctl, sizeof(ctl_t));
+  m->track.ip = ctl->ip;
   jur_view_t *v = &m->view;
   v->ng = ctl->ng; v->nd = ctl->nd; v->nw = ctl->nw > 0 ? ctl->nw : 1;
   v->refrac = ctl->refrac; v->write_bbt = ctl->write_bbt;
@@ -330,7 +335,7 @@ void jur_model_destroy(jur_model_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_rec = NULL;
-  void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_order, m->d_sort_tmp, m->d_blk_order,
+  void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_track, m->d_order, m->d_sort_tmp, m->d_blk_order,
                   m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_fov_shape, m->d_kq, m->d_ctb, m->d_scene, m->d_side, m->d_pp};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
@@ -461,6 +466,41 @@ static int k_elision_on(void) {
 static void view_set_k_zero(jur_model_t *m) { m->view.atm_k_zero = m->atm_k_zero && k_elision_on(); }
 int jur_model_k_zero(jur_model_t *m) { if (!m || m->view.atm_np < 2) return 0; view_set_k_zero(m); return m->view.atm_k_zero; }
 
+/* Profile table of the packed rows under ip == 2 (jur_track_rows: the rule in jurassic_hip.h), rebuilt with every
+ * atmosphere; its size changes from call to call, so the slab only grows.  Nobody reads the old table any more: the
+ * caller has waited for the model's last call. */
+static int upload_track(jur_model_t *m, double const *h, long n) {
+  jur_track_t *t = &m->track;
+  t->nprof = 0;
+  size_t const cap = (size_t)n / 2 + 1;
+  size_t const nd = 4 * cap, ni = 3 * cap + (size_t)n;
+  char *buf = (char *)malloc(sizeof(double) * nd + sizeof(int) * ni);
+  if (!buf) return JUR_ENOMEM;
+  double *hx1 = (double *)buf, *hlat = hx1 + 3 * cap;
+  int *hfirst = (int *)(buf + sizeof(double) * nd), *hlen = hfirst + cap, *hdir = hlen + cap, *hprof = hdir + cap;
+  long const nx = jur_track_rows(n, h, h + (size_t)n, h + 2 * (size_t)n, h + 3 * (size_t)n, hfirst, hlen, (double (*)[3])hx1, NULL, hdir, hprof);
+  if (nx < 0) { free(buf); return (int)nx; }
+  for (long ix = 0; ix < nx; ix++) hlat[ix] = h[3 * (size_t)n + hfirst[ix]];
+  size_t const bytes = sizeof(double) * nd + sizeof(int) * ni;
+  if (bytes > m->track_bytes) {
+    if (m->d_track) (void)hipFree(m->d_track);
+    m->d_track = NULL;
+    m->track_bytes = 0;
+    if (hipMalloc(&m->d_track, bytes) != hipSuccess) { free(buf); jur_set_error("cannot allocate the profile table of the track"); return JUR_EHIP; }
+    m->track_bytes = bytes;
+  }
+  hipError_t e = hipMemcpyAsync(m->d_track, buf, bytes, hipMemcpyHostToDevice, m->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+  free(buf);
+  if (e != hipSuccess) { jur_set_error("cannot upload the profile table of the track: %s", hipGetErrorString(e)); return JUR_EHIP; }
+  double const *dd = (double const *)m->d_track;
+  int const *di = (int const *)((char const *)m->d_track + sizeof(double) * nd);
+  t->x1 = dd; t->lat = dd + 3 * cap;
+  t->first = di; t->len = di + cap; t->dir = di + 2 * cap; t->prof_of = di + 3 * cap;
+  t->nprof = (int)nx;
+  return JUR_OK;
+}
+
 /* upload packed rows [6+ng+nw][n] and derive what the kernels want to know about them; origin: JUR_ATM_* */
 static int upload_atm_rows(jur_model_t *m, double const *h, long n, int origin) {
   HIPCHK(hipSetDevice(m->device));
@@ -482,6 +522,10 @@ static int upload_atm_rows(jur_model_t *m, double const *h, long n, int origin) 
   if (m->have_done) {
     HIPCHK(hipEventSynchronize(m->ev_done));
     m->have_done = 0;
+  }
+  if (m->track.ip == 2) {       /* before the rows go up: a refused track leaves the model without atmosphere */
+    int const rt = upload_track(m, h, n);
+    if (rt) return rt;
   }
   HIPCHK(hipMemcpyAsync(m->d_atm, h, sizeof(double) * nrow * (size_t)n, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
@@ -819,6 +863,7 @@ int jur_model_reserve(jur_model_t *m, long nr) {
  * (too many rays, or more (channel, gas) chains per ray than the LDS rings hold). */
 static int pencil_rays_per_group(jur_model_t const *m, long nr) {
   if (m->ctl->formod == 1) return 0;                        /* the fused kernel is emissivity growth only */
+  if (m->ctl->ip == 2) return 0;                            /* ... and traces one profile per ray */
   if (m->pencil_rays <= 0 || nr > m->pencil_rays) return 0;
   long const npair = (long)m->view.nd * (m->view.ng > 0 ? m->view.ng : 1);
   int rb = m->pencil_rb;
@@ -978,7 +1023,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
     c.tsurf = m->d_tsurf;
     c.los = m->d_los;
     c.blk_order = blk_order;                          /* (set only where the call is this one launch) */
-    TIMED(0, jurk_launch_trace(&m->view, &c, s), "trace");
+    TIMED(0, jurk_launch_trace(&m->view, &m->track, &c, s), "trace");
     c.blk_order = NULL;
     if (m->host_call) {
       /* host entry: the input radiances, which only the epilogue reads (NaN mask), are uploaded beside the first
@@ -1451,7 +1496,7 @@ int jur_curtis_godson_host(jur_model_t *m, long nr, double const *const geom[7],
       c.los = m->d_los;
       c.eps = m->d_eps;
       c.status = m->d_status;
-      int ek = jurk_launch_trace(&m->view, &c, s);
+      int ek = jurk_launch_trace(&m->view, &m->track, &c, s);
       if (!ek) ek = jurk_launch_cg(&m->view, &c, d_cgp, d_cgt, d_cgu, s);
       if (ek) { jur_set_error("curtis_godson: kernel launch failed: %s", hipGetErrorString((hipError_t)ek)); rc = JUR_EHIP; goto done; }
     }
@@ -1926,7 +1971,7 @@ int jur_kat_traceray(jur_model_t *m, long nr, double const *const geom[7], doubl
       c.los = m->d_los;
       c.eps = m->d_eps;
       c.status = m->d_status;
-      int ek = jurk_launch_trace(&m->view, &c, s);
+      int ek = jurk_launch_trace(&m->view, &m->track, &c, s);
       if (!ek) ek = jurk_kat_los(&m->view, &c, d_los, d_tsurf, s);
       if (ek) { jur_set_error("kat_traceray: kernel launch failed: %s", hipGetErrorString((hipError_t)ek)); rc = JUR_EHIP; goto done; }
     }
@@ -2675,6 +2720,15 @@ static int param_pass_extend(jur_model_t *m, hipStream_t s, char const *who, sce
 /* ---- what jur_kernel_scene_host's family and jur_trial_scene_host open with ------------------------------------------- */
 /* the atmosphere a scene entry can take: no global balance (hydz_tail: why not, in the entry's words), 2..JUR_NP points,
  * ascending time stamps */
+/* The scene entries are built on per-ray blocks of ONE slice's state; under ip == 2 a ray reads two profiles of a track.
+ * Refused before anything else is looked at. */
+static int scene_ip_check(jur_model_t const *m, char const *who) {
+  if (m->ctl->ip != 2) return JUR_OK;
+  jur_set_error("%s: ip = 2 (satellite track) interpolates every point of a ray between two profiles, and the scene entries "
+                "hold the state of one slice per ray: use jur_formod_host and jur_kernel", who);
+  return JUR_EINVAL;
+}
+
 static int scene_atm_check(jur_model_t const *m, char const *who, char const *hydz_tail, atm_t const *atm) {
   if (m->ctl->hydz >= 0) {
     jur_set_error("%s: hydz = %g >= 0 adjusts all points as one profile, so %s", who, m->ctl->hydz, hydz_tail);
@@ -2768,6 +2822,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
                              scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt, scene_diag_t const *dg,
                              scene_grad_t const *gd, scene_param_t *pm) {
   char const *const who = pm ? "jur_param_scene_host" : gd ? "jur_gradient_scene_host" : rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : (dg && dg->gin) ? "jur_gain_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+  { int const ri = scene_ip_check(m, who); if (ri) return ri; }
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
   if (rt) m->ov_cells = m->ov_failed = 0;           /* (the counts of jur_model_last_scene_overflow are this call's) */
@@ -3602,6 +3657,7 @@ done:
  * later calls would accept; if it cannot go back, with none ("no atmosphere set") */
 static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
   if (atm->np < 2 || atm->np > JUR_NP) return rc;
+  if (m->ctl->ip == 2 && rc != JUR_OK) return rc;   /* scene_ip_check refused the call before the model's atmosphere was touched */
   if (rc == JUR_OK) return jur_model_set_atm(m, atm);
   char msg[512];
   snprintf(msg, sizeof msg, "%s", jur_last_error());
@@ -3683,6 +3739,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
                             long const *rowptr, double const *y, double const *weight, int ntrial, double const *dx,
                             double const *prior_ivar, double const *prior_xa, double *cost, double *prior, long max_rays_per_pass) {
   char const *const who = "jur_trial_scene_host";
+  { int const ri = scene_ip_check(m, who); if (ri) return ri; }
   m->ov_cells = m->ov_failed = 0;                   /* (the counts of jur_model_last_scene_overflow are this call's) */
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (ntrial < 1 || ntrial > 64) { jur_set_error("%s: ntrial = %d: 1 to 64 trials per call", who, ntrial); return JUR_EINVAL; }
@@ -4216,6 +4273,7 @@ static int param_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
                             jur_param_scene_in_t const *pin, jur_param_scene_out_t const *pout,
                             double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
   char const *const who = "jur_param_scene_host";
+  { int const ri = scene_ip_check(m, who); if (ri) return ri; }
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   int rc = jur_param_check_args(who, pin->in, pout->out);
   if (rc) return rc;
@@ -4481,6 +4539,7 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
   memcpy(c->ctl, m->ctl, sizeof(ctl_t));
   c->d_atm = NULL; c->atm_cap = 0; c->atm_slices = 0; c->atm_k_zero = 0; c->view.atm_k_zero = 0;
   c->view.atm_np = 0;
+  c->d_track = NULL; c->track_bytes = 0; c->track.nprof = 0;
   c->d_los = NULL; c->d_eps = NULL; c->d_np = NULL; c->d_tsurf = NULL; c->d_status = NULL;
   c->los_bytes = 0; c->ws_rays = 0; c->ws_trace_rays = 0;
   c->d_order = NULL; c->d_sort_tmp = NULL; c->d_blk_order = NULL; c->order_cap = 0; c->sort_tmp_bytes = 0; c->n_blk_order = 0;
@@ -4503,6 +4562,8 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
 static void refresh_switches(jur_model_t *m, ctl_t const *ctl) {
   jur_view_t *v = &m->view;
   if (ctl->ng != v->ng || ctl->nd != v->nd) DIE("ng/nd changed after the tables were initialised");
+  if (ctl->ip != 1 && ctl->ip != 2) DIE("IP %d is not supported along the line of sight (1: profile, 2: satellite track)", ctl->ip);
+  if (ctl->ip != m->track.ip) { m->track.ip = ctl->ip; m->track.nprof = 0; m->h_atm_n = 0; }   /* the next set_atm builds the profile table */
   memcpy(m->ctl, ctl, sizeof(ctl_t));
   v->refrac = ctl->refrac; v->write_bbt = ctl->write_bbt; v->rayds = ctl->rayds; v->raydz = ctl->raydz;
   /* upstream looks the emitters up on the first call that has the switch on, whichever call that is

@@ -215,6 +215,9 @@ def lib():
         L.jur_kat_ega_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
         if hasattr(L, "jur_kat_cga_eps"):            # (an older build selected with JURASSIC_HIP_SO for an A/B run has none)
             L.jur_kat_cga_eps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, dp, dp, dp, dp, C.c_int, C.c_int, dp]
+        if hasattr(L, "jur_track_profiles"):         # (an older build selected with JURASSIC_HIP_SO for an A/B run has none)
+            L.jur_track_profiles.restype = C.c_long
+            L.jur_track_profiles.argtypes = [C.c_void_p, ip_, ip_, dp, ip_]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
         L.jur_kat_update.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int] + [dp] * 6
         L.jur_kat_traceray.argtypes = [C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), C.POINTER(C.c_int)]
@@ -1687,6 +1690,17 @@ def formod_contrib(ctl, atm, obs):
 def dropin_finalize():
     """Free the lanes and tables behind formod() (jur_dropin_finalize) -> number of lanes freed."""
     return lib().jur_dropin_finalize()
+
+
+def track_profiles(atm):
+    """jur_track_profiles: the profile table of a satellite track (IP 2; the rule in jurassic_hip.h), host only
+    -> dict(first, len, block_of (nprof,), x1 (nprof, 3)); JurassicError with upstream's words for a refused track."""
+    cap = atm.np // 2 + 1
+    first, length, block = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+    x1 = np.zeros((cap, 3))
+    ip_ = C.POINTER(C.c_int)
+    n = _chk(lib().jur_track_profiles(C.byref(atm), first.ctypes.data_as(ip_), length.ctypes.data_as(ip_), _p(x1), block.ctypes.data_as(ip_)))
+    return dict(first=first[:n], len=length[:n], block_of=block[:n], x1=x1[:n])
 
 
 def intpol_atm(ctl, dest, src, device=0):
