@@ -605,6 +605,17 @@ JUR_HIDDEN void jur_hydrostatic_profile(double hydz, int n, double const *z, dou
  * distinct slices of two points or more among the rays' (first, len) */
 JUR_HIDDEN int jur_scene_hydro_check(char const *who, int np, long nseg, int const *sfirst, int const *slen);
 JUR_HIDDEN long jur_scene_ray_slices_of(int np, long nr, int const *first, int const *len, int *sfirst, int *slen);
+/* segments of the balance as one value: n of them, their first points and lengths (host or device memory) */
+typedef struct { long n; long const *at; int const *len; } jur_hyseg_t;
+static inline jur_hyseg_t jur_hyseg_sub(jur_hyseg_t h, long from, long n) { jur_hyseg_t const o = {n, h.at + from, h.len + from}; return o; }
+/* The segment lists of a scene entry, malloc'ed as at[nh] with the ints len[nh] behind (NULL: out of memory): the nrs ray
+ * slices (hyf: first | len, nr apart); of the copies 1 .. ncopy - 1 laid out by off those whose raised row prow[j] the
+ * pressures depend on (p, T, row_h2o), *nhc of them; the trial copies 1 .. tncopy - 1 laid out by toff, *ntc of them */
+JUR_HIDDEN long *jur_scene_hydro_segments(size_t nh, long nr, long nrs, int const *hyf, long ncopy, long const *off, int const *prow,
+                                          int row_h2o, long tncopy, long const *toff, long *nhc, long *ntc);
+/* the default cap on the slots of a pass: a sixteenth of what `used` bytes leave of the workspace budget, in slots of
+ * slot_bytes; never fewer than 4096, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
+JUR_HIDDEN long jur_scene_default_cap(long budget, long used, size_t slot_bytes);
 /* the rays of every slice as one CSR (sid[r] < 0: a ray without state elements, in no list): sptr[nslice + 1], srays[up
  * to nr], the rays of a slice ascending; returns the length of the lists */
 JUR_HIDDEN long jur_scene_rays_by_slice(long nr, long nslice, int const *sid, long *sptr, int *srays);

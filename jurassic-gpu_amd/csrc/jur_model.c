@@ -1703,23 +1703,31 @@ int jur_model_ret_windows(jur_model_t const *m, ctl_t *ctl) {
   return JUR_OK;
 }
 
-static int scene_timed_begin(jur_model_t *m, hipStream_t s);
-static void scene_timed_end(jur_model_t *m, int ti, hipStream_t s);
+/* Events around the kernels of jur_kernel_scene_host while timing is on (kind 5) */
+static int scene_timed_begin(jur_model_t *m, hipStream_t s) {
+  int const ti = (m->timing && m->ntimed < JUR_MAX_TIMED) ? m->ntimed++ : -1;
+  if (ti >= 0) { m->evkind[ti] = 5; if (hipEventRecord(m->evpool[2 * ti], s) != hipSuccess) (void)hipGetLastError(); }
+  return ti;
+}
+static void scene_timed_end(jur_model_t *m, int ti, hipStream_t s) {
+  if (ti >= 0 && hipEventRecord(m->evpool[2 * ti + 1], s) != hipSuccess) (void)hipGetLastError();
+}
+/* one launch between the two records: yields the launch's status */
+#define SCENE_TIMED(m, s, launch) __extension__ ({ int const ti_ = scene_timed_begin(m, s); int const ek_ = (launch); scene_timed_end(m, ti_, s); ek_; })
+/* fmt: "%s: <what> kernel launch failed" */
+static int launch_failed(char const *fmt, char const *who) { jur_set_error(fmt, who); return JUR_EHIP; }
 
-/* jur_scene_hydro_kernel on nseg segments (d_at, d_len: device) of rows [nrow][ld] as the model lays an atmosphere out:
+/* jur_scene_hydro_kernel on the segments hy (device) of rows [nrow][ld] as the model lays an atmosphere out:
  * time, z, lon, lat, p, T, q[ng], k[nw].  Timed with the scene entries' kernels. */
-static int scene_hydro_launch(jur_model_t *m, hipStream_t s, long nseg, long const *d_at, int const *d_len, double *rows, size_t ld) {
-  if (nseg <= 0) return 0;
+static int scene_hydro_launch(jur_model_t *m, hipStream_t s, jur_hyseg_t hy, double *rows, size_t ld) {
+  if (hy.n <= 0) return 0;
   int const ig = m->view.ig_h2o;
   jur_scene_hydro_t hq;
   memset(&hq, 0, sizeof hq);
-  hq.nseg = nseg; hq.at = d_at; hq.len = d_len; hq.hydz = m->scene_hydz;
+  hq.nseg = hy.n; hq.at = hy.at; hq.len = hy.len; hq.hydz = m->scene_hydz;
   hq.z = rows + 1 * ld; hq.lat = rows + 3 * ld; hq.p = rows + 4 * ld; hq.t = rows + 5 * ld;
   hq.q = ig >= 0 ? rows + (6 + (size_t)ig) * ld : NULL;
-  int const ti = scene_timed_begin(m, s);
-  int const ek = jurk_scene_hydro(&hq, s);
-  scene_timed_end(m, ti, s);
-  return ek;
+  return SCENE_TIMED(m, s, jurk_scene_hydro(&hq, s));
 }
 
 /* ---- full a-priori precision of the slices ------------------------------------------------ */
@@ -2136,15 +2144,6 @@ done:
 }
 
 /* ---- block Jacobian of a scene -------------------------------------------------- */
-/* Events around the kernels of jur_kernel_scene_host while timing is on (kind 5) */
-static int scene_timed_begin(jur_model_t *m, hipStream_t s) {
-  int const ti = (m->timing && m->ntimed < JUR_MAX_TIMED) ? m->ntimed++ : -1;
-  if (ti >= 0) { m->evkind[ti] = 5; if (hipEventRecord(m->evpool[2 * ti], s) != hipSuccess) (void)hipGetLastError(); }
-  return ti;
-}
-static void scene_timed_end(jur_model_t *m, int ti, hipStream_t s) {
-  if (ti >= 0 && hipEventRecord(m->evpool[2 * ti + 1], s) != hipSuccess) (void)hipGetLastError();
-}
 
 /* Sibling of upload_atm_rows for rows that a kernel is about to write on the device: makes room for nt points in the
  * model's slab, waits for readers of the old rows and points the view at the new ones.  No host image of these rows
@@ -2285,12 +2284,8 @@ static int solve_enqueue(jur_model_t *m, hipStream_t s, char const *who, long ns
     pq.ivar = dr; pq.g = dg; pq.live = dlive;
     q.A = dAp; q.b = dg; q.prior_ivar = NULL; q.prior_dx = NULL; q.mode = JUR_DAMP_MARQUARDT;
     if (by_prior && hipMemsetAsync(dzl, 0, sizeof(double) * NS, s) != hipSuccess) { (void)hipGetLastError(); jur_set_error("%s: memset failed", who); return JUR_EHIP; }
-    if (!by_prior) {                              /* one assembly serves every damping: fma(lam, D, D) is the solve kernel's */
-      int const ti = scene_timed_begin(m, s);
-      int const ek = jurk_scene_prior_assemble(&pa, nb, s);
-      scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("%s: prior assembly kernel launch failed", who); return JUR_EHIP; }
-    }
+    /* without JUR_DAMP_PRIOR one assembly serves every damping: fma(lam, D, D) is the solve kernel's */
+    if (!by_prior && SCENE_TIMED(m, s, jurk_scene_prior_assemble(&pa, nb, s))) return launch_failed("%s: prior assembly kernel launch failed", who);
   }
   for (size_t l = 0; l < NL; l++) {
     q.lam = dlam + l * NS; q.dx = ddx + l * NB; q.pred = dpred + l * NS; q.status = dstat + l * NS;
@@ -2460,10 +2455,7 @@ static int gain_enqueue(jur_model_t *m, hipStream_t s, char const *who, jur_scen
   if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
   q->ncomp = in->ncomp;
   q->weff = W + o.weff; q->var = W + o.var; q->gmap = (int const *)(W + o.map); q->gain = gain_at ? gain_at : W + o.gain; q->sigc = W + o.sigc;
-  int const ti = scene_timed_begin(m, s);
-  int const ek = jurk_scene_gain(q, ntile, ngroups, s);
-  scene_timed_end(m, ti, s);
-  if (ek) { jur_set_error("%s: gain kernel launch failed", who); return JUR_EHIP; }
+  if (SCENE_TIMED(m, s, jurk_scene_gain(q, ntile, ngroups, s))) return launch_failed("%s: gain kernel launch failed", who);
   if (nk && out->gain) e = hipMemcpyAsync(out->gain, q->gain, sizeof(double) * nk, hipMemcpyDeviceToHost, s);
   if (NC && NB && e == hipSuccess) e = hipMemcpyAsync(out->sigma_comp, q->sigc, sizeof(double) * NC * NB, hipMemcpyDeviceToHost, s);
   if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
@@ -2480,19 +2472,22 @@ static double *scene_row_array(atm_t *atm, int ng, int row) {
 
 /* Host image of what the trial kernels index by: two blocks, each uploaded with one copy.
  * longs: wptr[ns + 1] | off[ncopy + 1] | sptr[ns + 1];  ints: cdesc[3 ncopy] (first | prow = -1 | pip = 0 of every copy,
- * for jur_scene_stack_kernel) | sfirst[ns] | erow[nb] | eip[nb] | tcopy0[nr] | srays[nlist] */
+ * for jur_scene_stack_kernel) | sfirst[ns] | erow[nb] | eip[nb] | tcopy0[nr] | srays[nlist]
+ * box: the box on the state per element, lo | hi (NULL: the model has none) */
 typedef struct {
   int ntrial;
   long nslice, nb, ncopy, nt, nr, nlist;
   long *longs, *wptr, *off, *sptr;
   int *ints, *cdesc, *sfirst, *erow, *eip, *tcopy0, *srays;
   size_t nlong, nint;
+  double *box;
 } trial_plan_t;
 
-static void trial_plan_free(trial_plan_t *p) { free(p->longs); free(p->ints); memset(p, 0, sizeof *p); }
+static void trial_plan_free(trial_plan_t *p) { free(p->longs); free(p->ints); free(p->box); memset(p, 0, sizeof *p); }
 
-static int trial_plan_make(trial_plan_t *p, char const *who, ctl_t const *ctl, atm_t const *atm, int ntrial, long nr, long nslice,
+static int trial_plan_make(trial_plan_t *p, char const *who, jur_model_t const *m, atm_t const *atm, int ntrial, long nr, long nslice,
                            jur_scene_slice_t const *sl, int const *sid) {
+  ctl_t const *const ctl = m->ctl;
   memset(p, 0, sizeof *p);
   size_t const NS = (size_t)nslice, NR = (size_t)nr;
   long nb = 0, nt = atm->np;
@@ -2531,23 +2526,63 @@ static int trial_plan_make(trial_plan_t *p, char const *who, ctl_t const *ctl, a
   if (rc) { trial_plan_free(p); return rc; }
   for (long r = 0; r < nr; r++) p->tcopy0[r] = sid[r] >= 0 ? (int)(1 + (long)sid[r] * ntrial) : 0;
   p->nlist = jur_scene_rays_by_slice(nr, nslice, sid, p->sptr, p->srays);
+  if (m->sb_nq && nb > 0) {
+    if (!(p->box = (double *)malloc(sizeof(double) * 2 * (size_t)nb))) { trial_plan_free(p); return JUR_ENOMEM; }
+    jur_state_bounds_expand(m->sb_lo, m->sb_hi, nb, p->erow, p->box, p->box + nb);
+  }
   return JUR_OK;
 }
 
 /* a field of view in a call: the kernel's arguments (shape, status word and the rays' time stamps and view-point altitudes
- * are the call's; the pass fills in the rest) and the effective mask [rays][nd] on the device */
-typedef struct { jur_scene_fov_t k; double const *live; } scene_fov_t;
+ * are the call's; the pass fills in the rest), the effective mask [rays][nd] on the device and, for the Jacobian passes,
+ * the convolved transmittances by ray [rays][nd] */
+typedef struct { jur_scene_fov_t k; double const *live; double *tau; } scene_fov_t;
+
+/* The device views of a trial pass, which trial_run consumes.  tq.R (a full prior precision is set) and of.flag
+ * (JUR_OVERFLOW_ISOLATE) say whether the last two take part. */
+typedef struct { jur_scene_stack_t sk; jur_scene_trial_t st; jur_scene_trial_pass_t ps; jur_scene_pquad_t tq; jur_scene_ovfold_t of; } trial_dev_t;
+
+/* ... of the plan pl, whose two blocks lie at Lp and Ip on the device, over the call's arrays there.  ivar, xa: the
+ * diagonal prior or both NULL; box: lo | hi or NULL; d_R: the full prior precision or NULL, laid out by aptr, with v for
+ * xa - (x + dx) of every trial; oflag, opart: the trials' overflow flags and the fold's counts, or NULL; state, choice: of
+ * the slices of a retrieval, or NULL. */
+static void trial_dev_fill(trial_dev_t *td, jur_model_t const *m, trial_plan_t const *pl, int np0, double tmax, double span,
+                           long const *Lp, int const *Ip, double *base, double const *geom, double const *in_rad, int const *first,
+                           int const *len, double const *y, double const *weight, double const *dx, double const *ivar,
+                           double const *xa, double *prior, double *cost, double const *box, double const *d_R, long const *aptr,
+                           double *v, int *oflag, long *opart, int *state, int const *choice) {
+  long const *const d_off = Lp + (pl->off - pl->longs);
+  memset(td, 0, sizeof *td);
+  jur_scene_stack_t *const sk = &td->sk;
+  sk->ncopy = (int)pl->ncopy; sk->np0 = np0; sk->nrow = 6 + m->view.ng + m->view.nw; sk->ng = m->view.ng; sk->nt = pl->nt;
+  sk->off = d_off; sk->first = Ip; sk->prow = Ip + pl->ncopy; sk->pip = Ip + 2 * pl->ncopy;
+  sk->base = base; sk->tmax = tmax; sk->span = span;
+  jur_scene_trial_t *const st = &td->st;
+  st->nslice = pl->nslice; st->ntrial = pl->ntrial; st->np0 = np0; st->nt = pl->nt;
+  st->wptr = Lp; st->off = d_off; st->sfirst = Ip + (pl->sfirst - pl->ints); st->erow = Ip + (pl->erow - pl->ints);
+  st->eip = Ip + (pl->eip - pl->ints); st->state = state; st->choice = choice;
+  st->base = base; st->dx = dx; st->ivar = ivar; st->xa = xa; st->prior = prior;
+  if (box) { st->lo = box; st->hi = box + pl->nb; }
+  jur_scene_trial_pass_t *const ps = &td->ps;
+  ps->nr = pl->nr; ps->nd = m->ctl->nd; ps->ntrial = pl->ntrial; ps->first = first; ps->len = len; ps->tcopy0 = Ip + (pl->tcopy0 - pl->ints);
+  ps->off = d_off; ps->in_geom = geom; ps->in_rad = in_rad; ps->nslice = pl->nslice; ps->sptr = Lp + (pl->sptr - pl->longs);
+  ps->srays = Ip + (pl->srays - pl->ints); ps->state = state; ps->y = y; ps->weight = weight; ps->cost = cost;
+  td->tq.nslice = pl->nslice; td->tq.nvec = pl->ntrial; td->tq.wptr = Lp; td->tq.aptr = aptr; td->tq.R = d_R; td->tq.v = v;
+  td->tq.out = prior; td->tq.state = state;
+  if (oflag) { td->of.nslice = pl->nslice; td->of.ntrial = pl->ntrial; td->of.flag = oflag; td->of.state = state; td->of.cost = cost; td->of.part = opart; }
+}
 
 /* One trial pass over the device: stacks the trial copies from the base rows (st->base), moves the elements by st->dx,
  * forms the prior terms (or zeroes them), traces the rays of every pass and continues the cost chains.  ps carries the
  * ray arrays of the call (or of its gathered rays); its r0, r1, n, geom, rad, atm_time and `above` are set here.  The
  * model's view is left on the trial atmosphere.  Nothing is waited for after the stacking. */
-/* nhy > 0 (the hydrostatic balance is on): the segments of the trial copies, balanced after the elements have moved.
+/* hy.n > 0 (the hydrostatic balance is on): the segments of the trial copies, balanced after the elements have moved.
  * of (JUR_OVERFLOW_ISOLATE): the untraceable rays of every pass are flagged in of->flag (zeroed by the caller) before the
  * next pass overwrites the counts, and folded into the costs after the last. */
-static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, jur_scene_stack_t *sk, jur_scene_trial_t *st,
-                     jur_scene_trial_pass_t *ps, long nb, long npass, long const *pass, long nmax, scene_fov_t *fv,
-                     jur_scene_pquad_t const *tq, long nhy, long const *d_hyat, int const *d_hylen, jur_scene_ovfold_t const *of) {
+static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, trial_dev_t *td, long nb, long npass,
+                     long const *pass, long nmax, scene_fov_t *fv, jur_hyseg_t hy) {
+  jur_scene_stack_t *const sk = &td->sk; jur_scene_trial_t *const st = &td->st; jur_scene_trial_pass_t *const ps = &td->ps;
+  jur_scene_pquad_t const *const tq = td->tq.R ? &td->tq : NULL; jur_scene_ovfold_t const *const of = td->of.flag ? &td->of : NULL;
   size_t const nrow = (size_t)sk->nrow;
   int const nd = ps->nd;
   int rc;
@@ -2557,9 +2592,9 @@ static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const
   int ti = scene_timed_begin(m, s);
   int ek = jurk_scene_stack(sk, s);
   if (!ek) ek = jurk_scene_elements(st, JUR_ELEM_APPLY, nb, s);
-  if (nhy > 0) {                                   /* (a timed launch of its own, between the two halves of this one) */
+  if (hy.n > 0) {                                  /* (a timed launch of its own, between the two halves of this one) */
     scene_timed_end(m, ti, s);
-    if (!ek) ek = scene_hydro_launch(m, s, nhy, d_hyat, d_hylen, (double *)m->d_atm, (size_t)sk->nt);
+    if (!ek) ek = scene_hydro_launch(m, s, hy, (double *)m->d_atm, (size_t)sk->nt);
     ti = scene_timed_begin(m, s);
   }
   hipError_t e = hipMemsetAsync(ps->cost, 0, sizeof(double) * (size_t)ps->nslice * (size_t)ps->ntrial, s);
@@ -2589,42 +2624,25 @@ static int trial_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const
     ps->r0 = pass[p]; ps->r1 = pass[p + 1]; ps->n = n;
     ps->geom = m->d_io; ps->rad = ps->geom + 7 * N;
     double *const tau = ps->rad + N * nd, *const tp = tau + N * nd;
-    ti = scene_timed_begin(m, s);
-    ek = jurk_scene_trial_rays(ps, s);
-    scene_timed_end(m, ti, s);
-    if (ek) { jur_set_error("%s: trial replication kernel launch failed", who); return JUR_EHIP; }
+    if (SCENE_TIMED(m, s, jurk_scene_trial_rays(ps, s))) return launch_failed("%s: trial replication kernel launch failed", who);
     if ((rc = jur_formod_device(m, n, ps->geom, ps->rad, tau, tp, m->d_io_np, m->d_status, s))) return rc;
     jur_scene_trial_pass_t pf = *ps;
     if (fv) {                                    /* the costs read the convolved radiances under the effective mask */
       fv->k.r0 = ps->r0; fv->k.r1 = ps->r1; fv->k.ntrial = ps->ntrial; fv->k.rowptr = NULL;
       fv->k.rad = ps->rad; fv->k.tau = NULL; fv->k.rad_f = m->d_fov; fv->k.tau_f = NULL;
-      ti = scene_timed_begin(m, s);
-      ek = jurk_scene_fov(&fv->k, s);
-      scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("%s: field-of-view kernel launch failed", who); return JUR_EHIP; }
+      if (SCENE_TIMED(m, s, jurk_scene_fov(&fv->k, s))) return launch_failed("%s: field-of-view kernel launch failed", who);
       pf.rad = m->d_fov; pf.in_rad = fv->live;
     }
-    ti = scene_timed_begin(m, s);
-    ek = jurk_scene_trial_cost(&pf, s);
-    scene_timed_end(m, ti, s);
-    if (ek) { jur_set_error("%s: trial cost kernel launch failed", who); return JUR_EHIP; }
+    if (SCENE_TIMED(m, s, jurk_scene_trial_cost(&pf, s))) return launch_failed("%s: trial cost kernel launch failed", who);
     if (of) {
       jur_scene_ovf_t oq;
       memset(&oq, 0, sizeof oq);
       oq.n = n; oq.r0 = ps->r0; oq.r1 = ps->r1; oq.ntrial = ps->ntrial; oq.per = ps->ntrial; oq.nslice = ps->nslice;
       oq.tcopy0 = ps->tcopy0; oq.np = m->d_io_np; oq.flag = (int *)of->flag;
-      ti = scene_timed_begin(m, s);
-      ek = jurk_scene_overflow(&oq, s);
-      scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("%s: overflow kernel launch failed", who); return JUR_EHIP; }
+      if (SCENE_TIMED(m, s, jurk_scene_overflow(&oq, s))) return launch_failed("%s: overflow kernel launch failed", who);
     }
   }
-  if (of) {
-    ti = scene_timed_begin(m, s);
-    ek = jurk_scene_overflow_fold(of, s);
-    scene_timed_end(m, ti, s);
-    if (ek) { jur_set_error("%s: overflow fold kernel launch failed", who); return JUR_EHIP; }
-  }
+  if (of && SCENE_TIMED(m, s, jurk_scene_overflow_fold(of, s))) return launch_failed("%s: overflow fold kernel launch failed", who);
   return JUR_OK;
 }
 
@@ -2810,18 +2828,431 @@ static int scene_open(scene_open_t *o, jur_model_t *m, char const *who, atm_t co
   return JUR_OK;
 }
 
+/* The uploads a call opens with, enqueued on s, to where the caller's slab has them: the base rows, the 7 geometry rows,
+ * the input radiances, nfl * nr ints of first | len (| the caller's own), the zeroed status word and, where a field of view
+ * is set, the effective mask.  fv is filled for the rays of the call. */
+static hipError_t scene_open_upload(jur_model_t *m, hipStream_t s, scene_open_t const *o, int np0, long nr, double const *const geom[7],
+                                    double const *rad_in, double *d_base, double *d_geom, double *d_inrad, int *d_first, int nfl,
+                                    double *d_live, scene_fov_t *fv) {
+  size_t const NR = (size_t)nr, nrow = 6 + (size_t)m->view.ng + m->view.nw, nrd = NR * (size_t)m->ctl->nd;
+  hipError_t e = hipMemcpyAsync(d_base, o->hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
+  for (int q = 0; q < 7 && e == hipSuccess; q++) e = hipMemcpyAsync(d_geom + (size_t)q * NR, geom[q], sizeof(double) * NR, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_inrad, rad_in, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_first, o->first, sizeof(int) * (size_t)nfl * NR, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
+  if (m->fov_n > 0 && e == hipSuccess) e = hipMemcpyAsync(d_live, o->hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+  memset(fv, 0, sizeof *fv);
+  fv->k.nr = nr; fv->k.nd = m->ctl->nd; fv->k.time = d_geom; fv->k.vpz = d_geom + 4 * NR;
+  fv->k.n = m->fov_n; fv->k.dz = m->d_fov_shape; fv->k.w = m->d_fov_shape + JUR_NSHAPE; fv->k.status = m->d_status;
+  fv->live = d_live;
+  return e;
+}
+
+/* A cut of a call's rays into passes: pass p is the rays [cut[p], cut[p + 1]) of the rays that rp (host) is the rowptr of.
+ * fwd: forward-only passes, one slot per ray and no blocks (the pass view comes with the all-zero rowptr then).  stay: the
+ * blocks of a Jacobian pass are written where they lie among those of all rays, from k on (device), not over those of
+ * the pass before.  k_home: where the blocks go on the host, or NULL. */
+typedef struct { long const *cut; long n; long const *rp; int fwd, stay; double *k, *k_home; } scene_cut_t;
+
+/* JUR_OVERFLOW_ISOLATE in the passes of a retrieval's iteration: the untraceable slots of every pass are flagged in
+ * fold.flag (the slice of a ray from tcopy0 and per, as jur_scene_ovf_t's), before the next pass overwrites the counts;
+ * after the last pass the flagged slices fail, on the device */
+typedef struct { int per; int const *tcopy0; jur_scene_ovfold_t fold; } scene_ovflags_t;
+
+/* The passes of one cut over the stacked atmosphere.  Installs and stacks the rows (st), balances the raised copies (hy),
+ * prepares the atmosphere, waits once and reserves the forward model's workspace for the largest pass, nmax slots.  Then
+ * per pass: the rays are replicated, the forward model runs, the untraceable slots are flagged (ov), the results are
+ * convolved (fv), the quotients taken, the sums continued (nq over ntiles tiles; forward-only from the held blocks gq over
+ * ngroups workgroups) and the chains of C (pm: phase 2 of jur_param_scene_host), the blocks go home, and the pass is
+ * waited for.  a carries the ray arrays and the rowptr of the cut's rays; what belongs to a pass is set here. */
+static int scene_passes_run(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, jur_scene_stack_t *st, jur_scene_pass_t *a,
+                            jur_scene_normal_t const *nq, long ntiles, jur_scene_grad_t const *gq, long ngroups, scene_fov_t *fv,
+                            jur_hyseg_t hy, scene_cut_t const *c, scene_ovflags_t const *ov, scene_param_t *pm, long nmax) {
+  int const nd = a->nd, fwd = c->fwd;
+  long const *const rp = c->rp;
+  int rc;
+  m->h_atm_n = 0;                                /* the device no longer holds the caller's atmosphere */
+  if ((rc = install_stacked_rows(m, atm, st->nt, st->ncopy - 1))) return rc;
+  st->rows = (double *)m->d_atm;
+  a->atm_time = m->view.atm_time;
+  int ek = SCENE_TIMED(m, s, jurk_scene_stack(st, s));
+  if (!ek) ek = scene_hydro_launch(m, s, hy, (double *)m->d_atm, (size_t)st->nt);
+  if (!ek) ek = jurk_prepare_atm(&m->view, (double *)m->d_atm + (size_t)st->nrow * (size_t)st->nt, s);
+  /* the one wait before the passes: the uploads have left the host arrays, the stacked rows stand */
+  if (ek || hipStreamSynchronize(s) != hipSuccess) {
+    (void)hipGetLastError(); m->view.atm_np = 0; jur_set_error("%s: stacking the atmosphere failed", who); return JUR_EHIP;
+  }
+  if ((rc = jur_model_reserve(m, nmax))) return rc;   /* the forward model's workspace for the largest pass, before the first */
+  for (long p = 0; p < c->n; p++) {
+    long const r0 = c->cut[p], r1 = c->cut[p + 1], n = fwd ? r1 - r0 : (rp[r1] - rp[r0]) + (r1 - r0), nk = fwd ? 0 : (rp[r1] - rp[r0]) * nd;
+    size_t const N = (size_t)n;
+    a->r0 = r0; a->r1 = r1; a->n = n;
+    if (c->stay && !fwd) a->k = c->k + (size_t)rp[r0] * (size_t)nd;
+    a->geom = m->d_io; a->rad = a->geom + 7 * N; a->tau = a->rad + N * nd; a->tp = a->tau + N * nd; a->np = m->d_io_np;
+    if (SCENE_TIMED(m, s, jurk_scene_rays(a, s))) return launch_failed("%s: replication kernel launch failed", who);
+    if ((rc = jur_formod_device(m, n, a->geom, a->rad, a->tau, a->tp, a->np, m->d_status, s))) return rc;
+    if (ov) {
+      jur_scene_ovf_t oq;
+      memset(&oq, 0, sizeof oq);
+      oq.n = n; oq.r0 = r0; oq.r1 = r1; oq.ntrial = 0; oq.per = ov->per; oq.nslice = ov->fold.nslice;
+      oq.rowptr = a->rowptr; oq.tcopy0 = ov->tcopy0; oq.np = a->np; oq.flag = (int *)ov->fold.flag;
+      if (SCENE_TIMED(m, s, jurk_scene_overflow(&oq, s))) return launch_failed("%s: overflow kernel launch failed", who);
+    }
+    jur_scene_pass_t af = *a;                    /* what reads the forward model's results ... */
+    if (fv) {                                    /* ... reads them convolved, the sums under the effective mask */
+      fv->k.r0 = r0; fv->k.r1 = r1; fv->k.ntrial = 0; fv->k.rowptr = a->rowptr;
+      fv->k.rad = a->rad; fv->k.tau = a->tau; fv->k.rad_f = m->d_fov; fv->k.tau_f = fv->tau;
+      if (SCENE_TIMED(m, s, jurk_scene_fov(&fv->k, s))) return launch_failed("%s: field-of-view kernel launch failed", who);
+      af.rad = m->d_fov; af.fov_tau = fv->tau; af.in_rad = fv->live;
+    }
+    if (SCENE_TIMED(m, s, jurk_scene_quot(&af, nk, s))) return launch_failed("%s: quotient kernel launch failed", who);
+    if (ntiles && !fwd && SCENE_TIMED(m, s, jurk_scene_normal(&af, nq, ntiles, s))) return launch_failed("%s: normal-equation kernel launch failed", who);
+    if (ngroups && fwd && SCENE_TIMED(m, s, jurk_scene_gradient(&af, nq, gq, ngroups, s))) return launch_failed("%s: gradient kernel launch failed", who);
+    if (pm && (rc = param_pass_extend(m, s, who, pm, r0, r1, a->k, rp[r0] * nd))) return rc;
+    /* the blocks of the pass go home (where asked for); the one wait of the pass */
+    hipError_t e = (nk > 0 && c->k_home) ? hipMemcpyAsync(c->k_home + (size_t)rp[r0] * nd, a->k, sizeof(double) * (size_t)nk, hipMemcpyDeviceToHost, s) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); return JUR_EHIP; }
+  }
+  /* all passes are done: the flagged slices fail before the solve */
+  if (ov && SCENE_TIMED(m, s, jurk_scene_overflow_fold(&ov->fold, s))) return launch_failed("%s: overflow fold kernel launch failed", who);
+  return JUR_OK;
+}
+
+/* The loop's part of the slab (jur_retrieve_scene_host).  dbl doubles: tcost | tprior [nlam][ns] | prior0 [ns] | xout | xa
+ * [nb] | the arrays of the rays that remain once slices have ended: geom [7][nr] | rad | y | weight [nr][nd] | dvec, xa - (x
+ * + dx) of every trial [nlam][nb] (a full prior precision) | box, lo | hi [nb] (the state is bounded).  lng longs behind
+ * them: the plan's | rowptr [nr + 1] and sptr [ns + 1] of the rays that remain | ov_lng partial counts of the two folds.
+ * ints, among the slab's: the plan's | state | choice [ns] | act | first | len | copy0 | tcopy0 of the rays that remain [nr]
+ * | their srays [nlist] | ov_int flags of the slices [ns] and of the trials [nlam][ns] (JUR_OVERFLOW_ISOLATE). */
+typedef struct { size_t dvec, box, ov_int, ov_lng, dbl, lng, ints; } loop_layout_t;
+
+static loop_layout_t loop_layout(trial_plan_t const *pl, size_t nr, size_t nrd, int full, int isolate) {
+  size_t const RL = (size_t)pl->ntrial, RS = (size_t)pl->nslice, nb = (size_t)pl->nb;
+  loop_layout_t o;
+  o.dvec = full ? RL * nb : 0; o.box = pl->box ? 2 * nb : 0;
+  o.ov_int = isolate ? RS + RL * RS : 0; o.ov_lng = isolate ? 2 * (size_t)JUR_OVERFLOW_PARTS : 0;
+  o.dbl = 2 * RL * RS + RS + 2 * nb + 7 * nr + 3 * nrd + o.dvec + o.box;
+  o.lng = pl->nlong + (nr + 1) + (RS + 1) + o.ov_lng;
+  o.ints = pl->nint + 2 * RS + 5 * nr + (size_t)pl->nlist + o.ov_int;
+  return o;
+}
+
+/* once slices have ended: the views of both kinds of pass read the rays that cq has gathered, rpc | sptrc | sraysc their
+ * rowptr and lists */
+static void scene_views_gathered(jur_scene_compact_t const *cq, long const *rpc, long const *sptrc, int const *sraysc, trial_dev_t *td,
+                                 jur_scene_pass_t *a, jur_scene_normal_t *nq, scene_fov_t *fv) {
+  jur_scene_trial_pass_t *const ps = &td->ps;
+  a->nr = ps->nr = fv->k.nr = cq->n;
+  a->rowptr = rpc;
+  a->first = ps->first = cq->first_c; a->len = ps->len = cq->len_c; a->copy0 = cq->copy0_c; ps->tcopy0 = cq->tcopy0_c;
+  a->in_geom = ps->in_geom = fv->k.time = cq->geom_c; fv->k.vpz = cq->geom_c + 4 * cq->n;
+  a->in_rad = ps->in_rad = cq->rad_c;
+  nq->sptr = ps->sptr = sptrc; nq->srays = ps->srays = sraysc;
+  nq->y = ps->y = cq->y_c; nq->weight = ps->weight = cq->weight_c;
+  fv->live = cq->live_c;
+}
+
+/* jur_retrieve_scene_host behind the opening: the iterations, each the passes of a Jacobian or reuse iteration, the solve
+ * for every damping, the trial pass on the steps where they lie and the policy; then the forward model on the retrieved
+ * atmosphere, *ret_atm (malloc'ed), whose results a->out_* name.  The views st, a, nq, gq and fv come as the opening has
+ * filled them for all rays of the call; d_base: the base rows.  ntiles == 0: no state elements, nothing to retrieve.
+ * scan_time: the time stamps of the rays.  The slab's parts are the caller's: Wrc (all-zero rowptr | koff | gptr of the held blocks, hkoff the host's; with
+ * kernel_recomp > 1), Wsv (solve_layout), Wrt and Irt (loop_layout), Wfov (a field of view: the mask of the rays that
+ * remain | the convolved radiances of the last forward model); hy: the balance's segments of the ray slices | the raised
+ * copies | the trial copies.  pass: the three cuts (Jacobian | trial | forward-only passes, nr + 1 longs each) as first
+ * made, cut anew here within cap and nmax once slices have ended. */
+static int retrieve_loop(jur_model_t *m, hipStream_t s, char const *who, atm_t const *atm, long nr, double const *scan_time,
+                         scene_retrieve_t const *rt, scene_open_t const *op, trial_plan_t const *pl, long ntiles, long na, long cap,
+                         long nmax, long *pass, long npass, long ntpass, long nfpass, jur_scene_stack_t *st, jur_scene_pass_t *a,
+                         jur_scene_normal_t *nq, jur_scene_grad_t const *gq, scene_fov_t *fv, double *d_base, long *Wrc, long *hkoff,
+                         jur_hyseg_t const hy[3], double const *d_R, double *Wsv, double *Wrt, int *Irt, double *Wfov, atm_t **ret_atm) {
+  jur_retrieve_in_t const *const rin = rt->in;
+  jur_retrieve_out_t const *const ro = rt->out;
+  int const looping = ntiles > 0, np0 = atm->np, nd = a->nd, fov = m->fov_n > 0, hyd = m->scene_hydz >= 0;
+  int const ov = m->scene_overflow == JUR_OVERFLOW_ISOLATE, ovl = ov && looping;   /* untraceable rays fail their trial or their slice, not the call */
+  int const every = looping ? m->kernel_recomp : 1;
+  long const nslice = op->nslice, nb = pl->nb, *const rp = op->rp;
+  int const *const sid = op->sid;
+  size_t const NR = (size_t)nr, nrd = NR * (size_t)nd, RL = (size_t)rin->nlam, RS = (size_t)nslice, nacc = (size_t)na + (size_t)nb + 2 * RS;
+  double const *const d_geom = a->in_geom, *const d_inrad = a->in_rad;   /* (of all rays: the views move on to the rays that remain) */
+  double *const d_k = a->k;
+  long const ngroups = every > 1 ? hkoff[NR + RS] : 0;   /* (hkoff: koff [nr] | gptr [ns + 1]) */
+  long *const tpass = pass + NR + 1, *const fpass = tpass + NR + 1, *const d_zrp = Wrc, *const d_koff = Wrc + NR + 1;
+  int rc = JUR_OK; hipError_t e = hipSuccess;
+  /* host arrays of the loop.  rd: lamt | pred | tcost | tprior | Jt [nlam][ns] each, cost | prior | J [ns] each; ri: status
+   * [nlam][ns], best | accept | choice [ns] each; hov: what comes home of the overflow flags per iteration, state [ns] |
+   * trial flags [nlam][ns], hovp the folds' partial counts; hjac: the states at the last Jacobian iteration */
+  double *rd = (double *)calloc(5 * RL * RS + 3 * RS + 1, sizeof(double)), *htimec = NULL;
+  int *ri = (int *)calloc(RL * RS + 4 * RS + 1, sizeof(int)), *hact = NULL, *hov = NULL, *hjac = NULL;
+  long *hcomp = NULL, *hovp = NULL; atm_t *ret = NULL;
+  if (!rd || !ri) { rc = JUR_ENOMEM; goto done; }
+  double *const lamt = rd, *const htcost = rd + 2 * RL * RS, *const htprior = rd + 3 * RL * RS, *const Jt = rd + 4 * RL * RS,
+         *const hcost = rd + 5 * RL * RS, *const hprior0 = hcost + RS, *const J = hprior0 + RS;
+  int *const hstatus = ri, *const best = ri + RL * RS, *const accept = best + RS, *const choice = accept + RS;
+  /* the dampings, predictions and statuses of an iteration as solve_enqueue takes them: the prior pair is on the device */
+  jur_solve_in_t const sin = {.nlam = rin->nlam, .mode = rin->mode, .lam = lamt, .prior_ivar = rin->prior_ivar, .prior_dx = rin->prior_xa};
+  jur_solve_out_t const sout = {.pred = rd + RL * RS, .status = hstatus};
+
+  /* the loop's part of the slab, the solver's part where the loop reads it */
+  loop_layout_t const ll = loop_layout(pl, NR, nrd, d_R != NULL, ov);
+  solve_layout_t const svl = solve_layout((size_t)na, (size_t)nb, RS, RL, rin->prior_ivar != NULL, d_R != NULL);
+  double *const d_tcost = Wrt, *const d_tprior = d_tcost + RL * RS, *const d_prior0 = d_tprior + RL * RS, *const d_xout = d_prior0 + RS,
+         *const d_xa = d_xout + nb, *const d_geomc = d_xa + nb, *const d_radc = d_geomc + 7 * NR, *const d_yc = d_radc + nrd,
+         *const d_wc = d_yc + nrd, *const d_dvec = d_wc + nrd, *const d_bd = d_dvec + ll.dvec;
+  long *const Lr = (long *)(Wrt + ll.dbl), *const d_rpc = Lr + pl->nlong, *const d_sptrc = d_rpc + NR + 1, *const d_ovp = d_sptrc + RS + 1;
+  int *const Ir = Irt, *const d_state = Ir + pl->nint, *const d_choice = d_state + RS, *const d_act = d_choice + RS,
+      *const d_firstc = d_act + NR, *const d_lenc = d_firstc + NR, *const d_copy0c = d_lenc + NR, *const d_tcopy0c = d_copy0c + NR,
+      *const d_sraysc = d_tcopy0c + NR, *const d_oflag = d_sraysc + pl->nlist, *const d_otflag = d_oflag + RS;
+  double *const d_livec = Wfov, *const d_frad = Wfov + nrd;
+  double *const sv_dx = Wsv + svl.dx, *const sv_r = Wsv + svl.r, *const sv_d = Wsv + svl.d;
+  long const novj = jur_scene_overflow_parts((long)RS), novt = jur_scene_overflow_parts((long)(RL * RS));
+  size_t const npr = (looping && rin->prior_ivar) ? (size_t)nb : 0;
+  trial_dev_t td;
+  scene_ovflags_t ovj;
+  jur_scene_compact_t cq;                         /* the gather: from the arrays of all rays into the loop's */
+  memset(&td, 0, sizeof td); memset(&ovj, 0, sizeof ovj); memset(&cq, 0, sizeof cq);
+  long *hrpc = NULL, *hsptrc = NULL, *hnlive = NULL;
+  long const *rp_cur = rp, *d_rp_cur = a->rowptr;   /* rowptr of the rays of a Jacobian pass: of all rays, or of those that remain */
+  long nr_cur = nr, nactive_built = (pl->nlist == nr) ? nslice : -1;   /* (rays without state elements are in no pass of the loop) */
+  double fac_max = 0;
+  if (!looping) {                                 /* no state elements: nothing to retrieve */
+    for (int it = 0; ro->h_work && it < rin->max_iter; it++) ro->h_work[2 * it] = ro->h_work[2 * it + 1] = 0;
+  } else {
+    hcomp = (long *)malloc(sizeof(long) * ((NR + 1) + (RS + 1) + RS));
+    hact = (int *)malloc(sizeof(int) * (2 * NR + (size_t)pl->nlist + 1));
+    if (every > 1) hjac = (int *)malloc(sizeof(int) * (RS + 1));
+    if (!hcomp || !hact || (every > 1 && !hjac)) { rc = JUR_ENOMEM; goto done; }
+    hrpc = hcomp; hsptrc = hrpc + NR + 1; hnlive = hsptrc + RS + 1;
+    e = hipMemcpyAsync(Lr, pl->longs, sizeof(long) * pl->nlong, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(Ir, pl->ints, sizeof(int) * pl->nint, hipMemcpyHostToDevice, s);
+    if (npr && e == hipSuccess) e = hipMemcpyAsync(sv_r, rin->prior_ivar, sizeof(double) * npr, hipMemcpyHostToDevice, s);
+    if (npr && e == hipSuccess) e = hipMemcpyAsync(d_xa, rin->prior_xa, sizeof(double) * npr, hipMemcpyHostToDevice, s);
+    if (ll.box && e == hipSuccess) e = hipMemcpyAsync(d_bd, pl->box, sizeof(double) * ll.box, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    /* (tq: d^T R d of the loop's states: of the trials, of the state as it stands) */
+    trial_dev_fill(&td, m, pl, np0, st->tmax, st->span, Lr, Ir, d_base, d_geom, d_inrad, a->first, a->len, nq->y, nq->weight, sv_dx,
+                   npr ? sv_r : NULL, npr ? d_xa : NULL, d_tprior, d_tcost, ll.box ? d_bd : NULL, d_R, nq->aptr, d_dvec,
+                   ovl ? d_otflag : NULL, d_ovp + JUR_OVERFLOW_PARTS, d_state, d_choice);
+    cq.nr = nr; cq.nd = nd; cq.act = d_act;
+    cq.geom = d_geom; cq.rad = d_inrad; cq.y = nq->y; cq.weight = nq->weight;
+    cq.first = a->first; cq.len = a->len; cq.copy0 = a->copy0; cq.tcopy0 = td.ps.tcopy0;
+    cq.geom_c = d_geomc; cq.rad_c = d_radc; cq.y_c = d_yc; cq.weight_c = d_wc;
+    cq.first_c = d_firstc; cq.len_c = d_lenc; cq.copy0_c = d_copy0c; cq.tcopy0_c = d_tcopy0c;
+    if (fov) { cq.live = fv->live; cq.live_c = d_livec; }
+    if (ovl) {
+      hov = (int *)malloc(sizeof(int) * (RS + RL * RS));
+      hovp = (long *)malloc(sizeof(long) * 2 * JUR_OVERFLOW_PARTS);
+      if (!hov || !hovp) { rc = JUR_ENOMEM; goto done; }
+      ovj.per = rin->nlam; ovj.tcopy0 = td.ps.tcopy0;
+      ovj.fold.nslice = nslice; ovj.fold.ntrial = 1; ovj.fold.flag = d_oflag; ovj.fold.state = d_state; ovj.fold.part = d_ovp;
+    }
+    for (int l = 0; l < rin->nlam; l++) fac_max = fmax(fac_max, rin->fac[l]);
+    for (long q = 0; q < nslice; q++) { ro->lam[q] = rin->lam0; ro->state[q] = JUR_RET_ACTIVE; ro->iters[q] = 0; ro->cost[q] = ro->prior[q] = 0; ro->nlive[q] = 0; }
+    if (ro->h_cost) {
+      size_t const MI = (size_t)rin->max_iter;
+      for (size_t i = 0; i < MI * RL * RS; i++) { ro->h_lam[i] = ro->h_tcost[i] = ro->h_tprior[i] = NAN; ro->h_status[i] = -1; }
+      for (size_t i = 0; i < MI * RS; i++) ro->h_best[i] = ro->h_accept[i] = -1;
+      for (size_t i = 0; i < 2 * MI; i++) ro->h_work[i] = 0;
+    }
+  }
+  for (int it = 0; looping && it < rin->max_iter; it++) {
+    /* the rays of the slices that are still active, in arrays of their own once a slice has ended */
+    long nactive = 0;
+    for (long q = 0; q < nslice; q++) nactive += ro->state[q] == JUR_RET_ACTIVE;
+    if (nactive == 0) break;
+    int const reuse = every > 1 && it % every != 0;   /* a reuse iteration */
+    int regathered = 0;                             /* the rays were gathered anew in this iteration */
+    if (nactive != nactive_built) {
+      int *const act = hact, *const pos = hact + NR, *const sraysc = pos + NR;
+      long const n = jur_scene_gather_active(nr, nslice, rp, sid, ro->state, pl->sptr, pl->srays, act, pos, hrpc, hsptrc, sraysc);
+      long const nl = hsptrc[nslice];
+      nr_cur = n; rp_cur = hrpc; nactive_built = nactive;
+      if (fov) {                                    /* (whole scans have left: the scans that remain are the call's) */
+        if (!htimec && !(htimec = (double *)malloc(sizeof(double) * NR))) { rc = JUR_ENOMEM; goto done; }
+        for (long i = 0; i < n; i++) htimec[i] = scan_time[act[i]];
+      }
+      npass = jur_scene_passes(nr_cur, rp_cur, cap, fov ? htimec : NULL, pass, NULL, NULL);   /* (within nmax, kmax: jur_scene_pass_reserve) */
+      ntpass = jur_trial_passes(nr_cur, rin->nlam, cap, fov ? htimec : NULL, tpass, NULL);
+      if (every > 1) {
+        long fmax = 0;
+        nfpass = jur_trial_passes(nr_cur, 1, cap, fov ? htimec : NULL, fpass, &fmax);
+        if (nfpass < 0 || fmax > nmax) { jur_set_error("%s: a forward-only pass of %ld slots, %ld reserved", who, fmax, nmax); rc = JUR_EINVAL; goto done; }
+      }
+      regathered = 1;
+      e = hipMemcpyAsync(d_act, act, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_sraysc, sraysc, sizeof(int) * (size_t)(nl ? nl : 1), hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_rpc, hrpc, sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_sptrc, hsptrc, sizeof(long) * (RS + 1), hipMemcpyHostToDevice, s);
+      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+      cq.n = n;
+      if (SCENE_TIMED(m, s, jurk_scene_compact(&cq, s))) { rc = launch_failed("%s: gathering kernel launch failed", who); goto done; }
+      scene_views_gathered(&cq, d_rpc, d_sptrc, d_sraysc, &td, a, nq, fv);
+      d_rp_cur = d_rpc; ovj.tcopy0 = td.ps.tcopy0;
+    }
+    /* the dampings of this iteration (the product is rounded first), the states, fresh accumulators, the prior */
+    for (int l = 0; l < rin->nlam; l++)
+      for (long q = 0; q < nslice; q++) {
+        double const v = ro->lam[q] * rin->fac[l];
+        lamt[(size_t)l * RS + (size_t)q] = fmin(fmax(v, rin->lam_min), rin->lam_max);
+      }
+    e = hipMemcpyAsync(d_state, ro->state, sizeof(int) * RS, hipMemcpyHostToDevice, s);
+    if (ovl && e == hipSuccess) e = hipMemsetAsync(d_oflag, 0, sizeof(int) * ll.ov_int, s);
+    /* (a reuse iteration keeps A of the last Jacobian iteration: b, cost and nlive alone start again) */
+    if (it > 0 && e == hipSuccess) e = reuse ? hipMemsetAsync(nq->b, 0, sizeof(double) * (nacc - (size_t)na), s)
+                                             : hipMemsetAsync(nq->A, 0, sizeof(double) * nacc, s);
+    if (every > 1 && (!reuse || regathered)) {
+      /* where the blocks of the rays that remain lie: a Jacobian iteration writes those of its rays back to back */
+      if (!reuse) memcpy(hjac, ro->state, sizeof(int) * RS);
+      long const nk = jur_scene_recomp_offsets(nr, rp, sid, hjac, ro->state, nd, hkoff);
+      if (nk != nr_cur) { if (nk >= 0) jur_set_error("%s: retained blocks out of step", who); rc = JUR_EINVAL; goto done; }
+      if (e == hipSuccess) e = hipMemcpyAsync(d_koff, hkoff, sizeof(long) * (size_t)nk, hipMemcpyHostToDevice, s);
+    }
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    int ek = 0;
+    if (npr) {
+      jur_scene_trial_t pq = td.st;
+      pq.out = sv_d; pq.dx = NULL; pq.prior = d_prior0;
+      int const ti = scene_timed_begin(m, s);
+      ek = jurk_scene_elements(&pq, JUR_ELEM_PRIOR_DX, nb, s);
+      if (!ek) ek = jurk_scene_prior(&pq, s);
+      if (!ek && d_R) {                             /* (sv_d holds xa - x) */
+        jur_scene_pquad_t bq = td.tq;
+        bq.nvec = 1; bq.v = sv_d; bq.out = d_prior0;
+        ek = jurk_scene_prior_quad(&bq, s);
+      }
+      scene_timed_end(m, ti, s);
+    } else if (hipMemsetAsync(d_prior0, 0, sizeof(double) * RS, s) != hipSuccess) ek = 1;
+    if (ek) { (void)hipGetLastError(); jur_set_error("%s: prior kernel launch failed", who); rc = JUR_EHIP; goto done; }
+
+    /* the passes: a reuse iteration's are forward-only, one slot per ray, which the kernels of a pass make of the all-zero
+     * rowptr; the blocks of a Jacobian iteration stay for them */
+    scene_cut_t const cut = {reuse ? fpass : pass, reuse ? nfpass : npass, rp_cur, reuse, every > 1, d_k, NULL};
+    a->rowptr = reuse ? d_zrp : d_rp_cur;
+    if ((rc = scene_passes_run(m, s, who, atm, st, a, nq, ntiles, gq, ngroups, fov ? fv : NULL, hy[1], &cut,
+                               ovl ? &ovj : NULL, NULL, nmax))) goto done;
+    if ((rc = solve_enqueue(m, s, who, nslice, na, nb, nq->wptr, nq->aptr, nq->A, nq->b, Wsv, &sin, &sout, d_state, d_R))) goto done;
+
+    /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
+    if ((rc = trial_run(m, s, who, atm, &td, nb, ntpass, tpass, nmax, fov ? fv : NULL, hy[2]))) goto done;
+    e = hipMemcpyAsync(hcost, nq->cost, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
+    if (ovl) {                                     /* the states and the trial flags come home with the scalars */
+      if (e == hipSuccess) e = hipMemcpyAsync(hov, d_state, sizeof(int) * RS, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(hov + RS, d_otflag, sizeof(int) * RL * RS, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(hovp, d_ovp, sizeof(long) * (size_t)novj, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(hovp + JUR_OVERFLOW_PARTS, d_ovp + JUR_OVERFLOW_PARTS, sizeof(long) * (size_t)novt, hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(hnlive, nq->nlive, sizeof(long) * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hprior0, d_prior0, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(htcost, d_tcost, sizeof(double) * RL * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(htprior, d_tprior, sizeof(double) * RL * RS, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    if ((rc = scene_status_rc(m, who, ov))) goto done;
+    if (ovl) {
+      /* a slice that failed in this iteration took no part in it: what it holds is of its last completed iteration */
+      for (long q = 0; q < nslice; q++)
+        if (ro->state[q] == JUR_RET_ACTIVE && hov[q] == JUR_RET_FAILED) {
+          ro->state[q] = JUR_RET_FAILED;
+          if (ro->iters[q] == 0) { ro->cost[q] = ro->prior[q] = NAN; ro->nlive[q] = 0; }
+        }
+      for (long g = 0; g < novj; g++) m->ov_failed += hovp[g];
+      for (long g = 0; g < novt; g++) m->ov_cells += hovp[JUR_OVERFLOW_PARTS + g];
+    }
+    long work = 0;
+    for (long r = 0; r < nr_cur; r++) work += reuse ? 1 : rp_cur[r + 1] - rp_cur[r] + 1;
+    for (long q = 0; q < nslice; q++) {
+      if (ro->state[q] != JUR_RET_ACTIVE) continue;
+      ro->cost[q] = hcost[q]; ro->prior[q] = hprior0[q]; ro->nlive[q] = hnlive[q]; ro->iters[q]++;
+      J[q] = hcost[q] + hprior0[q];
+      for (size_t l = 0; l < RL; l++) Jt[l * RS + (size_t)q] = htcost[l * RS + (size_t)q] + htprior[l * RS + (size_t)q];
+    }
+    if (ro->h_cost) {
+      size_t const at1 = (size_t)it * RS, at2 = (size_t)it * RL * RS;
+      for (long q = 0; q < nslice; q++) {
+        ro->h_cost[at1 + (size_t)q] = ro->cost[q]; ro->h_prior[at1 + (size_t)q] = ro->prior[q];
+        if (ro->state[q] != JUR_RET_ACTIVE) continue;
+        for (size_t l = 0; l < RL; l++) {
+          size_t const i = l * RS + (size_t)q;
+          ro->h_lam[at2 + i] = lamt[i]; ro->h_tcost[at2 + i] = htcost[i]; ro->h_tprior[at2 + i] = htprior[i];
+          ro->h_status[at2 + i] = (ovl && hov[RS + i]) ? JUR_TRIAL_OVERFLOW : hstatus[i];
+        }
+      }
+      ro->h_work[2 * it] = work; ro->h_work[2 * it + 1] = nr_cur * rin->nlam;
+    }
+    if ((rc = jur_retrieve_decide(rin->nlam, nslice, rin->tol, rin->lam_max, fac_max, J, Jt, lamt, hstatus, ro->lam, ro->state, best, accept))) goto done;
+    for (long q = 0; q < nslice; q++) {
+      choice[q] = accept[q] == 1 ? best[q] : -1;
+      if (accept[q] == 1) { ro->cost[q] = htcost[(size_t)best[q] * RS + (size_t)q]; ro->prior[q] = htprior[(size_t)best[q] * RS + (size_t)q]; }
+      if (ro->h_best) { ro->h_best[(size_t)it * RS + (size_t)q] = best[q]; ro->h_accept[(size_t)it * RS + (size_t)q] = accept[q]; }
+    }
+    e = hipMemcpyAsync(d_choice, choice, sizeof(int) * RS, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+    jur_scene_trial_t aq = td.st;
+    aq.state = NULL;                                /* (the choice alone says who moves: a slice may just have converged) */
+    ek = SCENE_TIMED(m, s, jurk_scene_elements(&aq, JUR_ELEM_ACCEPT, nb, s));
+    /* the base segments of the accepted slices are balanced; the others come back with the bits they have */
+    if (!ek) ek = scene_hydro_launch(m, s, hy[0], d_base, (size_t)np0);
+    if (ek || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); jur_set_error("%s: accepting the steps failed", who); rc = JUR_EHIP; goto done; }
+  }
+
+  /* what is still active has run out of iterations; the state comes home; the forward model on the retrieved atmosphere,
+   * for all rays, from the geometry and the mask that went up at the start */
+  if (!(ret = (atm_t *)malloc(sizeof(atm_t)))) { rc = JUR_ENOMEM; goto done; }
+  memcpy(ret, atm, sizeof(atm_t));
+  if (hyd) {                                      /* the balanced pressures of the base rows; outside the ray slices the caller's */
+    e = hipMemcpyAsync(ret->p, d_base + 4 * (size_t)np0, sizeof(double) * (size_t)np0, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipGetLastError(); jur_set_error("%s: bringing the pressures home failed", who); rc = JUR_EHIP; goto done; }
+  }
+  if (looping) {
+    for (long q = 0; q < nslice; q++) if (ro->state[q] == JUR_RET_ACTIVE) ro->state[q] = JUR_RET_MAXITER;
+    if (ro->h_cost)
+      for (int it = 0; it < rin->max_iter; it++)
+        if (ro->h_work[2 * it] == 0)                /* (an iteration that no slice reached) */
+          for (long q = 0; q < nslice; q++) { ro->h_cost[(size_t)it * RS + (size_t)q] = ro->cost[q]; ro->h_prior[(size_t)it * RS + (size_t)q] = ro->prior[q]; }
+    jur_scene_trial_t xq = td.st;
+    xq.out = d_xout;
+    int const ek = SCENE_TIMED(m, s, jurk_scene_elements(&xq, JUR_ELEM_STATE, nb, s));
+    e = ek ? hipErrorUnknown : hipMemcpyAsync(ro->x, d_xout, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipGetLastError(); jur_set_error("%s: bringing the state home failed", who); rc = JUR_EHIP; goto done; }
+    for (long i = 0; i < nb; i++) scene_row_array(ret, m->view.ng, pl->erow[i])[pl->eip[i]] = ro->x[i];
+  }
+  if ((rc = jur_model_set_atm(m, ret))) goto done;
+  e = hipMemcpyAsync(a->out_rad, d_inrad, sizeof(double) * nrd, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
+  if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
+  if ((rc = jur_formod_device(m, nr, d_geom, a->out_rad, a->out_tau, a->out_tp, a->out_np, m->d_status, s))) goto done;
+  if (fov) {                                      /* all rays of the call, one slot each */
+    fv->k.nr = nr; fv->k.time = d_geom; fv->k.vpz = d_geom + 4 * NR;
+    fv->k.r0 = 0; fv->k.r1 = nr; fv->k.ntrial = 1; fv->k.rowptr = NULL;
+    fv->k.rad = a->out_rad; fv->k.tau = a->out_tau; fv->k.rad_f = d_frad; fv->k.tau_f = fv->tau;
+    if (SCENE_TIMED(m, s, jurk_scene_fov(&fv->k, s))) { rc = launch_failed("%s: field-of-view kernel launch failed", who); goto done; }
+    a->out_rad = d_frad; a->out_tau = fv->tau;
+  }
+  *ret_atm = ret;
+  ret = NULL;
+done:
+  if (rc) (void)hipStreamSynchronize(s);          /* copies out of the arrays freed here may still be under way */
+  free(rd); free(ri); free(hact); free(hcomp); free(htimec); free(hjac); free(hov); free(hovp); free(ret);
+  return rc;
+}
+
 /* nm == NULL: jur_kernel_scene_host.  Otherwise the normal equations of the slices are accumulated on the device after
  * the quotients of every pass, and the blocks go home only where k is given.  With sv (jur_step_scene_host; nm is given
  * then) the systems are solved where they lie after the last pass, and A and b go home only where they are given.  With
  * gd (jur_gradient_scene_host; nm is given then, without A) the passes are forward-only and b, cost and nlive are summed
  * from the caller's blocks.  With pm (jur_param_scene_host) the call is that entry's phase 1 (dg with the gain is given
- * then) or phase 2 (nothing else is given; k may be NULL).  What the call opens with is scene_open's; of the device slab (scene_slab_reserve) the
- * solver's part is laid out by solve_layout and the diagnostics' by diag_layout, which the loop reads too. */
+ * then) or phase 2 (nothing else is given; k may be NULL).  With rt (jur_retrieve_scene_host; nm brings y and weight) the
+ * views made here go to retrieve_loop; every other entry has one cut of passes, scene_passes_run's.  who: the entry the
+ * messages name.  What the call opens with is scene_open's; of the device slab (scene_slab_reserve) the solver's part is
+ * laid out by solve_layout, the diagnostics' by diag_layout and the loop's by loop_layout. */
 static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                              double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass,
                              scene_normal_t const *nm, scene_solve_t const *sv, scene_retrieve_t const *rt, scene_diag_t const *dg,
-                             scene_grad_t const *gd, scene_param_t *pm) {
-  char const *const who = pm ? "jur_param_scene_host" : gd ? "jur_gradient_scene_host" : rt ? "jur_retrieve_scene_host" : sv ? "jur_step_scene_host" : (dg && dg->gin) ? "jur_gain_scene_host" : dg ? "jur_diagnose_scene_host" : nm ? "jur_normal_scene_host" : "jur_kernel_scene_host";   /* the entry the messages name */
+                             scene_grad_t const *gd, scene_param_t *pm, char const *who) {
   { int const ri = scene_ip_check(m, who); if (ri) return ri; }
   if (nr < 0 || max_rays_per_pass < 0) { jur_set_error("%s: bad arguments", who); return JUR_EINVAL; }
   if (sv) { int const rs = solve_check_args(who, sv->in, sv->out); if (rs) return rs; }
@@ -2843,19 +3274,15 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   scene_open_t op;
   long *off = NULL, *pass = NULL, *scopy = NULL, *nptr = NULL;
   int *cdesc = NULL, *iqa = NULL, *ipa = NULL, *srays = NULL;
-  double *rd = NULL, *htimec = NULL, *hbd = NULL;   /* (hbd: the box on the state per element, lo | hi) */
-  int *ri = NULL, *hact = NULL, *dmap = NULL, *gmap = NULL;
-  long *hcomp = NULL, ninv = 0, ndtile = 0, ngtile = 0;
+  int *dmap = NULL, *gmap = NULL;
+  long ninv = 0, ndtile = 0, ngtile = 0;
   long *hkoff = NULL;                               /* held blocks: the first double of every ray's | the gradient's workgroups by slice */
-  int *hjac = NULL;                                 /* ... and the states of the slices at the last Jacobian iteration */
   atm_t *ret_atm = NULL;
   int const fov = m->fov_n > 0;                     /* a field of view is set: the radiances of every pass are convolved */
   double const *d_R = NULL;                         /* the model's full prior precision on the device, where one is set */
   int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: every slice is balanced on its own */
   long *hyat = NULL;                                /* the segment lists of the balance on the host: at | len (ints behind) */
   int const ov = rt && m->scene_overflow == JUR_OVERFLOW_ISOLATE;   /* untraceable rays fail their trial or their slice, not the call */
-  int *hov = NULL;                                  /* ... what comes home of that per iteration: state [ns] | trial flags [nlam][ns] */
-  long *hovp = NULL;                                /* ... and the fold's partial counts: failed slices | trial cells */
   trial_plan_t pl;
   memset(&pl, 0, sizeof pl);
   if ((rc = scene_open(&op, m, who, atm, nr, geom, rad, rowptr,
@@ -2867,27 +3294,9 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   double const tmax = op.tmax, span = op.span;
   /* the copies of the slices: slice q is raised element by element by the copies scopy[q] ... */
   long ncopies = 0, nt = np0;
-  /* the retrieval loop is the step entry driven from here: its dampings, costs, predictions and statuses are host
-   * arrays of this call (rd: lamt | pred | tcost | tprior | Jt [nlam][ns] each, cost | prior | J [ns] each; ri: status
-   * [nlam][ns], best | accept | choice | active-before [ns] each) */
-  scene_normal_t nm_rt;
-  scene_solve_t sv_rt;
-  jur_solve_in_t sin_rt;
-  jur_solve_out_t sout_rt;
-  size_t const RL = rt ? (size_t)rt->in->nlam : 0, RS = (size_t)nslice;
-  if (rt) {
-    rd = (double *)calloc(5 * RL * RS + 3 * RS + 1, sizeof(double));
-    ri = (int *)calloc(RL * RS + 4 * RS + 1, sizeof(int));
-    if (!rd || !ri) { rc = JUR_ENOMEM; goto done; }
-    memset(&sin_rt, 0, sizeof sin_rt); memset(&sout_rt, 0, sizeof sout_rt);
-    sin_rt.nlam = rt->in->nlam; sin_rt.mode = rt->in->mode; sin_rt.lam = rd;
-    sin_rt.prior_ivar = rt->in->prior_ivar; sin_rt.prior_dx = rt->in->prior_xa;   /* (prior_dx is formed on the device) */
-    sout_rt.pred = rd + RL * RS; sout_rt.status = ri;
-    nm_rt = *nm;                                    /* (y and weight: the entry passes them this way) */
-    nm_rt.cost = rd + 5 * RL * RS; nm_rt.nlive = rt->out->nlive;
-    sv_rt.in = &sin_rt; sv_rt.out = &sout_rt;
-    nm = &nm_rt; sv = &sv_rt;
-  }
+  /* what is solved for: the dampings and the prior of the step entry, or of the retrieval's iterations */
+  size_t const RS = (size_t)nslice, nlam = sv ? (size_t)sv->in->nlam : rt ? (size_t)rt->in->nlam : 0;
+  int const sv_prior = sv ? sv->in->prior_ivar != NULL : rt ? rt->in->prior_ivar != NULL : 0;
   scopy = (long *)malloc(sizeof(long) * ((size_t)nslice + 1));
   if (!scopy) { rc = JUR_ENOMEM; goto done; }
   for (long q = 0; q < nslice; q++) {
@@ -2902,7 +3311,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   long nlist = 0, ntiles = 0, na = 0, nb = 0;
   long *sptr = NULL, *tptr = NULL, *wptr = NULL, *aptr = NULL;
   if (nm && nslice > 0) {
-    if ((!sv && !dg && ((!gd && !nm->A) || !nm->b)) || (!dg && (!nm->cost || !nm->nlive))) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
+    if (!rt && ((!sv && !dg && ((!gd && !nm->A) || !nm->b)) || (!dg && (!nm->cost || !nm->nlive)))) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
     nptr = (long *)calloc(4 * ((size_t)nslice + 1), sizeof(long));
     srays = (int *)malloc(sizeof(int) * NR);
     if (!nptr || !srays) { rc = JUR_ENOMEM; goto done; }
@@ -2917,7 +3326,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     ntiles = tptr[nslice]; na = aptr[nslice]; nb = wptr[nslice];
     if (gd) na = 0;                                 /* (the gradient has no A: b, cost and nlive alone are accumulated) */
     if (ntiles > 0x7fffffffL) { jur_set_error("%s: 2^31 tiles: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
-    if (sv && !rt && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
+    if (sv && (rc = solve_check_values(who, nslice, wptr, sv->in))) goto done;
     if (dg && (rc = jur_diag_check_prior(who, nslice, wptr, dg->prior_ivar))) goto done;
     if (dg && (rc = diag_maps_make(who, nslice, wptr, &ninv, &ndtile, &dmap))) goto done;
     if (gn) {
@@ -2952,22 +3361,22 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
         }
       free(owner);
       if (rc) goto done;
-      if ((rc = trial_plan_make(&pl, who, ctl, atm, rt->in->nlam, nr, nslice, sl, sid))) goto done;
+      if ((rc = trial_plan_make(&pl, who, m, atm, rt->in->nlam, nr, nslice, sl, sid))) goto done;
     }
   }
-  if ((sv || dg) && m->pp_nslice) {                 /* a full prior precision is set: of this layout, with prior_ivar */
+  if ((sv || rt || dg) && m->pp_nslice) {           /* a full prior precision is set: of this layout, with prior_ivar */
     long const none[1] = {0};
-    if ((rc = prior_precision_for(m, who, nslice, wptr ? wptr : none, sv ? sv->in->prior_ivar != NULL : dg->prior_ivar != NULL, &d_R))) goto done;
+    if ((rc = prior_precision_for(m, who, nslice, wptr ? wptr : none, dg ? dg->prior_ivar != NULL : sv_prior, &d_R))) goto done;
   }
   /* what the sums add to the slab: the accumulators A | b | cost | nlive, y and weight, the four running sums, the ray lists */
   size_t const nacc = (size_t)na + (size_t)nb + 2 * (size_t)(ntiles ? nslice : 0);
   size_t const acc_bytes = ntiles ? sizeof(double) * (nacc + 2 * NR * (size_t)nd + 4 * ((size_t)nslice + 1)) + sizeof(int) * (size_t)nlist : 0;
   /* ... and the solve: one more copy of the matrices, the vectors of one damping, the outputs of all */
-  solve_layout_t const svl = solve_layout((size_t)na, (size_t)nb, (size_t)nslice, sv ? (size_t)sv->in->nlam : 0, sv && sv->in->prior_ivar, d_R != NULL);
-  size_t const nsv = (sv && ntiles) ? svl.end : 0;
+  size_t const nsv = (nlam && ntiles) ? solve_layout((size_t)na, (size_t)nb, RS, nlam, sv_prior, d_R != NULL).end : 0;
   size_t const sv_bytes = sizeof(double) * nsv;
   /* ... or the diagnostics: the factor, S, AVK and the vectors */
-  size_t const ndg = (dg && ntiles) ? diag_layout((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, d_R != NULL, (size_t)ninv, (size_t)ndtile).end : 0;
+  diag_layout_t const dl = diag_layout((size_t)na, (size_t)nb, (size_t)nslice, dg && dg->prior_ivar, d_R != NULL, (size_t)ninv, (size_t)ndtile);
+  size_t const ndg = (dg && ntiles) ? dl.end : 0;
   size_t const dg_bytes = sizeof(double) * ndg;
   /* ... and a field of view: the effective mask and the convolved transmittances by ray; for the loop the mask of the
    * rays that remain and the convolved radiances of its last forward model */
@@ -2977,7 +3386,7 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)nt;
   /* ... and the hydrostatic balance: its segment lists (first point and length each) of the base rows' ray slices, of
    * the copies that raise p, T or H2O (at most all) and, in the loop, of the trial copies */
-  size_t const NH = hyd ? (size_t)nrs + (size_t)ncopies + (rt ? RL * RS : 0) : 0;
+  size_t const NH = hyd ? (size_t)nrs + (size_t)ncopies + (rt ? nlam * RS : 0) : 0;
   size_t const hy_bytes = (sizeof(long) + sizeof(int)) * NH;
   if (nt > 0x7fffffffL || (long)atm_bytes > m->ws_budget / 2) {
     jur_set_error("%s: the stacked atmosphere (%ld points, %zu bytes) exceeds the workspace budget: "
@@ -3021,17 +3430,12 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
 
   /* ... and the retrieval loop: the trial copies (counted beside the stacked rows, whose memory they share in turn), the
    * trial costs and priors, the prior term and the state, the arrays of the rays that remain once slices have ended
-   * (geometry, mask, y, weight; rowptr and sptr of their own), the plan's index arrays */
+   * (geometry, mask, y, weight; rowptr and sptr of their own), the plan's index arrays: loop_layout */
   int const looping = rt && ntiles;
-  size_t const NRD = NR * (size_t)nd;
-  size_t const nbd = (looping && m->sb_nq) ? 2 * (size_t)nb : 0;   /* a box on the state: lo | hi of every element */
-  size_t const rt_dbl = looping ? 2 * RL * RS + RS + 2 * (size_t)nb + 7 * NR + 3 * NRD + (d_R ? RL * (size_t)nb : 0) + nbd : 0;   /* (xa - (x + dx) of every trial; last: the box) */
-  int const ovl = ov && looping;                    /* JUR_OVERFLOW_ISOLATE: the flags of the slices and of the trials, the partial counts of the two folds */
-  size_t const nov_int = ovl ? RS + RL * RS : 0, nov_lng = ovl ? 2 * (size_t)JUR_OVERFLOW_PARTS : 0;
-  size_t const rt_lng = looping ? pl.nlong + (NR + 1) + (RS + 1) + nov_lng : 0;
-  size_t const rt_int = looping ? pl.nint + 2 * RS + 5 * NR + (size_t)nlist + nov_int : 0;
+  size_t const nrd = NR * (size_t)nd;
+  loop_layout_t const ll = looping ? loop_layout(&pl, NR, nrd, d_R != NULL, ov) : (loop_layout_t){0, 0, 0, 0, 0, 0, 0};
   size_t const rt_atm_bytes = looping ? sizeof(double) * (nrow + 1) * (size_t)pl.nt : 0;
-  size_t const rt_bytes = sizeof(double) * (rt_dbl + rt_lng) + sizeof(int) * rt_int;
+  size_t const rt_bytes = sizeof(double) * (ll.dbl + ll.lng) + sizeof(int) * ll.ints;
   used += (double)rt_atm_bytes;
   if (looping && !scene_fits(m, &used, rt_bytes)) {
     jur_set_error("%s: the trial copies (%ld points, %zu bytes) and the loop's arrays (%zu bytes) do not fit beside the solver "
@@ -3049,7 +3453,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   int const retain = gd || every > 1 || held;
   size_t const nkret = retain ? (size_t)rp[nr] * (size_t)nd : 0;
   size_t const nrc = retain ? (NR + 1) + NR + (RS + 1) : 0;
-  size_t const ngn = held ? gain_layout(pm ? 0 : nkret, (size_t)nb, NRD, (size_t)dg->gin->ncomp, (size_t)ngtile).end : 0;
+  gain_layout_t const gl = gain_layout(pm ? 0 : nkret, (size_t)nb, nrd, gn ? (size_t)dg->gin->ncomp : 0, (size_t)ngtile);
+  size_t const ngn = held ? gl.end : 0;
   size_t const kret_bytes = sizeof(double) * (nkret + nrc + ngn);
   if (held && !scene_fits(m, &used, kret_bytes)) {
     jur_set_error("%s: the retained blocks of all rays (%ld columns, %zu bytes), the gain and the budget's arrays (%zu bytes) do not "
@@ -3067,14 +3472,10 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   /* passes: contiguous ranges of rays whose slots (width + 1 each) stay within the cap; one ray beyond it goes alone */
   size_t const slot_bytes = sizeof(double) * (10 + (size_t)(fov ? 4 : 3) * (size_t)nd) + sizeof(int);   /* (with the convolved radiances) */
   long cap = max_rays_per_pass;
-  if (cap == 0) {
-    /* from the budget: a sixteenth of what the stacked atmosphere (at most half of it) leaves, for the arrays of a pass
-     * (the LOS and transmittance workspace of the forward model is sized from the budget by itself); never fewer than
-     * 4096 slots, a few hundred KB, so that a small budget does not end in a pass and a wait per ray */
-    long const avail = (m->ws_budget - (long)atm_bytes - (long)hy_bytes - (long)fov_bytes - (long)acc_bytes - (long)sv_bytes - (long)dg_bytes - (long)kret_bytes - (long)side_bytes) / 16;
-    cap = avail / (long)slot_bytes;
-    if (cap < 4096) cap = 4096;
-  }
+  /* from the budget, less the parts counted above but for the loop's (the forward model sizes its LOS and transmittance
+   * workspace from the budget by itself).  `used` sums byte counts that each fitted into half the budget: exact in double
+   * below 2^53, so equal to a sum in long; a budget beyond that gives a cap that is clamped on the next line either way. */
+  if (cap == 0) cap = jur_scene_default_cap(m->ws_budget, (long)used - (long)rt_atm_bytes - (long)rt_bytes, slot_bytes);
   if (cap > 0x7fffffffL) cap = 0x7fffffffL;
   long npass = 0, nmax = 0, kmax = 0;
   pass = (long *)malloc(sizeof(long) * 3 * (NR + 1));       /* (second part: the trial passes of the retrieval loop, third: its forward-only passes) */
@@ -3125,19 +3526,10 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   /* the balance's segments: the ray slices in the base rows; the copies whose raised row the pressures depend on, in the
    * stacked rows (the others inherit the balanced base: a second balance would return the same bits); every trial copy */
   long nhc = 0, ntc = 0;
-  if (hyd) {
-    if (!(hyat = (long *)malloc((sizeof(long) + sizeof(int)) * (NH ? NH : 1)))) { rc = JUR_ENOMEM; goto done; }
-    int *const hylen = (int *)(hyat + NH);
-    int const row_h2o = m->view.ig_h2o >= 0 ? 6 + m->view.ig_h2o : -1;
-    for (long q = 0; q < nrs; q++) { hyat[q] = op.hyf[q]; hylen[q] = op.hyf[NR + (size_t)q]; }
-    for (long j = 1; j < ncopy; j++)
-      if (prow[j] == 4 || prow[j] == 5 || prow[j] == row_h2o) { hyat[nrs + nhc] = off[j]; hylen[nrs + nhc] = (int)(off[j + 1] - off[j]); nhc++; }
-    if (rt && ntiles)
-      for (long j = 1; j < pl.ncopy; j++) { hyat[nrs + nhc + ntc] = pl.off[j]; hylen[nrs + nhc + ntc] = (int)(pl.off[j + 1] - pl.off[j]); ntc++; }
-  }
+  if (hyd && !(hyat = jur_scene_hydro_segments(NH, nr, nrs, op.hyf, ncopy, off, prow, m->view.ig_h2o >= 0 ? 6 + m->view.ig_h2o : -1,
+                                               looping ? pl.ncopy : 0, pl.off, &nhc, &ntc))) { rc = JUR_ENOMEM; goto done; }
 
   /* the device slab: doubles, then 64-bit integers, then 32-bit ones */
-  size_t const nrd = NR * (size_t)nd;
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_rad = o_inrad + nrd,
                o_tau = o_rad + nrd, o_tp = o_tau + nrd, o_h = o_tp + 3 * NR, o_k = o_h + (size_t)ncopy,
                o_rowptr = o_k + (retain ? nkret : (size_t)kmax), o_off = o_rowptr + NR + 1, o_y = o_off + (size_t)ncopy + 1;
@@ -3145,8 +3537,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
    * then sptr | tptr | wptr | aptr, then what the solve needs) */
   size_t const o_w = o_y + (ntiles ? nrd : 0), o_acc = o_w + (ntiles ? nrd : 0), o_nptr = o_acc + nacc,
                o_sv = o_nptr + (ntiles ? 4 * ((size_t)nslice + 1) : 0), o_dg = o_sv + nsv, o_fov = o_dg + ndg, o_rt = o_fov + nfov,
-               o_hy = o_rt + rt_dbl + rt_lng, o_rc = o_hy + NH, o_gn = o_rc + nrc, o_int = o_gn + ngn;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad; o_hy: the balance's first points) */
-  size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + rt_int + NH;   /* (the loop's ints follow the others, the balance's lengths those) */
+               o_hy = o_rt + ll.dbl + ll.lng, o_rc = o_hy + NH, o_gn = o_rc + nrc, o_int = o_gn + ngn;   /* (o_fov: live | tau by ray, and for the loop live of the remaining rays | rad; o_hy: the balance's first points) */
+  size_t const nint0 = 4 * NR + 3 * (size_t)ncopy + (size_t)nlist, nint = nint0 + ll.ints + NH;   /* (the loop's ints follow the others, the balance's lengths those) */
   hipStream_t s;
   if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * nint, &s))) goto done;
   if ((rc = ensure_io(m, nmax, 0))) goto done;
@@ -3157,14 +3549,13 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     int *const I = (int *)(D + o_int);
     int *const d_first = I, *const d_len = I + NR, *const d_copy0 = I + 2 * NR, *const d_np = I + 3 * NR, *const d_cdesc = I + 4 * NR;
     enqueued = 1;
-    hipError_t e = hipMemcpyAsync(D + o_base, op.hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
-    for (int q = 0; q < 7 && e == hipSuccess; q++) e = hipMemcpyAsync(D + o_geom + (size_t)q * NR, geom[q], sizeof(double) * NR, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(D + o_inrad, rad, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    double *const d_live = D + o_fov;             /* (the effective mask | the convolved transmittances by ray | the loop's) */
+    scene_fov_t fv;
+    hipError_t e = scene_open_upload(m, s, &op, np0, nr, geom, rad, D + o_base, D + o_geom, D + o_inrad, d_first, 3, d_live, &fv);
+    fv.tau = d_live + nrd;
     if (e == hipSuccess) e = hipMemcpyAsync(L + o_rowptr, rp, sizeof(long) * (NR + 1), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(L + o_off, off, sizeof(long) * ((size_t)ncopy + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_first, op.first, sizeof(int) * 3 * NR, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_cdesc, cdesc, sizeof(int) * 3 * (size_t)ncopy, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
     if (ntiles) {                                 /* the accumulators are zeroed here, once */
       if (e == hipSuccess) e = hipMemcpyAsync(D + o_y, nm->y, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
       if (e == hipSuccess) e = hipMemcpyAsync(D + o_w, nm->weight, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
@@ -3172,18 +3563,15 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
       if (e == hipSuccess) e = hipMemcpyAsync(d_cdesc + 3 * ncopy, srays, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, s);
       if (e == hipSuccess) e = hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
     }
-    if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_fov, op.hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
-    long const *const d_hyat = L + o_hy;
-    int const *const d_hylen = I + nint0 + rt_int;
+    jur_hyseg_t const hy_all = {(long)NH, L + o_hy, I + nint0 + ll.ints};   /* the ray slices | the raised copies | the trial copies */
+    jur_hyseg_t const hy[3] = {jur_hyseg_sub(hy_all, 0, nrs), jur_hyseg_sub(hy_all, nrs, nhc), jur_hyseg_sub(hy_all, nrs + nhc, ntc)};
     if (NH && e == hipSuccess) e = hipMemcpyAsync(L + o_hy, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
-    if (NH && e == hipSuccess) e = hipMemcpyAsync(I + nint0 + rt_int, hyat + NH, sizeof(int) * NH, hipMemcpyHostToDevice, s);
+    if (NH && e == hipSuccess) e = hipMemcpyAsync(I + nint0 + ll.ints, hyat + NH, sizeof(int) * NH, hipMemcpyHostToDevice, s);
     /* held blocks: the caller's go up as they are laid out, ray r's at rowptr[r] * nd */
     long *const d_zrp = L + o_rc, *const d_koff = d_zrp + NR + 1, *const d_gptr = d_koff + NR;
     long ngroups = 0;
     if (retain) {
-      hkoff = (long *)malloc(sizeof(long) * (NR + RS + 1));
-      hjac = (int *)malloc(sizeof(int) * (RS + 1));
-      if (!hkoff || !hjac) { rc = JUR_ENOMEM; goto done; }
+      if (!(hkoff = (long *)malloc(sizeof(long) * (NR + RS + 1)))) { rc = JUR_ENOMEM; goto done; }
       long *const hgptr = hkoff + NR;
       hgptr[0] = 0;
       for (long q = 0; q < nslice; q++) hgptr[q + 1] = hgptr[q] + (sl[q].nel + 255) / 256;
@@ -3197,16 +3585,10 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     }
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
     /* the base rows are balanced once, over the ray slices, before the first pass: the caller's atm is never written */
-    if (hyd && scene_hydro_launch(m, s, nrs, d_hyat, d_hylen, D + o_base, (size_t)np0)) {
+    if (scene_hydro_launch(m, s, hy[0], D + o_base, (size_t)np0)) {
       jur_set_error("%s: hydrostatic kernel launch failed", who); rc = JUR_EHIP; goto done;
     }
 
-    double *const d_live = D + o_fov, *const d_ftau = d_live + nrd, *const d_livec = d_ftau + nrd, *const d_frad = d_livec + nrd;
-    scene_fov_t fv;
-    memset(&fv, 0, sizeof fv);
-    fv.k.nr = nr; fv.k.nd = nd; fv.k.time = D + o_geom; fv.k.vpz = D + o_geom + 4 * NR;
-    fv.k.n = m->fov_n; fv.k.dz = m->d_fov_shape; fv.k.w = m->d_fov_shape + JUR_NSHAPE; fv.k.status = m->d_status;
-    fv.live = d_live;
     jur_scene_stack_t st;
     memset(&st, 0, sizeof st);
     st.ncopy = (int)ncopy; st.np0 = np0; st.nrow = (int)nrow; st.ng = ng; st.nt = nt;
@@ -3234,398 +3616,36 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
     jur_scene_grad_t gq;
     memset(&gq, 0, sizeof gq);
     gq.k = D + o_k; gq.koff = d_koff; gq.gptr = d_gptr;
-    long const *d_rp_cur = L + o_rowptr;            /* rowptr of the rays of a Jacobian pass: of all rays, or of those that remain */
-
-    /* the retrieval loop: what it adds on the device (uploaded once) and on the host */
-    jur_retrieve_in_t const *const rin = rt ? rt->in : NULL;
-    jur_retrieve_out_t const *const ro = rt ? rt->out : NULL;
-    double *const d_tcost = D + o_rt, *const d_tprior = d_tcost + RL * RS, *const d_prior0 = d_tprior + RL * RS, *const d_xout = d_prior0 + RS,
-           *const d_xa = d_xout + nb, *const d_geomc = d_xa + nb, *const d_radc = d_geomc + 7 * NR, *const d_yc = d_radc + NRD,
-           *const d_wc = d_yc + NRD, *const d_dvec = d_wc + NRD, *const d_bd = d_dvec + (d_R ? RL * (size_t)nb : 0);
-    long *const Lr = (long *)(D + o_rt + rt_dbl), *const d_rpc = Lr + pl.nlong, *const d_sptrc = d_rpc + NR + 1;
-    int *const Ir = I + nint0, *const d_state = Ir + pl.nint, *const d_choice = d_state + RS, *const d_act = d_choice + RS,
-        *const d_firstc = d_act + NR, *const d_lenc = d_firstc + NR, *const d_copy0c = d_lenc + NR, *const d_tcopy0c = d_copy0c + NR,
-        *const d_sraysc = d_tcopy0c + NR;
-    int *const d_oflag = d_sraysc + nlist, *const d_otflag = d_oflag + RS;   /* (JUR_OVERFLOW_ISOLATE: the flags, zeroed every iteration) */
-    long *const d_ovp = d_sptrc + RS + 1;                                    /* (... and the partial counts) */
-    long const novj = jur_scene_overflow_parts((long)RS), novt = jur_scene_overflow_parts((long)(RL * RS));
-    jur_scene_ovfold_t ofj, oft;
-    memset(&ofj, 0, sizeof ofj); memset(&oft, 0, sizeof oft);
-    size_t const npr = (looping && rin->prior_ivar) ? (size_t)nb : 0;
-    double *const sv_dx = D + o_sv + svl.dx, *const sv_r = D + o_sv + svl.r, *const sv_d = D + o_sv + svl.d;   /* (the solver's part of the slab) */
-    double *const lamt = rd, *const htcost = rd ? rd + 2 * RL * RS : NULL, *const htprior = rd ? rd + 3 * RL * RS : NULL,
-           *const Jt = rd ? rd + 4 * RL * RS : NULL, *const hcost = rd ? rd + 5 * RL * RS : NULL, *const hprior0 = hcost ? hcost + RS : NULL,
-           *const J = hprior0 ? hprior0 + RS : NULL;
-    int *const hstatus = ri, *const best = ri ? ri + RL * RS : NULL, *const accept = best ? best + RS : NULL, *const choice = accept ? accept + RS : NULL;
-    jur_scene_stack_t tsk;
-    jur_scene_trial_t tst;
-    jur_scene_trial_pass_t tps;
-    memset(&tsk, 0, sizeof tsk); memset(&tst, 0, sizeof tst); memset(&tps, 0, sizeof tps);
-    jur_scene_pquad_t tqd;                          /* d^T R d of the loop's states: of the trials, of the state as it stands */
-    memset(&tqd, 0, sizeof tqd);
-    long *hrpc = NULL, *hsptrc = NULL, *hnlive = NULL;
-    long const *rp_cur = rp;
-    long nr_cur = nr, nactive_built = (nlist == nr) ? nslice : -1;   /* (rays without state elements are in no pass of the loop) */
-    double fac_max = 0;
-    if (rt && !looping) {                         /* no state elements: nothing to retrieve */
-      for (int it = 0; ro->h_work && it < rin->max_iter; it++) ro->h_work[2 * it] = ro->h_work[2 * it + 1] = 0;
-    }
-    if (looping) {
-      hcomp = (long *)malloc(sizeof(long) * ((NR + 1) + (RS + 1) + RS));
-      hact = (int *)malloc(sizeof(int) * (2 * NR + (size_t)nlist + 1));
-      if (!hcomp || !hact) { rc = JUR_ENOMEM; goto done; }
-      hrpc = hcomp; hsptrc = hrpc + NR + 1; hnlive = hsptrc + RS + 1;
-      e = hipMemcpyAsync(Lr, pl.longs, sizeof(long) * pl.nlong, hipMemcpyHostToDevice, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(Ir, pl.ints, sizeof(int) * pl.nint, hipMemcpyHostToDevice, s);
-      if (npr && e == hipSuccess) e = hipMemcpyAsync(sv_r, rin->prior_ivar, sizeof(double) * npr, hipMemcpyHostToDevice, s);
-      if (npr && e == hipSuccess) e = hipMemcpyAsync(d_xa, rin->prior_xa, sizeof(double) * npr, hipMemcpyHostToDevice, s);
-      if (nbd) {                                    /* (the host array lives to the end of the call) */
-        if (!(hbd = (double *)malloc(sizeof(double) * nbd))) { rc = JUR_ENOMEM; goto done; }
-        jur_state_bounds_expand(m->sb_lo, m->sb_hi, nb, pl.erow, hbd, hbd + nb);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_bd, hbd, sizeof(double) * nbd, hipMemcpyHostToDevice, s);
-      }
-      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-      long const *const t_off = Lr + (pl.off - pl.longs);
-      tsk.ncopy = (int)pl.ncopy; tsk.np0 = np0; tsk.nrow = (int)nrow; tsk.ng = ng; tsk.nt = pl.nt;
-      tsk.off = t_off; tsk.first = Ir; tsk.prow = Ir + pl.ncopy; tsk.pip = Ir + 2 * pl.ncopy;
-      tsk.base = D + o_base; tsk.tmax = tmax; tsk.span = span;
-      tst.nslice = nslice; tst.ntrial = rin->nlam; tst.np0 = np0; tst.nt = pl.nt;
-      tst.wptr = Lr; tst.off = t_off; tst.sfirst = Ir + (pl.sfirst - pl.ints); tst.erow = Ir + (pl.erow - pl.ints);
-      tst.eip = Ir + (pl.eip - pl.ints); tst.state = d_state; tst.choice = d_choice;
-      tst.base = D + o_base; tst.dx = sv_dx; tst.ivar = npr ? sv_r : NULL; tst.xa = npr ? d_xa : NULL; tst.prior = d_tprior;
-      if (nbd) { tst.lo = d_bd; tst.hi = d_bd + nb; }
-      tps.nr = nr; tps.nd = nd; tps.ntrial = rin->nlam; tps.first = d_first; tps.len = d_len; tps.tcopy0 = Ir + (pl.tcopy0 - pl.ints);
-      tps.off = t_off; tps.in_geom = D + o_geom; tps.in_rad = D + o_inrad; tps.nslice = nslice; tps.sptr = Lr + (pl.sptr - pl.longs);
-      tps.srays = Ir + (pl.srays - pl.ints); tps.state = d_state; tps.y = D + o_y; tps.weight = D + o_w; tps.cost = d_tcost;
-      tqd.nslice = nslice; tqd.nvec = rin->nlam; tqd.wptr = Lr; tqd.aptr = nq.aptr; tqd.R = d_R; tqd.v = d_dvec; tqd.out = d_tprior;
-      tqd.state = d_state;
-      if (ovl) {
-        hov = (int *)malloc(sizeof(int) * (RS + RL * RS));
-        hovp = (long *)malloc(sizeof(long) * 2 * JUR_OVERFLOW_PARTS);
-        if (!hov || !hovp) { rc = JUR_ENOMEM; goto done; }
-        ofj.nslice = nslice; ofj.ntrial = 1; ofj.flag = d_oflag; ofj.state = d_state; ofj.part = d_ovp;
-        oft.nslice = nslice; oft.ntrial = rin->nlam; oft.flag = d_otflag; oft.state = d_state; oft.cost = d_tcost;
-        oft.part = d_ovp + JUR_OVERFLOW_PARTS;
-      }
-      for (int l = 0; l < rin->nlam; l++) fac_max = fmax(fac_max, rin->fac[l]);
-      for (long q = 0; q < nslice; q++) { ro->lam[q] = rin->lam0; ro->state[q] = JUR_RET_ACTIVE; ro->iters[q] = 0; ro->cost[q] = ro->prior[q] = 0; ro->nlive[q] = 0; }
-      if (ro->h_cost) {
-        size_t const MI = (size_t)rin->max_iter;
-        for (size_t i = 0; i < MI * RL * RS; i++) { ro->h_lam[i] = ro->h_tcost[i] = ro->h_tprior[i] = NAN; ro->h_status[i] = -1; }
-        for (size_t i = 0; i < MI * RS; i++) ro->h_best[i] = ro->h_accept[i] = -1;
-        for (size_t i = 0; i < 2 * MI; i++) ro->h_work[i] = 0;
-      }
-    }
-    int ti, ek;
-    int reuse = 0, regathered = 0;                  /* a reuse iteration; the rays were gathered anew in this iteration */
-    int const niter = rt ? (looping ? rin->max_iter : 0) : 1;
-    for (int it = 0; it < niter; it++) {
-    if (looping) {
-      /* the rays of the slices that are still active, in arrays of their own once a slice has ended */
-      long nactive = 0;
-      for (long q = 0; q < nslice; q++) nactive += ro->state[q] == JUR_RET_ACTIVE;
-      if (nactive == 0) break;
-      reuse = every > 1 && it % every != 0;
-      regathered = 0;
-      if (nactive != nactive_built) {
-        int *const act = hact, *const pos = hact + NR, *const sraysc = pos + NR;
-        long const n = jur_scene_gather_active(nr, nslice, rp, sid, ro->state, sptr, srays, act, pos, hrpc, hsptrc, sraysc);
-        long const nl = hsptrc[nslice];
-        nr_cur = n; rp_cur = hrpc; nactive_built = nactive;
-        if (fov) {                                  /* (whole scans have left: the scans that remain are the call's) */
-          if (!htimec && !(htimec = (double *)malloc(sizeof(double) * NR))) { rc = JUR_ENOMEM; goto done; }
-          for (long i = 0; i < n; i++) htimec[i] = geom[0][act[i]];
-        }
-        npass = jur_scene_passes(nr_cur, rp_cur, cap, fov ? htimec : NULL, pass, NULL, NULL);   /* (within nmax, kmax: jur_scene_pass_reserve) */
-        ntpass = jur_trial_passes(nr_cur, rin->nlam, cap, fov ? htimec : NULL, tpass, NULL);
-        if (every > 1) {
-          long fmax = 0;
-          nfpass = jur_trial_passes(nr_cur, 1, cap, fov ? htimec : NULL, fpass, &fmax);
-          if (nfpass < 0 || fmax > nmax) { jur_set_error("%s: a forward-only pass of %ld slots, %ld reserved", who, fmax, nmax); rc = JUR_EINVAL; goto done; }
-        }
-        regathered = 1;
-        e = hipMemcpyAsync(d_act, act, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_sraysc, sraysc, sizeof(int) * (size_t)(nl ? nl : 1), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rpc, hrpc, sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_sptrc, hsptrc, sizeof(long) * (RS + 1), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-        jur_scene_compact_t cq;
-        memset(&cq, 0, sizeof cq);
-        cq.nr = nr; cq.n = n; cq.nd = nd; cq.act = d_act;
-        cq.geom = D + o_geom; cq.rad = D + o_inrad; cq.y = D + o_y; cq.weight = D + o_w;
-        cq.first = d_first; cq.len = d_len; cq.copy0 = d_copy0; cq.tcopy0 = Ir + (pl.tcopy0 - pl.ints);
-        cq.geom_c = d_geomc; cq.rad_c = d_radc; cq.y_c = d_yc; cq.weight_c = d_wc;
-        cq.first_c = d_firstc; cq.len_c = d_lenc; cq.copy0_c = d_copy0c; cq.tcopy0_c = d_tcopy0c;
-        if (fov) { cq.live = d_live; cq.live_c = d_livec; }
-        ti = scene_timed_begin(m, s);
-        ek = jurk_scene_compact(&cq, s);
-        scene_timed_end(m, ti, s);
-        if (ek) { jur_set_error("%s: gathering kernel launch failed", who); rc = JUR_EHIP; goto done; }
-        a.nr = n; a.rowptr = d_rp_cur = d_rpc; a.first = d_firstc; a.len = d_lenc; a.copy0 = d_copy0c; a.in_geom = d_geomc; a.in_rad = d_radc;
-        nq.sptr = d_sptrc; nq.srays = d_sraysc; nq.y = d_yc; nq.weight = d_wc;
-        tps.nr = n; tps.first = d_firstc; tps.len = d_lenc; tps.tcopy0 = d_tcopy0c; tps.in_geom = d_geomc; tps.in_rad = d_radc;
-        tps.sptr = d_sptrc; tps.srays = d_sraysc; tps.y = d_yc; tps.weight = d_wc;
-        fv.k.nr = n; fv.k.time = d_geomc; fv.k.vpz = d_geomc + 4 * n; fv.live = d_livec;
-      }
-      /* the dampings of this iteration (the product is rounded first), the states, fresh accumulators, the prior */
-      for (int l = 0; l < rin->nlam; l++)
-        for (long q = 0; q < nslice; q++) {
-          double const v = ro->lam[q] * rin->fac[l];
-          lamt[(size_t)l * RS + (size_t)q] = fmin(fmax(v, rin->lam_min), rin->lam_max);
-        }
-      e = hipMemcpyAsync(d_state, ro->state, sizeof(int) * RS, hipMemcpyHostToDevice, s);
-      if (ovl && e == hipSuccess) e = hipMemsetAsync(d_oflag, 0, sizeof(int) * nov_int, s);
-      /* (a reuse iteration keeps A of the last Jacobian iteration: b, cost and nlive alone start again) */
-      if (it > 0 && e == hipSuccess) e = reuse ? hipMemsetAsync(D + o_acc + na, 0, sizeof(double) * (nacc - (size_t)na), s)
-                                               : hipMemsetAsync(D + o_acc, 0, sizeof(double) * nacc, s);
-      if (every > 1 && (!reuse || regathered)) {
-        /* where the blocks of the rays that remain lie: a Jacobian iteration writes those of its rays back to back */
-        if (!reuse) memcpy(hjac, ro->state, sizeof(int) * RS);
-        long const nk = jur_scene_recomp_offsets(nr, rp, sid, hjac, ro->state, nd, hkoff);
-        if (nk != nr_cur) { if (nk >= 0) jur_set_error("%s: retained blocks out of step", who); rc = JUR_EINVAL; goto done; }
-        if (e == hipSuccess) e = hipMemcpyAsync(d_koff, hkoff, sizeof(long) * (size_t)nk, hipMemcpyHostToDevice, s);
-      }
-      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-      ek = 0;
-      if (npr) {
-        jur_scene_trial_t pq = tst;
-        pq.out = sv_d; pq.dx = NULL; pq.prior = d_prior0;
-        ti = scene_timed_begin(m, s);
-        ek = jurk_scene_elements(&pq, JUR_ELEM_PRIOR_DX, nb, s);
-        if (!ek) ek = jurk_scene_prior(&pq, s);
-        if (!ek && d_R) {                           /* (sv_d holds xa - x) */
-          jur_scene_pquad_t bq = tqd;
-          bq.nvec = 1; bq.v = sv_d; bq.out = d_prior0;
-          ek = jurk_scene_prior_quad(&bq, s);
-        }
-        scene_timed_end(m, ti, s);
-      } else if (hipMemsetAsync(d_prior0, 0, sizeof(double) * RS, s) != hipSuccess) ek = 1;
-      if (ek) { (void)hipGetLastError(); jur_set_error("%s: prior kernel launch failed", who); rc = JUR_EHIP; goto done; }
-    }
-    m->h_atm_n = 0;                              /* the device no longer holds the caller's atmosphere */
-    if ((rc = install_stacked_rows(m, atm, nt, ncopies))) goto done;
-    st.rows = (double *)m->d_atm;
-    a.atm_time = m->view.atm_time;
-    ti = scene_timed_begin(m, s);
-    ek = jurk_scene_stack(&st, s);
-    scene_timed_end(m, ti, s);
-    if (!ek && hyd) ek = scene_hydro_launch(m, s, nhc, d_hyat + nrs, d_hylen + nrs, (double *)m->d_atm, (size_t)nt);
-    if (!ek) ek = jurk_prepare_atm(&m->view, (double *)m->d_atm + nrow * (size_t)nt, s);
-    /* the one wait before the passes: the uploads have left the host arrays, the stacked rows stand */
-    if (ek || hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipGetLastError(); m->view.atm_np = 0; jur_set_error("%s: stacking the atmosphere failed", who); rc = JUR_EHIP; goto done;
-    }
-    if ((rc = jur_model_reserve(m, nmax))) goto done;   /* the forward model's workspace for the largest pass, before the first */
-
-    long const *const rp = rp_cur;               /* (the passes below: of all rays, or of those that remain) */
-    /* forward-only passes (the gradient entry, a reuse iteration): one slot per ray, which the kernels of a pass make of
-     * the all-zero rowptr; copy 0 of every ray as in a Jacobian pass */
-    int const fwd = gd || reuse;
-    long const *const cut = reuse ? fpass : pass;
-    long const ncut = reuse ? nfpass : npass;
-    for (long p = 0; p < ncut; p++) {
-      long const r0 = cut[p], r1 = cut[p + 1], n = fwd ? r1 - r0 : (rp[r1] - rp[r0]) + (r1 - r0), nk = fwd ? 0 : (rp[r1] - rp[r0]) * nd;
-      size_t const N = (size_t)n;
-      a.r0 = r0; a.r1 = r1; a.n = n;
-      a.rowptr = fwd ? d_zrp : d_rp_cur;
-      if ((every > 1 || held) && !fwd) a.k = D + o_k + (size_t)rp[r0] * (size_t)nd;   /* (the blocks stay where the pass leaves them) */
-      a.geom = m->d_io; a.rad = a.geom + 7 * N; a.tau = a.rad + N * nd; a.tp = a.tau + N * nd; a.np = m->d_io_np;
-      ti = scene_timed_begin(m, s);
-      ek = jurk_scene_rays(&a, s);
-      scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("%s: replication kernel launch failed", who); rc = JUR_EHIP; goto done; }
-      if ((rc = jur_formod_device(m, n, a.geom, a.rad, a.tau, a.tp, a.np, m->d_status, s))) goto done;
-      if (ovl) {                                   /* the untraceable slots of the pass, before the next one overwrites the counts */
-        jur_scene_ovf_t oq;
-        memset(&oq, 0, sizeof oq);
-        oq.n = n; oq.r0 = r0; oq.r1 = r1; oq.ntrial = 0; oq.per = rin->nlam; oq.nslice = nslice;
-        oq.rowptr = a.rowptr; oq.tcopy0 = tps.tcopy0; oq.np = a.np; oq.flag = d_oflag;
-        ti = scene_timed_begin(m, s);
-        ek = jurk_scene_overflow(&oq, s);
-        scene_timed_end(m, ti, s);
-        if (ek) { jur_set_error("%s: overflow kernel launch failed", who); rc = JUR_EHIP; goto done; }
-      }
-      jur_scene_pass_t af = a;                     /* what reads the forward model's results ... */
-      if (fov) {                                   /* ... reads them convolved, the sums under the effective mask */
-        fv.k.r0 = r0; fv.k.r1 = r1; fv.k.ntrial = 0; fv.k.rowptr = a.rowptr;
-        fv.k.rad = a.rad; fv.k.tau = a.tau; fv.k.rad_f = m->d_fov; fv.k.tau_f = d_ftau;
-        ti = scene_timed_begin(m, s);
-        ek = jurk_scene_fov(&fv.k, s);
-        scene_timed_end(m, ti, s);
-        if (ek) { jur_set_error("%s: field-of-view kernel launch failed", who); rc = JUR_EHIP; goto done; }
-        af.rad = m->d_fov; af.fov_tau = d_ftau; af.in_rad = fv.live;
-      }
-      ti = scene_timed_begin(m, s);
-      ek = jurk_scene_quot(&af, nk, s);
-      scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("%s: quotient kernel launch failed", who); rc = JUR_EHIP; goto done; }
-      if (ntiles && !fwd) {
-        ti = scene_timed_begin(m, s);
-        ek = jurk_scene_normal(&af, &nq, ntiles, s);
-        scene_timed_end(m, ti, s);
-        if (ek) { jur_set_error("%s: normal-equation kernel launch failed", who); rc = JUR_EHIP; goto done; }
-      }
-      if (ngroups && fwd) {
-        ti = scene_timed_begin(m, s);
-        ek = jurk_scene_gradient(&af, &nq, &gq, ngroups, s);
-        scene_timed_end(m, ti, s);
-        if (ek) { jur_set_error("%s: gradient kernel launch failed", who); rc = JUR_EHIP; goto done; }
-      }
-      if (pm && pm->phase == 2 && (rc = param_pass_extend(m, s, who, pm, r0, r1, a.k, rp[r0] * nd))) goto done;
-      /* the blocks of the pass go home (where asked for); the one wait of the pass */
-      e = (nk > 0 && k) ? hipMemcpyAsync(k + (size_t)rp[r0] * nd, a.k, sizeof(double) * (size_t)nk, hipMemcpyDeviceToHost, s) : hipSuccess;
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    }
-    if (ovl) {                                     /* all passes are done: the flagged slices fail before the solve, on the device */
-      ti = scene_timed_begin(m, s);
-      ek = jurk_scene_overflow_fold(&ofj, s);
-      scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("%s: overflow fold kernel launch failed", who); rc = JUR_EHIP; goto done; }
-    }
-    if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out,
-                                   looping ? d_state : NULL, d_R))) goto done;
-    if (ndg && (rc = diag_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, D + o_dg, dg->prior_ivar, dg->out, ninv, ndtile, dmap, d_R))) goto done;
-    if (held) {
-      /* S and the breakdowns lie where the diagnostics left them, the blocks of all rays where the passes left them; the
-       * effective weights are formed from the results of the passes, under the mask the sums were formed under */
-      diag_layout_t const dl = diag_layout((size_t)na, (size_t)nb, (size_t)nslice, dg->prior_ivar != NULL, d_R != NULL, (size_t)ninv, (size_t)ndtile);
-      gain_layout_t const gl = gain_layout(pm ? 0 : nkret, (size_t)nb, NRD, (size_t)dg->gin->ncomp, (size_t)ngtile);
-      jur_scene_weff_t wq;
-      wq.n = (long)NRD; wq.mask = fov ? d_live : D + o_inrad; wq.f = D + o_rad; wq.y = D + o_y; wq.weight = D + o_w;
-      wq.weff = D + o_gn + gl.weff;
-      ti = scene_timed_begin(m, s);
-      ek = jurk_scene_weff(&wq, s);
-      scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("%s: effective-weight kernel launch failed", who); rc = JUR_EHIP; goto done; }
-      jur_scene_gain_t gq2;
-      memset(&gq2, 0, sizeof gq2);
-      gq2.nslice = nslice; gq2.nd = nd; gq2.wptr = nq.wptr; gq2.aptr = nq.aptr; gq2.sptr = nq.sptr; gq2.srays = nq.srays;
-      gq2.koff = d_koff; gq2.gptr = d_gptr; gq2.status = (int const *)(D + o_dg + dl.stat); gq2.S = D + o_dg + dl.S; gq2.k = D + o_k;
-      gq2.nrd = (long)NRD; gq2.nb = nb;
-      if ((rc = gain_enqueue(m, s, who, &gq2, D + o_gn, nkret, ngtile, ngroups, gmap, dg->gin, dg->gout, pm ? pm->gain : NULL))) goto done;
-      if (pm && NRD && hipMemcpyAsync(pm->weff, wq.weff, sizeof(double) * NRD, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-        (void)hipGetLastError(); jur_set_error("%s: keeping the effective weights failed", who); rc = JUR_EHIP; goto done;
-      }
-    }
-    if (!looping) break;
-
-    /* the trial pass on the steps where they lie; the scalars of the iteration come home; the policy; the choices go up */
-    if ((rc = trial_run(m, s, who, atm, &tsk, &tst, &tps, nb, ntpass, tpass, nmax, fov ? &fv : NULL, d_R ? &tqd : NULL,
-                        ntc, d_hyat + nrs + nhc, d_hylen + nrs + nhc, ovl ? &oft : NULL))) goto done;
-    e = hipMemcpyAsync(hcost, nq.cost, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
-    if (ovl) {                                     /* the states and the trial flags come home with the scalars */
-      if (e == hipSuccess) e = hipMemcpyAsync(hov, d_state, sizeof(int) * RS, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(hov + RS, d_otflag, sizeof(int) * RL * RS, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(hovp, d_ovp, sizeof(long) * (size_t)novj, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(hovp + JUR_OVERFLOW_PARTS, d_ovp + JUR_OVERFLOW_PARTS, sizeof(long) * (size_t)novt, hipMemcpyDeviceToHost, s);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(hnlive, nq.nlive, sizeof(long) * RS, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hprior0, d_prior0, sizeof(double) * RS, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(htcost, d_tcost, sizeof(double) * RL * RS, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(htprior, d_tprior, sizeof(double) * RL * RS, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->h_status, m->d_status, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if ((rc = scene_status_rc(m, who, ov))) goto done;
-    if (ovl) {
-      /* a slice that failed in this iteration took no part in it: what it holds is of its last completed iteration */
-      for (long q = 0; q < nslice; q++)
-        if (ro->state[q] == JUR_RET_ACTIVE && hov[q] == JUR_RET_FAILED) {
-          ro->state[q] = JUR_RET_FAILED;
-          if (ro->iters[q] == 0) { ro->cost[q] = ro->prior[q] = NAN; ro->nlive[q] = 0; }
-        }
-      for (long g = 0; g < novj; g++) m->ov_failed += hovp[g];
-      for (long g = 0; g < novt; g++) m->ov_cells += hovp[JUR_OVERFLOW_PARTS + g];
-    }
-    {
-      long work = 0;
-      for (long r = 0; r < nr_cur; r++) work += reuse ? 1 : rp_cur[r + 1] - rp_cur[r] + 1;
-      for (long q = 0; q < nslice; q++) {
-        if (ro->state[q] != JUR_RET_ACTIVE) continue;
-        ro->cost[q] = hcost[q]; ro->prior[q] = hprior0[q]; ro->nlive[q] = hnlive[q]; ro->iters[q]++;
-        J[q] = hcost[q] + hprior0[q];
-        for (size_t l = 0; l < RL; l++) Jt[l * RS + (size_t)q] = htcost[l * RS + (size_t)q] + htprior[l * RS + (size_t)q];
-      }
-      if (ro->h_cost) {
-        size_t const at1 = (size_t)it * RS, at2 = (size_t)it * RL * RS;
-        for (long q = 0; q < nslice; q++) {
-          ro->h_cost[at1 + (size_t)q] = ro->cost[q]; ro->h_prior[at1 + (size_t)q] = ro->prior[q];
-          if (ro->state[q] != JUR_RET_ACTIVE) continue;
-          for (size_t l = 0; l < RL; l++) {
-            size_t const i = l * RS + (size_t)q;
-            ro->h_lam[at2 + i] = lamt[i]; ro->h_tcost[at2 + i] = htcost[i]; ro->h_tprior[at2 + i] = htprior[i];
-            ro->h_status[at2 + i] = (ovl && hov[RS + i]) ? JUR_TRIAL_OVERFLOW : hstatus[i];
-          }
-        }
-        ro->h_work[2 * it] = work; ro->h_work[2 * it + 1] = nr_cur * rin->nlam;
-      }
-      if ((rc = jur_retrieve_decide(rin->nlam, nslice, rin->tol, rin->lam_max, fac_max, J, Jt, lamt, hstatus, ro->lam, ro->state, best, accept))) goto done;
-      for (long q = 0; q < nslice; q++) {
-        choice[q] = accept[q] == 1 ? best[q] : -1;
-        if (accept[q] == 1) { ro->cost[q] = htcost[(size_t)best[q] * RS + (size_t)q]; ro->prior[q] = htprior[(size_t)best[q] * RS + (size_t)q]; }
-        if (ro->h_best) { ro->h_best[(size_t)it * RS + (size_t)q] = best[q]; ro->h_accept[(size_t)it * RS + (size_t)q] = accept[q]; }
-      }
-      e = hipMemcpyAsync(d_choice, choice, sizeof(int) * RS, hipMemcpyHostToDevice, s);
-      if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-      jur_scene_trial_t aq = tst;
-      aq.state = NULL;                              /* (the choice alone says who moves: a slice may just have converged) */
-      ti = scene_timed_begin(m, s);
-      ek = jurk_scene_elements(&aq, JUR_ELEM_ACCEPT, nb, s);
-      scene_timed_end(m, ti, s);
-      /* the base segments of the accepted slices are balanced; the others come back with the bits they have */
-      if (!ek && hyd) ek = scene_hydro_launch(m, s, nrs, d_hyat, d_hylen, D + o_base, (size_t)np0);
-      if (ek || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); jur_set_error("%s: accepting the steps failed", who); rc = JUR_EHIP; goto done; }
-    }
-    }                                             /* (iterations) */
 
     if (rt) {
-      /* what is still active has run out of iterations; the state comes home; the forward model on the retrieved
-       * atmosphere, for all rays, from the geometry and the mask that went up at the start */
-      atm_t *ret = (atm_t *)malloc(sizeof(atm_t));
-      if (!ret) { rc = JUR_ENOMEM; goto done; }
-      memcpy(ret, atm, sizeof(atm_t));
-      if (hyd) {                                    /* the balanced pressures of the base rows; outside the ray slices the caller's */
-        e = hipMemcpyAsync(ret->p, D + o_base + 4 * (size_t)np0, sizeof(double) * (size_t)np0, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { (void)hipGetLastError(); free(ret); jur_set_error("%s: bringing the pressures home failed", who); rc = JUR_EHIP; goto done; }
+      if ((rc = retrieve_loop(m, s, who, atm, nr, geom[0], rt, &op, &pl, ntiles, na, cap, nmax, pass, npass, ntpass, nfpass, &st, &a, &nq,
+                              &gq, &fv, D + o_base, d_zrp, hkoff, hy, d_R, D + o_sv, D + o_rt, I + nint0, d_live + 2 * nrd, &ret_atm))) goto done;
+    } else {
+      /* the one cut of the call: forward-only for the gradient entry, one slot per ray, which the kernels of a pass make
+       * of the all-zero rowptr; with the gain the blocks stay where the pass leaves them */
+      scene_cut_t const cut = {pass, npass, rp, gd != NULL, held, D + o_k, k};
+      if (gd) a.rowptr = d_zrp;
+      if ((rc = scene_passes_run(m, s, who, atm, &st, &a, &nq, ntiles, &gq, ngroups, fov ? &fv : NULL, hy[1], &cut, NULL,
+                                 (pm && pm->phase == 2) ? pm : NULL, nmax))) goto done;
+      if (nsv && (rc = solve_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, nq.b, D + o_sv, sv->in, sv->out, NULL, d_R))) goto done;
+      if (ndg && (rc = diag_enqueue(m, s, who, nslice, na, nb, nq.wptr, nq.aptr, nq.A, D + o_dg, dg->prior_ivar, dg->out, ninv, ndtile, dmap, d_R))) goto done;
+      if (held) {
+        /* S and the breakdowns lie where the diagnostics left them, the blocks of all rays where the passes left them; the
+         * effective weights are formed from the results of the passes, under the mask the sums were formed under */
+        jur_scene_weff_t wq;
+        wq.n = (long)nrd; wq.mask = fov ? d_live : D + o_inrad; wq.f = D + o_rad; wq.y = D + o_y; wq.weight = D + o_w;
+        wq.weff = D + o_gn + gl.weff;
+        if (SCENE_TIMED(m, s, jurk_scene_weff(&wq, s))) { rc = launch_failed("%s: effective-weight kernel launch failed", who); goto done; }
+        jur_scene_gain_t gq2;
+        memset(&gq2, 0, sizeof gq2);
+        gq2.nslice = nslice; gq2.nd = nd; gq2.wptr = nq.wptr; gq2.aptr = nq.aptr; gq2.sptr = nq.sptr; gq2.srays = nq.srays;
+        gq2.koff = d_koff; gq2.gptr = d_gptr; gq2.status = (int const *)(D + o_dg + dl.stat); gq2.S = D + o_dg + dl.S; gq2.k = D + o_k;
+        gq2.nrd = (long)nrd; gq2.nb = nb;
+        if ((rc = gain_enqueue(m, s, who, &gq2, D + o_gn, nkret, ngtile, ngroups, gmap, dg->gin, dg->gout, pm ? pm->gain : NULL))) goto done;
+        if (pm && nrd && hipMemcpyAsync(pm->weff, wq.weff, sizeof(double) * nrd, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+          (void)hipGetLastError(); jur_set_error("%s: keeping the effective weights failed", who); rc = JUR_EHIP; goto done;
+        }
       }
-      if (looping) {
-        for (long q = 0; q < nslice; q++) if (ro->state[q] == JUR_RET_ACTIVE) ro->state[q] = JUR_RET_MAXITER;
-        if (ro->h_cost)
-          for (int it = 0; it < rin->max_iter; it++)
-            if (ro->h_work[2 * it] == 0)                /* (an iteration that no slice reached) */
-              for (long q = 0; q < nslice; q++) { ro->h_cost[(size_t)it * RS + (size_t)q] = ro->cost[q]; ro->h_prior[(size_t)it * RS + (size_t)q] = ro->prior[q]; }
-        jur_scene_trial_t xq = tst;
-        xq.out = d_xout;
-        ti = scene_timed_begin(m, s);
-        ek = jurk_scene_elements(&xq, JUR_ELEM_STATE, nb, s);
-        scene_timed_end(m, ti, s);
-        e = ek ? hipErrorUnknown : hipMemcpyAsync(ro->x, d_xout, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { (void)hipGetLastError(); free(ret); jur_set_error("%s: bringing the state home failed", who); rc = JUR_EHIP; goto done; }
-        for (long i = 0; i < nb; i++) scene_row_array(ret, ng, pl.erow[i])[pl.eip[i]] = ro->x[i];
-      }
-      rc = jur_model_set_atm(m, ret);
-      if (!rc) {
-        e = hipMemcpyAsync(D + o_rad, D + o_inrad, sizeof(double) * nrd, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
-        if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
-      }
-      if (!rc) rc = jur_formod_device(m, nr, D + o_geom, D + o_rad, D + o_tau, D + o_tp, d_np, m->d_status, s);
-      if (rc) { free(ret); goto done; }
-      a.out_rad = D + o_rad; a.out_tau = D + o_tau; a.out_tp = D + o_tp; a.out_np = d_np;
-      if (fov) {                                    /* all rays of the call, one slot each */
-        fv.k.nr = nr; fv.k.time = D + o_geom; fv.k.vpz = D + o_geom + 4 * NR;
-        fv.k.r0 = 0; fv.k.r1 = nr; fv.k.ntrial = 1; fv.k.rowptr = NULL;
-        fv.k.rad = D + o_rad; fv.k.tau = D + o_tau; fv.k.rad_f = d_frad; fv.k.tau_f = d_ftau;
-        ti = scene_timed_begin(m, s);
-        ek = jurk_scene_fov(&fv.k, s);
-        scene_timed_end(m, ti, s);
-        if (ek) { free(ret); jur_set_error("%s: field-of-view kernel launch failed", who); rc = JUR_EHIP; goto done; }
-        a.out_rad = d_frad; a.out_tau = d_ftau;
-      }
-      ret_atm = ret;
     }
     e = hipMemcpyAsync(rad, a.out_rad, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(tau, a.out_tau, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
@@ -3646,8 +3666,8 @@ static int kernel_scene_body(jur_model_t *m, atm_t const *atm, long nr, double c
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);   /* copies out of the arrays freed here may still be under way */
-  free(srays); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa); free(rd); free(ri); free(hact); free(hcomp);
-  free(ret_atm); free(dmap); free(gmap); free(htimec); free(hyat); free(hkoff); free(hjac); free(hbd); free(hov); free(hovp);
+  free(srays); free(scopy); free(nptr); free(off); free(pass); free(cdesc); free(iqa);
+  free(ret_atm); free(dmap); free(gmap); free(hyat); free(hkoff);
   scene_open_free(&op);
   trial_plan_free(&pl);
   return rc;
@@ -3669,7 +3689,7 @@ static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
 int jur_kernel_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
                           double *const tp[3], int *np_out, long const *rowptr, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_kernel_scene_host: null argument"); return JUR_EINVAL; }
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, NULL, NULL, NULL, NULL, NULL, NULL, "jur_kernel_scene_host"));
 }
 
 int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3677,7 +3697,7 @@ int jur_normal_scene_host(jur_model_t *m, atm_t const *atm, long nr, double cons
                           double *A, double *b, double *cost, long *nlive, double *k, long max_rays_per_pass) {
   if (!m || !atm) { jur_set_error("jur_normal_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, NULL, NULL, NULL, "jur_normal_scene_host"));
 }
 
 int jur_gradient_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3686,7 +3706,7 @@ int jur_gradient_scene_host(jur_model_t *m, atm_t const *atm, long nr, double co
   if (!m || !atm) { jur_set_error("jur_gradient_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, NULL, b, cost, nlive};
   scene_grad_t const gd = {k};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, NULL, NULL, &gd, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, NULL, NULL, &gd, NULL, "jur_gradient_scene_host"));
 }
 
 int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3696,7 +3716,7 @@ int jur_step_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const 
   if (!m || !atm) { jur_set_error("jur_step_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_solve_t const sv = {in, out};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL, NULL, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, &sv, NULL, NULL, NULL, NULL, "jur_step_scene_host"));
 }
 
 int jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3706,7 +3726,7 @@ int jur_diagnose_scene_host(jur_model_t *m, atm_t const *atm, long nr, double co
   if (!m || !atm) { jur_set_error("jur_diagnose_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_diag_t const dg = {prior_ivar, out, NULL, NULL};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, NULL, "jur_diagnose_scene_host"));
 }
 
 int jur_gain_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const *const geom[7], double *rad, double *tau,
@@ -3716,7 +3736,7 @@ int jur_gain_scene_host(jur_model_t *m, atm_t const *atm, long nr, double const 
   if (!m || !atm || !in || !out) { jur_set_error("jur_gain_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, A, b, cost, nlive};
   scene_diag_t const dg = {prior_ivar, diag, in, out};
-  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, NULL));
+  return scene_restore_atm(m, atm, kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, NULL, "jur_gain_scene_host"));
 }
 
 int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, long nr, double const *const geom[7],
@@ -3726,7 +3746,7 @@ int jur_retrieve_scene_host(jur_model_t *m, atm_t const *atm0, atm_t *atm_ret, l
   if (!m || !atm0 || !atm_ret) { jur_set_error("jur_retrieve_scene_host: null argument"); return JUR_EINVAL; }
   scene_normal_t const nm = {y, weight, NULL, NULL, NULL, NULL};
   scene_retrieve_t const rt = {in, out, atm_ret};
-  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt, NULL, NULL, NULL);
+  int const rc = kernel_scene_body(m, atm0, nr, geom, rad, tau, tp, np_out, rowptr, NULL, max_rays_per_pass, &nm, NULL, &rt, NULL, NULL, NULL, "jur_retrieve_scene_host");
   if (rc) return scene_restore_atm(m, atm0, rc);    /* (on success the model holds atm_ret) */
   if (nr != 0) return JUR_OK;
   if (atm_ret != atm0) memcpy(atm_ret, atm0, sizeof(atm_t));   /* no rays: nothing was retrieved */
@@ -3760,7 +3780,6 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   int enqueued = 0;
   scene_open_t op;
   long *pass = NULL;
-  double *hbd = NULL;                               /* the box per element on the host: lo | hi */
   int const fov = m->fov_n > 0;                     /* a field of view is set: the trial radiances are convolved */
   int const hyd = m->scene_hydz >= 0;               /* the hydrostatic balance is on: base rows and trial copies are balanced */
   long *hyat = NULL;
@@ -3771,7 +3790,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   long const nslice = op.nslice, nrs = op.nrs;
   if (nslice == 0) goto done;                         /* no state elements: nothing to write */
   if (!dx || !cost || !prior) { jur_set_error("%s: null argument", who); rc = JUR_EINVAL; goto done; }
-  if ((rc = trial_plan_make(&pl, who, ctl, atm, ntrial, nr, nslice, op.sl, op.sid))) goto done;
+  if ((rc = trial_plan_make(&pl, who, m, atm, ntrial, nr, nslice, op.sl, op.sid))) goto done;
   long const nb = pl.nb;
   for (int t = 0; t < ntrial; t++)
     for (long q = 0; q < nslice; q++)
@@ -3788,7 +3807,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
 
   size_t const NB = (size_t)nb, NS = (size_t)nslice, NT = (size_t)ntrial, npr = prior_ivar ? NB : 0;
   size_t const ndv = d_R ? NT * NB : 0;               /* (a full prior precision: xa - (x + dx) of every trial) */
-  size_t const nbd = m->sb_nq ? 2 * NB : 0;           /* (a box on the state: lo | hi of every element) */
+  size_t const nbd = pl.box ? 2 * NB : 0;             /* (a box on the state: lo | hi of every element) */
   size_t const atm_bytes = sizeof(double) * (nrow + 1) * (size_t)pl.nt;
   size_t const nfov = fov ? nrd : 0;                  /* (the effective mask) */
   size_t const NH = hyd ? (size_t)nrs + NT * NS : 0;  /* (the balance's segments: the ray slices, every trial copy) */
@@ -3803,25 +3822,14 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   }
   size_t const slot_bytes = sizeof(double) * (10 + (size_t)(fov ? 4 : 3) * (size_t)nd) + sizeof(int);
   long cap = max_rays_per_pass;
-  if (cap == 0) {                                     /* as the Jacobian entries size their passes */
-    cap = (m->ws_budget - (long)atm_bytes - (long)acc_bytes) / 16 / (long)slot_bytes;
-    if (cap < 4096) cap = 4096;
-  }
+  if (cap == 0) cap = jur_scene_default_cap(m->ws_budget, (long)atm_bytes + (long)acc_bytes, slot_bytes);   /* as the Jacobian entries size their passes */
   long nmax = 0;
   if (!(pass = (long *)malloc(sizeof(long) * (NR + 1)))) { rc = JUR_ENOMEM; goto done; }
   long const npass = jur_trial_passes(nr, ntrial, cap, fov ? geom[0] : NULL, pass, &nmax);
   if (npass < 0) { jur_set_error("%s: a scan with 2^31 trial rays", who); rc = JUR_EINVAL; goto done; }
 
-  if (nbd) {
-    if (!(hbd = (double *)malloc(sizeof(double) * nbd))) { rc = JUR_ENOMEM; goto done; }
-    jur_state_bounds_expand(m->sb_lo, m->sb_hi, nb, pl.erow, hbd, hbd + NB);
-  }
-  if (hyd) {
-    if (!(hyat = (long *)malloc((sizeof(long) + sizeof(int)) * (NH ? NH : 1)))) { rc = JUR_ENOMEM; goto done; }
-    int *const hylen = (int *)(hyat + NH);
-    for (long q = 0; q < nrs; q++) { hyat[q] = op.hyf[q]; hylen[q] = op.hyf[NR + (size_t)q]; }
-    for (long j = 1; j < pl.ncopy; j++) { hyat[nrs + j - 1] = pl.off[j]; hylen[nrs + j - 1] = (int)(pl.off[j + 1] - pl.off[j]); }
-  }
+  long nhc = 0, ntc = 0;                              /* (the balance's segments: no raised copies here, every trial copy) */
+  if (hyd && !(hyat = jur_scene_hydro_segments(NH, nr, nrs, op.hyf, 0, NULL, NULL, -1, pl.ncopy, pl.off, &nhc, &ntc))) { rc = JUR_ENOMEM; goto done; }
 
   size_t const o_base = 0, o_geom = o_base + nrow * (size_t)np0, o_inrad = o_geom + 7 * NR, o_y = o_inrad + nrd, o_w = o_y + nrd,
                o_dx = o_w + nrd, o_r = o_dx + NT * NB, o_xa = o_r + npr, o_cost = o_xa + npr, o_prior = o_cost + NT * NS,
@@ -3836,9 +3844,8 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     long *const L = (long *)(D + o_long);
     int *const I = (int *)(D + o_int), *const d_first = I + pl.nint, *const d_len = d_first + NR;
     enqueued = 1;
-    hipError_t e = hipMemcpyAsync(D + o_base, op.hbase, sizeof(double) * nrow * (size_t)np0, hipMemcpyHostToDevice, s);
-    for (int q = 0; q < 7 && e == hipSuccess; q++) e = hipMemcpyAsync(D + o_geom + (size_t)q * NR, geom[q], sizeof(double) * NR, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(D + o_inrad, rad_in, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
+    scene_fov_t fv;
+    hipError_t e = scene_open_upload(m, s, &op, np0, nr, geom, rad_in, D + o_base, D + o_geom, D + o_inrad, d_first, 2, D + o_live, &fv);
     if (e == hipSuccess) e = hipMemcpyAsync(D + o_y, y, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(D + o_w, weight, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && NB) e = hipMemcpyAsync(D + o_dx, dx, sizeof(double) * NT * NB, hipMemcpyHostToDevice, s);
@@ -3846,55 +3853,25 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (e == hipSuccess && npr) e = hipMemcpyAsync(D + o_xa, prior_xa, sizeof(double) * NB, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(L, pl.longs, sizeof(long) * pl.nlong, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(I, pl.ints, sizeof(int) * pl.nint, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_first, op.first, sizeof(int) * 2 * NR, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_status, 0, sizeof(int), s);
-    if (fov && e == hipSuccess) e = hipMemcpyAsync(D + o_live, op.hlive, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
-    if (nbd && e == hipSuccess) e = hipMemcpyAsync(D + o_bd, hbd, sizeof(double) * nbd, hipMemcpyHostToDevice, s);
-    long const *const d_hyat = L + pl.nlong;
-    int const *const d_hylen = d_len + NR;
+    if (nbd && e == hipSuccess) e = hipMemcpyAsync(D + o_bd, pl.box, sizeof(double) * nbd, hipMemcpyHostToDevice, s);
+    jur_hyseg_t const hy = {(long)NH, L + pl.nlong, d_len + NR};
     if (NH && e == hipSuccess) e = hipMemcpyAsync(L + pl.nlong, hyat, sizeof(long) * NH, hipMemcpyHostToDevice, s);
     if (NH && e == hipSuccess) e = hipMemcpyAsync(d_len + NR, hyat + NH, sizeof(int) * NH, hipMemcpyHostToDevice, s);
     long *const d_ovp = L + pl.nlong + NH;
     int *const d_otflag = d_len + NR + NH;
     if (ov && e == hipSuccess) e = hipMemsetAsync(d_otflag, 0, sizeof(int) * nov_int, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
-    if (hyd && scene_hydro_launch(m, s, nrs, d_hyat, d_hylen, D + o_base, (size_t)np0)) {   /* the base rows, once */
+    if (scene_hydro_launch(m, s, jur_hyseg_sub(hy, 0, nrs), D + o_base, (size_t)np0)) {   /* the base rows, once */
       jur_set_error("%s: hydrostatic kernel launch failed", who); rc = JUR_EHIP; goto done;
     }
 
-    scene_fov_t fv;
-    memset(&fv, 0, sizeof fv);
-    fv.k.nr = nr; fv.k.nd = nd; fv.k.time = D + o_geom; fv.k.vpz = D + o_geom + 4 * NR;
-    fv.k.n = m->fov_n; fv.k.dz = m->d_fov_shape; fv.k.w = m->d_fov_shape + JUR_NSHAPE; fv.k.status = m->d_status;
-    fv.live = D + o_live;
-    jur_scene_stack_t sk;
-    jur_scene_trial_t st;
-    jur_scene_trial_pass_t ps;
-    memset(&sk, 0, sizeof sk); memset(&st, 0, sizeof st); memset(&ps, 0, sizeof ps);
-    long const *const d_wptr = L, *const d_off = L + (pl.off - pl.longs), *const d_sptr = L + (pl.sptr - pl.longs);
-    sk.ncopy = (int)pl.ncopy; sk.np0 = np0; sk.nrow = (int)nrow; sk.ng = ng; sk.nt = pl.nt;
-    sk.off = d_off; sk.first = I; sk.prow = I + pl.ncopy; sk.pip = I + 2 * pl.ncopy;
-    sk.base = D + o_base; sk.h = NULL; sk.tmax = op.tmax; sk.span = op.span;
-    st.nslice = nslice; st.ntrial = ntrial; st.np0 = np0; st.nt = pl.nt;
-    st.wptr = d_wptr; st.off = d_off; st.sfirst = I + (pl.sfirst - pl.ints); st.erow = I + (pl.erow - pl.ints); st.eip = I + (pl.eip - pl.ints);
-    st.base = D + o_base; st.dx = D + o_dx; st.ivar = npr ? D + o_r : NULL; st.xa = npr ? D + o_xa : NULL; st.prior = D + o_prior;
-    if (nbd) { st.lo = D + o_bd; st.hi = D + o_bd + NB; }
-    ps.nr = nr; ps.nd = nd; ps.ntrial = ntrial; ps.first = d_first; ps.len = d_len; ps.tcopy0 = I + (pl.tcopy0 - pl.ints); ps.off = d_off;
-    ps.in_geom = D + o_geom; ps.in_rad = D + o_inrad; ps.nslice = nslice; ps.sptr = d_sptr; ps.srays = I + (pl.srays - pl.ints);
-    ps.y = D + o_y; ps.weight = D + o_w; ps.cost = D + o_cost;
-    jur_scene_pquad_t tq;
-    memset(&tq, 0, sizeof tq);
-    if (d_R) {                                        /* (the running sums of w^2 are the model's own) */
-      tq.nslice = nslice; tq.nvec = ntrial; tq.wptr = d_wptr; tq.aptr = (long const *)m->d_pp + NS + 1; tq.R = d_R;
-      tq.v = D + o_dv; tq.out = D + o_prior;
-    }
-    jur_scene_ovfold_t of;                            /* (JUR_OVERFLOW_ISOLATE: every slice of the call takes part) */
-    memset(&of, 0, sizeof of);
-    of.nslice = nslice; of.ntrial = ntrial; of.flag = d_otflag; of.cost = D + o_cost; of.part = d_ovp;
+    trial_dev_t td;                                 /* (the running sums of w^2 under a full prior precision are the model's own) */
+    trial_dev_fill(&td, m, &pl, np0, op.tmax, op.span, L, I, D + o_base, D + o_geom, D + o_inrad, d_first, d_len, D + o_y, D + o_w,
+                   D + o_dx, npr ? D + o_r : NULL, npr ? D + o_xa : NULL, D + o_prior, D + o_cost, nbd ? D + o_bd : NULL, d_R,
+                   d_R ? (long const *)m->d_pp + NS + 1 : NULL, D + o_dv, ov ? d_otflag : NULL, d_ovp, NULL, NULL);
     long const novt = jur_scene_overflow_parts((long)(NT * NS));
     long hovp[JUR_OVERFLOW_PARTS];
-    if ((rc = trial_run(m, s, who, atm, &sk, &st, &ps, nb, npass, pass, nmax, fov ? &fv : NULL, d_R ? &tq : NULL,
-                        hyd ? (long)(NT * NS) : 0, d_hyat + nrs, d_hylen + nrs, ov ? &of : NULL))) goto done;
+    if ((rc = trial_run(m, s, who, atm, &td, nb, npass, pass, nmax, fov ? &fv : NULL, jur_hyseg_sub(hy, nrs + nhc, ntc)))) goto done;
     e = hipMemcpyAsync(cost, D + o_cost, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
     if (ov && e == hipSuccess) e = hipMemcpyAsync(hovp, d_ovp, sizeof(long) * (size_t)novt, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(prior, D + o_prior, sizeof(double) * NT * NS, hipMemcpyDeviceToHost, s);
@@ -3909,7 +3886,7 @@ static int trial_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   }
 done:
   if (enqueued && rc) (void)hipStreamSynchronize(m->stream);
-  free(pass); free(hyat); free(hbd);
+  free(pass); free(hyat);
   scene_open_free(&op);
   trial_plan_free(&pl);
   return rc;
@@ -3973,10 +3950,7 @@ int jur_scene_hydrostatic_host(jur_model_t *m, atm_t const *atm_in, long nr, dou
     memset(&hq, 0, sizeof hq);
     hq.nseg = nseg; hq.at = d_at; hq.len = d_len; hq.hydz = m->scene_hydz;
     hq.z = D; hq.lat = D + N; hq.p = D + 2 * N; hq.t = D + 3 * N; hq.q = ig >= 0 ? D + 4 * N : NULL;
-    int const ti = scene_timed_begin(m, s);
-    int const ek = jurk_scene_hydro(&hq, s);
-    scene_timed_end(m, ti, s);
-    if (ek) { jur_set_error("%s: hydrostatic kernel launch failed", who); rc = JUR_EHIP; goto done; }
+    if (SCENE_TIMED(m, s, jurk_scene_hydro(&hq, s))) { rc = launch_failed("%s: hydrostatic kernel launch failed", who); goto done; }
     e = hipMemcpyAsync(h + 2 * N, D + 2 * N, sizeof(double) * N, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
@@ -4102,11 +4076,11 @@ int jur_gain_slices_host(jur_model_t *m, long nslice, long const *wptr, double c
   if (!wptr || !rowptr || !sid) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
   if ((rc = jur_diag_check_wptr(who, nslice, wptr))) return rc;
   if ((rc = jur_gain_check_layout(who, nslice, wptr, nr, rowptr, sid))) return rc;
-  size_t const NS = (size_t)nslice, NR = (size_t)nr, NRD = NR * (size_t)nd, nk = (size_t)rowptr[nr] * (size_t)nd;
-  if ((wptr[nslice] > 0 && !S) || (nk > 0 && !k) || (NRD > 0 && !weight_eff)) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
+  size_t const NS = (size_t)nslice, NR = (size_t)nr, nrd = NR * (size_t)nd, nk = (size_t)rowptr[nr] * (size_t)nd;
+  if ((wptr[nslice] > 0 && !S) || (nk > 0 && !k) || (nrd > 0 && !weight_eff)) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
   long *ptr = (long *)malloc(sizeof(long) * (4 * (NS + 1) + NR));
   int *srays = (int *)malloc(sizeof(int) * NR), *hmap = NULL;
-  unsigned char *hl = (unsigned char *)malloc(NRD ? NRD : 1);
+  unsigned char *hl = (unsigned char *)malloc(nrd ? nrd : 1);
   int enqueued = 0;
   if (!ptr || !srays || !hl) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
   {
@@ -4121,13 +4095,13 @@ int jur_gain_slices_host(jur_model_t *m, long nslice, long const *wptr, double c
     }
     for (long r = 0; r < nr; r++) koff[r] = rowptr[r] * nd;
     long const nlist = jur_scene_rays_by_slice(nr, nslice, sid, sptr, srays);
-    for (size_t at = 0; at < NRD; at++) hl[at] = sid[at / (size_t)nd] >= 0 && weight_eff[at] > 0;
+    for (size_t at = 0; at < nrd; at++) hl[at] = sid[at / (size_t)nd] >= 0 && weight_eff[at] > 0;
     if (in->ncomp > 0 && (rc = jur_gain_check_var(who, in->ncomp, nr, nd, in->var, hl))) goto done;
     if ((rc = gain_maps_make(who, nslice, wptr, sptr, nd, &ntile, &hmap))) goto done;
     long const na = aptr[nslice], nb = wptr[nslice], ngroups = gptr[nslice];
     if (ngroups > 0x7fffffffL) { jur_set_error("%s: 2^31 workgroups: call with fewer systems at a time", who); rc = JUR_EINVAL; goto done; }
     size_t const nlong = 4 * (NS + 1) + NR, o_S = nlong, o_k = o_S + (size_t)na, o_gn = o_k + nk;
-    gain_layout_t const gl = gain_layout(nk, (size_t)nb, NRD, (size_t)in->ncomp, (size_t)ntile);
+    gain_layout_t const gl = gain_layout(nk, (size_t)nb, nrd, (size_t)in->ncomp, (size_t)ntile);
     size_t const o_int = o_gn + gl.end;
     hipStream_t s;
     if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * (NS + (size_t)nlist + 1), &s))) goto done;
@@ -4138,7 +4112,7 @@ int jur_gain_slices_host(jur_model_t *m, long nslice, long const *wptr, double c
     hipError_t e = hipMemcpyAsync(L, ptr, sizeof(long) * nlong, hipMemcpyHostToDevice, s);
     if (na && e == hipSuccess) e = hipMemcpyAsync(D + o_S, S, sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s);
     if (nk && e == hipSuccess) e = hipMemcpyAsync(D + o_k, k, sizeof(double) * nk, hipMemcpyHostToDevice, s);
-    if (NRD && e == hipSuccess) e = hipMemcpyAsync(D + o_gn + gl.weff, weight_eff, sizeof(double) * NRD, hipMemcpyHostToDevice, s);
+    if (nrd && e == hipSuccess) e = hipMemcpyAsync(D + o_gn + gl.weff, weight_eff, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     if (status && e == hipSuccess) e = hipMemcpyAsync(d_stat, status, sizeof(int) * NS, hipMemcpyHostToDevice, s);
     if (nlist && e == hipSuccess) e = hipMemcpyAsync(d_srays, srays, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; goto done; }
@@ -4146,7 +4120,7 @@ int jur_gain_slices_host(jur_model_t *m, long nslice, long const *wptr, double c
     memset(&q, 0, sizeof q);
     q.nslice = nslice; q.nd = nd; q.wptr = L; q.aptr = L + (NS + 1); q.sptr = L + 2 * (NS + 1); q.gptr = L + 3 * (NS + 1);
     q.koff = L + 4 * (NS + 1); q.srays = d_srays; q.status = status ? d_stat : NULL; q.S = D + o_S; q.k = D + o_k;
-    q.nrd = (long)NRD; q.nb = nb;
+    q.nrd = (long)nrd; q.nb = nb;
     if ((rc = gain_enqueue(m, s, who, &q, D + o_gn, nk, ntile, ngroups, hmap, in, out, NULL))) goto done;
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) { jur_set_error("%s: %s", who, hipGetErrorString(e)); rc = JUR_EHIP; }
@@ -4173,7 +4147,7 @@ int jur_param_slices_host(jur_model_t *m, long nslice, long const *wptr, long co
     jur_set_error("%s: null argument (%s)", who, !wptr ? "wptr" : !bwptr ? "bwptr" : !rowptr ? "rowptr" : !rowptr_b ? "rowptr_b" : "sid");
     return JUR_EINVAL;
   }
-  size_t const NS = (size_t)nslice, NR = (size_t)nr, NRD = NR * (size_t)nd, NC = (size_t)(in->nvar + in->ncov);
+  size_t const NS = (size_t)nslice, NR = (size_t)nr, nrd = NR * (size_t)nd, NC = (size_t)(in->nvar + in->ncov);
   long *ptr = (long *)malloc(sizeof(long) * (6 * (NS + 1) + 2 * NR));
   int *srays = (int *)malloc(sizeof(int) * NR), *hmap = NULL;
   int enqueued = 0;
@@ -4185,7 +4159,7 @@ int jur_param_slices_host(jur_model_t *m, long nslice, long const *wptr, long co
     if (nc < 0) { rc = (int)nc; goto done; }
     if ((rc = jur_param_check_bwptr(who, nslice, bwptr, bw))) goto done;
     size_t const nk = (size_t)rowptr[nr] * (size_t)nd, nkb = (size_t)rowptr_b[nr] * (size_t)nd;
-    if ((nk > 0 && !gain) || (nkb > 0 && !kb) || (NRD > 0 && !weight_eff)) {
+    if ((nk > 0 && !gain) || (nkb > 0 && !kb) || (nrd > 0 && !weight_eff)) {
       jur_set_error("%s: null argument (%s)", who, (nk > 0 && !gain) ? "gain" : (nkb > 0 && !kb) ? "kb" : "weight_eff");
       rc = JUR_EINVAL; goto done;
     }
@@ -4208,7 +4182,7 @@ int jur_param_slices_host(jur_model_t *m, long nslice, long const *wptr, long co
       (void)jur_param_maps(nslice, wptr, bw, hmap);
     }
     size_t const nb = (size_t)wptr[nslice], nbw = (size_t)bw[nslice], nbb = (size_t)bbptr[nslice], NV = (size_t)in->nvar, NF = (size_t)in->ncov;
-    size_t const nlong = 6 * (NS + 1) + 2 * NR, o_g = nlong, o_kb = o_g + nk, o_we = o_kb + nkb, o_C = o_we + NRD, o_var = o_C + (size_t)nc,
+    size_t const nlong = 6 * (NS + 1) + 2 * NR, o_g = nlong, o_kb = o_g + nk, o_we = o_kb + nkb, o_C = o_we + nrd, o_var = o_C + (size_t)nc,
                  o_cov = o_var + NV * nbw, o_sig = o_cov + NF * nbb, o_int = o_sig + NC * nb;
     hipStream_t s;
     if ((rc = scene_slab_reserve(m, who, sizeof(double) * o_int + sizeof(int) * (3 * (size_t)ntile + (size_t)nlist + 1), &s))) goto done;
@@ -4219,7 +4193,7 @@ int jur_param_slices_host(jur_model_t *m, long nslice, long const *wptr, long co
     hipError_t e = hipMemcpyAsync(L, ptr, sizeof(long) * nlong, hipMemcpyHostToDevice, s);
     if (nk && e == hipSuccess) e = hipMemcpyAsync(D + o_g, gain, sizeof(double) * nk, hipMemcpyHostToDevice, s);
     if (nkb && e == hipSuccess) e = hipMemcpyAsync(D + o_kb, kb, sizeof(double) * nkb, hipMemcpyHostToDevice, s);
-    if (NRD && e == hipSuccess) e = hipMemcpyAsync(D + o_we, weight_eff, sizeof(double) * NRD, hipMemcpyHostToDevice, s);
+    if (nrd && e == hipSuccess) e = hipMemcpyAsync(D + o_we, weight_eff, sizeof(double) * nrd, hipMemcpyHostToDevice, s);
     if (NV * nbw > 0 && e == hipSuccess) e = hipMemcpyAsync(D + o_var, in->var, sizeof(double) * NV * nbw, hipMemcpyHostToDevice, s);
     if (NF * nbb > 0 && e == hipSuccess) e = hipMemcpyAsync(D + o_cov, in->cov, sizeof(double) * NF * nbb, hipMemcpyHostToDevice, s);
     if (ntile && e == hipSuccess) e = hipMemcpyAsync(d_map, hmap, sizeof(int) * 3 * (size_t)ntile, hipMemcpyHostToDevice, s);
@@ -4232,10 +4206,7 @@ int jur_param_slices_host(jur_model_t *m, long nslice, long const *wptr, long co
     q.pptr = L + 5 * (NS + 1); q.koff = L + 6 * (NS + 1); q.koffb = q.koff + NR;
     q.srays = d_srays; q.cmap = d_map; q.gain = D + o_g; q.kb = D + o_kb; q.weff = D + o_we; q.var = D + o_var; q.cov = D + o_cov;
     q.nb = (long)nb; q.nbw = (long)nbw; q.nbb = (long)nbb; q.C = D + o_C; q.sig = D + o_sig;
-    int const ti = scene_timed_begin(m, s);
-    int const ek = jurk_scene_param(&q, ntile, ngroups, s);
-    scene_timed_end(m, ti, s);
-    if (ek) { jur_set_error("%s: kernel launch failed", who); rc = JUR_EHIP; goto done; }
+    if (SCENE_TIMED(m, s, jurk_scene_param(&q, ntile, ngroups, s))) { rc = launch_failed("%s: kernel launch failed", who); goto done; }
     if (nc && out->C) e = hipMemcpyAsync(out->C, q.C, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost, s);
     if (NC * nb > 0 && e == hipSuccess) e = hipMemcpyAsync(out->sigma_param, q.sig, sizeof(double) * NC * nb, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -4286,7 +4257,7 @@ static int param_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   if (!geom || !rad || !tau || !tp || !rowptr) { jur_set_error("%s: null argument", who); return JUR_EINVAL; }
   jur_param_in_t const *const in = pin->in;
   jur_param_out_t const *const out = pout->out;
-  size_t const NR = (size_t)nr, NRD = NR * (size_t)nd, NC = (size_t)(in->nvar + in->ncov), nrow = 6 + (size_t)ng + nw;
+  size_t const NR = (size_t)nr, nrd = NR * (size_t)nd, NC = (size_t)(in->nvar + in->ncov), nrow = 6 + (size_t)ng + nw;
   int *first = (int *)malloc(sizeof(int) * 4 * NR), *len = first ? first + NR : NULL, *sid = len ? len + NR : NULL, *srays = sid ? sid + NR : NULL;
   long *rp = (long *)malloc(sizeof(long) * 2 * (NR + 1)), *rpb = rp ? rp + NR + 1 : NULL, *ptr = NULL, *mark = NULL;
   ctl_t *cb = (ctl_t *)malloc(sizeof(ctl_t));
@@ -4313,7 +4284,7 @@ static int param_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
   size_t const NS = (size_t)nslice, nlong = 6 * (NS + 1) + 2 * NR;
   ptr = (long *)calloc(nlong, sizeof(long));
   mark = (long *)calloc(NS ? NS : 1, sizeof(long));
-  hrad = (double *)malloc(sizeof(double) * (2 * NRD + 3 * NR));
+  hrad = (double *)malloc(sizeof(double) * (2 * nrd + 3 * NR));
   if (!ptr || !mark || !hrad) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
   {
     long *const wptr = ptr, *const bw = wptr + NS + 1, *const cptr = bw + NS + 1, *const bbptr = cptr + NS + 1, *const sptr = bbptr + NS + 1,
@@ -4337,7 +4308,7 @@ static int param_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     if (ntile > 0x7fffffffL / 5 || ngroups > 0x7fffffffL) { jur_set_error("%s: 2^31 workgroups: call with the rays of fewer slices at a time", who); rc = JUR_EINVAL; goto done; }
     size_t const nk = (size_t)rp[nr] * (size_t)nd, nb = (size_t)wptr[nslice], nbw = (size_t)bw[nslice], nbb = (size_t)bbptr[nslice],
                  NV = (size_t)in->nvar, NF = (size_t)in->ncov;
-    size_t const o_g = nlong, o_we = o_g + nk, o_C = o_we + NRD, o_var = o_C + (size_t)nc, o_cov = o_var + NV * nbw, o_sig = o_cov + NF * nbb,
+    size_t const o_g = nlong, o_we = o_g + nk, o_C = o_we + nrd, o_var = o_C + (size_t)nc, o_cov = o_var + NV * nbw, o_sig = o_cov + NF * nbb,
                  o_int = o_sig + NC * nb;
     size_t const side_bytes = sizeof(double) * o_int + sizeof(int) * (5 * (size_t)ntile + (size_t)nlist + 1);
     /* what phase 2 stacks under ctl_b's windows is known here: both phases are refused before the first is launched */
@@ -4354,7 +4325,7 @@ static int param_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     }
     (void)jur_scene_rays_by_slice(nr, nslice, sid, sptr, srays);
     if (ntile > 0 && !(hmap = (int *)malloc(sizeof(int) * 5 * (size_t)ntile))) { jur_set_error("%s: out of memory", who); rc = JUR_ENOMEM; goto done; }
-    memcpy(hrad, rad, sizeof(double) * NRD);
+    memcpy(hrad, rad, sizeof(double) * nrd);
     if ((rc = scene_side_reserve(m, who, side_bytes))) goto done;
     double *const D = (double *)m->d_side;
     long *const L = (long *)m->d_side;
@@ -4367,13 +4338,13 @@ static int param_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
     scene_param_t pm;
     memset(&pm, 0, sizeof pm);
     pm.phase = 1; pm.bytes = side_bytes; pm.gain = D + o_g; pm.weff = D + o_we;
-    if ((rc = kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, &pm))) goto done;
+    if ((rc = kernel_scene_body(m, atm, nr, geom, rad, tau, tp, np_out, rowptr, k, max_rays_per_pass, &nm, NULL, NULL, &dg, NULL, &pm, who))) goto done;
     enqueued = 1;
     hipError_t e = hipSuccess;
     if (pout->weight_eff) {
       /* jurk_scene_weff does not look at the slices (a ray without one is in no list): such a ray's measurements are
        * not live, and the array that goes home says so */
-      if (nslice > 0) e = hipMemcpyAsync(pout->weight_eff, pm.weff, sizeof(double) * NRD, hipMemcpyDeviceToHost, s);
+      if (nslice > 0) e = hipMemcpyAsync(pout->weight_eff, pm.weff, sizeof(double) * nrd, hipMemcpyDeviceToHost, s);
       if (e == hipSuccess) e = hipStreamSynchronize(s);
       for (long r = 0; r < nr && e == hipSuccess; r++)
         if (sid[r] < 0) memset(pout->weight_eff + (size_t)r * (size_t)nd, 0, sizeof(double) * (size_t)nd);
@@ -4395,17 +4366,14 @@ static int param_scene_body(jur_model_t *m, atm_t const *atm, long nr, double co
      * tau and tp of this call are the forward model's once more and go nowhere */
     if (ntile > 0 || pout->kb) {
       pm.phase = 2; pm.wptr = wptr; pm.bwptr = bw; pm.sptr = sptr; pm.srays = srays; pm.sid = sid; pm.mark = mark; pm.hmap = hmap; pm.d_pmap = d_pmap;
-      double *const tp2[3] = {hrad + 2 * NRD, hrad + 2 * NRD + NR, hrad + 2 * NRD + 2 * NR};
+      double *const tp2[3] = {hrad + 2 * nrd, hrad + 2 * nrd + NR, hrad + 2 * nrd + 2 * NR};
       ret_windows_copy(m->ctl, pin->ctl_b, ng, nw);
-      if ((rc = kernel_scene_body(m, atm, nr, geom, hrad, hrad + NRD, tp2, NULL, rpb, pout->kb, max_rays_per_pass, NULL, NULL, NULL, NULL, NULL, &pm))) goto done;
+      if ((rc = kernel_scene_body(m, atm, nr, geom, hrad, hrad + nrd, tp2, NULL, rpb, pout->kb, max_rays_per_pass, NULL, NULL, NULL, NULL, NULL, &pm, who))) goto done;
     }
 
     /* phase 3: the quadratic forms on the finished C; what was asked for comes home */
     if (NC * nb > 0) {
-      int const ti = scene_timed_begin(m, s);
-      int const ek = jurk_scene_param(q, 0, ngroups, s);
-      scene_timed_end(m, ti, s);
-      if (ek) { jur_set_error("%s: kernel launch failed", who); rc = JUR_EHIP; goto done; }
+      if (SCENE_TIMED(m, s, jurk_scene_param(q, 0, ngroups, s))) { rc = launch_failed("%s: kernel launch failed", who); goto done; }
     }
     if (nc && out->C) e = hipMemcpyAsync(out->C, q->C, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost, s);
     if (NC * nb > 0 && e == hipSuccess) e = hipMemcpyAsync(out->sigma_param, q->sig, sizeof(double) * NC * nb, hipMemcpyDeviceToHost, s);

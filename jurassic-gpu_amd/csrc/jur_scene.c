@@ -910,6 +910,25 @@ long jur_scene_ray_slices_of(int np, long nr, int const *first, int const *len, 
   return n;
 }
 
+long *jur_scene_hydro_segments(size_t nh, long nr, long nrs, int const *hyf, long ncopy, long const *off, int const *prow,
+                               int row_h2o, long tncopy, long const *toff, long *nhc, long *ntc) {
+  long *const at = (long *)malloc((sizeof(long) + sizeof(int)) * (nh ? nh : 1));
+  *nhc = *ntc = 0;
+  if (!at) return NULL;
+  int *const len = (int *)(at + nh);
+  long n = 0;
+  for (long q = 0; q < nrs; q++, n++) { at[n] = hyf[q]; len[n] = hyf[nr + q]; }
+  for (long j = 1; j < ncopy; j++)
+    if (prow[j] == 4 || prow[j] == 5 || prow[j] == row_h2o) { at[n] = off[j]; len[n] = (int)(off[j + 1] - off[j]); n++; ++*nhc; }
+  for (long j = 1; j < tncopy; j++, n++, ++*ntc) { at[n] = toff[j]; len[n] = (int)(toff[j + 1] - toff[j]); }
+  return at;
+}
+
+long jur_scene_default_cap(long budget, long used, size_t slot_bytes) {
+  long const cap = (budget - used) / 16 / (long)slot_bytes;
+  return cap < 4096 ? 4096 : cap;
+}
+
 long jur_scene_ray_slices(ctl_t const *ctl, atm_t const *atm, long nr, double const *time, int *sfirst, int *slen) {
   if (!ctl || !atm || nr < 0 || (nr > 0 && !time)) { jur_set_error("scene_ray_slices: bad arguments"); return JUR_EINVAL; }
   int const np = atm->np;
