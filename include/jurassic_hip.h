@@ -1064,7 +1064,7 @@ int  jur_model_arithmetic(jur_model_t const *m);
 /* Atmosphere along the line of sight, ctl->ip (IP in a control file): 1 (default) one vertical profile per ray, chosen
  * by its time stamp; 2 a satellite track: every point of the line of sight is interpolated between the two nearest
  * profiles of a track (intpol_atm_2d, jurassic.c:704-760).  Upstream's GPU tracer asserts IP 1 (jr_common.h:573, 581);
- * here IP 2 runs in the ray tracer, with one rule.  IP 3 stays refused at jur_model_create.
+ * here IP 2 runs in the ray tracer, with one rule, and IP 3 (a cloud of air parcels) with the rule further down.
  *   1. Time block.  A ray's time stamp selects the block [a0, a0 + n) of atmosphere points as under IP 1 (locate_atm);
  *      zmin .. zmax is the altitude range of the block's first column, as under IP 1.
  *   2. Profiles.  A profile is a maximal run of consecutive points with equal time stamp, longitude and latitude, so
@@ -1098,6 +1098,47 @@ int  jur_model_arithmetic(jur_model_t const *m);
  * block_of[] (number of the profile's time block, from 0) hold one entry per profile -- room for atm->np / 2 + 1
  * entries each; any of them may be NULL.  Returns the number of profiles, or JUR_EINVAL with the words above. */
 long jur_track_profiles(atm_t const *atm, int *first, int *len, double (*x1)[3], int *block_of);
+
+/* ctl->ip == 3, a point cloud: every point of the line of sight is the distance-weighted mean over the air parcels
+ * around it (intpol_atm_3d, jurassic.c:763-804), with ctl->cx and ctl->cz (CX, CZ in a control file) the horizontal and
+ * vertical influence lengths in km.  jur_model_create refuses cx or cz that is not > 0 or not finite with JUR_EINVAL
+ * (upstream would return NaN everywhere), and an ip other than 1, 2 or 3.  For one ray:
+ *   1. Slice.  The ray's time stamp selects the atmosphere points [a0, a0 + n) exactly as under IP 1 and IP 2
+ *      (locate_atm).  These points, and no others, are the cloud of that ray -- not upstream's literal loop over all
+ *      atm->np points: the departure the IP 2 rule makes too.
+ *   2. Altitude range.  zmin and zmax are the minimum and maximum of z over ALL points of the slice, by fmin / fmax in
+ *      ascending index.  Upstream's first-column rule (altitude_range_nn, jr_common.h:411-420) is degenerate for a
+ *      cloud, where no two points share a longitude and latitude; for a slice made of columns on one altitude grid
+ *      the two agree.  The exclusions stay: zmin == zmax and a slice of fewer than two points are not entered.
+ *   3. Cached positions.  x1[ip] = geo2cart(0, lon[ip], lat[ip]) for every atmosphere point, in the host's libm, once
+ *      per upload: what upstream caches.
+ *   4. Mean at a position.  The position gives z0; lon0, lat0 come from cart2geo of it and x0 = geo2cart(0, lon0,
+ *      lat0).  With rm2 = cx * cx, over the slice's points in ascending index: skip the point if dz = |z[ip] - z0| >=
+ *      cz; skip it if |lat[ip] - lat0| * 111.13 >= cx; dx2 = DIST2(x0, x1[ip]), skip it if dx2 >= rm2; otherwise
+ *      w = (1 - dz / cz) * (rm2 - dx2) / (rm2 + dx2), wsum += w and y += w * y[ip] for p, T, every q and every k.
+ *      Every product and sum is rounded on its own (no fused multiply-add); pressure is averaged linearly, as upstream
+ *      does, not through eip.  Finally y /= wsum by a true division when wsum >= 1e-6, otherwise every value is NaN.
+ *   5. Every evaluation of the tracer takes 4: the LOS point (p, T, q, k, the columns u = 10 q p / (k_B T) ds, q_H2O),
+ *      the mid-step probe and the three displaced probes of the refractivity gradient, the columns redone for the
+ *      point before the exit, and tsurf.
+ *   6. Holes.  A position with no parcel inside its influence region yields NaN by this arithmetic.  With refraction
+ *      off the NaN reaches that ray's records (p, T, q, k, u of the points in the hole), and those of no other ray;
+ *      the radiance update then leaves out every segment whose gas transmittance is not > 1e-50, a NaN one included,
+ *      exactly as upstream's new_obs_core does (jr_common.h:293-300), so the ray's radiance stays finite and misses
+ *      those segments (tests/test_cloud_gpu.py holds it to the CPU model's, NaN for NaN and value for value).
+ *      With refraction on the direction becomes NaN and the ray fills the LOS array: JUR_ENLOS.  The elision of an
+ *      atmosphere without extinction is never taken under IP 3, so a hole gives NaN in k as well.
+ * One kernel traces it (jur_cloud_trace_kernel, a lane per ray, the whole slice scanned at every evaluation; the
+ * slice's z, lat and x1 staged in LDS where a workgroup's rays agree on a slice of at most jur_cloud_lds_points()
+ * points: same doubles either way).  The fused kernel of small calls stays 1-D (jur_model_set_pencil stays accepted
+ * and has no effect).  Forward model, contributions, Curtis-Godson columns, the dense Jacobian (jur_kernel), the
+ * multi-device entries and the drop-in entries run under IP 3, with FORMOD 1 or 2, and ctl->hydz as under IP 2.  The
+ * scene entries return JUR_EINVAL before anything is launched, as under IP 2.
+ *
+ * jur_cloud_points: rule 3 for `atm`, host only: x1 has room for atm->np entries.  Returns atm->np, or JUR_EINVAL.
+ * jur_cloud_lds_points: the largest slice the tracer stages in LDS (a compiled constant). */
+long jur_cloud_points(atm_t const *atm, double (*x1)[3]);
+int  jur_cloud_lds_points(void);
 
 /* Frees the process-global state behind formod() / formod_GPU() / formod_pencil(): the lanes (streams, atmosphere,
  * workspaces, pinned images) and the emissivity tables loaded by the first call.  Upstream keeps its counterparts for
@@ -1147,6 +1188,13 @@ int jur_kat_update(jur_model_t *m, int id, long n, int what, double const *a, do
                    double *rad, double *tau, double *src);
 int jur_kat_traceray(jur_model_t *m, long nr, double const *const geom[7], double *los, double *tsurf, double *const tp[3],
                      int *np_out);
+/* jur_kat_cloud_mean: rule 4 of IP 3 (the model must have been created with ip = 3 and hold an atmosphere) on the
+ * device at n positions given AFTER the geometry step -- z0[i], lat0[i] and x0[i] = geo2cart(0, lon0, lat0) -- over the
+ * atmosphere points [a0, a0 + len), one position per lane: out [2 + ng + nw][n] holds p, T, every q, every k.  The
+ * device's sin and cos play no part, so the result is comparable bit for bit.  Slices of up to
+ * jur_cloud_lds_points() points are read from LDS as the tracer reads them, longer ones from the model's arrays. */
+int jur_kat_cloud_mean(jur_model_t *m, long n, int a0, int len, double const *z0, double const *lat0, double const (*x0)[3],
+                       double *out);
 
 #ifdef __cplusplus
 }

@@ -87,7 +87,8 @@ typedef struct {
  * view that grew would move the later arguments of every kernel and with them every kernel's text.  A profile is a
  * run of points with equal time stamp, longitude and latitude; the profiles of a time block are consecutive. */
 typedef struct {
-  int ip;                       /* ctl->ip: 1 one profile per time block, 2 the nearest two profiles of the block's track */
+  int ip;                       /* ctl->ip: 1 one profile per time block, 2 the nearest two profiles of the block's track,
+                                   3 the weighted mean over the block's cloud (the table of that: jur_cloud_t) */
   int nprof;                    /* profiles of the atmosphere on the device (ip == 2), else 0    */
   double const *x1;             /* [nprof][3] geo2cart(0, lon, lat) of every profile (host libm) */
   double const *lat;            /* [nprof] its latitude                                          */
@@ -95,6 +96,15 @@ typedef struct {
   int const *dir;               /* [nprof] its altitude axis: 1 strictly ascending, -1 strictly descending, 0 neither */
   int const *prof_of;           /* [atm_np] profile of every atmosphere point                    */
 } jur_track_t;
+
+/* Point cloud (ctl->ip == 3, the rule in jurassic_hip.h): the cached position of every atmosphere point, rebuilt with
+ * every atmosphere by jur_cloud_rows, and the influence region.  An argument of jur_cloud_trace_kernel alone, beside
+ * the view and NOT inside jur_track_t: either struct, grown, would move the arguments of kernels that exist. */
+typedef struct {
+  int np;                       /* points the table holds (== view.atm_np while an atmosphere is set), else 0 */
+  double cx, cz;                /* ctl->cx, ctl->cz: horizontal and vertical influence length [km], both > 0  */
+  double const *x1;             /* [np][3] geo2cart(0, lon, lat) of every atmosphere point (host libm)         */
+} jur_cloud_t;
 
 /* One chunk of rays handed to the kernels; all pointers are device memory.
  * Slot i of the chunk works on ray order[i] of the caller's arrays (order ==
@@ -125,8 +135,9 @@ typedef struct {
 
 /* kernel launchers (jur_kernels.hip); return hipError_t as int */
 int jurk_prepare_atm(jur_view_t const *v, double *d_pslope, void *stream);   /* fills atm_pslope */
-/* trk->ip == 2: jur_track_trace_kernel (one lane per ray, two profiles per point); else the 1-D tracers by launch */
-int jurk_launch_trace(jur_view_t const *v, jur_track_t const *trk, jur_chunk_t const *c, void *stream);
+/* trk->ip == 2: jur_track_trace_kernel (one lane per ray, two profiles per point); trk->ip == 3: jur_cloud_trace_kernel
+ * on the table `cld` (one lane per ray, the mean over the block's cloud); else the 1-D tracers by launch */
+int jurk_launch_trace(jur_view_t const *v, jur_track_t const *trk, jur_cloud_t const *cld, jur_chunk_t const *c, void *stream);
 /* the look-up kernel of the model's band model: cga == 0 emissivity growth (FORMOD 2), != 0 Curtis-Godson (FORMOD 1) */
 int jurk_launch_ega(jur_view_t const *v, jur_chunk_t const *c, int cga, void *stream);
 int jurk_launch_combine(jur_view_t const *v, jur_chunk_t const *c, void *stream);
@@ -173,6 +184,10 @@ int jurk_kat_continua(jur_view_t const *v, int d, long n, double const *p, doubl
                       double const *u_h2o, double *out, void *stream);
 int jurk_kat_update(jur_view_t const *v, int d, long n, int what, double const *a, double const *b, double const *c, double *rad,
                     double *tau, double *src, void *stream);
+/* rule 4 of IP 3 at n positions given after the geometry step: z0, lat0 [n], x0 [n][3] -> out [2 + ng + nw][n] */
+int jurk_kat_cloud_mean(jur_view_t const *v, jur_cloud_t const *cld, long n, int a0, int len, double const *z0, double const *lat0,
+                        double const *x0, double *out, void *stream);
+int jurk_cloud_lds_points(void);
 /* LOS records of the traced chunk (after jurk_launch_trace): los[ray][nfield][JUR_NLOS], tsurf[ray], indexed by ray id */
 int jurk_kat_los(jur_view_t const *v, jur_chunk_t const *c, double *los, double *tsurf, void *stream);
 
@@ -585,6 +600,8 @@ JUR_HIDDEN int jur_atm_slice(double const *time, long n, double t, long *first);
 /* jur_track_profiles on rows (jur_track.c), with the altitude direction of every profile and the profile of every point */
 JUR_HIDDEN long jur_track_rows(long n, double const *time, double const *z, double const *lon, double const *lat, int *first,
                                int *len, double (*x1)[3], int *block_of, int *dir, int *prof_of);
+/* jur_cloud_points on rows (jur_cloud.c) */
+JUR_HIDDEN long jur_cloud_rows(long n, double const *lon, double const *lat, double (*x1)[3]);
 JUR_HIDDEN size_t jur_state_vector(ctl_t const *ctl, atm_t const *atm, double *x, int *iqa, int *ipa);
 JUR_HIDDEN long jur_scene_slice_elements(ctl_t const *ctl, atm_t const *atm, int first, int len, long *cols, int *iqa, int *ipa);
 /* a distinct slice of a scene: points [first, first + len) with nel state elements; next: chain of the slices that

@@ -7,6 +7,8 @@
 //                         point, the point count and the surface temperature.
 //   jur_track_trace_kernel  the same for a model with IP 2: every point and probe interpolated between the two
 //                         nearest profiles of a satellite track (jurassic.c:704-760); writes the same workspace.
+//   jur_cloud_trace_kernel  the same for a model with IP 3: every point and probe the distance-weighted mean over a
+//                         cloud of air parcels (jurassic.c:763-804); writes the same workspace.
 //   jur_ega_kernel        one lane per ray, one (channel, gas) pair per workgroup: the sequential
 //                         emissivity-growth recurrence along the line of sight with its band
 //                         table look-ups (jr_common.h:237-280); writes the gas's transmittance of the
@@ -276,6 +278,7 @@ typedef __attribute__((address_space(3))) double const *lds_cptr;
 struct AtmGlobal {
   typedef double const *ptr;
   static constexpr bool track = false;   // one profile per time block (ip == 1); AtmTrack: the nearest two of a track
+  static constexpr bool cloud = false;   // AtmCloud: the weighted mean over the block's point cloud (ip == 3)
   jur_view_t const &v;
   __device__ __forceinline__ ptr z() const { return v.atm_z; }
   __device__ __forceinline__ ptr p() const { return v.atm_p; }
@@ -288,6 +291,7 @@ struct AtmGlobal {
 struct AtmLds {
   typedef lds_cptr ptr;
   static constexpr bool track = false;
+  static constexpr bool cloud = false;
   lds_cptr rows;
   int n, ng;
   __device__ __forceinline__ ptr z() const { return rows; }
@@ -387,6 +391,7 @@ template <class Tab>
 struct AtmTrack {
   typedef double const *ptr;
   static constexpr bool track = true;
+  static constexpr bool cloud = false;
   jur_view_t const &v;
   Tab T;
   int const *prof_of;
@@ -480,6 +485,129 @@ __device__ __attribute__((noinline)) void redo_columns_track(Tab T, double const
     los_u[(size_t)ig * fs] = 10. * track_row(atm_z, atm_q + (size_t)ig * atm_np, k, z) * p / (JUR_BOLTZMANN * t) * dsn;
 }
 
+// ---------------------------------------------------------------------------------------
+// point-cloud atmosphere along the line of sight (ctl->ip == 3: intpol_atm_3d, jurassic.c:763-804; the rule in
+// jurassic_hip.h)
+// ---------------------------------------------------------------------------------------
+// Where the gate columns of a ray's cloud -- altitude, latitude and cached position of every point of its time block --
+// are read from, indexed by atmosphere point in either case.  CloudGlobal: the model's rows and its position table
+// (jur_cloud_t).  CloudLds: the workgroup's copy of ONE block [a0, a0 + n) in LDS, columns z, lat, x1[0], x1[1], x1[2]
+// of n doubles each, with the block's altitude range, which the workgroup reduced while it staged.
+struct CloudGlobal {
+  static constexpr bool staged = false;
+  double const *z_, *lat_, *x1_;
+  __device__ __forceinline__ double z(int ip) const { return z_[ip]; }
+  __device__ __forceinline__ double lat(int ip) const { return lat_[ip]; }
+  __device__ __forceinline__ double x1(int ip, int i) const { return x1_[3 * (size_t)ip + i]; }
+};
+struct CloudLds {
+  static constexpr bool staged = true;
+  lds_cptr d;
+  int a0, n;
+  double zmin, zmax;
+  __device__ __forceinline__ double z(int ip) const { return d[ip - a0]; }
+  __device__ __forceinline__ double lat(int ip) const { return d[n + (ip - a0)]; }
+  __device__ __forceinline__ double x1(int ip, int i) const { return d[(2 + i) * n + (ip - a0)]; }
+};
+// the values p, T, q, k come from the model's rows, for the points that pass the gates
+template <class Tab>
+struct AtmCloud {
+  typedef double const *ptr;
+  static constexpr bool track = false;
+  static constexpr bool cloud = true;
+  jur_view_t const &v;
+  Tab T;
+  double cx, cz;
+  __device__ __forceinline__ int origin(int atm0) const { return atm0; }
+};
+
+// jurassic.c:778-792 on the points [a0, a0 + n), in ascending index: the three gates, the weight, wsum; hit(ip, w)
+// takes a point that contributes.  Every product and sum is rounded on its own (no contraction), every quotient is a
+// true division.
+template <class Tab, class F>
+__device__ __forceinline__ double cloud_scan(Tab const &T, int a0, int n, double cx, double cz, double z0, TrackGeo const &g,
+                                             F &&hit) {
+#pragma clang fp contract(off)
+  double const rm2 = cx * cx;
+  double wsum = 0;
+  for (int ip = a0; ip < a0 + n; ip++) {
+    double const dz = fabs(T.z(ip) - z0);
+    if (dz >= cz) continue;
+    if (fabs(T.lat(ip) - g.lat) * 111.13 >= cx) continue;
+    double const b0 = g.x0 - T.x1(ip, 0), b1 = g.x1 - T.x1(ip, 1), b2 = g.x2 - T.x1(ip, 2);
+    double const dx2 = b0 * b0 + b1 * b1 + b2 * b2;
+    if (dx2 >= rm2) continue;
+    double const w = (1 - dz / cz) * (rm2 - dx2) / (rm2 + dx2);
+    wsum += w;
+    hit(ip, w);
+  }
+  return wsum;
+}
+
+// the rows a point can take from the model's arrays: 0 p, 1 T, 2 .. q[ng], then k[nw]
+struct CloudRows {
+  double const *p, *t, *q, *k;
+  int atm_np, ng, nw;
+  __device__ __forceinline__ double const *row(int r) const {
+    return (r == 0) ? p : (r == 1) ? t : (r < 2 + ng) ? q + (size_t)(r - 2) * atm_np : k + (size_t)(r - 2 - ng) * atm_np;
+  }
+};
+struct CloudPT { double p, t; };
+
+// rule 4 for pressure and temperature alone (the refraction probes): jurassic.c:794-803 after the scan
+template <class Tab>
+__device__ __forceinline__ CloudPT cloud_mean_pt(Tab const &T, CloudRows const &R, int a0, int n, double cx, double cz, double z0,
+                                                 TrackGeo const &g) {
+#pragma clang fp contract(off)
+  double p = 0, t = 0;
+  double const wsum = cloud_scan(T, a0, n, cx, cz, z0, g, [&](int ip, double w) { p += w * R.p[ip]; t += w * R.t[ip]; });
+  if (wsum >= 1e-6) { p /= wsum; t /= wsum; }
+  else p = t = __builtin_nan("");
+  return {p, t};
+}
+
+// rule 4 for every row: y[0] p, y[1] T, y[2 ..] q[ng], k[nw] (2 + ng + nw doubles)
+template <class Tab>
+__device__ __forceinline__ void cloud_mean_all(Tab const &T, CloudRows const &R, int a0, int n, double cx, double cz, double z0,
+                                               TrackGeo const &g, double *__restrict__ y) {
+#pragma clang fp contract(off)
+  int const nrow = 2 + R.ng + R.nw;
+  for (int r = 0; r < nrow; r++) y[r] = 0;
+  double const wsum = cloud_scan(T, a0, n, cx, cz, z0, g, [&](int ip, double w) {
+    for (int r = 0; r < nrow; r++) y[r] += w * R.row(r)[ip];
+  });
+  if (wsum >= 1e-6) for (int r = 0; r < nrow; r++) y[r] /= wsum;
+  else for (int r = 0; r < nrow; r++) y[r] = __builtin_nan("");
+}
+
+// The two evaluations of the tracer, out of line as track_geo and clip_exit are: a probe (p, T) and a LOS point (every
+// row) at the position (px0, px1, px2), altitude z0.  Five scans a step, each over the whole cloud of the block.
+template <class Tab>
+__device__ __attribute__((noinline)) CloudPT cloud_probe(Tab T, double const *__restrict__ ap, double const *__restrict__ at, int a0,
+                                                         int n, double cx, double cz, double px0, double px1, double px2,
+                                                         double z0) {
+  return cloud_mean_pt(T, CloudRows{ap, at, nullptr, nullptr, 0, 0, 0}, a0, n, cx, cz, z0, track_geo(px0, px1, px2));
+}
+template <class Tab>
+__device__ __attribute__((noinline)) void cloud_point(Tab T, double const *__restrict__ ap, double const *__restrict__ at,
+                                                      double const *__restrict__ aq, double const *__restrict__ ak, int atm_np,
+                                                      int ng, int nw, int a0, int n, double cx, double cz, double px0, double px1,
+                                                      double px2, double z0, double *__restrict__ y) {
+  cloud_mean_all(T, CloudRows{ap, at, aq, ak, atm_np, ng, nw}, a0, n, cx, cz, z0, track_geo(px0, px1, px2), y);
+}
+
+// redo_columns under the 3-D rule: the point before the exit at position (px0, px1, px2), altitude z
+template <class Tab>
+__device__ __attribute__((noinline)) void redo_columns_cloud(Tab T, double const *__restrict__ ap, double const *__restrict__ at,
+                                                             double const *__restrict__ aq, double const *__restrict__ ak,
+                                                             int atm_np, int ng, int nw, int a0, int n, double cx, double cz,
+                                                             double px0, double px1, double px2, double z, double p, double t,
+                                                             double dsn, double *__restrict__ los_u, size_t fs) {
+  double y[2 + JUR_NG + JUR_NW];
+  cloud_mean_all(T, CloudRows{ap, at, aq, ak, atm_np, ng, nw}, a0, n, cx, cz, z, track_geo(px0, px1, px2), y);
+  for (int ig = 0; ig < ng; ig++) los_u[(size_t)ig * fs] = 10. * y[2 + ig] * p / (JUR_BOLTZMANN * t) * dsn;
+}
+
 struct ClipOut { double x0, x1, x2, frac; };
 __device__ __attribute__((noinline)) ClipOut clip_exit(double px0, double px1, double px2, double pz, double x0, double x1,
                                                        double x2, double z, double zfrac) {
@@ -569,6 +697,16 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
   int const ab = A.origin(atm0);       // the slice's first level in A's rows
   // altitude range of the first column of that slice (jr_common.h:411-420)
   double zmin = v.atm_z[atm0], zmax = zmin;
+  if constexpr (Atm::cloud) {
+    // 3-D rule: the range of ALL points of the block, in ascending index (no two points of a cloud share a column)
+    static_assert(LANES == 1, "the 3-D rule is traced one lane per ray");
+    if constexpr (decltype(A.T)::staged) { zmin = A.T.zmin; zmax = A.T.zmax; }
+    else
+      for (int ipp = atm0; ipp < atm0 + atmn; ++ipp) {
+        zmax = fmax(zmax, v.atm_z[ipp]);
+        zmin = fmin(zmin, v.atm_z[ipp]);
+      }
+  } else
   {
     double const lon0 = v.atm_lon[atm0], lat0 = v.atm_lat[atm0];
     for (int ipp = atm0; (ipp < atm0 + atmn) && (v.atm_lon[ipp] == lon0) && (v.atm_lat[ipp] == lat0); ++ipp) {
@@ -589,6 +727,12 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
     whole = (A.T.first(px0) == atm0) && (A.T.first(px0 + nx - 1) + A.T.len(px0 + nx - 1) == atm0 + atmn);
   }
   TrackPt tk{-1, -1, 0, 0, 0.}, tkr{-1, -1, 0, 0, 0.};   // the LOS points' and the probes' places in the track (2-D rule)
+  // 3-D rule: the cloud of the ray is its block; a staged block is walked by the workgroup's own (scalar) bounds
+  int c0 = 0, cn = 0;
+  if constexpr (Atm::cloud) {
+    if constexpr (decltype(A.T)::staged) { c0 = A.T.a0; cn = A.T.n; }
+    else { c0 = atm0; cn = atmn; }
+  }
   bool const outside = (obsz < zmin) || (vpz > zmax - 0.001) || (zmin == zmax) || (Atm::track && !whole);
   // (fused kernel: which lanes' rays never enter the atmosphere is said by ONE lane, in its own program order
   // before it starts stepping -- a branch of the lanes concerned could be scheduled behind the others' loop)
@@ -663,7 +807,11 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
           if (low_idx + 1 == np - 1) TR_LDS2 = dsp;
           double const dsn = (np >= 2) ? 0.5 * (ds_pp + dsp) : dsp * 0.5;
           L.put(JUR_F_DS, np - 1, dsn);
-          if constexpr (Atm::track)
+          if constexpr (Atm::cloud)
+            redo_columns_cloud(A.T, v.atm_p, v.atm_t, v.atm_q, v.atm_k, v.atm_np, v.ng, v.nw, c0, cn, A.cx, A.cz, TR_PX(0), TR_PX(1),
+                               TR_PX(2), TR_PZ, L.at(JUR_F_P, np - 1), L.at(JUR_F_T, np - 1), dsn, &L.at(f_u, np - 1),
+                               L.field_stride());
+          else if constexpr (Atm::track)
             redo_columns_track(A.T, v.atm_z, v.atm_q, v.atm_np, px0, nx, v.ng, TR_PX(0), TR_PX(1), TR_PX(2), TR_PZ,
                                L.at(JUR_F_P, np - 1), L.at(JUR_F_T, np - 1), dsn, &L.at(f_u, np - 1), L.field_stride());
           else
@@ -676,13 +824,27 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
 
       double p, t, rdz = 0;
       int ia = 0;
-      if constexpr (Atm::track) {   // the point's own longitude and latitude choose its two profiles
+      double cy[Atm::cloud ? 2 + JUR_NG + JUR_NW : 1];   // 3-D rule: the means p, T, q[ng], k[nw] at this point
+      if constexpr (Atm::cloud) {   // the point's own position weighs the parcels of its block
+        cloud_point(A.T, v.atm_p, v.atm_t, v.atm_q, v.atm_k, v.atm_np, v.ng, v.nw, c0, cn, A.cx, A.cz, x[0], x[1], x[2], z, cy);
+        p = cy[0];
+        t = cy[1];
+      } else if constexpr (Atm::track) {   // the point's own longitude and latitude choose its two profiles
         tk = track_locate(A.T, v.atm_z, px0, nx, z, track_geo(x[0], x[1], x[2]), tk);
         track_pt(A, tk, z, p, t);
       } else ia = intpol_pt<true>(A, ab, atmn, z, p, t, zdir, zhint, &rdz);
       double const dsn = (np >= 1) ? 0.5 * (ds_p + ds) : ds * 0.5;   // redone for the point before the exit
       L.put(JUR_F_DS, np, dsn);
-      if constexpr (Atm::track) {
+      if constexpr (Atm::cloud) {
+        double const kt = JUR_BOLTZMANN * t;
+        for (int ig = 0; ig < v.ng; ig++) {
+          double const qv = cy[2 + ig];
+          L.put(f_u + ig, np, 10. * qv * p / kt * dsn);
+          if (ig == v.ig_h2o) L.put(JUR_F_QH2O, np, qv);
+        }
+        // (no elision: the host never sets atm_k_zero under ip == 3 -- a hole is NaN in the extinction as well)
+        for (int iw = 0; iw < v.nw; iw++) L.put(f_k + iw, np, cy[2 + v.ng + iw]);
+      } else if constexpr (Atm::track) {
         double const kt = JUR_BOLTZMANN * t;
         for (int ig = 0; ig < v.ng; ig++) {
           double const qv = track_row(v.atm_z, A.q(ig), tk, z);
@@ -742,7 +904,21 @@ __device__ __forceinline__ TraceResult trace_ray(jur_view_t const &v, Atm const 
         n += refractivity(p, t);
         double xh[3], zz, llon, llat, pp, tt;
         for (int i = 0; i < 3; i++) xh[i] = x[i] + 0.5 * ds * ex0[i];
-        if constexpr (Atm::track) {
+        if constexpr (Atm::cloud) {
+          // every probe takes the 3-D rule at its own position (jr_common.h:669-679 with intpol_atm_geo)
+          zz = norm3(xh) - JUR_RE;
+          CloudPT pr = cloud_probe(A.T, v.atm_p, v.atm_t, c0, cn, A.cx, A.cz, xh[0], xh[1], xh[2], zz);
+          double const n2 = refractivity(pr.p, pr.t);
+          for (int i = 0; i < 3; i++) {
+            double const h = 0.02;
+            xh[i] += h;
+            zz = norm3(xh) - JUR_RE;
+            pr = cloud_probe(A.T, v.atm_p, v.atm_t, c0, cn, A.cx, A.cz, xh[0], xh[1], xh[2], zz);
+            ngr[i] = div_rcp(refractivity(pr.p, pr.t) - n2, h, 1. / h);
+            xh[i] -= h;
+          }
+          (void)llon; (void)llat; (void)pp; (void)tt;
+        } else if constexpr (Atm::track) {
           // every probe takes the 2-D rule at its own longitude and latitude (jr_common.h:669-679 with intpol_atm_geo)
           zz = norm3(xh) - JUR_RE;
           tkr = track_locate(A.T, v.atm_z, px0, nx, zz, track_geo(xh[0], xh[1], xh[2]), tkr);
@@ -1067,6 +1243,109 @@ __global__ __launch_bounds__(256, JUR_TRACK_MIN_WAVES) void jur_track_trace_kern
   c.tp[0][ray] = t.tpz;
   c.tp[1][ray] = t.tplon;
   c.tp[2][ray] = t.tplat;
+}
+
+// One lane per ray under the 3-D rule (ctl->ip == 3): every LOS point and every probe is the distance-weighted mean
+// over the cloud of air parcels its time block holds (AtmCloud).  Workgroups of four LOS tiles.  When all live rays of
+// the workgroup use ONE block and it has no more than JUR_CLOUD_LDS_POINTS points, the block's gate columns -- z, lat,
+// x1[0..2], five doubles a point -- are copied to LDS once, the altitude range of the block is reduced on the way, and
+// the scans -- the whole block at every one of a step's five evaluations -- read the gates there through LDS-typed
+// pointers (CloudLds): all lanes read the same point at the same time, one broadcast read.  The values p, T, q, k of
+// the points that pass the gates come from the model's rows.  Else every lane reads the model's arrays and finds the
+// range by its own pass (CloudGlobal).  Same values from another place, same operations in the same order: same
+// doubles (a minimum and a maximum are selections: the tree and the pass select the same value).  Full scan, no warm
+// start, no pruning.  No atomics on results, no waiting on other rays: the agreement is the slice kernel's.
+// (The name does not begin with jur_trace_ for the reason jur_track_trace_kernel's does not.)
+// LDS: 4 x 7680 B of tangent-point columns + 40 B per point + the agreement = 71 696 B: two workgroups per CU.
+#ifndef JUR_CLOUD_LDS_POINTS
+#define JUR_CLOUD_LDS_POINTS 1024
+#endif
+// a workgroup's block in LDS and its altitude range; `red`: 512 doubles of LDS nobody else uses until the next barrier.
+// Called by every thread of the workgroup with the same (scalar) a0 and n, 1 <= n <= JUR_CLOUD_LDS_POINTS and
+// a0 + n <= atm_np: every index below stays inside tab[5 n], the rows and x1[3 atm_np].
+__device__ __forceinline__ void cloud_stage(jur_view_t const &v, double const *__restrict__ x1, int a0, int n, double *tab,
+                                            double *red, double &zmin, double &zmax) {
+  double lo = v.atm_z[a0], hi = lo;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    double const z = v.atm_z[a0 + i];
+    tab[i] = z;
+    tab[n + i] = v.atm_lat[a0 + i];
+    for (int j = 0; j < 3; j++) tab[(2 + j) * n + i] = x1[3 * (size_t)(a0 + i) + j];
+    hi = fmax(hi, z);
+    lo = fmin(lo, z);
+  }
+  red[threadIdx.x] = lo;
+  red[256 + threadIdx.x] = hi;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red[threadIdx.x] = fmin(red[threadIdx.x], red[threadIdx.x + s]);
+      red[256 + threadIdx.x] = fmax(red[256 + threadIdx.x], red[256 + threadIdx.x + s]);
+    }
+    __syncthreads();
+  }
+  zmin = red[0];
+  zmax = red[256];
+  __syncthreads();                          // the partials have been read: their LDS may be written again
+}
+
+__global__ __launch_bounds__(256, 2) void jur_cloud_trace_kernel(jur_view_t v, jur_chunk_t c, jur_cloud_t k) {
+  __shared__ double tr_all[4][15][64];
+  __shared__ double tab[5 * JUR_CLOUD_LDS_POINTS];
+  __shared__ int agree[4];                 // min a0, max a0, min n, max n over the workgroup's rays
+  double (&tr_sh)[15][64] = tr_all[threadIdx.x >> 6];
+  int const r = ordered_block<1>(c.blk_order, (int)blockIdx.x) * blockDim.x + threadIdx.x;   // slot in the chunk
+  bool const live = r < c.n;
+  if (threadIdx.x == 0) { agree[0] = 0x7fffffff; agree[1] = -1; agree[2] = 0x7fffffff; agree[3] = -1; }
+  __syncthreads();
+  if (live) {
+    int a, m;
+    find_slice(v, c.geom[0][c.order ? (long)c.order[r] : c.first + r], a, m);   // what trace_ray finds for this ray
+    atomicMin(&agree[0], a); atomicMax(&agree[1], a);
+    atomicMin(&agree[2], m); atomicMax(&agree[3], m);
+  }
+  __syncthreads();
+  int const a0 = __builtin_amdgcn_readfirstlane(agree[0]), n = __builtin_amdgcn_readfirstlane(agree[2]);
+  // (no live ray: a0 = 0x7fffffff, agree[1] = -1; a0 + n <= atm_np: find_slice)
+  bool const staged = __builtin_amdgcn_readfirstlane((a0 == agree[1]) && (n == agree[3]) && (n >= 1) && (n <= JUR_CLOUD_LDS_POINTS));
+  double zmin = 0, zmax = 0;
+  if (staged) cloud_stage(v, k.x1, a0, n, tab, &tr_all[0][0][0], zmin, zmax);   // (uniform branch: every thread is here)
+  if (!live) return;
+  long const ray = c.order ? (long)c.order[r] : c.first + r;
+  LosWorkspace L{c.los + (size_t)(r >> 6) * los_tile_doubles(JUR_F_K + v.nw + v.ng) + (r & 63), JUR_F_K + v.nw + v.ng};
+  TraceResult t;
+  if (staged)
+    t = trace_ray(v, AtmCloud<CloudLds>{v, CloudLds{(lds_cptr)tab, a0, n, zmin, zmax}, k.cx, k.cz}, c.geom[0][ray], c.geom[1][ray],
+                  c.geom[2][ray], c.geom[3][ray], c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
+  else
+    t = trace_ray(v, AtmCloud<CloudGlobal>{v, CloudGlobal{v.atm_z, v.atm_lat, k.x1}, k.cx, k.cz}, c.geom[0][ray], c.geom[1][ray],
+                  c.geom[2][ray], c.geom[3][ray], c.geom[4][ray], c.geom[5][ray], c.geom[6][ray], L, tr_sh, c.status);
+  c.np[r] = t.np;
+  c.tsurf[r] = t.tsurf;
+  if (c.np_out) c.np_out[ray] = t.np;
+  c.tp[0][ray] = t.tpz;
+  c.tp[1][ray] = t.tplon;
+  c.tp[2][ray] = t.tplat;
+}
+
+// Known-answer hook: rule 4 (cloud_mean_all, what the tracer's LOS points take) at n positions given after the
+// geometry step, one per lane, on the points [a0, a0 + len) -- staged as the tracer stages them where they fit.
+__global__ __launch_bounds__(256) void jur_kat_cloud_mean_kernel(jur_view_t v, jur_cloud_t k, long n, int a0, int len,
+                                                                 double const *__restrict__ z0, double const *__restrict__ lat0,
+                                                                 double const *__restrict__ x0, double *__restrict__ out) {
+  __shared__ double tab[5 * JUR_CLOUD_LDS_POINTS];
+  __shared__ double red[512];
+  bool const staged = len <= JUR_CLOUD_LDS_POINTS;
+  double zmin = 0, zmax = 0;
+  if (staged) cloud_stage(v, k.x1, a0, len, tab, red, zmin, zmax);
+  long const i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  TrackGeo const g{lat0[i], x0[3 * i], x0[3 * i + 1], x0[3 * i + 2]};
+  CloudRows const R{v.atm_p, v.atm_t, v.atm_q, v.atm_k, v.atm_np, v.ng, v.nw};
+  double y[2 + JUR_NG + JUR_NW];
+  if (staged) cloud_mean_all(CloudLds{(lds_cptr)tab, a0, len, zmin, zmax}, R, a0, len, k.cx, k.cz, z0[i], g, y);
+  else cloud_mean_all(CloudGlobal{v.atm_z, v.atm_lat, k.x1}, R, a0, len, k.cx, k.cz, z0[i], g, y);
+  for (int r = 0; r < 2 + v.ng + v.nw; r++) out[(size_t)r * n + i] = y[r];
 }
 
 #undef TR_PZ
@@ -4529,8 +4808,24 @@ extern "C" void jurk_tune_trace_slice(int mode) { g_trace_slice = (mode == 1 || 
 #define JUR_TRACE_SLAB_DOUBLES 1280
 #endif
 
-extern "C" int jurk_launch_trace(jur_view_t const *v, jur_track_t const *trk, jur_chunk_t const *c, void *stream) {
+extern "C" int jurk_cloud_lds_points(void) { return JUR_CLOUD_LDS_POINTS; }
+
+extern "C" int jurk_kat_cloud_mean(jur_view_t const *v, jur_cloud_t const *cld, long n, int a0, int len, double const *z0,
+                                   double const *lat0, double const *x0, double *out, void *stream) {
+  // (the kernel indexes the rows and the table by a0 .. a0 + len - 1)
+  if (n < 1 || a0 < 0 || len < 1 || (long)a0 + len > v->atm_np || !cld || cld->np != v->atm_np || !cld->x1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(jur_kat_cloud_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *v, *cld, n, a0,
+                     len, z0, lat0, x0, out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jurk_launch_trace(jur_view_t const *v, jur_track_t const *trk, jur_cloud_t const *cld, jur_chunk_t const *c, void *stream) {
   if (c->n <= 0) return 0;
+  if (trk && trk->ip == 3) {             // the 3-D rule has one instance too; its table holds a position per atmosphere point
+    if (!cld || !cld->x1 || cld->np != v->atm_np || cld->np < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(jur_cloud_trace_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *v, *c, *cld);
+    return (int)hipGetLastError();
+  }
   if (trk && trk->ip == 2) {             // the 2-D rule has one instance: a lane per ray, workgroups of 256 slots
     if (trk->nprof < 1) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(jur_track_trace_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *v, *c, *trk);

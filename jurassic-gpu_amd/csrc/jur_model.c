@@ -38,6 +38,9 @@ struct jur_model {
   jur_track_t track;            /* ctl->ip and, under ip == 2, the profile table of the atmosphere on the device */
   void *d_track;                /* its grow-only slab: x1 | lat as doubles, then first | len | dir | prof_of as ints */
   size_t track_bytes;
+  jur_cloud_t cloud;            /* under ip == 3: cx, cz and the cached position of every point of the atmosphere on the device */
+  void *d_cloud;                /* its grow-only slab: x1 [np][3] */
+  size_t cloud_bytes;
   int atm_cap;
   int atm_slices;               /* distinct time stamps in the atmosphere        */
   int atm_k_zero;               /* jur_atm_k_zero of the rows on the device (view.atm_k_zero: this, where the switch is on) */
@@ -157,8 +160,11 @@ static int check_ctl(ctl_t const *ctl) {
   if (ctl->ng < 0 || ctl->ng > JUR_NG) { jur_set_error("ctl->ng=%d outside 0..%d", ctl->ng, JUR_NG); return JUR_EINVAL; }
   if (ctl->nd < 1 || ctl->nd > JUR_ND) { jur_set_error("ctl->nd=%d outside 1..%d", ctl->nd, JUR_ND); return JUR_EINVAL; }
   if (ctl->nw < 0 || ctl->nw > JUR_NW) { jur_set_error("ctl->nw=%d outside 0..%d", ctl->nw, JUR_NW); return JUR_EINVAL; }
-  if (ctl->ip == 3) { jur_set_error("IP 3 (3-D interpolation of a point cloud) is not supported along the line of sight: ctl->ip is 1 (profile) or 2 (satellite track)"); return JUR_EINVAL; }
-  if (ctl->ip != 1 && ctl->ip != 2) { jur_set_error("Unknown interpolation method, check IP! (ctl->ip == %d; 1 or 2)", ctl->ip); return JUR_EINVAL; }
+  if (ctl->ip != 1 && ctl->ip != 2 && ctl->ip != 3) { jur_set_error("Unknown interpolation method, check IP! (ctl->ip == %d; 1, 2 or 3)", ctl->ip); return JUR_EINVAL; }
+  if (ctl->ip == 3 && !(ctl->cx > 0 && isfinite(ctl->cx) && ctl->cz > 0 && isfinite(ctl->cz))) {
+    jur_set_error("IP 3 (point cloud) needs finite influence lengths CX > 0 and CZ > 0 [km]: ctl->cx = %g, ctl->cz = %g", ctl->cx, ctl->cz);
+    return JUR_EINVAL;
+  }
   for (int id = 0; id < ctl->nd; id++)
     if (ctl->window[id] < 0 || ctl->window[id] >= (ctl->nw > 0 ? ctl->nw : 1)) { jur_set_error("ctl->window[%d] out of range", id); return JUR_EINVAL; }
   return JUR_OK;
@@ -198,6 +204,7 @@ int jur_model_create(jur_model_t **out, ctl_t const *ctl, jur_tables_t const *tb
   if (!m->ctl) { free(m); return JUR_ENOMEM; }
   memcpy(m->ctl, ctl, sizeof(ctl_t));
   m->track.ip = ctl->ip;
+  m->cloud.cx = ctl->cx; m->cloud.cz = ctl->cz;
   jur_view_t *v = &m->view;
   v->ng = ctl->ng; v->nd = ctl->nd; v->nw = ctl->nw > 0 ? ctl->nw : 1;
   v->refrac = ctl->refrac; v->write_bbt = ctl->write_bbt;
@@ -335,7 +342,7 @@ void jur_model_destroy(jur_model_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->shared_tables) m->d_chan = m->d_sr = m->d_pair = m->d_pair_e0 = m->d_lvl = m->d_crv = m->d_ue = m->d_rec = NULL;
-  void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_track, m->d_order, m->d_sort_tmp, m->d_blk_order,
+  void *ptrs[] = {m->d_chan, m->d_sr, m->d_pair, m->d_pair_e0, m->d_lvl, m->d_crv, m->d_ue, m->d_rec, m->d_atm, m->d_track, m->d_cloud, m->d_order, m->d_sort_tmp, m->d_blk_order,
                   m->d_los, m->d_eps, m->d_np, m->d_tsurf, m->d_status, m->d_io, m->d_io_np, m->d_fov, m->d_fov_shape, m->d_kq, m->d_ctb, m->d_scene, m->d_side, m->d_pp};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; i++)
     if (ptrs[i]) (void)hipFree(ptrs[i]);
@@ -501,6 +508,33 @@ static int upload_track(jur_model_t *m, double const *h, long n) {
   return JUR_OK;
 }
 
+/* Positions of the packed rows' points under ip == 3 (jur_cloud_rows: rule 3 in jurassic_hip.h), rebuilt with every
+ * atmosphere; the slab only grows.  Nobody reads the old table any more: the caller has waited for the model's last call. */
+static int upload_cloud(jur_model_t *m, double const *h, long n) {
+  jur_cloud_t *t = &m->cloud;
+  t->np = 0;
+  size_t const bytes = sizeof(double) * 3 * (size_t)n;
+  double *buf = (double *)malloc(bytes);
+  if (!buf) return JUR_ENOMEM;
+  long const nx = jur_cloud_rows(n, h + 2 * (size_t)n, h + 3 * (size_t)n, (double (*)[3])buf);
+  if (nx < 0) { free(buf); return (int)nx; }
+  if (bytes > m->cloud_bytes) {
+    if (m->d_cloud) (void)hipFree(m->d_cloud);
+    m->d_cloud = NULL;
+    m->cloud_bytes = 0;
+    if (hipMalloc(&m->d_cloud, bytes) != hipSuccess) { free(buf); jur_set_error("cannot allocate the position table of the cloud"); return JUR_EHIP; }
+    m->cloud_bytes = bytes;
+  }
+  hipError_t e = hipMemcpyAsync(m->d_cloud, buf, bytes, hipMemcpyHostToDevice, m->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+  free(buf);
+  if (e != hipSuccess) { jur_set_error("cannot upload the position table of the cloud: %s", hipGetErrorString(e)); return JUR_EHIP; }
+  t->x1 = (double const *)m->d_cloud;
+  t->cx = m->ctl->cx; t->cz = m->ctl->cz;
+  t->np = (int)nx;
+  return JUR_OK;
+}
+
 /* upload packed rows [6+ng+nw][n] and derive what the kernels want to know about them; origin: JUR_ATM_* */
 static int upload_atm_rows(jur_model_t *m, double const *h, long n, int origin) {
   HIPCHK(hipSetDevice(m->device));
@@ -527,10 +561,15 @@ static int upload_atm_rows(jur_model_t *m, double const *h, long n, int origin) 
     int const rt = upload_track(m, h, n);
     if (rt) return rt;
   }
+  if (m->track.ip == 3) {
+    int const rt = upload_cloud(m, h, n);
+    if (rt) return rt;
+  }
   HIPCHK(hipMemcpyAsync(m->d_atm, h, sizeof(double) * nrow * (size_t)n, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   derive_atm_facts(m, h, h + (size_t)n, n);
   m->atm_k_zero = jur_atm_k_zero(h + (6 + (size_t)ng) * (size_t)n, (long)nw * n, v->atm_sorted, origin);
+  if (m->track.ip == 3) m->atm_k_zero = 0;   /* a mean over no parcel is NaN, in the extinction as well: never elided */
   view_set_k_zero(m);
   double const *d = (double const *)m->d_atm;
   v->atm_np = (int)n;           /* (jurk_prepare_atm reads it) */
@@ -863,7 +902,7 @@ int jur_model_reserve(jur_model_t *m, long nr) {
  * (too many rays, or more (channel, gas) chains per ray than the LDS rings hold). */
 static int pencil_rays_per_group(jur_model_t const *m, long nr) {
   if (m->ctl->formod == 1) return 0;                        /* the fused kernel is emissivity growth only */
-  if (m->ctl->ip == 2) return 0;                            /* ... and traces one profile per ray */
+  if (m->ctl->ip == 2 || m->ctl->ip == 3) return 0;         /* ... and traces one profile per ray */
   if (m->pencil_rays <= 0 || nr > m->pencil_rays) return 0;
   long const npair = (long)m->view.nd * (m->view.ng > 0 ? m->view.ng : 1);
   int rb = m->pencil_rb;
@@ -1023,7 +1062,7 @@ static int formod_device_body(jur_model_t *m, long nr, double const *d_geom, lon
     c.tsurf = m->d_tsurf;
     c.los = m->d_los;
     c.blk_order = blk_order;                          /* (set only where the call is this one launch) */
-    TIMED(0, jurk_launch_trace(&m->view, &m->track, &c, s), "trace");
+    TIMED(0, jurk_launch_trace(&m->view, &m->track, &m->cloud, &c, s), "trace");
     c.blk_order = NULL;
     if (m->host_call) {
       /* host entry: the input radiances, which only the epilogue reads (NaN mask), are uploaded beside the first
@@ -1496,7 +1535,7 @@ int jur_curtis_godson_host(jur_model_t *m, long nr, double const *const geom[7],
       c.los = m->d_los;
       c.eps = m->d_eps;
       c.status = m->d_status;
-      int ek = jurk_launch_trace(&m->view, &m->track, &c, s);
+      int ek = jurk_launch_trace(&m->view, &m->track, &m->cloud, &c, s);
       if (!ek) ek = jurk_launch_cg(&m->view, &c, d_cgp, d_cgt, d_cgu, s);
       if (ek) { jur_set_error("curtis_godson: kernel launch failed: %s", hipGetErrorString((hipError_t)ek)); rc = JUR_EHIP; goto done; }
     }
@@ -1936,6 +1975,34 @@ int jur_kat_update(jur_model_t *m, int id, long n, int what, double const *a, do
   return kat_finish(m, ek, n, 3, 3, io, d);
 }
 
+/* Rule 4 of IP 3 on the device at n positions given after the geometry step (z0, lat0, x0 = geo2cart(0, lon0, lat0)), on
+ * the points [a0, a0 + len) of the model's atmosphere: out [2 + ng + nw][n] -- p, T, q, k. */
+int jur_kat_cloud_mean(jur_model_t *m, long n, int a0, int len, double const *z0, double const *lat0, double const (*x0)[3], double *out) {
+  if (!m || n < 1 || !z0 || !lat0 || !x0 || !out) { jur_set_error("kat_cloud_mean: bad arguments"); return JUR_EINVAL; }
+  if (m->ctl->ip != 3) { jur_set_error("kat_cloud_mean: the model was not created with ip = 3"); return JUR_EINVAL; }
+  if (m->view.atm_np < 2 || m->cloud.np != m->view.atm_np) { jur_set_error("kat_cloud_mean: no atmosphere set"); return JUR_EINVAL; }
+  if (a0 < 0 || len < 1 || (long)a0 + len > m->view.atm_np) { jur_set_error("kat_cloud_mean: points [%d, %d + %d) outside the atmosphere's %d", a0, a0, len, m->view.atm_np); return JUR_EINVAL; }
+  int const nrow = 2 + m->view.ng + m->view.nw;
+  HIPCHK(hipSetDevice(m->device));
+  int rc = wait_done(m, m->stream);
+  if (rc) return rc;
+  double *d = NULL;
+  size_t const N = (size_t)n;
+  HIPCHK(hipMalloc((void **)&d, sizeof(double) * N * (size_t)(5 + nrow)));
+  hipError_t e = hipMemcpy(d, z0, sizeof(double) * N, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + N, lat0, sizeof(double) * N, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + 2 * N, x0, sizeof(double) * 3 * N, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(d); jur_set_error("kat_cloud_mean: upload failed"); return JUR_EHIP; }
+  int const ek = jurk_kat_cloud_mean(&m->view, &m->cloud, n, a0, len, d, d + N, d + 2 * N, d + 5 * N, m->stream);
+  if (ek) { jur_set_error("known-answer kernel not launched: %s", hipGetErrorString((hipError_t)ek)); rc = JUR_EHIP; }
+  if (!rc && hipStreamSynchronize(m->stream) != hipSuccess) { jur_set_error("known-answer kernel failed"); rc = JUR_EHIP; }
+  if (!rc && hipMemcpy(out, d + 5 * N, sizeof(double) * N * (size_t)nrow, hipMemcpyDeviceToHost) != hipSuccess) rc = JUR_EHIP;
+  (void)hipFree(d);
+  return rc;
+}
+
+int jur_cloud_lds_points(void) { return jurk_cloud_lds_points(); }
+
 /* The ray tracer's LOS records point by point: the chunk loop of jur_curtis_godson_host (the same launches of
  * jurk_launch_trace, so jur_tune_trace selects the kernel as in production), each chunk gathered from the workspace
  * before the next one overwrites it.  An overflowing ray comes back clamped, with JUR_ENLOS. */
@@ -1979,7 +2046,7 @@ int jur_kat_traceray(jur_model_t *m, long nr, double const *const geom[7], doubl
       c.los = m->d_los;
       c.eps = m->d_eps;
       c.status = m->d_status;
-      int ek = jurk_launch_trace(&m->view, &m->track, &c, s);
+      int ek = jurk_launch_trace(&m->view, &m->track, &m->cloud, &c, s);
       if (!ek) ek = jurk_kat_los(&m->view, &c, d_los, d_tsurf, s);
       if (ek) { jur_set_error("kat_traceray: kernel launch failed: %s", hipGetErrorString((hipError_t)ek)); rc = JUR_EHIP; goto done; }
     }
@@ -2741,6 +2808,11 @@ static int param_pass_extend(jur_model_t *m, hipStream_t s, char const *who, sce
 /* The scene entries are built on per-ray blocks of ONE slice's state; under ip == 2 a ray reads two profiles of a track.
  * Refused before anything else is looked at. */
 static int scene_ip_check(jur_model_t const *m, char const *who) {
+  if (m->ctl->ip == 3) {
+    jur_set_error("%s: ip = 3 (point cloud) averages every point of a ray over the air parcels around it, and the scene entries "
+                  "hold the state of one slice per ray: use jur_formod_host and jur_kernel", who);
+    return JUR_EINVAL;
+  }
   if (m->ctl->ip != 2) return JUR_OK;
   jur_set_error("%s: ip = 2 (satellite track) interpolates every point of a ray between two profiles, and the scene entries "
                 "hold the state of one slice per ray: use jur_formod_host and jur_kernel", who);
@@ -3677,7 +3749,7 @@ done:
  * later calls would accept; if it cannot go back, with none ("no atmosphere set") */
 static int scene_restore_atm(jur_model_t *m, atm_t const *atm, int rc) {
   if (atm->np < 2 || atm->np > JUR_NP) return rc;
-  if (m->ctl->ip == 2 && rc != JUR_OK) return rc;   /* scene_ip_check refused the call before the model's atmosphere was touched */
+  if ((m->ctl->ip == 2 || m->ctl->ip == 3) && rc != JUR_OK) return rc;   /* scene_ip_check refused the call before the model's atmosphere was touched */
   if (rc == JUR_OK) return jur_model_set_atm(m, atm);
   char msg[512];
   snprintf(msg, sizeof msg, "%s", jur_last_error());
@@ -4508,6 +4580,7 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
   c->d_atm = NULL; c->atm_cap = 0; c->atm_slices = 0; c->atm_k_zero = 0; c->view.atm_k_zero = 0;
   c->view.atm_np = 0;
   c->d_track = NULL; c->track_bytes = 0; c->track.nprof = 0;
+  c->d_cloud = NULL; c->cloud_bytes = 0; c->cloud.np = 0; c->cloud.x1 = NULL;
   c->d_los = NULL; c->d_eps = NULL; c->d_np = NULL; c->d_tsurf = NULL; c->d_status = NULL;
   c->los_bytes = 0; c->ws_rays = 0; c->ws_trace_rays = 0;
   c->d_order = NULL; c->d_sort_tmp = NULL; c->d_blk_order = NULL; c->order_cap = 0; c->sort_tmp_bytes = 0; c->n_blk_order = 0;
@@ -4530,8 +4603,12 @@ static jur_model_t *clone_lane(jur_model_t const *m) {
 static void refresh_switches(jur_model_t *m, ctl_t const *ctl) {
   jur_view_t *v = &m->view;
   if (ctl->ng != v->ng || ctl->nd != v->nd) DIE("ng/nd changed after the tables were initialised");
-  if (ctl->ip != 1 && ctl->ip != 2) DIE("IP %d is not supported along the line of sight (1: profile, 2: satellite track)", ctl->ip);
-  if (ctl->ip != m->track.ip) { m->track.ip = ctl->ip; m->track.nprof = 0; m->h_atm_n = 0; }   /* the next set_atm builds the profile table */
+  if (ctl->ip != 1 && ctl->ip != 2 && ctl->ip != 3) DIE("IP %d is not supported along the line of sight (1: profile, 2: satellite track, 3: point cloud)", ctl->ip);
+  if (ctl->ip == 3 && !(ctl->cx > 0 && isfinite(ctl->cx) && ctl->cz > 0 && isfinite(ctl->cz))) DIE("IP 3 needs finite CX > 0 and CZ > 0 (cx = %g, cz = %g)", ctl->cx, ctl->cz);
+  /* the next set_atm builds the profile table or the position table (the influence lengths travel with it) */
+  if (ctl->ip != m->track.ip || (ctl->ip == 3 && (ctl->cx != m->cloud.cx || ctl->cz != m->cloud.cz))) {
+    m->track.ip = ctl->ip; m->track.nprof = 0; m->cloud.np = 0; m->cloud.cx = ctl->cx; m->cloud.cz = ctl->cz; m->h_atm_n = 0;
+  }
   memcpy(m->ctl, ctl, sizeof(ctl_t));
   v->refrac = ctl->refrac; v->write_bbt = ctl->write_bbt; v->rayds = ctl->rayds; v->raydz = ctl->raydz;
   /* upstream looks the emitters up on the first call that has the switch on, whichever call that is

@@ -218,6 +218,12 @@ def lib():
         if hasattr(L, "jur_track_profiles"):         # (an older build selected with JURASSIC_HIP_SO for an A/B run has none)
             L.jur_track_profiles.restype = C.c_long
             L.jur_track_profiles.argtypes = [C.c_void_p, ip_, ip_, dp, ip_]
+        if hasattr(L, "jur_cloud_points"):           # (an older build selected with JURASSIC_HIP_SO for an A/B run has none)
+            L.jur_cloud_points.restype = C.c_long
+            L.jur_cloud_points.argtypes = [C.c_void_p, dp]
+            L.jur_cloud_lds_points.restype = C.c_int
+            L.jur_cloud_lds_points.argtypes = []
+            L.jur_kat_cloud_mean.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, dp, dp, dp, dp]
         L.jur_kat_continua.argtypes = [C.c_void_p, C.c_int, C.c_long] + [dp] * 6
         L.jur_kat_update.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int] + [dp] * 6
         L.jur_kat_traceray.argtypes = [C.c_void_p, C.c_long, C.POINTER(dp), dp, dp, C.POINTER(dp), C.POINTER(C.c_int)]
@@ -1135,6 +1141,17 @@ class Model:
                     u=np.ascontiguousarray(los[:, 4 + nw:].transpose(1, 0, 2)),
                     np=npts, tsurf=tsurf, tp=np.ascontiguousarray(tp.T), status=rc)
 
+    def kat_cloud_mean(self, a0, length, z0, lat0, x0):
+        """Rule 4 of IP 3 on the device (jur_kat_cloud_mean) over the atmosphere points [a0, a0 + length) at the
+        positions z0, lat0 (n,), x0 (n, 3) = geo2cart(0, lon0, lat0) -> (2 + ng + nw, n): p, T, q, k."""
+        z0, lat0, x0 = (np.ascontiguousarray(x, dtype=np.float64) for x in (z0, lat0, x0))
+        n = len(z0)
+        if lat0.shape != (n,) or x0.shape != (n, 3):
+            raise ValueError("kat_cloud_mean: z0, lat0 (n,) and x0 (n, 3)")
+        out = np.zeros((2 + self.ng + max(self.nw, 1), n))
+        _chk(lib().jur_kat_cloud_mean(self.h, n, int(a0), int(length), _p(z0), _p(lat0), _p(x0), _p(out)))
+        return out
+
     def enable_timing(self, on=True):
         _chk(lib().jur_model_enable_timing(self.h, int(on)))
 
@@ -1701,6 +1718,19 @@ def track_profiles(atm):
     ip_ = C.POINTER(C.c_int)
     n = _chk(lib().jur_track_profiles(C.byref(atm), first.ctypes.data_as(ip_), length.ctypes.data_as(ip_), _p(x1), block.ctypes.data_as(ip_)))
     return dict(first=first[:n], len=length[:n], block_of=block[:n], x1=x1[:n])
+
+
+def cloud_points(atm):
+    """jur_cloud_points: x1 = geo2cart(0, lon, lat) of every point of a cloud (IP 3; rule 3 in jurassic_hip.h), host
+    only -> (np, 3)"""
+    x1 = np.zeros((max(int(atm.np), 1), 3))
+    n = _chk(lib().jur_cloud_points(C.byref(atm), _p(x1)))
+    return x1[:n]
+
+
+def cloud_lds_points():
+    """jur_cloud_lds_points: the largest slice the IP 3 tracer stages in LDS"""
+    return int(lib().jur_cloud_lds_points())
 
 
 def intpol_atm(ctl, dest, src, device=0):
